@@ -19,7 +19,9 @@ figure (4096 per GPU) is measured in the same process and reported beside it (`w
 the timed region.  The batch dimension shards with no collective inside the loop; one RCCL all-gather of
 the iterates closes the timed region.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0; `ms_per_step` is the wall time of one timed step.  `--dump-outputs DIR` also writes the
+iterates the last timed step produced (DIR/iterates.npy, float32): inputs, weights and noise are seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -56,7 +58,8 @@ def find_traffic(B, H, D, attention, kind):
 def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=20)
+    p.add_argument("--steps", type=int, default=20,
+                   help="timed denoise steps; past --train-steps the sampling loop starts over from the same x_T")
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--batch", type=int, default=4096, help="trajectories per GPU of the weak-scaling workload (and of N = 1)")
     p.add_argument("--global-batch", type=int, default=None,
@@ -83,6 +86,9 @@ def parse(argv=None):
                    help="seconds the self-launcher waits for its ranks before it terminates them (N > 1 without torchrun)")
     p.add_argument("--stub-engine", action="store_true",
                    help="replace the HIP engine by a sleep (tests/test_bench_launcher.py only; the line says so)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the iterates the last timed step produced (the headline workload's "
+                        "gathered batch, float32) to DIR/iterates.npy; above 64 MB a fixed seeded sample of whole trajectories")
     return p.parse_args(argv)
 
 
@@ -245,6 +251,19 @@ def timed_run(eng, dist, world, dev, cond, x_T, inpaint, W, K, T, profile, sync,
     import torch
     from state_policy_diffusionmodel_amd.distributed import ShardedSampler
     ss = ShardedSampler(eng)
+    pos = [0]                                              # steps run so far in the current pass of the T-step schedule
+
+    def run(n):
+        # n more denoise steps; past the end of the schedule the loop starts over from x_T (same inputs, same noise), so
+        # --steps + --warmup may exceed T
+        while n > 0:
+            if pos[0] == T:
+                ss.begin(cond, x_T, noise=None, inpaint=inpaint, seed=7)
+                pos[0] = 0
+            m = min(n, T - pos[0])
+            ss.run(pos[0], pos[0] + m)
+            pos[0] += m
+            n -= m
 
     def barrier():
         sync()
@@ -253,7 +272,7 @@ def timed_run(eng, dist, world, dev, cond, x_T, inpaint, W, K, T, profile, sync,
             sync()
 
     ss.begin(cond, x_T, noise=None, inpaint=inpaint, seed=7)
-    ss.run(0, W)                                           # untimed warm-up steps
+    run(W)                                                 # untimed warm-up steps
     if world > 1:
         ss.result()                                        # untimed: the backend sets its channels up on the first call of a kind
     # The timed region is EXACTLY K denoise steps: the first K - P the way the product runs them (spdm_sample_run replays each
@@ -267,11 +286,10 @@ def timed_run(eng, dist, world, dev, cond, x_T, inpaint, W, K, T, profile, sync,
         eng.profile("prepare")                             # events created here, outside the timed region
     barrier()
     t0 = time.perf_counter()
-    if K - P > 0:
-        ss.run(W, W + K - P)
+    run(K - P)
     if profile:
         eng.profile(True)
-    ss.run(W + K - P, W + K)
+    run(P)
     out = ss.result()                                      # N > 1: one all-gather (RCCL over xGMI) closes the timed region
     barrier()
     el = time.perf_counter() - t0
@@ -285,7 +303,7 @@ def timed_run(eng, dist, world, dev, cond, x_T, inpaint, W, K, T, profile, sync,
     if profile and W + 2 * K <= T:
         barrier()
         t1 = time.perf_counter()
-        ss.run(W + K, W + 2 * K)
+        run(K)
         barrier()
         el_graph = time.perf_counter() - t1
     tmax = torch.tensor([el, el_graph if el_graph is not None else 0.0], device=dev, dtype=torch.float64)
@@ -332,8 +350,8 @@ def main():
     H, D = args.horizon, args.state_dim
     cond_dim = OBS_H * OBS_DIM
     K, W, T = args.steps, args.warmup, args.train_steps
-    if K + W > T:
-        raise SystemExit(f"steps + warmup ({K + W}) exceed the schedule length ({T})")
+    if K < 1 or W < 0:
+        raise SystemExit(f"--steps must be >= 1 and --warmup >= 0 (got {K}, {W})")
     attention = not args.no_attention
     Bw = args.batch                                        # weak scaling: per-GPU batch
     Bg = args.global_batch or args.batch                   # strong scaling: global batch
@@ -375,6 +393,8 @@ def main():
             raise SystemExit(f"bench: gathered iterates have shape {tuple(out.shape)}, expected {(world * B, 1, H, D)}")
         if not bool(torch.isfinite(out).all()):
             raise SystemExit("bench: non-finite iterate")
+        if args.dump_outputs and mode == headline and rank == 0:
+            dump_outputs(args.dump_outputs, {"iterates": out})
         del cond, x_T, inpaint, out
         runs[mode] = dict(B=B, el=el, launches=launches, conv_ms=conv_ms, conv_flops=conv_flops, el_graph=el_graph,
                           instr_steps=instr_steps)
@@ -419,6 +439,26 @@ def main():
     eng.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64_000_000                # --dump-outputs: at most 64 MB in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as float32 <path>/<name>.npy.  The arrays share DUMP_MAX_BYTES; one above its share keeps
+    a fixed seeded sample of its leading-dimension rows (whole trajectories), in order, so two runs compare row for row."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > budget:
+            row = a.nbytes // a.shape[0]
+            keep = np.sort(np.random.default_rng(0).choice(a.shape[0], size=max(budget // row, 1), replace=False))
+            print(f"[bench] {name}: {a.nbytes} bytes > {budget}: dumping {keep.size} of {a.shape[0]} rows (seeded sample)",
+                  file=sys.stderr)
+            a = a[keep]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def roofline(args, r, split, B, H, D, el, K):

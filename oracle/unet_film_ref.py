@@ -12,8 +12,8 @@ Pinning: ``tools/make_golden.py`` (run in the build container, where
 generated ``state_dict`` into it with ``strict=True``, runs it on seeded inputs
 and commits inputs + outputs under ``tests/golden/``;
 ``tests/test_oracle.py`` checks this restatement against those vectors, and
-``tests/test_oracle_vs_reference.py`` against the live import when the
-reference tree is present.
+``tests/test_oracle_vs_reference.py`` against the reference's recorded
+state_dict inventory and forward outputs (``ref_inventory.json``, ``refpin_*.npz``).
 
 The restatement is deliberately NOT a module tree: it is a flat function over
 a name -> tensor dict, written from the reference's behaviour, one helper per

@@ -6,8 +6,8 @@ The tensor NAMES and SHAPES are exactly those of the reference module's
 ``state_dict()`` (``models/Unet_FiLmLayer.py:240-264`` builds the module tree;
 162 tensors / 24 823 297 parameters at ``global_cond_dim=1350``), so a real
 checkpoint's ``noise_estimator.*`` entries can be fed to the same packer.
-``tests/test_oracle_vs_reference.py`` loads a generated dict into the imported
-reference module with ``strict=True`` to pin the inventory key-for-key.
+``tests/test_oracle_vs_reference.py`` pins the inventory key-for-key against the
+reference module's recorded ``state_dict()`` (``tests/golden/ref_inventory.json``).
 """
 from __future__ import annotations
 

@@ -52,3 +52,29 @@ def test_traffic_summary_is_found_by_geometry():
     assert c5["_file"] != head["_file"]
     assert bench.find_traffic(64, 32, 3, True, "ddpm") is None
     assert bench.find_traffic(4096, 32, 3, False, "ddpm") is None        # the no-attention model was not profiled
+
+
+def _bench_dump(out_dir, *extra):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "64", "--no-cpu-baseline",
+                        "--dump-outputs", str(out_dir), *extra], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    import numpy as np
+    return d, np.load(os.path.join(str(out_dir), "iterates.npy"))
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_reproducible(tmp_path):
+    """--dump-outputs: the same arguments give the same inputs and so, on this deterministic engine, the same bits; steps
+    past the schedule length restart the loop from x_T (3 warm-up + 7 timed steps of an 8-step schedule end 2 steps into
+    the second pass: what 2 timed steps of a fresh run compute)."""
+    import numpy as np
+    d1, a = _bench_dump(tmp_path / "a", "--steps", "3", "--warmup", "3")
+    d2, b = _bench_dump(tmp_path / "b", "--steps", "3", "--warmup", "3")
+    assert d1["steps"] == d2["steps"] == 3
+    assert a.dtype == np.float32 and a.shape == (64, 1, 32, 3) and np.isfinite(a).all()
+    np.testing.assert_array_equal(a, b)
+    dw, w = _bench_dump(tmp_path / "w", "--steps", "7", "--warmup", "3", "--train-steps", "8")
+    df, f = _bench_dump(tmp_path / "f", "--steps", "2", "--warmup", "0", "--train-steps", "8")
+    assert dw["steps"] == 7 and df["steps"] == 2
+    assert np.abs(w - f).max() <= 1e-5

@@ -71,3 +71,49 @@ def test_launcher_terminates_the_other_ranks_when_one_dies():
     assert "a rank failed" in r.stderr
     assert time.monotonic() - t0 < 60
     assert not [ln for ln in r.stdout.splitlines() if ln.lstrip().startswith("{")]     # never a line from a broken job
+
+
+def test_dump_outputs_writes_what_the_timed_path_returns(tmp_path):
+    """--dump-outputs DIR: the iterates of the last timed step as float32 DIR/iterates.npy.  The stub engine hands x_T back
+    unchanged, so the file must be the seeded synthetic x_T -- the same on every run."""
+    import numpy as np
+    import torch
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, BENCH, "--stub-engine", "--steps", "2", "--warmup", "1", "--batch", "8",
+                        "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300, cwd=ROOT, env=_env())
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(r.stdout.strip())["steps"] == 2
+    assert sorted(os.listdir(d)) == ["iterates.npy"]
+    a = np.load(d / "iterates.npy")
+    assert a.dtype == np.float32 and a.shape == (8, 1, 32, 3)
+    g = torch.Generator().manual_seed(1000)                    # bench.py inputs(): cond first, then x_T
+    torch.randn(8, 1, 10, 135, generator=g)
+    np.testing.assert_array_equal(a, torch.rand(8, 1, 32, 3, generator=g).numpy())
+
+
+def test_steps_may_exceed_the_schedule_length():
+    """--steps sets the number of timed steps even past --train-steps: the loop starts over from x_T."""
+    r = subprocess.run([sys.executable, BENCH, "--stub-engine", "--steps", "7", "--warmup", "3", "--train-steps", "4",
+                        "--batch", "8"], capture_output=True, text=True, timeout=300, cwd=ROOT, env=_env())
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip())
+    assert d["steps"] == 7 and d["warmup"] == 3
+    assert abs(d["value"] - 8 * 1000.0 / d["ms_per_step"]) <= 1e-6 * d["value"]
+
+
+def test_dump_sample_is_fixed_and_bounded(tmp_path, monkeypatch):
+    """Above the size cap the dump keeps a seeded sample of whole rows, in order, identical from run to run."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 40 * 96 * 4)
+    x = torch.arange(100 * 96, dtype=torch.float32).reshape(100, 1, 32, 3)
+    bench.dump_outputs(str(tmp_path / "a"), {"iterates": x})
+    bench.dump_outputs(str(tmp_path / "b"), {"iterates": x})
+    a, b = np.load(tmp_path / "a" / "iterates.npy"), np.load(tmp_path / "b" / "iterates.npy")
+    assert a.shape == (40, 1, 32, 3) and a.nbytes <= bench.DUMP_MAX_BYTES
+    np.testing.assert_array_equal(a, b)
+    rows = a[:, 0, 0, 0] / 96
+    assert np.all(np.diff(rows) > 0) and np.all(rows == np.round(rows))      # whole rows of x, in order
+    np.testing.assert_array_equal(a, x.numpy()[rows.astype(int)])

@@ -14,6 +14,7 @@ reference source or bytecode is copied.  Weights are not stored: the GPU box
 regenerates them from the seed (state_policy_diffusionmodel_amd/weights.py)
 and checks the hash.
 """
+import json
 import os
 import sys
 import types
@@ -147,10 +148,52 @@ def encoder_case(name, n, wseed=5, iseed=11):
     print("wrote", path, os.path.getsize(path) // 1024, "KiB")
 
 
+def inventory_case():
+    """The reference module's state_dict inventory (ordered names and shapes) at the metric's cond_dim, both model variants."""
+    UNet_Film, UNet_Film_noAttention = import_reference()
+    inv = {}
+    for key, cls in (("attention", UNet_Film), ("no_attention", UNet_Film_noAttention)):
+        m = cls(1, 1, 1000, time_dim=256, global_cond_dim=1350)
+        inv[key] = [[k, list(v.shape)] for k, v in m.state_dict().items()]
+    path = os.path.join(OUT, "ref_inventory.json")
+    with open(path, "w") as fh:          # one tensor per line
+        fh.write("{\n" + ",\n".join(f'"{key}": [\n' + ",\n".join(json.dumps(e) for e in entries) + "\n]"
+                                    for key, entries in inv.items()) + "\n}\n")
+    print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+
+
+def pin_case(H, D, B, attention, wseed=11, obs_h=3, obs_dim=11):
+    """tests/test_oracle_vs_reference.py: reference forward on randn inputs, one scalar and one per-sample t."""
+    cond_dim = obs_h * obs_dim
+    m, sd = build_reference_model(cond_dim, wseed, attention)
+    g = gen(H * 100 + D)
+    x = torch.randn(B, 1, H, D, generator=g)
+    y = torch.randn(B, 1, obs_h, obs_dim, generator=g)
+    out = {"x": x.numpy(), "cond": y.numpy(), "wseed": wseed, "attention": int(attention),
+           "weights_sha256": blob_sha256(sd)}
+    with torch.no_grad():
+        for i, t in enumerate((torch.tensor([42]), torch.arange(B) * 300)):
+            out[f"t{i}"] = t.numpy()
+            out[f"eps{i}"] = m(x, t, y).numpy()
+    path = os.path.join(OUT, f"refpin_h{H}d{D}_b{B}.npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+
+
+def pins():
+    inventory_case()
+    pin_case(24, 4, 3, True)
+    pin_case(8, 1, 2, True)
+    pin_case(48, 8, 1, False)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     if "--encoder-only" in sys.argv:
         encoder_case("n5", 5)
+        return
+    if "--pins-only" in sys.argv:
+        pins()
         return
     torch.set_num_threads(8)
     # U-Net forward, the shape set of SURVEY.md section 8(c)
@@ -167,6 +210,7 @@ def main():
     trajectory_case("ddim_T100_n10_h32d3_b1", "ddim", 100, 10, 32, 3, 1)
     trajectory_case("ddpm_T12_h32d3_b2_inp4", "ddpm", 12, 12, 32, 3, 2, inp_h=4)
     encoder_case("n5", 5)
+    pins()
 
 
 if __name__ == "__main__":
