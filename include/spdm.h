@@ -70,6 +70,22 @@ typedef struct {
 #define SPDM_FLAG_DEBUG_KEEP 1    /* keep every intermediate alive for spdm_debug_tensor */
 #define SPDM_FLAG_EXACT_FP32 2    /* contractions on the exact fp32 MFMA path instead of the default split-fp16
                                     path (hi + 2^-11 lo, 3 fp16 MFMAs, fp32 accumulate); env SPDM_PREC=f32 does the same */
+#define SPDM_FLAG_SIMPLE_UNET 4   /* the noise predictor is UNet of models/simple_Unet.py (Diffusion_DDPM's default
+                                    model='UNet', models/diffusion_ddpm.py:53-62) instead of UNet_Film[_noAttention]:
+                                     - attention must be 0 (spdm_create returns SPDM_ERR_INVALID otherwise);
+                                     - conditioning is required: cond_dim >= 1 at create, and spdm_unet_forward /
+                                       spdm_sample* with d_cond == NULL return SPDM_ERR_INVALID (the reference's
+                                       channel counts only match with y given);
+                                     - spdm_load_weights takes UNet.state_dict() names ("input_conv.first.weight",
+                                       "down1.cond_emb_layer.1.weight", ...) including the buffer
+                                       "pos_encoding.pos_encoding", which must be (num_train_timesteps, time_dim):
+                                       it IS the time table (spdm_set_time_table may still overwrite it), so timesteps
+                                       are valid below its row count (noise_steps + 1 in the reference);
+                                     - evaluation semantics (model.eval()): the positional encoding's dropout is off;
+                                     - spdm_debug_tensor names: x1 x2 x3 x4 u1 u2 u3 (block outputs, in the plan's
+                                       channel-padded storage: real channels first, zeros after);
+                                     - every other entry point (schedules, sampling, graphs, switches, profiler,
+                                       pinned geometry, precision flags) behaves as for UNet_Film. */
 
 /* One entry per tensor of the reference state_dict (names exactly as
  * UNet_Film.state_dict() gives them, e.g. "down1.cond_encoder.2.weight"),
@@ -126,7 +142,7 @@ int  spdm_schedule_tables(int32_t kind, int32_t num_train_timesteps, int32_t num
 /* Replaces: self.noise_estimator(x_t, torch.tensor([t]), obs_cond)
  * (models/diffusion_ddpm.py:272 -> UNet_Film.forward, models/Unet_FiLmLayer.py:277-312).
  * d_x (B,H,D), h_t[t_count] with t_count == 1 (broadcast) or B, d_cond (B,cond_dim),
- * d_eps (B,H,D).  cond may be NULL (no FiLM, `y=None`). */
+ * d_eps (B,H,D).  cond may be NULL (no FiLM, `y=None`), except under SPDM_FLAG_SIMPLE_UNET. */
 int  spdm_unet_forward(spdm_handle* h, int32_t B, const float* d_x, const int32_t* h_t,
                        int32_t t_count, const float* d_cond, float* d_eps, void* stream);
 

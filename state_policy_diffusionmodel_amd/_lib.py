@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("SPDM_LIB") or os.path.join(HERE, "libspdm_hip.so")   
 SPDM_DDPM, SPDM_DDIM = 0, 1
 SPDM_FLAG_DEBUG_KEEP = 1
 SPDM_FLAG_EXACT_FP32 = 2
+SPDM_FLAG_SIMPLE_UNET = 4
 ABI_VERSION = 1
 
 

@@ -167,6 +167,7 @@ __global__ __launch_bounds__(256) void pool_kernel(const AffineSrc src, float* _
     const AffineParams ap = load_affine_params(src, c4 * 4);
     float mean, rstd;
     block_sample_stats(src, b, sm, mean, rstd);
+    if (rl >= rpp) return;               // C / 4 need not divide 256 (192 channels: 240 of the 256 threads work)
     const Affine4 af = finish_affine(ap, mean, rstd);
     const int r_end = min(HWo, (int)(blockIdx.y + 1) * rows_per_block);
     for (int ro = blockIdx.y * rows_per_block + rl; ro < r_end; ro += rpp) {
@@ -194,7 +195,7 @@ static inline int rows_per_block_for(int HW, int B) {
 
 hipError_t launch_pool(const AffineSrc& src, float* dst, int B, int H, int W, hipStream_t s) {
     const int C4 = src.C / 4;
-    if (src.C % 4 != 0 || C4 > 256 || 256 % C4 != 0 || (H & 1) || (W & 1) || B <= 0) return hipErrorInvalidValue;
+    if (src.C % 4 != 0 || C4 < 1 || C4 > 256 || (H & 1) || (W & 1) || B <= 0) return hipErrorInvalidValue;
     const int HWo = (H / 2) * (W / 2);
     const int rpb = rows_per_block_for(HWo, B);
     hipLaunchKernelGGL(pool_kernel, dim3(B, (HWo + rpb - 1) / rpb), dim3(256), 0, s, src, dst, H, W, rpb);
@@ -244,6 +245,7 @@ __global__ __launch_bounds__(256) void upcat_kernel(const AffineSrc up, const Af
         if (up.st.p != nullptr) { mu_u = sm_u[0]; rs_u = sm_u[1]; }
         if (skip.st.p != nullptr) { mu_s = sm_s[0]; rs_s = sm_s[1]; }
     }
+    if (rl >= rpp) return;               // C / 4 need not divide 256 (after the only barrier)
     const Affine4 af = is_up ? finish_affine(ap, mu_u, rs_u) : finish_affine(ap, mu_s, rs_s);
     const float sch = (Ho > 1) ? (float)(Hin - 1) / (float)(Ho - 1) : 0.f;
     const float scw = (Wo > 1) ? (float)(Win - 1) / (float)(Wo - 1) : 0.f;
@@ -279,7 +281,7 @@ __global__ __launch_bounds__(256) void upcat_kernel(const AffineSrc up, const Af
 hipError_t launch_upcat(const AffineSrc& up, const AffineSrc& skip, float* dst, int B, int Hin, int Win,
                         hipStream_t s) {
     const int C = up.C + skip.C, C4 = C / 4;
-    if (up.C % 4 != 0 || skip.C % 4 != 0 || C4 > 256 || 256 % C4 != 0 || B <= 0) return hipErrorInvalidValue;
+    if (up.C % 4 != 0 || skip.C % 4 != 0 || C4 < 1 || C4 > 256 || B <= 0) return hipErrorInvalidValue;
     const int HWo = 4 * Hin * Win;
     const int rpb = rows_per_block_for(HWo, B);
     hipLaunchKernelGGL(upcat_kernel, dim3(B, (HWo + rpb - 1) / rpb), dim3(256), 0, s, up, skip, dst, Hin, Win, rpb);
@@ -474,6 +476,109 @@ __global__ void silu_kernel(const float* __restrict__ x, float* __restrict__ y, 
 }
 hipError_t launch_silu(const float* x, float* y, size_t n, hipStream_t s) {
     hipLaunchKernelGGL(silu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, y, n);
+    return hipGetLastError();
+}
+
+// -------------------------------------------------------------------------------------------------
+// The concat-conditioned U-Net (models/simple_Unet.py).  Its tensors live in channel-padded storage: real
+// channels at the positions of the plan's channel map, exact zeros elsewhere (zero weights, zero GroupNorm gain and offset,
+// statistics over the real channel count), so every kernel below only has to keep the padded lanes at zero.
+
+// nn.SiLU() + flatten of cond_emb_layer (simple_Unet.py:146-150, :197-201), zero-padded to Kp
+__global__ void silu_pad_kernel(const float* __restrict__ cond, float* __restrict__ dst, int B, int cond_dim, int Kp) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)B * Kp) return;
+    const int b = (int)(i / Kp), k = (int)(i - (size_t)b * Kp);
+    float v = 0.f;
+    if (k < cond_dim) {
+        const float x = cond[(size_t)b * cond_dim + k];
+        v = x / (1.0f + expf(-x));
+    }
+    dst[i] = v;
+}
+hipError_t launch_silu_pad(const float* cond, float* dst, int B, int cond_dim, int Kp, hipStream_t s) {
+    if (!cond || !dst || B <= 0 || cond_dim < 1 || Kp < cond_dim) return hipErrorInvalidValue;
+    const size_t n = (size_t)B * Kp;
+    hipLaunchKernelGGL(silu_pad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, cond, dst, B, cond_dim, Kp);
+    return hipGetLastError();
+}
+
+// End of DoubleConvolution.forward (simple_Unet.py:112-121): y = GELU(GN(x) + res), res == nullptr: y = GELU(GN(x)).
+// res has the layout of x (the residual block maps its channels to themselves).
+__global__ __launch_bounds__(256) void dc_finish_kernel(const AffineSrc src, const float* __restrict__ res,
+                                                        float* __restrict__ dst, int HW, int rows_per_block) {
+    __shared__ float sm[2];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    float mean, rstd;
+    block_sample_stats(src, b, sm, mean, rstd);
+    const int C = src.C, C4 = C >> 2;
+    const int c4 = tid % C4, rl = tid / C4, rpp = 256 / C4;
+    if (rl >= rpp) return;
+    const Affine4 af = make_affine(src, c4 * 4, mean, rstd);
+    const int r_end = min(HW, (int)(blockIdx.y + 1) * rows_per_block);
+    for (int r = blockIdx.y * rows_per_block + rl; r < r_end; r += rpp) {
+        const size_t o = ((size_t)b * HW + r) * C + c4 * 4;
+        float4 v = apply_affine(af, *reinterpret_cast<const float4*>(src.x + o));
+        if (res != nullptr) {
+            const float4 q = *reinterpret_cast<const float4*>(res + o);
+            v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
+        }
+        v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w);
+        *reinterpret_cast<float4*>(dst + o) = v;
+    }
+}
+hipError_t launch_dc_finish(const AffineSrc& src, const float* res, float* dst, int B, int HW, hipStream_t s) {
+    const int C4 = src.C / 4;
+    if (!src.x || !dst || src.C % 4 != 0 || C4 < 1 || C4 > 256 || B <= 0 || HW <= 0) return hipErrorInvalidValue;
+    const int rpb = rows_per_block_for(HW, B);
+    hipLaunchKernelGGL(dc_finish_kernel, dim3(B, (HW + rpb - 1) / rpb), dim3(256), 0, s, src, res, dst, HW, rpb);
+    return hipGetLastError();
+}
+
+// Tail of DownSample / UpSample.forward (simple_Unet.py:160-176, :209-224) on the raw output of the block's last conv:
+//   y[:, 0:Cr]       = GELU(GN(x)) + temb[t][c]                   (Linear(SiLU(pe[t])), tabulated per t)
+//   y[:, Cr:Cr + 32] = cemb[b][0:32]                              (Linear(SiLU(cond)), step-invariant, broadcast over H x W)
+//   y[:, Cr + 32:Co] = 0                                          (storage padding)
+__global__ __launch_bounds__(256) void simple_tail_kernel(const AffineSrc src, int Cr, const float* __restrict__ temb, int temb_ld,
+                                                          const int* __restrict__ t_dev, int t_count,
+                                                          const float* __restrict__ cemb, int cemb_ld, float* __restrict__ dst,
+                                                          int Co, int HW, int rows_per_block) {
+    __shared__ float sm[2];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    float mean, rstd;
+    block_sample_stats(src, b, sm, mean, rstd);
+    const int C4 = Co >> 2;
+    const int c4 = tid % C4, rl = tid / C4, rpp = 256 / C4;
+    if (rl >= rpp) return;
+    const int c = c4 * 4;
+    const bool from_x = c < Cr;
+    Affine4 af{};
+    float4 k = make_float4(0.f, 0.f, 0.f, 0.f);      // what is added (real channels) or stored (cond / padding channels)
+    if (from_x) {
+        af = make_affine(src, c, mean, rstd);
+        k = *reinterpret_cast<const float4*>(temb + (size_t)t_dev[t_count == 1 ? 0 : b] * temb_ld + c);
+    } else if (c < Cr + 32) {
+        k = *reinterpret_cast<const float4*>(cemb + (size_t)b * cemb_ld + (c - Cr));
+    }
+    const int r_end = min(HW, (int)(blockIdx.y + 1) * rows_per_block);
+    for (int r = blockIdx.y * rows_per_block + rl; r < r_end; r += rpp) {
+        float4 v = k;
+        if (from_x) {
+            const float4 x = apply_affine(af, *reinterpret_cast<const float4*>(src.x + ((size_t)b * HW + r) * src.C + c));
+            v.x = gelu_erf(x.x) + k.x; v.y = gelu_erf(x.y) + k.y; v.z = gelu_erf(x.z) + k.z; v.w = gelu_erf(x.w) + k.w;
+        }
+        *reinterpret_cast<float4*>(dst + ((size_t)b * HW + r) * Co + c) = v;
+    }
+}
+hipError_t launch_simple_tail(const AffineSrc& src, int Cr, const float* temb, int temb_ld, const int* t_dev, int t_count,
+                              const float* cemb, int cemb_ld, float* dst, int Co, int B, int HW, hipStream_t s) {
+    const int C4 = Co / 4;
+    if (!src.x || !dst || !temb || !t_dev || !cemb || B <= 0 || HW <= 0 || t_count < 1) return hipErrorInvalidValue;
+    if (Co % 4 != 0 || C4 < 1 || C4 > 256 || Cr % 4 != 0 || Cr < 4 || Cr > src.C || src.C % 4 != 0 || Cr + 32 > Co) return hipErrorInvalidValue;
+    if (temb_ld < Cr || temb_ld % 4 != 0 || cemb_ld < 32 || cemb_ld % 4 != 0) return hipErrorInvalidValue;
+    const int rpb = rows_per_block_for(HW, B);
+    hipLaunchKernelGGL(simple_tail_kernel, dim3(B, (HW + rpb - 1) / rpb), dim3(256), 0, s, src, Cr, temb, temb_ld, t_dev, t_count,
+                       cemb, cemb_ld, dst, Co, HW, rpb);
     return hipGetLastError();
 }
 

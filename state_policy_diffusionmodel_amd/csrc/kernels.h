@@ -226,6 +226,13 @@ hipError_t launch_layernorm(const float* x, const float* g, const float* b, floa
 hipError_t launch_mish_pad(const float* cond, float* dst, int B, int cond_dim, int Kp, hipStream_t s);
 hipError_t launch_silu(const float* x, float* y, size_t n, hipStream_t s);
 hipError_t launch_gelu(const float* x, float* y, size_t n, hipStream_t s);
+// the concat-conditioned U-Net (models/simple_Unet.py; channel-padded storage)
+hipError_t launch_silu_pad(const float* cond, float* dst, int B, int cond_dim, int Kp, hipStream_t s);
+// y = GELU(GN(x) + res) (res null: GELU(GN(x))), (B, HW, C) -> same
+hipError_t launch_dc_finish(const AffineSrc& src, const float* res, float* dst, int B, int HW, hipStream_t s);
+// block tail: y[:, :Cr] = GELU(GN(x)) + temb[t][c], y[:, Cr:Cr+32] = cemb[b], zeros up to Co
+hipError_t launch_simple_tail(const AffineSrc& src, int Cr, const float* temb, int temb_ld, const int* t_dev, int t_count,
+                              const float* cemb, int cemb_ld, float* dst, int Co, int B, int HW, hipStream_t s);
 
 struct StepArgs {
     const float* feat;            // (B, Hp*Wp, 64) channels-last

@@ -111,7 +111,8 @@ struct Value {             // a tensor plus the GroupNorm affine still pending o
     bool pending_gn() const { return st.valid; }
 };
 
-struct ConvW { float* w = nullptr; float* ws = nullptr; float* wf = nullptr; int taps = 0, cin = 0, cout = 0; };   // ws: split-fp16 copy; wf: its fragment-order copy (conv_wide.hip)
+struct ConvW { float* w = nullptr; float* ws = nullptr; float* wf = nullptr; int taps = 0, cin = 0, cout = 0;
+               int cnorm = 0; };   // cnorm > 0: real output channels of a channel-padded layer (its GroupNorm divides by these)   // ws: split-fp16 copy; wf: its fragment-order copy (conv_wide.hip)
 struct DoubleConvW { ConvW first, second; float* gamma = nullptr; float* beta = nullptr; };
 struct LinW { float* w = nullptr; float* ws = nullptr; float* b = nullptr; int in = 0, out = 0; };
 struct ResampleW { DoubleConvW dc1, dc2; LinW emb, film; float* temb_table = nullptr; int cout = 0; };
@@ -139,6 +140,9 @@ struct spdm_handle {
     float* outc_w = nullptr;
     float outc_b = 0.f;
     bool weights_loaded = false, temb_ready = false;
+    bool simple = false;                  // SPDM_FLAG_SIMPLE_UNET: models/simple_Unet.py (plan_simple); inc / down / up hold its blocks
+    LinW cemb;                            // ... its six cond_emb_layer projections stacked: [6 x 32][film_kp]
+    float* d_cemb = nullptr;              // ... Linear(SiLU(cond)) of the call, [B][6 x 32]
     bool split = true;                    // split-fp16 MFMA path (default); SPDM_PREC=f32 selects the exact fp32 MFMA path
     unsigned sw = 0;                      // kernel-selection switches (SW_*, kernels.h): environment read once at create
     int demoted = 0;                      // tensors outside the split format's range, kept on the exact fp32 kernels
@@ -297,6 +301,7 @@ static int dry_plan_all(spdm_handle* h) {
     size_t peak = 0;
     for (int mask = 0; mask < 512; ++mask) {      // bits 0-2 pool read through, 3-5 upsample + concat read through, 6-8 two-source conv
         if (((mask >> 3) & (mask >> 6) & 7) != 0) continue;       // (a block is one or the other)
+        if (h->simple && mask != 0) break;                         // (plan_simple materialises every resampling op)
         h->dry_fuse_mask = mask;
         h->arena.peak = 0;
         h->arena.reset();
@@ -310,11 +315,64 @@ static int dry_plan_all(spdm_handle* h) {
     return SPDM_OK;
 }
 
+// ---- models/simple_Unet.py in channel-padded storage ----
+// Every tensor and every convolution of this network is stored with a multiple of 64 channels (the implicit-GEMM kernels need
+// K % 32 == 0 and N % 64 == 0).  A ChanMap says where each real channel lives; the other lanes hold exact zeros: zero weight
+// rows and columns, zero GroupNorm gain and offset, statistics over the real channel count (ConvW::cnorm).  An UpSample's
+// concatenation keeps both halves at their own padded widths, so its first convolution's input channels are re-laid out on load.
+struct ChanMap {
+    int width = 0;
+    std::vector<int> pos;                 // storage position of real channel i
+    int real() const { return (int)pos.size(); }
+    static ChanMap ident(int C) {
+        ChanMap m;
+        m.width = (int)align_up((size_t)C, 64);
+        for (int i = 0; i < C; ++i) m.pos.push_back(i);
+        return m;
+    }
+    static ChanMap cat(const ChanMap& a, const ChanMap& b) {
+        ChanMap m;
+        m.width = a.width + b.width;
+        m.pos = a.pos;
+        for (int p : b.pos) m.pos.push_back(a.width + p);
+        return m;
+    }
+};
+// UNet.__init__, simple_Unet.py:270-280: blocks down1..3, up1..3 -- input channels (cin_b > 0: cat(upsampled cin_a, skip cin_b))
+// and the output channels of doubleConv2; each block then appends 32 conditioning channels
+struct SimpleBlock { int cin_a, cin_b, cout; };
+static const SimpleBlock kSimpleBlocks[6] = {{16, 0, 32}, {64, 0, 128}, {160, 0, 256}, {288, 160, 128}, {160, 64, 64}, {96, 16, 32}};
+static constexpr int SIMPLE_COND_CH = 32;       // cond_emb_layer output width (simple_Unet.py:149,200)
+static ChanMap simple_in_map(int k) {
+    const SimpleBlock& b = kSimpleBlocks[k];
+    return b.cin_b ? ChanMap::cat(ChanMap::ident(b.cin_a), ChanMap::ident(b.cin_b)) : ChanMap::ident(b.cin_a);
+}
+static int simple_out_width(int k) { return (int)align_up((size_t)kSimpleBlocks[k].cout + SIMPLE_COND_CH, 64); }
+static ResampleW& simple_block(spdm_handle* h, int k) { return k < 3 ? h->down[k] : h->up[k - 3]; }
+
 // channel / tap geometry of every layer (UNet_Film.__init__, models/Unet_FiLmLayer.py:246-264); known
 // before any weight is loaded, so that create() can size the workspace with a dry run of the plan
 static void init_arch(spdm_handle* h) {
     // level-3 maps are (Hp/8) x 1: a 3x3 kernel only ever multiplies its centre column there
     const int t3 = (h->Wp >> 3) == 1 ? 3 : 9;
+    if (h->simple) {
+        auto shape = [](ConvW& c, const ChanMap& in, const ChanMap& out, int taps) {
+            c.cin = in.width; c.cout = out.width; c.taps = taps; c.cnorm = out.real();
+        };
+        const ChanMap c16 = ChanMap::ident(16);
+        shape(h->inc.second, c16, c16, 9);
+        for (int k = 0; k < 6; ++k) {
+            ResampleW& r = simple_block(h, k);
+            const ChanMap in = simple_in_map(k), out = ChanMap::ident(kSimpleBlocks[k].cout);
+            const int taps = (k == 2) ? t3 : 9;   // down3 runs on the level-3 maps
+            shape(r.dc1.first, in, in, taps);
+            shape(r.dc1.second, in, in, taps);
+            shape(r.dc2.first, in, out, taps);
+            shape(r.dc2.second, out, out, taps);
+            r.cout = kSimpleBlocks[k].cout;
+        }
+        return;
+    }
     auto dc = [](DoubleConvW& d, int cin, int cout, int taps) {
         d.first.cin = cin; d.first.cout = cout; d.first.taps = taps;
         d.second.cin = cout; d.second.cout = cout; d.second.taps = taps;
@@ -345,9 +403,14 @@ extern "C" int spdm_create(const spdm_config* cfg, spdm_handle** out) {
     if (cfg->time_dim < 32 || cfg->time_dim % 32 != 0) return fail(SPDM_ERR_INVALID, "time_dim must be a multiple of 32");
     if (cfg->cond_dim < 0 || cfg->max_batch < 1 || cfg->num_train_timesteps < 1)
         return fail(SPDM_ERR_INVALID, "cond_dim >= 0, max_batch >= 1, num_train_timesteps >= 1 required");
+    if ((cfg->flags & SPDM_FLAG_SIMPLE_UNET) && cfg->attention != 0)
+        return fail(SPDM_ERR_INVALID, "SPDM_FLAG_SIMPLE_UNET (models/simple_Unet.py) has no attention blocks: attention must be 0");
+    if ((cfg->flags & SPDM_FLAG_SIMPLE_UNET) && cfg->cond_dim < 1)
+        return fail(SPDM_ERR_INVALID, "SPDM_FLAG_SIMPLE_UNET needs cond_dim >= 1 (the network is only defined with conditioning)");
     HIP_TRY(hipSetDevice(cfg->device));
     spdm_handle* h = new spdm_handle();
     h->cfg = *cfg;
+    h->simple = (cfg->flags & SPDM_FLAG_SIMPLE_UNET) != 0;
     h->sw = switches_from_env();          // the ONLY place the product path reads SPDM_* switches
     if (const char* pe = getenv("SPDM_PREC")) h->split = !(strcmp(pe, "f32") == 0 || strcmp(pe, "fp32") == 0);
     if (cfg->flags & SPDM_FLAG_EXACT_FP32) h->split = false;
@@ -369,7 +432,8 @@ extern "C" int spdm_create(const spdm_config* cfg, spdm_handle** out) {
         if (hipMemset(h->d_step, 0, sizeof(int) * 4) != hipSuccess) { rc = fail(SPDM_ERR_HIP, "memset failed"); break; }
         if ((rc = dev_alloc(h, (void**)&h->d_condm, sizeof(float) * (size_t)mb * h->film_kp))) break;
         static const int film_c[6] = {128, 256, 256, 128, 64, 64};
-        for (int i = 0; i < 6 && !rc; ++i) rc = dev_alloc(h, (void**)&h->d_film[i], sizeof(float) * (size_t)mb * 2 * film_c[i]);
+        if (h->simple) rc = dev_alloc(h, (void**)&h->d_cemb, sizeof(float) * (size_t)mb * 6 * SIMPLE_COND_CH);
+        for (int i = 0; i < 6 && !rc && !h->simple; ++i) rc = dev_alloc(h, (void**)&h->d_film[i], sizeof(float) * (size_t)mb * 2 * film_c[i]);
         if (rc) break;
         if ((rc = dev_alloc(h, (void**)&h->d_x, sizeof(float) * (size_t)mb * H0 * D))) break;
         if (h->split && !(h->sw & SW_NO_SPLITK) && (rc = dev_alloc(h, (void**)&h->d_partial, SPLITK_WORKSPACE_BYTES))) break;
@@ -569,6 +633,57 @@ struct Loader {
         if (!split_range_ok(std::vector<float>(w, w + (size_t)out * in))) { demote(wname); return nullptr; }
         return upload(frag_order_weights(split_format(std::vector<float>(w, w + (size_t)out * in)), 1, out, in));
     }
+    // ---- models/simple_Unet.py: re-layout into channel-padded storage (ChanMap) ----
+    // (Cout, Cin, 3, 3) -> [taps][mo.width][mi.width], real (o, i) at (mo.pos[o], mi.pos[i]), zeros elsewhere
+    ConvW conv_mapped(const std::string& name, const ChanMap& mo, const ChanMap& mi, int taps) {
+        ConvW c;
+        const int co = mo.real(), ci = mi.real(), N = mo.width, K = mi.width;
+        const float* src = find(name, {co, ci, 3, 3});
+        if (!src) return c;
+        std::vector<float> v((size_t)taps * N * K, 0.f);
+        for (int t = 0; t < taps; ++t) {
+            const int kh = (taps == 9) ? t / 3 : t, kw = (taps == 9) ? t % 3 : 1;
+            for (int o = 0; o < co; ++o)
+                for (int i = 0; i < ci; ++i)
+                    v[((size_t)t * N + mo.pos[o]) * K + mi.pos[i]] = src[(((size_t)o * ci + i) * 3 + kh) * 3 + kw];
+        }
+        c.w = upload(v);
+        c.ws = upload_split(v, K, name);
+        if (c.ws) c.wf = upload(frag_order_weights(split_format(v), taps, N, K));
+        c.taps = taps; c.cin = K; c.cout = N; c.cnorm = co;
+        return c;
+    }
+    float* vec_mapped(const std::string& name, const ChanMap& m) {
+        const float* src = find(name, {m.real()});
+        if (!src) return nullptr;
+        std::vector<float> v(m.width, 0.f);
+        for (int i = 0; i < m.real(); ++i) v[m.pos[i]] = src[i];
+        return upload(v);
+    }
+    // DoubleConvolution (simple_Unet.py:92-104): ONE GroupNorm module serves both convolutions
+    DoubleConvW dconv_mapped(const std::string& p, const ChanMap& mi, const ChanMap& mo, int taps) {
+        DoubleConvW d;
+        d.first = conv_mapped(p + ".first.weight", mo, mi, taps);
+        d.second = conv_mapped(p + ".second.weight", mo, mo, taps);
+        d.gamma = vec_mapped(p + ".norm.weight", mo);
+        d.beta = vec_mapped(p + ".norm.bias", mo);
+        return d;
+    }
+    // Linear (out, in) with its output rows padded to out_pad (zero rows, zero bias)
+    LinW linear_pad_out(const std::string& wname, const std::string& bname, int out, int in, int out_pad) {
+        LinW l;
+        const float* w = find(wname, {out, in});
+        const float* b = find(bname, {out});
+        if (!w || !b) return l;
+        std::vector<float> v((size_t)out_pad * in, 0.f), bv(out_pad, 0.f);
+        memcpy(v.data(), w, sizeof(float) * (size_t)out * in);
+        memcpy(bv.data(), b, sizeof(float) * out);
+        l.w = upload(v);
+        l.ws = (in % 32 == 0) ? upload_split(v, in, wname) : nullptr;
+        l.b = upload(bv);
+        l.in = in; l.out = out_pad;
+        return l;
+    }
     AttnW attn(const std::string& p, int C) {
         AttnW a;
         a.C = C;
@@ -620,6 +735,69 @@ static int replan_arena(spdm_handle* h) {
     return SPDM_OK;
 }
 
+// UNet.state_dict() of models/simple_Unet.py (SPDM_FLAG_SIMPLE_UNET) into channel-padded storage; Loader::err carries failures
+static int load_simple(spdm_handle* h, Loader& L, int t3) {
+    const ChanMap c16 = ChanMap::ident(16);
+    {   // input_conv.first (16,1,3,3) -> [9][64] (conv_in_kernel's layout; output lanes 16..63 zero)
+        const float* src = L.find("input_conv.first.weight", {16, 1, 3, 3});
+        if (src) {
+            std::vector<float> v(9 * 64, 0.f);
+            for (int t = 0; t < 9; ++t)
+                for (int o = 0; o < 16; ++o) v[t * 64 + o] = src[o * 9 + t];
+            h->w_inc_first = L.upload(v);
+        }
+    }
+    h->inc.second = L.conv_mapped("input_conv.second.weight", c16, c16, 9);
+    h->inc.gamma = L.vec_mapped("input_conv.norm.weight", c16);
+    h->inc.beta = L.vec_mapped("input_conv.norm.bias", c16);
+    static const char* names[6] = {"down1", "down2", "down3", "up1", "up2", "up3"};
+    const int Kp = h->film_kp, cd = h->cfg.cond_dim, td = h->cfg.time_dim;
+    std::vector<float> cw((size_t)6 * SIMPLE_COND_CH * Kp, 0.f), cb((size_t)6 * SIMPLE_COND_CH, 0.f);
+    for (int k = 0; k < 6; ++k) {
+        const std::string p = names[k];
+        ResampleW& r = simple_block(h, k);
+        const ChanMap in = simple_in_map(k), out = ChanMap::ident(kSimpleBlocks[k].cout);
+        const int taps = (k == 2) ? t3 : 9;
+        r.dc1 = L.dconv_mapped(p + ".doubleConv1", in, in, taps);
+        r.dc2 = L.dconv_mapped(p + ".doubleConv2", in, out, taps);
+        r.emb = L.linear_pad_out(p + ".emb_layer.1.weight", p + ".emb_layer.1.bias", out.real(), td, out.width);
+        r.cout = out.real();
+        const float* w = L.find(p + ".cond_emb_layer.1.weight", {SIMPLE_COND_CH, cd});
+        const float* b = L.find(p + ".cond_emb_layer.1.bias", {SIMPLE_COND_CH});
+        if (w && b)
+            for (int o = 0; o < SIMPLE_COND_CH; ++o) {
+                memcpy(&cw[((size_t)k * SIMPLE_COND_CH + o) * Kp], w + (size_t)o * cd, sizeof(float) * cd);
+                cb[(size_t)k * SIMPLE_COND_CH + o] = b[o];
+            }
+    }
+    h->cemb.w = L.upload(cw);
+    h->cemb.ws = L.upload_split(cw, Kp, "cond_emb_layer");
+    h->cemb.b = L.upload(cb);
+    h->cemb.in = Kp; h->cemb.out = 6 * SIMPLE_COND_CH;
+    {   // outc: Conv2d(64, out, 1) with bias (simple_Unet.py:280); the 64 channels are up3's 32 + 32, unpadded
+        const float* w = L.find("outc.weight", {1, 64, 1, 1});
+        const float* b = L.find("outc.bias", {1});
+        if (w && b) {
+            h->outc_w = L.upload(std::vector<float>(w, w + 64));
+            h->outc_b = b[0];
+        }
+    }
+    if (L.err != SPDM_OK) return L.err;
+    // pos_encoding.pos_encoding (noise_steps + 1, time_dim): the sin/cos-interleaved table of PositionalEncoding (:226-257)
+    // IS the time table of this network
+    auto it = L.idx.find("pos_encoding.pos_encoding");
+    if (it == L.idx.end()) return fail(SPDM_ERR_MISSING, "tensor 'pos_encoding.pos_encoding' not in the index");
+    const spdm_tensor_index* e = it->second;
+    if (e->ndim != 2 || e->shape[1] != td || e->shape[0] != h->cfg.num_train_timesteps)
+        return fail(SPDM_ERR_INVALID, "pos_encoding.pos_encoding is (%d, %d): the handle needs (num_train_timesteps = %d, time_dim = %d) "
+                    "-- create it with num_train_timesteps equal to the buffer's row count", e->shape[0], e->ndim > 1 ? e->shape[1] : 0,
+                    h->cfg.num_train_timesteps, td);
+    const float* pe = L.find("pos_encoding.pos_encoding", {h->cfg.num_train_timesteps, td});
+    if (!pe) return L.err;
+    h->time_table.assign(pe, pe + (size_t)h->cfg.num_train_timesteps * td);
+    return SPDM_OK;
+}
+
 extern "C" int spdm_load_weights(spdm_handle* h, const float* blob, size_t n, const spdm_tensor_index* index,
                                  int32_t n_index) {
     if (!h || !blob || !index || n_index <= 0) return fail(SPDM_ERR_INVALID, "null argument");
@@ -634,6 +812,9 @@ extern "C" int spdm_load_weights(spdm_handle* h, const float* blob, size_t n, co
     }
     // level-3 maps are (Hp/8) x 1: a 3x3 kernel only ever multiplies its centre column there
     const int t3 = (h->Wp >> 3) == 1 ? 3 : 9;
+    if (h->simple) {
+        SPDM_TRY(load_simple(h, L, t3));
+    } else {
     {   // inc.first (64,1,3,3) -> [9][64]
         const float* src = L.find("inc.first.weight", {64, 1, 3, 3});
         if (src) {
@@ -668,11 +849,12 @@ extern "C" int spdm_load_weights(spdm_handle* h, const float* blob, size_t n, co
             h->outc_b = b[0];
         }
     }
+    }
     if (L.err != SPDM_OK) return L.err;
     // time-embedding tables (one per resample block), filled lazily on the first evaluation
     ResampleW* blocks[6] = {&h->down[0], &h->down[1], &h->down[2], &h->up[0], &h->up[1], &h->up[2]};
     for (ResampleW* r : blocks)
-        SPDM_TRY(dev_alloc(h, (void**)&r->temb_table, sizeof(float) * (size_t)h->cfg.num_train_timesteps * r->cout));
+        SPDM_TRY(dev_alloc(h, (void**)&r->temb_table, sizeof(float) * (size_t)h->cfg.num_train_timesteps * r->emb.out));
     SPDM_TRY(dev_alloc(h, (void**)&h->d_time_silu, sizeof(float) * (size_t)h->cfg.num_train_timesteps * h->cfg.time_dim));
     h->weights_loaded = true;
     h->temb_ready = false;
@@ -778,7 +960,7 @@ struct Ctx {
         t.off = off; t.p = (float*)(h->arena.base + off); t.valid = true;
         return t;
     }
-    StatsBuf salloc(int HW, int C, int m_tile, int n_tiles) {
+    StatsBuf salloc(int HW, int C, int m_tile, int n_tiles, int C_norm = 0) {     // C_norm > 0: real channels of padded storage
         StatsBuf sb;
         const int slots = stats_slots(HW, m_tile, n_tiles);
         // reserve for the finest tiling any batch size can select (gemm_geometry is batch-dependent, the
@@ -794,7 +976,7 @@ struct Ctx {
         }
         sb.off = off; sb.p = (double*)(h->arena.base + off); sb.valid = true;
         sb.ref.p = sb.p; sb.ref.slots = slots; sb.ref.m_tile = m_tile; sb.ref.n_tiles = n_tiles; sb.ref.HW = HW;
-        sb.ref.inv_count = 1.0 / ((double)C * (double)HW);
+        sb.ref.inv_count = 1.0 / ((double)(C_norm > 0 ? C_norm : C) * (double)HW);
         return sb;
     }
     void free(Tensor& t) { if (t.valid) { h->arena.release(t.off); t.valid = false; } }
@@ -824,7 +1006,7 @@ struct Ctx {
         const int split = (h->split && w.cin % 32 == 0 && (!h->weights_loaded || w.ws)) ? 1 : 0;
         const GemmGeom g = gemm_geometry(Bg() * HW, w.cout, w.cin, HW, Wl(level), w.taps, split, h->sw, /*stats_epi=*/h->d_partial != nullptr);
         out.t = talloc(w.cout, level);
-        out.st = salloc(HW, w.cout, g.st_m_tile, g.st_n_tiles);
+        out.st = salloc(HW, w.cout, g.st_m_tile, g.st_n_tiles, w.cnorm);
         out.gamma = gamma; out.beta = beta;
         if (err || dry) return out;
         GemmArgs a{};
@@ -1337,10 +1519,92 @@ static int plan_unet(Ctx& c, const float* x, bool use_cond, Tensor* feat_out) {
     return c.err;
 }
 
+// one evaluation of models/simple_Unet.py's UNet.forward (:282-300, y given; eval mode: no dropout on pe[t]) in channel-padded
+// storage (ChanMap): x (B,H0,D) -> feat (B, Hp*Wp, 64) = up3's 32 channels + its 32 conditioning channels, what outc reads.
+// Every resampling op is materialised (launch_pool / launch_upcat on finished tensors); the convolutions are launch_gemm's.
+static int plan_simple(Ctx& c, const float* x, Tensor* feat_out) {
+    spdm_handle* h = c.h;
+    const int B = c.B;
+    // DoubleConvolution.forward (:106-121) on the finished tensor `in`: two convs (GN + GELU of the first applied in the second's
+    // load prologue), then y = GELU(GN(raw) + in) (residual) or GELU(GN(raw)).  Consumes `in`.
+    auto dconv = [&](Tensor& in, const DoubleConvW& w, int level, bool residual) {
+        Value vin;
+        vin.t = in;
+        Value raw = c.double_conv(vin, w, level, /*keep_in=*/true);
+        Tensor y = c.talloc(raw.t.C, level);
+        if (!c.err && !c.dry) c.check(launch_dc_finish(c.asrc(raw), residual ? in.p : nullptr, y.p, B, c.HWl(level), c.s), "dc_finish");
+        c.free(raw);
+        c.free(in);
+        return y;
+    };
+    // DownSample / UpSample body after the resampling op (:160-176, :209-224).  Consumes `in`.
+    auto block = [&](Tensor& in, int k, int level) {
+        ResampleW& r = simple_block(h, k);
+        Tensor a = dconv(in, r.dc1, level, /*residual=*/true);
+        Value va;
+        va.t = a;
+        Value raw = c.double_conv(va, r.dc2, level);
+        Tensor y = c.talloc(simple_out_width(k), level);
+        if (!c.err && !c.dry)
+            c.check(launch_simple_tail(c.asrc(raw), r.cout, r.temb_table, r.emb.out, h->d_t, c.h_tcount, h->d_cemb + SIMPLE_COND_CH * k,
+                                       h->cemb.out, y.p, y.C, B, c.HWl(level), c.s), "simple block tail");
+        c.free(raw);
+        return y;
+    };
+    // ---- input_conv = DoubleConvolution(1, 16) on pad_to(x, 8) (:284,289) ----
+    Value v0;
+    v0.t = c.talloc(64, 0);
+    v0.st = c.salloc(c.HWl(0), 64, c.HWl(0) / conv_in_parts(h->Hp, h->Wp, c.Bg()), 1, /*C_norm=*/16);
+    v0.gamma = h->inc.gamma; v0.beta = h->inc.beta;
+    if (!c.err && !c.dry)
+        c.check(launch_conv_in(x, h->w_inc_first, v0.t.p, v0.st.p, B, h->cfg.horizon, h->cfg.state_dim, h->Hp, h->Wp,
+                               h->lh, h->lw, h->d_step, h->d_t, h->d_timesteps, h->n_steps, c.adv, c.s, c.Bg()), "conv_in");
+    Value r0 = c.conv(v0, h->inc.second, 0, /*gelu=*/true, h->inc.gamma, h->inc.beta);
+    c.free(v0);
+    Tensor x1 = c.talloc(64, 0);
+    if (!c.err && !c.dry) c.check(launch_dc_finish(c.asrc(r0), nullptr, x1.p, B, c.HWl(0), c.s), "dc_finish");
+    c.free(r0);
+    c.tap("x1", x1);
+    // ---- down1..3 (:290-292): MaxPool2d(2) of the finished skip tensor, then the block ----
+    static const char* xn[3] = {"x2", "x3", "x4"};
+    Tensor skips[3] = {x1, Tensor{}, Tensor{}};
+    Tensor cur = x1;
+    for (int i = 0; i < 3; ++i) {
+        Tensor p = c.talloc(cur.C, i + 1);
+        Value vc;
+        vc.t = cur;
+        if (!c.err && !c.dry) c.check(launch_pool(c.asrc(vc), p.p, B, c.Hl(i), c.Wl(i), c.s), "maxpool");
+        cur = block(p, i, i + 1);
+        c.tap(xn[i], cur);
+        if (i < 2) skips[i + 1] = cur;
+    }
+    // ---- up1..3 (:294-296): cat([Upsample(x2, bilinear, align_corners=True)(x), skip]), then the block ----
+    static const char* un[3] = {"u1", "u2", "u3"};
+    for (int i = 0; i < 3; ++i) {
+        const int lin = 3 - i, lout = 2 - i;
+        Tensor& skip = skips[2 - i];
+        Tensor cat = c.talloc(cur.C + skip.C, lout);
+        Value vu, vs;
+        vu.t = cur;
+        vs.t = skip;
+        if (!c.err && !c.dry) c.check(launch_upcat(c.asrc(vu), c.asrc(vs), cat.p, B, c.Hl(lin), c.Wl(lin), c.s), "upsample+concat");
+        c.free(cur);
+        c.free(skip);
+        cur = block(cat, 3 + i, lout);
+        c.tap(un[i], cur);
+    }
+    *feat_out = cur;
+    return c.err;
+}
+
+static int plan_net(Ctx& c, const float* x, bool use_cond, Tensor* feat_out) {
+    return c.h->simple ? plan_simple(c, x, feat_out) : plan_unet(c, x, use_cond, feat_out);
+}
+
 static int plan_forward(spdm_handle* h, int B, bool use_cond, hipStream_t s, Tensor* feat_out) {
     Ctx c{h, B, s, h->arena.dry};
     h->arena.reset();
-    return plan_unet(c, h->d_x, use_cond, feat_out);
+    return plan_net(c, h->d_x, use_cond, feat_out);
 }
 
 // time-embedding tables: Linear(SiLU(pos_encoding(t))) for every t (models/Unet_FiLmLayer.py:136-142)
@@ -1356,8 +1620,8 @@ static int ensure_temb(spdm_handle* h, hipStream_t s) {
         GemmArgs a{};
         a.sw = h->sw;
         a.split = (h->split && blocks[i]->emb.ws) ? 1 : 0;
-        a.src = h->d_time_silu; a.src_ld = dim; a.wgt = a.split ? blocks[i]->emb.ws : blocks[i]->emb.w; a.dst = blocks[i]->temb_table; a.dst_ld = blocks[i]->cout;
-        a.M = T; a.K = dim; a.N = blocks[i]->cout; a.taps = 1; a.H = 1; a.W = 1; a.HW = 1;
+        a.src = h->d_time_silu; a.src_ld = dim; a.wgt = a.split ? blocks[i]->emb.ws : blocks[i]->emb.w; a.dst = blocks[i]->temb_table; a.dst_ld = blocks[i]->emb.out;
+        a.M = T; a.K = dim; a.N = blocks[i]->emb.out; a.taps = 1; a.H = 1; a.W = 1; a.HW = 1;   // (N: cout, padded for simple_Unet.py)
         a.pro = PRO_NONE; a.epi = EPI_BIAS; a.bias = blocks[i]->emb.b;
         e = launch_gemm(a, s);
     }
@@ -1373,6 +1637,24 @@ static int ensure_temb(spdm_handle* h, hipStream_t s) {
 static int compute_film(spdm_handle* h, int B, const float* d_cond, hipStream_t s) {
     h->have_film = false;
     if (!d_cond || h->cfg.cond_dim <= 0) return SPDM_OK;
+    if (h->simple) {
+        // models/simple_Unet.py: the six cond_emb_layer projections Linear(SiLU(flatten(cond))) (:146-150, :197-201) in ONE
+        // GEMM over the stacked weights -> d_cemb [B][6 x 32]; step-invariant, hoisted out of the denoise loop like FiLM
+        hipError_t e = launch_silu_pad(d_cond, h->d_condm, B, h->cfg.cond_dim, h->film_kp, s);
+        if (e == hipSuccess) {
+            GemmArgs a{};
+            a.sw = h->sw;
+            a.split = (h->split && h->cemb.ws) ? 1 : 0;
+            a.src = h->d_condm; a.src_ld = h->film_kp; a.wgt = a.split ? h->cemb.ws : h->cemb.w; a.dst = h->d_cemb; a.dst_ld = h->cemb.out;
+            a.M = B; a.K = h->film_kp; a.N = h->cemb.out; a.taps = 1; a.H = 1; a.W = 1; a.HW = 1;
+            a.geom_M = (h->sw & SW_PIN_GEOMETRY) ? h->cfg.max_batch : 0;
+            a.pro = PRO_NONE; a.epi = EPI_BIAS; a.bias = h->cemb.b;
+            e = launch_gemm(a, s);
+        }
+        if (e != hipSuccess) return fail(SPDM_ERR_HIP, "conditioning projections: %s", hipGetErrorString(e));
+        h->have_film = true;
+        return SPDM_OK;
+    }
     hipError_t e = launch_mish_pad(d_cond, h->d_condm, B, h->cfg.cond_dim, h->film_kp, s);
     ResampleW* blocks[6] = {&h->down[0], &h->down[1], &h->down[2], &h->up[0], &h->up[1], &h->up[2]};
     for (int i = 0; i < 6 && e == hipSuccess; ++i) {
@@ -1416,6 +1698,7 @@ extern "C" int spdm_unet_forward(spdm_handle* h, int32_t B, const float* d_x, co
     if (t_count != 1 && t_count != B) return fail(SPDM_ERR_INVALID, "t_count must be 1 or B");
     for (int i = 0; i < t_count; ++i)
         if (h_t[i] < 0 || h_t[i] >= h->cfg.num_train_timesteps) return fail(SPDM_ERR_INVALID, "t = %d outside [0,%d)", h_t[i], h->cfg.num_train_timesteps);
+    if (h->simple && !d_cond) return fail(SPDM_ERR_INVALID, "d_cond is null: models/simple_Unet.py's UNet needs its conditioning");
     HIP_TRY(hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     SPDM_TRY(ensure_temb(h, s));
@@ -1428,7 +1711,7 @@ extern "C" int spdm_unet_forward(spdm_handle* h, int32_t B, const float* d_x, co
     c.h_tcount = t_count;
     h->arena.reset();
     Tensor feat;
-    SPDM_TRY(plan_unet(c, h->d_x, d_cond != nullptr, &feat));
+    SPDM_TRY(plan_net(c, h->d_x, d_cond != nullptr, &feat));
     StepArgs a = step_args(h, B, feat);
     a.eps_out = d_eps;
     a.ptrs_dev = nullptr;
@@ -1444,6 +1727,7 @@ extern "C" int spdm_sample_begin(spdm_handle* h, int32_t B, const float* d_cond,
     SPDM_TRY(check_ready(h, B));
     if (h->sched_kind < 0) return fail(SPDM_ERR_STATE, "no schedule set (spdm_set_schedule)");
     if (!d_xT) return fail(SPDM_ERR_INVALID, "d_xT is null");
+    if (h->simple && !d_cond) return fail(SPDM_ERR_INVALID, "d_cond is null: models/simple_Unet.py's UNet needs its conditioning");
     if (inp_h < 0 || inp_h > h->cfg.horizon) return fail(SPDM_ERR_INVALID, "inpaint horizon %d outside [0,%d]", inp_h, h->cfg.horizon);
     HIP_TRY(hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
@@ -1480,7 +1764,7 @@ static int enqueue_step(spdm_handle* h, int i, hipStream_t s) {
     c.adv = (i >= 0) ? i : -1;          // the step's first kernel (conv_in_kernel) does the bookkeeping
     h->arena.reset();
     Tensor feat;
-    SPDM_TRY(plan_unet(c, h->d_x, h->have_film, &feat));
+    SPDM_TRY(plan_net(c, h->d_x, h->have_film, &feat));
     StepArgs a = step_args(h, h->sB, feat);
     HIP_TRY(launch_out_step(a, s));
     return SPDM_OK;

@@ -14,6 +14,13 @@ types -- so ``generate.py``'s idiom
 works unchanged.  What runs underneath is libspdm_hip.so (no torch compute in the loop).
 Training, validation plots and the Lightning plumbing are out of scope.
 
+All three noise predictors of ``__init__`` (models/diffusion_ddpm.py:53-62) run on that path: ``model='UNet_Film'``,
+``'UNet_FilmnoAttention'``, and every other value -- the constructor's own default ``'UNet'`` -- for
+models/simple_Unet.py's concat-conditioned ``UNet``.  Evaluation always has eval semantics: that network's
+positional-encoding dropout is off, as in the reference's ``validation_step`` and ``sample()`` after ``model.eval()``;
+the reference's ``training_step`` runs it with dropout p = 0.1, which ``training_step`` here does not reproduce (its
+forward half is the eval-mode network).
+
 Explicit, non-breaking extensions: ``sample(..., x_T=, noise=, batched=, seed=)`` for
 fixed-noise parity runs and for B > 1 independent trajectories (the reference hard-wires
 B = 1 by taking ``obs_cond[0]``, ``models/diffusion_ddpm.py:246``).
@@ -26,7 +33,7 @@ import torch
 
 from .engine import SpdmEngine
 from .schedulers import DDIMScheduler, DDPMScheduler, _LinearBetaScheduler
-from .weights import random_state_dict, state_dict_to_numpy
+from .weights import is_simple_model, random_state_dict, state_dict_to_numpy
 
 
 def _as_spec(sched) -> _LinearBetaScheduler:
@@ -82,20 +89,17 @@ class Diffusion_DDPM:
         self.prediction_dim = prediction_dim
         self.inpaint_horizon = inpaint_horizon
         self.lr = learning_rate
-        # --- architecture switch (:54-62); the concat-conditioned 'UNet' is a different network
-        if model == "UNet_Film":
-            self.attention = True
-        elif model == "UNet_FilmnoAttention":
-            self.attention = False
-        else:
-            raise NotImplementedError("only model='UNet_Film' / 'UNet_FilmnoAttention' are on the MI355X path "
-                                      "(simple_Unet.py is out of scope, SURVEY.md section 2)")
+        # --- architecture switch (:54-62): every name but the two FiLM ones builds simple_Unet.UNet
+        self.model_name = model
+        self.simple = is_simple_model(model)
+        self.attention = model == "UNet_Film"
         # --- scheduler (:65-70); beta schedule is hard-coded 'linear' there, noise_scheduler_type unused
         self.noise_scheduler = DDPMScheduler(num_train_timesteps=self.noise_steps, beta_schedule="linear",
                                              clip_sample=False, prediction_type="epsilon")
         self.cond_dim = observation_dim * obs_horizon
         if state_dict is None:   # random-init, like constructing the reference module without a checkpoint
-            state_dict = random_state_dict(self.cond_dim, seed=weight_seed, attention=self.attention)
+            state_dict = random_state_dict(self.cond_dim, seed=weight_seed, attention=self.attention,
+                                           model=model, noise_steps=self.noise_steps)
         self.noise_estimator = NoiseEstimator(self, state_dict)
         # the reference loads a private autoencoder checkpoint here (:84-88).  Given that encoder's tensors
         # (vision_encoder_state_dict: keys 0.weight .. 7.bias, as in the diffusion checkpoint's 'vision_encoder.*'), the
@@ -126,9 +130,10 @@ class Diffusion_DDPM:
             pass                                   # a name (e.g. 'resnet18') in the yaml is not a callable: ignored
         ctor.update(kwargs)
         sd, other = load_checkpoint_state_dict(str(checkpoint_path))
-        attention = ctor.get("model", "UNet") != "UNet_FilmnoAttention"
+        model = ctor.get("model", "UNet")            # (no key: the constructor's default, simple_Unet.UNet)
+        attention = model != "UNet_FilmnoAttention"
         cond_dim = int(ctor.get("observation_dim", 2)) * int(ctor.get("obs_horizon", 10))
-        check_state_dict(sd, cond_dim, attention=attention)
+        check_state_dict(sd, cond_dim, attention=attention, model=model, noise_steps=int(ctor.get("noise_steps", 1000)))
         if "vision_encoder_state_dict" not in ctor and any(k.startswith("vision_encoder.") for k in other):
             from .vision import encoder_state_dict_from
             from .weights import safe_load_state_dict
@@ -145,14 +150,20 @@ class Diffusion_DDPM:
     # ------------------------------------------------------------------------------------------
     def _engine_for(self, batch: int, H: int, D: int, pin: bool = False) -> SpdmEngine:
         spec = _as_spec(self.noise_scheduler)
-        T = max(int(spec.config.num_train_timesteps), int(self.noise_steps))
-        key = (H, D, T, batch if pin else 0)       # (a pinned engine is tied to ONE global batch)
+        if self.simple:
+            # simple_Unet.py: the time table is the network's own pos_encoding buffer (noise_steps + 1 rows at construction);
+            # a schedule reaching past it is refused when it is installed, as the reference's pe[t] would fail
+            T = int(self.noise_estimator._sd["pos_encoding.pos_encoding"].shape[0])
+        else:
+            T = max(int(spec.config.num_train_timesteps), int(self.noise_steps))
+        key = ("UNet" if self.simple else self.attention, H, D, T, batch if pin else 0)   # (a pinned engine: ONE global batch)
         if self._engine is None or self._engine_key != key or batch > self._engine.max_batch:
             if self._engine is not None:
                 self._engine.close()
             self._engine = SpdmEngine(H, D, self.cond_dim, max_batch=batch if pin else max(batch, self._max_batch),
                                       device=self._device_index, attention=self.attention,
-                                      num_train_timesteps=T, pin_geometry=pin)
+                                      num_train_timesteps=T, pin_geometry=pin,
+                                      model="UNet" if self.simple else None)
             self._engine.load_state_dict(self.noise_estimator._sd)
             self._engine_key = key
         return self._engine

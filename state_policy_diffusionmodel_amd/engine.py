@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .weights import pack_state_dict, unet_film_param_spec
+from .weights import is_simple_model, pack_state_dict, unet_film_param_spec, unet_simple_param_spec
 
 
 def reference_time_table(T: int, channels: int = 256) -> torch.Tensor:
@@ -33,8 +33,18 @@ def _ptr(t: Optional[torch.Tensor]):
 class SpdmEngine:
     def __init__(self, horizon: int, state_dim: int, cond_dim: int, max_batch: int, device: int = 0,
                  attention: bool = True, time_dim: int = 256, num_train_timesteps: int = 1000,
-                 debug: bool = False, exact_fp32: bool = False, pin_geometry: bool = False):
+                 debug: bool = False, exact_fp32: bool = False, pin_geometry: bool = False,
+                 model: Optional[str] = None):
+        """``model``: None -> UNet_Film (``attention=True``) / UNet_FilmnoAttention (``attention=False``); a model name as
+        Diffusion_DDPM takes it otherwise -- ``'UNet'`` (any non-FiLM name) is models/simple_Unet.py's network, whose
+        time table is the state_dict's own ``pos_encoding.pos_encoding`` buffer: ``num_train_timesteps`` must then be
+        that buffer's row count (noise_steps + 1)."""
         self.lib = _lib.load()
+        self.simple = model is not None and is_simple_model(model)
+        if model is not None and not self.simple:
+            attention = model == "UNet_Film"
+        if self.simple:
+            attention = False
         if not torch.cuda.is_available():
             raise RuntimeError("SpdmEngine needs a visible MI355X (HIP device); there is no CPU fallback")
         self.device = torch.device("cuda", device)
@@ -43,7 +53,8 @@ class SpdmEngine:
         self.num_train_timesteps = int(num_train_timesteps)
         cfg = _lib.SpdmConfig(self.horizon, self.state_dim, self.cond_dim, self.time_dim, int(self.attention),
                               self.max_batch, device, self.num_train_timesteps,
-                              (_lib.SPDM_FLAG_DEBUG_KEEP if debug else 0) | (_lib.SPDM_FLAG_EXACT_FP32 if exact_fp32 else 0))
+                              (_lib.SPDM_FLAG_DEBUG_KEEP if debug else 0) | (_lib.SPDM_FLAG_EXACT_FP32 if exact_fp32 else 0)
+                              | (_lib.SPDM_FLAG_SIMPLE_UNET if self.simple else 0))
         h = ctypes.c_void_p()
         _lib.check(self.lib.spdm_create(ctypes.byref(cfg), ctypes.byref(h)), "spdm_create")
         self._h = h
@@ -55,9 +66,10 @@ class SpdmEngine:
         self._keep = []           # tensors the C side reads asynchronously during a session
         self.n_steps = 0
         self.kind = None
-        tab = reference_time_table(self.num_train_timesteps, self.time_dim).numpy()
-        _lib.check(self.lib.spdm_set_time_table(self._h, tab.ctypes.data_as(ctypes.c_void_p),
-                                                self.num_train_timesteps), "spdm_set_time_table")
+        if not self.simple:        # (simple_Unet.py: the table is the state_dict's pos_encoding buffer, set by load_state_dict)
+            tab = reference_time_table(self.num_train_timesteps, self.time_dim).numpy()
+            _lib.check(self.lib.spdm_set_time_table(self._h, tab.ctypes.data_as(ctypes.c_void_p),
+                                                    self.num_train_timesteps), "spdm_set_time_table")
 
     # -- lifetime -----------------------------------------------------------------------------
     def close(self):
@@ -118,7 +130,10 @@ class SpdmEngine:
         """state_dict of the reference noise predictor (names as ``UNet_Film.state_dict()``;
         a Lightning checkpoint's ``noise_estimator.`` prefix is stripped)."""
         blob, idx = pack_state_dict(sd)
-        want = set(unet_film_param_spec(self.cond_dim, self.time_dim, self.attention).keys())
+        if self.simple:
+            want = set(unet_simple_param_spec(self.cond_dim, self.num_train_timesteps - 1, self.time_dim).keys())
+        else:
+            want = set(unet_film_param_spec(self.cond_dim, self.time_dim, self.attention).keys())
         have = {e.name.decode() for e in idx}
         missing = sorted(want - have)
         if missing:

@@ -95,17 +95,88 @@ def unet_film_param_spec(global_cond_dim: int, time_dim: int = 256,
     return OrderedDict(spec)
 
 
+# ---- the concat-conditioned U-Net of models/simple_Unet.py (Diffusion_DDPM's default model='UNet') -----------------------
+SIMPLE_MODEL = "UNet"
+FILM_MODELS = ("UNet_Film", "UNet_FilmnoAttention")
+
+
+def is_simple_model(model: str) -> bool:
+    """models/diffusion_ddpm.py:53-62: every ``model`` value other than the two FiLM names builds simple_Unet.UNet."""
+    return model not in FILM_MODELS
+
+
+def _simple_double_conv(prefix: str, cin: int, cout: int):
+    # reference: DoubleConvolution.__init__, models/simple_Unet.py:92-104 (one GroupNorm module for both convolutions)
+    return _double_conv(prefix, cin, cout)
+
+
+def _simple_block(prefix: str, cin: int, cout: int, time_dim: int, cond_dim: int):
+    # reference: DownSample / UpSample.__init__, models/simple_Unet.py:132-150, 183-201
+    out = _simple_double_conv(f"{prefix}.doubleConv1", cin, cin)
+    out += _simple_double_conv(f"{prefix}.doubleConv2", cin, cout)
+    out += [
+        (f"{prefix}.emb_layer.1.weight", (cout, time_dim)),
+        (f"{prefix}.emb_layer.1.bias", (cout,)),
+        (f"{prefix}.cond_emb_layer.1.weight", (32, cond_dim)),
+        (f"{prefix}.cond_emb_layer.1.bias", (32,)),
+    ]
+    return out
+
+
+def unet_simple_param_spec(global_cond_dim: int, noise_steps: int = 1000,
+                           time_dim: int = 256) -> "OrderedDict[str, Tuple[int, ...]]":
+    """Ordered name -> shape map of ``UNet(1, 1, noise_steps, time_dim, global_cond_dim).state_dict()``
+    (models/simple_Unet.py:260-280): the positional-encoding buffer first, then input_conv, down1..3, up1..3, outc --
+    79 tensors.  Block widths (input -> output, then 32 conditioning channels appended): 16 -> 32 (+32), 64 -> 128,
+    160 -> 256, up: 288 + 160 -> 128, 160 + 64 -> 64, 96 + 16 -> 32."""
+    spec: List[Tuple[str, Tuple[int, ...]]] = [("pos_encoding.pos_encoding", (noise_steps + 1, time_dim))]
+    spec += _simple_double_conv("input_conv", 1, 16)
+    spec += _simple_block("down1", 16, 32, time_dim, global_cond_dim)
+    spec += _simple_block("down2", 64, 128, time_dim, global_cond_dim)
+    spec += _simple_block("down3", 160, 256, time_dim, global_cond_dim)
+    spec += _simple_block("up1", 288 + 160, 128, time_dim, global_cond_dim)
+    spec += _simple_block("up2", 160 + 64, 64, time_dim, global_cond_dim)
+    spec += _simple_block("up3", 96 + 16, 32, time_dim, global_cond_dim)
+    spec += [("outc.weight", (1, 64, 1, 1)), ("outc.bias", (1,))]
+    return OrderedDict(spec)
+
+
+def simple_pos_encoding(max_len: int, dim: int = 256) -> np.ndarray:
+    """The ``pos_encoding`` buffer of simple_Unet.PositionalEncoding (models/simple_Unet.py:244-251): row p holds
+    sin(p w_0), cos(p w_0), sin(p w_1), ... (interleaved), w_i = exp(-ln(10000) 2i / dim).  Evaluated in fp64 and
+    rounded to fp32, so that the generated state_dict -- and the sha256 the fixtures pin -- is the same on every host
+    (torch's fp32 sin/cos differ by an ulp between CPU instruction sets); it agrees with a table built in torch fp32 to 6e-5, the rounding of the fp32 argument p w_i at p ~ 1000."""
+    freq = np.exp(-math.log(10000.0) * np.arange(0, dim, 2, dtype=np.float64) / dim)
+    arg = np.arange(max_len, dtype=np.float64)[:, None] * freq[None, :]
+    pe = np.empty((max_len, dim), dtype=np.float64)
+    pe[:, 0::2] = np.sin(arg)
+    pe[:, 1::2] = np.cos(arg)
+    return np.ascontiguousarray(pe, dtype=np.float32)
+
+
 def random_state_dict(global_cond_dim: int, seed: int = 0, time_dim: int = 256,
-                      attention: bool = True) -> "OrderedDict[str, np.ndarray]":
+                      attention: bool = True, *, model: str = "UNet_Film",
+                      noise_steps: int = 1000) -> "OrderedDict[str, np.ndarray]":
     """Deterministic random-init weights (numpy PCG64, independent of torch's
     initialisers so the GPU box regenerates the identical 99 MB blob from the
     seed). Scale follows torch's defaults (U(+-1/sqrt(fan_in)) for conv/linear
     weights and biases); norm gains/offsets and the attention biases are made
     non-trivial on purpose so that a kernel which drops one of them fails
-    parity instead of passing on ones/zeros."""
+    parity instead of passing on ones/zeros.
+
+    ``model``: a FiLM name (default; ``attention`` selects between the two) or any other value for the
+    models/simple_Unet.py network (``noise_steps`` sizes its ``pos_encoding`` buffer, which holds the
+    reference's sin/cos table rather than random values)."""
     rng = np.random.default_rng(seed)
     out: "OrderedDict[str, np.ndarray]" = OrderedDict()
-    for name, shape in unet_film_param_spec(global_cond_dim, time_dim, attention).items():
+    if is_simple_model(model):
+        spec = unet_simple_param_spec(global_cond_dim, noise_steps, time_dim)
+    else:
+        spec = unet_film_param_spec(global_cond_dim, time_dim, model == "UNet_Film" and attention)
+    for name, shape in spec.items():
+        if name == "pos_encoding.pos_encoding":
+            out[name] = simple_pos_encoding(shape[0], shape[1])
+            continue
         is_norm = (".norm." in name) or (".ln." in name) or (".ff_self.0." in name)
         if is_norm and name.endswith("weight"):
             w = 1.0 + 0.1 * rng.uniform(-1.0, 1.0, size=shape)
@@ -121,7 +192,7 @@ def random_state_dict(global_cond_dim: int, seed: int = 0, time_dim: int = 256,
                 fan_in = n // 3
             elif name.startswith("outc"):
                 fan_in = 64
-            elif ".cond_encoder." in name:
+            elif ".cond_encoder." in name or ".cond_emb_layer." in name:
                 fan_in = global_cond_dim
             elif ".emb_layer." in name:
                 fan_in = time_dim
@@ -238,17 +309,33 @@ def load_checkpoint_state_dict(checkpoint_path: str, prefix: str = "noise_estima
     return unet, other
 
 
-def check_state_dict(sd, global_cond_dim: int, time_dim: int = 256, attention: bool = True) -> None:
+def check_state_dict(sd, global_cond_dim: int, time_dim: int = 256, attention: bool = True, *,
+                     model: str = "UNet_Film", noise_steps: int = 1000) -> None:
     """Key-for-key / shape-for-shape check against the UNet_Film parameter inventory (the same 162-tensor inventory
-    the golden fixtures pin against the reference module, tools/make_golden.py)."""
-    spec = unet_film_param_spec(global_cond_dim, time_dim=time_dim, attention=attention)
+    the golden fixtures pin against the reference module, tools/make_golden.py) -- or, for ``model='UNet'`` (any
+    non-FiLM name), against simple_Unet.UNet's 79-tensor inventory (tools/make_golden_simple.py).  A state_dict of
+    the other family is named as such in the error."""
+    simple = is_simple_model(model)
+    if simple and "inc.first.weight" in sd:
+        raise ValueError(f"state_dict is a UNet_Film / UNet_FilmnoAttention one (it has 'inc.first.weight'), but "
+                         f"model={model!r} builds models/simple_Unet.py's UNet: pass model='UNet_Film' or "
+                         f"'UNet_FilmnoAttention'")
+    if not simple and "input_conv.first.weight" in sd:
+        raise ValueError(f"state_dict is a models/simple_Unet.py UNet one (it has 'input_conv.first.weight'), but "
+                         f"model={model!r} builds UNet_Film: pass model='UNet'")
+    if simple:
+        spec = unet_simple_param_spec(global_cond_dim, noise_steps=noise_steps, time_dim=time_dim)
+        label = f"UNet(noise_steps={noise_steps}, global_cond_dim={global_cond_dim}, time_dim={time_dim})"
+    else:
+        spec = unet_film_param_spec(global_cond_dim, time_dim=time_dim, attention=attention)
+        label = (f"UNet_Film{'' if attention else '_noAttention'}(global_cond_dim={global_cond_dim}, "
+                 f"time_dim={time_dim})")
     want = dict(spec)
     missing = [k for k in want if k not in sd]
     extra = [k for k in sd if k not in want and not k.endswith("num_batches_tracked")]
     bad = [f"{k}: {tuple(sd[k].shape)} != {want[k]}" for k in want if k in sd and tuple(sd[k].shape) != tuple(want[k])]
     if missing or extra or bad:
-        raise ValueError("state_dict does not match UNet_Film"
-                         f"{'' if attention else '_noAttention'}(global_cond_dim={global_cond_dim}, time_dim={time_dim}): "
+        raise ValueError(f"state_dict does not match {label}: "
                          f"missing {missing[:4]}{'...' if len(missing) > 4 else ''}, unexpected {extra[:4]}"
                          f"{'...' if len(extra) > 4 else ''}, shape mismatches {bad[:4]}")
 
