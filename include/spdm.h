@@ -251,6 +251,42 @@ int  spdm_debug_geometry(int32_t M, int32_t N, int32_t K, int32_t HW, int32_t W,
  * (nn.GELU(), models/Unet_FiLmLayer.py:104). */
 int  spdm_op_gelu(const float* d_x, float* d_y, size_t n, void* stream);
 
+/* Op-level test hook: ONE implicit-GEMM launch of the product (a 3x3 / 3x1 convolution or a Linear layer, with its load
+ * prologue and store epilogue) on caller-supplied device tensors, synchronously.  The launch is built as the plan builds it:
+ * geometry, split-K + combine (on a partial buffer the hook allocates), the split and fragment-order weight copies packed by
+ * the weight loader's own code from the torch-layout host weight, and the kernel-selection switches read from the
+ * environment (SPDM_NO_WIDE, SPDM_NO_SKINNY, ... as spdm_create reads them).  Not on the product path.
+ * Shapes: the output is B x (H x W) rows of N channels; K = input channels per tap; taps 9 (3x3 conv, weight (N, K, 3, 3)),
+ * 3 (3x1 conv of a W == 1 map, the centre column of a (N, K, 3, 3) weight) or 1 (Linear, weight (N, K), H = W = 1).
+ * Statistics buffers are the kernels' raw fp64 partials: [sample][slot][2] = {sum x, sum x^2}, `slots` per sample, slot of
+ * tile (mt, nt) = (mt - first m-tile of the sample) * n_tiles + nt; a Linear's per-row statistics use sample = row.
+ * Invalid combinations (the plan's own guards: fused sources, two-source inputs, K % 32, N % 64, ...) return
+ * SPDM_ERR_INVALID without launching anything. */
+typedef struct {
+    int32_t B, H, W, K, N, taps;
+    int32_t split;                  /* 1: split-fp16 MFMA path, 0: exact fp32 path */
+    int32_t pro;                    /* 0 none, 1 GroupNorm, 2 GroupNorm + GELU, 3 MaxPool2d(2) read-through, 4 upsample + concat */
+    int32_t epi;                    /* 0 GroupNorm statistics, 1 bias, 2 bias + GELU, 3 bias + residual, 4 plain */
+    const float* d_src;  int32_t src_ld;          /* pro 3: the (2H x 2W) map; pro 4: the (H/2 x W/2) map of up_C channels */
+    const float* d_skip; int32_t skip_ld;  int32_t up_C;   /* two-source / pro 4 input: channels [up_C, K) from skip */
+    const float* h_weight;          /* HOST, torch layout */
+    /* pending GroupNorm (or, taps == 1, LayerNorm) of src and of skip: partials as a producer wrote them (d_*_stats NULL: none) */
+    const double* d_src_stats; int32_t src_slots, src_m_tile, src_n_tiles, src_cnorm;   /* cnorm: channels the statistics divide by */
+    const float* d_gamma; const float* d_beta;
+    const double* d_skip_stats; int32_t skip_slots, skip_m_tile, skip_n_tiles, skip_cnorm;
+    const float* d_skip_gamma; const float* d_skip_beta;
+    const float* d_bias; const float* d_resid; int32_t resid_ld;
+    float* d_dst; int32_t dst_ld;
+    double* d_stats; size_t stats_cap;            /* epi 0: output partials, capacity in doubles */
+    double* d_row_stats; size_t row_stats_cap;    /* optional (taps == 1): per-row partials of the stored values */
+    int32_t out[10];                /* as recorded by the launch that ran: {kernel (0 conv_gemm, 1 conv_skinny, 2 conv_reg64,
+                                       3 conv3x3_wide), variant (0 plain, 1 width-2 zero-tap skipping, 2 / 3 width-4 / width-8 row
+                                       classes, 4 pipelined slab hand-over, 5 two chunks per hand-over), m_tile, n_tile of the
+                                       kernel, ksplit, two_source, fused_source, stats slots, stats m_tile, stats n_tiles} */
+} spdm_op_gemm_args;
+
+int  spdm_op_gemm(spdm_op_gemm_args* args);
+
 #ifdef __cplusplus
 }
 #endif

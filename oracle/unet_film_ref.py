@@ -48,12 +48,13 @@ def pad_amounts(h: int, w: int, stride: int = 8):
     return lw, uw, lh, uh
 
 
-def sinusoid_table(t: torch.Tensor, channels: int = 256) -> torch.Tensor:
+def sinusoid_table(t: torch.Tensor, channels: int = 256, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """``UNet_Film.pos_encoding`` (models/Unet_FiLmLayer.py:266-274) applied to
     ``t.unsqueeze(-1).float()`` (``:281``): [sin(t*f) || cos(t*f)] with
-    f_i = 1 / 10000**(2i/channels); halves concatenated, not interleaved."""
-    t = t.reshape(-1, 1).to(torch.float32)
-    inv_freq = 1.0 / (10000 ** (torch.arange(0, channels, 2) / channels))
+    f_i = 1 / 10000**(2i/channels); halves concatenated, not interleaved.
+    ``dtype``: float32 as the reference; float64 for a high-precision evaluation of the same network."""
+    t = t.reshape(-1, 1).to(dtype)
+    inv_freq = 1.0 / (10000 ** (torch.arange(0, channels, 2, dtype=dtype) / channels))
     arg = t.repeat(1, channels // 2) * inv_freq
     return torch.cat([torch.sin(arg), torch.cos(arg)], dim=-1)
 
@@ -140,8 +141,9 @@ def unet_film_forward(sd, x: torch.Tensor, t: torch.Tensor, y: Optional[torch.Te
     Returns eps (B,1,H,D).  ``taps`` (optional dict) receives the named
     intermediates in NCHW for block-level tests."""
     sd = _as_torch(sd)
-    x = x.to(torch.float32)
-    temb = sinusoid_table(t, time_dim)
+    dt = torch.float64 if x.dtype == torch.float64 else torch.float32      # (float64: a high-precision evaluation)
+    x = x.to(dt)
+    temb = sinusoid_table(t, time_dim, dt)
     lw, uw, lh, uh = pad_amounts(x.shape[-2], x.shape[-1], 8)
     xp = F.pad(x, (lw, uw, lh, uh), "constant", 0.0)
 

@@ -19,6 +19,21 @@ SPDM_FLAG_SIMPLE_UNET = 4
 ABI_VERSION = 1
 
 
+class SpdmOpGemmArgs(ctypes.Structure):
+    """spdm_op_gemm_args (include/spdm.h)."""
+    _fields_ = ([(n, c_int32) for n in ("B", "H", "W", "K", "N", "taps", "split", "pro", "epi")] +
+                [("d_src", c_void_p), ("src_ld", c_int32), ("d_skip", c_void_p), ("skip_ld", c_int32), ("up_C", c_int32),
+                 ("h_weight", c_void_p),
+                 ("d_src_stats", c_void_p)] + [(n, c_int32) for n in ("src_slots", "src_m_tile", "src_n_tiles", "src_cnorm")] +
+                [("d_gamma", c_void_p), ("d_beta", c_void_p),
+                 ("d_skip_stats", c_void_p)] + [(n, c_int32) for n in ("skip_slots", "skip_m_tile", "skip_n_tiles", "skip_cnorm")] +
+                [("d_skip_gamma", c_void_p), ("d_skip_beta", c_void_p),
+                 ("d_bias", c_void_p), ("d_resid", c_void_p), ("resid_ld", c_int32),
+                 ("d_dst", c_void_p), ("dst_ld", c_int32),
+                 ("d_stats", c_void_p), ("stats_cap", c_size_t), ("d_row_stats", c_void_p), ("row_stats_cap", c_size_t),
+                 ("out", c_int32 * 10)])
+
+
 class SpdmConfig(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("horizon", "state_dim", "cond_dim", "time_dim", "attention", "max_batch",
                                         "device", "num_train_timesteps", "flags")]
@@ -55,6 +70,7 @@ SYMBOLS = {
     "spdm_encoder_forward": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "spdm_encoder_destroy": (None, [c_void_p]),
     "spdm_op_gelu": (c_int32, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "spdm_op_gemm": (c_int32, [POINTER(SpdmOpGemmArgs)]),
     "spdm_debug_geometry": (c_int32, [c_int32] * 6 + [ctypes.c_uint32, POINTER(c_int32 * 10)]),
     "spdm_bench_gemm": (c_int32, [c_int32] * 12 + [POINTER(c_double)]),   # ms_out[2]: {ms per launch, max|split - fp32|}
 }

@@ -921,6 +921,7 @@ static hipError_t launch_cfg(const GemmArgs& a, const GemmGeom& g, hipStream_t s
     if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return e;
     const int n_mtiles = (a.M + M_T - 1) / M_T;
     const int grid = n_mtiles * g.n_tiles * std::max(a.ksplit, 1);
+    if (a.route) *a.route = GemmRoute{ROUTE_GEMM, W2 ? VAR_W2 : VAR_PLAIN, M_T, N_T};
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NTHR), lds, s, a, g.slots);
     return hipGetLastError();
 }

@@ -376,6 +376,7 @@ hipError_t launch_conv_reg64(const GemmArgs& a, const GemmGeom& g, hipStream_t s
     const size_t lds = R_WBYTES + (128 + R_WAVES * R_MAXT * 2) * sizeof(float);
     auto launch = [&](auto kern) -> hipError_t {
         if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return e;
+        if (a.route) *a.route = GemmRoute{ROUTE_REG, VAR_PLAIN, 64, 64};
         hipLaunchKernelGGL(kern, dim3(grid), dim3(R_NTHR), lds, s, a, g.slots, nw, n_wt);
         return hipGetLastError();
     };

@@ -410,6 +410,7 @@ hipError_t launch_skinny_rc(const GemmArgs& a, const GemmGeom& g, hipStream_t s)
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const int grid = ((a.M + M_T - 1) / M_T) * (a.N / N_T);
     const void* kern = nullptr;
+    if (a.route) *a.route = GemmRoute{ROUTE_SKINNY, VAR_PLAIN, M_T, N_T};
 #define SKINNY_GO(PRO_)                                                                              \
     {                                                                                                \
         auto k_ = conv_skinny_kernel<RT, CT, PRO_>;                                                  \

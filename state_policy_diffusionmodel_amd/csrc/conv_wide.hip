@@ -1069,6 +1069,7 @@ hipError_t launch_wide_cfg(const GemmArgs& a, const GemmGeom& g, hipStream_t s) 
     if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return e;
     const int n_mtiles = (a.M + M_T - 1) / M_T;
     if (a.ksplit > 1 && a.K % 64 != 0) return hipErrorInvalidValue;          // split-K walks even chunk ranges
+    if (a.route) *a.route = GemmRoute{ROUTE_WIDE, WP == 4 ? VAR_WP4 : WP == 8 ? VAR_WP8 : W2 ? VAR_W2 : PIPE ? VAR_PIPE : G2 ? VAR_G2 : VAR_PLAIN, M_T, N_T};
     hipLaunchKernelGGL(kern, dim3(n_mtiles * g.n_tiles * std::max(a.ksplit, 1)), dim3(NTHR), lds, s, a, g.slots, NS);
     return hipGetLastError();
 }

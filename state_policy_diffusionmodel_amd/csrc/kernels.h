@@ -82,6 +82,13 @@ int spdm_tune(int idx, int dflt);      // conv_gemm.hip: SPDM_TUNE<idx> (read on
 enum { PRO_NONE = 0, PRO_GN = 1, PRO_GN_GELU = 2, PRO_POOL = 3, PRO_UPCAT = 4 };
 enum { EPI_STATS = 0, EPI_BIAS = 1, EPI_BIAS_GELU = 2, EPI_BIAS_RESID = 3, EPI_PLAIN = 4 };
 
+// The kernel configuration a launch dispatched, recorded by the launch itself when GemmArgs::route is set (spdm_op_gemm).
+enum { ROUTE_GEMM = 0, ROUTE_SKINNY = 1, ROUTE_REG = 2, ROUTE_WIDE = 3 };
+// variant: 0 plain; 1 width-2 zero-tap skipping; 2 / 3 width-4 / width-8 row classes (conv_wide); 4 pipelined slab hand-over
+// (conv_wide); 5 two chunks per hand-over (conv_wide, SPDM_G2)
+enum { VAR_PLAIN = 0, VAR_W2 = 1, VAR_WP4 = 2, VAR_WP8 = 3, VAR_PIPE = 4, VAR_G2 = 5 };
+struct GemmRoute { int kernel, variant, m_tile, n_tile; };
+
 struct GemmArgs {
     const float* src;  int src_ld;     // [M][src_ld], K valid channels
     const float* wgt;                  // [taps][N][K]  (k contiguous); split: per 32-k chunk [32 fp16 hi | 32 fp16 lo]
@@ -112,6 +119,7 @@ struct GemmArgs {
     unsigned sw;                       // kernel-selection switches (SW_*) of the owning handle
     int debug;                         // ablation knobs for spdm_bench_gemm only (0 in the product path)
     unsigned long long* stamps;        // DBG_STAMP: [2][128] s_memtime stamps of one workgroup (diagnostic builds of the bench)
+    GemmRoute* route;                  // optional (host): the launch records the configuration it dispatched (spdm_op_gemm; null in the plan)
 };
 enum { DBG_NO_MFMA = 1, DBG_NO_WLOAD = 2, DBG_NO_GELU = 4, DBG_NO_STORE = 8, DBG_NO_ALOAD = 16, DBG_PP = 64, DBG_STAMP = 128 };
 

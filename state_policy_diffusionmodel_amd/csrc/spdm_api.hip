@@ -534,10 +534,7 @@ struct Loader {
     }
     // (Cout,Cin,3,3) -> [taps][Cout][Cin]; taps == 3 keeps only the centre column (W == 1 levels, where
     // the left/right taps only ever see zero padding)
-    ConvW conv(const std::string& name, int cout, int cin, int taps) {
-        ConvW c;
-        const float* src = find(name, {cout, cin, 3, 3});
-        if (!src) return c;
+    static std::vector<float> conv_taps(const float* src, int cout, int cin, int taps) {
         std::vector<float> v((size_t)taps * cout * cin);
         for (int t = 0; t < taps; ++t) {
             const int kh = (taps == 9) ? t / 3 : t, kw = (taps == 9) ? t % 3 : 1;
@@ -545,6 +542,13 @@ struct Loader {
                 for (int i = 0; i < cin; ++i)
                     v[((size_t)t * cout + o) * cin + i] = src[(((size_t)o * cin + i) * 3 + kh) * 3 + kw];
         }
+        return v;
+    }
+    ConvW conv(const std::string& name, int cout, int cin, int taps) {
+        ConvW c;
+        const float* src = find(name, {cout, cin, 3, 3});
+        if (!src) return c;
+        const std::vector<float> v = conv_taps(src, cout, cin, taps);
         c.w = upload(v);
         c.ws = (cin % 32 == 0) ? upload_split(v, cin, name) : nullptr;
         if (c.ws && cout % 64 == 0) c.wf = upload(frag_order_weights(split_format(v), taps, cout, cin));
@@ -1958,12 +1962,13 @@ extern "C" int spdm_bench_gemm(int32_t device, int32_t B, int32_t H, int32_t W, 
     HIP_TRY(hipMalloc((void**)&st_out2, (size_t)B * g2.slots * 2 * 8));
     HIP_TRY(hipMemset(st_out2, 0, (size_t)B * g2.slots * 2 * 8));
     {   // deterministic pseudo-random fill (values ~U(-1,1)); split weights are packed as at load time
-        std::vector<float> hsrc(nsrc), hw(nw), hgb((size_t)(Cin + Cout) * 2);
+        std::vector<float> hsrc(nsrc), hw(nw), hgb((size_t)(Cin + Cout) * 2), hres(ndst);
         unsigned x = 12345u;
         auto rnd = [&]() { x = x * 1664525u + 1013904223u; return ((x >> 8) * (1.0f / 8388608.0f)) - 1.0f; };
         for (auto& v : hsrc) v = rnd();
         for (auto& v : hw) v = rnd() * 0.05f;
         for (auto& v : hgb) v = 1.0f + 0.1f * rnd();
+        for (auto& v : hres) v = rnd();           // a non-zero residual: EPI_BIAS_RESID adds something
         HIP_TRY(hipMemcpy(wgt32, hw.data(), nw * 4, hipMemcpyHostToDevice));
         if (split) {
             std::vector<float> out(nw);
@@ -1989,7 +1994,7 @@ extern "C" int spdm_bench_gemm(int32_t device, int32_t B, int32_t H, int32_t W, 
         HIP_TRY(hipMemcpy(wgt, hw.data(), nw * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(gb, hgb.data(), hgb.size() * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(st_in, hst.data(), hst.size() * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(resid, 0, ndst * 4));
+        HIP_TRY(hipMemcpy(resid, hres.data(), ndst * 4, hipMemcpyHostToDevice));
     }
     GemmArgs a{};
     a.sw = sw;
@@ -2189,5 +2194,133 @@ extern "C" int spdm_op_gelu(const float* d_x, float* d_y, size_t n, void* stream
     if (!d_x || !d_y || n == 0) return fail(SPDM_ERR_INVALID, "bad argument");
     HIP_TRY(launch_gelu(d_x, d_y, n, (hipStream_t)stream));
     if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));
+    return SPDM_OK;
+}
+
+// op-level test hook: one launch_gemm exactly as the plan builds it, on the caller's tensors (include/spdm.h)
+extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {
+    if (!p) return fail(SPDM_ERR_INVALID, "op_gemm: null argument");
+    spdm_op_gemm_args& q = *p;
+    for (int i = 0; i < 10; ++i) q.out[i] = -1;
+    const int HW = q.H * q.W;
+    if (q.B <= 0 || q.H <= 0 || q.W <= 0 || q.K <= 0 || q.N <= 0) return fail(SPDM_ERR_INVALID, "op_gemm: empty shape");
+    if (!(q.taps == 9 || q.taps == 3 || q.taps == 1)) return fail(SPDM_ERR_INVALID, "op_gemm: taps must be 9, 3 or 1");
+    if (q.taps == 3 && q.W != 1) return fail(SPDM_ERR_INVALID, "op_gemm: 3-tap convolutions need W == 1");
+    if (q.taps == 1 && HW != 1) return fail(SPDM_ERR_INVALID, "op_gemm: a Linear layer has H == W == 1 (B = rows)");
+    if (q.taps != 1 && q.W > 8) return fail(SPDM_ERR_INVALID, "op_gemm: maps wider than 8");
+    if (q.K % 32 != 0 || q.N % 64 != 0) return fail(SPDM_ERR_INVALID, "op_gemm: K %% 32 == 0 and N %% 64 == 0 required (K %d, N %d)", q.K, q.N);
+    if (q.pro < PRO_NONE || q.pro > PRO_UPCAT || q.epi < EPI_STATS || q.epi > EPI_PLAIN) return fail(SPDM_ERR_INVALID, "op_gemm: unknown pro / epi");
+    if (!q.d_src || !q.d_dst || !q.h_weight) return fail(SPDM_ERR_INVALID, "op_gemm: src, dst and weight are required");
+    if (q.dst_ld < q.N || q.dst_ld % 4 || q.src_ld % 4) return fail(SPDM_ERR_INVALID, "op_gemm: bad leading dimension");
+    const bool fused = q.pro == PRO_POOL || q.pro == PRO_UPCAT, two = !fused && q.d_skip != nullptr;
+    if (q.src_ld < ((fused && q.pro == PRO_UPCAT) || two ? q.up_C : q.K)) return fail(SPDM_ERR_INVALID, "op_gemm: src_ld too small");
+    if ((q.d_skip != nullptr) != (q.pro == PRO_UPCAT || two)) return fail(SPDM_ERR_INVALID, "op_gemm: skip is the second source of pro 4 / a two-source input only");
+    if (q.d_skip && (q.up_C <= 0 || q.up_C >= q.K || q.skip_ld % 4 || q.skip_ld < q.K - q.up_C)) return fail(SPDM_ERR_INVALID, "op_gemm: bad up_C / skip_ld");
+    if (two && (q.pro != PRO_NONE || q.d_src_stats)) return fail(SPDM_ERR_INVALID, "op_gemm: a two-source input takes its prologue from the skip statistics only");
+    if (q.d_skip_stats && !q.d_skip) return fail(SPDM_ERR_INVALID, "op_gemm: skip statistics without skip");
+    if ((q.pro == PRO_GN || q.pro == PRO_GN_GELU) && !q.d_src_stats) return fail(SPDM_ERR_INVALID, "op_gemm: GroupNorm prologue without statistics");
+    if ((q.d_src_stats && (!q.d_gamma || !q.d_beta || q.src_slots <= 0 || q.src_m_tile <= 0 || q.src_n_tiles <= 0)) ||
+        (q.d_skip_stats && (!q.d_skip_gamma || !q.d_skip_beta || q.skip_slots <= 0 || q.skip_m_tile <= 0 || q.skip_n_tiles <= 0)))
+        return fail(SPDM_ERR_INVALID, "op_gemm: pending GroupNorm needs gamma, beta and the partials' geometry");
+    if (q.d_src_stats && q.pro == PRO_NONE) return fail(SPDM_ERR_INVALID, "op_gemm: src statistics given with pro 0");
+    if (q.epi != EPI_STATS && q.epi != EPI_PLAIN && !q.d_bias) return fail(SPDM_ERR_INVALID, "op_gemm: bias epilogue without bias");
+    if (q.epi == EPI_BIAS_RESID && (!q.d_resid || q.resid_ld < q.N || q.resid_ld % 4)) return fail(SPDM_ERR_INVALID, "op_gemm: bad residual");
+    if (q.d_row_stats && q.taps != 1) return fail(SPDM_ERR_INVALID, "op_gemm: row statistics are a Linear layer's output");
+    const int M = q.B * HW;
+    const int src_rows = q.pro == PRO_POOL ? 4 * HW : q.pro == PRO_UPCAT ? HW / 4 : HW;      // rows per sample of src
+    if (q.pro == PRO_UPCAT && ((q.H & 1) || (q.W & 1))) return fail(SPDM_ERR_INVALID, "op_gemm: upsample read-through needs an even map");
+    const std::vector<float> w32 = q.taps == 1 ? std::vector<float>(q.h_weight, q.h_weight + (size_t)q.N * q.K)
+                                               : Loader::conv_taps(q.h_weight, q.N, q.K, q.taps);
+    if (q.split && !Loader::split_range_ok(w32)) return fail(SPDM_ERR_INVALID, "op_gemm: weights outside the split format's range (the loader keeps such a layer on the exact path)");
+    const unsigned sw = switches_from_env();
+    GemmArgs a{};
+    a.sw = sw;
+    a.split = q.split ? 1 : 0;
+    a.src = q.d_src; a.src_ld = q.src_ld; a.dst = q.d_dst; a.dst_ld = q.dst_ld;
+    a.M = M; a.K = q.K; a.N = q.N; a.taps = q.taps; a.geom_M = M;
+    a.H = q.H; a.W = q.W; a.HW = HW;
+    a.pro = q.pro;
+    auto ref = [](const double* st, int slots, int m_tile, int n_tiles, int rows, int cnorm) {
+        StatsRef r{};
+        r.p = st; r.slots = slots; r.m_tile = m_tile; r.n_tiles = n_tiles; r.HW = rows; r.inv_count = 1.0 / ((double)cnorm * rows);
+        return r;
+    };
+    const int src_c = (q.pro == PRO_UPCAT || two) ? q.up_C : q.K;
+    if (q.d_src_stats) {
+        a.pro_stats = ref(q.d_src_stats, q.src_slots, q.src_m_tile, q.src_n_tiles, src_rows, q.src_cnorm > 0 ? q.src_cnorm : src_c);
+        a.pro_gamma = q.d_gamma; a.pro_beta = q.d_beta;
+    }
+    if (q.d_skip) { a.up_C = q.up_C; a.skip = q.d_skip; a.skip_ld = q.skip_ld; }
+    if (q.d_skip_stats) {
+        const StatsRef sr = ref(q.d_skip_stats, q.skip_slots, q.skip_m_tile, q.skip_n_tiles, HW, q.skip_cnorm > 0 ? q.skip_cnorm : q.K - q.up_C);
+        if (two) { a.pro = PRO_GN; a.pro_stats = sr; a.pro_gamma = q.d_skip_gamma; a.pro_beta = q.d_skip_beta; }   // (Ctx::conv_two)
+        else { a.skip_stats = sr; a.skip_gamma = q.d_skip_gamma; a.skip_beta = q.d_skip_beta; }
+    }
+    a.epi = q.epi; a.bias = q.d_bias; a.resid = q.d_resid; a.resid_ld = q.resid_ld;
+    a.row_stats = q.d_row_stats;
+    // as the plan: a split-precision convolution may split K unless switched off (the handle then holds no partial buffer)
+    const bool may_partial = a.split && q.taps != 1 && q.epi == EPI_STATS && !(sw & SW_NO_SPLITK);
+    const GemmGeom g = gemm_geometry(M, q.N, q.K, HW, q.W, q.taps, a.split, sw, may_partial);
+    if (q.epi == EPI_STATS && (!q.d_stats || q.stats_cap < (size_t)q.B * g.slots * 2))
+        return fail(SPDM_ERR_INVALID, "op_gemm: statistics buffer needs %zu doubles", (size_t)q.B * g.slots * 2);
+    if (q.d_row_stats && q.row_stats_cap < (size_t)M * g.n_tiles * 2)
+        return fail(SPDM_ERR_INVALID, "op_gemm: row statistics buffer needs %zu doubles", (size_t)M * g.n_tiles * 2);
+    if (g.ksplit > 1 && (size_t)g.ksplit * M * q.N * sizeof(float) > SPLITK_WORKSPACE_BYTES)
+        return fail(SPDM_ERR_INVALID, "op_gemm: split-K slabs exceed the workspace");
+    std::vector<void*> owned;
+    auto release = [&]() { for (void* v : owned) (void)hipFree(v); };
+    auto upload = [&](const void* h, size_t bytes, void** d) -> hipError_t {
+        hipError_t e = hipMalloc(d, std::max<size_t>(bytes, 256));
+        if (e != hipSuccess) return e;
+        owned.push_back(*d);
+        return h ? hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice) : hipSuccess;
+    };
+    hipError_t e = hipSuccess;
+    void* dw = nullptr;
+    void* dwf = nullptr;
+    if (a.split) {
+        const std::vector<float> ws = Loader::split_format(w32);
+        e = upload(ws.data(), ws.size() * 4, &dw);
+        if (e == hipSuccess && q.taps != 1) {       // Loader::conv's fragment-order copy (Cout % 64 == 0 here)
+            const std::vector<float> wf = frag_order_weights(ws, q.taps, q.N, q.K);
+            e = upload(wf.data(), wf.size() * 4, &dwf);
+        }
+    } else {
+        e = upload(w32.data(), w32.size() * 4, &dw);
+    }
+    a.wgt = (const float*)dw; a.wgt_frag = (const float*)dwf;
+    if (e == hipSuccess && may_partial) {
+        void* dp = nullptr;
+        e = upload(nullptr, g.ksplit > 1 ? (size_t)g.ksplit * M * q.N * sizeof(float) : 0, &dp);
+        a.partial = (float*)dp;
+    }
+    if (e != hipSuccess) { release(); return fail(SPDM_ERR_HIP, "op_gemm: %s", hipGetErrorString(e)); }
+    a.epi_stats = q.epi == EPI_STATS ? q.d_stats : nullptr;
+    if (fused && !gemm_takes_fused_source(a)) {
+        release();
+        return fail(SPDM_ERR_INVALID, "op_gemm: this launch does not take a fused source (the plan materialises it)");
+    }
+    if (two && !gemm_takes_two_sources(a)) {
+        release();
+        return fail(SPDM_ERR_INVALID, "op_gemm: this launch does not take a two-source input (the plan concatenates)");
+    }
+    GemmRoute r{-1, -1, -1, -1};
+    a.route = &r;                 // the launch records what it dispatched
+    // unwritten partials read as NaN
+    if (q.epi == EPI_STATS) e = hipMemset(q.d_stats, 0xff, (size_t)q.B * g.slots * 2 * sizeof(double));
+    if (e == hipSuccess && q.d_row_stats) e = hipMemset(q.d_row_stats, 0xff, (size_t)M * g.n_tiles * 2 * sizeof(double));
+    if (e != hipSuccess) { release(); return fail(SPDM_ERR_HIP, "op_gemm: %s", hipGetErrorString(e)); }
+    const hipError_t el = launch_gemm(a, nullptr);
+    // (the split-K main kernel may have been launched before the combine reported an error: always drain the device first)
+    const hipError_t es = hipDeviceSynchronize();
+    release();
+    if (el != hipSuccess)
+        return fail(el == hipErrorInvalidValue && r.kernel < 0 ? SPDM_ERR_INVALID : SPDM_ERR_HIP,
+                    "op_gemm: launch_gemm failed (%s) %s; device: %s", hipGetErrorString(el),
+                    r.kernel < 0 ? "before any kernel was dispatched (a host-side shape contract)" : "after a kernel was dispatched",
+                    hipGetErrorString(es));
+    if (es != hipSuccess) return fail(SPDM_ERR_HIP, "op_gemm: %s", hipGetErrorString(es));
+    q.out[0] = r.kernel; q.out[1] = r.variant; q.out[2] = r.m_tile; q.out[3] = r.n_tile; q.out[4] = g.ksplit;
+    q.out[5] = two ? 1 : 0; q.out[6] = fused ? 1 : 0; q.out[7] = g.slots; q.out[8] = g.st_m_tile; q.out[9] = g.st_n_tiles;
     return SPDM_OK;
 }

@@ -73,8 +73,9 @@ def simple_unet_forward(sd, x, t, y):
     counts only match with conditioning)."""
     if y is None:
         raise ValueError("simple_Unet.UNet needs its conditioning y")
-    x = torch.as_tensor(x, dtype=torch.float32)
-    y = torch.as_tensor(y, dtype=torch.float32)
+    dt = torch.float64 if torch.as_tensor(x).dtype == torch.float64 else torch.float32   # (float64: high-precision evaluation)
+    x = torch.as_tensor(x, dtype=dt)
+    y = torch.as_tensor(y, dtype=dt)
     t = torch.as_tensor(t, dtype=torch.int64).reshape(-1)
     xp, pads = pad_to_8(x)
     pe_t = _t(sd, "pos_encoding.pos_encoding")[t]                  # (1|B, time_dim)

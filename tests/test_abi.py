@@ -38,6 +38,9 @@ def test_structs_match_header():
     assert ctypes.sizeof(_lib.SpdmConfig) == 9 * 4
     from state_policy_diffusionmodel_amd.weights import NAME_MAX, TensorIndex
     assert NAME_MAX == 64 and ctypes.sizeof(TensorIndex) == 64 + 8 + 8 + 4 + 16 + 4  # + tail padding to 8
+    # spdm_op_gemm_args: 22 int32 fields and 16 pointers / sizes (LP64) in declaration order, out[10] last
+    A = _lib.SpdmOpGemmArgs
+    assert ctypes.sizeof(A) == 272 and A.stats_cap.offset == 208 and A.out.offset == 232
 
 
 def _builtin_tables(lib, kind, T, n):

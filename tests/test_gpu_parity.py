@@ -551,3 +551,102 @@ def test_fused_attention_head_kernel_matches_the_three_launch_path():
             assert np.abs(got - ref).max() <= 5e-6, (H, D, B)
         finally:
             eng.close()
+
+
+def _widened(sd, seed):
+    """weights(33, 21) with the ranges random_state_dict never draws (its fixtures' weights_sha256 stays put): GroupNorm
+    gains U(-1.5, 1.5) with every 7th exactly zero, offsets U(-0.5, 0.5), the FiLM cond_encoder x 3."""
+    g = torch.Generator().manual_seed(seed)
+    out = {}
+    for k, v in sd.items():
+        v = torch.as_tensor(np.array(v)).clone()
+        if ".norm.weight" in k:
+            v = torch.rand(v.shape, generator=g) * 3.0 - 1.5
+            v[::7] = 0.0
+        elif ".norm.bias" in k:
+            v = torch.rand(v.shape, generator=g) - 0.5
+        elif ".cond_encoder." in k:
+            v = v * 3.0
+        out[k] = v.float()
+    return out
+
+
+def _route(M, N, K, HW, W, taps=9):
+    """{m_tile, n_tile, kernel} the plan's geometry gives a statistics-epilogue convolution (spdm_debug_geometry)."""
+    import ctypes
+    from state_policy_diffusionmodel_amd import _lib
+    out = (ctypes.c_int32 * 10)()
+    _lib.check(_lib.load().spdm_debug_geometry(M, N, K, HW, W, taps, 0, out), "spdm_debug_geometry")
+    return dict(m_tile=out[0], n_tile=out[1], skinny=out[5] & 1, reg=(out[5] >> 1) & 1)
+
+
+def _assert_resampling_routes(B, H, blocks):
+    """B = 2: the first convolutions of the Down / UpSample blocks run on conv_skinny, the kernel that reads MaxPool /
+    upsample + concat through (fused sources); B = 512: the UpSample ones are 128-wide conv_wide tilings, the kernel that takes
+    the upsampled tensor and the skip as two sources.  blocks: (level, K, N, up) of those convolutions."""
+    for level, K, N, up in blocks:
+        h, w = H >> level, 8 >> level
+        r = _route(B * h * w, N, K, h * w, w, 9 if w > 1 else 3)
+        if B <= 4:
+            assert r["skinny"], (B, level, K, N, r)
+        elif up:
+            assert not r["skinny"] and not r["reg"] and r["n_tile"] == 128 and r["m_tile"] in (128, 256), (B, level, K, N, r)
+
+
+# B = 2: the Down / UpSample input convolutions read through MaxPool / upsample+concat on conv_skinny (fused sources);
+# B = 512: the UpSample input convolutions take the upsampled tensor and the skip as two sources on conv3x3_wide_kernel.
+# Measured max |eps - oracle64| / eps scale: 3.3e-7 (B 2, attention) 8.7e-7 (512, attention) 8.5e-7 (2) 1.2e-6 (512).
+@pytest.mark.parametrize("B", [2, 512])
+@pytest.mark.parametrize("attention", [True, False])
+def test_widened_weights_against_float64_oracle(B, attention):
+    """The HIP U-Net with gains that are negative and zero, larger offsets and a stronger FiLM against the oracle in
+    float64; tolerance relative to the scale of eps."""
+    H, D, obs_h, obs_dim = 32, 3, 3, 11
+    # Down: MaxPool -> down{1,2,3}.doubleConv1.first (C -> C); Up: cat -> up{1,2,3}.doubleConv1.first (C -> C)
+    _assert_resampling_routes(B, H, [(1, 64, 64, False), (2, 128, 128, False), (2, 512, 512, True), (1, 256, 256, True),
+                                     (0, 128, 128, True)])
+    sd = _widened(weights(obs_h * obs_dim, 21, attention), 5)
+    g = torch.Generator().manual_seed(77 + B)
+    x = torch.randn(B, 1, H, D, generator=g) * 1.5
+    y = torch.randn(B, 1, obs_h, obs_dim, generator=g)
+    t = (torch.arange(B) * 37) % 1000
+    eng = make_engine(H, D, obs_h * obs_dim, B, sd, attention)
+    try:
+        got = eng.unet_forward(x.cuda(), t, y.cuda()).cpu().double()
+    finally:
+        eng.close()
+    idx = [0, 1] if B == 2 else [0, 1, 255, 256, B - 1]
+    sd64 = {k: v.double() for k, v in sd.items()}
+    want = unet_film_forward(sd64, x[idx].double(), t[idx], y[idx].double(), attention=attention)
+    scale = float(want.abs().max())
+    err = float((got[idx] - want).abs().max())
+    print(f"widened B={B} attention={attention}: max |eps - oracle64| = {err:.2e} (eps scale {scale:.2f})")
+    assert err <= 4e-6 * max(scale, 1.0), (err, scale)
+
+
+def test_widened_weights_simple_unet_against_float64_reference():
+    """The same for model='UNet' (simple_Unet.py) against tests/simple_unet_ref.py in float64, at a small and a large batch.
+    Measured max |eps - ref64| / eps scale: 5.9e-7 (B 2), 1.1e-6 (B 512)."""
+    from simple_unet_ref import simple_unet_forward
+    from test_gpu_simple_unet import make_engine as make_simple, weights as simple_weights
+    H, D, obs_h, obs_dim = 16, 3, 2, 4
+    for B in (2, 512):
+        base = simple_weights(obs_h * obs_dim, 0, 1000)
+        sd = {k: torch.as_tensor(np.array(v)) for k, v in base.items()}
+        sd = {**_widened({k: v for k, v in sd.items() if k != "pos_encoding.pos_encoding"}, 6),
+              "pos_encoding.pos_encoding": sd["pos_encoding.pos_encoding"].float()}
+        g = torch.Generator().manual_seed(5 + B)
+        x = torch.randn(B, 1, H, D, generator=g)
+        y = torch.randn(B, 1, obs_h, obs_dim, generator=g)
+        t = (torch.arange(B) * 37) % 1000
+        eng = make_simple(H, D, obs_h * obs_dim, B, sd)
+        try:
+            got = eng.unet_forward(x.cuda(), t, y.cuda()).cpu().double()
+        finally:
+            eng.close()
+        idx = [0, 1] if B == 2 else [0, 255, 256, B - 1]
+        want = simple_unet_forward({k: v.double() for k, v in sd.items()}, x[idx].double(), t[idx], y[idx].double())
+        scale = float(want.abs().max())
+        err = float((got[idx] - want).abs().max())
+        print(f"widened simple UNet B={B}: max |eps - ref64| = {err:.2e} (eps scale {scale:.2f})")
+        assert err <= 4e-6 * max(scale, 1.0), (B, err, scale)
