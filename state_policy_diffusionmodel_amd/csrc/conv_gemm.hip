@@ -855,13 +855,16 @@ GemmGeom gemm_geometry(int M, int N, int K, int HW, int W, int taps, int split, 
     return g;
 }
 
+GemmGeom gemm_geometry(const GemmArgs& a) {
+    return gemm_geometry(a.geom_M > 0 ? a.geom_M : a.M, a.N, a.K, a.HW, a.W, a.taps, a.split, a.sw, a.epi == EPI_STATS && a.partial != nullptr);
+}
+
 // Which launches take a fused source (GemmArgs: PRO_POOL / PRO_UPCAT): the small-grid kernel (conv_skinny.hip) for both modes.
 // The plan (spdm_api.hip) asks before it decides whether to materialise the pooled / concatenated tensor.
 bool gemm_takes_fused_source(const GemmArgs& a) {
     if (!(a.pro == PRO_POOL || a.pro == PRO_UPCAT) || !a.split || a.wgt_frag == nullptr || (a.sw & SW_NO_FUSED_SRC) || a.epi != EPI_STATS) return false;
     if (a.pro == PRO_UPCAT && (a.up_C <= 0 || a.up_C >= a.K || a.up_C % CK != 0 || (a.H & 1) || (a.W & 1))) return false;
-    const GemmGeom g = gemm_geometry(a.geom_M > 0 ? a.geom_M : a.M, a.N, a.K, a.HW, a.W, a.taps, a.split, a.sw, a.epi == EPI_STATS && a.partial != nullptr);
-    return g.skinny != 0;
+    return gemm_geometry(a).skinny != 0;
 }
 
 // Two-source input (GemmArgs::skip with pro = PRO_NONE / PRO_GN: channels [0, up_C) from src, the rest from skip): conv_wide.hip's
@@ -869,7 +872,7 @@ bool gemm_takes_fused_source(const GemmArgs& a) {
 bool gemm_takes_two_sources(const GemmArgs& a0) {
     if (a0.skip == nullptr || !a0.split || a0.wgt_frag == nullptr || (a0.sw & SW_NO_FUSED_SRC) || a0.epi != EPI_STATS) return false;
     GemmArgs a = a0;
-    const GemmGeom g = gemm_geometry(a.geom_M > 0 ? a.geom_M : a.M, a.N, a.K, a.HW, a.W, a.taps, a.split, a.sw, a.epi == EPI_STATS && a.partial != nullptr);
+    const GemmGeom g = gemm_geometry(a);
     if (g.skinny || g.reg || g.m_tile == 512) return false;
     a.ksplit = g.ksplit;
     return conv_wide_supported(a, g);
@@ -896,6 +899,8 @@ static bool uses_wp8(const GemmArgs& a0, const GemmGeom& g) {
     return conv_wide_supported(a, g);
 }
 double gemm_flops(const GemmArgs& a) {
+    // (unlike gemm_geometry(a), asks for the statistics-epilogue geometry without a partial buffer too -- SPDM_NO_SPLITK, the
+    // exact path -- where the launch's tiling can differ: the profiled FLOP count of those runs keeps its present value)
     const GemmGeom g = gemm_geometry(a.geom_M > 0 ? a.geom_M : a.M, a.N, a.K, a.HW, a.W, a.taps, a.split, a.sw, a.epi == EPI_STATS);
     const double taps = uses_w2(a, g) ? 6.0 : uses_wp4(a, g) ? 7.5 : uses_wp8(a, g) ? 8.25 : (double)a.taps;
     return 2.0 * (double)a.M * (double)a.N * (double)a.K * taps;
@@ -931,7 +936,7 @@ static hipError_t launch_gemm_kernel(const GemmArgs& a, const GemmGeom& g, hipSt
 hipError_t launch_gemm(const GemmArgs& a0, hipStream_t s) {
     GemmArgs a = a0;
     a.ksplit = 1;
-    const GemmGeom g = gemm_geometry(a.geom_M > 0 ? a.geom_M : a.M, a.N, a.K, a.HW, a.W, a.taps, a.split, a.sw, a.epi == EPI_STATS && a.partial != nullptr);
+    const GemmGeom g = gemm_geometry(a);
     const bool fused_src = a.pro == PRO_POOL || a.pro == PRO_UPCAT;
     if (fused_src && !g.skinny) return hipErrorInvalidValue;                            // (the plan asks gemm_takes_fused_source first)
     if (!fused_src && a.skip != nullptr && !gemm_takes_two_sources(a)) return hipErrorInvalidValue;   // (... gemm_takes_two_sources)

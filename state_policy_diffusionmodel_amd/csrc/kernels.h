@@ -135,6 +135,8 @@ struct GemmGeom {
 // K = input channels (per tap); ksplit is only ever > 1 for split-precision 3x3 / 3x1 convolutions with the statistics
 // epilogue (the callers that pass stats_epi = true)
 GemmGeom gemm_geometry(int M, int N, int K, int HW, int W, int taps, int split, unsigned sw, bool stats_epi = false);
+// ... of a launch, as launch_gemm chooses it: rows as geom_M says, split-K only with the statistics epilogue and a partial buffer
+GemmGeom gemm_geometry(const GemmArgs& a);
 constexpr size_t SPLITK_WORKSPACE_BYTES = (size_t)48 << 20;     // partial slabs of one launch (handle-owned buffer)
 // rows of one sample a combine workgroup owns (a power-of-two fraction of HW; <= 2048 values = two 16-byte pieces per thread
 // where HW allows: at batch 1 the combine is a handful of workgroups, so each must be short)

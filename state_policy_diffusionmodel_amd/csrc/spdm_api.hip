@@ -927,6 +927,43 @@ extern "C" int spdm_set_schedule_tables(spdm_handle* h, int32_t kind, int32_t n,
 }
 
 // -------------------------------------------------------------------------------------------------
+// The arguments of one implicit-GEMM launch (launch_gemm): the one place where a layer becomes a launch.  The plan's
+// convolutions (Ctx::conv_args) and Linear layers (linear_args), the time-embedding, FiLM and encoder Linears, spdm_bench_gemm
+// and spdm_op_gemm all build their launches here.
+//   M rows of N outputs from K input channels per tap, H x W maps (1 x 1: a Linear layer); geom_M > 0: choose the kernel as for
+//   that many rows (GemmArgs::geom_M); partial: the split-K slabs (null: no split-K).
+//   src: the input (leading dimension src.C) with its pending GroupNorm or LayerNorm (src.st.p null: none) for prologue `pro`.
+//   skip (skip.x null: none): input channels [up_C, K) -- the skip half of PRO_UPCAT, which carries its own pending GroupNorm,
+//   or of a two-source input, whose prologue is the skip's pending GroupNorm (src, the upsampled half, is finished).
+static GemmArgs gemm_args(int M, int geom_M, int H, int W, int K, int N, int taps, int split, unsigned sw, float* partial,
+                          int pro, const AffineSrc& src, int up_C, const AffineSrc& skip, const float* wgt, const float* wgt_frag,
+                          float* dst, int dst_ld, int epi, double* epi_stats, const float* bias = nullptr,
+                          const float* resid = nullptr, int resid_ld = 0, double* row_stats = nullptr) {
+    GemmArgs a{};
+    a.M = M; a.geom_M = geom_M; a.H = H; a.W = W; a.HW = H * W; a.K = K; a.N = N; a.taps = taps;
+    a.split = split; a.sw = sw; a.partial = partial;
+    a.src = src.x; a.src_ld = src.C; a.wgt = wgt; a.wgt_frag = wgt_frag;
+    a.pro = pro;
+    const AffineSrc& pending = (skip.x && pro != PRO_UPCAT) ? skip : src;
+    if (pending.st.p) { a.pro_stats = pending.st; a.pro_gamma = pending.gamma; a.pro_beta = pending.beta; }
+    if (skip.x) {
+        a.up_C = up_C; a.skip = skip.x; a.skip_ld = skip.C;
+        if (pro == PRO_UPCAT && skip.st.p) { a.skip_stats = skip.st; a.skip_gamma = skip.gamma; a.skip_beta = skip.beta; }
+    }
+    a.dst = dst; a.dst_ld = dst_ld;
+    a.epi = epi; a.epi_stats = epi_stats; a.bias = bias; a.resid = resid; a.resid_ld = resid_ld; a.row_stats = row_stats;
+    return a;
+}
+// One Linear layer: y[rows][N] = x[rows][K] @ W^T + b (+GELU | +resid, epi), the LayerNorm pending on x (x.st.p) in the load
+// prologue; on the layer's split copy where the caller runs split precision and the layer has one
+static GemmArgs linear_args(const AffineSrc& x, int rows, int geom_M, const LinW& w, bool split, unsigned sw, int epi, float* y,
+                            const float* resid = nullptr, double* row_stats = nullptr) {
+    const int sp = (split && w.ws) ? 1 : 0;
+    return gemm_args(rows, geom_M, 1, 1, w.in, w.out, 1, sp, sw, nullptr, x.st.p ? PRO_GN : PRO_NONE, x, 0, AffineSrc{},
+                     sp ? w.ws : w.w, nullptr, y, w.out, epi, nullptr, w.b, resid, w.out, row_stats);
+}
+
+// -------------------------------------------------------------------------------------------------
 // plan helpers
 struct Ctx {
     spdm_handle* h;
@@ -1000,44 +1037,55 @@ struct Ctx {
         if (h->arena.keep && !dry) { h->taps[name] = t; h->tapB = B; }
     }
 
-    // one 3x3 conv: reads `in` (finishing its pending GroupNorm, + GELU if asked, in the load
-    // prologue), writes the raw output and its GroupNorm partial sums
-    Value conv(const Value& in, const ConvW& w, int level, bool gelu, const float* gamma, const float* beta) {
+    // the launch of one statistics-epilogue convolution of this plan (out: null while only asking which kernel would take it);
+    // h->d_partial non-null: launch_gemm may split K (small grids)
+    GemmArgs conv_args(const ConvW& w, int level, int split, int pro, const AffineSrc& src, int up_C, const AffineSrc& skip,
+                       const Value* out) const {
+        const int HW = HWl(level);
+        return gemm_args(B * HW, Bg() * HW, Hl(level), Wl(level), w.cin, w.cout, w.taps, split, h->sw, h->d_partial, pro, src, up_C,
+                         skip, split ? w.ws : w.w, split ? w.wf : nullptr, out ? out->t.p : nullptr, w.cout, EPI_STATS,
+                         out ? out->st.p : nullptr);
+    }
+    // workspace of a conv result: the raw output and its GroupNorm partial sums in the statistics layout of g
+    Value conv_out(const ConvW& w, int level, const GemmGeom& g, const float* gamma, const float* beta, int C_norm = 0) {
         Value out;
-        const int HW = HWl(level), M = B * HW;
-        // by shape before the weights are known (the dry run at create); afterwards a tensor outside the split format's
-        // range has no split copy and stays on the exact fp32 kernel (Loader::conv)
-        const int split = (h->split && w.cin % 32 == 0 && (!h->weights_loaded || w.ws)) ? 1 : 0;
-        const GemmGeom g = gemm_geometry(Bg() * HW, w.cout, w.cin, HW, Wl(level), w.taps, split, h->sw, /*stats_epi=*/h->d_partial != nullptr);
         out.t = talloc(w.cout, level);
-        out.st = salloc(HW, w.cout, g.st_m_tile, g.st_n_tiles, w.cnorm);
+        out.st = salloc(HWl(level), w.cout, g.st_m_tile, g.st_n_tiles, C_norm);
         out.gamma = gamma; out.beta = beta;
-        if (err || dry) return out;
-        GemmArgs a{};
-        a.sw = h->sw;
-        a.split = split;
-        a.src = in.t.p; a.src_ld = in.t.C; a.wgt = a.split ? w.ws : w.w; a.dst = out.t.p; a.dst_ld = w.cout;
-        a.wgt_frag = a.split ? w.wf : nullptr;
-        if (a.wgt == nullptr) { if (!err) err = fail(SPDM_ERR_STATE, "plan: conv weights missing"); return out; }
-        a.M = M; a.K = w.cin; a.N = w.cout; a.taps = w.taps; a.geom_M = Bg() * HW;
-        a.H = Hl(level); a.W = Wl(level); a.HW = HW;
-        a.pro = in.pending_gn() ? (gelu ? PRO_GN_GELU : PRO_GN) : PRO_NONE;
-        if (in.pending_gn()) { a.pro_stats = in.st.ref; a.pro_gamma = in.gamma; a.pro_beta = in.beta; }
-        a.epi = EPI_STATS; a.epi_stats = out.st.p;
-        a.partial = h->d_partial;            // non-null: launch_gemm may split K (small grids)
-        if (in.t.C != w.cin) { if (!err) err = fail(SPDM_ERR_INVALID, "plan: conv input has %d channels, weight expects %d", in.t.C, w.cin); return out; }
-        // Profiling (spdm_profile_*): HIP events on the launch stream.  Runs of CONSECUTIVE conv launches (the two
-        // DoubleConvolutions of a block: nothing else is launched in between) share one event pair -- every event
-        // record is a queue barrier that costs the neighbouring kernels their overlap (62 records per step were
-        // worth 0.25 ms), and the class average only needs total time / launches.
-        const bool solo = h->prof && h->prof_open < 0;
+        return out;
+    }
+    // the statistics layout the sizing pass reserves for a convolution reading through a resampling op (conv_fused, conv_two)
+    GemmGeom dry_geometry(const ConvW& w, int level) const {
+        return gemm_geometry(B * HWl(level), w.cout, w.cin, HWl(level), Wl(level), w.taps, (w.cin % 32 == 0) ? 1 : 0, h->sw, /*stats_epi=*/true);
+    }
+    // One implicit-GEMM launch of the plan.  Profiling (spdm_profile_*) times the statistics-epilogue convolutions with HIP events
+    // on the launch stream.  Runs of CONSECUTIVE conv launches (the two DoubleConvolutions of a block: nothing else is launched in
+    // between) share one event pair -- every event record is a queue barrier that costs the neighbouring kernels their overlap
+    // (62 records per step were worth 0.25 ms), and the class average only needs total time / launches.
+    void gemm(const GemmArgs& a, const char* what) {
+        const bool prof = h->prof && a.epi == EPI_STATS;
+        const bool solo = prof && h->prof_open < 0;
         if (solo) prof_begin();
-        if (h->prof && h->prof_open >= 0) {
+        if (prof && h->prof_open >= 0) {
             h->prof_evts[h->prof_open].flops += gemm_flops(a);
             h->prof_evts[h->prof_open].launches += 1;
         }
-        check(launch_gemm(a, s), "conv3x3 implicit GEMM");
+        check(launch_gemm(a, s), what);
         if (solo) prof_end();
+    }
+    // one 3x3 conv: reads `in` (finishing its pending GroupNorm, + GELU if asked, in the load
+    // prologue), writes the raw output and its GroupNorm partial sums
+    Value conv(const Value& in, const ConvW& w, int level, bool gelu, const float* gamma, const float* beta) {
+        // by shape before the weights are known (the dry run at create); afterwards a tensor outside the split format's
+        // range has no split copy and stays on the exact fp32 kernel (Loader::conv)
+        const int split = (h->split && w.cin % 32 == 0 && (!h->weights_loaded || w.ws)) ? 1 : 0;
+        const int pro = in.pending_gn() ? (gelu ? PRO_GN_GELU : PRO_GN) : PRO_NONE;
+        auto args = [&](const Value* out) { return conv_args(w, level, split, pro, asrc(in), 0, AffineSrc{}, out); };
+        Value out = conv_out(w, level, gemm_geometry(args(nullptr)), gamma, beta, w.cnorm);
+        if (err || dry) return out;
+        if ((split ? w.ws : w.w) == nullptr) { err = fail(SPDM_ERR_STATE, "plan: conv weights missing"); return out; }
+        if (in.t.C != w.cin) { err = fail(SPDM_ERR_INVALID, "plan: conv input has %d channels, weight expects %d", in.t.C, w.cin); return out; }
+        gemm(args(&out), "conv3x3 implicit GEMM");
         return out;
     }
     void prof_begin() {
@@ -1078,55 +1126,22 @@ struct Ctx {
     bool conv_fused(int mode, const Value& src0, const Value* skip, const ConvW& w, int level, const float* gamma,
                     const float* beta, Value* out_v) {
         if (err || !h->split || (h->sw & SW_NO_FUSED_SRC) || h->arena.keep || h->d_partial == nullptr) return false;
-        const int HW = HWl(level), M = B * HW;
         if (dry) {
             // sizing pass: the fused / materialised choice of a real run depends on its batch (launch geometry), so the dry runs walk
             // every combination (spdm_handle::dry_fuse_mask) and the slab is sized for the worst
             if (!((h->dry_fuse_mask >> fuse_slot) & 1)) return false;
-            const int split = (w.cin % 32 == 0) ? 1 : 0;
-            const GemmGeom g = gemm_geometry(M, w.cout, w.cin, HW, Wl(level), w.taps, split, h->sw, /*stats_epi=*/true);
-            Value out;
-            out.t = talloc(w.cout, level);
-            out.st = salloc(HW, w.cout, g.st_m_tile, g.st_n_tiles);
-            out.gamma = gamma; out.beta = beta;
-            *out_v = out;
+            *out_v = conv_out(w, level, dry_geometry(w, level), gamma, beta);
             return true;
         }
         if (!h->weights_loaded || !w.ws || !w.wf) return false;
-        GemmArgs a{};
-        a.sw = h->sw;
-        a.split = 1;
-        a.src = src0.t.p; a.src_ld = src0.t.C; a.wgt = w.ws; a.wgt_frag = w.wf; a.dst_ld = w.cout;
-        a.M = M; a.K = w.cin; a.N = w.cout; a.taps = w.taps; a.geom_M = Bg() * HW;
-        a.H = Hl(level); a.W = Wl(level); a.HW = HW;
-        a.pro = mode;
-        if (src0.pending_gn()) { a.pro_stats = src0.st.ref; a.pro_gamma = src0.gamma; a.pro_beta = src0.beta; }
-        if (mode == PRO_UPCAT) {
-            if (!skip || src0.t.C + skip->t.C != w.cin) return false;
-            a.up_C = src0.t.C; a.skip = skip->t.p; a.skip_ld = skip->t.C;
-            if (skip->pending_gn()) { a.skip_stats = skip->st.ref; a.skip_gamma = skip->gamma; a.skip_beta = skip->beta; }
-        } else if (src0.t.C != w.cin) {
-            return false;
-        }
-        a.epi = EPI_STATS;
-        a.partial = h->d_partial;
-        if (!gemm_takes_fused_source(a)) return false;
-        const GemmGeom g = gemm_geometry(a.geom_M, w.cout, w.cin, HW, Wl(level), w.taps, 1, h->sw, /*stats_epi=*/h->d_partial != nullptr);
-        Value out;
-        out.t = talloc(w.cout, level);
-        out.st = salloc(HW, w.cout, g.st_m_tile, g.st_n_tiles);
-        out.gamma = gamma; out.beta = beta;
-        if (err) { *out_v = out; return true; }
-        a.dst = out.t.p; a.epi_stats = out.st.p;
-        const bool solo = h->prof && h->prof_open < 0;
-        if (solo) prof_begin();
-        if (h->prof && h->prof_open >= 0) {
-            h->prof_evts[h->prof_open].flops += gemm_flops(a);
-            h->prof_evts[h->prof_open].launches += 1;
-        }
-        check(launch_gemm(a, s), "conv3x3 implicit GEMM (fused source)");
-        if (solo) prof_end();
-        *out_v = out;
+        const bool upcat = mode == PRO_UPCAT;
+        if (upcat ? (!skip || src0.t.C + skip->t.C != w.cin) : src0.t.C != w.cin) return false;
+        auto args = [&](const Value* out) {
+            return conv_args(w, level, 1, mode, asrc(src0), upcat ? src0.t.C : 0, upcat ? asrc(*skip) : AffineSrc{}, out);
+        };
+        if (!gemm_takes_fused_source(args(nullptr))) return false;
+        *out_v = conv_out(w, level, gemm_geometry(args(nullptr)), gamma, beta);
+        if (!err) gemm(args(out_v), "conv3x3 implicit GEMM (fused source)");
         return true;
     }
     // The first convolution of an UpSample block with a TWO-SOURCE input (conv_wide.hip TWO): channels [0, C_up) from `up2x`, the
@@ -1134,65 +1149,23 @@ struct Ctx {
     // (models/Unet_FiLmLayer.py:218) is never materialised.  Returns false, nothing done, when the launch would not be a
     // two-source configuration.
     bool conv_two(const Tensor& up2x, const Value& skip, const ConvW& w, int level, const float* gamma, const float* beta, Value* out_v) {
-        if (err || !h->split || (h->sw & SW_NO_FUSED_SRC) || h->arena.keep) return false;
-        const int HW = HWl(level), M = B * HW;
-        if (up2x.C + skip.t.C != w.cin) return false;
-        if (dry) {                       // sizing pass (see conv_fused): bit 6 + block of dry_fuse_mask
-            if (!((h->dry_fuse_mask >> (3 + fuse_slot)) & 1)) return false;
-            const GemmGeom g = gemm_geometry(M, w.cout, w.cin, HW, Wl(level), w.taps, (w.cin % 32 == 0) ? 1 : 0, h->sw, /*stats_epi=*/true);
-            Value out;
-            out.t = talloc(w.cout, level);
-            out.st = salloc(HW, w.cout, g.st_m_tile, g.st_n_tiles);
-            out.gamma = gamma; out.beta = beta;
-            *out_v = out;
-            return true;
-        }
-        if (!h->weights_loaded || !w.ws || !w.wf) return false;
-        GemmArgs a{};
-        a.sw = h->sw;
-        a.split = 1;
-        a.src = up2x.p; a.src_ld = up2x.C; a.wgt = w.ws; a.wgt_frag = w.wf; a.dst_ld = w.cout;
-        a.M = M; a.K = w.cin; a.N = w.cout; a.taps = w.taps; a.geom_M = Bg() * HW;
-        a.H = Hl(level); a.W = Wl(level); a.HW = HW;
-        a.up_C = up2x.C; a.skip = skip.t.p; a.skip_ld = skip.t.C;
-        a.pro = skip.pending_gn() ? PRO_GN : PRO_NONE;
-        if (skip.pending_gn()) { a.pro_stats = skip.st.ref; a.pro_gamma = skip.gamma; a.pro_beta = skip.beta; }
-        a.epi = EPI_STATS;
-        a.partial = h->d_partial;
-        if (!gemm_takes_two_sources(a)) return false;
-        const GemmGeom g = gemm_geometry(a.geom_M, w.cout, w.cin, HW, Wl(level), w.taps, 1, h->sw, /*stats_epi=*/h->d_partial != nullptr);
-        Value out;
-        out.t = talloc(w.cout, level);
-        out.st = salloc(HW, w.cout, g.st_m_tile, g.st_n_tiles);
-        out.gamma = gamma; out.beta = beta;
-        *out_v = out;
-        if (err) return true;
-        a.dst = out.t.p; a.epi_stats = out.st.p;
-        const bool solo = h->prof && h->prof_open < 0;
-        if (solo) prof_begin();
-        if (h->prof && h->prof_open >= 0) {
-            h->prof_evts[h->prof_open].flops += gemm_flops(a);
-            h->prof_evts[h->prof_open].launches += 1;
-        }
-        check(launch_gemm(a, s), "conv3x3 implicit GEMM (two-source input)");
-        if (solo) prof_end();
+        if (!conv_two_ok(up2x.C, skip, w, level)) return false;
+        *out_v = conv_out(w, level, dry ? dry_geometry(w, level) : gemm_geometry(two_args(up2x.p, skip, w, level, nullptr)), gamma, beta);
+        if (!err && !dry) gemm(two_args(up2x.p, skip, w, level, out_v), "conv3x3 implicit GEMM (two-source input)");
         return true;
     }
-    // would conv_two take this block?  (asked BEFORE the upsample is launched)
+    // would conv_two take this block?  (asked BEFORE the upsample is launched: C_up channels of it)
     bool conv_two_ok(int C_up, const Value& skip, const ConvW& w, int level) const {
-        if (err || !h->split || (h->sw & SW_NO_FUSED_SRC) || h->arena.keep) return false;
-        if (dry) return C_up + skip.t.C == w.cin && ((h->dry_fuse_mask >> (3 + fuse_slot)) & 1);
-        if (!h->weights_loaded || !w.ws || !w.wf) return false;
-        const int HW = HWl(level);
-        GemmArgs a{};
-        a.sw = h->sw; a.split = 1;
-        a.src = skip.t.p; a.src_ld = C_up; a.wgt = w.ws; a.wgt_frag = w.wf; a.dst_ld = w.cout;     // (src: any non-null pointer; not dereferenced)
-        a.M = B * HW; a.K = w.cin; a.N = w.cout; a.taps = w.taps; a.H = Hl(level); a.W = Wl(level); a.HW = HW;
-        a.geom_M = Bg() * HW;
-        a.up_C = C_up; a.skip = skip.t.p; a.skip_ld = skip.t.C;
-        a.pro = skip.pending_gn() ? PRO_GN : PRO_NONE;
-        a.epi = EPI_STATS; a.partial = h->d_partial;
-        return C_up + skip.t.C == w.cin && gemm_takes_two_sources(a);
+        if (err || !h->split || (h->sw & SW_NO_FUSED_SRC) || h->arena.keep || C_up + skip.t.C != w.cin) return false;
+        if (dry) return (h->dry_fuse_mask >> (3 + fuse_slot)) & 1;       // sizing pass (see conv_fused): bit 6 + block of dry_fuse_mask
+        // (up: any non-null pointer; not dereferenced)
+        return h->weights_loaded && w.ws && w.wf && gemm_takes_two_sources(two_args(skip.t.p, skip, w, level, nullptr));
+    }
+    // conv_two's launch: input channels [0, C_up) from `up` (finished), the rest from the skip connection, whose pending GroupNorm
+    // is the load prologue
+    GemmArgs two_args(const float* up, const Value& skip, const ConvW& w, int level, const Value* out) const {
+        const int C_up = w.cin - skip.t.C;
+        return conv_args(w, level, 1, skip.pending_gn() ? PRO_GN : PRO_NONE, AffineSrc{up, C_up}, C_up, asrc(skip), out);
     }
     // y[rows][N] = x[rows][K] @ W^T + b  (+GELU | +resid)
     // per-token LayerNorm statistics buffer: [rows][n_tiles][2] fp64 (StatsRef with HW = 1: "sample" = row)
@@ -1212,16 +1185,8 @@ struct Ctx {
                 const StatsBuf* ln = nullptr, const float* ln_g = nullptr, const float* ln_b = nullptr,
                 double* row_stats_out = nullptr) {
         if (err || dry) return;
-        GemmArgs a{};
-        a.sw = h->sw;
-        a.split = (h->split && w.ws) ? 1 : 0;
-        a.src = x; a.src_ld = ld; a.wgt = a.split ? w.ws : w.w; a.dst = y; a.dst_ld = w.out;
-        a.M = rows; a.K = w.in; a.N = w.out; a.taps = 1; a.H = 1; a.W = 1; a.HW = 1;
-        a.geom_M = (rows / B) * Bg();
-        a.pro = PRO_NONE; a.epi = epi; a.bias = w.b; a.resid = resid; a.resid_ld = w.out;
-        if (ln) { a.pro = PRO_GN; a.pro_stats = ln->ref; a.pro_gamma = ln_g; a.pro_beta = ln_b; }   // LayerNorm in the load prologue
-        a.row_stats = row_stats_out;
-        check(launch_gemm(a, s), "linear GEMM");
+        const AffineSrc src = ln ? AffineSrc{x, ld, ln->ref, ln_g, ln_b} : AffineSrc{x, ld};    // LayerNorm in the load prologue
+        gemm(linear_args(src, rows, (rows / B) * Bg(), w, h->split, h->sw, epi, y, resid, row_stats_out), "linear GEMM");
     }
     // SelfAttention.forward, models/Unet_FiLmLayer.py:71-82.  Consumes x (and its per-token LayerNorm
     // statistics xs, produced by film_apply), returns the block output.  Both LayerNorms run as the load
@@ -1256,47 +1221,20 @@ struct Ctx {
         const int TMh = 8192 / C;
         const bool head = h->split && sa_tail_supported(C, h->sw) && sa_head_supported(C, L, h->sw) && h->weights_loaded && w.qkv_wf &&
                           (!fs || sa_tail_film_local(C, L)) && ((Bg() * L + TMh - 1) / TMh) >= ((h->sw & SW_SA_HEAD) ? 1 : spdm_tune(16, 2048));
-        if (head) {
-            free(xs);
-            Tensor att1 = ralloc(rows, C);
-            if (!err && !dry)
-                check(launch_sa_head(C, x.p, att1.p, rows, w.qkv_wf, w.in_proj.b, w.ln_g, w.ln_b, abp, L, s, fs), "attention in_proj + core");
-            free(qkv);
-            if (h->split && sa_tail_supported(C, h->sw) && (!h->weights_loaded || w.tail_wf[0])) {
-                Tensor out = talloc(C, level);
+        if (!head) {
+            if (h->split && sa_tail_supported(C, h->sw) && (!h->weights_loaded || w.qkv_wf)) {     // LayerNorm + in_proj in one 64-row kernel (sa_tail.hip)
                 if (!err && !dry)
-                    check(launch_sa_tail(C, att1.p, x.p, out.p, rows, w.tail_wf[0], w.tail_wf[1], w.tail_wf[2], w.out_proj.b, w.ff1.b,
-                                            w.ff2.b, w.ff_ln_g, w.ff_ln_b, abp, L, s, fs), "attention tail");
-                free(att1);
-                free(x);
-                if (ab) free(*ab);
-                return out;
+                    check(launch_sa_qkv(C, x.p, qkv.p, rows, w.qkv_wf, w.in_proj.b, w.ln_g, w.ln_b, abp, L, s, fs), "attention in_proj");
+            } else {
+                linear(x.p, C, rows, w.in_proj, qkv.p, EPI_BIAS, nullptr, &xs, w.ln_g, w.ln_b);
             }
-            // (no fused tail for this block: the GEMM chain below continues from att1)
-            Tensor av = talloc(C, level);
-            const int nt_av1 = gemm_geometry((rows / B) * Bg(), C, C, 1, 1, 1, (h->split && w.out_proj.ws) ? 1 : 0, h->sw).n_tiles;
-            StatsBuf avs = row_stats_alloc(rows, C, nt_av1);
-            linear(att1.p, C, rows, w.out_proj, av.p, EPI_BIAS_RESID, x.p, nullptr, nullptr, nullptr, avs.p);
-            free(att1);
-            free(x);
-            Tensor f1 = ralloc(rows, C);
-            linear(av.p, C, rows, w.ff1, f1.p, EPI_BIAS_GELU, nullptr, &avs, w.ff_ln_g, w.ff_ln_b);
-            free(avs);
-            Tensor out = talloc(C, level);
-            linear(f1.p, C, rows, w.ff2, out.p, EPI_BIAS_RESID, av.p);
-            free(f1);
-            free(av);
-            return out;
-        }
-        if (h->split && sa_tail_supported(C, h->sw) && (!h->weights_loaded || w.qkv_wf)) {     // LayerNorm + in_proj in one 64-row kernel (sa_tail.hip)
-            if (!err && !dry)
-                check(launch_sa_qkv(C, x.p, qkv.p, rows, w.qkv_wf, w.in_proj.b, w.ln_g, w.ln_b, abp, L, s, fs), "attention in_proj");
-        } else {
-            linear(x.p, C, rows, w.in_proj, qkv.p, EPI_BIAS, nullptr, &xs, w.ln_g, w.ln_b);
         }
         free(xs);
         Tensor att = ralloc(rows, C);
-        if (!err && !dry) check(launch_attention_auto(qkv.p, att.p, B, L, C, 4, h->sw, s), "attention core");
+        if (!err && !dry) {
+            if (head) check(launch_sa_head(C, x.p, att.p, rows, w.qkv_wf, w.in_proj.b, w.ln_g, w.ln_b, abp, L, s, fs), "attention in_proj + core");
+            else check(launch_attention_auto(qkv.p, att.p, B, L, C, 4, h->sw, s), "attention core");
+        }
         free(qkv);
         if (h->split && sa_tail_supported(C, h->sw) && (!h->weights_loaded || w.tail_wf[0])) {
             // out_proj + residual + LayerNorm + ff_self + residual in one kernel (sa_tail.hip)
@@ -1371,6 +1309,37 @@ struct Ctx {
         free(v);
         return y;
     }
+    // the block tail (film_tail; tap `name` where it is materialised) and the SelfAttention block sa[blk] after it.  The attention
+    // kernels finish the tail themselves from the raw tensor (film_local), take it as coefficients on load (film_foldable), or
+    // read the materialised tensor.  Consumes v.
+    Tensor film_attention(Value& v, const ResampleW& w, int blk, int level, bool use_cond, const char* name) {
+        const AttnW& sa = h->sa[blk];
+        StatsBuf ys;
+        Tensor y, ab;
+        if (film_local(sa, level)) {
+            const FilmSpec fs = film_spec(v, w, blk, use_cond);
+            y = v.t;
+            v.t.valid = false;
+            y = attention(y, ys, sa, level, nullptr, &fs);
+            free(v);                               // (its statistics: released after the last launch that reads them is enqueued)
+            return y;
+        }
+        if (film_foldable(sa, level)) {
+            y = film_coef(v, w, blk, use_cond, &ab);
+        } else {
+            y = film_tail(v, w, blk, level, use_cond, (h->cfg.attention && !sa_fused(sa, level)) ? &ys : nullptr);
+            tap(name, y);
+        }
+        if (h->cfg.attention) y = attention(y, ys, sa, level, &ab);
+        return y;
+    }
+    // debug runs (arena.keep): the finished tensor of a value with a pending GroupNorm, as tap `name`
+    void tap_gn(const char* name, const Value& v, int level) {
+        if (!h->arena.keep) return;
+        Tensor m = talloc(v.t.C, level);
+        if (!dry && !err) check(launch_gn_apply(asrc(v), m.p, B, HWl(level), s), "gn_apply");
+        tap(name, m);
+    }
     int h_tcount = 1;
     int fuse_slot = 0;     // which resampling op conv_fused is being asked about (dry runs: bit of dry_fuse_mask)
     int adv = -2;          // loop bookkeeping done by conv_in_kernel: -2 none, -1 advance, >= 0 set
@@ -1390,11 +1359,7 @@ static int plan_unet(Ctx& c, const float* x, bool use_cond, Tensor* feat_out) {
                                h->lh, h->lw, h->d_step, h->d_t, h->d_timesteps, h->n_steps, c.adv, c.s, c.Bg()), "conv_in");
     Value x1 = c.conv(v0, h->inc.second, 0, /*gelu=*/true, h->inc.gamma, h->inc.beta);   // x1 = GN(raw), pending
     c.free(v0);
-    if (h->arena.keep) {
-        Tensor m = c.talloc(64, 0);
-        if (!c.dry && !c.err) c.check(launch_gn_apply(c.asrc(x1), m.p, B, c.HWl(0), c.s), "gn_apply");
-        c.tap("x1", m);
-    }
+    c.tap_gn("x1", x1, 0);
 
     // ---- encoder: down1..3 (+ sa1..3) ----
     Value skips[3];            // x1 (pending GN), x2, x3 (materialised)
@@ -1421,24 +1386,7 @@ static int plan_unet(Ctx& c, const float* x, bool use_cond, Tensor* feat_out) {
         }
         Value b2 = c.double_conv(a, h->down[i].dc2, lout);
         c.prof_end();
-        StatsBuf ys;
-        Tensor y, ab;
-        if (c.film_local(h->sa[i], lout)) {           // the attention kernels finish the block tail themselves, from the raw tensor
-            const FilmSpec fs = c.film_spec(b2, h->down[i], i, use_cond);
-            y = b2.t;
-            b2.t.valid = false;
-            y = c.attention(y, ys, h->sa[i], lout, nullptr, &fs);
-            c.free(b2);                               // (its statistics: released after the last launch that reads them is enqueued)
-        } else {
-        if (c.film_foldable(h->sa[i], lout)) {
-            y = c.film_coef(b2, h->down[i], i, use_cond, &ab);
-        } else {
-            y = c.film_tail(b2, h->down[i], i, lout, use_cond,
-                            (h->cfg.attention && !c.sa_fused(h->sa[i], lout)) ? &ys : nullptr);
-            c.tap(dn[i], y);
-        }
-        if (h->cfg.attention) y = c.attention(y, ys, h->sa[i], lout, &ab);
-        }
+        const Tensor y = c.film_attention(b2, h->down[i], i, lout, use_cond, dn[i]);
         c.tap(xn[i], y);
         Value nv;
         nv.t = y;
@@ -1451,11 +1399,7 @@ static int plan_unet(Ctx& c, const float* x, bool use_cond, Tensor* feat_out) {
     Value b2 = c.double_conv(b1, h->bot[1], 3);
     Value x5 = c.double_conv(b2, h->bot[2], 3);         // pending GN
     c.prof_end();
-    if (h->arena.keep) {
-        Tensor m = c.talloc(256, 3);
-        if (!c.dry && !c.err) c.check(launch_gn_apply(c.asrc(x5), m.p, B, c.HWl(3), c.s), "gn_apply");
-        c.tap("x5", m);
-    }
+    c.tap_gn("x5", x5, 3);
     // ---- decoder: up1..3 (+ sa4..6) ----
     static const char* un[3] = {"u1", "u2", "u3"};
     static const char* an[3] = {"a4", "a5", "a6"};
@@ -1496,24 +1440,7 @@ static int plan_unet(Ctx& c, const float* x, bool use_cond, Tensor* feat_out) {
         }
         Value b3 = c.double_conv(a, h->up[i].dc2, lout);
         c.prof_end();
-        StatsBuf ys;
-        Tensor y, ab;
-        if (c.film_local(h->sa[3 + i], lout)) {
-            const FilmSpec fs = c.film_spec(b3, h->up[i], 3 + i, use_cond);
-            y = b3.t;
-            b3.t.valid = false;
-            y = c.attention(y, ys, h->sa[3 + i], lout, nullptr, &fs);
-            c.free(b3);
-        } else {
-        if (c.film_foldable(h->sa[3 + i], lout)) {
-            y = c.film_coef(b3, h->up[i], 3 + i, use_cond, &ab);
-        } else {
-            y = c.film_tail(b3, h->up[i], 3 + i, lout, use_cond,
-                            (h->cfg.attention && !c.sa_fused(h->sa[3 + i], lout)) ? &ys : nullptr);
-            c.tap(un[i], y);
-        }
-        if (h->cfg.attention) y = c.attention(y, ys, h->sa[3 + i], lout, &ab);
-        }
+        const Tensor y = c.film_attention(b3, h->up[i], 3 + i, lout, use_cond, un[i]);
         c.tap(an[i], y);
         Value nv;
         nv.t = y;
@@ -1620,15 +1547,8 @@ static int ensure_temb(spdm_handle* h, hipStream_t s) {
     hipError_t e = hipMemcpyAsync(tmp, h->time_table.data(), sizeof(float) * (size_t)T * dim, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = launch_silu(tmp, h->d_time_silu, (size_t)T * dim, s);
     ResampleW* blocks[6] = {&h->down[0], &h->down[1], &h->down[2], &h->up[0], &h->up[1], &h->up[2]};
-    for (int i = 0; i < 6 && e == hipSuccess; ++i) {
-        GemmArgs a{};
-        a.sw = h->sw;
-        a.split = (h->split && blocks[i]->emb.ws) ? 1 : 0;
-        a.src = h->d_time_silu; a.src_ld = dim; a.wgt = a.split ? blocks[i]->emb.ws : blocks[i]->emb.w; a.dst = blocks[i]->temb_table; a.dst_ld = blocks[i]->emb.out;
-        a.M = T; a.K = dim; a.N = blocks[i]->emb.out; a.taps = 1; a.H = 1; a.W = 1; a.HW = 1;   // (N: cout, padded for simple_Unet.py)
-        a.pro = PRO_NONE; a.epi = EPI_BIAS; a.bias = blocks[i]->emb.b;
-        e = launch_gemm(a, s);
-    }
+    for (int i = 0; i < 6 && e == hipSuccess; ++i)      // (N: cout, padded for simple_Unet.py)
+        e = launch_gemm(linear_args(AffineSrc{h->d_time_silu, dim}, T, 0, blocks[i]->emb, h->split, h->sw, EPI_BIAS, blocks[i]->temb_table), s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(tmp);
     if (e != hipSuccess) return fail(SPDM_ERR_HIP, "time-embedding tables: %s", hipGetErrorString(e));
@@ -1641,36 +1561,21 @@ static int ensure_temb(spdm_handle* h, hipStream_t s) {
 static int compute_film(spdm_handle* h, int B, const float* d_cond, hipStream_t s) {
     h->have_film = false;
     if (!d_cond || h->cfg.cond_dim <= 0) return SPDM_OK;
+    const AffineSrc condm{h->d_condm, h->film_kp};
+    const int geom_M = (h->sw & SW_PIN_GEOMETRY) ? h->cfg.max_batch : 0;
     if (h->simple) {
         // models/simple_Unet.py: the six cond_emb_layer projections Linear(SiLU(flatten(cond))) (:146-150, :197-201) in ONE
         // GEMM over the stacked weights -> d_cemb [B][6 x 32]; step-invariant, hoisted out of the denoise loop like FiLM
         hipError_t e = launch_silu_pad(d_cond, h->d_condm, B, h->cfg.cond_dim, h->film_kp, s);
-        if (e == hipSuccess) {
-            GemmArgs a{};
-            a.sw = h->sw;
-            a.split = (h->split && h->cemb.ws) ? 1 : 0;
-            a.src = h->d_condm; a.src_ld = h->film_kp; a.wgt = a.split ? h->cemb.ws : h->cemb.w; a.dst = h->d_cemb; a.dst_ld = h->cemb.out;
-            a.M = B; a.K = h->film_kp; a.N = h->cemb.out; a.taps = 1; a.H = 1; a.W = 1; a.HW = 1;
-            a.geom_M = (h->sw & SW_PIN_GEOMETRY) ? h->cfg.max_batch : 0;
-            a.pro = PRO_NONE; a.epi = EPI_BIAS; a.bias = h->cemb.b;
-            e = launch_gemm(a, s);
-        }
+        if (e == hipSuccess) e = launch_gemm(linear_args(condm, B, geom_M, h->cemb, h->split, h->sw, EPI_BIAS, h->d_cemb), s);
         if (e != hipSuccess) return fail(SPDM_ERR_HIP, "conditioning projections: %s", hipGetErrorString(e));
         h->have_film = true;
         return SPDM_OK;
     }
     hipError_t e = launch_mish_pad(d_cond, h->d_condm, B, h->cfg.cond_dim, h->film_kp, s);
     ResampleW* blocks[6] = {&h->down[0], &h->down[1], &h->down[2], &h->up[0], &h->up[1], &h->up[2]};
-    for (int i = 0; i < 6 && e == hipSuccess; ++i) {
-        GemmArgs a{};
-        a.sw = h->sw;
-        a.split = (h->split && blocks[i]->film.ws) ? 1 : 0;
-        a.src = h->d_condm; a.src_ld = h->film_kp; a.wgt = a.split ? blocks[i]->film.ws : blocks[i]->film.w; a.dst = h->d_film[i]; a.dst_ld = 2 * blocks[i]->cout;
-        a.M = B; a.K = h->film_kp; a.N = 2 * blocks[i]->cout; a.taps = 1; a.H = 1; a.W = 1; a.HW = 1;
-        a.geom_M = (h->sw & SW_PIN_GEOMETRY) ? h->cfg.max_batch : 0;
-        a.pro = PRO_NONE; a.epi = EPI_BIAS; a.bias = blocks[i]->film.b;
-        e = launch_gemm(a, s);
-    }
+    for (int i = 0; i < 6 && e == hipSuccess; ++i)
+        e = launch_gemm(linear_args(condm, B, geom_M, blocks[i]->film, h->split, h->sw, EPI_BIAS, h->d_film[i]), s);
     if (e != hipSuccess) return fail(SPDM_ERR_HIP, "FiLM projections: %s", hipGetErrorString(e));
     h->have_film = true;
     return SPDM_OK;
@@ -1971,17 +1876,7 @@ extern "C" int spdm_bench_gemm(int32_t device, int32_t B, int32_t H, int32_t W, 
         for (auto& v : hres) v = rnd();           // a non-zero residual: EPI_BIAS_RESID adds something
         HIP_TRY(hipMemcpy(wgt32, hw.data(), nw * 4, hipMemcpyHostToDevice));
         if (split) {
-            std::vector<float> out(nw);
-            for (size_t base = 0; base < nw; base += 32) {
-                _Float16* hp = reinterpret_cast<_Float16*>(&out[base]);
-                for (int j = 0; j < 32; ++j) {
-                    const float v = hw[base + j] * 128.0f;
-                    const _Float16 hi = (_Float16)v;
-                    hp[j] = hi;
-                    hp[32 + j] = (_Float16)(v - (float)hi);
-                }
-            }
-            hw.swap(out);
+            hw = Loader::split_format(hw);
             if ((taps == 9 || taps == 3) && Cout % 64 == 0 && Cin % 32 == 0) {
                 const std::vector<float> fr = frag_order_weights(hw, taps, Cout, Cin);
                 HIP_TRY(hipMalloc((void**)&wfrag, nw * 4));
@@ -1996,23 +1891,14 @@ extern "C" int spdm_bench_gemm(int32_t device, int32_t B, int32_t H, int32_t W, 
         HIP_TRY(hipMemcpy(st_in, hst.data(), hst.size() * 8, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(resid, hres.data(), ndst * 4, hipMemcpyHostToDevice));
     }
-    GemmArgs a{};
-    a.sw = sw;
-    a.src = src; a.src_ld = Cin; a.wgt = wgt; a.wgt_frag = wfrag; a.split = split; a.dst = dst; a.dst_ld = Cout;
-    a.M = M; a.K = Cin; a.N = Cout; a.taps = taps; a.H = H; a.W = W; a.HW = HW;
-    if (row_ln) { a.H = 1; a.W = 1; a.HW = 1; }             // like Ctx::linear: every row is its own LayerNorm "sample"
-    a.pro = pro;
-    a.pro_stats.p = st_in; a.pro_stats.slots = 1; a.pro_stats.m_tile = row_ln ? (1 << 30) : HW; a.pro_stats.n_tiles = 1;
-    a.pro_stats.HW = row_ln ? 1 : HW;
-    a.pro_stats.inv_count = 1.0 / ((double)Cin * (row_ln ? 1 : HW));
-    a.pro_gamma = gb; a.pro_beta = gb + Cin;
-    a.epi = epi; a.epi_stats = st_out; a.bias = gb + 2 * Cin; a.resid = resid; a.resid_ld = Cout;
-    a.debug = debug;
     float* d_part = nullptr;
-    if (may_splitk) {
-        HIP_TRY(hipMalloc((void**)&d_part, SPLITK_WORKSPACE_BYTES));
-        a.partial = d_part;
-    }
+    if (may_splitk) HIP_TRY(hipMalloc((void**)&d_part, SPLITK_WORKSPACE_BYTES));
+    // (row_ln: like Ctx::linear, every row is its own LayerNorm "sample")
+    const StatsRef st_ref{st_in, 1, row_ln ? (1 << 30) : HW, 1, row_ln ? 1 : HW, 1.0 / ((double)Cin * (row_ln ? 1 : HW))};
+    GemmArgs a = gemm_args(M, 0, row_ln ? 1 : H, row_ln ? 1 : W, Cin, Cout, taps, split, sw, d_part, pro,
+                           AffineSrc{src, Cin, st_ref, gb, gb + Cin}, 0, AffineSrc{}, wgt, wfrag, dst, Cout, epi, st_out,
+                           gb + 2 * Cin, resid, Cout);
+    a.debug = debug;
     unsigned long long* d_stamps = nullptr;
     if (debug & DBG_STAMP) {
         HIP_TRY(hipMalloc((void**)&d_stamps, (size_t)65536 * 8 * 8));      // conv_wide: 8 stamps per workgroup
@@ -2163,12 +2049,9 @@ extern "C" int spdm_encoder_forward(spdm_encoder* e, int32_t n_images, const flo
     for (int i0 = 0; i0 < n_images; i0 += chunk) {
         const int m = std::min(chunk, n_images - i0);
         HIP_TRY(launch_encoder_convs(d_images + (size_t)i0 * 3 * 96 * 96, e->w1, e->b1, e->w2, e->b2, e->w3, e->b3, e->feat, m, s));
-        GemmArgs a{};                   // Linear(9216, 128) on the exact fp32 MFMA path
-        a.split = 0;
-        a.src = e->feat; a.src_ld = ENC_FEAT; a.wgt = e->wl; a.dst = d_latent + (size_t)i0 * ENC_LATENT; a.dst_ld = ENC_LATENT;
-        a.M = m; a.K = ENC_FEAT; a.N = ENC_LATENT; a.taps = 1; a.H = 1; a.W = 1; a.HW = 1;
-        a.pro = PRO_NONE; a.epi = EPI_BIAS; a.bias = e->bl;
-        HIP_TRY(launch_gemm(a, s));
+        const LinW lin{e->wl, nullptr, e->bl, ENC_FEAT, ENC_LATENT};      // Linear(9216, 128) on the exact fp32 MFMA path
+        HIP_TRY(launch_gemm(linear_args(AffineSrc{e->feat, ENC_FEAT}, m, 0, lin, /*split=*/false, /*sw=*/0, EPI_BIAS,
+                                        d_latent + (size_t)i0 * ENC_LATENT), s));
     }
     if (!stream) HIP_TRY(hipStreamSynchronize(s));
     return SPDM_OK;
@@ -2233,34 +2116,10 @@ extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {
                                                : Loader::conv_taps(q.h_weight, q.N, q.K, q.taps);
     if (q.split && !Loader::split_range_ok(w32)) return fail(SPDM_ERR_INVALID, "op_gemm: weights outside the split format's range (the loader keeps such a layer on the exact path)");
     const unsigned sw = switches_from_env();
-    GemmArgs a{};
-    a.sw = sw;
-    a.split = q.split ? 1 : 0;
-    a.src = q.d_src; a.src_ld = q.src_ld; a.dst = q.d_dst; a.dst_ld = q.dst_ld;
-    a.M = M; a.K = q.K; a.N = q.N; a.taps = q.taps; a.geom_M = M;
-    a.H = q.H; a.W = q.W; a.HW = HW;
-    a.pro = q.pro;
-    auto ref = [](const double* st, int slots, int m_tile, int n_tiles, int rows, int cnorm) {
-        StatsRef r{};
-        r.p = st; r.slots = slots; r.m_tile = m_tile; r.n_tiles = n_tiles; r.HW = rows; r.inv_count = 1.0 / ((double)cnorm * rows);
-        return r;
-    };
-    const int src_c = (q.pro == PRO_UPCAT || two) ? q.up_C : q.K;
-    if (q.d_src_stats) {
-        a.pro_stats = ref(q.d_src_stats, q.src_slots, q.src_m_tile, q.src_n_tiles, src_rows, q.src_cnorm > 0 ? q.src_cnorm : src_c);
-        a.pro_gamma = q.d_gamma; a.pro_beta = q.d_beta;
-    }
-    if (q.d_skip) { a.up_C = q.up_C; a.skip = q.d_skip; a.skip_ld = q.skip_ld; }
-    if (q.d_skip_stats) {
-        const StatsRef sr = ref(q.d_skip_stats, q.skip_slots, q.skip_m_tile, q.skip_n_tiles, HW, q.skip_cnorm > 0 ? q.skip_cnorm : q.K - q.up_C);
-        if (two) { a.pro = PRO_GN; a.pro_stats = sr; a.pro_gamma = q.d_skip_gamma; a.pro_beta = q.d_skip_beta; }   // (Ctx::conv_two)
-        else { a.skip_stats = sr; a.skip_gamma = q.d_skip_gamma; a.skip_beta = q.d_skip_beta; }
-    }
-    a.epi = q.epi; a.bias = q.d_bias; a.resid = q.d_resid; a.resid_ld = q.resid_ld;
-    a.row_stats = q.d_row_stats;
+    const int split = q.split ? 1 : 0;
     // as the plan: a split-precision convolution may split K unless switched off (the handle then holds no partial buffer)
-    const bool may_partial = a.split && q.taps != 1 && q.epi == EPI_STATS && !(sw & SW_NO_SPLITK);
-    const GemmGeom g = gemm_geometry(M, q.N, q.K, HW, q.W, q.taps, a.split, sw, may_partial);
+    const bool may_partial = split && q.taps != 1 && q.epi == EPI_STATS && !(sw & SW_NO_SPLITK);
+    const GemmGeom g = gemm_geometry(M, q.N, q.K, HW, q.W, q.taps, split, sw, may_partial);
     if (q.epi == EPI_STATS && (!q.d_stats || q.stats_cap < (size_t)q.B * g.slots * 2))
         return fail(SPDM_ERR_INVALID, "op_gemm: statistics buffer needs %zu doubles", (size_t)q.B * g.slots * 2);
     if (q.d_row_stats && q.row_stats_cap < (size_t)M * g.n_tiles * 2)
@@ -2278,7 +2137,8 @@ extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {
     hipError_t e = hipSuccess;
     void* dw = nullptr;
     void* dwf = nullptr;
-    if (a.split) {
+    void* dp = nullptr;
+    if (split) {
         const std::vector<float> ws = Loader::split_format(w32);
         e = upload(ws.data(), ws.size() * 4, &dw);
         if (e == hipSuccess && q.taps != 1) {       // Loader::conv's fragment-order copy (Cout % 64 == 0 here)
@@ -2288,14 +2148,24 @@ extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {
     } else {
         e = upload(w32.data(), w32.size() * 4, &dw);
     }
-    a.wgt = (const float*)dw; a.wgt_frag = (const float*)dwf;
-    if (e == hipSuccess && may_partial) {
-        void* dp = nullptr;
-        e = upload(nullptr, g.ksplit > 1 ? (size_t)g.ksplit * M * q.N * sizeof(float) : 0, &dp);
-        a.partial = (float*)dp;
-    }
+    if (e == hipSuccess && may_partial) e = upload(nullptr, g.ksplit > 1 ? (size_t)g.ksplit * M * q.N * sizeof(float) : 0, &dp);
     if (e != hipSuccess) { release(); return fail(SPDM_ERR_HIP, "op_gemm: %s", hipGetErrorString(e)); }
-    a.epi_stats = q.epi == EPI_STATS ? q.d_stats : nullptr;
+    // the caller's tensors as the plan's sources, pending GroupNorms from the raw partials; then the plan's own builder
+    auto ref = [](const double* st, int slots, int m_tile, int n_tiles, int rows, int cnorm) {
+        return StatsRef{st, slots, m_tile, n_tiles, rows, 1.0 / ((double)cnorm * rows)};
+    };
+    const int src_c = (q.pro == PRO_UPCAT || two) ? q.up_C : q.K;
+    AffineSrc src{q.d_src, q.src_ld}, skip{q.d_skip, q.skip_ld};
+    if (q.d_src_stats)
+        src = AffineSrc{q.d_src, q.src_ld, ref(q.d_src_stats, q.src_slots, q.src_m_tile, q.src_n_tiles, src_rows,
+                                               q.src_cnorm > 0 ? q.src_cnorm : src_c), q.d_gamma, q.d_beta};
+    if (q.d_skip_stats)
+        skip = AffineSrc{q.d_skip, q.skip_ld, ref(q.d_skip_stats, q.skip_slots, q.skip_m_tile, q.skip_n_tiles, HW,
+                                                  q.skip_cnorm > 0 ? q.skip_cnorm : q.K - q.up_C), q.d_skip_gamma, q.d_skip_beta};
+    const int pro = (two && q.d_skip_stats) ? PRO_GN : q.pro;         // (Ctx::two_args)
+    GemmArgs a = gemm_args(M, M, q.H, q.W, q.K, q.N, q.taps, split, sw, (float*)dp, pro, src, q.up_C, skip, (const float*)dw,
+                           (const float*)dwf, q.d_dst, q.dst_ld, q.epi, q.epi == EPI_STATS ? q.d_stats : nullptr, q.d_bias,
+                           q.d_resid, q.resid_ld, q.d_row_stats);
     if (fused && !gemm_takes_fused_source(a)) {
         release();
         return fail(SPDM_ERR_INVALID, "op_gemm: this launch does not take a fused source (the plan materialises it)");
