@@ -35,7 +35,7 @@ extern "C" {
 #endif
 
 #define SPDM_NAME_MAX 64
-#define SPDM_ABI_VERSION 1
+#define SPDM_ABI_VERSION 2
 
 typedef enum {
     SPDM_OK = 0,
@@ -86,6 +86,11 @@ typedef struct {
                                        channel-padded storage: real channels first, zeros after);
                                      - every other entry point (schedules, sampling, graphs, switches, profiler,
                                        pinned geometry, precision flags) behaves as for UNet_Film. */
+
+#define SPDM_FLAG_TRAIN 8         /* the handle also serves spdm_train_loss_grad: it keeps flipped / transposed weight copies for
+                                    the backward pass and a training workspace sized at max_batch.  UNet_Film_noAttention only:
+                                    spdm_create returns SPDM_ERR_INVALID with attention = 1 or SPDM_FLAG_SIMPLE_UNET.  Every
+                                    other entry point behaves as on a handle without the flag. */
 
 /* One entry per tensor of the reference state_dict (names exactly as
  * UNet_Film.state_dict() gives them, e.g. "down1.cond_encoder.2.weight"),
@@ -163,6 +168,21 @@ int  spdm_sample(spdm_handle* h, int32_t B, const float* d_cond,
                  const float* d_inpaint, int32_t inp_h, int32_t inpaint_per_sample,
                  const float* d_xT, const float* d_noise, uint64_t seed, uint64_t sample_offset,
                  float* d_out, float* d_history, void* stream);
+
+/* Replaces: one training_step of Diffusion_DDPM up to loss.backward() (models/diffusion_ddpm.py:128-173,
+ * process_single_batch): eps = unet(x_noisy, t, cond); loss = mean((noise - eps)^2); the gradients of the loss with respect to
+ * every weight of the network and to cond.  Handle created with SPDM_FLAG_TRAIN (SPDM_ERR_STATE otherwise).
+ *  d_x_noisy, d_noise (B,H,D); h_t[t_count], t_count == 1 (broadcast) or B; d_cond (B,cond_dim) or NULL (no FiLM);
+ *  d_loss     one float on the device;
+ *  d_eps      NULL or (B,H,D): the predicted noise;
+ *  d_grad     device blob laid out as the blob last given to spdm_load_weights: the gradient of every tensor at that tensor's
+ *             offset, torch layout (tensors the call does not reach -- the FiLM encoders when d_cond is NULL -- get zeros);
+ *  d_grad_cond NULL or (B,cond_dim): the gradient with respect to cond (for a caller that trains the vision encoder jointly).
+ * Every contraction of the call runs on the exact fp32 MFMA path, whatever the handle's precision.
+ * Deterministic: no float atomics; two calls with the same inputs give bit-identical results. */
+int  spdm_train_loss_grad(spdm_handle* h, int32_t B, const float* d_x_noisy, const int32_t* h_t, int32_t t_count,
+                          const float* d_cond, const float* d_noise, float* d_loss, float* d_eps, float* d_grad,
+                          float* d_grad_cond, void* stream);
 
 /* The same loop in three pieces, so a caller (bench.py) can time an exact range
  * of denoise steps: begin() hoists the step-invariant FiLM projections and

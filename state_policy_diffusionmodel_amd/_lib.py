@@ -16,7 +16,8 @@ SPDM_DDPM, SPDM_DDIM = 0, 1
 SPDM_FLAG_DEBUG_KEEP = 1
 SPDM_FLAG_EXACT_FP32 = 2
 SPDM_FLAG_SIMPLE_UNET = 4
-ABI_VERSION = 1
+SPDM_FLAG_TRAIN = 8
+ABI_VERSION = 2
 
 
 class SpdmOpGemmArgs(ctypes.Structure):
@@ -53,6 +54,8 @@ SYMBOLS = {
     "spdm_unet_forward": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "spdm_sample": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_uint64,
                               c_uint64, c_void_p, c_void_p, c_void_p]),
+    "spdm_train_loss_grad": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p]),
     "spdm_sample_begin": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                     c_uint64, c_uint64, c_void_p, c_void_p]),
     "spdm_sample_run": (c_int32, [c_void_p, c_int32, c_int32, c_void_p]),

@@ -264,6 +264,36 @@ struct StepArgs {
     int B, H0, D, Hp, Wp, lh, lw;
 };
 hipError_t launch_out_step(const StepArgs& a, hipStream_t s);
+
+// train.hip: the training-loss gradient of UNet_Film_noAttention (spdm_train_loss_grad).  Channels-last [B][HW][C] throughout.
+// weight gradient of a 3x3 (taps 9), 3x1 (taps 3, W == 1) or 1x1 / Linear (taps 1) layer: dst = sum_m dy[m][co] x[shift(m)][ci]
+// on fp32 MFMA, rows split into partial slabs (budget_floats of `partial`) added in a fixed order; conv9: (Co, Ci, 3, 3) torch
+// layout (taps 3: side columns exact zeros), else (Co, Ci)
+int wgrad_chunks(long long M, int taps, int Co, int Ci, size_t budget_floats);
+hipError_t launch_wgrad(const float* dy, int ldy, const float* x, int ldx, long long M, int H, int W, int taps, int Co, int Ci,
+                        int conv9, float* partial, size_t budget_floats, float* dst, hipStream_t s);
+hipError_t launch_colsum(const float* src, int ld, long long M, int C, float* dst, hipStream_t s);
+hipError_t launch_gn_stats(const float* y, int B, int n, float* mean, float* rstd, hipStream_t s);
+hipError_t launch_gn_act(const float* y, const float* mean, const float* rstd, const float* gamma, const float* beta, int B,
+                         int HW, int C, int gelu, float* out, hipStream_t s);
+hipError_t launch_gn_bwd(const float* y, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                         const float* g, int gelu, int B, int HW, int C, float* dy, float* dgb, hipStream_t s);
+hipError_t launch_gn_param(const float* p0, const float* p1, int B, int C, float* dgamma, float* dbeta, hipStream_t s);
+hipError_t launch_film_bwd(const float* z, const float* temb, const int* t_dev, int t_count, const float* film,
+                           const float* dout, int B, int HW, int C, float* dz, float* de, float* dfilm, hipStream_t s);
+hipError_t launch_gather_rows(const float* table, const int* t_dev, int t_count, int B, int n, float* out, hipStream_t s);
+hipError_t launch_pad(const float* x, int B, int H0, int D, int Hp, int Wp, int lh, int lw, float* xp, hipStream_t s);
+hipError_t launch_conv_in_plain(const float* xp, const float* w /*[9][64]*/, int B, int H, int W, float* out, hipStream_t s);
+hipError_t launch_outc(const float* u, const float* w, float bias, long long M, float* out, hipStream_t s);
+hipError_t launch_outc_bwd(const float* deps, const float* w, long long M, float* du, hipStream_t s);
+hipError_t launch_mse(const float* eps_pad, const float* noise, int B, int H0, int D, int Hp, int Wp, int lh, int lw,
+                      float* loss, float* deps_pad, float* eps_out, hipStream_t s);
+hipError_t launch_pool_bwd(const float* in, const float* dout, int B, int H, int W, int C, float* din, hipStream_t s);
+hipError_t launch_up_bwd(const float* dcat, int ld, int B, int h, int w, int C, float* dx, hipStream_t s);
+hipError_t launch_add_cols(const float* src, int ld, int c0, long long M, int C, float* dst, hipStream_t s);
+hipError_t launch_mish_bwd(const float* dm, int nblk, int B, int ld, const float* cond, int cond_dim, float* grad_cond,
+                           hipStream_t s);
+
 hipError_t launch_advance(int* step_dev, int* t_dev, const int* timesteps_dev, int n_steps, hipStream_t s);
 hipError_t launch_set_step(int* step_dev, int* t_dev, const int* timesteps_dev, int n_steps, int i, hipStream_t s);
 

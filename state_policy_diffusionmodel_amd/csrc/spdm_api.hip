@@ -112,9 +112,12 @@ struct Value {             // a tensor plus the GroupNorm affine still pending o
 };
 
 struct ConvW { float* w = nullptr; float* ws = nullptr; float* wf = nullptr; int taps = 0, cin = 0, cout = 0;
-               int cnorm = 0; };   // cnorm > 0: real output channels of a channel-padded layer (its GroupNorm divides by these)   // ws: split-fp16 copy; wf: its fragment-order copy (conv_wide.hip)
+               int cnorm = 0;
+               float* wt = nullptr; };   // wt (SPDM_FLAG_TRAIN): [taps][Cin][Cout], taps flipped -- the data-gradient convolution's weights
+                                         // cnorm > 0: real output channels of a channel-padded layer (its GroupNorm divides by these)   // ws: split-fp16 copy; wf: its fragment-order copy (conv_wide.hip)
 struct DoubleConvW { ConvW first, second; float* gamma = nullptr; float* beta = nullptr; };
-struct LinW { float* w = nullptr; float* ws = nullptr; float* b = nullptr; int in = 0, out = 0; };
+struct LinW { float* w = nullptr; float* ws = nullptr; float* b = nullptr; int in = 0, out = 0;
+              float* wt = nullptr; };   // wt (SPDM_FLAG_TRAIN, FiLM encoders): [in padded to 64][out], the data gradient's weights
 struct ResampleW { DoubleConvW dc1, dc2; LinW emb, film; float* temb_table = nullptr; int cout = 0; };
 struct AttnW {
     LinW in_proj, out_proj, ff1, ff2;
@@ -140,6 +143,11 @@ struct spdm_handle {
     float* outc_w = nullptr;
     float outc_b = 0.f;
     bool weights_loaded = false, temb_ready = false;
+    bool train = false;                   // SPDM_FLAG_TRAIN: spdm_train_loss_grad (train_pass)
+    std::map<std::string, size_t> grad_off;   // ... offset of every tensor in the last spdm_load_weights blob
+    size_t grad_floats = 0;               // ... and that blob's size
+    float* tws = nullptr;                 // ... training workspace (train_pass at max_batch)
+    size_t tws_floats = 0;
     bool simple = false;                  // SPDM_FLAG_SIMPLE_UNET: models/simple_Unet.py (plan_simple); inc / down / up hold its blocks
     LinW cemb;                            // ... its six cond_emb_layer projections stacked: [6 x 32][film_kp]
     float* d_cemb = nullptr;              // ... Linear(SiLU(cond)) of the call, [B][6 x 32]
@@ -396,6 +404,8 @@ static void init_arch(spdm_handle* h) {
     for (int i = 0; i < 6; ++i) h->sa[i].C = sc[i];
 }
 
+static size_t train_workspace_floats(spdm_handle* h);
+
 extern "C" int spdm_create(const spdm_config* cfg, spdm_handle** out) {
     if (!cfg || !out) return fail(SPDM_ERR_INVALID, "null argument");
     if (cfg->horizon < 1 || cfg->state_dim < 1 || cfg->state_dim > 8)
@@ -405,12 +415,15 @@ extern "C" int spdm_create(const spdm_config* cfg, spdm_handle** out) {
         return fail(SPDM_ERR_INVALID, "cond_dim >= 0, max_batch >= 1, num_train_timesteps >= 1 required");
     if ((cfg->flags & SPDM_FLAG_SIMPLE_UNET) && cfg->attention != 0)
         return fail(SPDM_ERR_INVALID, "SPDM_FLAG_SIMPLE_UNET (models/simple_Unet.py) has no attention blocks: attention must be 0");
+    if ((cfg->flags & SPDM_FLAG_TRAIN) && (cfg->attention != 0 || (cfg->flags & SPDM_FLAG_SIMPLE_UNET)))
+        return fail(SPDM_ERR_INVALID, "SPDM_FLAG_TRAIN serves UNet_Film_noAttention only (attention = 0, no SPDM_FLAG_SIMPLE_UNET)");
     if ((cfg->flags & SPDM_FLAG_SIMPLE_UNET) && cfg->cond_dim < 1)
         return fail(SPDM_ERR_INVALID, "SPDM_FLAG_SIMPLE_UNET needs cond_dim >= 1 (the network is only defined with conditioning)");
     HIP_TRY(hipSetDevice(cfg->device));
     spdm_handle* h = new spdm_handle();
     h->cfg = *cfg;
     h->simple = (cfg->flags & SPDM_FLAG_SIMPLE_UNET) != 0;
+    h->train = (cfg->flags & SPDM_FLAG_TRAIN) != 0;
     h->sw = switches_from_env();          // the ONLY place the product path reads SPDM_* switches
     if (const char* pe = getenv("SPDM_PREC")) h->split = !(strcmp(pe, "f32") == 0 || strcmp(pe, "fp32") == 0);
     if (cfg->flags & SPDM_FLAG_EXACT_FP32) h->split = false;
@@ -448,6 +461,10 @@ extern "C" int spdm_create(const spdm_config* cfg, spdm_handle** out) {
         if (e != hipSuccess) { rc = fail(SPDM_ERR_NOMEM, "workspace of %zu bytes: %s", h->arena.cap, hipGetErrorString(e)); break; }
         h->owned.push_back(h->arena.base);
         if (h->sw & SW_ARENA_TRACE) fprintf(stderr, "[spdm] arena %p, %zu MiB\n", (void*)h->arena.base, h->arena.cap >> 20);
+        if (h->train) {
+            h->tws_floats = train_workspace_floats(h);
+            if ((rc = dev_alloc(h, (void**)&h->tws, sizeof(float) * h->tws_floats))) break;
+        }
     } while (0);
     if (rc) { spdm_destroy(h); return rc; }
     default_time_table(h->time_table, cfg->num_train_timesteps, cfg->time_dim);
@@ -544,12 +561,25 @@ struct Loader {
         }
         return v;
     }
+    // (Cout,Cin,3,3) -> [taps][Cin][Cout] with the taps rotated 180 degrees: the weights of the convolution that takes the output
+    // gradient to the input gradient (dX = conv3x3(dY, rot180(W) with Cin and Cout swapped)); tap order as conv_taps
+    static std::vector<float> conv_taps_flipped(const float* src, int cout, int cin, int taps) {
+        std::vector<float> v((size_t)taps * cin * cout);
+        for (int t = 0; t < taps; ++t) {
+            const int kh = (taps == 9) ? 2 - t / 3 : 2 - t, kw = (taps == 9) ? 2 - t % 3 : 1;
+            for (int i = 0; i < cin; ++i)
+                for (int o = 0; o < cout; ++o)
+                    v[((size_t)t * cin + i) * cout + o] = src[(((size_t)o * cin + i) * 3 + kh) * 3 + kw];
+        }
+        return v;
+    }
     ConvW conv(const std::string& name, int cout, int cin, int taps) {
         ConvW c;
         const float* src = find(name, {cout, cin, 3, 3});
         if (!src) return c;
         const std::vector<float> v = conv_taps(src, cout, cin, taps);
         c.w = upload(v);
+        if (h->train) c.wt = upload(conv_taps_flipped(src, cout, cin, taps));
         c.ws = (cin % 32 == 0) ? upload_split(v, cin, name) : nullptr;
         if (c.ws && cout % 64 == 0) c.wf = upload(frag_order_weights(split_format(v), taps, cout, cin));
         c.taps = taps; c.cin = cin; c.cout = cout;
@@ -585,8 +615,18 @@ struct Loader {
         r.dc1 = dconv(p + ".doubleConv1", cin, cin, taps);
         r.dc2 = dconv(p + ".doubleConv2", cin, cout, taps);
         r.emb = linear(p + ".emb_layer.1.weight", p + ".emb_layer.1.bias", cout, h->cfg.time_dim, h->cfg.time_dim);
-        if (h->cfg.cond_dim > 0)
+        if (h->cfg.cond_dim > 0) {
             r.film = linear(p + ".cond_encoder.2.weight", p + ".cond_encoder.2.bias", 2 * cout, h->cfg.cond_dim, h->film_kp);
+            if (h->train) {
+                const float* w = find(p + ".cond_encoder.2.weight", {2 * cout, h->cfg.cond_dim});
+                if (w) {
+                    std::vector<float> t((size_t)align_up(h->cfg.cond_dim, 64) * 2 * cout, 0.f);
+                    for (int o = 0; o < 2 * cout; ++o)
+                        for (int i = 0; i < h->cfg.cond_dim; ++i) t[(size_t)i * 2 * cout + o] = w[(size_t)o * h->cfg.cond_dim + i];
+                    r.film.wt = upload(t);
+                }
+            }
+        }
         r.cout = cout;
         return r;
     }
@@ -855,6 +895,11 @@ extern "C" int spdm_load_weights(spdm_handle* h, const float* blob, size_t n, co
     }
     }
     if (L.err != SPDM_OK) return L.err;
+    if (h->train) {
+        h->grad_off.clear();
+        h->grad_floats = n;
+        for (const auto& kv : L.idx) h->grad_off[kv.first] = (size_t)kv.second->offset;
+    }
     // time-embedding tables (one per resample block), filled lazily on the first evaluation
     ResampleW* blocks[6] = {&h->down[0], &h->down[1], &h->down[2], &h->up[0], &h->up[1], &h->up[2]};
     for (ResampleW* r : blocks)
@@ -1783,6 +1828,320 @@ extern "C" int spdm_sample(spdm_handle* h, int32_t B, const float* d_cond, const
         if (rc == SPDM_OK && e != hipSuccess) rc = fail(SPDM_ERR_HIP, "stream sync: %s", hipGetErrorString(e));
     }
     return rc;
+}
+
+// -------------------------------------------------------------------------------------------------
+// Training-loss gradient of UNet_Film_noAttention (SPDM_FLAG_TRAIN, spdm_train_loss_grad).
+// The forward half materialises every tensor the backward half reads -- each convolution's input (after GroupNorm + GELU, the
+// pool or the upsample + concat), its raw output and the per-sample GroupNorm statistics -- in the handle's training workspace,
+// a bump allocation whose size a dry run at max_batch fixed at create.  Convolutions and Linear layers are launches of the
+// plan's implicit-GEMM kernels (gemm_args) on the exact fp32 path, the data gradients with the flipped (ConvW::wt) /
+// transposed (LinW::wt) weight copies.  Training is exact-fp32 on any handle.  Weight gradients: launch_wgrad (train.hip).
+struct TrainPass {
+    spdm_handle* h;
+    int B, t_count;
+    bool use_cond, dry;
+    hipStream_t s;
+    float* d_grad;
+    size_t used = 0;
+    int err = SPDM_OK;
+    static constexpr size_t WGRAD_BUDGET = (size_t)16 << 20;   // floats of weight-gradient partial slabs (64 MiB)
+    float* partial = nullptr;
+    int* iota = nullptr;                   // 0 .. B-1: the per-sample rows of temb[] (t_dev of the tail kernels)
+    float* temb[6] = {};                   // Linear(SiLU(pos_encoding(t_b))) of the call, [B][C], exact fp32 path
+    float* film[6] = {};                   // Linear(Mish(cond)) of the call, [B][2C], exact fp32 path
+
+    unsigned sw() const { return h->sw | SW_NO_SKINNY | SW_NO_REG64 | SW_NO_WIDE | SW_NO_SPLITK; }   // plain-epilogue launches: conv_gemm
+    int Hl(int l) const { return h->Hp >> l; }
+    int Wl(int l) const { return h->Wp >> l; }
+    int HWl(int l) const { return Hl(l) * Wl(l); }
+    float* alloc(size_t n) {
+        float* p = dry ? nullptr : h->tws + used;
+        used += align_up(std::max<size_t>(n, 1), 64);
+        if (!dry && used > h->tws_floats && !err) err = fail(SPDM_ERR_NOMEM, "training workspace exhausted (batch %d)", B);
+        return err ? nullptr : p;
+    }
+    bool run() const { return !dry && !err; }
+    void chk(hipError_t e, const char* what) {
+        if (e != hipSuccess && !err) err = fail(SPDM_ERR_HIP, "train: %s: %s", what, hipGetErrorString(e));
+    }
+    float* G(const std::string& name) {
+        if (dry || err) return nullptr;
+        auto it = h->grad_off.find(name);
+        if (it == h->grad_off.end()) { err = fail(SPDM_ERR_MISSING, "train: tensor '%s' not in the loaded index", name.c_str()); return nullptr; }
+        return d_grad + it->second;
+    }
+
+    // y = conv(x, w) on the exact fp32 path (the gradient is only as continuous as the MaxPool choices)
+    void conv_fwd(const ConvW& w, const float* x, int level, float* y) {
+        if (!run()) return;
+        chk(launch_gemm(gemm_args(B * HWl(level), 0, Hl(level), Wl(level), w.cin, w.cout, w.taps, 0, sw(), nullptr, PRO_NONE,
+                                  AffineSrc{x, w.cin}, 0, AffineSrc{}, w.w, nullptr, y, w.cout, EPI_PLAIN, nullptr), s),
+            "conv forward");
+    }
+    // dx = conv(dy, rot180(w)^T): the forward kernels on the exact path
+    void conv_dgrad(const ConvW& w, const float* dy, int level, float* dx) {
+        if (!run()) return;
+        if (!w.wt) { err = fail(SPDM_ERR_STATE, "train: flipped weights missing"); return; }
+        chk(launch_gemm(gemm_args(B * HWl(level), 0, Hl(level), Wl(level), w.cout, w.cin, w.taps, 0, sw(), nullptr, PRO_NONE,
+                                  AffineSrc{dy, w.cout}, 0, AffineSrc{}, w.wt, nullptr, dx, w.cin, EPI_PLAIN, nullptr), s),
+            "conv data gradient");
+    }
+    void wgrad(const float* dy, int ldy, const float* x, int ldx, long long M, int level, int taps, int Co, int Ci, int conv9,
+               float* dst) {
+        if (!run() || !dst) return;
+        chk(launch_wgrad(dy, ldy, x, ldx, M, taps == 1 ? 1 : Hl(level), taps == 1 ? 1 : Wl(level), taps, Co, Ci, conv9, partial,
+                         WGRAD_BUDGET, dst, s), "weight gradient");
+    }
+
+    struct DC {                  // one DoubleConvolution's saved tensors
+        const float* x0 = nullptr; int cin = 0, C = 0, level = 0;
+        float *y1 = nullptr, *a1 = nullptr, *y2 = nullptr, *z = nullptr;
+        float *m1 = nullptr, *r1 = nullptr, *m2 = nullptr, *r2 = nullptr;
+    };
+    DC dc_fwd(const DoubleConvW& d, const float* x0, int level, bool inc) {
+        DC a;
+        a.x0 = x0; a.cin = d.first.cin; a.C = d.first.cout; a.level = level;
+        const size_t n = (size_t)B * HWl(level) * a.C;
+        a.y1 = alloc(n); a.a1 = alloc(n); a.y2 = alloc(n); a.z = alloc(n);
+        a.m1 = alloc(B); a.r1 = alloc(B); a.m2 = alloc(B); a.r2 = alloc(B);
+        if (!run()) return a;
+        const int HW = HWl(level);
+        if (inc) chk(launch_conv_in_plain(x0, h->w_inc_first, B, Hl(level), Wl(level), a.y1, s), "inc.first");
+        else conv_fwd(d.first, x0, level, a.y1);
+        if (!run()) return a;
+        chk(launch_gn_stats(a.y1, B, HW * a.C, a.m1, a.r1, s), "GroupNorm statistics");
+        chk(launch_gn_act(a.y1, a.m1, a.r1, d.gamma, d.beta, B, HW, a.C, 1, a.a1, s), "GroupNorm + GELU");
+        conv_fwd(d.second, a.a1, level, a.y2);
+        if (!run()) return a;
+        chk(launch_gn_stats(a.y2, B, HW * a.C, a.m2, a.r2, s), "GroupNorm statistics");
+        chk(launch_gn_act(a.y2, a.m2, a.r2, d.gamma, d.beta, B, HW, a.C, 0, a.z, s), "GroupNorm");
+        return a;
+    }
+    // dz: gradient of the block output; dx0 (null: not wanted) receives the gradient of its input
+    void dc_bwd(const DC& a, const DoubleConvW& d, const std::string& p, const float* dz, float* dx0) {
+        const int HW = HWl(a.level);
+        const long long M = (long long)B * HW;
+        const size_t n = (size_t)M * a.C;
+        float* dy2 = alloc(n);
+        float* da1 = alloc(n);
+        float* dy1 = alloc(n);
+        float* dgb2 = alloc((size_t)B * a.C * 2);
+        float* dgb1 = alloc((size_t)B * a.C * 2);
+        if (!run()) return;
+        const int taps = d.second.taps;
+        chk(launch_gn_bwd(a.y2, a.m2, a.r2, d.gamma, d.beta, dz, 0, B, HW, a.C, dy2, dgb2, s), "GroupNorm backward");
+        wgrad(dy2, a.C, a.a1, a.C, M, a.level, taps, a.C, a.C, 1, G(p + ".second.weight"));
+        conv_dgrad(d.second, dy2, a.level, da1);
+        if (!run()) return;
+        chk(launch_gn_bwd(a.y1, a.m1, a.r1, d.gamma, d.beta, da1, 1, B, HW, a.C, dy1, dgb1, s), "GroupNorm + GELU backward");
+        float* dg = G(p + ".norm.weight");
+        float* db = G(p + ".norm.bias");
+        if (!run()) return;
+        chk(launch_gn_param(dgb2, dgb1, B, a.C, dg, db, s), "GroupNorm affine gradient");
+        wgrad(dy1, a.C, a.x0, a.cin, M, a.level, d.first.taps, a.C, a.cin, 1, G(p + ".first.weight"));
+        if (dx0) conv_dgrad(d.first, dy1, a.level, dx0);
+    }
+
+    struct Block {               // a Down / UpSample block
+        DC dc1, dc2;
+        const float* in = nullptr;   // pooled or upsampled + concatenated input (dc1.x0)
+        float* out = nullptr;
+    };
+    // x + Linear(SiLU(temb)), then FiLM
+    float* film_fwd(int i, const ResampleW& r, const DC& dc2, int level) {
+        float* out = alloc((size_t)B * HWl(level) * r.cout);
+        if (run())
+            chk(launch_film_apply(AffineSrc{dc2.z, r.cout}, temb[i], iota, B, use_cond ? film[i] : nullptr, out, nullptr, B,
+                                  HWl(level), s), "time embedding + FiLM");
+        return out;
+    }
+    // backward of the block tail; returns the gradient of dc2's output.  tsilu: SiLU(pos_encoding(t)) rows; dm: this block's
+    // [B][cond_dim padded to 64] gradient of Mish(cond)
+    float* film_bwd(int i, const ResampleW& r, const DC& dc2, const std::string& p, const float* dout, const float* tsilu,
+                    float* dm) {
+        const int C = r.cout, level = dc2.level;
+        float* dz = alloc((size_t)B * HWl(level) * C);
+        float* de = alloc((size_t)B * C);
+        float* df = use_cond ? alloc((size_t)B * 2 * C) : nullptr;
+        if (!run()) return dz;
+        chk(launch_film_bwd(dc2.z, temb[i], iota, B, use_cond ? film[i] : nullptr, dout, B, HWl(level), C, dz, de, df, s),
+            "FiLM backward");
+        const int td = h->cfg.time_dim;
+        wgrad(de, C, tsilu, td, B, 0, 1, C, td, 0, G(p + ".emb_layer.1.weight"));
+        if (float* gb = G(p + ".emb_layer.1.bias"); run()) chk(launch_colsum(de, C, B, C, gb, s), "bias gradient");
+        if (use_cond) {
+            const int cd = h->cfg.cond_dim, kp64 = (int)align_up(cd, 64);
+            wgrad(df, 2 * C, h->d_condm, h->film_kp, B, 0, 1, 2 * C, cd, 0, G(p + ".cond_encoder.2.weight"));
+            if (float* gb = G(p + ".cond_encoder.2.bias"); run()) chk(launch_colsum(df, 2 * C, B, 2 * C, gb, s), "bias gradient");
+            if (!run()) return dz;
+            if (!r.film.wt) { err = fail(SPDM_ERR_STATE, "train: transposed FiLM weights missing"); return dz; }
+            chk(launch_gemm(gemm_args(B, 0, 1, 1, 2 * C, kp64, 1, 0, sw(), nullptr, PRO_NONE, AffineSrc{df, 2 * C}, 0, AffineSrc{},
+                                      r.film.wt, nullptr, dm, kp64, EPI_PLAIN, nullptr), s), "FiLM data gradient");
+        }
+        return dz;
+    }
+};
+
+static const char* const kDown[3] = {"down1", "down2", "down3"};
+static const char* const kUp[3] = {"up1", "up2", "up3"};
+static const char* const kBot[3] = {"bot1", "bot2", "bot3"};
+
+static int train_pass(TrainPass& T, const float* d_x, const float* d_cond, const float* d_noise, float* d_loss, float* d_eps,
+                      float* d_grad_cond) {
+    spdm_handle* h = T.h;
+    const int B = T.B, H0 = h->cfg.horizon, D = h->cfg.state_dim;
+    const long long M0 = (long long)B * T.HWl(0);
+    T.partial = T.alloc(TrainPass::WGRAD_BUDGET);
+    // time-embedding and FiLM projections of the call on the exact path (the sampling plan's tables follow the handle's
+    // precision: a split-fp16 perturbation of 1e-6 already moves near-tie MaxPool choices)
+    const int td = h->cfg.time_dim;
+    float* tsilu = T.alloc((size_t)B * td);
+    T.iota = (int*)T.alloc((size_t)B);
+    if (T.run()) {
+        std::vector<int> iota(B);
+        for (int b = 0; b < B; ++b) iota[b] = b;
+        T.chk(hipMemcpyAsync(T.iota, iota.data(), sizeof(int) * B, hipMemcpyHostToDevice, T.s), "iota");
+        T.chk(hipStreamSynchronize(T.s), "iota");
+        T.chk(launch_gather_rows(h->d_time_silu, h->d_t, T.t_count, B, td, tsilu, T.s), "time rows");
+    }
+    ResampleW* blocks[6] = {&h->down[0], &h->down[1], &h->down[2], &h->up[0], &h->up[1], &h->up[2]};
+    for (int i = 0; i < 6; ++i) {
+        const ResampleW& r = *blocks[i];
+        T.temb[i] = T.alloc((size_t)B * r.cout);
+        T.film[i] = T.use_cond ? T.alloc((size_t)B * 2 * r.cout) : nullptr;
+        if (T.run())
+            T.chk(launch_gemm(linear_args(AffineSrc{tsilu, td}, B, 0, r.emb, false, T.sw(), EPI_BIAS, T.temb[i]), T.s), "time embedding");
+        if (T.run() && T.use_cond)
+            T.chk(launch_gemm(linear_args(AffineSrc{h->d_condm, h->film_kp}, B, 0, r.film, false, T.sw(), EPI_BIAS, T.film[i]), T.s),
+                  "FiLM projection");
+    }
+    // ---- forward ----
+    float* xp = T.alloc((size_t)M0);
+    if (T.run()) T.chk(launch_pad(d_x, B, H0, D, h->Hp, h->Wp, h->lh, h->lw, xp, T.s), "pad");
+    const TrainPass::DC inc = T.dc_fwd(h->inc, xp, 0, true);
+    const float* skips[4] = {inc.z, nullptr, nullptr, nullptr};     // x1 x2 x3 x4
+    int skipC[4] = {64, 0, 0, 0};
+    TrainPass::Block down[3], up[3];
+    for (int k = 0; k < 3; ++k) {
+        const ResampleW& r = h->down[k];
+        const int cin = r.dc1.first.cin, lv = k + 1;
+        float* p = T.alloc((size_t)B * T.HWl(lv) * cin);
+        if (T.run()) T.chk(launch_pool(AffineSrc{skips[k], cin}, p, B, T.Hl(k), T.Wl(k), T.s), "max pool");
+        down[k].in = p;
+        down[k].dc1 = T.dc_fwd(r.dc1, p, lv, false);
+        down[k].dc2 = T.dc_fwd(r.dc2, down[k].dc1.z, lv, false);
+        down[k].out = T.film_fwd(k, r, down[k].dc2, lv);
+        skips[k + 1] = down[k].out;
+        skipC[k + 1] = r.cout;
+    }
+    TrainPass::DC bot[3];
+    const float* xb = skips[3];
+    for (int k = 0; k < 3; ++k) { bot[k] = T.dc_fwd(h->bot[k], xb, 3, false); xb = bot[k].z; }
+    const float* xin = xb;      // x5, then u1, u2
+    int cu = 256;
+    for (int k = 0; k < 3; ++k) {
+        const ResampleW& r = h->up[k];
+        const int lv = 2 - k, cs = skipC[2 - k], cin = r.dc1.first.cin;
+        if (cu + cs != cin && !T.err) T.err = fail(SPDM_ERR_STATE, "train: up block %d has %d + %d input channels, weight expects %d", k, cu, cs, cin);
+        float* c = T.alloc((size_t)B * T.HWl(lv) * cin);
+        if (T.run()) T.chk(launch_upcat(AffineSrc{xin, cu}, AffineSrc{skips[2 - k], cs}, c, B, T.Hl(lv + 1), T.Wl(lv + 1), T.s), "upsample + concat");
+        up[k].in = c;
+        up[k].dc1 = T.dc_fwd(r.dc1, c, lv, false);
+        up[k].dc2 = T.dc_fwd(r.dc2, up[k].dc1.z, lv, false);
+        up[k].out = T.film_fwd(3 + k, r, up[k].dc2, lv);
+        xin = up[k].out;
+        cu = r.cout;
+    }
+    float* eps_pad = T.alloc((size_t)M0);
+    float* deps = T.alloc((size_t)M0);
+    if (T.run()) T.chk(launch_outc(xin, h->outc_w, h->outc_b, M0, eps_pad, T.s), "outc");
+    if (T.run()) T.chk(launch_mse(eps_pad, d_noise, B, H0, D, h->Hp, h->Wp, h->lh, h->lw, d_loss, deps, d_eps, T.s), "MSE loss");
+    // ---- backward ----
+    const int kp64 = (int)align_up(std::max(h->cfg.cond_dim, 1), 64);
+    float* dm = T.alloc((size_t)6 * B * kp64);
+    float* dskip[4];                                  // gradients of x1 .. x4 (accumulated: the pool and the skip both read them)
+    for (int k = 0; k < 4; ++k) dskip[k] = T.alloc((size_t)B * T.HWl(k) * skipC[k]);
+    float* dup[3];                                    // gradients of x5, u1, u2 (the coarse input of up block k)
+    const int upC[3] = {256, h->up[0].cout, h->up[1].cout};
+    for (int k = 0; k < 3; ++k) dup[k] = T.alloc((size_t)B * T.HWl(3 - k) * upC[k]);
+    float* du3 = T.alloc((size_t)M0 * 64);
+    if (T.run()) {
+        T.chk(hipMemsetAsync(T.d_grad, 0, sizeof(float) * h->grad_floats, T.s), "memset");
+        T.chk(hipMemsetAsync(dm, 0, sizeof(float) * 6 * B * kp64, T.s), "memset");
+        for (int k = 0; k < 4; ++k) T.chk(hipMemsetAsync(dskip[k], 0, sizeof(float) * B * T.HWl(k) * skipC[k], T.s), "memset");
+        for (int k = 0; k < 3; ++k) T.chk(hipMemsetAsync(dup[k], 0, sizeof(float) * B * T.HWl(3 - k) * upC[k], T.s), "memset");
+        T.chk(launch_outc_bwd(deps, h->outc_w, M0, du3, T.s), "outc backward");
+    }
+    T.wgrad(deps, 1, xin, 64, M0, 0, 1, 1, 64, 0, T.G("outc.weight"));
+    if (float* gb = T.G("outc.bias"); T.run()) T.chk(launch_colsum(deps, 1, M0, 1, gb, T.s), "bias gradient");
+    const float* dout = du3;
+    for (int k = 2; k >= 0; --k) {
+        const ResampleW& r = h->up[k];
+        const int lv = 2 - k, cs = skipC[2 - k], cin = r.dc1.first.cin, cuk = upC[k];
+        const std::string p = kUp[k];
+        float* dz2 = T.film_bwd(3 + k, r, up[k].dc2, p, dout, tsilu, dm + (size_t)(3 + k) * B * kp64);
+        float* dz1 = T.alloc((size_t)B * T.HWl(lv) * r.dc1.first.cout);
+        float* dc = T.alloc((size_t)B * T.HWl(lv) * cin);
+        T.dc_bwd(up[k].dc2, r.dc2, p + ".doubleConv2", dz2, dz1);
+        T.dc_bwd(up[k].dc1, r.dc1, p + ".doubleConv1", dz1, dc);
+        if (T.run()) {
+            T.chk(launch_up_bwd(dc, cin, B, T.Hl(lv + 1), T.Wl(lv + 1), cuk, dup[k], T.s), "upsample backward");
+            T.chk(launch_add_cols(dc, cin, cuk, (long long)B * T.HWl(lv), cs, dskip[2 - k], T.s), "concat backward");
+        }
+        dout = dup[k];
+    }
+    // dup[0] is the gradient of x5 = bot3's output
+    const float* dbz = dup[0];
+    for (int k = 2; k >= 0; --k) {
+        float* dx = (k == 0) ? nullptr : T.alloc((size_t)B * T.HWl(3) * h->bot[k].first.cin);
+        T.dc_bwd(bot[k], h->bot[k], kBot[k], dbz, k == 0 ? dskip[3] : dx);
+        dbz = dx;
+    }
+    // bot1's input gradient went into dskip[3] -- which nothing else reads: copy semantics are enough (dskip[3] was zero)
+    for (int k = 2; k >= 0; --k) {
+        const ResampleW& r = h->down[k];
+        const int lv = k + 1, cin = r.dc1.first.cin;
+        const std::string p = kDown[k];
+        float* dz2 = T.film_bwd(k, r, down[k].dc2, p, dskip[k + 1], tsilu, dm + (size_t)k * B * kp64);
+        float* dz1 = T.alloc((size_t)B * T.HWl(lv) * r.dc1.first.cout);
+        float* dpool = T.alloc((size_t)B * T.HWl(lv) * cin);
+        T.dc_bwd(down[k].dc2, r.dc2, p + ".doubleConv2", dz2, dz1);
+        T.dc_bwd(down[k].dc1, r.dc1, p + ".doubleConv1", dz1, dpool);
+        if (T.run()) T.chk(launch_pool_bwd(skips[k], dpool, B, T.Hl(k), T.Wl(k), cin, dskip[k], T.s), "max pool backward");
+    }
+    T.dc_bwd(inc, h->inc, "inc", dskip[0], nullptr);
+    if (T.use_cond && d_grad_cond && T.run())
+        T.chk(launch_mish_bwd(dm, 6, B, kp64, d_cond, h->cfg.cond_dim, d_grad_cond, T.s), "Mish backward");
+    return T.err;
+}
+
+static size_t train_workspace_floats(spdm_handle* h) {
+    TrainPass T{h, h->cfg.max_batch, 1, h->cfg.cond_dim > 0, true, nullptr, nullptr};
+    (void)train_pass(T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    return T.used;
+}
+
+extern "C" int spdm_train_loss_grad(spdm_handle* h, int32_t B, const float* d_x, const int32_t* h_t, int32_t t_count,
+                                    const float* d_cond, const float* d_noise, float* d_loss, float* d_eps, float* d_grad,
+                                    float* d_grad_cond, void* stream) {
+    if (!h) return fail(SPDM_ERR_INVALID, "null handle");
+    if (!h->train) return fail(SPDM_ERR_STATE, "spdm_train_loss_grad needs a handle created with SPDM_FLAG_TRAIN");
+    SPDM_TRY(check_ready(h, B));
+    if (!d_x || !h_t || !d_noise || !d_loss || !d_grad) return fail(SPDM_ERR_INVALID, "null argument");
+    if (t_count != 1 && t_count != B) return fail(SPDM_ERR_INVALID, "t_count must be 1 or B");
+    for (int i = 0; i < t_count; ++i)
+        if (h_t[i] < 0 || h_t[i] >= h->cfg.num_train_timesteps) return fail(SPDM_ERR_INVALID, "t = %d outside [0,%d)", h_t[i], h->cfg.num_train_timesteps);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    SPDM_TRY(ensure_temb(h, s));
+    HIP_TRY(hipMemcpyAsync(h->d_t, h_t, sizeof(int) * t_count, hipMemcpyHostToDevice, s));
+    SPDM_TRY(compute_film(h, B, d_cond, s));
+    TrainPass T{h, B, t_count, d_cond != nullptr && h->cfg.cond_dim > 0, false, s, d_grad};
+    SPDM_TRY(train_pass(T, d_x, d_cond, d_noise, d_loss, d_eps, d_grad_cond));
+    h->session = false;
+    if (!stream) HIP_TRY(hipStreamSynchronize(s));
+    return SPDM_OK;
 }
 
 extern "C" int spdm_debug_tensor(spdm_handle* h, const char* name, float* d_out, size_t cap, int32_t shape[4]) {

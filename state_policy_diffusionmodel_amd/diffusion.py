@@ -12,14 +12,15 @@ types -- so ``generate.py``'s idiom
     history = model.sample(batch=obs, option='sample_history')            # generate.py:73-76
 
 works unchanged.  What runs underneath is libspdm_hip.so (no torch compute in the loop).
-Training, validation plots and the Lightning plumbing are out of scope.
+The optimiser, validation plots and the Lightning plumbing are out of scope.
 
 All three noise predictors of ``__init__`` (models/diffusion_ddpm.py:53-62) run on that path: ``model='UNet_Film'``,
 ``'UNet_FilmnoAttention'``, and every other value -- the constructor's own default ``'UNet'`` -- for
 models/simple_Unet.py's concat-conditioned ``UNet``.  Evaluation always has eval semantics: that network's
 positional-encoding dropout is off, as in the reference's ``validation_step`` and ``sample()`` after ``model.eval()``;
 the reference's ``training_step`` runs it with dropout p = 0.1, which ``training_step`` here does not reproduce (its
-forward half is the eval-mode network).
+forward half is the eval-mode network).  ``training_step(..., backward=True)`` also computes the gradients, for
+``'UNet_FilmnoAttention'`` only (``spdm_train_loss_grad``); the optimiser stays in torch.
 
 Explicit, non-breaking extensions: ``sample(..., x_T=, noise=, batched=, seed=)`` for
 fixed-noise parity runs and for B > 1 independent trajectories (the reference hard-wires
@@ -66,8 +67,27 @@ class NoiseEstimator:
         self._owner = owner
         self._sd = state_dict_to_numpy(state_dict)
 
+        self._grads: Optional[Dict[str, torch.Tensor]] = None
+        self.grad_cond: Optional[torch.Tensor] = None
+
     def state_dict(self):
         return {k: torch.from_numpy(v) for k, v in self._sd.items()}
+
+    def load_state_dict(self, state_dict) -> None:
+        """Replace the weights (e.g. after an optimiser step) and push them into every engine the owner has cached: the
+        training engine is refreshed in place (SpdmEngine.refresh_weights); the sampling engine is too, when present."""
+        self._sd = state_dict_to_numpy(state_dict)
+        for eng in (self._owner._engine, self._owner._train_engine):
+            if eng is not None:
+                eng.refresh_weights(self._sd)
+
+    def grads(self) -> Dict[str, torch.Tensor]:
+        """Gradients of the loss of the last ``training_step(..., backward=True)``: state_dict name -> tensor (torch layout,
+        on the device), as ``{n: p.grad for n, p in noise_estimator.named_parameters()}`` after ``loss.backward()``.
+        ``grad_cond`` holds d loss / d obs_cond of that step (None without conditioning)."""
+        if self._grads is None:
+            raise RuntimeError("no gradients: call training_step(..., backward=True) first")
+        return self._grads
 
     def __call__(self, x: torch.Tensor, t: torch.Tensor, y: Optional[torch.Tensor] = None) -> torch.Tensor:
         eng = self._owner._engine_for(x.shape[0], x.shape[-2], x.shape[-1])
@@ -112,6 +132,8 @@ class Diffusion_DDPM:
         self._max_batch = max_batch
         self._engine: Optional[SpdmEngine] = None
         self._engine_key = None
+        self._train_engine: Optional[SpdmEngine] = None     # training_step(backward=True): cached apart from sampling
+        self._train_key = None
 
     # ------------------------------------------------------------------------------------------
     _HPARAM_KEYS = ("noise_steps", "obs_horizon", "pred_horizon", "observation_dim", "prediction_dim", "learning_rate",
@@ -167,6 +189,25 @@ class Diffusion_DDPM:
             self._engine.load_state_dict(self.noise_estimator._sd)
             self._engine_key = key
         return self._engine
+
+    def _check_trainable(self) -> None:
+        if self.simple or self.attention:
+            raise NotImplementedError(
+                f"training_step(backward=True) computes gradients for model='UNet_FilmnoAttention' only (this model is "
+                f"{self.model_name!r}); the attention U-Net and simple_Unet.py have no backward pass on the HIP path")
+
+    def _train_engine_for(self, batch: int, H: int, D: int) -> SpdmEngine:
+        self._check_trainable()
+        T = max(int(_as_spec(self.noise_scheduler).config.num_train_timesteps), int(self.noise_steps))
+        key = (H, D, T)
+        if self._train_engine is None or self._train_key != key or batch > self._train_engine.max_batch:
+            if self._train_engine is not None:
+                self._train_engine.close()
+            self._train_engine = SpdmEngine(H, D, self.cond_dim, max_batch=max(batch, self._max_batch),
+                                            device=self._device_index, attention=False, num_train_timesteps=T, train=True)
+            self._train_engine.load_state_dict(self.noise_estimator._sd)
+            self._train_key = key
+        return self._train_engine
 
     def add_constraints(self, x_t: torch.Tensor, x_inpaint: torch.Tensor) -> torch.Tensor:
         """models/diffusion_ddpm.py:216-219 (in place, broadcast over the batch)."""
@@ -309,14 +350,19 @@ class Diffusion_DDPM:
         x_0 = self.sample(dict(observation_batch), x_T=x_T, noise=noise)
         return x_0, observation_batch, inpaint_vector
 
-    # ==================== Training, forward half (models/diffusion_ddpm.py:140-172) ====================
+    # ==================== Training (models/diffusion_ddpm.py:128-173) ====================
     def training_step(self, batch, batch_idx: int = 0, *, t: Optional[torch.Tensor] = None,
-                      noise: Optional[torch.Tensor] = None, return_parts: bool = False):
-        """The forward computation of the reference's ``training_step``: noising of the target window at a per-sample
-        timestep (``add_noise``), in-painting of the observed rows, ONE U-Net evaluation with ``t`` of shape (B,), MSE
-        against the noise.  The U-Net runs on the HIP path (``spdm_unet_forward`` with per-sample t); there is no
-        backward pass here -- the returned loss carries no graph (training itself is outside this path).
+                      noise: Optional[torch.Tensor] = None, return_parts: bool = False, backward: bool = False):
+        """The reference's ``training_step``: noising of the target window at a per-sample timestep (``add_noise``),
+        in-painting of the observed rows, ONE U-Net evaluation with ``t`` of shape (B,), MSE against the noise.  The U-Net
+        runs on the HIP path (``spdm_unet_forward`` with per-sample t); the returned loss carries no torch graph.
+        ``backward=True`` (model='UNet_FilmnoAttention' only, NotImplementedError otherwise) is ``loss.backward()`` as
+        well: the step runs ``spdm_train_loss_grad`` on a training engine cached apart from the sampling engines and
+        leaves the gradients in ``noise_estimator.grads()`` (and d loss / d obs_cond in ``noise_estimator.grad_cond``)
+        for a torch optimiser; ``noise_estimator.load_state_dict`` takes the updated weights back.
         ``t`` / ``noise`` may be passed for reproducibility (the reference draws them with torch.randint / randn_like)."""
+        if backward:
+            self._check_trainable()
         observation_batch = self.prepare_observation_batch(batch)
         prediction_batch = self.prepare_prediction_batch(batch)
         obs_cond = self.prepare_obs_cond_vectors(observation_batch).unsqueeze(1)            # (B,1,obs_h,obs_dim)
@@ -332,6 +378,12 @@ class Diffusion_DDPM:
         noise = noise.to(self.device).float()
         x_noisy = _as_spec(self.noise_scheduler).add_noise(prediction_vector, noise, t)
         x_noisy = self.add_constraints(x_noisy, x_0_inpaint)
+        if backward:
+            eng = self._train_engine_for(B, x_noisy.shape[-2], x_noisy.shape[-1])
+            loss, noise_estimated, grads, grad_cond = eng.loss_and_grad(x_noisy, t, obs_cond, noise)
+            self.noise_estimator._grads = grads
+            self.noise_estimator.grad_cond = grad_cond
+            return (loss, noise_estimated, x_noisy) if return_parts else loss
         noise_estimated = self.noise_estimator(x_noisy, t, obs_cond)
         loss = torch.mean((noise - noise_estimated) ** 2)                                  # nn.MSELoss, :49
         return (loss, noise_estimated, x_noisy) if return_parts else loss

@@ -34,11 +34,13 @@ class SpdmEngine:
     def __init__(self, horizon: int, state_dim: int, cond_dim: int, max_batch: int, device: int = 0,
                  attention: bool = True, time_dim: int = 256, num_train_timesteps: int = 1000,
                  debug: bool = False, exact_fp32: bool = False, pin_geometry: bool = False,
-                 model: Optional[str] = None):
+                 model: Optional[str] = None, train: bool = False):
         """``model``: None -> UNet_Film (``attention=True``) / UNet_FilmnoAttention (``attention=False``); a model name as
         Diffusion_DDPM takes it otherwise -- ``'UNet'`` (any non-FiLM name) is models/simple_Unet.py's network, whose
         time table is the state_dict's own ``pos_encoding.pos_encoding`` buffer: ``num_train_timesteps`` must then be
-        that buffer's row count (noise_steps + 1)."""
+        that buffer's row count (noise_steps + 1).
+
+        ``train``: the handle also serves ``loss_and_grad`` (SPDM_FLAG_TRAIN; UNet_FilmnoAttention only)."""
         self.lib = _lib.load()
         self.simple = model is not None and is_simple_model(model)
         if model is not None and not self.simple:
@@ -54,18 +56,27 @@ class SpdmEngine:
         cfg = _lib.SpdmConfig(self.horizon, self.state_dim, self.cond_dim, self.time_dim, int(self.attention),
                               self.max_batch, device, self.num_train_timesteps,
                               (_lib.SPDM_FLAG_DEBUG_KEEP if debug else 0) | (_lib.SPDM_FLAG_EXACT_FP32 if exact_fp32 else 0)
-                              | (_lib.SPDM_FLAG_SIMPLE_UNET if self.simple else 0))
+                              | (_lib.SPDM_FLAG_SIMPLE_UNET if self.simple else 0) | (_lib.SPDM_FLAG_TRAIN if train else 0))
+        self.train = bool(train)
+        self._cfg = cfg
+        self._pin = bool(pin_geometry)
+        self._create()
+        self._keep = []           # tensors the C side reads asynchronously during a session
+        self.n_steps = 0
+        self.kind = None
+        self._weights_loaded = False
+        self._sched = None
+        self._switches = {}
+
+    def _create(self) -> None:
         h = ctypes.c_void_p()
-        _lib.check(self.lib.spdm_create(ctypes.byref(cfg), ctypes.byref(h)), "spdm_create")
+        _lib.check(self.lib.spdm_create(ctypes.byref(self._cfg), ctypes.byref(h)), "spdm_create")
         self._h = h
-        if pin_geometry:
+        if self._pin:
             # kernel selection (tile sizes, split-K, the small-grid kernel, fused sources) normally follows the batch of the call;
             # pinned, every call runs the kernels a batch of max_batch would -- so a rank that holds a shard of a larger batch
             # (max_batch = the GLOBAL batch) reproduces the single-GPU trajectories bit for bit (multi-GPU)
             _lib.check(self.lib.spdm_set_switch(self._h, b"SPDM_PIN_GEOMETRY", 1), "spdm_set_switch")
-        self._keep = []           # tensors the C side reads asynchronously during a session
-        self.n_steps = 0
-        self.kind = None
         if not self.simple:        # (simple_Unet.py: the table is the state_dict's pos_encoding buffer, set by load_state_dict)
             tab = reference_time_table(self.num_train_timesteps, self.time_dim).numpy()
             _lib.check(self.lib.spdm_set_time_table(self._h, tab.ctypes.data_as(ctypes.c_void_p),
@@ -106,6 +117,7 @@ class SpdmEngine:
         """Flip one kernel-selection switch (``SPDM_NO_GRAPH``, ``SPDM_NO_WIDE``, ...) on this handle.  The
         environment is read once, at construction; this is the test / tuning hook for a live engine."""
         _lib.check(self.lib.spdm_set_switch(self._h, name.encode(), int(bool(on))), "spdm_set_switch")
+        self._switches[name] = bool(on)
 
     def nonfinite(self) -> bool:
         """True if the last sampling loop / U-Net evaluation produced a non-finite value (synchronises the stream).
@@ -138,8 +150,39 @@ class SpdmEngine:
         missing = sorted(want - have)
         if missing:
             raise KeyError(f"state_dict lacks {len(missing)} tensors, e.g. {missing[:3]}")
+        if self._weights_loaded and self.train:
+            self.refresh_weights(sd)
+            return
         _lib.check(self.lib.spdm_load_weights(self._h, blob.ctypes.data_as(ctypes.c_void_p), blob.size, idx,
                                               len(idx)), "spdm_load_weights")
+        self._weights_loaded = True
+        self._index = [(e.name.decode(), int(e.offset), tuple(e.shape[d] for d in range(e.ndim))) for e in idx]
+        self._blob_floats = int(blob.size)
+
+    def refresh_weights(self, sd) -> None:
+        """Put updated weights (an optimiser step) into this engine.  A handle takes its weights once, so a fresh handle of the
+        same configuration is created, loaded (spdm_load_weights), given the installed schedule and switches, and only then
+        replaces the old one: on any failure the engine keeps its previous handle and weights.  Costs a handle creation per
+        call (tools/bench_train.py times it as the host weight refresh)."""
+        old, old_keep = self._h, self._keep
+        self._create()
+        try:
+            blob, idx = pack_state_dict(sd)
+            _lib.check(self.lib.spdm_load_weights(self._h, blob.ctypes.data_as(ctypes.c_void_p), blob.size, idx,
+                                                  len(idx)), "spdm_load_weights")
+            for name, on in self._switches.items():
+                _lib.check(self.lib.spdm_set_switch(self._h, name.encode(), int(on)), "spdm_set_switch")
+            if self._sched is not None:
+                self._sched()
+        except Exception:
+            self.lib.spdm_destroy(self._h)
+            self._h, self._keep = old, old_keep
+            raise
+        self.lib.spdm_destroy(old)
+        self._keep = []
+        self._weights_loaded = True
+        self._index = [(e.name.decode(), int(e.offset), tuple(e.shape[d] for d in range(e.ndim))) for e in idx]
+        self._blob_floats = int(blob.size)
 
     def set_scheduler(self, sched) -> None:
         """Install the tables of a host scheduler object (schedulers.py) for the loop."""
@@ -150,12 +193,14 @@ class SpdmEngine:
                                                      ts.ctypes.data_as(ctypes.c_void_p),
                                                      coef.ctypes.data_as(ctypes.c_void_p)), "spdm_set_schedule_tables")
         self.n_steps, self.kind = int(ts.size), int(sched.kind)
+        self._sched = lambda: self.set_scheduler(sched)
 
     def set_builtin_schedule(self, kind: int, num_train_timesteps: int, num_inference_steps: int,
                              beta_start: float = 1e-4, beta_end: float = 0.02) -> None:
         _lib.check(self.lib.spdm_set_schedule(self._h, kind, num_train_timesteps, num_inference_steps,
                                               beta_start, beta_end), "spdm_set_schedule")
         self.n_steps, self.kind = int(num_inference_steps), int(kind)
+        self._sched = lambda: self.set_builtin_schedule(kind, num_train_timesteps, num_inference_steps, beta_start, beta_end)
 
     # -- the noise predictor ------------------------------------------------------------------
     def unet_forward(self, x: torch.Tensor, t, cond: Optional[torch.Tensor]) -> torch.Tensor:
@@ -168,6 +213,38 @@ class SpdmEngine:
         _lib.check(self.lib.spdm_unet_forward(self._h, B, _ptr(xs), tt.ctypes.data_as(ctypes.c_void_p), int(tt.size),
                                               _ptr(cs), _ptr(eps), self._stream()), "spdm_unet_forward")
         return eps
+
+    # -- training ---------------------------------------------------------------------------------
+    def loss_and_grad(self, x_noisy: torch.Tensor, t, cond: Optional[torch.Tensor], noise: torch.Tensor,
+                      flat: bool = False):
+        """One training step's forward and backward pass (models/diffusion_ddpm.py:128-173): eps = unet(x_noisy, t, cond),
+        loss = mean((noise - eps)^2), and the gradients of loss.  Returns ``(loss, eps, grads, grad_cond)``: ``grads`` maps
+        every state_dict name to its gradient (torch layout, on the device) -- or, ``flat=True``, is one flat tensor laid
+        out as the packed state_dict; ``grad_cond`` is d loss / d cond (None without cond)."""
+        if not self.train:
+            raise RuntimeError("loss_and_grad needs an engine created with train=True")
+        if not self._weights_loaded:
+            raise RuntimeError("load_state_dict first")
+        B = x_noisy.shape[0]
+        H, D = self.horizon, self.state_dim
+        xs = self._dev(x_noisy, (B, H, D))
+        ns = self._dev(noise, (B, H, D))
+        cs = self._dev(cond, (B, self.cond_dim)) if cond is not None else None
+        tt = np.ascontiguousarray(torch.as_tensor(t).reshape(-1).cpu().numpy().astype(np.int32))
+        loss = torch.empty((), device=self.device, dtype=torch.float32)
+        eps = torch.empty((B, 1, H, D), device=self.device, dtype=torch.float32)
+        g = torch.empty(self._blob_floats, device=self.device, dtype=torch.float32)
+        gc = torch.empty((B,) + tuple(cond.shape[1:]), device=self.device, dtype=torch.float32) if cs is not None else None
+        _lib.check(self.lib.spdm_train_loss_grad(self._h, B, _ptr(xs), tt.ctypes.data_as(ctypes.c_void_p), int(tt.size),
+                                                 _ptr(cs), _ptr(ns), _ptr(loss), _ptr(eps), _ptr(g), _ptr(gc),
+                                                 self._stream()), "spdm_train_loss_grad")
+        if flat:
+            return loss, eps, g, gc
+        grads = {}
+        for name, off, shape in self._index:
+            n = int(np.prod(shape)) if shape else 1
+            grads[name] = g[off:off + n].view(shape)
+        return loss, eps, grads, gc
 
     # -- the sampling loop --------------------------------------------------------------------
     def sample_begin(self, cond, x_T, noise=None, inpaint=None, seed: int = 0, sample_offset: int = 0,
