@@ -615,24 +615,32 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned
 // each reads 4 of the 64 feature channels, a 4-step xor-shuffle finishes the dot product.  The
 // scheduler arithmetic uses explicitly rounded fp32 operations (no FMA contraction) in the
 // library's operation order, so that with identical eps the update is bit-identical to torch's.
+// EPS_IN: eps was computed by sa6's epilogue (StepArgs::eps_in, one thread per element): everything after the dot product.
+template <bool EPS_IN>
 __global__ __launch_bounds__(256) void out_step_kernel(const StepArgs a) {
     const size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t e = gt >> 4;
-    const int l16 = (int)(gt & 15);
+    const size_t e = EPS_IN ? gt : gt >> 4;
+    const int l16 = EPS_IN ? 0 : (int)(gt & 15);
     const size_t E = (size_t)a.B * a.H0 * a.D;
     const bool live = e < E;
     const size_t ee = live ? e : 0;
     const int HD = a.H0 * a.D;
     const int b = (int)(ee / HD), he = (int)(ee - (size_t)b * HD);
     const int h0 = he / a.D, d = he - h0 * a.D;
-    const int p = (h0 + a.lh) * a.Wp + (d + a.lw);
-    const float4 f = *reinterpret_cast<const float4*>(a.feat + ((size_t)b * a.Hp * a.Wp + p) * 64 + l16 * 4);
-    const float4 w = *reinterpret_cast<const float4*>(a.w + l16 * 4);
-    float dot = (f.x * w.x + f.y * w.y) + (f.z * w.z + f.w * w.w);
+    float eps;
+    if constexpr (EPS_IN) {
+        if (!live) return;
+        eps = a.eps_in[e];
+    } else {
+        const int p = (h0 + a.lh) * a.Wp + (d + a.lw);
+        const float4 f = *reinterpret_cast<const float4*>(a.feat + ((size_t)b * a.Hp * a.Wp + p) * 64 + l16 * 4);
+        const float4 w = *reinterpret_cast<const float4*>(a.w + l16 * 4);
+        float dot = (f.x * w.x + f.y * w.y) + (f.z * w.z + f.w * w.w);
 #pragma unroll
-    for (int o = 8; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
-    const float eps = dot + a.bias;
-    if (!live || l16 != 0) return;
+        for (int o = 8; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
+        eps = dot + a.bias;
+        if (!live || l16 != 0) return;
+    }
     if (a.eps_out != nullptr) {
         a.eps_out[e] = eps;
         if (!(fabsf(eps) <= 3.0e38f)) *a.flag_dev = 1;
@@ -675,8 +683,8 @@ __global__ __launch_bounds__(256) void out_step_kernel(const StepArgs a) {
 hipError_t launch_out_step(const StepArgs& a, hipStream_t s) {
     const size_t E = (size_t)a.B * a.H0 * a.D;
     if (E == 0) return hipErrorInvalidValue;
-    const size_t threads = E * 16;
-    hipLaunchKernelGGL(out_step_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, a);
+    const size_t threads = a.eps_in ? E : E * 16;
+    hipLaunchKernelGGL(a.eps_in ? out_step_kernel<true> : out_step_kernel<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -58,6 +58,7 @@ enum : unsigned {
     SW_NO_SA_TAIL = 1u << 9, SW_ATTN_VALU = 1u << 10, SW_SA_NO_WLDS = 1u << 11, SW_NO_FILM_FOLD = 1u << 12,
     SW_NO_GRAPH = 1u << 13, SW_NO_SPLITK = 1u << 14, SW_ARENA_TRACE = 1u << 15, SW_NO_WIDE_PIPE = 1u << 16, SW_NO_SKINNY = 1u << 17, SW_DEEP = 1u << 18,
     SW_NO_FILM_LOCAL = 1u << 19, SW_NO_FUSED_SRC = 1u << 20, SW_FILM_LOCAL = 1u << 21, SW_PIN_GEOMETRY = 1u << 22, SW_NO_WP4 = 1u << 23, SW_G2 = 1u << 24, SW_NO_WP8 = 1u << 25, SW_NO_SA_HEAD = 1u << 26, SW_SA_HEAD = 1u << 27, SW_NO_REG64 = 1u << 28,
+    SW_NO_SA_CROP = 1u << 29, SW_NO_SA_OUTC = 1u << 30,
 };
 struct SwitchName { const char* env; unsigned bit; };
 inline const SwitchName* switch_table(int* n) {
@@ -70,7 +71,8 @@ inline const SwitchName* switch_table(int* n) {
         {"SPDM_NO_FILM_LOCAL", SW_NO_FILM_LOCAL}, {"SPDM_NO_FUSED_SRC", SW_NO_FUSED_SRC},
         {"SPDM_FILM_LOCAL", SW_FILM_LOCAL}, {"SPDM_PIN_GEOMETRY", SW_PIN_GEOMETRY},
         {"SPDM_NO_WP4", SW_NO_WP4}, {"SPDM_G2", SW_G2}, {"SPDM_NO_WP8", SW_NO_WP8},
-        {"SPDM_NO_SA_HEAD", SW_NO_SA_HEAD}, {"SPDM_SA_HEAD", SW_SA_HEAD}, {"SPDM_NO_REG64", SW_NO_REG64}};
+        {"SPDM_NO_SA_HEAD", SW_NO_SA_HEAD}, {"SPDM_SA_HEAD", SW_SA_HEAD}, {"SPDM_NO_REG64", SW_NO_REG64},
+        {"SPDM_NO_SA_CROP", SW_NO_SA_CROP}, {"SPDM_NO_SA_OUTC", SW_NO_SA_OUTC}};
     *n = (int)(sizeof(t) / sizeof(t[0]));
     return t;
 }
@@ -249,6 +251,7 @@ struct StepArgs {
     const float* w; float bias;   // outc 1x1 conv
     float* x;                     // (B, H0, D) current iterate, updated in place
     float* eps_out;               // non-null: only write eps (spdm_unet_forward)
+    const float* eps_in;          // non-null: eps [B][H0][D] already computed (sa6's epilogue, SaCrop::eps); feat, w, bias unused
     const float* coef;            // device [n_steps][6]
     const int* step_dev;          // device scalar: loop iteration
     int kind;
@@ -307,10 +310,15 @@ bool sa_fused_supported(int L, int C);
 // w_hl: {Wqkv hi, lo, Wo hi, lo, W1 hi, lo, W2 hi, lo} as fp16 [rows][64], input axis permuted by perm16 inside
 // each group of 16, pre-scaled by 128 (spdm_api.hip: Loader::perm_split)
 // ab (optional): the block input is ab-affine of x per sample (film_coef_kernel), applied on load
+// crop (optional): the block's only consumer is outc + unpad (sa6), so only the H0 x D tokens at (lh, lw) of the Hp x Wp map
+// are computed (sa_crop64_kernel): out holds the block output at those tokens only, or -- eps non-null -- outc is applied in the
+// epilogue and eps [B][H0][D] is written instead of out
+struct SaCrop { int H0, D, Wp, lh, lw; const float* outc_w; float outc_b; float* eps; };
+bool sa_crop_supported(int L, int C, int H0, int D);
 hipError_t launch_sa_fused64(const float* x, float* out, int B, int L, const float* ln1_g, const float* ln1_b,
                              const float* ln2_g, const float* ln2_b, const void* const w_hl[8], const float* bqkv,
                              const float* bo, const float* b1, const float* b2, const float* ab, unsigned sw, hipStream_t s,
-                             const FilmSpec* fs = nullptr);
+                             const FilmSpec* fs = nullptr, const SaCrop* crop = nullptr);
 
 // ---- row-wise tail of a C = 128 / 256 SelfAttention block (sa_tail.hip): out_proj + x -> LayerNorm -> ff1 -> GELU -> ff2 + av ----
 bool sa_tail_supported(int C, unsigned sw);

@@ -52,6 +52,8 @@ struct SaFusedArgs {
     const float *bqkv, *bo, *b1, *b2;
     const float* ab;       // optional [B][2][64]: the block input is y = A x + B per sample (FiLM tail folded into the load)
     FilmSpec fs;           // fs.on: ... with the coefficients evaluated here (wave 0, film_coef_row_wave) instead of read from ab
+    SaCrop crop;           // sa_crop64_kernel: the query tokens (the H0 x D rectangle at (lh, lw) of the Hp x Wp map) and outc
+    int Q, qw;             //   Q = H0 D queries, qw per wave
 };
 
 typedef unsigned s_u32x4 __attribute__((ext_vector_type(4)));
@@ -98,6 +100,24 @@ __device__ __forceinline__ s_f32x16 sa_gemm_tile(const _Float16* __restrict__ Wh
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[ks], acc, 0, 0, 0);
     }
     return acc;
+}
+// the same product for two B operands (two token tiles): each weight fragment is loaded once for both
+__device__ __forceinline__ void sa_gemm_tile2(const _Float16* __restrict__ Wh, const _Float16* __restrict__ Wl, int row0, int li,
+                                              int kh, const s_f16x8 (&bh0)[4], const s_f16x8 (&bl0)[4], const s_f16x8 (&bh1)[4],
+                                              const s_f16x8 (&bl1)[4], s_f32x16& acc0, s_f32x16& acc1) {
+    const _Float16* ph = Wh + ((size_t)(row0 >> 5) * 256 + 32 * kh + li) * 8;
+    const _Float16* pl = Wl + ((size_t)(row0 >> 5) * 256 + 32 * kh + li) * 8;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+        const s_f16x8 ah = *reinterpret_cast<const s_f16x8*>(ph + 512 * ks);
+        const s_f16x8 al = *reinterpret_cast<const s_f16x8*>(pl + 512 * ks);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh0[ks], acc0, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl0[ks], acc0, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh0[ks], acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh1[ks], acc1, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl1[ks], acc1, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh1[ks], acc1, 0, 0, 0);
+    }
 }
 // same product with the weight rows staged in LDS (rows padded 128 -> 144 bytes: 32 rows x 16 bytes conflict-free)
 constexpr int SA_WROW = 72;          // halfs per staged weight row
@@ -543,6 +563,284 @@ __global__ __launch_bounds__(512, 2) void sa_fused64_kernel(const SaFusedArgs a)
     }   // trajectories of this workgroup
 }
 
+// Query-cropped block for the last SelfAttention (sa6), whose only consumer is outc + unpad: only the Q = H0 D tokens of the
+// unpadded trajectory are ever read.  Every token still needs LayerNorm 1 and its K / V (each query attends to all L keys),
+// but the q projection, the attention loop, out-proj, residual, LayerNorm 2, the feed-forward and the store run for the Q
+// query tokens only, packed densely onto the MFMA columns: wave w owns queries w qw .. w qw + qw - 1 (qw = ceil(Q / nwave)
+// of its 32 lanes; at H0 = 32, D = 3: 24 of 32).  nwave = min(4, key tiles); wave w projects the K / V of key tiles w and
+// w + nwave (same LDS layout as the un-staged sa_fused64: two workgroups per CU, weights read from L2).  One trajectory per
+// workgroup, so nothing depends on the batch or the grid.  The per-query arithmetic is that of sa_fused64.
+// OUTC: the epilogue also applies outc (Conv2d(64, 1, 1) + bias) and writes eps [B][H0][D] instead of the 64 channels.
+template <bool FULL, bool OUTC>
+__global__ __launch_bounds__(256, 2) void sa_crop64_kernel(const SaFusedArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sa_smem[];
+    const int L = a.L;
+    const int nwave = blockDim.x >> 6;
+    const int nkb = (L + 31) / 32;                 // key tiles
+    const int Lp = nkb * 32;
+    const int VROW = Lp + 8;
+    // K hi | K lo | V^T hi | V^T lo | FiLM row  (sa_fused64 without staged weights)
+    _Float16* const Khi = reinterpret_cast<_Float16*>(sa_smem);
+    _Float16* const Klo = Khi + (size_t)Lp * SA_KROW;
+    _Float16* const Vhi = Klo + (size_t)Lp * SA_KROW;
+    _Float16* const Vlo = Vhi + (size_t)32 * VROW;
+    float* const ab_s = reinterpret_cast<float*>(Vlo + (size_t)32 * VROW);
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 31, kh = lane >> 5;
+    const int b = blockIdx.x;
+    const int tk0 = wave * 32 + li, tk1 = (wave + nwave) * 32 + li;     // this lane's key / value tokens
+    const bool two = wave + nwave < nkb;                                 // (wave-uniform) second key tile
+    // this lane's query: index qi of the row-major H0 x D crop.  Lanes past qw (or past Q) duplicate a live query and store nothing.
+    const int qraw = wave * a.qw + li;
+    const bool qlive = li < a.qw && qraw < a.Q;
+    const int qi = min(qraw, a.Q - 1);
+    const int qh = qi / a.crop.D, qd = qi - qh * a.crop.D;
+    const int tq = (a.crop.lh + qh) * a.crop.Wp + a.crop.lw + qd;
+
+    for (int i = tid; i < 16 * VROW; i += blockDim.x) {      // constant rows 16..31 of V^T (see sa_fused64)
+        const int row = i / VROW;
+        Vhi[16 * VROW + i] = (row == 0 || row == 4) ? (_Float16)1.0f : (_Float16)0.f;
+        Vlo[16 * VROW + i] = (_Float16)0.f;
+    }
+    const bool fold = a.ab != nullptr || a.fs.on;
+    if (fold) {
+        if (a.fs.on) {
+            if (tid < 64) film_coef_row_wave(a.fs, b, tid, ab_s);
+        } else if (tid < 2 * SA_C / 4) {
+            *reinterpret_cast<s_f32x4*>(ab_s + 4 * tid) = *reinterpret_cast<const s_f32x4*>(a.ab + (size_t)b * 2 * SA_C + 4 * tid);
+        }
+        __syncthreads();
+    }
+    const float* xb = a.x + (size_t)b * L * SA_C;
+    const float* xq = xb + (size_t)tq * SA_C;
+    const float* xk0 = xb + (size_t)min(tk0, L - 1) * SA_C;
+    const float* xk1 = xb + (size_t)min(tk1, L - 1) * SA_C;
+
+    s_f16x8 bh[4], bl[4];
+    s_f32x16 av[2];
+#pragma unroll
+    for (int T = 0; T < 2; ++T)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) av[T][r] = 0.f;
+
+    // LayerNorm-1 fragments of the token at row xr_ into bh_ / bl_ (normalised in place: registers are the limit here)
+#define SA_LN1_FRAGS(xr_, bh_, bl_)                         \
+    {                                                       \
+        s_f32x16 x1_[2];                                    \
+        SA_LOAD_X(x1_, xr_)                                 \
+        sa_layernorm(x1_, x1_, a.ln1_g, a.ln1_b, kh);       \
+        sa_make_frags(x1_, bh_, bl_);                       \
+    }
+    // z -> (z * DESCALE + bias[row0 + feature]) * sc
+    auto bias_tile = [&](s_f32x16& z, int row0, float sc) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const s_f32x4 bb = *reinterpret_cast<const s_f32x4*>(a.bqkv + row0 + 8 * g + 4 * kh);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) z[4 * g + j] = (z[4 * g + j] * SA_DESCALE + bb[j]) * sc;
+        }
+    };
+    // K and V of one token and head, split as they go to LDS (made right after the projection: the fp32 tiles die early)
+    struct KV { s_f16x8 k_h, k_l; s_u32x4 v_h, v_l; };
+    auto pack_kv = [&](const s_f32x16& kt, const s_f32x16& vt, KV (&kv)[2]) {
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+            sa_split8(kv[sub].k_h, kv[sub].k_l, [&](int j) { return kt[8 * sub + j] * 16.0f; });
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                unsigned hu, lu;
+                split_pair_f16(vt[8 * sub + 2 * q] * 16.0f, vt[8 * sub + 2 * q + 1] * 16.0f, hu, lu);
+                kv[sub].v_h[q] = hu;
+                kv[sub].v_l[q] = lu;
+            }
+        }
+    };
+    // K row and V^T column of token t
+    auto store_kv = [&](int t, const KV& kv) {
+        *reinterpret_cast<s_f16x8*>(Khi + t * SA_KROW + 8 * kh) = kv.k_h;
+        *reinterpret_cast<s_f16x8*>(Klo + t * SA_KROW + 8 * kh) = kv.k_l;
+        const int tp = (t & ~12) | ((t & 4) << 1) | ((t & 8) >> 1);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {                // V^T[d][token], d = 8 (q>>1) + 4 kh + 2 (q&1) + 0..1
+            const s_f16x2 h2 = __builtin_bit_cast(s_f16x2, (unsigned)kv.v_h[q]), l2 = __builtin_bit_cast(s_f16x2, (unsigned)kv.v_l[q]);
+            const int dd = 8 * (q >> 1) + 4 * kh + 2 * (q & 1);
+            Vhi[dd * VROW + tp] = h2[0];
+            Vlo[dd * VROW + tp] = l2[0];
+            Vhi[(dd + 1) * VROW + tp] = h2[1];
+            Vlo[(dd + 1) * VROW + tp] = l2[1];
+        }
+    };
+
+    for (int p = 0; p < 2; ++p) {
+        KV kv0[2], kv1[2];
+        s_f16x8 qh[2], ql[2];
+        // K / V of the key tiles (both tiles in one pass over the weights: the same fragments, loaded once)
+        if (two) {
+            s_f16x8 bh1[4], bl1[4];
+            SA_LN1_FRAGS(xk0, bh, bl)
+            SA_LN1_FRAGS(xk1, bh1, bl1)
+            s_f32x16 kt0, kt1, vt0, vt1;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { kt0[r] = 0.f; kt1[r] = 0.f; vt0[r] = 0.f; vt1[r] = 0.f; }
+            sa_gemm_tile2(a.wqkv_h, a.wqkv_l, 64 + 32 * p, li, kh, bh, bl, bh1, bl1, kt0, kt1);
+            sa_gemm_tile2(a.wqkv_h, a.wqkv_l, 128 + 32 * p, li, kh, bh, bl, bh1, bl1, vt0, vt1);
+            bias_tile(kt0, 64 + 32 * p, 1.0f);
+            bias_tile(vt0, 128 + 32 * p, 1.0f);
+            bias_tile(kt1, 64 + 32 * p, 1.0f);
+            bias_tile(vt1, 128 + 32 * p, 1.0f);
+            pack_kv(kt0, vt0, kv0);
+            pack_kv(kt1, vt1, kv1);
+        } else {
+            SA_LN1_FRAGS(xk0, bh, bl)
+            s_f32x16 kt, vt;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { kt[r] = 0.f; vt[r] = 0.f; }
+            kt = sa_gemm_tile(a.wqkv_h, a.wqkv_l, 64 + 32 * p, li, kh, bh, bl, kt);
+            vt = sa_gemm_tile(a.wqkv_h, a.wqkv_l, 128 + 32 * p, li, kh, bh, bl, vt);
+            bias_tile(kt, 64 + 32 * p, 1.0f);
+            bias_tile(vt, 128 + 32 * p, 1.0f);
+            pack_kv(kt, vt, kv0);
+        }
+        {
+            SA_LN1_FRAGS(xq, bh, bl)
+            s_f32x16 qt;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) qt[r] = 0.f;
+            qt = sa_gemm_tile(a.wqkv_h, a.wqkv_l, 32 * p, li, kh, bh, bl, qt);
+            bias_tile(qt, 32 * p, 0.25f);          // 1/sqrt(16), applied to q like torch
+#pragma unroll
+            for (int sub = 0; sub < 2; ++sub) sa_split8(qh[sub], ql[sub], [&](int j) { return qt[8 * sub + j] * 16.0f; });
+        }
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+            const int head = 2 * p + sub;
+            const s_f16x8 q_h = qh[sub], q_l = ql[sub];
+            __syncthreads();                        // every wave is done with the previous head's K / V^T
+            store_kv(tk0, kv0[sub]);
+            if (two) store_kv(tk1, kv1[sub]);
+            __syncthreads();
+
+            // ---- flash attention of this wave's queries over all key blocks (sa_fused64's loop) ----
+            s_f32x16 acc_o;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc_o[r] = 0.f;
+            float m = -1e30f;
+            for (int kb = 0; kb < nkb; ++kb) {
+                s_f32x16 acc_s;
+                SA_SCORES(acc_s, kb)
+                constexpr float SC = 1.44269504088896340736f / 256.0f;
+                float sc[16];
+                float mraw = -3.0e38f;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    sc[r] = acc_s[r];
+                    if (!FULL) {
+                        const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                        if (key >= L) sc[r] = -3.0e38f;
+                    }
+                    mraw = fmaxf(mraw, sc[r]);
+                }
+                mraw = max_xor32(mraw);
+                const float m_new = fmaxf(m, mraw * SC);
+                if (__any(m_new > m)) {
+                    const float alpha = __builtin_amdgcn_exp2f(m - m_new);
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc_o[r] *= alpha;
+                }
+                const float off = 10.0f - m_new;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) sc[r] = __builtin_amdgcn_exp2f(__fmaf_rn(sc[r], SC, off));
+                m = m_new;
+#pragma unroll
+                for (int s2 = 0; s2 < 2; ++s2) {
+                    s_f16x8 p_h, p_l;
+                    sa_split8(p_h, p_l, [&](int j) { return sc[8 * s2 + j]; });
+                    const s_f16x8 v_h = *reinterpret_cast<const s_f16x8*>(Vhi + li * VROW + kb * 32 + 16 * s2 + 8 * kh);
+                    const s_f16x8 v_l = *reinterpret_cast<const s_f16x8*>(Vlo + li * VROW + kb * 32 + 16 * s2 + 8 * kh);
+                    acc_o = __builtin_amdgcn_mfma_f32_32x32x16_f16(v_h, p_h, acc_o, 0, 0, 0);
+                    acc_o = __builtin_amdgcn_mfma_f32_32x32x16_f16(v_h, p_l, acc_o, 0, 0, 0);
+                    acc_o = __builtin_amdgcn_mfma_f32_32x32x16_f16(v_l, p_h, acc_o, 0, 0, 0);
+                }
+            }
+            const float inv = 1.0f / (acc_o[8] * 16.0f);
+            s_f16x8 o_h, o_l;
+            sa_split8(o_h, o_l, [&](int j) { return (acc_o[j] * inv) * 16.0f; });
+#pragma unroll
+            for (int T = 0; T < 2; ++T) {
+                const s_f16x8 ah = *reinterpret_cast<const s_f16x8*>(a.wo_h + ((size_t)(4 * T + head) * 64 + 32 * kh + li) * 8);
+                const s_f16x8 al = *reinterpret_cast<const s_f16x8*>(a.wo_l + ((size_t)(4 * T + head) * 64 + 32 * kh + li) * 8);
+                av[T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, o_h, av[T], 0, 0, 0);
+                av[T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, o_l, av[T], 0, 0, 0);
+                av[T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, o_h, av[T], 0, 0, 0);
+            }
+        }
+    }
+#undef SA_LN1_FRAGS
+
+    // ---- av = out_proj + b_o + x;  feed-forward  (query tokens only) ----
+#pragma unroll
+    for (int T = 0; T < 2; ++T) {
+        sa_bias(av[T], a.bo, T, kh);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            s_f32x4 v = *reinterpret_cast<const s_f32x4*>(xq + 32 * T + 8 * g + 4 * kh);
+            if (fold)
+                v = v * *reinterpret_cast<const s_f32x4*>(ab_s + 32 * T + 8 * g + 4 * kh) +
+                    *reinterpret_cast<const s_f32x4*>(ab_s + SA_C + 32 * T + 8 * g + 4 * kh);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) av[T][4 * g + j] += v[j];
+        }
+    }
+    {
+        s_f32x16 ln[2];
+        sa_layernorm(av, ln, a.ln2_g, a.ln2_b, kh);
+        sa_make_frags(ln, bh, bl);
+    }
+    s_f32x16 f[2];
+#pragma unroll
+    for (int T = 0; T < 2; ++T) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) f[T][r] = 0.f;
+        f[T] = sa_gemm_tile(a.w1_h, a.w1_l, 32 * T, li, kh, bh, bl, f[T]);
+        sa_bias(f[T], a.b1, T, kh);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) f[T][r] = gelu_erf(f[T][r]);
+    }
+    sa_make_frags(f, bh, bl);
+#pragma unroll
+    for (int T = 0; T < 2; ++T) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) f[T][r] = 0.f;
+        f[T] = sa_gemm_tile(a.w2_h, a.w2_l, 32 * T, li, kh, bh, bl, f[T]);
+        sa_bias(f[T], a.b2, T, kh);
+    }
+    if constexpr (OUTC) {
+        // eps = outc_w . out + outc_b: this lane half's 32 features, then the other half's
+        float dot = 0.f;
+#pragma unroll
+        for (int T = 0; T < 2; ++T)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const s_f32x4 w = *reinterpret_cast<const s_f32x4*>(a.crop.outc_w + 32 * T + 8 * g + 4 * kh);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) dot += (f[T][4 * g + j] + av[T][4 * g + j]) * w[j];
+            }
+        dot = sum_xor32(dot);
+        if (qlive && kh == 0) a.crop.eps[(size_t)b * a.Q + qi] = dot + a.crop.outc_b;
+    } else if (qlive) {
+        float* orow = a.out + ((size_t)b * L + tq) * SA_C;
+#pragma unroll
+        for (int T = 0; T < 2; ++T)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const s_f32x4 v = {f[T][4 * g] + av[T][4 * g], f[T][4 * g + 1] + av[T][4 * g + 1],
+                                   f[T][4 * g + 2] + av[T][4 * g + 2], f[T][4 * g + 3] + av[T][4 * g + 3]};
+                *reinterpret_cast<s_f32x4*>(orow + 32 * T + 8 * g + 4 * kh) = v;
+            }
+    }
+}
+
 #ifdef SPDM_DIAG_SAF
 extern "C" int spdm_debug_saf_stamps(unsigned long long* out64) {
     return hipMemcpyFromSymbol(out64, HIP_SYMBOL(g_saf_stamps), sizeof(unsigned long long) * 64) == hipSuccess ? 0 : -1;
@@ -551,11 +849,23 @@ extern "C" int spdm_debug_saf_stamps(unsigned long long* out64) {
 
 bool sa_fused_supported(int L, int C) { return C == SA_C && L >= 1 && L <= 512; }
 
+static int sa_crop_waves(int L) { return std::min(4, (L + 31) / 32); }
+bool sa_crop_supported(int L, int C, int H0, int D) {
+    const int Q = H0 * D;
+    return C == SA_C && L >= 1 && L <= 256 && Q >= 1 && Q < L && Q <= 32 * sa_crop_waves(L);
+}
+
 hipError_t launch_sa_fused64(const float* x, float* out, int B, int L, const float* ln1_g, const float* ln1_b,
                              const float* ln2_g, const float* ln2_b, const void* const w_hl[8], const float* bqkv,
                              const float* bo, const float* b1, const float* b2, const float* ab, unsigned sw, hipStream_t s,
-                             const FilmSpec* fs) {
+                             const FilmSpec* fs, const SaCrop* crop) {
     if (!sa_fused_supported(L, SA_C) || B <= 0) return hipErrorInvalidValue;
+    if (crop) {
+        const SaCrop& c = *crop;
+        if (!sa_crop_supported(L, SA_C, c.H0, c.D) || c.lh < 0 || c.lw < 0 || c.Wp < 1 || c.lw + c.D > c.Wp ||
+            (c.lh + c.H0) * c.Wp > L || (c.eps != nullptr && c.outc_w == nullptr) || (c.eps == nullptr && out == nullptr))
+            return hipErrorInvalidValue;
+    }
     if (fs && (ab != nullptr || fs->C != SA_C)) return hipErrorInvalidValue;
     SaFusedArgs a{};
     a.x = x; a.out = out; a.L = L; a.nb = B;
@@ -568,6 +878,20 @@ hipError_t launch_sa_fused64(const float* x, float* out, int B, int L, const flo
     if (fs) { a.fs = *fs; a.fs.on = 1; }
     const bool pair = L > 256;                                                    // two workgroups per trajectory
     if (pair && (ab != nullptr || fs != nullptr)) return hipErrorInvalidValue;    // (the plan keeps film_apply there)
+    if (crop) {
+        a.crop = *crop;
+        a.Q = crop->H0 * crop->D;
+        const int nw = sa_crop_waves(L), Lp = (L + 31) / 32 * 32;
+        a.qw = (a.Q + nw - 1) / nw;
+        const size_t lds = ((size_t)2 * Lp * SA_KROW + (size_t)2 * 32 * (Lp + 8)) * sizeof(_Float16) + 2 * SA_C * sizeof(float);
+        const bool full = (L % 32 == 0), outc = crop->eps != nullptr;
+        void (*kern)(const SaFusedArgs) = full ? (outc ? sa_crop64_kernel<true, true> : sa_crop64_kernel<true, false>)
+                                               : (outc ? sa_crop64_kernel<false, true> : sa_crop64_kernel<false, false>);
+        if (lds > 64 * 1024)
+            if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, dim3(B), dim3(64 * nw), lds, s, a);
+        return hipGetLastError();
+    }
     const int nwave = pair ? 8 : (L + 31) / 32;
     const int Lp = pair ? 512 : nwave * 32;
     const bool wlds = !pair && (nwave >= 4) && !(sw & SW_SA_NO_WLDS);      // long sequences: weights staged in LDS

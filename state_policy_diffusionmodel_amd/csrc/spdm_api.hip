@@ -1239,16 +1239,36 @@ struct Ctx {
     bool sa_fused(const AttnW& w, int level) const {
         return h->split && sa_fused_supported(HWl(level), w.C) && !(h->sw & SW_NO_SA_FUSED) && (!h->weights_loaded || w.fw[0]);
     }
+    // The last block (sa6) feeds only outc + unpad, which read the H0 x D tokens of the trajectory: sa_fused64 then computes the
+    // block for those tokens only (SaCrop).  Not in debug runs (the a6 tap keeps its full meaning).
+    bool sa_crop(const AttnW& w, int level) const {
+        return sa_fused(w, level) && !h->arena.keep && !(h->sw & SW_NO_SA_CROP) &&
+               sa_crop_supported(HWl(level), w.C, h->cfg.horizon, h->cfg.state_dim);
+    }
+    bool eps_ready = false;    // the plan's final tensor holds eps [B][H0][D] (outc applied by sa6's epilogue): StepArgs::eps_in
     // ab (optional): x is the RAW conv output and the block input is ab-affine of it (film_coef); consumed here.
     // fs (optional, instead of ab): the kernels evaluate those coefficients themselves (FilmSpec, kernels.h)
-    Tensor attention(Tensor& x, StatsBuf& xs, const AttnW& w, int level, Tensor* ab = nullptr, const FilmSpec* fs = nullptr) {
+    // final_outc: the block's only consumer is outc + unpad (sa6 of plan_unet)
+    Tensor attention(Tensor& x, StatsBuf& xs, const AttnW& w, int level, Tensor* ab = nullptr, const FilmSpec* fs = nullptr,
+                     bool final_outc = false) {
         const int L = HWl(level), rows = B * L, C = w.C;
         const float* abp = (ab && ab->valid) ? ab->p : nullptr;
         if (sa_fused(w, level)) {            // whole block in one kernel (sa_fused.hip)
+            // (cropped: the same tensor is reserved -- the dry run sizes both routes alike -- and holds the block output at the
+            //  query tokens only, or, with outc folded in, eps [B][H0][D] at its start)
             Tensor out = talloc(C, level);
+            SaCrop crop{h->cfg.horizon, h->cfg.state_dim, h->Wp, h->lh, h->lw, nullptr, 0.f, nullptr};
+            const bool cropped = final_outc && sa_crop(w, level);
+            if (cropped && !(h->sw & SW_NO_SA_OUTC) && h->outc_w) {
+                crop.outc_w = h->outc_w;
+                crop.outc_b = h->outc_b;
+                crop.eps = out.p;
+                eps_ready = true;
+            }
             if (!err && !dry)
                 check(launch_sa_fused64(x.p, out.p, B, L, w.ln_g, w.ln_b, w.ff_ln_g, w.ff_ln_b, w.fw, w.in_proj.b,
-                                        w.out_proj.b, w.ff1.b, w.ff2.b, abp, h->sw, s, fs), "fused attention block");
+                                        w.out_proj.b, w.ff1.b, w.ff2.b, abp, h->sw, s, fs, cropped ? &crop : nullptr),
+                      "fused attention block");
             free(x);
             free(xs);
             if (ab) free(*ab);
@@ -1357,7 +1377,7 @@ struct Ctx {
     // the block tail (film_tail; tap `name` where it is materialised) and the SelfAttention block sa[blk] after it.  The attention
     // kernels finish the tail themselves from the raw tensor (film_local), take it as coefficients on load (film_foldable), or
     // read the materialised tensor.  Consumes v.
-    Tensor film_attention(Value& v, const ResampleW& w, int blk, int level, bool use_cond, const char* name) {
+    Tensor film_attention(Value& v, const ResampleW& w, int blk, int level, bool use_cond, const char* name, bool final_outc = false) {
         const AttnW& sa = h->sa[blk];
         StatsBuf ys;
         Tensor y, ab;
@@ -1365,7 +1385,7 @@ struct Ctx {
             const FilmSpec fs = film_spec(v, w, blk, use_cond);
             y = v.t;
             v.t.valid = false;
-            y = attention(y, ys, sa, level, nullptr, &fs);
+            y = attention(y, ys, sa, level, nullptr, &fs, final_outc);
             free(v);                               // (its statistics: released after the last launch that reads them is enqueued)
             return y;
         }
@@ -1375,7 +1395,7 @@ struct Ctx {
             y = film_tail(v, w, blk, level, use_cond, (h->cfg.attention && !sa_fused(sa, level)) ? &ys : nullptr);
             tap(name, y);
         }
-        if (h->cfg.attention) y = attention(y, ys, sa, level, &ab);
+        if (h->cfg.attention) y = attention(y, ys, sa, level, &ab, nullptr, final_outc);
         return y;
     }
     // debug runs (arena.keep): the finished tensor of a value with a pending GroupNorm, as tap `name`
@@ -1485,7 +1505,7 @@ static int plan_unet(Ctx& c, const float* x, bool use_cond, Tensor* feat_out) {
         }
         Value b3 = c.double_conv(a, h->up[i].dc2, lout);
         c.prof_end();
-        const Tensor y = c.film_attention(b3, h->up[i], 3 + i, lout, use_cond, un[i]);
+        const Tensor y = c.film_attention(b3, h->up[i], 3 + i, lout, use_cond, un[i], /*final_outc=*/i == 2);
         c.tap(an[i], y);
         Value nv;
         nv.t = y;
@@ -1633,9 +1653,10 @@ static int check_ready(spdm_handle* h, int B) {
     return SPDM_OK;
 }
 
-static StepArgs step_args(spdm_handle* h, int B, const Tensor& feat) {
+static StepArgs step_args(spdm_handle* h, int B, const Tensor& feat, bool eps_ready) {
     StepArgs a{};
     a.feat = feat.p; a.w = h->outc_w; a.bias = h->outc_b; a.x = h->d_x; a.eps_out = nullptr;
+    a.eps_in = eps_ready ? feat.p : nullptr;
     a.coef = h->d_coef; a.step_dev = h->d_step; a.kind = h->sched_kind;
     a.noise = h->s_noise; a.rng_dev = h->d_rng; a.flag_dev = h->d_step + 2;
     a.inpaint = h->s_inpaint; a.inp_h = h->s_inp_h; a.inpaint_per_sample = h->s_inp_per_sample;
@@ -1666,7 +1687,7 @@ extern "C" int spdm_unet_forward(spdm_handle* h, int32_t B, const float* d_x, co
     h->arena.reset();
     Tensor feat;
     SPDM_TRY(plan_net(c, h->d_x, d_cond != nullptr, &feat));
-    StepArgs a = step_args(h, B, feat);
+    StepArgs a = step_args(h, B, feat, c.eps_ready);
     a.eps_out = d_eps;
     a.ptrs_dev = nullptr;
     HIP_TRY(launch_out_step(a, s));
@@ -1719,7 +1740,7 @@ static int enqueue_step(spdm_handle* h, int i, hipStream_t s) {
     h->arena.reset();
     Tensor feat;
     SPDM_TRY(plan_net(c, h->d_x, h->have_film, &feat));
-    StepArgs a = step_args(h, h->sB, feat);
+    StepArgs a = step_args(h, h->sB, feat, c.eps_ready);
     HIP_TRY(launch_out_step(a, s));
     return SPDM_OK;
 }

@@ -54,7 +54,7 @@ def main():
         if is_conv3x3(k) and k in write:
             n += cnt
             tot += cnt * (2.0 * avg + write[k][1]) * 1024.0
-    steps = max(fetch.get("out_step_kernel", [1, 0])[0], 1)        # one out_step_kernel launch per denoise step
+    steps = max(sum(v[0] for k, v in fetch.items() if k.startswith("out_step_kernel")), 1)   # one out_step_kernel launch per denoise step
     outp = a.prefix + "_roofline_traffic" + sfx + ".json"
     json.dump({
         "kernel_class": "conv3x3_wide_kernel<...> + conv_reg64_kernel<...> + conv_gemm_kernel<HALO=true,...> + conv_skinny_kernel<...> (all 3x3/3x1 implicit-GEMM launches of a denoise step)",
