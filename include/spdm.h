@@ -88,9 +88,16 @@ typedef struct {
                                        pinned geometry, precision flags) behaves as for UNet_Film. */
 
 #define SPDM_FLAG_TRAIN 8         /* the handle also serves spdm_train_loss_grad: it keeps flipped / transposed weight copies for
-                                    the backward pass and a training workspace sized at max_batch.  UNet_Film_noAttention only:
-                                    spdm_create returns SPDM_ERR_INVALID with attention = 1 or SPDM_FLAG_SIMPLE_UNET.  Every
-                                    other entry point behaves as on a handle without the flag. */
+                                    the backward pass and a training workspace sized at max_batch.  UNet_Film_noAttention, or
+                                    UNet_Film (attention = 1) together with SPDM_FLAG_TRAIN_ATTENTION: spdm_create returns
+                                    SPDM_ERR_INVALID with attention = 1 and no SPDM_FLAG_TRAIN_ATTENTION, and with
+                                    SPDM_FLAG_SIMPLE_UNET.  Every other entry point behaves as on a handle without the flag. */
+
+#define SPDM_FLAG_TRAIN_ATTENTION 16   /* with SPDM_FLAG_TRAIN and attention = 1: spdm_train_loss_grad covers UNet_Film's six
+                                    SelfAttention blocks too (their weights' gradients are part of the blob).  Opt-in because its
+                                    workspace is larger.  SPDM_ERR_INVALID without SPDM_FLAG_TRAIN, with attention = 0, with
+                                    SPDM_FLAG_SIMPLE_UNET, and where a block's token count H_l x W_l exceeds 512 (horizon above
+                                    64).  Every other entry point behaves as on a plain attention handle. */
 
 /* One entry per tensor of the reference state_dict (names exactly as
  * UNet_Film.state_dict() gives them, e.g. "down1.cond_encoder.2.weight"),
@@ -171,7 +178,8 @@ int  spdm_sample(spdm_handle* h, int32_t B, const float* d_cond,
 
 /* Replaces: one training_step of Diffusion_DDPM up to loss.backward() (models/diffusion_ddpm.py:128-173,
  * process_single_batch): eps = unet(x_noisy, t, cond); loss = mean((noise - eps)^2); the gradients of the loss with respect to
- * every weight of the network and to cond.  Handle created with SPDM_FLAG_TRAIN (SPDM_ERR_STATE otherwise).
+ * every weight of the network and to cond.  Handle created with SPDM_FLAG_TRAIN (SPDM_ERR_STATE otherwise); a UNet_Film handle
+ * (attention = 1) also needs SPDM_FLAG_TRAIN_ATTENTION, and then its gradient covers the sa1 .. sa6 tensors.
  *  d_x_noisy, d_noise (B,H,D); h_t[t_count], t_count == 1 (broadcast) or B; d_cond (B,cond_dim) or NULL (no FiLM);
  *  d_loss     one float on the device;
  *  d_eps      NULL or (B,H,D): the predicted noise;

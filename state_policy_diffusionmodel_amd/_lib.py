@@ -17,6 +17,7 @@ SPDM_FLAG_DEBUG_KEEP = 1
 SPDM_FLAG_EXACT_FP32 = 2
 SPDM_FLAG_SIMPLE_UNET = 4
 SPDM_FLAG_TRAIN = 8
+SPDM_FLAG_TRAIN_ATTENTION = 16
 ABI_VERSION = 2
 
 

@@ -297,6 +297,22 @@ hipError_t launch_add_cols(const float* src, int ld, int c0, long long M, int C,
 hipError_t launch_mish_bwd(const float* dm, int nblk, int B, int ld, const float* cond, int cond_dim, float* grad_cond,
                            hipStream_t s);
 
+// train_attn.hip: the SelfAttention blocks of the training pass (SPDM_FLAG_TRAIN_ATTENTION), exact fp32.  Rows are tokens, [rows][C].
+// LayerNorm(C), C in {64, 128, 256}: y, and the per-row mean and 1 / std the backward pass reads
+hipError_t launch_ln_fwd(const float* x, const float* g, const float* b, long long rows, int C, float* y, float* mean, float* rstd,
+                         hipStream_t s);
+// dx = LayerNorm backward of gy (+ add, may be null); part [ln_bwd_blocks(rows)][2C]: per-workgroup [d gamma | d beta] partials
+constexpr int LN_BWD_ROWS = 64;
+int ln_bwd_blocks(long long rows);
+hipError_t launch_ln_bwd(const float* x, const float* mean, const float* rstd, const float* gamma, const float* gy,
+                         const float* add, long long rows, int C, float* dx, float* part, hipStream_t s);
+hipError_t launch_gelu_bwd(const float* u, const float* dh, size_t n, float* du, hipStream_t s);
+// attention core with its log-sum-exp (lse [B heads][L]), and its backward into dqkv [B L][3C] (in_proj's packed layout)
+bool attn_train_supported(int L, int C, int heads);
+hipError_t launch_attn_fwd_lse(const float* qkv, float* out, float* lse, int B, int L, int C, int heads, hipStream_t s);
+hipError_t launch_attn_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int B, int L,
+                           int C, int heads, hipStream_t s);
+
 hipError_t launch_advance(int* step_dev, int* t_dev, const int* timesteps_dev, int n_steps, hipStream_t s);
 hipError_t launch_set_step(int* step_dev, int* t_dev, const int* timesteps_dev, int n_steps, int i, hipStream_t s);
 

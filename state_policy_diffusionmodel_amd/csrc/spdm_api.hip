@@ -117,7 +117,8 @@ struct ConvW { float* w = nullptr; float* ws = nullptr; float* wf = nullptr; int
                                          // cnorm > 0: real output channels of a channel-padded layer (its GroupNorm divides by these)   // ws: split-fp16 copy; wf: its fragment-order copy (conv_wide.hip)
 struct DoubleConvW { ConvW first, second; float* gamma = nullptr; float* beta = nullptr; };
 struct LinW { float* w = nullptr; float* ws = nullptr; float* b = nullptr; int in = 0, out = 0;
-              float* wt = nullptr; };   // wt (SPDM_FLAG_TRAIN, FiLM encoders): [in padded to 64][out], the data gradient's weights
+              float* wt = nullptr; };   // wt (SPDM_FLAG_TRAIN, FiLM encoders): [in padded to 64][out], the data gradient's weights;
+                                        // (SPDM_FLAG_TRAIN_ATTENTION, attention Linears): [in][out]
 struct ResampleW { DoubleConvW dc1, dc2; LinW emb, film; float* temb_table = nullptr; int cout = 0; };
 struct AttnW {
     LinW in_proj, out_proj, ff1, ff2;
@@ -144,6 +145,7 @@ struct spdm_handle {
     float outc_b = 0.f;
     bool weights_loaded = false, temb_ready = false;
     bool train = false;                   // SPDM_FLAG_TRAIN: spdm_train_loss_grad (train_pass)
+    bool train_attn = false;              // ... SPDM_FLAG_TRAIN_ATTENTION: through the SelfAttention blocks (TrainPass::sa_fwd / sa_bwd)
     std::map<std::string, size_t> grad_off;   // ... offset of every tensor in the last spdm_load_weights blob
     size_t grad_floats = 0;               // ... and that blob's size
     float* tws = nullptr;                 // ... training workspace (train_pass at max_batch)
@@ -415,8 +417,14 @@ extern "C" int spdm_create(const spdm_config* cfg, spdm_handle** out) {
         return fail(SPDM_ERR_INVALID, "cond_dim >= 0, max_batch >= 1, num_train_timesteps >= 1 required");
     if ((cfg->flags & SPDM_FLAG_SIMPLE_UNET) && cfg->attention != 0)
         return fail(SPDM_ERR_INVALID, "SPDM_FLAG_SIMPLE_UNET (models/simple_Unet.py) has no attention blocks: attention must be 0");
-    if ((cfg->flags & SPDM_FLAG_TRAIN) && (cfg->attention != 0 || (cfg->flags & SPDM_FLAG_SIMPLE_UNET)))
-        return fail(SPDM_ERR_INVALID, "SPDM_FLAG_TRAIN serves UNet_Film_noAttention only (attention = 0, no SPDM_FLAG_SIMPLE_UNET)");
+    if ((cfg->flags & SPDM_FLAG_TRAIN_ATTENTION) &&
+        (!(cfg->flags & SPDM_FLAG_TRAIN) || cfg->attention == 0 || (cfg->flags & SPDM_FLAG_SIMPLE_UNET)))
+        return fail(SPDM_ERR_INVALID, "SPDM_FLAG_TRAIN_ATTENTION needs SPDM_FLAG_TRAIN and attention = 1 (UNet_Film), no SPDM_FLAG_SIMPLE_UNET");
+    if ((cfg->flags & SPDM_FLAG_TRAIN) && (cfg->flags & SPDM_FLAG_SIMPLE_UNET))
+        return fail(SPDM_ERR_INVALID, "SPDM_FLAG_TRAIN serves UNet_Film_noAttention, or UNet_Film with SPDM_FLAG_TRAIN_ATTENTION: not SPDM_FLAG_SIMPLE_UNET");
+    if ((cfg->flags & SPDM_FLAG_TRAIN) && cfg->attention != 0 && !(cfg->flags & SPDM_FLAG_TRAIN_ATTENTION))
+        return fail(SPDM_ERR_INVALID, "SPDM_FLAG_TRAIN with attention = 1 (UNet_Film) needs SPDM_FLAG_TRAIN_ATTENTION as well; "
+                                      "without it the flag serves UNet_Film_noAttention only (attention = 0)");
     if ((cfg->flags & SPDM_FLAG_SIMPLE_UNET) && cfg->cond_dim < 1)
         return fail(SPDM_ERR_INVALID, "SPDM_FLAG_SIMPLE_UNET needs cond_dim >= 1 (the network is only defined with conditioning)");
     HIP_TRY(hipSetDevice(cfg->device));
@@ -424,6 +432,7 @@ extern "C" int spdm_create(const spdm_config* cfg, spdm_handle** out) {
     h->cfg = *cfg;
     h->simple = (cfg->flags & SPDM_FLAG_SIMPLE_UNET) != 0;
     h->train = (cfg->flags & SPDM_FLAG_TRAIN) != 0;
+    h->train_attn = (cfg->flags & SPDM_FLAG_TRAIN_ATTENTION) != 0;
     h->sw = switches_from_env();          // the ONLY place the product path reads SPDM_* switches
     if (const char* pe = getenv("SPDM_PREC")) h->split = !(strcmp(pe, "f32") == 0 || strcmp(pe, "fp32") == 0);
     if (cfg->flags & SPDM_FLAG_EXACT_FP32) h->split = false;
@@ -436,6 +445,16 @@ extern "C" int spdm_create(const spdm_config* cfg, spdm_handle** out) {
     h->film_kp = (int)align_up((size_t)std::max(cfg->cond_dim, 1), 32);
     const int mb = cfg->max_batch;
     init_arch(h);
+    for (int i = 0; i < 6 && h->train_attn; ++i) {
+        const int lv = (i < 3) ? i + 1 : 2 - (i - 3);
+        const int L = (h->Hp >> lv) * (h->Wp >> lv);
+        if (!attn_train_supported(L, h->sa[i].C, 4)) {
+            const int C = h->sa[i].C;
+            spdm_destroy(h);
+            return fail(SPDM_ERR_INVALID, "SPDM_FLAG_TRAIN_ATTENTION: sa%d has %d tokens of %d channels; the training attention "
+                                          "kernels take 1 .. 512 tokens (horizon <= 64)", i + 1, L, C);
+        }
+    }
     int rc = SPDM_OK;
     do {
         if ((rc = dev_alloc(h, (void**)&h->d_t, sizeof(int) * mb))) break;
@@ -754,7 +773,22 @@ struct Loader {
         a.ff_ln_b = vec(p + ".ff_self.0.bias", C);
         a.ff1 = linear(p + ".ff_self.1.weight", p + ".ff_self.1.bias", C, C, C);
         a.ff2 = linear(p + ".ff_self.3.weight", p + ".ff_self.3.bias", C, C, C);
+        if (h->train_attn) {
+            a.in_proj.wt = transposed(p + ".attention.in_proj_weight", 3 * C, C);
+            a.out_proj.wt = transposed(p + ".attention.out_proj.weight", C, C);
+            a.ff1.wt = transposed(p + ".ff_self.1.weight", C, C);
+            a.ff2.wt = transposed(p + ".ff_self.3.weight", C, C);
+        }
         return a;
+    }
+    // (out, in) -> [in][out]: the weights of a Linear layer's data gradient (dx = dy W)
+    float* transposed(const std::string& name, int out, int in) {
+        const float* w = find(name, {out, in});
+        if (!w) return nullptr;
+        std::vector<float> t((size_t)in * out);
+        for (int o = 0; o < out; ++o)
+            for (int i = 0; i < in; ++i) t[(size_t)i * out + o] = w[(size_t)o * in + i];
+        return upload(t);
     }
 };
 
@@ -1852,7 +1886,8 @@ extern "C" int spdm_sample(spdm_handle* h, int32_t B, const float* d_cond, const
 }
 
 // -------------------------------------------------------------------------------------------------
-// Training-loss gradient of UNet_Film_noAttention (SPDM_FLAG_TRAIN, spdm_train_loss_grad).
+// Training-loss gradient of UNet_Film_noAttention (SPDM_FLAG_TRAIN, spdm_train_loss_grad), and of UNet_Film
+// with SPDM_FLAG_TRAIN_ATTENTION (the SelfAttention blocks after each block tail: sa_fwd / sa_bwd, section 8.3).
 // The forward half materialises every tensor the backward half reads -- each convolution's input (after GroupNorm + GELU, the
 // pool or the upsample + concat), its raw output and the per-sample GroupNorm statistics -- in the handle's training workspace,
 // a bump allocation whose size a dry run at max_batch fixed at create.  Convolutions and Linear layers are launches of the
@@ -2002,6 +2037,94 @@ struct TrainPass {
         }
         return dz;
     }
+
+    // ---- SelfAttention (SPDM_FLAG_TRAIN_ATTENTION; models/Unet_FiLmLayer.py:71-82) ----
+    // The block's tokens are the rows of its [B * HW][C] input, token-major already.  LN -> in_proj -> attention core -> out_proj
+    // + x -> LN -> ff1 -> GELU -> ff2 + a, the Linears on the exact fp32 GEMM path, the core on train_attn.hip's fp32 kernel.
+    static constexpr int HEADS = 4;        // nn.MultiheadAttention(C, 4)
+    struct SA {                  // one block's saved tensors
+        const float* x = nullptr; int C = 0, level = 0;
+        float *y1 = nullptr, *m1 = nullptr, *r1 = nullptr;     // LayerNorm 1 output and row statistics
+        float *qkv = nullptr, *o = nullptr, *lse = nullptr;    // in_proj output, attention core output, its log-sum-exp
+        float *a = nullptr, *y2 = nullptr, *m2 = nullptr, *r2 = nullptr;   // out_proj(o) + x, LayerNorm 2
+        float *u = nullptr, *gl = nullptr, *out = nullptr;     // ff1 output, GELU(u), block output
+    };
+    void lin_fwd(const LinW& w, const float* x, long long M, int epi, float* y, const float* resid = nullptr) {
+        if (!run()) return;
+        chk(launch_gemm(linear_args(AffineSrc{x, w.in}, (int)M, 0, w, false, sw(), epi, y, resid), s), "attention Linear");
+    }
+    // dx = dy W: the forward kernels with the transposed copy
+    void lin_dgrad(const LinW& w, const float* dy, long long M, float* dx) {
+        if (!run()) return;
+        if (!w.wt) { err = fail(SPDM_ERR_STATE, "train: transposed attention weights missing"); return; }
+        chk(launch_gemm(gemm_args((int)M, 0, 1, 1, w.out, w.in, 1, 0, sw(), nullptr, PRO_NONE, AffineSrc{dy, w.out}, 0, AffineSrc{},
+                                  w.wt, nullptr, dx, w.in, EPI_PLAIN, nullptr), s), "attention Linear data gradient");
+    }
+    void lin_wb(const float* dy, const float* x, long long M, int Co, int Ci, const std::string& wn, const std::string& bn) {
+        wgrad(dy, Co, x, Ci, M, 0, 1, Co, Ci, 0, G(wn));
+        if (float* gb = G(bn); run()) chk(launch_colsum(dy, Co, M, Co, gb, s), "bias gradient");
+    }
+    void ln_param(const float* part, int nblk, int C, const std::string& gn, const std::string& bn) {
+        float* dg = G(gn);
+        float* db = G(bn);
+        if (!run()) return;
+        chk(launch_colsum(part, 2 * C, nblk, C, dg, s), "LayerNorm affine gradient");
+        chk(launch_colsum(part + C, 2 * C, nblk, C, db, s), "LayerNorm affine gradient");
+    }
+    SA sa_fwd(int i, const float* x, int level) {
+        const AttnW& w = h->sa[i];
+        SA a;
+        a.x = x; a.C = w.C; a.level = level;
+        const long long M = (long long)B * HWl(level);
+        const size_t n = (size_t)M * a.C;
+        a.y1 = alloc(n); a.m1 = alloc(M); a.r1 = alloc(M);
+        a.qkv = alloc(3 * n); a.o = alloc(n); a.lse = alloc((size_t)M * HEADS);
+        a.a = alloc(n); a.y2 = alloc(n); a.m2 = alloc(M); a.r2 = alloc(M);
+        a.u = alloc(n); a.gl = alloc(n); a.out = alloc(n);
+        if (!run()) return a;
+        chk(launch_ln_fwd(x, w.ln_g, w.ln_b, M, a.C, a.y1, a.m1, a.r1, s), "LayerNorm");
+        lin_fwd(w.in_proj, a.y1, M, EPI_BIAS, a.qkv);
+        if (run()) chk(launch_attn_fwd_lse(a.qkv, a.o, a.lse, B, HWl(level), a.C, HEADS, s), "attention core");
+        lin_fwd(w.out_proj, a.o, M, EPI_BIAS_RESID, a.a, x);
+        if (run()) chk(launch_ln_fwd(a.a, w.ff_ln_g, w.ff_ln_b, M, a.C, a.y2, a.m2, a.r2, s), "LayerNorm");
+        lin_fwd(w.ff1, a.y2, M, EPI_BIAS, a.u);
+        if (run()) chk(launch_gelu(a.u, a.gl, n, s), "GELU");
+        lin_fwd(w.ff2, a.gl, M, EPI_BIAS_RESID, a.out, a.a);
+        return a;
+    }
+    // dout: the gradient of the block output; returns the gradient of its input
+    float* sa_bwd(int i, const SA& a, const float* dout) {
+        const AttnW& w = h->sa[i];
+        const std::string p = "sa" + std::to_string(i + 1);
+        const long long M = (long long)B * HWl(a.level);
+        const size_t n = (size_t)M * a.C;
+        const int C = a.C, nblk = ln_bwd_blocks(M);
+        float* dgl = alloc(n);
+        float* du = alloc(n);
+        float* dy2 = alloc(n);
+        float* da = alloc(n);
+        float* dob = alloc(n);
+        float* dqkv = alloc(3 * n);
+        float* dy1 = alloc(n);
+        float* dx = alloc(n);
+        float* part = alloc((size_t)nblk * 2 * C);
+        if (!run()) return dx;
+        lin_wb(dout, a.gl, M, C, C, p + ".ff_self.3.weight", p + ".ff_self.3.bias");
+        lin_dgrad(w.ff2, dout, M, dgl);
+        if (run()) chk(launch_gelu_bwd(a.u, dgl, n, du, s), "GELU backward");
+        lin_wb(du, a.y2, M, C, C, p + ".ff_self.1.weight", p + ".ff_self.1.bias");
+        lin_dgrad(w.ff1, du, M, dy2);
+        if (run()) chk(launch_ln_bwd(a.a, a.m2, a.r2, w.ff_ln_g, dy2, dout, M, C, da, part, s), "LayerNorm backward");   // + residual
+        ln_param(part, nblk, C, p + ".ff_self.0.weight", p + ".ff_self.0.bias");
+        lin_wb(da, a.o, M, C, C, p + ".attention.out_proj.weight", p + ".attention.out_proj.bias");
+        lin_dgrad(w.out_proj, da, M, dob);
+        if (run()) chk(launch_attn_bwd(a.qkv, a.o, dob, a.lse, dqkv, B, HWl(a.level), C, HEADS, s), "attention core backward");
+        lin_wb(dqkv, a.y1, M, 3 * C, C, p + ".attention.in_proj_weight", p + ".attention.in_proj_bias");
+        lin_dgrad(w.in_proj, dqkv, M, dy1);
+        if (run()) chk(launch_ln_bwd(a.x, a.m1, a.r1, w.ln_g, dy1, da, M, C, dx, part, s), "LayerNorm backward");        // + residual
+        ln_param(part, nblk, C, p + ".ln.weight", p + ".ln.bias");
+        return dx;
+    }
 };
 
 static const char* const kDown[3] = {"down1", "down2", "down3"};
@@ -2044,6 +2167,8 @@ static int train_pass(TrainPass& T, const float* d_x, const float* d_cond, const
     const float* skips[4] = {inc.z, nullptr, nullptr, nullptr};     // x1 x2 x3 x4
     int skipC[4] = {64, 0, 0, 0};
     TrainPass::Block down[3], up[3];
+    TrainPass::SA sa[6];                              // SPDM_FLAG_TRAIN_ATTENTION: sa1 .. sa6
+    const bool attn = h->train_attn;
     for (int k = 0; k < 3; ++k) {
         const ResampleW& r = h->down[k];
         const int cin = r.dc1.first.cin, lv = k + 1;
@@ -2053,7 +2178,8 @@ static int train_pass(TrainPass& T, const float* d_x, const float* d_cond, const
         down[k].dc1 = T.dc_fwd(r.dc1, p, lv, false);
         down[k].dc2 = T.dc_fwd(r.dc2, down[k].dc1.z, lv, false);
         down[k].out = T.film_fwd(k, r, down[k].dc2, lv);
-        skips[k + 1] = down[k].out;
+        if (attn) sa[k] = T.sa_fwd(k, down[k].out, lv);
+        skips[k + 1] = attn ? sa[k].out : down[k].out;
         skipC[k + 1] = r.cout;
     }
     TrainPass::DC bot[3];
@@ -2071,7 +2197,8 @@ static int train_pass(TrainPass& T, const float* d_x, const float* d_cond, const
         up[k].dc1 = T.dc_fwd(r.dc1, c, lv, false);
         up[k].dc2 = T.dc_fwd(r.dc2, up[k].dc1.z, lv, false);
         up[k].out = T.film_fwd(3 + k, r, up[k].dc2, lv);
-        xin = up[k].out;
+        if (attn) sa[3 + k] = T.sa_fwd(3 + k, up[k].out, lv);
+        xin = attn ? sa[3 + k].out : up[k].out;
         cu = r.cout;
     }
     float* eps_pad = T.alloc((size_t)M0);
@@ -2101,6 +2228,7 @@ static int train_pass(TrainPass& T, const float* d_x, const float* d_cond, const
         const ResampleW& r = h->up[k];
         const int lv = 2 - k, cs = skipC[2 - k], cin = r.dc1.first.cin, cuk = upC[k];
         const std::string p = kUp[k];
+        if (attn) dout = T.sa_bwd(3 + k, sa[3 + k], dout);
         float* dz2 = T.film_bwd(3 + k, r, up[k].dc2, p, dout, tsilu, dm + (size_t)(3 + k) * B * kp64);
         float* dz1 = T.alloc((size_t)B * T.HWl(lv) * r.dc1.first.cout);
         float* dc = T.alloc((size_t)B * T.HWl(lv) * cin);
@@ -2124,7 +2252,8 @@ static int train_pass(TrainPass& T, const float* d_x, const float* d_cond, const
         const ResampleW& r = h->down[k];
         const int lv = k + 1, cin = r.dc1.first.cin;
         const std::string p = kDown[k];
-        float* dz2 = T.film_bwd(k, r, down[k].dc2, p, dskip[k + 1], tsilu, dm + (size_t)k * B * kp64);
+        const float* dfo = attn ? T.sa_bwd(k, sa[k], dskip[k + 1]) : dskip[k + 1];   // dskip[k + 1]: both readers of sa_{k+1}'s output
+        float* dz2 = T.film_bwd(k, r, down[k].dc2, p, dfo, tsilu, dm + (size_t)k * B * kp64);
         float* dz1 = T.alloc((size_t)B * T.HWl(lv) * r.dc1.first.cout);
         float* dpool = T.alloc((size_t)B * T.HWl(lv) * cin);
         T.dc_bwd(down[k].dc2, r.dc2, p + ".doubleConv2", dz2, dz1);

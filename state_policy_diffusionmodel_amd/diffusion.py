@@ -20,7 +20,8 @@ models/simple_Unet.py's concat-conditioned ``UNet``.  Evaluation always has eval
 positional-encoding dropout is off, as in the reference's ``validation_step`` and ``sample()`` after ``model.eval()``;
 the reference's ``training_step`` runs it with dropout p = 0.1, which ``training_step`` here does not reproduce (its
 forward half is the eval-mode network).  ``training_step(..., backward=True)`` also computes the gradients, for
-``'UNet_FilmnoAttention'`` only (``spdm_train_loss_grad``); the optimiser stays in torch.
+``'UNet_FilmnoAttention'`` (``spdm_train_loss_grad``) and -- constructed with ``train_attention=True`` --
+``'UNet_Film'``; the optimiser stays in torch.
 
 Explicit, non-breaking extensions: ``sample(..., x_T=, noise=, batched=, seed=)`` for
 fixed-noise parity runs and for B > 1 independent trajectories (the reference hard-wires
@@ -100,7 +101,7 @@ class Diffusion_DDPM:
                  model: str = "UNet", vision_encoder: Optional[Callable] = None,
                  noise_scheduler_type: str = "linear", inpaint_horizon: int = 10, step_size: int = 1,
                  *, state_dict=None, weight_seed: int = 0, device: int = 0, max_batch: int = 1,
-                 vision_encoder_state_dict=None):
+                 vision_encoder_state_dict=None, train_attention: bool = False):
         # --- Diffusion params (models/diffusion_ddpm.py:42-48)
         self.noise_steps = noise_steps
         self.obs_horizon = obs_horizon
@@ -113,6 +114,7 @@ class Diffusion_DDPM:
         self.model_name = model
         self.simple = is_simple_model(model)
         self.attention = model == "UNet_Film"
+        self.train_attention = bool(train_attention)      # training_step(backward=True) for UNet_Film (SPDM_FLAG_TRAIN_ATTENTION)
         # --- scheduler (:65-70); beta schedule is hard-coded 'linear' there, noise_scheduler_type unused
         self.noise_scheduler = DDPMScheduler(num_train_timesteps=self.noise_steps, beta_schedule="linear",
                                              clip_sample=False, prediction_type="epsilon")
@@ -191,10 +193,11 @@ class Diffusion_DDPM:
         return self._engine
 
     def _check_trainable(self) -> None:
-        if self.simple or self.attention:
+        if self.simple or (self.attention and not self.train_attention):
             raise NotImplementedError(
                 f"training_step(backward=True) computes gradients for model='UNet_FilmnoAttention' only (this model is "
-                f"{self.model_name!r}); the attention U-Net and simple_Unet.py have no backward pass on the HIP path")
+                f"{self.model_name!r}), or for model='UNet_Film' constructed with train_attention=True; simple_Unet.py "
+                f"has no backward pass on the HIP path")
 
     def _train_engine_for(self, batch: int, H: int, D: int) -> SpdmEngine:
         self._check_trainable()
@@ -204,7 +207,8 @@ class Diffusion_DDPM:
             if self._train_engine is not None:
                 self._train_engine.close()
             self._train_engine = SpdmEngine(H, D, self.cond_dim, max_batch=max(batch, self._max_batch),
-                                            device=self._device_index, attention=False, num_train_timesteps=T, train=True)
+                                            device=self._device_index, attention=self.attention, num_train_timesteps=T,
+                                            train=True, train_attention=self.attention)
             self._train_engine.load_state_dict(self.noise_estimator._sd)
             self._train_key = key
         return self._train_engine
@@ -356,7 +360,8 @@ class Diffusion_DDPM:
         """The reference's ``training_step``: noising of the target window at a per-sample timestep (``add_noise``),
         in-painting of the observed rows, ONE U-Net evaluation with ``t`` of shape (B,), MSE against the noise.  The U-Net
         runs on the HIP path (``spdm_unet_forward`` with per-sample t); the returned loss carries no torch graph.
-        ``backward=True`` (model='UNet_FilmnoAttention' only, NotImplementedError otherwise) is ``loss.backward()`` as
+        ``backward=True`` (model='UNet_FilmnoAttention', or 'UNet_Film' with ``train_attention=True``; NotImplementedError
+        otherwise) is ``loss.backward()`` as
         well: the step runs ``spdm_train_loss_grad`` on a training engine cached apart from the sampling engines and
         leaves the gradients in ``noise_estimator.grads()`` (and d loss / d obs_cond in ``noise_estimator.grad_cond``)
         for a torch optimiser; ``noise_estimator.load_state_dict`` takes the updated weights back.

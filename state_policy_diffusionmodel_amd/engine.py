@@ -34,19 +34,25 @@ class SpdmEngine:
     def __init__(self, horizon: int, state_dim: int, cond_dim: int, max_batch: int, device: int = 0,
                  attention: bool = True, time_dim: int = 256, num_train_timesteps: int = 1000,
                  debug: bool = False, exact_fp32: bool = False, pin_geometry: bool = False,
-                 model: Optional[str] = None, train: bool = False):
+                 model: Optional[str] = None, train: bool = False, train_attention: bool = False):
         """``model``: None -> UNet_Film (``attention=True``) / UNet_FilmnoAttention (``attention=False``); a model name as
         Diffusion_DDPM takes it otherwise -- ``'UNet'`` (any non-FiLM name) is models/simple_Unet.py's network, whose
         time table is the state_dict's own ``pos_encoding.pos_encoding`` buffer: ``num_train_timesteps`` must then be
         that buffer's row count (noise_steps + 1).
 
-        ``train``: the handle also serves ``loss_and_grad`` (SPDM_FLAG_TRAIN; UNet_FilmnoAttention only)."""
+        ``train``: the handle also serves ``loss_and_grad`` (SPDM_FLAG_TRAIN; UNet_FilmnoAttention only).
+        ``train_attention``: ``loss_and_grad`` for UNet_Film, through its SelfAttention blocks (SPDM_FLAG_TRAIN |
+        SPDM_FLAG_TRAIN_ATTENTION); needs the FiLM model with attention and implies ``train``."""
         self.lib = _lib.load()
         self.simple = model is not None and is_simple_model(model)
         if model is not None and not self.simple:
             attention = model == "UNet_Film"
         if self.simple:
             attention = False
+        if train_attention:
+            if self.simple or not attention:
+                raise ValueError("train_attention=True needs UNet_Film (the FiLM model with attention)")
+            train = True
         if not torch.cuda.is_available():
             raise RuntimeError("SpdmEngine needs a visible MI355X (HIP device); there is no CPU fallback")
         self.device = torch.device("cuda", device)
@@ -56,8 +62,10 @@ class SpdmEngine:
         cfg = _lib.SpdmConfig(self.horizon, self.state_dim, self.cond_dim, self.time_dim, int(self.attention),
                               self.max_batch, device, self.num_train_timesteps,
                               (_lib.SPDM_FLAG_DEBUG_KEEP if debug else 0) | (_lib.SPDM_FLAG_EXACT_FP32 if exact_fp32 else 0)
-                              | (_lib.SPDM_FLAG_SIMPLE_UNET if self.simple else 0) | (_lib.SPDM_FLAG_TRAIN if train else 0))
+                              | (_lib.SPDM_FLAG_SIMPLE_UNET if self.simple else 0) | (_lib.SPDM_FLAG_TRAIN if train else 0)
+                              | (_lib.SPDM_FLAG_TRAIN_ATTENTION if train_attention else 0))
         self.train = bool(train)
+        self.train_attention = bool(train_attention)
         self._cfg = cfg
         self._pin = bool(pin_geometry)
         self._create()

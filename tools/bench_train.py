@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Time one training step of UNet_Film_noAttention (H = 32, D = 3) at B = 16, 64, 256: the HIP step (spdm_train_loss_grad:
+"""Time one training step of UNet_Film_noAttention -- or, with --attention, of UNet_Film with its six SelfAttention blocks
+(SpdmEngine(train_attention=True)) -- (H = 32, D = 3) at B = 16, 64, 256: the HIP step (spdm_train_loss_grad:
 forward, MSE loss, full backward), the host weight refresh an optimiser step then needs (SpdmEngine.refresh_weights), and
 torch-CPU fp32 autograd of the oracle on 16 threads for the same step.  One JSON line per batch size.
-usage: python tools/bench_train.py [--iters N] [B ...]"""
+usage: python tools/bench_train.py [--attention] [--iters N] [B ...]"""
 import json
 import os
 import statistics
@@ -21,12 +22,12 @@ from state_policy_diffusionmodel_amd.weights import random_state_dict
 H, D, COND = 32, 3, 1350
 
 
-def cpu_step(sd, x, t, cond, noise):
+def cpu_step(sd, x, t, cond, noise, attention):
     params = {k: torch.from_numpy(np.asarray(v)).requires_grad_(True) for k, v in sd.items()}
     fwd = getattr(unet_film_forward, "__wrapped__", unet_film_forward)
     t0 = time.perf_counter()
     with torch.enable_grad():
-        loss = torch.mean((noise - fwd(params, x, t, cond, attention=False)) ** 2)
+        loss = torch.mean((noise - fwd(params, x, t, cond, attention=attention)) ** 2)
         loss.backward()
     return (time.perf_counter() - t0) * 1e3
 
@@ -34,20 +35,23 @@ def cpu_step(sd, x, t, cond, noise):
 def main():
     args = sys.argv[1:]
     iters = 20
+    attention = "--attention" in args
+    if attention:
+        args.remove("--attention")
     if "--iters" in args:
         i = args.index("--iters")
         iters = int(args[i + 1])
         del args[i:i + 2]
     batches = [int(a) for a in args] or [16, 64, 256]
     torch.set_num_threads(16)
-    sd = random_state_dict(COND, seed=0, attention=False)
+    sd = random_state_dict(COND, seed=0, attention=attention)
     for B in batches:
         g = torch.Generator().manual_seed(B)
         x = torch.randn(B, 1, H, D, generator=g)
         noise = torch.randn(B, 1, H, D, generator=g)
         cond = torch.randn(B, 1, 10, 135, generator=g)
         t = torch.randint(0, 1000, (B,), generator=g)
-        eng = SpdmEngine(H, D, COND, max_batch=B, attention=False, train=True)
+        eng = SpdmEngine(H, D, COND, max_batch=B, attention=attention, train=True, train_attention=attention)
         eng.load_state_dict(sd)
         xd, nd, cd = x.cuda(), noise.cuda(), cond.cuda()
         for _ in range(3):
@@ -67,9 +71,9 @@ def main():
             refresh.append((time.perf_counter() - t0) * 1e3)
         ws = eng.device_bytes
         eng.close()
-        cpu = cpu_step(sd, x, t, cond, noise)
+        cpu = cpu_step(sd, x, t, cond, noise, attention)
         hip = statistics.median(step)
-        print(json.dumps({"B": B, "H": H, "D": D, "hip_step_ms": round(hip, 3), "hip_step_min_ms": round(min(step), 3),
+        print(json.dumps({"model": "UNet_Film" if attention else "UNet_Film_noAttention", "B": B, "H": H, "D": D, "hip_step_ms": round(hip, 3), "hip_step_min_ms": round(min(step), 3),
                           "weight_refresh_ms": round(statistics.median(refresh), 2), "device_bytes": ws,
                           "cpu_autograd_ms": round(cpu, 1), "cpu_threads": 16, "cpu_over_hip": round(cpu / hip, 1)}),
               flush=True)

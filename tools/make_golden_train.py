@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""Record the training-gradient fixture tests/golden/train_grad_h16d3_b2.npz.
+"""Record the training-gradient fixture tests/golden/train_grad_h16d3_b2.npz (--attention: train_grad_attn_h16d3_b2.npz).
 
 Runs ONLY in the build container (needs /root/reference).  It imports the reference module
 UNet_Film_noAttention (models/Unet_FiLmLayer_noAttention.py, with a stub for the unused top-level
 `import torchvision`), loads OUR deterministic generated weights into it (strict=True), evaluates, in float64,
 one training step's loss on seeded inputs -- loss = mean((noise - model(x_noisy, t, cond))^2), per-sample t -- then
-loss.backward().  Stored: the inputs, the loss, d loss / d cond, and for every parameter the gradient's L2 norm, its sum
+loss.backward().  With --attention the module is UNet_Film (models/Unet_FiLmLayer.py, six SelfAttention blocks) and
+the fixture is read by tests/test_train_grad_attn_reference.py.  Stored: the inputs, the loss, d loss / d cond, and for every parameter the gradient's L2 norm, its sum
 and 256 elements at seeded flat indices.  Only data is written (tests/test_train_grad_reference.py reads it).
 """
 import os
@@ -22,7 +23,8 @@ import torch
 from state_policy_diffusionmodel_amd.weights import blob_sha256, random_state_dict
 
 REF = "/root/reference"
-OUT = os.path.join(ROOT, "tests", "golden", "train_grad_h16d3_b2.npz")
+ATTENTION = "--attention" in sys.argv[1:]
+OUT = os.path.join(ROOT, "tests", "golden", "train_grad_attn_h16d3_b2.npz" if ATTENTION else "train_grad_h16d3_b2.npz")
 B, H, D, OBS_H, OBS_DIM, WSEED, N_SAMPLES = 2, 16, 3, 2, 7, 21, 256
 
 
@@ -36,13 +38,16 @@ def main():
     if "torchvision" not in sys.modules:
         sys.modules["torchvision"] = types.ModuleType("torchvision")
     sys.path.insert(0, REF)
-    from models.Unet_FiLmLayer_noAttention import UNet_Film_noAttention
+    if ATTENTION:
+        from models.Unet_FiLmLayer import UNet_Film as Net
+    else:
+        from models.Unet_FiLmLayer_noAttention import UNet_Film_noAttention as Net
     cond_dim = OBS_H * OBS_DIM
     # float64 throughout: with float64 as the default dtype the time encoding's frequencies are float64 too (its input,
     # t.float(), holds exact integers), and so is every parameter
     torch.set_default_dtype(torch.float64)
-    m = UNet_Film_noAttention(in_channels=1, out_channels=1, noise_steps=1000, time_dim=256, global_cond_dim=cond_dim)
-    sd = random_state_dict(cond_dim, seed=WSEED, attention=False)
+    m = Net(in_channels=1, out_channels=1, noise_steps=1000, time_dim=256, global_cond_dim=cond_dim)
+    sd = random_state_dict(cond_dim, seed=WSEED, attention=ATTENTION)
     m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
     g = torch.Generator().manual_seed(77)
     x = torch.randn(B, 1, H, D, generator=g, dtype=torch.float64)
