@@ -89,15 +89,24 @@ typedef struct {
 
 #define SPDM_FLAG_TRAIN 8         /* the handle also serves spdm_train_loss_grad: it keeps flipped / transposed weight copies for
                                     the backward pass and a training workspace sized at max_batch.  UNet_Film_noAttention, or
-                                    UNet_Film (attention = 1) together with SPDM_FLAG_TRAIN_ATTENTION: spdm_create returns
+                                    UNet_Film (attention = 1) together with SPDM_FLAG_TRAIN_ATTENTION, or simple_Unet.py's UNet
+                                    (SPDM_FLAG_SIMPLE_UNET) together with SPDM_FLAG_TRAIN_SIMPLE: spdm_create returns
                                     SPDM_ERR_INVALID with attention = 1 and no SPDM_FLAG_TRAIN_ATTENTION, and with
-                                    SPDM_FLAG_SIMPLE_UNET.  Every other entry point behaves as on a handle without the flag. */
+                                    SPDM_FLAG_SIMPLE_UNET and no SPDM_FLAG_TRAIN_SIMPLE.  Every other entry point behaves as on a
+                                    handle without the flag. */
 
 #define SPDM_FLAG_TRAIN_ATTENTION 16   /* with SPDM_FLAG_TRAIN and attention = 1: spdm_train_loss_grad covers UNet_Film's six
                                     SelfAttention blocks too (their weights' gradients are part of the blob).  Opt-in because its
                                     workspace is larger.  SPDM_ERR_INVALID without SPDM_FLAG_TRAIN, with attention = 0, with
                                     SPDM_FLAG_SIMPLE_UNET, and where a block's token count H_l x W_l exceeds 512 (horizon above
                                     64).  Every other entry point behaves as on a plain attention handle. */
+
+#define SPDM_FLAG_TRAIN_SIMPLE 32  /* with SPDM_FLAG_TRAIN and SPDM_FLAG_SIMPLE_UNET: spdm_train_loss_grad serves simple_Unet.py's
+                                    UNet (its gradient covers every parameter; the blob slot of the buffer
+                                    "pos_encoding.pos_encoding" receives zeros; d_cond is required).  Training mode of the
+                                    positional encoding's dropout through spdm_train_set_time_scale.  SPDM_ERR_INVALID without
+                                    SPDM_FLAG_TRAIN, without SPDM_FLAG_SIMPLE_UNET and with SPDM_FLAG_TRAIN_ATTENTION.  Every other
+                                    entry point behaves as on a plain SPDM_FLAG_SIMPLE_UNET handle. */
 
 /* One entry per tensor of the reference state_dict (names exactly as
  * UNet_Film.state_dict() gives them, e.g. "down1.cond_encoder.2.weight"),
@@ -179,7 +188,8 @@ int  spdm_sample(spdm_handle* h, int32_t B, const float* d_cond,
 /* Replaces: one training_step of Diffusion_DDPM up to loss.backward() (models/diffusion_ddpm.py:128-173,
  * process_single_batch): eps = unet(x_noisy, t, cond); loss = mean((noise - eps)^2); the gradients of the loss with respect to
  * every weight of the network and to cond.  Handle created with SPDM_FLAG_TRAIN (SPDM_ERR_STATE otherwise); a UNet_Film handle
- * (attention = 1) also needs SPDM_FLAG_TRAIN_ATTENTION, and then its gradient covers the sa1 .. sa6 tensors.
+ * (attention = 1) also needs SPDM_FLAG_TRAIN_ATTENTION, and then its gradient covers the sa1 .. sa6 tensors; a
+ * SPDM_FLAG_SIMPLE_UNET handle needs SPDM_FLAG_TRAIN_SIMPLE and a non-NULL d_cond (SPDM_ERR_INVALID otherwise).
  *  d_x_noisy, d_noise (B,H,D); h_t[t_count], t_count == 1 (broadcast) or B; d_cond (B,cond_dim) or NULL (no FiLM);
  *  d_loss     one float on the device;
  *  d_eps      NULL or (B,H,D): the predicted noise;
@@ -191,6 +201,13 @@ int  spdm_sample(spdm_handle* h, int32_t B, const float* d_cond,
 int  spdm_train_loss_grad(spdm_handle* h, int32_t B, const float* d_x_noisy, const int32_t* h_t, int32_t t_count,
                           const float* d_cond, const float* d_noise, float* d_loss, float* d_eps, float* d_grad,
                           float* d_grad_cond, void* stream);
+
+/* PositionalEncoding's Dropout(p) in training mode (simple_Unet.py:226-257) for the NEXT spdm_train_loss_grad call on a
+ * SPDM_FLAG_TRAIN_SIMPLE handle (SPDM_ERR_STATE on any other): d_scale is a (B, time_dim) device array -- the dropout mask
+ * divided by (1 - p) -- and that call evaluates the network on pe[t_b] * d_scale[b].  The call consumes the setting, whatever
+ * its outcome; it fails with SPDM_ERR_INVALID if its B differs.  d_scale == NULL clears the setting now.  The array is read by
+ * that call, on its stream: it must stay valid until then. */
+int  spdm_train_set_time_scale(spdm_handle* h, const float* d_scale, int32_t B);
 
 /* The same loop in three pieces, so a caller (bench.py) can time an exact range
  * of denoise steps: begin() hoists the step-invariant FiLM projections and

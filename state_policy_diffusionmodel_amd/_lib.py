@@ -18,6 +18,7 @@ SPDM_FLAG_EXACT_FP32 = 2
 SPDM_FLAG_SIMPLE_UNET = 4
 SPDM_FLAG_TRAIN = 8
 SPDM_FLAG_TRAIN_ATTENTION = 16
+SPDM_FLAG_TRAIN_SIMPLE = 32
 ABI_VERSION = 2
 
 
@@ -57,6 +58,7 @@ SYMBOLS = {
                               c_uint64, c_void_p, c_void_p, c_void_p]),
     "spdm_train_loss_grad": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p]),
+    "spdm_train_set_time_scale": (c_int32, [c_void_p, c_void_p, c_int32]),
     "spdm_sample_begin": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                     c_uint64, c_uint64, c_void_p, c_void_p]),
     "spdm_sample_run": (c_int32, [c_void_p, c_int32, c_int32, c_void_p]),

@@ -275,8 +275,15 @@ hipError_t launch_out_step(const StepArgs& a, hipStream_t s);
 int wgrad_chunks(long long M, int taps, int Co, int Ci, size_t budget_floats);
 hipError_t launch_wgrad(const float* dy, int ldy, const float* x, int ldx, long long M, int H, int W, int taps, int Co, int Ci,
                         int conv9, float* partial, size_t budget_floats, float* dst, hipStream_t s);
+// the same for a channel-padded layer (models/simple_Unet.py, taps 9 or 3): dy [M][Co], x [M][Ci] at storage widths, dst the
+// (no, ni, 3, 3) torch tensor of the real channels, gathered through the device maps pos_o[no] / pos_i[ni]
+hipError_t launch_wgrad_mapped(const float* dy, const float* x, long long M, int H, int W, int taps, int Co, int Ci,
+                               const int* pos_o, int no, const int* pos_i, int ni, float* partial, size_t budget_floats, float* dst,
+                               hipStream_t s);
 hipError_t launch_colsum(const float* src, int ld, long long M, int C, float* dst, hipStream_t s);
 hipError_t launch_gn_stats(const float* y, int B, int n, float* mean, float* rstd, hipStream_t s);
+// ... statistics over cnt of the n values per sample (channel-padded storage: HW * C_real, the padded lanes hold zeros)
+hipError_t launch_gn_stats_real(const float* y, int B, int n, int cnt, float* mean, float* rstd, hipStream_t s);
 hipError_t launch_gn_act(const float* y, const float* mean, const float* rstd, const float* gamma, const float* beta, int B,
                          int HW, int C, int gelu, float* out, hipStream_t s);
 hipError_t launch_gn_bwd(const float* y, const float* mean, const float* rstd, const float* gamma, const float* beta,
@@ -307,6 +314,27 @@ int ln_bwd_blocks(long long rows);
 hipError_t launch_ln_bwd(const float* x, const float* mean, const float* rstd, const float* gamma, const float* gy,
                          const float* add, long long rows, int C, float* dx, float* part, hipStream_t s);
 hipError_t launch_gelu_bwd(const float* u, const float* dh, size_t n, float* du, hipStream_t s);
+
+// train_simple.hip: the training pass of models/simple_Unet.py (SPDM_FLAG_TRAIN_SIMPLE) in channel-padded storage; a channel map
+// is its device array pos[nreal] (storage lane of each real channel), C the storage width (multiple of 64, <= 512)
+hipError_t launch_gn_bwd_mapped(const float* y, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                                const float* g, int gelu, int B, int HW, int C, const int* pos, int nreal, float* dy, float* dgb,
+                                hipStream_t s);
+hipError_t launch_gn_param_mapped(const float* p0, const float* p1, int B, int C, const int* pos, int nreal, float* dgamma,
+                                  float* dbeta, hipStream_t s);
+// pre = GN(y) + res, out = GELU(pre) (the end of a residual DoubleConvolution)
+hipError_t launch_gn_res(const float* y, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                         const float* res, int B, int HW, int C, float* pre, float* out, hipStream_t s);
+// block tail: out[:, :Cr] = GELU(GN(y)) + temb[b], out[:, Cr:Cr+32] = cemb[b], zeros up to Co; and its backward
+hipError_t launch_simple_tail_fwd(const float* y, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                                  int Cz, int Cr, const float* temb, int temb_ld, const float* cemb, int cemb_ld, int B, int HW,
+                                  int Co, float* out, hipStream_t s);
+hipError_t launch_simple_tail_bwd(const float* dout, int B, int HW, int Co, int Cr, int Cz, float* dz, float* dtemb, float* dcemb,
+                                  int cemb_ld, hipStream_t s);
+// out[b] = SiLU(pe[t_b] * scale[b]) (PositionalEncoding's dropout as a per-sample multiplier)
+hipError_t launch_time_rows_scaled(const float* pe, const int* t_dev, int t_count, const float* scale, int B, int n, float* out,
+                                   hipStream_t s);
+hipError_t launch_silu_bwd(const float* ds, int ld, const float* cond, int B, int cond_dim, float* grad_cond, hipStream_t s);
 // attention core with its log-sum-exp (lse [B heads][L]), and its backward into dqkv [B L][3C] (in_proj's packed layout)
 bool attn_train_supported(int L, int C, int heads);
 hipError_t launch_attn_fwd_lse(const float* qkv, float* out, float* lse, int B, int L, int C, int heads, hipStream_t s);

@@ -114,6 +114,7 @@ struct Value {             // a tensor plus the GroupNorm affine still pending o
 struct ConvW { float* w = nullptr; float* ws = nullptr; float* wf = nullptr; int taps = 0, cin = 0, cout = 0;
                int cnorm = 0;
                float* wt = nullptr; };   // wt (SPDM_FLAG_TRAIN): [taps][Cin][Cout], taps flipped -- the data-gradient convolution's weights
+                                         // (SPDM_FLAG_TRAIN_SIMPLE: at the padded widths, [taps][mi.width][mo.width])
                                          // cnorm > 0: real output channels of a channel-padded layer (its GroupNorm divides by these)   // ws: split-fp16 copy; wf: its fragment-order copy (conv_wide.hip)
 struct DoubleConvW { ConvW first, second; float* gamma = nullptr; float* beta = nullptr; };
 struct LinW { float* w = nullptr; float* ws = nullptr; float* b = nullptr; int in = 0, out = 0;
@@ -152,6 +153,14 @@ struct spdm_handle {
     size_t tws_floats = 0;
     bool simple = false;                  // SPDM_FLAG_SIMPLE_UNET: models/simple_Unet.py (plan_simple); inc / down / up hold its blocks
     LinW cemb;                            // ... its six cond_emb_layer projections stacked: [6 x 32][film_kp]
+                                          //     (SPDM_FLAG_TRAIN_SIMPLE: cemb.wt = [cond_dim padded to 64][6 x 32], d SiLU(cond))
+    bool train_simple = false;            // SPDM_FLAG_TRAIN_SIMPLE: spdm_train_loss_grad of simple_Unet.py (train_pass_simple)
+    int* d_pos16 = nullptr;               // ... device channel maps (ChanMap::pos) of input_conv's 16 channels,
+    int* d_pos_in[6] = {};                //     of each block's input and
+    int* d_pos_out[6] = {};               //     of its doubleConv2 output (simple_in_map(k), ChanMap::ident(cout))
+    float* d_time_pe = nullptr;           // ... the raw time table pe (T, time_dim) on the device, for the dropout multiplier
+    const float* t_scale = nullptr;       // ... spdm_train_set_time_scale: (t_scale_B, time_dim) multiplier of the next call
+    int t_scale_B = 0;
     float* d_cemb = nullptr;              // ... Linear(SiLU(cond)) of the call, [B][6 x 32]
     bool split = true;                    // split-fp16 MFMA path (default); SPDM_PREC=f32 selects the exact fp32 MFMA path
     unsigned sw = 0;                      // kernel-selection switches (SW_*, kernels.h): environment read once at create
@@ -420,8 +429,12 @@ extern "C" int spdm_create(const spdm_config* cfg, spdm_handle** out) {
     if ((cfg->flags & SPDM_FLAG_TRAIN_ATTENTION) &&
         (!(cfg->flags & SPDM_FLAG_TRAIN) || cfg->attention == 0 || (cfg->flags & SPDM_FLAG_SIMPLE_UNET)))
         return fail(SPDM_ERR_INVALID, "SPDM_FLAG_TRAIN_ATTENTION needs SPDM_FLAG_TRAIN and attention = 1 (UNet_Film), no SPDM_FLAG_SIMPLE_UNET");
-    if ((cfg->flags & SPDM_FLAG_TRAIN) && (cfg->flags & SPDM_FLAG_SIMPLE_UNET))
-        return fail(SPDM_ERR_INVALID, "SPDM_FLAG_TRAIN serves UNet_Film_noAttention, or UNet_Film with SPDM_FLAG_TRAIN_ATTENTION: not SPDM_FLAG_SIMPLE_UNET");
+    if ((cfg->flags & SPDM_FLAG_TRAIN_SIMPLE) &&
+        (!(cfg->flags & SPDM_FLAG_TRAIN) || !(cfg->flags & SPDM_FLAG_SIMPLE_UNET) || (cfg->flags & SPDM_FLAG_TRAIN_ATTENTION)))
+        return fail(SPDM_ERR_INVALID, "SPDM_FLAG_TRAIN_SIMPLE needs SPDM_FLAG_TRAIN and SPDM_FLAG_SIMPLE_UNET, no SPDM_FLAG_TRAIN_ATTENTION");
+    if ((cfg->flags & SPDM_FLAG_TRAIN) && (cfg->flags & SPDM_FLAG_SIMPLE_UNET) && !(cfg->flags & SPDM_FLAG_TRAIN_SIMPLE))
+        return fail(SPDM_ERR_INVALID, "SPDM_FLAG_TRAIN with SPDM_FLAG_SIMPLE_UNET (simple_Unet.py) needs SPDM_FLAG_TRAIN_SIMPLE as well; "
+                                      "without it the flag serves UNet_Film_noAttention, or UNet_Film with SPDM_FLAG_TRAIN_ATTENTION");
     if ((cfg->flags & SPDM_FLAG_TRAIN) && cfg->attention != 0 && !(cfg->flags & SPDM_FLAG_TRAIN_ATTENTION))
         return fail(SPDM_ERR_INVALID, "SPDM_FLAG_TRAIN with attention = 1 (UNet_Film) needs SPDM_FLAG_TRAIN_ATTENTION as well; "
                                       "without it the flag serves UNet_Film_noAttention only (attention = 0)");
@@ -433,6 +446,7 @@ extern "C" int spdm_create(const spdm_config* cfg, spdm_handle** out) {
     h->simple = (cfg->flags & SPDM_FLAG_SIMPLE_UNET) != 0;
     h->train = (cfg->flags & SPDM_FLAG_TRAIN) != 0;
     h->train_attn = (cfg->flags & SPDM_FLAG_TRAIN_ATTENTION) != 0;
+    h->train_simple = (cfg->flags & SPDM_FLAG_TRAIN_SIMPLE) != 0;
     h->sw = switches_from_env();          // the ONLY place the product path reads SPDM_* switches
     if (const char* pe = getenv("SPDM_PREC")) h->split = !(strcmp(pe, "f32") == 0 || strcmp(pe, "fp32") == 0);
     if (cfg->flags & SPDM_FLAG_EXACT_FP32) h->split = false;
@@ -713,6 +727,13 @@ struct Loader {
         c.w = upload(v);
         c.ws = upload_split(v, K, name);
         if (c.ws) c.wf = upload(frag_order_weights(split_format(v), taps, N, K));
+        if (h->train_simple) {     // [taps][K][N], taps rotated 180 degrees (conv_taps_flipped at the padded widths)
+            std::vector<float> t((size_t)taps * K * N, 0.f);
+            for (int tp = 0; tp < taps; ++tp)
+                for (int o = 0; o < N; ++o)
+                    for (int i = 0; i < K; ++i) t[((size_t)(taps - 1 - tp) * K + i) * N + o] = v[((size_t)tp * N + o) * K + i];
+            c.wt = upload(t);
+        }
         c.taps = taps; c.cin = K; c.cout = N; c.cnorm = co;
         return c;
     }
@@ -852,6 +873,30 @@ static int load_simple(spdm_handle* h, Loader& L, int t3) {
     h->cemb.ws = L.upload_split(cw, Kp, "cond_emb_layer");
     h->cemb.b = L.upload(cb);
     h->cemb.in = Kp; h->cemb.out = 6 * SIMPLE_COND_CH;
+    if (h->train_simple) {
+        // d SiLU(cond) = dcemb [B][6 x 32] . W_stacked: the transposed copy [cond_dim padded to 64][6 x 32] (the GEMM's N % 64)
+        const int N = 6 * SIMPLE_COND_CH, kp64 = (int)align_up((size_t)cd, 64);
+        std::vector<float> t((size_t)kp64 * N, 0.f);
+        for (int o = 0; o < N; ++o)
+            for (int i = 0; i < cd; ++i) t[(size_t)i * N + o] = cw[(size_t)o * Kp + i];
+        h->cemb.wt = L.upload(t);
+        // the channel maps the backward pass gathers through (GroupNorm lanes, weight-gradient write-out)
+        auto upload_map = [&](const ChanMap& m) -> int* {
+            void* p = nullptr;
+            if (dev_alloc(h, &p, sizeof(int) * m.pos.size()) != SPDM_OK) { L.err = SPDM_ERR_HIP; return nullptr; }
+            if (hipMemcpy(p, m.pos.data(), sizeof(int) * m.pos.size(), hipMemcpyHostToDevice) != hipSuccess) {
+                L.err = fail(SPDM_ERR_HIP, "channel map upload failed");
+                return nullptr;
+            }
+            return (int*)p;
+        };
+        h->d_pos16 = upload_map(c16);
+        for (int k = 0; k < 6; ++k) {
+            h->d_pos_in[k] = upload_map(simple_in_map(k));
+            h->d_pos_out[k] = upload_map(ChanMap::ident(kSimpleBlocks[k].cout));
+        }
+        if (dev_alloc(h, (void**)&h->d_time_pe, sizeof(float) * (size_t)h->cfg.num_train_timesteps * td) != SPDM_OK) L.err = SPDM_ERR_HIP;
+    }
     {   // outc: Conv2d(64, out, 1) with bias (simple_Unet.py:280); the 64 channels are up3's 32 + 32, unpadded
         const float* w = L.find("outc.weight", {1, 64, 1, 1});
         const float* b = L.find("outc.bias", {1});
@@ -1645,6 +1690,8 @@ static int ensure_temb(spdm_handle* h, hipStream_t s) {
     HIP_TRY(hipMalloc((void**)&tmp, sizeof(float) * (size_t)T * dim));
     hipError_t e = hipMemcpyAsync(tmp, h->time_table.data(), sizeof(float) * (size_t)T * dim, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = launch_silu(tmp, h->d_time_silu, (size_t)T * dim, s);
+    if (e == hipSuccess && h->d_time_pe)          // (SPDM_FLAG_TRAIN_SIMPLE: the raw rows the dropout multiplier scales)
+        e = hipMemcpyAsync(h->d_time_pe, tmp, sizeof(float) * (size_t)T * dim, hipMemcpyDeviceToDevice, s);
     ResampleW* blocks[6] = {&h->down[0], &h->down[1], &h->down[2], &h->up[0], &h->up[1], &h->up[2]};
     for (int i = 0; i < 6 && e == hipSuccess; ++i)      // (N: cout, padded for simple_Unet.py)
         e = launch_gemm(linear_args(AffineSrc{h->d_time_silu, dim}, T, 0, blocks[i]->emb, h->split, h->sw, EPI_BIAS, blocks[i]->temb_table), s);
@@ -1906,6 +1953,7 @@ struct TrainPass {
     int* iota = nullptr;                   // 0 .. B-1: the per-sample rows of temb[] (t_dev of the tail kernels)
     float* temb[6] = {};                   // Linear(SiLU(pos_encoding(t_b))) of the call, [B][C], exact fp32 path
     float* film[6] = {};                   // Linear(Mish(cond)) of the call, [B][2C], exact fp32 path
+    const float* tscale = nullptr;         // SPDM_FLAG_TRAIN_SIMPLE: (B, time_dim) multiplier of pe[t_b] (spdm_train_set_time_scale)
 
     unsigned sw() const { return h->sw | SW_NO_SKINNY | SW_NO_REG64 | SW_NO_WIDE | SW_NO_SPLITK; }   // plain-epilogue launches: conv_gemm
     int Hl(int l) const { return h->Hp >> l; }
@@ -2125,6 +2173,94 @@ struct TrainPass {
         ln_param(part, nblk, C, p + ".ln.weight", p + ".ln.bias");
         return dx;
     }
+
+    // ---- models/simple_Unet.py (SPDM_FLAG_TRAIN_SIMPLE) in channel-padded storage ----
+    // A DoubleConvolution whose output channels (and GroupNorm lanes) follow the map mo (device copy pos); the residual one
+    // (doubleConv1) ends in GELU(GN(y2) + x0) and saves the pre-activation.
+    struct SDC {
+        DC d;
+        ChanMap mo;
+        const int* pos = nullptr; int nreal = 0;
+        bool residual = false;
+        float* pre = nullptr;        // residual: GN(y2) + x0
+    };
+    // inc: input_conv (x0 the padded map, conv_in layout); tail: the block tail reads y2 itself (d.z is not materialised)
+    SDC sdc_fwd(const DoubleConvW& w, const float* x0, int level, bool inc, bool residual, bool tail, const ChanMap& mo,
+                const int* pos) {
+        SDC a;
+        DC& d = a.d;
+        a.mo = mo; a.pos = pos; a.nreal = mo.real(); a.residual = residual;
+        const int nreal = a.nreal;
+        d.x0 = x0; d.cin = inc ? 1 : w.first.cin; d.C = inc ? 64 : w.first.cout; d.level = level;
+        const int HW = HWl(level);
+        const size_t n = (size_t)B * HW * d.C;
+        d.y1 = alloc(n); d.a1 = alloc(n); d.y2 = alloc(n);
+        d.z = tail ? nullptr : alloc(n);
+        a.pre = residual ? alloc(n) : nullptr;
+        d.m1 = alloc(B); d.r1 = alloc(B); d.m2 = alloc(B); d.r2 = alloc(B);
+        if (!run()) return a;
+        if (inc) chk(launch_conv_in_plain(x0, h->w_inc_first, B, Hl(level), Wl(level), d.y1, s), "input_conv.first");
+        else conv_fwd(w.first, x0, level, d.y1);
+        if (!run()) return a;
+        chk(launch_gn_stats_real(d.y1, B, HW * d.C, HW * nreal, d.m1, d.r1, s), "GroupNorm statistics");
+        chk(launch_gn_act(d.y1, d.m1, d.r1, w.gamma, w.beta, B, HW, d.C, 1, d.a1, s), "GroupNorm + GELU");
+        conv_fwd(w.second, d.a1, level, d.y2);
+        if (!run()) return a;
+        chk(launch_gn_stats_real(d.y2, B, HW * d.C, HW * nreal, d.m2, d.r2, s), "GroupNorm statistics");
+        if (residual) chk(launch_gn_res(d.y2, d.m2, d.r2, w.gamma, w.beta, x0, B, HW, d.C, a.pre, d.z, s), "GroupNorm + residual + GELU");
+        else if (!tail) chk(launch_gn_act(d.y2, d.m2, d.r2, w.gamma, w.beta, B, HW, d.C, 1, d.z, s), "GroupNorm + GELU");
+        return a;
+    }
+    // weight gradient of a padded 3x3 / 3x1 layer into its torch tensor: identity maps (real channels first) contract the real
+    // channels only; a concatenation's map goes through launch_wgrad_mapped
+    void wgrad_map(const float* dy, const float* x, int level, int taps, const ChanMap& mo, const int* po, const ChanMap& mi,
+                   const int* pi, float* dst) {
+        if (!run() || !dst) return;
+        const long long M = (long long)B * HWl(level);
+        auto ident = [](const ChanMap& m) { return m.pos.back() == m.real() - 1; };
+        if (ident(mo) && ident(mi)) { wgrad(dy, mo.width, x, mi.width, M, level, taps, mo.real(), mi.real(), 1, dst); return; }
+        chk(launch_wgrad_mapped(dy, x, M, Hl(level), Wl(level), taps, mo.width, mi.width, po, mo.real(), pi, mi.real(), partial,
+                                WGRAD_BUDGET, dst, s), "weight gradient");
+    }
+    // dz: gradient of the DoubleConvolution's output (residual) or of GELU(GN(y2)) (otherwise); mi / pi: the map of its input.
+    // dx0 (null: not wanted) receives the gradient of its input, the residual branch included.
+    void sdc_bwd(const SDC& a, const DoubleConvW& w, const std::string& p, const float* dz, const ChanMap& mi, const int* pi,
+                 float* dx0, bool inc = false) {
+        const DC& d = a.d;
+        const int HW = HWl(d.level);
+        const long long M = (long long)B * HW;
+        const size_t n = (size_t)M * d.C;
+        const ChanMap& mo = a.mo;
+        float* gpre = a.residual ? alloc(n) : nullptr;
+        float* dy2 = alloc(n);
+        float* da1 = alloc(n);
+        float* dy1 = alloc(n);
+        float* dgb2 = alloc((size_t)B * d.C * 2);
+        float* dgb1 = alloc((size_t)B * d.C * 2);
+        if (!run()) return;
+        if (a.residual) {
+            chk(launch_gelu_bwd(a.pre, dz, n, gpre, s), "residual GELU backward");
+            chk(launch_gn_bwd_mapped(d.y2, d.m2, d.r2, w.gamma, w.beta, gpre, 0, B, HW, d.C, a.pos, a.nreal, dy2, dgb2, s),
+                "GroupNorm backward");
+        } else {
+            chk(launch_gn_bwd_mapped(d.y2, d.m2, d.r2, w.gamma, w.beta, dz, 1, B, HW, d.C, a.pos, a.nreal, dy2, dgb2, s),
+                "GroupNorm + GELU backward");
+        }
+        wgrad_map(dy2, d.a1, d.level, w.second.taps, mo, a.pos, mo, a.pos, G(p + ".second.weight"));
+        conv_dgrad(w.second, dy2, d.level, da1);
+        if (!run()) return;
+        chk(launch_gn_bwd_mapped(d.y1, d.m1, d.r1, w.gamma, w.beta, da1, 1, B, HW, d.C, a.pos, a.nreal, dy1, dgb1, s),
+            "GroupNorm + GELU backward");
+        float* dg = G(p + ".norm.weight");
+        float* db = G(p + ".norm.bias");
+        if (!run()) return;
+        chk(launch_gn_param_mapped(dgb2, dgb1, B, d.C, a.pos, a.nreal, dg, db, s), "GroupNorm affine gradient");
+        if (inc) wgrad(dy1, d.C, d.x0, 1, M, d.level, 9, a.nreal, 1, 1, G(p + ".first.weight"));
+        else wgrad_map(dy1, d.x0, d.level, w.first.taps, mo, a.pos, mi, pi, G(p + ".first.weight"));
+        if (!dx0) return;
+        conv_dgrad(w.first, dy1, d.level, dx0);
+        if (a.residual && run()) chk(launch_add_cols(gpre, d.C, 0, M, d.C, dx0, s), "residual gradient");
+    }
 };
 
 static const char* const kDown[3] = {"down1", "down2", "down3"};
@@ -2266,9 +2402,163 @@ static int train_pass(TrainPass& T, const float* d_x, const float* d_cond, const
     return T.err;
 }
 
+// Training-loss gradient of models/simple_Unet.py's UNet (SPDM_FLAG_TRAIN_SIMPLE), in the channel-padded storage
+// of plan_simple: every saved tensor keeps exact zeros on its padded lanes, the GroupNorms count real channels
+// only, and the weight gradients are gathered back to torch layout through the layers' channel maps.  The time rows are
+// SiLU(pe[t_b] * scale_b) under spdm_train_set_time_scale (PositionalEncoding's dropout), the gathered SiLU(pe) rows otherwise.
+static const char* const kSimpleNames[6] = {"down1", "down2", "down3", "up1", "up2", "up3"};
+
+static int train_pass_simple(TrainPass& T, const float* d_x, const float* d_cond, const float* d_noise, float* d_loss,
+                             float* d_eps, float* d_grad_cond) {
+    spdm_handle* h = T.h;
+    const int B = T.B, H0 = h->cfg.horizon, D = h->cfg.state_dim, td = h->cfg.time_dim, cd = h->cfg.cond_dim;
+    const int NC = 6 * SIMPLE_COND_CH;
+    const long long M0 = (long long)B * T.HWl(0);
+    T.partial = T.alloc(TrainPass::WGRAD_BUDGET);
+    // time rows, the six emb_layer projections and the stacked cond_emb_layer projection of the call, exact fp32
+    float* tsilu = T.alloc((size_t)B * td);
+    if (T.run()) {
+        if (T.tscale) T.chk(launch_time_rows_scaled(h->d_time_pe, h->d_t, T.t_count, T.tscale, B, td, tsilu, T.s), "time rows");
+        else T.chk(launch_gather_rows(h->d_time_silu, h->d_t, T.t_count, B, td, tsilu, T.s), "time rows");
+    }
+    for (int k = 0; k < 6; ++k) {       // (sized by the channel map: the dry run at create precedes spdm_load_weights)
+        const ResampleW& r = simple_block(h, k);
+        T.temb[k] = T.alloc((size_t)B * ChanMap::ident(kSimpleBlocks[k].cout).width);
+        if (T.run() && r.emb.out != ChanMap::ident(kSimpleBlocks[k].cout).width)
+            T.err = fail(SPDM_ERR_STATE, "train: emb_layer of block %d has %d outputs", k, r.emb.out);
+        if (T.run())
+            T.chk(launch_gemm(linear_args(AffineSrc{tsilu, td}, B, 0, r.emb, false, T.sw(), EPI_BIAS, T.temb[k]), T.s), "time embedding");
+    }
+    float* cemb = T.alloc((size_t)B * NC);            // [B][6 x 32]: block k's Linear(SiLU(cond)) at columns 32 k
+    if (T.run())
+        T.chk(launch_gemm(linear_args(AffineSrc{h->d_condm, h->film_kp}, B, 0, h->cemb, false, T.sw(), EPI_BIAS, cemb), T.s),
+              "conditioning projection");
+    // ---- forward ----
+    struct SBlock { TrainPass::SDC dc1, dc2; float* out = nullptr; int aw = 0, bw = 0; };
+    SBlock blk[6];
+    const ChanMap c16 = ChanMap::ident(16);
+    float* xp = T.alloc((size_t)M0);
+    if (T.run()) T.chk(launch_pad(d_x, B, H0, D, h->Hp, h->Wp, h->lh, h->lw, xp, T.s), "pad");
+    const TrainPass::SDC inc = T.sdc_fwd(h->inc, xp, 0, true, false, false, c16, h->d_pos16);
+    const float* skips[4] = {inc.d.z, nullptr, nullptr, nullptr};     // x1 x2 x3 x4
+    int skipW[4] = {c16.width, 0, 0, 0};
+    auto block_fwd = [&](int k, const float* in, int lv) {
+        const ResampleW& r = simple_block(h, k);
+        const ChanMap mi = simple_in_map(k), mo = ChanMap::ident(kSimpleBlocks[k].cout);
+        SBlock& b = blk[k];
+        b.dc1 = T.sdc_fwd(r.dc1, in, lv, false, true, false, mi, h->d_pos_in[k]);
+        b.dc2 = T.sdc_fwd(r.dc2, b.dc1.d.z, lv, false, false, true, mo, h->d_pos_out[k]);
+        const int Wo = simple_out_width(k);
+        b.out = T.alloc((size_t)B * T.HWl(lv) * Wo);
+        if (T.run())
+            T.chk(launch_simple_tail_fwd(b.dc2.d.y2, b.dc2.d.m2, b.dc2.d.r2, r.dc2.gamma, r.dc2.beta, mo.width, r.cout, T.temb[k],
+                                         r.emb.out, cemb + SIMPLE_COND_CH * k, NC, B, T.HWl(lv), Wo, b.out, T.s), "block tail");
+    };
+    for (int k = 0; k < 3; ++k) {                     // down1..3: MaxPool2d(2), then the block
+        const int lv = k + 1, w = simple_in_map(k).width;
+        if (w != skipW[k] && !T.err) T.err = fail(SPDM_ERR_STATE, "train: down block %d reads %d channels, stored %d", k, w, skipW[k]);
+        float* p = T.alloc((size_t)B * T.HWl(lv) * w);
+        if (T.run()) T.chk(launch_pool(AffineSrc{skips[k], w}, p, B, T.Hl(k), T.Wl(k), T.s), "max pool");
+        block_fwd(k, p, lv);
+        skips[k + 1] = blk[k].out;
+        skipW[k + 1] = simple_out_width(k);
+    }
+    const float* xin = skips[3];                      // x4, then u1, u2
+    int xw = skipW[3];
+    for (int k = 0; k < 3; ++k) {                     // up1..3: cat([Upsample(x), skip]), then the block
+        const int lv = 2 - k, w = simple_in_map(3 + k).width;
+        SBlock& b = blk[3 + k];
+        b.aw = xw; b.bw = skipW[2 - k];
+        if (b.aw + b.bw != w && !T.err) T.err = fail(SPDM_ERR_STATE, "train: up block %d has %d + %d input channels, map %d", k, b.aw, b.bw, w);
+        float* c = T.alloc((size_t)B * T.HWl(lv) * w);
+        if (T.run())
+            T.chk(launch_upcat(AffineSrc{xin, b.aw}, AffineSrc{skips[2 - k], b.bw}, c, B, T.Hl(lv + 1), T.Wl(lv + 1), T.s), "upsample + concat");
+        block_fwd(3 + k, c, lv);
+        xin = b.out;
+        xw = simple_out_width(3 + k);
+    }
+    if (xw != 64 && !T.err) T.err = fail(SPDM_ERR_STATE, "train: outc reads 64 channels, up3 stores %d", xw);
+    float* eps_pad = T.alloc((size_t)M0);
+    float* deps = T.alloc((size_t)M0);
+    if (T.run()) T.chk(launch_outc(xin, h->outc_w, h->outc_b, M0, eps_pad, T.s), "outc");
+    if (T.run()) T.chk(launch_mse(eps_pad, d_noise, B, H0, D, h->Hp, h->Wp, h->lh, h->lw, d_loss, deps, d_eps, T.s), "MSE loss");
+    // ---- backward ----
+    float* dcemb = T.alloc((size_t)B * NC);
+    float* dskip[4];                                  // gradients of x1 .. x4 (accumulated: the pool / upsample and the skip read them)
+    for (int k = 0; k < 4; ++k) dskip[k] = T.alloc((size_t)B * T.HWl(k) * skipW[k]);
+    float* dup[3] = {dskip[3], nullptr, nullptr};     // gradients of x4, u1, u2 (the coarse input of up block k)
+    for (int k = 1; k < 3; ++k) dup[k] = T.alloc((size_t)B * T.HWl(3 - k) * simple_out_width(2 + k));
+    float* du3 = T.alloc((size_t)M0 * 64);
+    if (T.run()) {
+        T.chk(hipMemsetAsync(T.d_grad, 0, sizeof(float) * h->grad_floats, T.s), "memset");
+        for (int k = 0; k < 4; ++k) T.chk(hipMemsetAsync(dskip[k], 0, sizeof(float) * B * T.HWl(k) * skipW[k], T.s), "memset");
+        for (int k = 1; k < 3; ++k)
+            T.chk(hipMemsetAsync(dup[k], 0, sizeof(float) * B * T.HWl(3 - k) * simple_out_width(2 + k), T.s), "memset");
+        T.chk(launch_outc_bwd(deps, h->outc_w, M0, du3, T.s), "outc backward");
+    }
+    T.wgrad(deps, 1, xin, 64, M0, 0, 1, 1, 64, 0, T.G("outc.weight"));
+    if (float* gb = T.G("outc.bias"); T.run()) T.chk(launch_colsum(deps, 1, M0, 1, gb, T.s), "bias gradient");
+    // one block backward: tail, doubleConv2, doubleConv1; dout the gradient of the block output, din receives its input's
+    auto block_bwd = [&](int k, const float* dout, int lv, float* din) {
+        const ResampleW& r = simple_block(h, k);
+        const SBlock& b = blk[k];
+        const std::string p = kSimpleNames[k];
+        const ChanMap mi = simple_in_map(k);
+        const int Cz = b.dc2.mo.width, Cr = r.cout;
+        const long long M = (long long)B * T.HWl(lv);
+        float* dz2 = T.alloc((size_t)M * Cz);
+        float* dtemb = T.alloc((size_t)B * Cr);
+        float* dz1 = T.alloc((size_t)M * mi.width);
+        if (T.run())
+            T.chk(launch_simple_tail_bwd(dout, B, T.HWl(lv), simple_out_width(k), Cr, Cz, dz2, dtemb, dcemb + SIMPLE_COND_CH * k, NC, T.s),
+                  "block tail backward");
+        T.wgrad(dtemb, Cr, tsilu, td, B, 0, 1, Cr, td, 0, T.G(p + ".emb_layer.1.weight"));
+        if (float* gb = T.G(p + ".emb_layer.1.bias"); T.run()) T.chk(launch_colsum(dtemb, Cr, B, Cr, gb, T.s), "bias gradient");
+        T.sdc_bwd(b.dc2, r.dc2, p + ".doubleConv2", dz2, mi, h->d_pos_in[k], dz1);
+        T.sdc_bwd(b.dc1, r.dc1, p + ".doubleConv1", dz1, mi, h->d_pos_in[k], din);
+    };
+    const float* dout = du3;
+    for (int k = 2; k >= 0; --k) {
+        const SBlock& b = blk[3 + k];
+        const int lv = 2 - k, w = b.aw + b.bw;
+        const long long M = (long long)B * T.HWl(lv);
+        float* dc = T.alloc((size_t)M * w);
+        block_bwd(3 + k, dout, lv, dc);
+        if (T.run()) {
+            T.chk(launch_up_bwd(dc, w, B, T.Hl(lv + 1), T.Wl(lv + 1), b.aw, dup[k], T.s), "upsample backward");
+            T.chk(launch_add_cols(dc, w, b.aw, M, b.bw, dskip[2 - k], T.s), "concat backward");
+        }
+        dout = dup[k];
+    }
+    for (int k = 2; k >= 0; --k) {                    // dskip[k + 1] is complete: both readers of the block output are done
+        const int lv = k + 1, w = skipW[k];
+        float* dpool = T.alloc((size_t)B * T.HWl(lv) * w);
+        block_bwd(k, dskip[k + 1], lv, dpool);
+        if (T.run()) T.chk(launch_pool_bwd(skips[k], dpool, B, T.Hl(k), T.Wl(k), w, dskip[k], T.s), "max pool backward");
+    }
+    T.sdc_bwd(inc, h->inc, "input_conv", dskip[0], c16, h->d_pos16, nullptr, /*inc=*/true);
+    // ---- conditioning: the six cond_emb_layer Linears on SiLU(cond), then d cond through the SiLU ----
+    const int kp64 = (int)align_up((size_t)cd, 64);
+    float* dsilu = T.alloc((size_t)B * kp64);
+    for (int k = 0; k < 6; ++k) {
+        const std::string p = kSimpleNames[k];
+        T.wgrad(dcemb + SIMPLE_COND_CH * k, NC, h->d_condm, h->film_kp, B, 0, 1, SIMPLE_COND_CH, cd, 0, T.G(p + ".cond_emb_layer.1.weight"));
+        if (float* gb = T.G(p + ".cond_emb_layer.1.bias"); T.run())
+            T.chk(launch_colsum(dcemb + SIMPLE_COND_CH * k, NC, B, SIMPLE_COND_CH, gb, T.s), "bias gradient");
+    }
+    if (d_grad_cond && T.run()) {
+        if (!h->cemb.wt) return T.err = fail(SPDM_ERR_STATE, "train: transposed conditioning weights missing");
+        T.chk(launch_gemm(gemm_args(B, 0, 1, 1, NC, kp64, 1, 0, T.sw(), nullptr, PRO_NONE, AffineSrc{dcemb, NC}, 0, AffineSrc{},
+                                    h->cemb.wt, nullptr, dsilu, kp64, EPI_PLAIN, nullptr), T.s), "conditioning data gradient");
+        if (T.run()) T.chk(launch_silu_bwd(dsilu, kp64, d_cond, B, cd, d_grad_cond, T.s), "SiLU backward");
+    }
+    return T.err;
+}
+
 static size_t train_workspace_floats(spdm_handle* h) {
     TrainPass T{h, h->cfg.max_batch, 1, h->cfg.cond_dim > 0, true, nullptr, nullptr};
-    (void)train_pass(T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (h->train_simple) (void)train_pass_simple(T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    else (void)train_pass(T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
     return T.used;
 }
 
@@ -2276,9 +2566,16 @@ extern "C" int spdm_train_loss_grad(spdm_handle* h, int32_t B, const float* d_x,
                                     const float* d_cond, const float* d_noise, float* d_loss, float* d_eps, float* d_grad,
                                     float* d_grad_cond, void* stream) {
     if (!h) return fail(SPDM_ERR_INVALID, "null handle");
+    const float* tscale = h->t_scale;     // spdm_train_set_time_scale: consumed by this call, whatever its outcome
+    const int tscale_B = h->t_scale_B;
+    h->t_scale = nullptr;
+    h->t_scale_B = 0;
     if (!h->train) return fail(SPDM_ERR_STATE, "spdm_train_loss_grad needs a handle created with SPDM_FLAG_TRAIN");
     SPDM_TRY(check_ready(h, B));
     if (!d_x || !h_t || !d_noise || !d_loss || !d_grad) return fail(SPDM_ERR_INVALID, "null argument");
+    if (h->simple && !d_cond) return fail(SPDM_ERR_INVALID, "SPDM_FLAG_SIMPLE_UNET: d_cond is required (simple_Unet.py's UNet is only defined with conditioning)");
+    if (tscale && tscale_B != B)
+        return fail(SPDM_ERR_INVALID, "spdm_train_set_time_scale was given %d rows, this call has B = %d", tscale_B, B);
     if (t_count != 1 && t_count != B) return fail(SPDM_ERR_INVALID, "t_count must be 1 or B");
     for (int i = 0; i < t_count; ++i)
         if (h_t[i] < 0 || h_t[i] >= h->cfg.num_train_timesteps) return fail(SPDM_ERR_INVALID, "t = %d outside [0,%d)", h_t[i], h->cfg.num_train_timesteps);
@@ -2288,9 +2585,20 @@ extern "C" int spdm_train_loss_grad(spdm_handle* h, int32_t B, const float* d_x,
     HIP_TRY(hipMemcpyAsync(h->d_t, h_t, sizeof(int) * t_count, hipMemcpyHostToDevice, s));
     SPDM_TRY(compute_film(h, B, d_cond, s));
     TrainPass T{h, B, t_count, d_cond != nullptr && h->cfg.cond_dim > 0, false, s, d_grad};
-    SPDM_TRY(train_pass(T, d_x, d_cond, d_noise, d_loss, d_eps, d_grad_cond));
+    T.tscale = tscale;
+    SPDM_TRY(h->train_simple ? train_pass_simple(T, d_x, d_cond, d_noise, d_loss, d_eps, d_grad_cond)
+                             : train_pass(T, d_x, d_cond, d_noise, d_loss, d_eps, d_grad_cond));
     h->session = false;
     if (!stream) HIP_TRY(hipStreamSynchronize(s));
+    return SPDM_OK;
+}
+
+extern "C" int spdm_train_set_time_scale(spdm_handle* h, const float* d_scale, int32_t B) {
+    if (!h) return fail(SPDM_ERR_INVALID, "null handle");
+    if (!h->train_simple) return fail(SPDM_ERR_STATE, "spdm_train_set_time_scale needs a handle created with SPDM_FLAG_TRAIN_SIMPLE");
+    if (d_scale && (B < 1 || B > h->cfg.max_batch)) return fail(SPDM_ERR_INVALID, "batch %d outside [1, max_batch = %d]", B, h->cfg.max_batch);
+    h->t_scale = d_scale;
+    h->t_scale_B = d_scale ? B : 0;
     return SPDM_OK;
 }
 

@@ -94,6 +94,28 @@ __global__ void wgrad_combine_kernel(const float* __restrict__ partial, int nchu
     dst[i] = s;
 }
 
+// The same sum for a channel-padded layer (models/simple_Unet.py): partials at storage widths Co x Ci, dst (no, ni, 3, 3) in torch
+// layout gathered through the maps' device arrays pos_o / pos_i (storage lane of each real channel)
+__global__ void wgrad_combine_mapped_kernel(const float* __restrict__ partial, int nchunks, int taps, int Co, int Ci,
+                                            const int* __restrict__ pos_o, int no, const int* __restrict__ pos_i, int ni,
+                                            float* __restrict__ dst) {
+    const size_t n = (size_t)no * ni * 9;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int t9 = (int)(i % 9);
+    const size_t oc = i / 9;                  // co_real * ni + ci_real
+    const int co = pos_o[oc / ni], ci = pos_i[oc % ni];
+    int tap = t9;
+    if (taps == 3) tap = (t9 % 3 == 1) ? t9 / 3 : -1;
+    float s = 0.f;
+    if (tap >= 0) {
+        const size_t slab = (size_t)taps * Co * Ci;
+        const float* p = partial + ((size_t)tap * Co + co) * Ci + ci;
+        for (int c = 0; c < nchunks; ++c) s += p[(size_t)c * slab];
+    }
+    dst[i] = s;
+}
+
 // dst[c] = sum_m src[m * ld + c] (bias gradients): one workgroup per column, fixed-order tree
 __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ src, int ld, long long M, float* __restrict__ dst) {
     __shared__ float red[256];
@@ -109,8 +131,9 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ s
     if (threadIdx.x == 0) dst[c] = red[0];
 }
 
-// per-sample mean and 1 / sqrt(var + eps) of GroupNorm(1, C) over HW * C values (fp64 sums, fixed-order tree)
-__global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__ y, int n, float* __restrict__ mean,
+// per-sample mean and 1 / sqrt(var + eps) of GroupNorm(1, C) over the n = HW * C values of a sample (fp64 sums, fixed-order
+// tree), divided by cnt: n, or HW * C_real for channel-padded storage whose padded lanes hold zeros
+__global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__ y, int n, int cnt, float* __restrict__ mean,
                                                        float* __restrict__ rstd) {
     __shared__ double s1[256], s2[256];
     const int b = blockIdx.x;
@@ -124,7 +147,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        const double mu = s1[0] / n, var = fmax(s2[0] / n - mu * mu, 0.0);
+        const double mu = s1[0] / cnt, var = fmax(s2[0] / cnt - mu * mu, 0.0);
         mean[b] = (float)mu;
         rstd[b] = (float)(1.0 / sqrt(var + 1e-5));
     }
@@ -419,18 +442,38 @@ int wgrad_chunks(long long M, int taps, int Co, int Ci, size_t budget_floats) {
     return (int)n;
 }
 
-hipError_t launch_wgrad(const float* dy, int ldy, const float* x, int ldx, long long M, int H, int W, int taps, int Co, int Ci,
-                        int conv9, float* partial, size_t budget_floats, float* dst, hipStream_t s) {
+// the partial slabs of a weight gradient: returns their count, 0 if they do not fit the budget
+static int wgrad_partials(const float* dy, int ldy, const float* x, int ldx, long long M, int H, int W, int taps, int Co, int Ci,
+                          float* partial, size_t budget_floats, hipStream_t s) {
     const int nch = wgrad_chunks(M, taps, Co, Ci, budget_floats);
-    if ((size_t)nch * taps * Co * Ci > budget_floats) return hipErrorInvalidValue;
+    if ((size_t)nch * taps * Co * Ci > budget_floats) return 0;
     long long rows = (M + nch - 1) / nch;
     rows = (rows + 3) / 4 * 4;
     const int tiles = ((Co + 63) / 64) * ((Ci + 63) / 64);
     hipLaunchKernelGGL(wgrad_partial_kernel, dim3(tiles, taps, nch), dim3(256), 0, s, dy, ldy, x, ldx, M, H, W, H * W, taps, Co,
                        Ci, (int)rows, partial);
+    return nch;
+}
+
+hipError_t launch_wgrad(const float* dy, int ldy, const float* x, int ldx, long long M, int H, int W, int taps, int Co, int Ci,
+                        int conv9, float* partial, size_t budget_floats, float* dst, hipStream_t s) {
+    const int nch = wgrad_partials(dy, ldy, x, ldx, M, H, W, taps, Co, Ci, partial, budget_floats, s);
+    if (nch == 0) return hipErrorInvalidValue;
     const size_t n = (size_t)Co * Ci * (conv9 ? 9 : 1);
     hipLaunchKernelGGL(wgrad_combine_kernel, dim3(nblocks(n, 256)), dim3(256), 0, s, (const float*)partial, nch, taps, Co, Ci,
                        conv9, dst);
+    return hipGetLastError();
+}
+
+hipError_t launch_wgrad_mapped(const float* dy, const float* x, long long M, int H, int W, int taps, int Co, int Ci,
+                               const int* pos_o, int no, const int* pos_i, int ni, float* partial, size_t budget_floats, float* dst,
+                               hipStream_t s) {
+    if (taps != 9 && taps != 3) return hipErrorInvalidValue;
+    const int nch = wgrad_partials(dy, Co, x, Ci, M, H, W, taps, Co, Ci, partial, budget_floats, s);
+    if (nch == 0) return hipErrorInvalidValue;
+    const size_t n = (size_t)no * ni * 9;
+    hipLaunchKernelGGL(wgrad_combine_mapped_kernel, dim3(nblocks(n, 256)), dim3(256), 0, s, (const float*)partial, nch, taps, Co, Ci,
+                       pos_o, no, pos_i, ni, dst);
     return hipGetLastError();
 }
 
@@ -440,7 +483,13 @@ hipError_t launch_colsum(const float* src, int ld, long long M, int C, float* ds
 }
 
 hipError_t launch_gn_stats(const float* y, int B, int n, float* mean, float* rstd, hipStream_t s) {
-    hipLaunchKernelGGL(gn_stats_kernel, dim3(B), dim3(256), 0, s, y, n, mean, rstd);
+    hipLaunchKernelGGL(gn_stats_kernel, dim3(B), dim3(256), 0, s, y, n, n, mean, rstd);
+    return hipGetLastError();
+}
+
+hipError_t launch_gn_stats_real(const float* y, int B, int n, int cnt, float* mean, float* rstd, hipStream_t s) {
+    if (cnt < 1 || cnt > n) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gn_stats_kernel, dim3(B), dim3(256), 0, s, y, n, cnt, mean, rstd);
     return hipGetLastError();
 }
 

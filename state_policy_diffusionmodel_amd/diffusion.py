@@ -18,10 +18,11 @@ All three noise predictors of ``__init__`` (models/diffusion_ddpm.py:53-62) run 
 ``'UNet_FilmnoAttention'``, and every other value -- the constructor's own default ``'UNet'`` -- for
 models/simple_Unet.py's concat-conditioned ``UNet``.  Evaluation always has eval semantics: that network's
 positional-encoding dropout is off, as in the reference's ``validation_step`` and ``sample()`` after ``model.eval()``;
-the reference's ``training_step`` runs it with dropout p = 0.1, which ``training_step`` here does not reproduce (its
-forward half is the eval-mode network).  ``training_step(..., backward=True)`` also computes the gradients, for
-``'UNet_FilmnoAttention'`` (``spdm_train_loss_grad``) and -- constructed with ``train_attention=True`` --
-``'UNet_Film'``; the optimiser stays in torch.
+the reference's ``training_step`` runs it with dropout p = 0.1, which ``training_step(..., backward=True,
+time_scale=mask)`` reproduces when the caller draws the mask (otherwise its forward half is the eval-mode network).
+``training_step(..., backward=True)`` also computes the gradients, for ``'UNet_FilmnoAttention'``
+(``spdm_train_loss_grad``), for simple_Unet.py's ``'UNet'`` and -- constructed with
+``train_attention=True`` -- ``'UNet_Film'``; the optimiser stays in torch.
 
 Explicit, non-breaking extensions: ``sample(..., x_T=, noise=, batched=, seed=)`` for
 fixed-noise parity runs and for B > 1 independent trajectories (the reference hard-wires
@@ -193,22 +194,26 @@ class Diffusion_DDPM:
         return self._engine
 
     def _check_trainable(self) -> None:
-        if self.simple or (self.attention and not self.train_attention):
+        if self.attention and not self.train_attention:
             raise NotImplementedError(
-                f"training_step(backward=True) computes gradients for model='UNet_FilmnoAttention' only (this model is "
-                f"{self.model_name!r}), or for model='UNet_Film' constructed with train_attention=True; simple_Unet.py "
-                f"has no backward pass on the HIP path")
+                f"training_step(backward=True) computes gradients for model='UNet_FilmnoAttention', for simple_Unet.py's "
+                f"model='UNet', or for model='UNet_Film' constructed with train_attention=True (this model is "
+                f"{self.model_name!r})")
 
     def _train_engine_for(self, batch: int, H: int, D: int) -> SpdmEngine:
         self._check_trainable()
-        T = max(int(_as_spec(self.noise_scheduler).config.num_train_timesteps), int(self.noise_steps))
+        if self.simple:      # simple_Unet.py: the time table is the network's own pos_encoding buffer (as in _engine_for)
+            T = int(self.noise_estimator._sd["pos_encoding.pos_encoding"].shape[0])
+        else:
+            T = max(int(_as_spec(self.noise_scheduler).config.num_train_timesteps), int(self.noise_steps))
         key = (H, D, T)
         if self._train_engine is None or self._train_key != key or batch > self._train_engine.max_batch:
             if self._train_engine is not None:
                 self._train_engine.close()
             self._train_engine = SpdmEngine(H, D, self.cond_dim, max_batch=max(batch, self._max_batch),
                                             device=self._device_index, attention=self.attention, num_train_timesteps=T,
-                                            train=True, train_attention=self.attention)
+                                            train=True, train_attention=self.attention and not self.simple,
+                                            model="UNet" if self.simple else None, train_simple=self.simple)
             self._train_engine.load_state_dict(self.noise_estimator._sd)
             self._train_key = key
         return self._train_engine
@@ -356,16 +361,23 @@ class Diffusion_DDPM:
 
     # ==================== Training (models/diffusion_ddpm.py:128-173) ====================
     def training_step(self, batch, batch_idx: int = 0, *, t: Optional[torch.Tensor] = None,
-                      noise: Optional[torch.Tensor] = None, return_parts: bool = False, backward: bool = False):
+                      noise: Optional[torch.Tensor] = None, return_parts: bool = False, backward: bool = False,
+                      time_scale: Optional[torch.Tensor] = None):
         """The reference's ``training_step``: noising of the target window at a per-sample timestep (``add_noise``),
         in-painting of the observed rows, ONE U-Net evaluation with ``t`` of shape (B,), MSE against the noise.  The U-Net
         runs on the HIP path (``spdm_unet_forward`` with per-sample t); the returned loss carries no torch graph.
-        ``backward=True`` (model='UNet_FilmnoAttention', or 'UNet_Film' with ``train_attention=True``; NotImplementedError
-        otherwise) is ``loss.backward()`` as
+        ``backward=True`` (model='UNet_FilmnoAttention', 'UNet', or 'UNet_Film' with ``train_attention=True``;
+        NotImplementedError otherwise) is ``loss.backward()`` as
         well: the step runs ``spdm_train_loss_grad`` on a training engine cached apart from the sampling engines and
         leaves the gradients in ``noise_estimator.grads()`` (and d loss / d obs_cond in ``noise_estimator.grad_cond``)
         for a torch optimiser; ``noise_estimator.load_state_dict`` takes the updated weights back.
-        ``t`` / ``noise`` may be passed for reproducibility (the reference draws them with torch.randint / randn_like)."""
+        ``t`` / ``noise`` may be passed for reproducibility (the reference draws them with torch.randint / randn_like).
+        ``time_scale`` (model='UNet' with ``backward=True`` only; ValueError otherwise): the (B, time_dim) multiplier of
+        pe[t] that PositionalEncoding's Dropout(p=0.1) applies in training mode.  The caller draws it as the reference's
+        dropout would: ``F.dropout(torch.ones(B, 256, device='cuda'), 0.1, True)``.  Without it the step is the eval-mode
+        network's (no dropout)."""
+        if time_scale is not None and not (backward and self.simple):
+            raise ValueError("time_scale applies to model='UNet' (simple_Unet.py's dropout on pe[t]) with backward=True only")
         if backward:
             self._check_trainable()
         observation_batch = self.prepare_observation_batch(batch)
@@ -385,7 +397,7 @@ class Diffusion_DDPM:
         x_noisy = self.add_constraints(x_noisy, x_0_inpaint)
         if backward:
             eng = self._train_engine_for(B, x_noisy.shape[-2], x_noisy.shape[-1])
-            loss, noise_estimated, grads, grad_cond = eng.loss_and_grad(x_noisy, t, obs_cond, noise)
+            loss, noise_estimated, grads, grad_cond = eng.loss_and_grad(x_noisy, t, obs_cond, noise, time_scale=time_scale)
             self.noise_estimator._grads = grads
             self.noise_estimator.grad_cond = grad_cond
             return (loss, noise_estimated, x_noisy) if return_parts else loss

@@ -34,7 +34,8 @@ class SpdmEngine:
     def __init__(self, horizon: int, state_dim: int, cond_dim: int, max_batch: int, device: int = 0,
                  attention: bool = True, time_dim: int = 256, num_train_timesteps: int = 1000,
                  debug: bool = False, exact_fp32: bool = False, pin_geometry: bool = False,
-                 model: Optional[str] = None, train: bool = False, train_attention: bool = False):
+                 model: Optional[str] = None, train: bool = False, train_attention: bool = False,
+                 train_simple: bool = False):
         """``model``: None -> UNet_Film (``attention=True``) / UNet_FilmnoAttention (``attention=False``); a model name as
         Diffusion_DDPM takes it otherwise -- ``'UNet'`` (any non-FiLM name) is models/simple_Unet.py's network, whose
         time table is the state_dict's own ``pos_encoding.pos_encoding`` buffer: ``num_train_timesteps`` must then be
@@ -42,7 +43,9 @@ class SpdmEngine:
 
         ``train``: the handle also serves ``loss_and_grad`` (SPDM_FLAG_TRAIN; UNet_FilmnoAttention only).
         ``train_attention``: ``loss_and_grad`` for UNet_Film, through its SelfAttention blocks (SPDM_FLAG_TRAIN |
-        SPDM_FLAG_TRAIN_ATTENTION); needs the FiLM model with attention and implies ``train``."""
+        SPDM_FLAG_TRAIN_ATTENTION); needs the FiLM model with attention and implies ``train``.
+        ``train_simple``: ``loss_and_grad`` for simple_Unet.py's UNet (SPDM_FLAG_TRAIN | SPDM_FLAG_TRAIN_SIMPLE); needs
+        ``model='UNet'`` and implies ``train``."""
         self.lib = _lib.load()
         self.simple = model is not None and is_simple_model(model)
         if model is not None and not self.simple:
@@ -52,6 +55,10 @@ class SpdmEngine:
         if train_attention:
             if self.simple or not attention:
                 raise ValueError("train_attention=True needs UNet_Film (the FiLM model with attention)")
+            train = True
+        if train_simple:
+            if not self.simple:
+                raise ValueError("train_simple=True needs model='UNet' (simple_Unet.py's network)")
             train = True
         if not torch.cuda.is_available():
             raise RuntimeError("SpdmEngine needs a visible MI355X (HIP device); there is no CPU fallback")
@@ -63,9 +70,11 @@ class SpdmEngine:
                               self.max_batch, device, self.num_train_timesteps,
                               (_lib.SPDM_FLAG_DEBUG_KEEP if debug else 0) | (_lib.SPDM_FLAG_EXACT_FP32 if exact_fp32 else 0)
                               | (_lib.SPDM_FLAG_SIMPLE_UNET if self.simple else 0) | (_lib.SPDM_FLAG_TRAIN if train else 0)
-                              | (_lib.SPDM_FLAG_TRAIN_ATTENTION if train_attention else 0))
+                              | (_lib.SPDM_FLAG_TRAIN_ATTENTION if train_attention else 0)
+                              | (_lib.SPDM_FLAG_TRAIN_SIMPLE if train_simple else 0))
         self.train = bool(train)
         self.train_attention = bool(train_attention)
+        self.train_simple = bool(train_simple)
         self._cfg = cfg
         self._pin = bool(pin_geometry)
         self._create()
@@ -224,13 +233,18 @@ class SpdmEngine:
 
     # -- training ---------------------------------------------------------------------------------
     def loss_and_grad(self, x_noisy: torch.Tensor, t, cond: Optional[torch.Tensor], noise: torch.Tensor,
-                      flat: bool = False):
+                      flat: bool = False, time_scale: Optional[torch.Tensor] = None):
         """One training step's forward and backward pass (models/diffusion_ddpm.py:128-173): eps = unet(x_noisy, t, cond),
         loss = mean((noise - eps)^2), and the gradients of loss.  Returns ``(loss, eps, grads, grad_cond)``: ``grads`` maps
         every state_dict name to its gradient (torch layout, on the device) -- or, ``flat=True``, is one flat tensor laid
-        out as the packed state_dict; ``grad_cond`` is d loss / d cond (None without cond)."""
+        out as the packed state_dict; ``grad_cond`` is d loss / d cond (None without cond).  For simple_Unet.py's UNet
+        (``train_simple=True``) ``grads`` covers its parameters only (not the ``pos_encoding.pos_encoding`` buffer, whose
+        slot of the flat tensor holds zeros), and ``time_scale`` (B, time_dim) -- PositionalEncoding's dropout mask over
+        (1 - p), e.g. ``F.dropout(torch.ones(B, 256, device='cuda'), 0.1, True)`` -- multiplies pe[t_b] (training mode)."""
         if not self.train:
             raise RuntimeError("loss_and_grad needs an engine created with train=True")
+        if time_scale is not None and not self.train_simple:
+            raise ValueError("time_scale needs an engine created with train_simple=True (simple_Unet.py's UNet)")
         if not self._weights_loaded:
             raise RuntimeError("load_state_dict first")
         B = x_noisy.shape[0]
@@ -243,6 +257,11 @@ class SpdmEngine:
         eps = torch.empty((B, 1, H, D), device=self.device, dtype=torch.float32)
         g = torch.empty(self._blob_floats, device=self.device, dtype=torch.float32)
         gc = torch.empty((B,) + tuple(cond.shape[1:]), device=self.device, dtype=torch.float32) if cs is not None else None
+        if time_scale is not None:
+            if tuple(time_scale.shape) != (B, self.time_dim):
+                raise ValueError(f"time_scale must be (B, time_dim) = ({B}, {self.time_dim}), got {tuple(time_scale.shape)}")
+            ts = self._dev(time_scale)
+            _lib.check(self.lib.spdm_train_set_time_scale(self._h, _ptr(ts), B), "spdm_train_set_time_scale")
         _lib.check(self.lib.spdm_train_loss_grad(self._h, B, _ptr(xs), tt.ctypes.data_as(ctypes.c_void_p), int(tt.size),
                                                  _ptr(cs), _ptr(ns), _ptr(loss), _ptr(eps), _ptr(g), _ptr(gc),
                                                  self._stream()), "spdm_train_loss_grad")
@@ -250,6 +269,8 @@ class SpdmEngine:
             return loss, eps, g, gc
         grads = {}
         for name, off, shape in self._index:
+            if self.simple and name == "pos_encoding.pos_encoding":      # a buffer, not a parameter
+                continue
             n = int(np.prod(shape)) if shape else 1
             grads[name] = g[off:off + n].view(shape)
         return loss, eps, grads, gc

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Time one training step of UNet_Film_noAttention -- or, with --attention, of UNet_Film with its six SelfAttention blocks
-(SpdmEngine(train_attention=True)) -- (H = 32, D = 3) at B = 16, 64, 256: the HIP step (spdm_train_loss_grad:
+(SpdmEngine(train_attention=True)), or, with --simple, of simple_Unet.py's UNet (SpdmEngine(model='UNet', train_simple=True),
+CPU side: tests/simple_unet_ref.py) -- (H = 32, D = 3) at B = 16, 64, 256: the HIP step (spdm_train_loss_grad:
 forward, MSE loss, full backward), the host weight refresh an optimiser step then needs (SpdmEngine.refresh_weights), and
 torch-CPU fp32 autograd of the oracle on 16 threads for the same step.  One JSON line per batch size.
-usage: python tools/bench_train.py [--attention] [--iters N] [B ...]"""
+usage: python tools/bench_train.py [--attention | --simple] [--iters N] [B ...]"""
 import json
 import os
 import statistics
@@ -12,19 +13,24 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch
 
 from oracle.unet_film_ref import unet_film_forward
+from simple_unet_ref import simple_unet_forward
 from state_policy_diffusionmodel_amd.engine import SpdmEngine
 from state_policy_diffusionmodel_amd.weights import random_state_dict
 
 H, D, COND = 32, 3, 1350
 
 
-def cpu_step(sd, x, t, cond, noise, attention):
-    params = {k: torch.from_numpy(np.asarray(v)).requires_grad_(True) for k, v in sd.items()}
+def cpu_step(sd, x, t, cond, noise, attention, simple=False):
+    params = {k: torch.from_numpy(np.asarray(v)).requires_grad_(k != "pos_encoding.pos_encoding") for k, v in sd.items()}
     fwd = getattr(unet_film_forward, "__wrapped__", unet_film_forward)
+    if simple:
+        sfwd = getattr(simple_unet_forward, "__wrapped__", simple_unet_forward)
+        fwd = lambda p, x, t, c, attention: sfwd(p, x, t, c)       # noqa: E731
     t0 = time.perf_counter()
     with torch.enable_grad():
         loss = torch.mean((noise - fwd(params, x, t, cond, attention=attention)) ** 2)
@@ -38,20 +44,27 @@ def main():
     attention = "--attention" in args
     if attention:
         args.remove("--attention")
+    simple = "--simple" in args
+    if simple:
+        args.remove("--simple")
     if "--iters" in args:
         i = args.index("--iters")
         iters = int(args[i + 1])
         del args[i:i + 2]
     batches = [int(a) for a in args] or [16, 64, 256]
     torch.set_num_threads(16)
-    sd = random_state_dict(COND, seed=0, attention=attention)
+    sd = (random_state_dict(COND, seed=0, model="UNet", noise_steps=1000) if simple else
+          random_state_dict(COND, seed=0, attention=attention))
     for B in batches:
         g = torch.Generator().manual_seed(B)
         x = torch.randn(B, 1, H, D, generator=g)
         noise = torch.randn(B, 1, H, D, generator=g)
         cond = torch.randn(B, 1, 10, 135, generator=g)
         t = torch.randint(0, 1000, (B,), generator=g)
-        eng = SpdmEngine(H, D, COND, max_batch=B, attention=attention, train=True, train_attention=attention)
+        if simple:
+            eng = SpdmEngine(H, D, COND, max_batch=B, model="UNet", num_train_timesteps=1001, train_simple=True)
+        else:
+            eng = SpdmEngine(H, D, COND, max_batch=B, attention=attention, train=True, train_attention=attention)
         eng.load_state_dict(sd)
         xd, nd, cd = x.cuda(), noise.cuda(), cond.cuda()
         for _ in range(3):
@@ -71,9 +84,10 @@ def main():
             refresh.append((time.perf_counter() - t0) * 1e3)
         ws = eng.device_bytes
         eng.close()
-        cpu = cpu_step(sd, x, t, cond, noise, attention)
+        cpu = cpu_step(sd, x, t, cond, noise, attention, simple)
         hip = statistics.median(step)
-        print(json.dumps({"model": "UNet_Film" if attention else "UNet_Film_noAttention", "B": B, "H": H, "D": D, "hip_step_ms": round(hip, 3), "hip_step_min_ms": round(min(step), 3),
+        model = "UNet (simple_Unet.py)" if simple else "UNet_Film" if attention else "UNet_Film_noAttention"
+        print(json.dumps({"model": model, "B": B, "H": H, "D": D, "hip_step_ms": round(hip, 3), "hip_step_min_ms": round(min(step), 3),
                           "weight_refresh_ms": round(statistics.median(refresh), 2), "device_bytes": ws,
                           "cpu_autograd_ms": round(cpu, 1), "cpu_threads": 16, "cpu_over_hip": round(cpu / hip, 1)}),
               flush=True)
