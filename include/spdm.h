@@ -129,9 +129,28 @@ void spdm_destroy(spdm_handle* h);
 
 /* Replaces: load_state_dict of the `noise_estimator.*` tensors
  * (generate.py:25-27 -> Lightning load_from_checkpoint).  `h_blob` is a HOST
- * array; the library re-lays the weights out for its kernels and uploads them. */
+ * array; the library uploads it once and re-lays the weights out for its kernels on the device. */
 int  spdm_load_weights(spdm_handle* h, const float* h_blob, size_t n_floats,
                        const spdm_tensor_index* h_index, int32_t n_index);
+
+/* Put updated weights (an optimiser step) into a loaded handle, in place: no allocation, the same workspace.
+ * `d_blob` is a DEVICE blob of n_floats floats laid out as the blob last given to spdm_load_weights -- the layout
+ * spdm_train_loss_grad writes its gradient in, so `param -= lr * grad` works on it directly.  Any handle kind.
+ * Enqueues the split format's range check on `stream` and synchronises once to read its verdicts (and outc's bias,
+ * a host scalar of the handle); then enqueues the re-layout of every weight copy on `stream` and returns:
+ * `d_blob` must stay unchanged until `stream` has passed those kernels.  The time-embedding tables are recomputed
+ * on the next evaluation; an open sampling session ends (spdm_sample_run answers SPDM_ERR_STATE until the next
+ * spdm_sample_begin); a captured step graph whose outc bias changed is captured again on its next run.
+ * The `pos_encoding.pos_encoding` slot of a simple_Unet.py blob is not read: the time table stays as loaded.
+ * SPDM_ERR_INVALID: null pointer, or n_floats differs from the loaded blob's.  SPDM_ERR_STATE: no weights loaded;
+ * or the set of tensors outside the split format's range (spdm_demoted_tensors) would change -- the workspace plan
+ * depends on it: nothing is written, the handle keeps its weights bit for bit, and spdm_last_error names the first
+ * such tensor; load the blob into a new handle instead. */
+int  spdm_update_weights(spdm_handle* h, const float* d_blob, size_t n_floats, void* stream);
+
+/* Test hook: a 64-bit hash of the bytes of every device weight copy (in the order spdm_load_weights made them),
+ * of outc's bias and of the set of tensors outside the split format's range.  Synchronises the device. */
+int  spdm_debug_weight_digest(const spdm_handle* h, uint64_t* out);
 
 /* Optional: overwrite the sinusoidal table pos_encoding(t) for t = 0..T-1
  * (models/Unet_FiLmLayer.py:266-274), (T, time_dim) fp32 on the host.  By

@@ -19,6 +19,7 @@ SPDM_FLAG_SIMPLE_UNET = 4
 SPDM_FLAG_TRAIN = 8
 SPDM_FLAG_TRAIN_ATTENTION = 16
 SPDM_FLAG_TRAIN_SIMPLE = 32
+SPDM_ERR_STATE = -3
 ABI_VERSION = 2
 
 
@@ -49,6 +50,8 @@ SYMBOLS = {
     "spdm_create": (c_int32, [POINTER(SpdmConfig), POINTER(c_void_p)]),
     "spdm_destroy": (None, [c_void_p]),
     "spdm_load_weights": (c_int32, [c_void_p, c_void_p, c_size_t, POINTER(TensorIndex), c_int32]),
+    "spdm_update_weights": (c_int32, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "spdm_debug_weight_digest": (c_int32, [c_void_p, POINTER(c_uint64)]),
     "spdm_set_time_table": (c_int32, [c_void_p, c_void_p, c_int32]),
     "spdm_set_schedule": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_float, c_float]),
     "spdm_set_schedule_tables": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),

@@ -380,4 +380,32 @@ hipError_t launch_sa_head(int C, const float* x, float* att, int rows, const flo
 hipError_t launch_sa_qkv(int C, const float* x, float* qkv, int rows, const float* wf_in, const float* b_in, const float* ln_g,
                          const float* ln_b, const float* ab, int L, hipStream_t s, const FilmSpec* fs = nullptr);
 
+// ---- weight re-layout on the device (weight_layout.hip; spdm_api.hip records the copies as it loads) ----------------------
+// One kernel-layout copy of a weight as a gather from the torch-layout blob: logical dense array [n0][n1][n2], element
+// (i0, i1, i2) = blob[src + sum_k contrib_k] where axis k contributes i_k * stride[k] (zero when i_k >= lim[k]) or, tab[k] >= 0,
+// tabs[tab[k] + i_k] (zero when that entry is -1).  fmt says how the logical elements become the destination:
+//   WL_F32      the logical array itself (bit copy)
+//   WL_SPLIT    split format of it: per 32-element chunk 32 fp16 hi | 32 fp16 lo of 128 w (same byte size)
+//   WL_FRAG     frag_order_weights(split, taps, N, K) of it ([taps][N][K])
+//   WL_PERM_HI / _LO   the hi / lo fp16 halves of a [out][64] matrix in sa_fused.hip's fragment order (half the bytes)
+//   WL_RANGE    no destination: flags[slot] = 1 when an element is outside the split format's range, !(|w| < 511)
+enum { WL_F32 = 0, WL_SPLIT, WL_FRAG, WL_PERM_HI, WL_PERM_LO, WL_RANGE, WL_NFMT };
+struct WeightCopy {
+    long long src = 0;
+    long long stride[3] = {0, 0, 0};
+    int n[3] = {1, 1, 1};
+    int lim[3] = {1, 1, 1};
+    int tab[3] = {-1, -1, -1};
+    int fmt = WL_F32;
+    int taps = 1, N = 0, K = 0;          // WL_FRAG geometry
+    int slot = -1;                       // WL_RANGE: flag index (one per tensor name)
+    void* dst = nullptr;
+    long long count = 0;                 // destination floats (WL_RANGE: logical elements)
+    long long blk0 = 0;                  // first workgroup of this copy in its format's launch
+};
+long long weight_copy_blocks(long long count);
+// one launch over copies[0, n_copies) -- all of format fmt, blk0 ascending, `blocks` workgroups in all
+hipError_t launch_weight_copies(int fmt, const float* blob, const long long* tabs, const WeightCopy* copies, int n_copies,
+                                long long blocks, int* flags, hipStream_t s);
+
 }  // namespace spdm

@@ -143,7 +143,19 @@ struct spdm_handle {
     ResampleW down[3], up[3];
     AttnW sa[6];
     float* outc_w = nullptr;
-    float outc_b = 0.f;
+    float outc_b = 0.f;                   // a host scalar: the step kernel's argument
+    // device weight layouts (Loader, weight_layout.hip): what spdm_update_weights replays on a new blob
+    std::vector<WeightCopy> wl_copies;    // every copy spdm_load_weights made, in the order it made them (spdm_debug_weight_digest)
+    WeightCopy* d_wl = nullptr;           // ... on the device, grouped by format
+    WeightCopy* d_wl_range = nullptr;     // the split format's range checks (WL_RANGE)
+    int wl_first[WL_NFMT] = {}, wl_count[WL_NFMT] = {};
+    long long wl_blocks[WL_NFMT] = {};    // per format: first entry, entries and workgroups of its launch
+    long long* d_wl_tabs = nullptr;       // offset tables of the copies' table axes
+    int* d_wl_flags = nullptr;            // [slots] range verdicts + outc's bias (bits), read back together
+    std::vector<std::string> wl_slots;    // tensor name of each range slot
+    std::vector<int> wl_oor;              // ... outside the range at load (those tensors have no split copies)
+    size_t blob_floats = 0;               // size of the loaded blob
+    long long outc_b_off = -1;            // outc.bias in it
     bool weights_loaded = false, temb_ready = false;
     bool train = false;                   // SPDM_FLAG_TRAIN: spdm_train_loss_grad (train_pass)
     bool train_attn = false;              // ... SPDM_FLAG_TRAIN_ATTENTION: through the SelfAttention blocks (TrainPass::sa_fwd / sa_bwd)
@@ -524,113 +536,163 @@ extern "C" size_t spdm_device_bytes(const spdm_handle* h) { return h ? h->persis
 
 // -------------------------------------------------------------------------------------------------
 // weights
+//
+// Every kernel-layout copy of a weight is made on the device from the torch-layout blob (weight_layout.hip).  The Loader
+// below is the one place each layout is defined: it records one WeightCopy (a gather, kernels.h) per copy as it walks the
+// network, and spdm_load_weights / spdm_update_weights run the recorded table.  It walks twice: the plan pass checks every
+// name and shape and records the split format's range checks; once the device has answered them, the load pass allocates
+// the copies -- a tensor outside the range gets no split copy -- and records them.
+static char g_plan_only;                   // the plan pass's stand-in for a copy it does not allocate
+
 struct Loader {
     spdm_handle* h;
-    const float* blob;
+    const float* blob;                     // host blob (spdm_load_weights): the few values the host itself keeps
     size_t n;
     std::map<std::string, const spdm_tensor_index*> idx;
     int err = SPDM_OK;
+    bool plan = true;
+    std::vector<int> oor;                  // load pass: per range slot, outside the split format's range
+    std::map<std::string, int> slot_of;    // range slot of each tensor name (the stacked cond_emb_layer is one name)
+    std::vector<std::string> slots;
+    std::vector<WeightCopy> copies, ranges;
+    std::vector<long long> tabs;           // offset tables of the copies' table axes
     std::set<std::string> demoted_names;   // tensors outside the split format's range (counted once each, however many copies they lose)
     void demote(const std::string& name) { demoted_names.insert(name); if (h) h->demoted = (int)demoted_names.size(); }
-    const float* find(const std::string& name, std::initializer_list<int> shape) {
+    long long at(const std::string& name, std::initializer_list<int> shape) {
         auto it = idx.find(name);
-        if (it == idx.end()) { err = fail(SPDM_ERR_MISSING, "tensor '%s' not in the index", name.c_str()); return nullptr; }
+        if (it == idx.end()) { err = fail(SPDM_ERR_MISSING, "tensor '%s' not in the index", name.c_str()); return -1; }
         const spdm_tensor_index* e = it->second;
         size_t numel = 1;
         int d = 0;
         for (int sdim : shape) {
-            if (d >= e->ndim || e->shape[d] != sdim) { err = fail(SPDM_ERR_INVALID, "tensor '%s': unexpected shape", name.c_str()); return nullptr; }
+            if (d >= e->ndim || e->shape[d] != sdim) { err = fail(SPDM_ERR_INVALID, "tensor '%s': unexpected shape", name.c_str()); return -1; }
             numel *= (size_t)sdim;
             ++d;
         }
-        if (d != e->ndim || numel != e->numel || e->offset + e->numel > n) { err = fail(SPDM_ERR_INVALID, "tensor '%s': bad extent", name.c_str()); return nullptr; }
-        return blob + e->offset;
+        if (d != e->ndim || numel != e->numel || e->offset + e->numel > n) { err = fail(SPDM_ERR_INVALID, "tensor '%s': bad extent", name.c_str()); return -1; }
+        return (long long)e->offset;
     }
-    // fp32 [rows][K] -> per 32-k chunk [32 x fp16 hi | 32 x fp16 lo] of x' = 128 x (conv_gemm.hip, PREC_SPLIT):
-    // hi = fp16(x'), lo = fp16(x' - hi); same byte size as the fp32 array
-    // The split format scales weights by 2^7 before the fp16 cast: |w| >= 511.75 would become inf.  Such a tensor gets no
-    // split copy and its layer runs on the exact fp32 kernel instead (same results, 5x slower for that layer).
-    static bool split_range_ok(const std::vector<float>& v) {
-        float mx = 0.f;
-        for (float x : v) { const float ax = std::fabs(x); if (!(ax <= mx)) mx = ax; }    // NaN-propagating max
-        return mx < 511.0f;
+    // ---- the gathers ----
+    // dense [n0][n1][n2] read row-major from src
+    static WeightCopy dense(long long src, int n0, int n1, int n2) {
+        WeightCopy c;
+        c.src = src;
+        c.n[0] = c.lim[0] = n0; c.n[1] = c.lim[1] = n1; c.n[2] = c.lim[2] = n2;
+        c.stride[0] = (long long)n1 * n2; c.stride[1] = n2; c.stride[2] = 1;
+        return c;
     }
-    static std::vector<float> split_format(const std::vector<float>& v) {
-        std::vector<float> out(v.size());
-        for (size_t base = 0; base < v.size(); base += 32) {
-            _Float16* hp = reinterpret_cast<_Float16*>(&out[base]);
-            for (int j = 0; j < 32; ++j) {
-                const float x = v[base + j] * 128.0f;
-                const _Float16 hi = (_Float16)x;
-                hp[j] = hi;
-                hp[32 + j] = (_Float16)(x - (float)hi);
+    // axis 0 = the taps of a (Cout, Cin, 3, 3) tensor: taps == 3 keeps only the centre column (W == 1 levels, where the left /
+    // right taps only ever see zero padding); flipped = rotated 180 degrees (the data gradient's convolution)
+    static void tap_axis(WeightCopy& c, int taps, bool flipped) {
+        c.n[0] = c.lim[0] = taps;
+        if (taps == 9) { c.src += flipped ? 8 : 0; c.stride[0] = flipped ? -1 : 1; }
+        else { c.src += flipped ? 7 : 1; c.stride[0] = flipped ? -3 : 3; }
+    }
+    int table(const std::vector<long long>& t) {
+        const int at = (int)tabs.size();
+        tabs.insert(tabs.end(), t.begin(), t.end());
+        return at;
+    }
+    // storage position -> source step of its real channel (ChanMap), -1 for a padding lane
+    int map_table(const ChanMap& m, long long stride) {
+        std::vector<long long> t(m.width, -1);
+        for (int i = 0; i < m.real(); ++i) t[m.pos[i]] = (long long)i * stride;
+        return table(t);
+    }
+    // every element the copy can read lies inside the blob
+    bool inside(const WeightCopy& c) const {
+        long long lo = c.src, hi = c.src;
+        for (int k = 0; k < 3; ++k) {
+            if (c.tab[k] >= 0) {
+                long long tmin = LLONG_MAX, tmax = LLONG_MIN;
+                for (int i = 0; i < c.n[k]; ++i) {
+                    const long long t = tabs[c.tab[k] + i];
+                    if (t >= 0) { tmin = std::min(tmin, t); tmax = std::max(tmax, t); }
+                }
+                if (tmin == LLONG_MAX) continue;
+                lo += tmin; hi += tmax;
+            } else {
+                const long long span = (long long)(std::min(c.lim[k], c.n[k]) - 1) * c.stride[k];
+                if (span < 0) lo += span; else hi += span;
             }
         }
-        return out;
+        return lo >= 0 && hi < (long long)n;
     }
-    float* upload_split(const std::vector<float>& v, size_t K, const std::string& name) {
-        if (K % 32 != 0) { err = fail(SPDM_ERR_INVALID, "split weights need K %% 32 == 0"); return nullptr; }
-        if (!split_range_ok(v)) { demote(name); return nullptr; }
-        return upload(split_format(v));
-    }
-    float* upload(const std::vector<float>& v) {
+    void* put(WeightCopy c, int fmt) {
+        c.fmt = fmt;
+        c.count = (long long)c.n[0] * c.n[1] * c.n[2];
+        if (fmt == WL_PERM_HI || fmt == WL_PERM_LO) c.count /= 2;          // fp16 halves
+        if (plan) return &g_plan_only;
+        if (!inside(c)) { err = fail(SPDM_ERR_INVALID, "weight copy reads outside the blob"); return nullptr; }
         void* p = nullptr;
-        if (dev_alloc(h, &p, v.size() * sizeof(float)) != SPDM_OK) { err = SPDM_ERR_HIP; return nullptr; }
-        if (hipMemcpy(p, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-            err = fail(SPDM_ERR_HIP, "weight upload failed");
-            return nullptr;
-        }
-        return (float*)p;
+        if (dev_alloc(h, &p, (size_t)c.count * sizeof(float)) != SPDM_OK) { err = SPDM_ERR_HIP; return nullptr; }
+        c.dst = p;
+        copies.push_back(c);
+        return p;
     }
-    // (Cout,Cin,3,3) -> [taps][Cout][Cin]; taps == 3 keeps only the centre column (W == 1 levels, where
-    // the left/right taps only ever see zero padding)
-    static std::vector<float> conv_taps(const float* src, int cout, int cin, int taps) {
-        std::vector<float> v((size_t)taps * cout * cin);
-        for (int t = 0; t < taps; ++t) {
-            const int kh = (taps == 9) ? t / 3 : t, kw = (taps == 9) ? t % 3 : 1;
-            for (int o = 0; o < cout; ++o)
-                for (int i = 0; i < cin; ++i)
-                    v[((size_t)t * cout + o) * cin + i] = src[(((size_t)o * cin + i) * 3 + kh) * 3 + kw];
-        }
-        return v;
+    float* f32(const WeightCopy& c) { return (float*)put(c, WL_F32); }
+    // fragment-order split copy (frag_order_weights, kernels.h) of the logical [taps][N][K] array
+    float* frag(WeightCopy c, int taps, int N, int K) {
+        c.taps = taps; c.N = N; c.K = K;
+        return (float*)put(c, WL_FRAG);
     }
-    // (Cout,Cin,3,3) -> [taps][Cin][Cout] with the taps rotated 180 degrees: the weights of the convolution that takes the output
-    // gradient to the input gradient (dX = conv3x3(dY, rot180(W) with Cin and Cout swapped)); tap order as conv_taps
-    static std::vector<float> conv_taps_flipped(const float* src, int cout, int cin, int taps) {
-        std::vector<float> v((size_t)taps * cin * cout);
-        for (int t = 0; t < taps; ++t) {
-            const int kh = (taps == 9) ? 2 - t / 3 : 2 - t, kw = (taps == 9) ? 2 - t % 3 : 1;
-            for (int i = 0; i < cin; ++i)
-                for (int o = 0; o < cout; ++o)
-                    v[((size_t)t * cin + i) * cout + o] = src[(((size_t)o * cin + i) * 3 + kh) * 3 + kw];
+    // The split format scales weights by 2^7 before the fp16 cast: |w| >= 511.75 would become inf.  Such a tensor gets no
+    // split copy and its layer runs on the exact fp32 kernel instead (same results, 5x slower for that layer).  Plan pass:
+    // queue the check of this copy's logical array under the tensor's name; load pass: the device's verdict.
+    bool in_range(WeightCopy c, const std::string& name) {
+        auto it = slot_of.find(name);
+        int s = 0;
+        if (it == slot_of.end()) { s = (int)slots.size(); slot_of[name] = s; slots.push_back(name); }
+        else s = it->second;
+        if (plan) {
+            c.fmt = WL_RANGE; c.slot = s; c.count = (long long)c.n[0] * c.n[1] * c.n[2];
+            if (!inside(c)) { err = fail(SPDM_ERR_INVALID, "weight copy reads outside the blob"); return false; }
+            ranges.push_back(c);
+            return true;
         }
-        return v;
+        if (oor[s]) { demote(name); return false; }
+        return true;
     }
+    // fp32 [rows][K] -> per 32-k chunk [32 x fp16 hi | 32 x fp16 lo] of x' = 128 x (conv_gemm.hip, PREC_SPLIT)
+    float* split(const WeightCopy& c, int K, const std::string& name) {
+        if (K % 32 != 0) { err = fail(SPDM_ERR_INVALID, "split weights need K %% 32 == 0"); return nullptr; }
+        if (!in_range(c, name)) return nullptr;
+        return (float*)put(c, WL_SPLIT);
+    }
+    // (Cout,Cin,3,3) -> w [taps][Cout][Cin], its split and fragment-order copies, and (SPDM_FLAG_TRAIN) wt [taps][Cin][Cout]
+    // with the taps rotated 180 degrees: the weights of the convolution that takes the output gradient to the input gradient
     ConvW conv(const std::string& name, int cout, int cin, int taps) {
         ConvW c;
-        const float* src = find(name, {cout, cin, 3, 3});
-        if (!src) return c;
-        const std::vector<float> v = conv_taps(src, cout, cin, taps);
-        c.w = upload(v);
-        if (h->train) c.wt = upload(conv_taps_flipped(src, cout, cin, taps));
-        c.ws = (cin % 32 == 0) ? upload_split(v, cin, name) : nullptr;
-        if (c.ws && cout % 64 == 0) c.wf = upload(frag_order_weights(split_format(v), taps, cout, cin));
+        const long long o = at(name, {cout, cin, 3, 3});
+        if (o < 0) return c;
+        WeightCopy v = dense(o, taps, cout, cin);
+        v.stride[1] = (long long)cin * 9; v.stride[2] = 9;
+        tap_axis(v, taps, false);
+        c.w = f32(v);
+        if (h->train) {
+            WeightCopy t = dense(o, taps, cin, cout);
+            t.stride[1] = 9; t.stride[2] = (long long)cin * 9;
+            tap_axis(t, taps, true);
+            c.wt = f32(t);
+        }
+        c.ws = (cin % 32 == 0) ? split(v, cin, name) : nullptr;
+        if (c.ws && cout % 64 == 0) c.wf = frag(v, taps, cout, cin);
         c.taps = taps; c.cin = cin; c.cout = cout;
         return c;
     }
     float* vec(const std::string& name, int nelem) {
-        const float* src = find(name, {nelem});
-        if (!src) return nullptr;
-        return upload(std::vector<float>(src, src + nelem));
+        const long long o = at(name, {nelem});
+        return o < 0 ? nullptr : f32(dense(o, 1, 1, nelem));
     }
+    // (out, in) -> [out][in_pad], zero columns beyond in
     LinW linear(const std::string& wname, const std::string& bname, int out, int in, int in_pad) {
         LinW l;
-        const float* w = find(wname, {out, in});
-        if (!w) return l;
-        std::vector<float> v((size_t)out * in_pad, 0.f);
-        for (int o = 0; o < out; ++o) memcpy(&v[(size_t)o * in_pad], w + (size_t)o * in, sizeof(float) * in);
-        l.w = upload(v);
-        l.ws = (in_pad % 32 == 0) ? upload_split(v, in_pad, wname) : nullptr;
+        const long long o = at(wname, {out, in});
+        if (o < 0) return l;
+        WeightCopy v = dense(o, 1, out, in_pad);
+        v.stride[1] = in; v.lim[2] = in;
+        l.w = f32(v);
+        l.ws = (in_pad % 32 == 0) ? split(v, in_pad, wname) : nullptr;
         l.b = vec(bname, out);
         l.in = in_pad; l.out = out;
         return l;
@@ -650,99 +712,68 @@ struct Loader {
         r.emb = linear(p + ".emb_layer.1.weight", p + ".emb_layer.1.bias", cout, h->cfg.time_dim, h->cfg.time_dim);
         if (h->cfg.cond_dim > 0) {
             r.film = linear(p + ".cond_encoder.2.weight", p + ".cond_encoder.2.bias", 2 * cout, h->cfg.cond_dim, h->film_kp);
-            if (h->train) {
-                const float* w = find(p + ".cond_encoder.2.weight", {2 * cout, h->cfg.cond_dim});
-                if (w) {
-                    std::vector<float> t((size_t)align_up(h->cfg.cond_dim, 64) * 2 * cout, 0.f);
-                    for (int o = 0; o < 2 * cout; ++o)
-                        for (int i = 0; i < h->cfg.cond_dim; ++i) t[(size_t)i * 2 * cout + o] = w[(size_t)o * h->cfg.cond_dim + i];
-                    r.film.wt = upload(t);
+            if (h->train) {      // (2 cout, cond_dim) -> [cond_dim padded to 64][2 cout]: the FiLM encoder's data gradient
+                const int cd = h->cfg.cond_dim;
+                const long long o = at(p + ".cond_encoder.2.weight", {2 * cout, cd});
+                if (o >= 0) {
+                    WeightCopy t = dense(o, 1, (int)align_up(cd, 64), 2 * cout);
+                    t.stride[1] = 1; t.lim[1] = cd; t.stride[2] = cd;
+                    r.film.wt = f32(t);
                 }
             }
         }
         r.cout = cout;
         return r;
     }
-    // (out, 64) fp32 -> two fp16 arrays (hi, lo of 128 x) of [out][64] in fragment order, input axis permuted inside each group of 16 by
-    // perm16 = 0 1 2 3 8 9 10 11 | 4 5 6 7 12 13 14 15: the k-slot order of an accumulator tile used as B operand
+    // (out, 64) fp32 -> two fp16 arrays (hi, lo of 128 x) of [out][64] in MFMA A-fragment order, input axis permuted inside each
+    // group of 16 by perm16 = 0 1 2 3 8 9 10 11 | 4 5 6 7 12 13 14 15: the k-slot order of an accumulator tile used as B operand
     // (sa_fused.hip)
     void perm_split(const std::string& wname, int out, void** hi_dev, void** lo_dev) {
-        static const int perm16[16] = {0, 1, 2, 3, 8, 9, 10, 11, 4, 5, 6, 7, 12, 13, 14, 15};
-        const float* w = find(wname, {out, 64});
-        if (!w) return;
-        if (!split_range_ok(std::vector<float>(w, w + (size_t)out * 64))) { demote(wname); return; }   // block falls back to the GEMM chain
-        std::vector<_Float16> hi((size_t)out * 64), lo((size_t)out * 64);
-        for (int o = 0; o < out; ++o)
-            for (int g = 0; g < 4; ++g)
-                for (int pos = 0; pos < 16; ++pos) {
-                    const float x = w[(size_t)o * 64 + 16 * g + perm16[pos]] * 128.0f;
-                    const _Float16 h16 = (_Float16)x;
-                    hi[(size_t)o * 64 + 16 * g + pos] = h16;
-                    lo[(size_t)o * 64 + 16 * g + pos] = (_Float16)(x - (float)h16);
-                }
-        // device layout = MFMA A-fragment order: block (o / 32) * 4 + ks, lane kh * 32 + o % 32 -> halfs [o][16 ks + 8 kh ..]
-        auto to_frag = [&](const std::vector<_Float16>& rm) {
-            std::vector<_Float16> f(rm.size());
-            for (int o = 0; o < out; ++o)
-                for (int ks = 0; ks < 4; ++ks)
-                    for (int kh = 0; kh < 2; ++kh)
-                        for (int j = 0; j < 8; ++j)
-                            f[((((size_t)(o / 32) * 4 + ks) * 64) + kh * 32 + o % 32) * 8 + j] = rm[(size_t)o * 64 + 16 * ks + 8 * kh + j];
-            return f;
-        };
-        hi = to_frag(hi);
-        lo = to_frag(lo);
-        for (int which = 0; which < 2; ++which) {
-            void* d = nullptr;
-            const std::vector<_Float16>& src = which ? lo : hi;
-            if (dev_alloc(h, &d, src.size() * sizeof(_Float16)) != SPDM_OK) { err = SPDM_ERR_HIP; return; }
-            if (hipMemcpy(d, src.data(), src.size() * sizeof(_Float16), hipMemcpyHostToDevice) != hipSuccess) {
-                err = fail(SPDM_ERR_HIP, "weight upload failed");
-                return;
-            }
-            *(which ? lo_dev : hi_dev) = d;
-        }
+        const long long o = at(wname, {out, 64});
+        if (o < 0) return;
+        const WeightCopy v = dense(o, 1, out, 64);
+        if (!in_range(v, wname)) return;        // block falls back to the GEMM chain
+        *hi_dev = put(v, WL_PERM_HI);
+        *lo_dev = put(v, WL_PERM_LO);
     }
     // fragment-order split copy of a (out, in) Linear weight (sa_tail.hip reads its B operands straight from it)
     float* linear_frag(const std::string& wname, int out, int in) {
-        const float* w = find(wname, {out, in});
-        if (!w) return nullptr;
-        if (!split_range_ok(std::vector<float>(w, w + (size_t)out * in))) { demote(wname); return nullptr; }
-        return upload(frag_order_weights(split_format(std::vector<float>(w, w + (size_t)out * in)), 1, out, in));
+        const long long o = at(wname, {out, in});
+        if (o < 0) return nullptr;
+        const WeightCopy v = dense(o, 1, out, in);
+        if (!in_range(v, wname)) return nullptr;
+        return frag(v, 1, out, in);
     }
     // ---- models/simple_Unet.py: re-layout into channel-padded storage (ChanMap) ----
     // (Cout, Cin, 3, 3) -> [taps][mo.width][mi.width], real (o, i) at (mo.pos[o], mi.pos[i]), zeros elsewhere
     ConvW conv_mapped(const std::string& name, const ChanMap& mo, const ChanMap& mi, int taps) {
         ConvW c;
         const int co = mo.real(), ci = mi.real(), N = mo.width, K = mi.width;
-        const float* src = find(name, {co, ci, 3, 3});
-        if (!src) return c;
-        std::vector<float> v((size_t)taps * N * K, 0.f);
-        for (int t = 0; t < taps; ++t) {
-            const int kh = (taps == 9) ? t / 3 : t, kw = (taps == 9) ? t % 3 : 1;
-            for (int o = 0; o < co; ++o)
-                for (int i = 0; i < ci; ++i)
-                    v[((size_t)t * N + mo.pos[o]) * K + mi.pos[i]] = src[(((size_t)o * ci + i) * 3 + kh) * 3 + kw];
-        }
-        c.w = upload(v);
-        c.ws = upload_split(v, K, name);
-        if (c.ws) c.wf = upload(frag_order_weights(split_format(v), taps, N, K));
+        const long long o = at(name, {co, ci, 3, 3});
+        if (o < 0) return c;
+        WeightCopy v = dense(o, taps, N, K);
+        tap_axis(v, taps, false);
+        v.tab[1] = map_table(mo, (long long)ci * 9);
+        v.tab[2] = map_table(mi, 9);
+        c.w = f32(v);
+        c.ws = split(v, K, name);
+        if (c.ws) c.wf = frag(v, taps, N, K);
         if (h->train_simple) {     // [taps][K][N], taps rotated 180 degrees (conv_taps_flipped at the padded widths)
-            std::vector<float> t((size_t)taps * K * N, 0.f);
-            for (int tp = 0; tp < taps; ++tp)
-                for (int o = 0; o < N; ++o)
-                    for (int i = 0; i < K; ++i) t[((size_t)(taps - 1 - tp) * K + i) * N + o] = v[((size_t)tp * N + o) * K + i];
-            c.wt = upload(t);
+            WeightCopy t = dense(o, taps, K, N);
+            tap_axis(t, taps, true);
+            t.tab[1] = map_table(mi, 9);
+            t.tab[2] = map_table(mo, (long long)ci * 9);
+            c.wt = f32(t);
         }
         c.taps = taps; c.cin = K; c.cout = N; c.cnorm = co;
         return c;
     }
     float* vec_mapped(const std::string& name, const ChanMap& m) {
-        const float* src = find(name, {m.real()});
-        if (!src) return nullptr;
-        std::vector<float> v(m.width, 0.f);
-        for (int i = 0; i < m.real(); ++i) v[m.pos[i]] = src[i];
-        return upload(v);
+        const long long o = at(name, {m.real()});
+        if (o < 0) return nullptr;
+        WeightCopy v = dense(o, 1, 1, m.width);
+        v.tab[2] = map_table(m, 1);
+        return f32(v);
     }
     // DoubleConvolution (simple_Unet.py:92-104): ONE GroupNorm module serves both convolutions
     DoubleConvW dconv_mapped(const std::string& p, const ChanMap& mi, const ChanMap& mo, int taps) {
@@ -756,15 +787,16 @@ struct Loader {
     // Linear (out, in) with its output rows padded to out_pad (zero rows, zero bias)
     LinW linear_pad_out(const std::string& wname, const std::string& bname, int out, int in, int out_pad) {
         LinW l;
-        const float* w = find(wname, {out, in});
-        const float* b = find(bname, {out});
-        if (!w || !b) return l;
-        std::vector<float> v((size_t)out_pad * in, 0.f), bv(out_pad, 0.f);
-        memcpy(v.data(), w, sizeof(float) * (size_t)out * in);
-        memcpy(bv.data(), b, sizeof(float) * out);
-        l.w = upload(v);
-        l.ws = (in % 32 == 0) ? upload_split(v, in, wname) : nullptr;
-        l.b = upload(bv);
+        const long long w = at(wname, {out, in});
+        const long long b = at(bname, {out});
+        if (w < 0 || b < 0) return l;
+        WeightCopy v = dense(w, 1, out_pad, in);
+        v.lim[1] = out;
+        l.w = f32(v);
+        l.ws = (in % 32 == 0) ? split(v, in, wname) : nullptr;
+        WeightCopy bv = dense(b, 1, 1, out_pad);
+        bv.lim[2] = out;
+        l.b = f32(bv);
         l.in = in; l.out = out_pad;
         return l;
     }
@@ -804,12 +836,29 @@ struct Loader {
     }
     // (out, in) -> [in][out]: the weights of a Linear layer's data gradient (dx = dy W)
     float* transposed(const std::string& name, int out, int in) {
-        const float* w = find(name, {out, in});
-        if (!w) return nullptr;
-        std::vector<float> t((size_t)in * out);
-        for (int o = 0; o < out; ++o)
-            for (int i = 0; i < in; ++i) t[(size_t)i * out + o] = w[(size_t)o * in + i];
-        return upload(t);
+        const long long o = at(name, {out, in});
+        if (o < 0) return nullptr;
+        WeightCopy t = dense(o, 1, in, out);
+        t.stride[1] = 1; t.stride[2] = in;
+        return f32(t);
+    }
+    // first conv (cout, 1, 3, 3) -> [9][64] (conv_in_kernel's layout; output lanes cout..63 zero)
+    float* conv_in(const std::string& name, int cout) {
+        const long long o = at(name, {cout, 1, 3, 3});
+        if (o < 0) return nullptr;
+        WeightCopy v = dense(o, 1, 9, 64);
+        v.stride[1] = 1; v.stride[2] = 9; v.lim[2] = cout;
+        return f32(v);
+    }
+    // outc: Conv2d(64, 1, 1) with bias -- its bias is a host scalar of the handle (the step kernel's argument)
+    void outc() {
+        h->outc_w = nullptr;
+        const long long w = at("outc.weight", {1, 64, 1, 1});
+        const long long b = at("outc.bias", {1});
+        if (w < 0 || b < 0) return;
+        h->outc_w = f32(dense(w, 1, 1, 64));
+        h->outc_b = blob[b];
+        h->outc_b_off = b;
     }
 };
 
@@ -837,21 +886,13 @@ static int replan_arena(spdm_handle* h) {
 // UNet.state_dict() of models/simple_Unet.py (SPDM_FLAG_SIMPLE_UNET) into channel-padded storage; Loader::err carries failures
 static int load_simple(spdm_handle* h, Loader& L, int t3) {
     const ChanMap c16 = ChanMap::ident(16);
-    {   // input_conv.first (16,1,3,3) -> [9][64] (conv_in_kernel's layout; output lanes 16..63 zero)
-        const float* src = L.find("input_conv.first.weight", {16, 1, 3, 3});
-        if (src) {
-            std::vector<float> v(9 * 64, 0.f);
-            for (int t = 0; t < 9; ++t)
-                for (int o = 0; o < 16; ++o) v[t * 64 + o] = src[o * 9 + t];
-            h->w_inc_first = L.upload(v);
-        }
-    }
+    h->w_inc_first = L.conv_in("input_conv.first.weight", 16);
     h->inc.second = L.conv_mapped("input_conv.second.weight", c16, c16, 9);
     h->inc.gamma = L.vec_mapped("input_conv.norm.weight", c16);
     h->inc.beta = L.vec_mapped("input_conv.norm.bias", c16);
     static const char* names[6] = {"down1", "down2", "down3", "up1", "up2", "up3"};
     const int Kp = h->film_kp, cd = h->cfg.cond_dim, td = h->cfg.time_dim;
-    std::vector<float> cw((size_t)6 * SIMPLE_COND_CH * Kp, 0.f), cb((size_t)6 * SIMPLE_COND_CH, 0.f);
+    std::vector<long long> cw_off(6, -1), cb_off(6, -1);
     for (int k = 0; k < 6; ++k) {
         const std::string p = names[k];
         ResampleW& r = simple_block(h, k);
@@ -861,25 +902,30 @@ static int load_simple(spdm_handle* h, Loader& L, int t3) {
         r.dc2 = L.dconv_mapped(p + ".doubleConv2", in, out, taps);
         r.emb = L.linear_pad_out(p + ".emb_layer.1.weight", p + ".emb_layer.1.bias", out.real(), td, out.width);
         r.cout = out.real();
-        const float* w = L.find(p + ".cond_emb_layer.1.weight", {SIMPLE_COND_CH, cd});
-        const float* b = L.find(p + ".cond_emb_layer.1.bias", {SIMPLE_COND_CH});
-        if (w && b)
-            for (int o = 0; o < SIMPLE_COND_CH; ++o) {
-                memcpy(&cw[((size_t)k * SIMPLE_COND_CH + o) * Kp], w + (size_t)o * cd, sizeof(float) * cd);
-                cb[(size_t)k * SIMPLE_COND_CH + o] = b[o];
-            }
+        cw_off[k] = L.at(p + ".cond_emb_layer.1.weight", {SIMPLE_COND_CH, cd});
+        cb_off[k] = L.at(p + ".cond_emb_layer.1.bias", {SIMPLE_COND_CH});
     }
-    h->cemb.w = L.upload(cw);
-    h->cemb.ws = L.upload_split(cw, Kp, "cond_emb_layer");
-    h->cemb.b = L.upload(cb);
-    h->cemb.in = Kp; h->cemb.out = 6 * SIMPLE_COND_CH;
-    if (h->train_simple) {
-        // d SiLU(cond) = dcemb [B][6 x 32] . W_stacked: the transposed copy [cond_dim padded to 64][6 x 32] (the GEMM's N % 64)
-        const int N = 6 * SIMPLE_COND_CH, kp64 = (int)align_up((size_t)cd, 64);
-        std::vector<float> t((size_t)kp64 * N, 0.f);
-        for (int o = 0; o < N; ++o)
-            for (int i = 0; i < cd; ++i) t[(size_t)i * N + o] = cw[(size_t)o * Kp + i];
-        h->cemb.wt = L.upload(t);
+    if (L.err != SPDM_OK) return L.err;
+    {   // the six cond_emb_layer Linears stacked: w [6 x 32][Kp] (columns beyond cond_dim zero), b [6 x 32]
+        WeightCopy cw = Loader::dense(0, 6, SIMPLE_COND_CH, Kp);
+        cw.tab[0] = L.table(cw_off);
+        cw.stride[1] = cd; cw.lim[2] = cd;
+        WeightCopy cb = Loader::dense(0, 1, 6, SIMPLE_COND_CH);
+        cb.tab[1] = L.table(cb_off);
+        h->cemb.w = L.f32(cw);
+        h->cemb.ws = L.split(cw, Kp, "cond_emb_layer");
+        h->cemb.b = L.f32(cb);
+        h->cemb.in = Kp; h->cemb.out = 6 * SIMPLE_COND_CH;
+        if (h->train_simple) {
+            // d SiLU(cond) = dcemb [B][6 x 32] . W_stacked: the transposed copy [cond_dim padded to 64][6 x 32] (the GEMM's N % 64)
+            WeightCopy t = Loader::dense(0, (int)align_up((size_t)cd, 64), 6, SIMPLE_COND_CH);
+            t.stride[0] = 1; t.lim[0] = cd;
+            t.tab[1] = L.table(cw_off);
+            t.stride[2] = cd;
+            h->cemb.wt = L.f32(t);
+        }
+    }
+    if (h->train_simple && !L.plan) {
         // the channel maps the backward pass gathers through (GroupNorm lanes, weight-gradient write-out)
         auto upload_map = [&](const ChanMap& m) -> int* {
             void* p = nullptr;
@@ -897,17 +943,10 @@ static int load_simple(spdm_handle* h, Loader& L, int t3) {
         }
         if (dev_alloc(h, (void**)&h->d_time_pe, sizeof(float) * (size_t)h->cfg.num_train_timesteps * td) != SPDM_OK) L.err = SPDM_ERR_HIP;
     }
-    {   // outc: Conv2d(64, out, 1) with bias (simple_Unet.py:280); the 64 channels are up3's 32 + 32, unpadded
-        const float* w = L.find("outc.weight", {1, 64, 1, 1});
-        const float* b = L.find("outc.bias", {1});
-        if (w && b) {
-            h->outc_w = L.upload(std::vector<float>(w, w + 64));
-            h->outc_b = b[0];
-        }
-    }
+    L.outc();      // Conv2d(64, out, 1) with bias (simple_Unet.py:280); the 64 channels are up3's 32 + 32, unpadded
     if (L.err != SPDM_OK) return L.err;
     // pos_encoding.pos_encoding (noise_steps + 1, time_dim): the sin/cos-interleaved table of PositionalEncoding (:226-257)
-    // IS the time table of this network
+    // IS the time table of this network (spdm_update_weights does not read this slot)
     auto it = L.idx.find("pos_encoding.pos_encoding");
     if (it == L.idx.end()) return fail(SPDM_ERR_MISSING, "tensor 'pos_encoding.pos_encoding' not in the index");
     const spdm_tensor_index* e = it->second;
@@ -915,9 +954,72 @@ static int load_simple(spdm_handle* h, Loader& L, int t3) {
         return fail(SPDM_ERR_INVALID, "pos_encoding.pos_encoding is (%d, %d): the handle needs (num_train_timesteps = %d, time_dim = %d) "
                     "-- create it with num_train_timesteps equal to the buffer's row count", e->shape[0], e->ndim > 1 ? e->shape[1] : 0,
                     h->cfg.num_train_timesteps, td);
-    const float* pe = L.find("pos_encoding.pos_encoding", {h->cfg.num_train_timesteps, td});
-    if (!pe) return L.err;
-    h->time_table.assign(pe, pe + (size_t)h->cfg.num_train_timesteps * td);
+    const long long pe = L.at("pos_encoding.pos_encoding", {h->cfg.num_train_timesteps, td});
+    if (pe < 0) return L.err;
+    h->time_table.assign(L.blob + pe, L.blob + pe + (size_t)h->cfg.num_train_timesteps * td);
+    return SPDM_OK;
+}
+
+// UNet_Film / UNet_Film_noAttention state_dict
+static int load_film(spdm_handle* h, Loader& L, int t3) {
+    h->w_inc_first = L.conv_in("inc.first.weight", 64);
+    h->inc.second = L.conv("inc.second.weight", 64, 64, 9);
+    h->inc.gamma = L.vec("inc.norm.weight", 64);
+    h->inc.beta = L.vec("inc.norm.bias", 64);
+    h->down[0] = L.resample("down1", 64, 128, 9);
+    h->down[1] = L.resample("down2", 128, 256, 9);
+    h->down[2] = L.resample("down3", 256, 256, t3);
+    h->bot[0] = L.dconv("bot1", 256, 512, t3);
+    h->bot[1] = L.dconv("bot2", 512, 512, t3);
+    h->bot[2] = L.dconv("bot3", 512, 256, t3);
+    h->up[0] = L.resample("up1", 512, 128, 9);
+    h->up[1] = L.resample("up2", 256, 64, 9);
+    h->up[2] = L.resample("up3", 128, 64, 9);
+    if (h->cfg.attention) {
+        static const int sc[6] = {128, 256, 256, 128, 64, 64};
+        for (int i = 0; i < 6; ++i) h->sa[i] = L.attn("sa" + std::to_string(i + 1), sc[i]);
+    }
+    L.outc();
+    return L.err;
+}
+
+// a recorded table on the device, grouped by format in launch order (each format's workgroups numbered from 0): the range
+// checks (WL_RANGE) or the copies (every other format)
+static int upload_copies(spdm_handle* h, const std::vector<WeightCopy>& rec, bool ranges, WeightCopy** d_out) {
+    std::vector<WeightCopy> t;
+    for (int f = ranges ? WL_RANGE : 0; f < (ranges ? WL_RANGE + 1 : WL_RANGE); ++f) {
+        h->wl_first[f] = (int)t.size();
+        long long blk = 0;
+        for (WeightCopy c : rec)
+            if (c.fmt == f) { c.blk0 = blk; blk += weight_copy_blocks(c.count); t.push_back(c); }
+        h->wl_count[f] = (int)t.size() - h->wl_first[f];
+        h->wl_blocks[f] = blk;
+    }
+    if (t.empty()) return SPDM_OK;
+    SPDM_TRY(dev_alloc(h, (void**)d_out, sizeof(WeightCopy) * t.size()));
+    HIP_TRY(hipMemcpy(*d_out, t.data(), sizeof(WeightCopy) * t.size(), hipMemcpyHostToDevice));
+    return SPDM_OK;
+}
+
+// enqueue the range checks of a device blob and read their verdicts back, with outc's bias: one synchronisation
+static int check_ranges(spdm_handle* h, const float* d_blob, hipStream_t s, std::vector<int>* oor, float* outc_b) {
+    const size_t ns = h->wl_slots.size();
+    if (ns) HIP_TRY(hipMemsetAsync(h->d_wl_flags, 0, sizeof(int) * ns, s));
+    HIP_TRY(launch_weight_copies(WL_RANGE, d_blob, h->d_wl_tabs, h->d_wl_range, h->wl_count[WL_RANGE], h->wl_blocks[WL_RANGE],
+                                 h->d_wl_flags, s));
+    HIP_TRY(hipMemcpyAsync(h->d_wl_flags + ns, d_blob + h->outc_b_off, sizeof(float), hipMemcpyDeviceToDevice, s));
+    std::vector<int> back(ns + 1);
+    HIP_TRY(hipMemcpyAsync(back.data(), h->d_wl_flags, sizeof(int) * (ns + 1), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    oor->assign(back.begin(), back.begin() + ns);
+    memcpy(outc_b, &back[ns], sizeof(float));
+    return SPDM_OK;
+}
+
+// enqueue every kernel-layout copy of a device blob into the handle's weight buffers
+static int relayout(spdm_handle* h, const float* d_blob, hipStream_t s) {
+    for (int f = WL_F32; f < WL_RANGE; ++f)
+        HIP_TRY(launch_weight_copies(f, d_blob, h->d_wl_tabs, h->d_wl + h->wl_first[f], h->wl_count[f], h->wl_blocks[f], nullptr, s));
     return SPDM_OK;
 }
 
@@ -935,45 +1037,34 @@ extern "C" int spdm_load_weights(spdm_handle* h, const float* blob, size_t n, co
     }
     // level-3 maps are (Hp/8) x 1: a 3x3 kernel only ever multiplies its centre column there
     const int t3 = (h->Wp >> 3) == 1 ? 3 : 9;
-    if (h->simple) {
-        SPDM_TRY(load_simple(h, L, t3));
-    } else {
-    {   // inc.first (64,1,3,3) -> [9][64]
-        const float* src = L.find("inc.first.weight", {64, 1, 3, 3});
-        if (src) {
-            std::vector<float> v(9 * 64);
-            for (int t = 0; t < 9; ++t)
-                for (int o = 0; o < 64; ++o) v[t * 64 + o] = src[o * 9 + t];
-            h->w_inc_first = L.upload(v);
-        }
+    auto walk = [&]() { return h->simple ? load_simple(h, L, t3) : load_film(h, L, t3); };
+    SPDM_TRY(walk());                      // plan pass: names, shapes, range checks
+    if (h->outc_b_off < 0) return fail(SPDM_ERR_MISSING, "outc.bias not loaded");
+    // the blob on the device, once; the range checks run on it
+    struct DevBlob { float* p = nullptr; ~DevBlob() { if (p) { (void)hipDeviceSynchronize(); (void)hipFree(p); } } } db;
+    HIP_TRY(hipMalloc((void**)&db.p, std::max<size_t>(n, 1) * sizeof(float)));
+    HIP_TRY(hipMemcpy(db.p, blob, n * sizeof(float), hipMemcpyHostToDevice));
+    if (!L.tabs.empty()) {
+        SPDM_TRY(dev_alloc(h, (void**)&h->d_wl_tabs, sizeof(long long) * L.tabs.size()));
+        HIP_TRY(hipMemcpy(h->d_wl_tabs, L.tabs.data(), sizeof(long long) * L.tabs.size(), hipMemcpyHostToDevice));
     }
-    h->inc.second = L.conv("inc.second.weight", 64, 64, 9);
-    h->inc.gamma = L.vec("inc.norm.weight", 64);
-    h->inc.beta = L.vec("inc.norm.bias", 64);
-    h->down[0] = L.resample("down1", 64, 128, 9);
-    h->down[1] = L.resample("down2", 128, 256, 9);
-    h->down[2] = L.resample("down3", 256, 256, t3);
-    h->bot[0] = L.dconv("bot1", 256, 512, t3);
-    h->bot[1] = L.dconv("bot2", 512, 512, t3);
-    h->bot[2] = L.dconv("bot3", 512, 256, t3);
-    h->up[0] = L.resample("up1", 512, 128, 9);
-    h->up[1] = L.resample("up2", 256, 64, 9);
-    h->up[2] = L.resample("up3", 128, 64, 9);
-    if (h->cfg.attention) {
-        static const int sc[6] = {128, 256, 256, 128, 64, 64};
-        for (int i = 0; i < 6; ++i) h->sa[i] = L.attn("sa" + std::to_string(i + 1), sc[i]);
-    }
-    h->outc_w = nullptr;
-    {
-        const float* w = L.find("outc.weight", {1, 64, 1, 1});
-        const float* b = L.find("outc.bias", {1});
-        if (w && b) {
-            h->outc_w = L.upload(std::vector<float>(w, w + 64));
-            h->outc_b = b[0];
-        }
-    }
-    }
-    if (L.err != SPDM_OK) return L.err;
+    h->wl_slots = L.slots;
+    SPDM_TRY(dev_alloc(h, (void**)&h->d_wl_flags, sizeof(int) * (L.slots.size() + 1)));
+    SPDM_TRY(upload_copies(h, L.ranges, true, &h->d_wl_range));
+    float ob = 0.f;
+    SPDM_TRY(check_ranges(h, db.p, nullptr, &L.oor, &ob));
+    // load pass: allocate and record the copies (none of the split ones for a tensor outside the range), then make them
+    const std::vector<long long> plan_tabs = L.tabs;
+    L.tabs.clear();
+    L.plan = false;
+    SPDM_TRY(walk());
+    if (L.tabs != plan_tabs) return fail(SPDM_ERR_INVALID, "weight layout tables differ between the loader's passes");
+    h->wl_oor = L.oor;
+    h->wl_copies = L.copies;
+    SPDM_TRY(upload_copies(h, L.copies, false, &h->d_wl));
+    SPDM_TRY(relayout(h, db.p, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    h->blob_floats = n;
     if (h->train) {
         h->grad_off.clear();
         h->grad_floats = n;
@@ -991,6 +1082,64 @@ extern "C" int spdm_load_weights(spdm_handle* h, const float* blob, size_t n, co
         // weights known and grow the slab if this plan needs more.
         SPDM_TRY(replan_arena(h));
     }
+    return SPDM_OK;
+}
+
+extern "C" int spdm_update_weights(spdm_handle* h, const float* d_blob, size_t n, void* stream) {
+    if (!h || !d_blob) return fail(SPDM_ERR_INVALID, "null argument");
+    if (!h->weights_loaded) return fail(SPDM_ERR_STATE, "spdm_load_weights has not been called");
+    if (n != h->blob_floats) return fail(SPDM_ERR_INVALID, "blob has %zu floats; the loaded one had %zu", n, h->blob_floats);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> oor;
+    float ob = 0.f;
+    SPDM_TRY(check_ranges(h, d_blob, s, &oor, &ob));
+    for (size_t i = 0; i < oor.size(); ++i)
+        if ((oor[i] != 0) != (h->wl_oor[i] != 0))
+            return fail(SPDM_ERR_STATE, "tensor '%s' %s the split format's range (|w| < 511): the workspace plan follows the set of "
+                        "such tensors -- load these weights into a new handle", h->wl_slots[i].c_str(), oor[i] ? "left" : "came back into");
+    SPDM_TRY(relayout(h, d_blob, s));
+    h->temb_ready = false;                 // the time-embedding tables and a session's FiLM / cond_emb projections are
+    h->session = false;                    // functions of the old weights
+    uint32_t a, b;
+    memcpy(&a, &ob, 4);
+    memcpy(&b, &h->outc_b, 4);
+    if (a != b) {
+        // outc's bias is an argument the captured step graph baked in (StepArgs::bias, SaCrop::outc_b): capture again next time
+        h->outc_b = ob;
+        if (h->step_exec || h->step_graph) {
+            HIP_TRY(hipDeviceSynchronize());
+            if (h->step_exec) (void)hipGraphExecDestroy(h->step_exec);
+            if (h->step_graph) (void)hipGraphDestroy(h->step_graph);
+            h->step_exec = nullptr;
+            h->step_graph = nullptr;
+        }
+    }
+    return SPDM_OK;
+}
+
+extern "C" int spdm_debug_weight_digest(const spdm_handle* h, uint64_t* out) {
+    if (!h || !out) return fail(SPDM_ERR_INVALID, "null argument");
+    if (!h->weights_loaded) return fail(SPDM_ERR_STATE, "spdm_load_weights has not been called");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(hipDeviceSynchronize());
+    uint64_t x = 1469598103934665603ull;          // FNV-1a over 64-bit words
+    auto mix = [&](const void* p, size_t bytes) {
+        const unsigned char* c = (const unsigned char*)p;
+        size_t i = 0;
+        for (; i + 8 <= bytes; i += 8) { uint64_t w; memcpy(&w, c + i, 8); x = (x ^ w) * 1099511628211ull; }
+        for (; i < bytes; ++i) x = (x ^ c[i]) * 1099511628211ull;
+    };
+    std::vector<unsigned char> buf;
+    for (const WeightCopy& c : h->wl_copies) {
+        buf.resize((size_t)c.count * sizeof(float));
+        HIP_TRY(hipMemcpy(buf.data(), c.dst, buf.size(), hipMemcpyDeviceToHost));
+        mix(buf.data(), buf.size());
+    }
+    mix(&h->outc_b, sizeof(float));
+    for (size_t i = 0; i < h->wl_slots.size(); ++i)
+        if (h->wl_oor[i]) mix(h->wl_slots[i].data(), h->wl_slots[i].size() + 1);
+    *out = x;
     return SPDM_OK;
 }
 
@@ -2655,6 +2804,39 @@ extern "C" int spdm_profile_read(spdm_handle* h, int64_t* launches, double* tota
     return SPDM_OK;
 }
 
+// ---- host copies of two weight layouts, for the standalone GEMM entry points below (spdm_bench_gemm, spdm_op_gemm); a
+// handle's weights are laid out on the device (Loader, weight_layout.hip) ----
+// fp32 [rows][K] -> per 32-k chunk [32 x fp16 hi | 32 x fp16 lo] of x' = 128 x: hi = fp16(x'), lo = fp16(x' - hi)
+static std::vector<float> host_split_format(const std::vector<float>& v) {
+    std::vector<float> out(v.size());
+    for (size_t base = 0; base < v.size(); base += 32) {
+        _Float16* hp = reinterpret_cast<_Float16*>(&out[base]);
+        for (int j = 0; j < 32; ++j) {
+            const float x = v[base + j] * 128.0f;
+            const _Float16 hi = (_Float16)x;
+            hp[j] = hi;
+            hp[32 + j] = (_Float16)(x - (float)hi);
+        }
+    }
+    return out;
+}
+static bool host_split_range_ok(const std::vector<float>& v) {
+    float mx = 0.f;
+    for (float x : v) { const float ax = std::fabs(x); if (!(ax <= mx)) mx = ax; }
+    return mx < 511.0f;
+}
+// (Cout,Cin,3,3) -> [taps][Cout][Cin]; taps == 3 keeps only the centre column
+static std::vector<float> host_conv_taps(const float* src, int cout, int cin, int taps) {
+    std::vector<float> v((size_t)taps * cout * cin);
+    for (int t = 0; t < taps; ++t) {
+        const int kh = (taps == 9) ? t / 3 : t, kw = (taps == 9) ? t % 3 : 1;
+        for (int o = 0; o < cout; ++o)
+            for (int i = 0; i < cin; ++i)
+                v[((size_t)t * cout + o) * cin + i] = src[(((size_t)o * cin + i) * 3 + kh) * 3 + kw];
+    }
+    return v;
+}
+
 // -------------------------------------------------------------------------------------------------
 // Micro-benchmark of one implicit-GEMM launch shape on synthetic data (tools/bench_gemm.py); not on
 // the product path.  Returns the average device time per launch in *ms_out (HIP events).
@@ -2693,7 +2875,7 @@ extern "C" int spdm_bench_gemm(int32_t device, int32_t B, int32_t H, int32_t W, 
         for (auto& v : hres) v = rnd();           // a non-zero residual: EPI_BIAS_RESID adds something
         HIP_TRY(hipMemcpy(wgt32, hw.data(), nw * 4, hipMemcpyHostToDevice));
         if (split) {
-            hw = Loader::split_format(hw);
+            hw = host_split_format(hw);
             if ((taps == 9 || taps == 3) && Cout % 64 == 0 && Cin % 32 == 0) {
                 const std::vector<float> fr = frag_order_weights(hw, taps, Cout, Cin);
                 HIP_TRY(hipMalloc((void**)&wfrag, nw * 4));
@@ -2834,8 +3016,9 @@ extern "C" int spdm_encoder_create(int32_t device, const float* blob, size_t n, 
     spdm_encoder* e = new spdm_encoder();
     e->device = device;
     for (const Item& it : items) {
-        const float* src = L.find(it.name, it.shape);
-        if (!src) { spdm_encoder_destroy(e); return L.err; }
+        const long long off = L.at(it.name, it.shape);
+        if (off < 0) { spdm_encoder_destroy(e); return L.err; }
+        const float* src = blob + off;
         size_t numel = 1;
         for (int d : it.shape) numel *= (size_t)d;
         void* p = nullptr;
@@ -2930,8 +3113,8 @@ extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {
     const int src_rows = q.pro == PRO_POOL ? 4 * HW : q.pro == PRO_UPCAT ? HW / 4 : HW;      // rows per sample of src
     if (q.pro == PRO_UPCAT && ((q.H & 1) || (q.W & 1))) return fail(SPDM_ERR_INVALID, "op_gemm: upsample read-through needs an even map");
     const std::vector<float> w32 = q.taps == 1 ? std::vector<float>(q.h_weight, q.h_weight + (size_t)q.N * q.K)
-                                               : Loader::conv_taps(q.h_weight, q.N, q.K, q.taps);
-    if (q.split && !Loader::split_range_ok(w32)) return fail(SPDM_ERR_INVALID, "op_gemm: weights outside the split format's range (the loader keeps such a layer on the exact path)");
+                                               : host_conv_taps(q.h_weight, q.N, q.K, q.taps);
+    if (q.split && !host_split_range_ok(w32)) return fail(SPDM_ERR_INVALID, "op_gemm: weights outside the split format's range (the loader keeps such a layer on the exact path)");
     const unsigned sw = switches_from_env();
     const int split = q.split ? 1 : 0;
     // as the plan: a split-precision convolution may split K unless switched off (the handle then holds no partial buffer)
@@ -2956,9 +3139,9 @@ extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {
     void* dwf = nullptr;
     void* dp = nullptr;
     if (split) {
-        const std::vector<float> ws = Loader::split_format(w32);
+        const std::vector<float> ws = host_split_format(w32);
         e = upload(ws.data(), ws.size() * 4, &dw);
-        if (e == hipSuccess && q.taps != 1) {       // Loader::conv's fragment-order copy (Cout % 64 == 0 here)
+        if (e == hipSuccess && q.taps != 1) {       // the loader's fragment-order copy (Cout % 64 == 0 here)
             const std::vector<float> wf = frag_order_weights(ws, q.taps, q.N, q.K);
             e = upload(wf.data(), wf.size() * 4, &dwf);
         }

@@ -32,11 +32,13 @@ from __future__ import annotations
 
 from typing import Callable, Dict, List, Optional
 
+import numpy as np
+
 import torch
 
 from .engine import SpdmEngine
 from .schedulers import DDIMScheduler, DDPMScheduler, _LinearBetaScheduler
-from .weights import is_simple_model, random_state_dict, state_dict_to_numpy
+from .weights import is_simple_model, pack_state_dict, random_state_dict, state_dict_to_numpy
 
 
 def _as_spec(sched) -> _LinearBetaScheduler:
@@ -61,26 +63,85 @@ def _as_spec(sched) -> _LinearBetaScheduler:
     raise TypeError(f"unsupported scheduler class {name} (DDPM / DDIM only)")
 
 
+def _index_of(idx):
+    """The layout of a packed state_dict (weights.pack_state_dict): [(name, offset, shape)]."""
+    return [(e.name.decode(), int(e.offset), tuple(e.shape[d] for d in range(e.ndim))) for e in idx]
+
+
 class NoiseEstimator:
     """``self.noise_estimator`` of the reference (``UNet_Film(...)`` built at
     models/diffusion_ddpm.py:76-82): holds the weights; calling it evaluates the HIP U-Net."""
 
     def __init__(self, owner: "Diffusion_DDPM", state_dict):
         self._owner = owner
-        self._sd = state_dict_to_numpy(state_dict)
+        self._host_sd = state_dict_to_numpy(state_dict)
+        self._flat: Optional[torch.nn.Parameter] = None     # flat_parameter(): the packed state_dict on the device
+        self._flat_index = None                             # ... its layout [(name, offset, shape)]
+        self._flat_version = 0                              # ... its torch version when _host_sd last matched it
 
         self._grads: Optional[Dict[str, torch.Tensor]] = None
         self.grad_cond: Optional[torch.Tensor] = None
 
+    @property
+    def _sd(self) -> Dict[str, np.ndarray]:
+        """The host copy of the weights, brought up to date from ``flat_parameter()`` when an optimiser changed it."""
+        if self._flat is not None and self._flat._version != self._flat_version:
+            host = self._flat.detach().cpu().numpy()
+            sd = {}
+            for name, off, shape in self._flat_index:
+                n = int(np.prod(shape)) if shape else 1
+                sd[name] = host[off:off + n].reshape(shape).copy()
+            self._host_sd = sd
+            self._flat_version = self._flat._version
+        return self._host_sd
+
     def state_dict(self):
         return {k: torch.from_numpy(v) for k, v in self._sd.items()}
 
+    def _engines(self):
+        return [e for e in (self._owner._engine, self._owner._train_engine) if e is not None]
+
     def load_state_dict(self, state_dict) -> None:
-        """Replace the weights (e.g. after an optimiser step) and push them into every engine the owner has cached: the
-        training engine is refreshed in place (SpdmEngine.refresh_weights); the sampling engine is too, when present."""
-        self._sd = state_dict_to_numpy(state_dict)
-        for eng in (self._owner._engine, self._owner._train_engine):
-            if eng is not None:
+        """Replace the weights (e.g. after an optimiser step) and push them into every engine the owner has cached: packed
+        and uploaded once, then put into each engine in place (SpdmEngine.update_weights); an engine whose packed layout
+        differs is rebuilt (SpdmEngine.refresh_weights).  ``flat_parameter()``, if created, takes the new values."""
+        self._host_sd = state_dict_to_numpy(state_dict)
+        blob, idx = pack_state_dict(self._host_sd)
+        index = _index_of(idx)
+        dev = None
+        for eng in self._engines():
+            if eng._index == index:
+                if dev is None:
+                    dev = torch.from_numpy(blob).to(eng.device)
+                eng.update_weights(dev)
+            else:
+                eng.refresh_weights(self._host_sd)
+        if self._flat is not None:
+            if index == self._flat_index:
+                with torch.no_grad():
+                    self._flat.copy_(torch.from_numpy(blob).to(self._flat.device))
+                self._flat_version = self._flat._version
+            else:
+                self._flat = None
+
+    def flat_parameter(self) -> torch.nn.Parameter:
+        """The weights as ONE device parameter in the packed state_dict layout (``SpdmEngine.pack_weights``), created on
+        first use; the optimiser of ``Diffusion_DDPM.configure_optimizers`` steps it.  After
+        ``training_step(backward=True)`` its ``.grad`` is the flat gradient, and ``grads()`` are views of that storage."""
+        if self._flat is None:
+            blob, idx = pack_state_dict(self._host_sd)
+            self._flat = torch.nn.Parameter(torch.from_numpy(blob).to(self._owner.device))
+            self._flat_index = _index_of(idx)
+            self._flat_version = self._flat._version
+        return self._flat
+
+    def _push(self) -> None:
+        """Put ``flat_parameter()``'s values into every cached engine (in place where the layout matches)."""
+        flat = self._flat.detach()
+        for eng in self._engines():
+            if eng._index == self._flat_index:
+                eng.update_weights(flat)
+            else:
                 eng.refresh_weights(self._sd)
 
     def grads(self) -> Dict[str, torch.Tensor]:
@@ -397,7 +458,16 @@ class Diffusion_DDPM:
         x_noisy = self.add_constraints(x_noisy, x_0_inpaint)
         if backward:
             eng = self._train_engine_for(B, x_noisy.shape[-2], x_noisy.shape[-1])
-            loss, noise_estimated, grads, grad_cond = eng.loss_and_grad(x_noisy, t, obs_cond, noise, time_scale=time_scale)
+            loss, noise_estimated, g, grad_cond = eng.loss_and_grad(x_noisy, t, obs_cond, noise, flat=True, time_scale=time_scale)
+            grads = {}
+            for name, off, shape in eng._index:
+                if self.simple and name == "pos_encoding.pos_encoding":      # a buffer, not a parameter
+                    continue
+                n = int(np.prod(shape)) if shape else 1
+                grads[name] = g[off:off + n].view(shape)
+            ne = self.noise_estimator
+            if ne._flat is not None and ne._flat_index == eng._index:
+                ne._flat.grad = g                 # loss.backward(): the flat gradient, the same storage as grads()
             self.noise_estimator._grads = grads
             self.noise_estimator.grad_cond = grad_cond
             return (loss, noise_estimated, x_noisy) if return_parts else loss
@@ -407,6 +477,32 @@ class Diffusion_DDPM:
 
     def validation_step(self, batch, batch_idx: int = 0, **kw):
         return self.training_step(batch, batch_idx, **kw)
+
+    # ==================== Optimisation (models/diffusion_ddpm.py:114-124, train.py) ====================
+    def configure_optimizers(self):
+        """The reference's optimiser: Adam(lr) over the weights -- here the one flat device parameter
+        (``noise_estimator.flat_parameter()``) -- and ReduceLROnPlateau('min', patience=5) on ``val_loss``, in
+        Lightning's dict shape."""
+        optimizer = torch.optim.Adam([self.noise_estimator.flat_parameter()], lr=self.lr)
+        scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, "min", patience=5)
+        return {
+            "optimizer": optimizer,
+            "lr_scheduler": {
+                "scheduler": scheduler,
+                "monitor": "val_loss",
+                "frequency": 1
+            },
+        }
+
+    def optimizer_step(self, optimizer, gradient_clip_val: Optional[float] = 0.5) -> None:
+        """One optimiser step after ``training_step(backward=True)``: clip the global gradient norm (Lightning's
+        ``gradient_clip_val``, 0.5 in train.py), ``optimizer.step()``, then put the new weights into every cached engine
+        in place (``SpdmEngine.update_weights``) -- no host round trip of the weights."""
+        p = self.noise_estimator.flat_parameter()
+        if gradient_clip_val:
+            torch.nn.utils.clip_grad_norm_([p], gradient_clip_val)
+        optimizer.step()
+        self.noise_estimator._push()
 
 
 class Diffusion_DDIM(Diffusion_DDPM):

@@ -84,6 +84,7 @@ class SpdmEngine:
         self._weights_loaded = False
         self._sched = None
         self._switches = {}
+        self._rebuilds = 0
 
     def _create(self) -> None:
         h = ctypes.c_void_p()
@@ -200,6 +201,56 @@ class SpdmEngine:
         self._weights_loaded = True
         self._index = [(e.name.decode(), int(e.offset), tuple(e.shape[d] for d in range(e.ndim))) for e in idx]
         self._blob_floats = int(blob.size)
+
+    def pack_weights(self, sd) -> torch.Tensor:
+        """state_dict -> one flat fp32 tensor on the engine's device laid out as the loaded blob (the layout of
+        ``update_weights`` and ``loss_and_grad(flat=True)``).  Raises ValueError if the names, shapes or offsets differ
+        from the loaded index."""
+        if not self._weights_loaded:
+            raise RuntimeError("load_state_dict first")
+        blob, idx = pack_state_dict(sd)
+        index = [(e.name.decode(), int(e.offset), tuple(e.shape[d] for d in range(e.ndim))) for e in idx]
+        if index != self._index or int(blob.size) != self._blob_floats:
+            raise ValueError("state_dict does not pack into the loaded blob's layout (names, shapes or offsets differ)")
+        return torch.from_numpy(blob).to(self.device)
+
+    def unpack_weights(self, flat: torch.Tensor) -> dict:
+        """The inverse of ``pack_weights``: name -> host numpy array (a copy)."""
+        host = flat.detach().to("cpu", torch.float32).numpy()
+        out = {}
+        for name, off, shape in self._index:
+            n = int(np.prod(shape)) if shape else 1
+            out[name] = host[off:off + n].reshape(shape).copy()
+        return out
+
+    def update_weights(self, flat: torch.Tensor) -> None:
+        """Put updated weights (an optimiser step) into this engine in place: ``flat`` is a contiguous fp32 tensor on the
+        engine's device in the packed layout (``pack_weights``).  The re-layout runs on the current stream; ``flat`` must
+        stay unchanged until that stream has passed it.  If the set of tensors outside the split format's range
+        (``demoted_tensors``) would change, the handle is rebuilt from a host copy instead (``refresh_weights``;
+        counted by ``weight_rebuilds``)."""
+        if not self._weights_loaded:
+            raise RuntimeError("load_state_dict first")
+        if (flat.device != self.device or flat.dtype != torch.float32 or not flat.is_contiguous()
+                or flat.numel() != self._blob_floats):
+            raise ValueError(f"update_weights needs a contiguous fp32 tensor of {self._blob_floats} floats on {self.device}")
+        rc = self.lib.spdm_update_weights(self._h, _ptr(flat), flat.numel(), self._stream())
+        if rc == _lib.SPDM_ERR_STATE:          # the range set changed: the workspace plan depends on it
+            self.refresh_weights(self.unpack_weights(flat))
+            self._rebuilds += 1
+            return
+        _lib.check(rc, "spdm_update_weights")
+
+    @property
+    def weight_rebuilds(self) -> int:
+        """``update_weights`` calls that had to rebuild the handle (a tensor entered or left the split format's range)."""
+        return self._rebuilds
+
+    def weight_digest(self) -> int:
+        """Hash of every device weight copy, outc's bias and the demotion set (test hook; synchronises the device)."""
+        d = ctypes.c_uint64(0)
+        _lib.check(self.lib.spdm_debug_weight_digest(self._h, ctypes.byref(d)), "spdm_debug_weight_digest")
+        return int(d.value)
 
     def set_scheduler(self, sched) -> None:
         """Install the tables of a host scheduler object (schedulers.py) for the loop."""
