@@ -136,7 +136,7 @@ __global__ __launch_bounds__(R_NTHR, 1) void conv_reg64_kernel(const GemmArgs a,
     R_LOAD_RAW(min(wt_first, n_wt - 1), 0)          // (the first tile's rows fly under the weight staging)
 
     // ---- weights -> LDS, once: block ((tap 2 + ks) 4 + nb') x {hi, lo}, lane (kg, l16) <- row n = 4 l16 + nb' of the fragment-order
-    //      copy (frag_order_weights, kernels.h: block ((tap 2 + ks) 4 + n / 16) x {hi, lo}, lane (kg, n % 16)) ----
+    //      copy (WL_FRAG, weight_layout.hip: block ((tap 2 + ks) 4 + n / 16) x {hi, lo}, lane (kg, n % 16)) ----
     {
         // (all 18 loads of a thread in flight before the first LDS write: the weights are cold in L2 inside a real step, and a
         //  load -> store loop is 18 dependent round trips -- measured +5 us per launch against the warm micro-benchmark)

@@ -13,7 +13,7 @@
 //   * the input slab of ALL chunks (rows + halo, every 32-channel chunk, prologue applied once) is staged in LDS up
 //     front -- it is tiny (<= 87 KB);
 //   * the 8 waves split K: wave w takes the (chunk, tap) items i = w, w + 8, ... and streams their weight fragments
-//     straight from global memory in fragment order (frag_order_weights, kernels.h), one item ahead; every wave
+//     straight from global memory in fragment order (WL_FRAG, weight_layout.hip), one item ahead; every wave
 //     accumulates the whole tile;
 //   * the 8 partial tiles are added through LDS in the fixed order w = 0..7 (deterministic, no atomics) and the epilogue --
 //     output rows, per-sample fp64 GroupNorm partial sums -- runs in the same kernel: no partial slabs in HBM, no combine

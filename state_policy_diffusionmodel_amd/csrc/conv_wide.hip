@@ -14,7 +14,7 @@
 //     strip (8 x 4 or 8 x 2 tiles of 16 x 16 = 128 / 64 accumulator registers); <= 256 registers and <= 77 KiB of
 //     LDS, so two workgroups share a CU;
 //   * the WEIGHT fragments never touch LDS: the host stores a fragment-order copy of the split weights
-//     (frag_order_weights, kernels.h: one 1-KiB block per MFMA B operand, lane-contiguous) and each wave loads its B
+//     (WL_FRAG, weight_layout.hip: one 1-KiB block per MFMA B operand, lane-contiguous) and each wave loads its B
 //     operands straight into registers with coalesced global_load_dwordx4, one phase (48 MFMAs) ahead.  The waves of
 //     a workgroup then only meet at the slab hand-over -- one barrier pair per 32-channel chunk instead of one
 //     barrier per tap -- and the MFMA stream of a chunk is unbroken;

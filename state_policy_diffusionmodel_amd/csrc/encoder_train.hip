@@ -304,13 +304,6 @@ __global__ __launch_bounds__(256) void enc_conv1_wgrad_kernel(const float* __res
 }
 
 // dst[c][r] = src[r][c]
-__global__ void enc_transpose_kernel(const float* __restrict__ src, int R, int C, float* __restrict__ dst) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)R * C) return;
-    const int c = (int)(i / R), r = (int)(i - (size_t)c * R);
-    dst[i] = src[(size_t)r * C + c];
-}
-
 __global__ void enc_add_kernel(const float* __restrict__ src, size_t n, float* __restrict__ dst) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] += src[i];
@@ -371,12 +364,6 @@ hipError_t launch_encoder_conv1_wgrad(const float* img, const float* dx2, const 
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     if (hipError_t e = launch_colsum(part, ENC_W1_LD, nblk, E_C1 * 12, dw, s); e != hipSuccess) return e;
     return launch_colsum(part + E_C1 * 12, ENC_W1_LD, nblk, E_C1, db, s);
-}
-
-hipError_t launch_transpose(const float* src, int R, int C, float* dst, hipStream_t s) {
-    if (R <= 0 || C <= 0 || !src || !dst) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(enc_transpose_kernel, dim3(blocks_of((size_t)R * C, 256)), dim3(256), 0, s, src, R, C, dst);
-    return hipGetLastError();
 }
 
 hipError_t launch_add(const float* src, size_t n, float* dst, hipStream_t s) {

@@ -95,7 +95,7 @@ struct GemmArgs {
     const float* src;  int src_ld;     // [M][src_ld], K valid channels
     const float* wgt;                  // [taps][N][K]  (k contiguous); split: per 32-k chunk [32 fp16 hi | 32 fp16 lo]
     int split;                         // 0: fp32 MFMA (exact); 1: split-fp16 MFMA (wgt in the split format)
-    const float* wgt_frag;             // optional: fragment-order copy of the split weights (frag_order_weights) -> conv_wide.hip
+    const float* wgt_frag;             // optional: fragment-order copy of the split weights (WL_FRAG, weight_layout.hip) -> conv_wide.hip
     float* dst;        int dst_ld;
     int M, K, N;
     int geom_M;                        // > 0: choose tiles / split-K / kernel as for THIS many rows (SW_PIN_GEOMETRY: a shard of a larger batch
@@ -170,26 +170,6 @@ double gemm_flops(const GemmArgs& a);
 bool conv_wide_supported(const GemmArgs& a, const GemmGeom& g);
 hipError_t launch_conv_wide(const GemmArgs& a, const GemmGeom& g, hipStream_t s);
 
-// Fragment-order copy of split-format weights [taps][N][K] for conv_wide.hip (v_mfma_f32_16x16x32_f16 B operands):
-//   block ((tap K/32 + chunk) N/16 + nb16) x {hi, lo} of 1 KiB; lane (kg 16 + l16) -> 16 bytes = 8 fp16 of row
-//   nb16 16 + l16, k = chunk 32 + kg 8 .. -- so a wave's operand load is one coalesced global_load_dwordx4.
-//   Same bytes as the split array, permuted.  (N % 16 == 0, K % 32 == 0.)
-inline std::vector<float> frag_order_weights(const std::vector<float>& split, int taps, int N, int K) {
-    std::vector<float> out(split.size());
-    const int nch = K / 32, nbn = N / 16;
-    for (int t = 0; t < taps; ++t)
-        for (int c = 0; c < nch; ++c)
-            for (int nb = 0; nb < nbn; ++nb)
-                for (int part = 0; part < 2; ++part)
-                    for (int kg = 0; kg < 4; ++kg)
-                        for (int l16 = 0; l16 < 16; ++l16) {
-                            const size_t dst = ((((size_t)(t * nch + c) * nbn + nb) * 2 + part) * 64 + kg * 16 + l16) * 4;
-                            const size_t src = ((size_t)t * N + nb * 16 + l16) * K + c * 32 + part * 16 + kg * 4;
-                            for (int j = 0; j < 4; ++j) out[dst + j] = split[src + j];
-                        }
-    return out;
-}
-
 // ---- streaming / small kernels (elementwise.hip) -------------------------------------------
 // first conv, Cin = 1, fused zero-padding of the (H0, D) trajectory to (Hp, Wp)
 // ... and, as the first kernel of a denoise step, the loop bookkeeping (adv: -2 none, -1 advance by one, >= 0 set the step)
@@ -250,7 +230,6 @@ hipError_t launch_encoder_dz2(const float* dx3, const float* x3, int n_images, f
 int encoder_conv1_wgrad_blocks(int n_images);
 hipError_t launch_encoder_conv1_wgrad(const float* img, const float* dx2, const float* x2, int n_images, float* part,
                                       float* dw, float* db, hipStream_t s);
-hipError_t launch_transpose(const float* src, int R, int C, float* dst, hipStream_t s);     // dst[c][r] = src[r][c]
 hipError_t launch_add(const float* src, size_t n, float* dst, hipStream_t s);               // dst += src
 // plain GN apply (materialise): y = GN(x)
 hipError_t launch_gn_apply(const AffineSrc& src, float* dst, int B, int HW, hipStream_t s);
@@ -401,13 +380,13 @@ hipError_t launch_sa_head(int C, const float* x, float* att, int rows, const flo
 hipError_t launch_sa_qkv(int C, const float* x, float* qkv, int rows, const float* wf_in, const float* b_in, const float* ln_g,
                          const float* ln_b, const float* ab, int L, hipStream_t s, const FilmSpec* fs = nullptr);
 
-// ---- weight re-layout on the device (weight_layout.hip; spdm_api.hip records the copies as it loads) ----------------------
+// ---- weight re-layout on the device (weight_layout.hip; spdm_api.hip's Recorder records the copies) ----------------------
 // One kernel-layout copy of a weight as a gather from the torch-layout blob: logical dense array [n0][n1][n2], element
 // (i0, i1, i2) = blob[src + sum_k contrib_k] where axis k contributes i_k * stride[k] (zero when i_k >= lim[k]) or, tab[k] >= 0,
 // tabs[tab[k] + i_k] (zero when that entry is -1).  fmt says how the logical elements become the destination:
 //   WL_F32      the logical array itself (bit copy)
 //   WL_SPLIT    split format of it: per 32-element chunk 32 fp16 hi | 32 fp16 lo of 128 w (same byte size)
-//   WL_FRAG     frag_order_weights(split, taps, N, K) of it ([taps][N][K])
+//   WL_FRAG     the fragment-order copy of that split array, read as [taps][N][K] (layout: weight_layout.hip)
 //   WL_PERM_HI / _LO   the hi / lo fp16 halves of a [out][64] matrix in sa_fused.hip's fragment order (half the bytes)
 //   WL_RANGE    no destination: flags[slot] = 1 when an element is outside the split format's range, !(|w| < 511)
 enum { WL_F32 = 0, WL_SPLIT, WL_FRAG, WL_PERM_HI, WL_PERM_LO, WL_RANGE, WL_NFMT };

@@ -12,7 +12,7 @@
 //     32 rows x 256 channels -- same slab bytes, same registers per thread, same tile per wave in both shapes;
 //   * the A operand of each product is a 64-row x 128-channel slab in LDS (conv_wide's row format: per 32-channel
 //     chunk [32 x fp16 hi | 32 x fp16 lo], rows padded to 144 bytes); weights come straight from global memory in
-//     fragment order (frag_order_weights, taps = 1), one 32-channel chunk ahead, also across the three products;
+//     fragment order (WL_FRAG, weight_layout.hip, taps = 1), one 32-channel chunk ahead, also across the three products;
 //   * between products the accumulators go through LDS once (the dead slab's space) and are picked up ROW-WISE --
 //     thread (row 8 i + tid / 32, columns 4 (tid % 32) ..) for i = 0..7, the same assignment the loader uses -- so
 //     bias, residual, LayerNorm (two-pass over the 128 values of a row: a half-wave holds one row), GELU and the fp16

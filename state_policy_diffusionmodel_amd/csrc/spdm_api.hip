@@ -130,6 +130,96 @@ struct AttnW {
     float* qkv_wf = nullptr;                           // ... and of in_proj
 };
 
+// -------------------------------------------------------------------------------------------------
+// The device weight-copy table (weight_layout.hip): the recorded copies (a Recorder, below, fills it in), the split format's
+// range checks and the copies' offset tables, their device mirrors and every device allocation made for them, the copies'
+// destinations included.  A spdm_handle and a spdm_encoder hold one each; the standalone GEMM entry points build a temporary one.
+struct WeightTable {
+    std::vector<WeightCopy> copies;       // every copy, in the order it was recorded (spdm_debug_weight_digest)
+    std::vector<WeightCopy> ranges;       // the split format's range checks (WL_RANGE)
+    std::vector<long long> tabs;          // offset tables of the copies' table axes
+    std::vector<std::string> slots;       // tensor name of each range slot
+    std::vector<int> oor;                 // ... outside the range at load (those tensors have no split copies)
+    long long scalar_off = -1;            // >= 0: one blob float read back with the verdicts (outc's bias)
+    WeightCopy* d_copies = nullptr;       // the copies on the device, grouped by format
+    WeightCopy* d_ranges = nullptr;
+    int first[WL_NFMT] = {}, count[WL_NFMT] = {};
+    long long blocks[WL_NFMT] = {};       // per format: first entry, entries and workgroups of its launch
+    long long* d_tabs = nullptr;
+    int* d_flags = nullptr;               // [slots] range verdicts + the scalar (bits), read back together
+    std::vector<void*> owned;             // every hipMalloc to free
+    size_t bytes = 0;
+    WeightTable() = default;
+    WeightTable(const WeightTable&) = delete;
+    WeightTable& operator=(const WeightTable&) = delete;
+    ~WeightTable() { clear(); }
+    void clear() {                        // back to an empty table
+        for (void* p : owned) (void)hipFree(p);
+        owned.clear(); copies.clear(); ranges.clear(); tabs.clear(); slots.clear(); oor.clear();
+        d_copies = d_ranges = nullptr; d_tabs = nullptr; d_flags = nullptr;
+        scalar_off = -1; bytes = 0;
+    }
+    int alloc(void** p, size_t n) {
+        HIP_TRY(hipMalloc(p, std::max<size_t>(n, 256)));
+        owned.push_back(*p);
+        bytes += n;
+        return SPDM_OK;
+    }
+    // the recorded range checks (rng) or copies on the device, grouped by format in launch order (each format's workgroups
+    // numbered from 0).  Called again when more copies have been recorded; the earlier mirror stays owned.
+    int upload(bool rng) {
+        if (!d_tabs && !tabs.empty()) {
+            SPDM_TRY(alloc((void**)&d_tabs, sizeof(long long) * tabs.size()));
+            HIP_TRY(hipMemcpy(d_tabs, tabs.data(), sizeof(long long) * tabs.size(), hipMemcpyHostToDevice));
+        }
+        if (rng) SPDM_TRY(alloc((void**)&d_flags, sizeof(int) * (slots.size() + 1)));
+        std::vector<WeightCopy> t;
+        for (int f = rng ? WL_RANGE : 0; f < (rng ? WL_RANGE + 1 : WL_RANGE); ++f) {
+            first[f] = (int)t.size();
+            long long blk = 0;
+            for (WeightCopy c : rng ? ranges : copies)
+                if (c.fmt == f) { c.blk0 = blk; blk += weight_copy_blocks(c.count); t.push_back(c); }
+            count[f] = (int)t.size() - first[f];
+            blocks[f] = blk;
+        }
+        if (t.empty()) return SPDM_OK;
+        WeightCopy** d = rng ? &d_ranges : &d_copies;
+        SPDM_TRY(alloc((void**)d, sizeof(WeightCopy) * t.size()));
+        HIP_TRY(hipMemcpy(*d, t.data(), sizeof(WeightCopy) * t.size(), hipMemcpyHostToDevice));
+        return SPDM_OK;
+    }
+    // enqueue the range checks of a device blob and read their verdicts back, with the scalar: one synchronisation
+    int check_ranges(const float* d_blob, hipStream_t s, std::vector<int>* verdicts, float* scalar = nullptr) {
+        const size_t ns = slots.size();
+        if (ns) HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(int) * ns, s));
+        HIP_TRY(launch_weight_copies(WL_RANGE, d_blob, d_tabs, d_ranges, count[WL_RANGE], blocks[WL_RANGE], d_flags, s));
+        if (scalar_off >= 0) HIP_TRY(hipMemcpyAsync(d_flags + ns, d_blob + scalar_off, sizeof(float), hipMemcpyDeviceToDevice, s));
+        std::vector<int> back(ns + 1);
+        HIP_TRY(hipMemcpyAsync(back.data(), d_flags, sizeof(int) * (ns + 1), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        verdicts->assign(back.begin(), back.begin() + ns);
+        if (scalar) memcpy(scalar, &back[ns], sizeof(float));
+        return SPDM_OK;
+    }
+    // enqueue every kernel-layout copy of a device blob into the copies' buffers
+    int relayout(const float* d_blob, hipStream_t s) {
+        for (int f = WL_F32; f < WL_RANGE; ++f)
+            HIP_TRY(launch_weight_copies(f, d_blob, d_tabs, d_copies + first[f], count[f], blocks[f], nullptr, s));
+        return SPDM_OK;
+    }
+};
+
+// a host blob on the device for as long as a table is being built from it
+struct DevBlob {
+    float* p = nullptr;
+    ~DevBlob() { if (p) { (void)hipDeviceSynchronize(); (void)hipFree(p); } }
+    int upload(const float* blob, size_t n) {
+        HIP_TRY(hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(float)));
+        HIP_TRY(hipMemcpy(p, blob, n * sizeof(float), hipMemcpyHostToDevice));
+        return SPDM_OK;
+    }
+};
+
 struct ProfEvt { hipEvent_t a, b; double flops; int launches; };
 
 struct spdm_handle {
@@ -144,18 +234,8 @@ struct spdm_handle {
     AttnW sa[6];
     float* outc_w = nullptr;
     float outc_b = 0.f;                   // a host scalar: the step kernel's argument
-    // device weight layouts (Loader, weight_layout.hip): what spdm_update_weights replays on a new blob
-    std::vector<WeightCopy> wl_copies;    // every copy spdm_load_weights made, in the order it made them (spdm_debug_weight_digest)
-    WeightCopy* d_wl = nullptr;           // ... on the device, grouped by format
-    WeightCopy* d_wl_range = nullptr;     // the split format's range checks (WL_RANGE)
-    int wl_first[WL_NFMT] = {}, wl_count[WL_NFMT] = {};
-    long long wl_blocks[WL_NFMT] = {};    // per format: first entry, entries and workgroups of its launch
-    long long* d_wl_tabs = nullptr;       // offset tables of the copies' table axes
-    int* d_wl_flags = nullptr;            // [slots] range verdicts + outc's bias (bits), read back together
-    std::vector<std::string> wl_slots;    // tensor name of each range slot
-    std::vector<int> wl_oor;              // ... outside the range at load (those tensors have no split copies)
+    WeightTable wt;                       // every kernel-layout copy of the weights; what spdm_update_weights replays on a new blob
     size_t blob_floats = 0;               // size of the loaded blob
-    long long outc_b_off = -1;            // outc.bias in it
     bool weights_loaded = false, temb_ready = false;
     bool train = false;                   // SPDM_FLAG_TRAIN: spdm_train_loss_grad (train_pass)
     bool train_attn = false;              // ... SPDM_FLAG_TRAIN_ATTENTION: through the SelfAttention blocks (TrainPass::sa_fwd / sa_bwd)
@@ -532,33 +612,39 @@ extern "C" void spdm_destroy(spdm_handle* h) {
 
 extern "C" int32_t spdm_uses_split_precision(const spdm_handle* h) { return (h && h->split) ? 1 : 0; }
 
-extern "C" size_t spdm_device_bytes(const spdm_handle* h) { return h ? h->persistent_bytes + h->arena.cap : 0; }
+extern "C" size_t spdm_device_bytes(const spdm_handle* h) { return h ? h->persistent_bytes + h->wt.bytes + h->arena.cap : 0; }
 
 // -------------------------------------------------------------------------------------------------
 // weights
 //
-// Every kernel-layout copy of a weight is made on the device from the torch-layout blob (weight_layout.hip).  The Loader
-// below is the one place each layout is defined: it records one WeightCopy (a gather, kernels.h) per copy as it walks the
-// network, and spdm_load_weights / spdm_update_weights run the recorded table.  It walks twice: the plan pass checks every
+// Every kernel-layout copy of a weight is made on the device from the torch-layout blob (weight_layout.hip).  The Recorder
+// below is the one place each layout is defined: it records one WeightCopy (a gather, kernels.h) per copy into a WeightTable,
+// for the Loader as it walks the network, for the encoder and for the standalone GEMM entry points alike; the table's
+// relayout then makes the copies (spdm_load_weights, spdm_update_weights, ...).  A walk runs twice: the plan pass checks every
 // name and shape and records the split format's range checks; once the device has answered them, the load pass allocates
-// the copies -- a tensor outside the range gets no split copy -- and records them.
+// the copies -- a tensor outside the range gets no split copy -- and records them (both_passes).  A table with no split
+// copies needs the load pass only (plan = false).
 static char g_plan_only;                   // the plan pass's stand-in for a copy it does not allocate
 
-struct Loader {
-    spdm_handle* h;
-    const float* blob;                     // host blob (spdm_load_weights): the few values the host itself keeps
-    size_t n;
+struct Recorder {
+    WeightTable& wt;
+    size_t n;                              // floats of the blob
     std::map<std::string, const spdm_tensor_index*> idx;
     int err = SPDM_OK;
     bool plan = true;
-    std::vector<int> oor;                  // load pass: per range slot, outside the split format's range
     std::map<std::string, int> slot_of;    // range slot of each tensor name (the stacked cond_emb_layer is one name)
-    std::vector<std::string> slots;
-    std::vector<WeightCopy> copies, ranges;
-    std::vector<long long> tabs;           // offset tables of the copies' table axes
-    std::set<std::string> demoted_names;   // tensors outside the split format's range (counted once each, however many copies they lose)
-    void demote(const std::string& name) { demoted_names.insert(name); if (h) h->demoted = (int)demoted_names.size(); }
-    long long at(const std::string& name, std::initializer_list<int> shape) {
+    std::vector<long long> plan_tabs;      // the plan pass's offset tables: the load pass must build the same
+    std::set<std::string> demoted;         // tensors outside the split format's range (once each, however many copies they lose)
+    Recorder(WeightTable& table, size_t blob_floats, const spdm_tensor_index* index = nullptr, int n_index = 0)
+        : wt(table), n(blob_floats) {
+        for (int i = 0; i < n_index; ++i) {
+            char name[SPDM_NAME_MAX + 1];
+            memcpy(name, index[i].name, SPDM_NAME_MAX);
+            name[SPDM_NAME_MAX] = 0;
+            idx[name] = &index[i];
+        }
+    }
+    long long at(const std::string& name, const std::vector<int>& shape) {
         auto it = idx.find(name);
         if (it == idx.end()) { err = fail(SPDM_ERR_MISSING, "tensor '%s' not in the index", name.c_str()); return -1; }
         const spdm_tensor_index* e = it->second;
@@ -588,16 +674,23 @@ struct Loader {
         if (taps == 9) { c.src += flipped ? 8 : 0; c.stride[0] = flipped ? -1 : 1; }
         else { c.src += flipped ? 7 : 1; c.stride[0] = flipped ? -3 : 3; }
     }
-    int table(const std::vector<long long>& t) {
-        const int at = (int)tabs.size();
-        tabs.insert(tabs.end(), t.begin(), t.end());
+    // (Cout, Cin, 3, 3) at src as [taps][Cout][Cin]
+    static WeightCopy conv_taps(long long src, int cout, int cin, int taps) {
+        WeightCopy v = dense(src, taps, cout, cin);
+        v.stride[1] = (long long)cin * 9; v.stride[2] = 9;
+        tap_axis(v, taps, false);
+        return v;
+    }
+    int table(const std::vector<long long>& tab) {
+        const int at = (int)wt.tabs.size();
+        wt.tabs.insert(wt.tabs.end(), tab.begin(), tab.end());
         return at;
     }
     // storage position -> source step of its real channel (ChanMap), -1 for a padding lane
     int map_table(const ChanMap& m, long long stride) {
-        std::vector<long long> t(m.width, -1);
-        for (int i = 0; i < m.real(); ++i) t[m.pos[i]] = (long long)i * stride;
-        return table(t);
+        std::vector<long long> tab(m.width, -1);
+        for (int i = 0; i < m.real(); ++i) tab[m.pos[i]] = (long long)i * stride;
+        return table(tab);
     }
     // every element the copy can read lies inside the blob
     bool inside(const WeightCopy& c) const {
@@ -606,8 +699,8 @@ struct Loader {
             if (c.tab[k] >= 0) {
                 long long tmin = LLONG_MAX, tmax = LLONG_MIN;
                 for (int i = 0; i < c.n[k]; ++i) {
-                    const long long t = tabs[c.tab[k] + i];
-                    if (t >= 0) { tmin = std::min(tmin, t); tmax = std::max(tmax, t); }
+                    const long long v = wt.tabs[c.tab[k] + i];
+                    if (v >= 0) { tmin = std::min(tmin, v); tmax = std::max(tmax, v); }
                 }
                 if (tmin == LLONG_MAX) continue;
                 lo += tmin; hi += tmax;
@@ -624,14 +717,12 @@ struct Loader {
         if (fmt == WL_PERM_HI || fmt == WL_PERM_LO) c.count /= 2;          // fp16 halves
         if (plan) return &g_plan_only;
         if (!inside(c)) { err = fail(SPDM_ERR_INVALID, "weight copy reads outside the blob"); return nullptr; }
-        void* p = nullptr;
-        if (dev_alloc(h, &p, (size_t)c.count * sizeof(float)) != SPDM_OK) { err = SPDM_ERR_HIP; return nullptr; }
-        c.dst = p;
-        copies.push_back(c);
-        return p;
+        if (wt.alloc(&c.dst, (size_t)c.count * sizeof(float)) != SPDM_OK) { err = SPDM_ERR_HIP; return nullptr; }
+        wt.copies.push_back(c);
+        return c.dst;
     }
     float* f32(const WeightCopy& c) { return (float*)put(c, WL_F32); }
-    // fragment-order split copy (frag_order_weights, kernels.h) of the logical [taps][N][K] array
+    // fragment-order split copy (WL_FRAG, weight_layout.hip) of the logical [taps][N][K] array
     float* frag(WeightCopy c, int taps, int N, int K) {
         c.taps = taps; c.N = N; c.K = K;
         return (float*)put(c, WL_FRAG);
@@ -642,15 +733,15 @@ struct Loader {
     bool in_range(WeightCopy c, const std::string& name) {
         auto it = slot_of.find(name);
         int s = 0;
-        if (it == slot_of.end()) { s = (int)slots.size(); slot_of[name] = s; slots.push_back(name); }
+        if (it == slot_of.end()) { s = (int)wt.slots.size(); slot_of[name] = s; wt.slots.push_back(name); }
         else s = it->second;
         if (plan) {
             c.fmt = WL_RANGE; c.slot = s; c.count = (long long)c.n[0] * c.n[1] * c.n[2];
             if (!inside(c)) { err = fail(SPDM_ERR_INVALID, "weight copy reads outside the blob"); return false; }
-            ranges.push_back(c);
+            wt.ranges.push_back(c);
             return true;
         }
-        if (oor[s]) { demote(name); return false; }
+        if (wt.oor[s]) { demoted.insert(name); return false; }
         return true;
     }
     // fp32 [rows][K] -> per 32-k chunk [32 x fp16 hi | 32 x fp16 lo] of x' = 128 x (conv_gemm.hip, PREC_SPLIT)
@@ -659,15 +750,48 @@ struct Loader {
         if (!in_range(c, name)) return nullptr;
         return (float*)put(c, WL_SPLIT);
     }
+    // (out, in) at src -> [in][out]: the weights of a Linear layer's data gradient (dx = dy W)
+    float* transposed(long long src, int out, int in) {
+        if (src < 0) return nullptr;
+        WeightCopy c = dense(src, 1, in, out);
+        c.stride[1] = 1; c.stride[2] = in;
+        return f32(c);
+    }
+    // walk() records through this Recorder and returns err.  Plan pass; the device answers the range checks on the blob; load pass
+    template <class Walk>
+    int both_passes(const float* d_blob, Walk walk) {
+        SPDM_TRY(walk());
+        SPDM_TRY(wt.upload(true));
+        SPDM_TRY(wt.check_ranges(d_blob, nullptr, &wt.oor));
+        plan_tabs.swap(wt.tabs);
+        plan = false;
+        SPDM_TRY(walk());
+        return finish(d_blob);
+    }
+    // after the load pass: the recorded copies on the device, made from the blob
+    int finish(const float* d_blob) {
+        SPDM_TRY(err);
+        if (wt.tabs != plan_tabs) return fail(SPDM_ERR_INVALID, "weight layout tables differ between the loader's passes");
+        SPDM_TRY(wt.upload(false));
+        SPDM_TRY(wt.relayout(d_blob, nullptr));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return SPDM_OK;
+    }
+};
+
+// The model walkers: the one part of weight loading that reads the handle's configuration (h->train*, h->cfg, h->film_kp)
+struct Loader : Recorder {
+    spdm_handle* h;
+    const float* blob;                     // host blob (spdm_load_weights): the few values the host itself keeps
+    Loader(spdm_handle* handle, const float* host_blob, size_t blob_floats, const spdm_tensor_index* index, int n_index)
+        : Recorder(handle->wt, blob_floats, index, n_index), h(handle), blob(host_blob) {}
     // (Cout,Cin,3,3) -> w [taps][Cout][Cin], its split and fragment-order copies, and (SPDM_FLAG_TRAIN) wt [taps][Cin][Cout]
     // with the taps rotated 180 degrees: the weights of the convolution that takes the output gradient to the input gradient
     ConvW conv(const std::string& name, int cout, int cin, int taps) {
         ConvW c;
         const long long o = at(name, {cout, cin, 3, 3});
         if (o < 0) return c;
-        WeightCopy v = dense(o, taps, cout, cin);
-        v.stride[1] = (long long)cin * 9; v.stride[2] = 9;
-        tap_axis(v, taps, false);
+        const WeightCopy v = conv_taps(o, cout, cin, taps);
         c.w = f32(v);
         if (h->train) {
             WeightCopy t = dense(o, taps, cin, cout);
@@ -827,20 +951,12 @@ struct Loader {
         a.ff1 = linear(p + ".ff_self.1.weight", p + ".ff_self.1.bias", C, C, C);
         a.ff2 = linear(p + ".ff_self.3.weight", p + ".ff_self.3.bias", C, C, C);
         if (h->train_attn) {
-            a.in_proj.wt = transposed(p + ".attention.in_proj_weight", 3 * C, C);
-            a.out_proj.wt = transposed(p + ".attention.out_proj.weight", C, C);
-            a.ff1.wt = transposed(p + ".ff_self.1.weight", C, C);
-            a.ff2.wt = transposed(p + ".ff_self.3.weight", C, C);
+            a.in_proj.wt = transposed(at(p + ".attention.in_proj_weight", {3 * C, C}), 3 * C, C);
+            a.out_proj.wt = transposed(at(p + ".attention.out_proj.weight", {C, C}), C, C);
+            a.ff1.wt = transposed(at(p + ".ff_self.1.weight", {C, C}), C, C);
+            a.ff2.wt = transposed(at(p + ".ff_self.3.weight", {C, C}), C, C);
         }
         return a;
-    }
-    // (out, in) -> [in][out]: the weights of a Linear layer's data gradient (dx = dy W)
-    float* transposed(const std::string& name, int out, int in) {
-        const long long o = at(name, {out, in});
-        if (o < 0) return nullptr;
-        WeightCopy t = dense(o, 1, in, out);
-        t.stride[1] = 1; t.stride[2] = in;
-        return f32(t);
     }
     // first conv (cout, 1, 3, 3) -> [9][64] (conv_in_kernel's layout; output lanes cout..63 zero)
     float* conv_in(const std::string& name, int cout) {
@@ -858,7 +974,7 @@ struct Loader {
         if (w < 0 || b < 0) return;
         h->outc_w = f32(dense(w, 1, 1, 64));
         h->outc_b = blob[b];
-        h->outc_b_off = b;
+        wt.scalar_off = b;
     }
 };
 
@@ -907,10 +1023,10 @@ static int load_simple(spdm_handle* h, Loader& L, int t3) {
     }
     if (L.err != SPDM_OK) return L.err;
     {   // the six cond_emb_layer Linears stacked: w [6 x 32][Kp] (columns beyond cond_dim zero), b [6 x 32]
-        WeightCopy cw = Loader::dense(0, 6, SIMPLE_COND_CH, Kp);
+        WeightCopy cw = Recorder::dense(0, 6, SIMPLE_COND_CH, Kp);
         cw.tab[0] = L.table(cw_off);
         cw.stride[1] = cd; cw.lim[2] = cd;
-        WeightCopy cb = Loader::dense(0, 1, 6, SIMPLE_COND_CH);
+        WeightCopy cb = Recorder::dense(0, 1, 6, SIMPLE_COND_CH);
         cb.tab[1] = L.table(cb_off);
         h->cemb.w = L.f32(cw);
         h->cemb.ws = L.split(cw, Kp, "cond_emb_layer");
@@ -918,7 +1034,7 @@ static int load_simple(spdm_handle* h, Loader& L, int t3) {
         h->cemb.in = Kp; h->cemb.out = 6 * SIMPLE_COND_CH;
         if (h->train_simple) {
             // d SiLU(cond) = dcemb [B][6 x 32] . W_stacked: the transposed copy [cond_dim padded to 64][6 x 32] (the GEMM's N % 64)
-            WeightCopy t = Loader::dense(0, (int)align_up((size_t)cd, 64), 6, SIMPLE_COND_CH);
+            WeightCopy t = Recorder::dense(0, (int)align_up((size_t)cd, 64), 6, SIMPLE_COND_CH);
             t.stride[0] = 1; t.lim[0] = cd;
             t.tab[1] = L.table(cw_off);
             t.stride[2] = cd;
@@ -983,87 +1099,20 @@ static int load_film(spdm_handle* h, Loader& L, int t3) {
     return L.err;
 }
 
-// a recorded table on the device, grouped by format in launch order (each format's workgroups numbered from 0): the range
-// checks (WL_RANGE) or the copies (every other format)
-static int upload_copies(spdm_handle* h, const std::vector<WeightCopy>& rec, bool ranges, WeightCopy** d_out) {
-    std::vector<WeightCopy> t;
-    for (int f = ranges ? WL_RANGE : 0; f < (ranges ? WL_RANGE + 1 : WL_RANGE); ++f) {
-        h->wl_first[f] = (int)t.size();
-        long long blk = 0;
-        for (WeightCopy c : rec)
-            if (c.fmt == f) { c.blk0 = blk; blk += weight_copy_blocks(c.count); t.push_back(c); }
-        h->wl_count[f] = (int)t.size() - h->wl_first[f];
-        h->wl_blocks[f] = blk;
-    }
-    if (t.empty()) return SPDM_OK;
-    SPDM_TRY(dev_alloc(h, (void**)d_out, sizeof(WeightCopy) * t.size()));
-    HIP_TRY(hipMemcpy(*d_out, t.data(), sizeof(WeightCopy) * t.size(), hipMemcpyHostToDevice));
-    return SPDM_OK;
-}
-
-// enqueue the range checks of a device blob and read their verdicts back, with outc's bias: one synchronisation
-static int check_ranges(spdm_handle* h, const float* d_blob, hipStream_t s, std::vector<int>* oor, float* outc_b) {
-    const size_t ns = h->wl_slots.size();
-    if (ns) HIP_TRY(hipMemsetAsync(h->d_wl_flags, 0, sizeof(int) * ns, s));
-    HIP_TRY(launch_weight_copies(WL_RANGE, d_blob, h->d_wl_tabs, h->d_wl_range, h->wl_count[WL_RANGE], h->wl_blocks[WL_RANGE],
-                                 h->d_wl_flags, s));
-    HIP_TRY(hipMemcpyAsync(h->d_wl_flags + ns, d_blob + h->outc_b_off, sizeof(float), hipMemcpyDeviceToDevice, s));
-    std::vector<int> back(ns + 1);
-    HIP_TRY(hipMemcpyAsync(back.data(), h->d_wl_flags, sizeof(int) * (ns + 1), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    oor->assign(back.begin(), back.begin() + ns);
-    memcpy(outc_b, &back[ns], sizeof(float));
-    return SPDM_OK;
-}
-
-// enqueue every kernel-layout copy of a device blob into the handle's weight buffers
-static int relayout(spdm_handle* h, const float* d_blob, hipStream_t s) {
-    for (int f = WL_F32; f < WL_RANGE; ++f)
-        HIP_TRY(launch_weight_copies(f, d_blob, h->d_wl_tabs, h->d_wl + h->wl_first[f], h->wl_count[f], h->wl_blocks[f], nullptr, s));
-    return SPDM_OK;
-}
-
 extern "C" int spdm_load_weights(spdm_handle* h, const float* blob, size_t n, const spdm_tensor_index* index,
                                  int32_t n_index) {
     if (!h || !blob || !index || n_index <= 0) return fail(SPDM_ERR_INVALID, "null argument");
     if (h->weights_loaded) return fail(SPDM_ERR_STATE, "weights already loaded on this handle");
     HIP_TRY(hipSetDevice(h->cfg.device));
-    Loader L{h, blob, n};
-    for (int i = 0; i < n_index; ++i) {
-        char name[SPDM_NAME_MAX + 1];
-        memcpy(name, index[i].name, SPDM_NAME_MAX);
-        name[SPDM_NAME_MAX] = 0;
-        L.idx[name] = &index[i];
-    }
+    Loader L(h, blob, n, index, n_index);
     // level-3 maps are (Hp/8) x 1: a 3x3 kernel only ever multiplies its centre column there
     const int t3 = (h->Wp >> 3) == 1 ? 3 : 9;
     auto walk = [&]() { return h->simple ? load_simple(h, L, t3) : load_film(h, L, t3); };
-    SPDM_TRY(walk());                      // plan pass: names, shapes, range checks
-    if (h->outc_b_off < 0) return fail(SPDM_ERR_MISSING, "outc.bias not loaded");
-    // the blob on the device, once; the range checks run on it
-    struct DevBlob { float* p = nullptr; ~DevBlob() { if (p) { (void)hipDeviceSynchronize(); (void)hipFree(p); } } } db;
-    HIP_TRY(hipMalloc((void**)&db.p, std::max<size_t>(n, 1) * sizeof(float)));
-    HIP_TRY(hipMemcpy(db.p, blob, n * sizeof(float), hipMemcpyHostToDevice));
-    if (!L.tabs.empty()) {
-        SPDM_TRY(dev_alloc(h, (void**)&h->d_wl_tabs, sizeof(long long) * L.tabs.size()));
-        HIP_TRY(hipMemcpy(h->d_wl_tabs, L.tabs.data(), sizeof(long long) * L.tabs.size(), hipMemcpyHostToDevice));
-    }
-    h->wl_slots = L.slots;
-    SPDM_TRY(dev_alloc(h, (void**)&h->d_wl_flags, sizeof(int) * (L.slots.size() + 1)));
-    SPDM_TRY(upload_copies(h, L.ranges, true, &h->d_wl_range));
-    float ob = 0.f;
-    SPDM_TRY(check_ranges(h, db.p, nullptr, &L.oor, &ob));
-    // load pass: allocate and record the copies (none of the split ones for a tensor outside the range), then make them
-    const std::vector<long long> plan_tabs = L.tabs;
-    L.tabs.clear();
-    L.plan = false;
-    SPDM_TRY(walk());
-    if (L.tabs != plan_tabs) return fail(SPDM_ERR_INVALID, "weight layout tables differ between the loader's passes");
-    h->wl_oor = L.oor;
-    h->wl_copies = L.copies;
-    SPDM_TRY(upload_copies(h, L.copies, false, &h->d_wl));
-    SPDM_TRY(relayout(h, db.p, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
+    DevBlob db;                            // the blob on the device, once; the range checks run on it
+    int rc = db.upload(blob, n);
+    if (rc == SPDM_OK) rc = L.both_passes(db.p, walk);
+    if (rc != SPDM_OK) { h->wt.clear(); return rc; }      // (a corrected blob may be loaded into this handle)
+    h->demoted = (int)L.demoted.size();
     h->blob_floats = n;
     if (h->train) {
         h->grad_off.clear();
@@ -1093,12 +1142,12 @@ extern "C" int spdm_update_weights(spdm_handle* h, const float* d_blob, size_t n
     hipStream_t s = (hipStream_t)stream;
     std::vector<int> oor;
     float ob = 0.f;
-    SPDM_TRY(check_ranges(h, d_blob, s, &oor, &ob));
+    SPDM_TRY(h->wt.check_ranges(d_blob, s, &oor, &ob));
     for (size_t i = 0; i < oor.size(); ++i)
-        if ((oor[i] != 0) != (h->wl_oor[i] != 0))
+        if ((oor[i] != 0) != (h->wt.oor[i] != 0))
             return fail(SPDM_ERR_STATE, "tensor '%s' %s the split format's range (|w| < 511): the workspace plan follows the set of "
-                        "such tensors -- load these weights into a new handle", h->wl_slots[i].c_str(), oor[i] ? "left" : "came back into");
-    SPDM_TRY(relayout(h, d_blob, s));
+                        "such tensors -- load these weights into a new handle", h->wt.slots[i].c_str(), oor[i] ? "left" : "came back into");
+    SPDM_TRY(h->wt.relayout(d_blob, s));
     h->temb_ready = false;                 // the time-embedding tables and a session's FiLM / cond_emb projections are
     h->session = false;                    // functions of the old weights
     uint32_t a, b;
@@ -1131,14 +1180,14 @@ extern "C" int spdm_debug_weight_digest(const spdm_handle* h, uint64_t* out) {
         for (; i < bytes; ++i) x = (x ^ c[i]) * 1099511628211ull;
     };
     std::vector<unsigned char> buf;
-    for (const WeightCopy& c : h->wl_copies) {
+    for (const WeightCopy& c : h->wt.copies) {
         buf.resize((size_t)c.count * sizeof(float));
         HIP_TRY(hipMemcpy(buf.data(), c.dst, buf.size(), hipMemcpyDeviceToHost));
         mix(buf.data(), buf.size());
     }
     mix(&h->outc_b, sizeof(float));
-    for (size_t i = 0; i < h->wl_slots.size(); ++i)
-        if (h->wl_oor[i]) mix(h->wl_slots[i].data(), h->wl_slots[i].size() + 1);
+    for (size_t i = 0; i < h->wt.slots.size(); ++i)
+        if (h->wt.oor[i]) mix(h->wt.slots[i].data(), h->wt.slots[i].size() + 1);
     *out = x;
     return SPDM_OK;
 }
@@ -1238,6 +1287,16 @@ static GemmArgs linear_args(const AffineSrc& x, int rows, int geom_M, const LinW
 
 // -------------------------------------------------------------------------------------------------
 // plan helpers
+// Statistics slots reserved per sample for a raw conv output [HW][C] whose own tiling writes `slots`: room for the finest
+// tiling any batch size can select (gemm_geometry is batch-dependent, the dry run that sizes the arena is not): 128-row x
+// 64-wide tiles, or the split-K combine kernel's row groups
+static int stats_slots_reserved(int HW, int C, int slots) {
+    return std::max(std::max(std::max(slots, stats_slots(HW, 128, std::max(1, C / 64))),   // (coarser tilings need fewer)
+                             stats_slots(HW, combine_rows(HW, C), 1)),
+                    std::max(stats_slots(HW, 16, std::max(1, C / 16)),              // conv_skinny's finest tiling
+                             stats_slots(HW, std::max(HW / 4, 1), 1)));             // conv_in_kernel's four row parts
+}
+
 struct Ctx {
     spdm_handle* h;
     int B;
@@ -1277,12 +1336,7 @@ struct Ctx {
     StatsBuf salloc(int HW, int C, int m_tile, int n_tiles, int C_norm = 0) {     // C_norm > 0: real channels of padded storage
         StatsBuf sb;
         const int slots = stats_slots(HW, m_tile, n_tiles);
-        // reserve for the finest tiling any batch size can select (gemm_geometry is batch-dependent, the
-        // dry run that sizes the arena is not): 128-row x 64-wide tiles, or the split-K combine kernel's row groups
-        const int slots_max = std::max(std::max(std::max(slots, stats_slots(HW, 128, std::max(1, C / 64))),   // (coarser tilings need fewer)
-                                                stats_slots(HW, combine_rows(HW, C), 1)),
-                                       std::max(stats_slots(HW, 16, std::max(1, C / 16)),              // conv_skinny's finest tiling
-                                                stats_slots(HW, std::max(HW / 4, 1), 1)));             // conv_in_kernel's four row parts
+        const int slots_max = stats_slots_reserved(HW, C, slots);
         size_t off = 0;
         if (!h->arena.alloc(sizeof(double) * 2 * (size_t)B * slots_max, &off)) {
             if (!err) err = fail(SPDM_ERR_NOMEM, "workspace exhausted (batch %d)", B);
@@ -2804,39 +2858,6 @@ extern "C" int spdm_profile_read(spdm_handle* h, int64_t* launches, double* tota
     return SPDM_OK;
 }
 
-// ---- host copies of two weight layouts, for the standalone GEMM entry points below (spdm_bench_gemm, spdm_op_gemm); a
-// handle's weights are laid out on the device (Loader, weight_layout.hip) ----
-// fp32 [rows][K] -> per 32-k chunk [32 x fp16 hi | 32 x fp16 lo] of x' = 128 x: hi = fp16(x'), lo = fp16(x' - hi)
-static std::vector<float> host_split_format(const std::vector<float>& v) {
-    std::vector<float> out(v.size());
-    for (size_t base = 0; base < v.size(); base += 32) {
-        _Float16* hp = reinterpret_cast<_Float16*>(&out[base]);
-        for (int j = 0; j < 32; ++j) {
-            const float x = v[base + j] * 128.0f;
-            const _Float16 hi = (_Float16)x;
-            hp[j] = hi;
-            hp[32 + j] = (_Float16)(x - (float)hi);
-        }
-    }
-    return out;
-}
-static bool host_split_range_ok(const std::vector<float>& v) {
-    float mx = 0.f;
-    for (float x : v) { const float ax = std::fabs(x); if (!(ax <= mx)) mx = ax; }
-    return mx < 511.0f;
-}
-// (Cout,Cin,3,3) -> [taps][Cout][Cin]; taps == 3 keeps only the centre column
-static std::vector<float> host_conv_taps(const float* src, int cout, int cin, int taps) {
-    std::vector<float> v((size_t)taps * cout * cin);
-    for (int t = 0; t < taps; ++t) {
-        const int kh = (taps == 9) ? t / 3 : t, kw = (taps == 9) ? t % 3 : 1;
-        for (int o = 0; o < cout; ++o)
-            for (int i = 0; i < cin; ++i)
-                v[((size_t)t * cout + o) * cin + i] = src[(((size_t)o * cin + i) * 3 + kh) * 3 + kw];
-    }
-    return v;
-}
-
 // -------------------------------------------------------------------------------------------------
 // Micro-benchmark of one implicit-GEMM launch shape on synthetic data (tools/bench_gemm.py); not on
 // the product path.  Returns the average device time per launch in *ms_out (HIP events).
@@ -2849,11 +2870,11 @@ extern "C" int spdm_bench_gemm(int32_t device, int32_t B, int32_t H, int32_t W, 
     const bool may_splitk = split && epi == EPI_STATS && !(sw & SW_NO_SPLITK);
     const GemmGeom g = gemm_geometry(M, Cout, Cin, HW, W, taps, split, sw, may_splitk);
     float *src = nullptr, *wgt = nullptr, *wgt32 = nullptr, *dst = nullptr, *dst2 = nullptr, *gb = nullptr, *resid = nullptr, *wfrag = nullptr;
+    DevBlob db;
+    WeightTable wt;                        // wgt32, wgt and wfrag: freed with it
     double *st_in = nullptr, *st_out = nullptr, *st_out2 = nullptr;
     const size_t nsrc = (size_t)M * Cin, nw = (size_t)taps * Cout * Cin, ndst = (size_t)M * Cout;
     HIP_TRY(hipMalloc((void**)&src, nsrc * 4));
-    HIP_TRY(hipMalloc((void**)&wgt, nw * 4));
-    HIP_TRY(hipMalloc((void**)&wgt32, nw * 4));
     HIP_TRY(hipMalloc((void**)&dst2, ndst * 4));
     HIP_TRY(hipMalloc((void**)&dst, ndst * 4));
     HIP_TRY(hipMalloc((void**)&resid, ndst * 4));
@@ -2865,7 +2886,7 @@ extern "C" int spdm_bench_gemm(int32_t device, int32_t B, int32_t H, int32_t W, 
     const GemmGeom g2 = gemm_geometry(M, Cout, Cin, HW, W, taps, 0, sw);
     HIP_TRY(hipMalloc((void**)&st_out2, (size_t)B * g2.slots * 2 * 8));
     HIP_TRY(hipMemset(st_out2, 0, (size_t)B * g2.slots * 2 * 8));
-    {   // deterministic pseudo-random fill (values ~U(-1,1)); split weights are packed as at load time
+    {   // deterministic pseudo-random fill (values ~U(-1,1)); the weights are laid out as at load time
         std::vector<float> hsrc(nsrc), hw(nw), hgb((size_t)(Cin + Cout) * 2), hres(ndst);
         unsigned x = 12345u;
         auto rnd = [&]() { x = x * 1664525u + 1013904223u; return ((x >> 8) * (1.0f / 8388608.0f)) - 1.0f; };
@@ -2873,19 +2894,21 @@ extern "C" int spdm_bench_gemm(int32_t device, int32_t B, int32_t H, int32_t W, 
         for (auto& v : hw) v = rnd() * 0.05f;
         for (auto& v : hgb) v = 1.0f + 0.1f * rnd();
         for (auto& v : hres) v = rnd();           // a non-zero residual: EPI_BIAS_RESID adds something
-        HIP_TRY(hipMemcpy(wgt32, hw.data(), nw * 4, hipMemcpyHostToDevice));
-        if (split) {
-            hw = host_split_format(hw);
-            if ((taps == 9 || taps == 3) && Cout % 64 == 0 && Cin % 32 == 0) {
-                const std::vector<float> fr = frag_order_weights(hw, taps, Cout, Cin);
-                HIP_TRY(hipMalloc((void**)&wfrag, nw * 4));
-                HIP_TRY(hipMemcpy(wfrag, fr.data(), nw * 4, hipMemcpyHostToDevice));
-            }
-        }
+        // generated in [taps][Cout][Cin] order: a dense source for the copies Loader::conv makes
+        Recorder R(wt, nw);
+        auto walk = [&]() {
+            const WeightCopy v = Recorder::dense(0, taps, Cout, Cin);
+            wgt32 = R.f32(v);
+            wgt = split ? R.split(v, Cin, "weight") : wgt32;
+            wfrag = (split && wgt && (taps == 9 || taps == 3) && Cout % 64 == 0) ? R.frag(v, taps, Cout, Cin) : nullptr;
+            return R.err;
+        };
+        SPDM_TRY(db.upload(hw.data(), nw));
+        SPDM_TRY(R.both_passes(db.p, walk));
+        if (!wgt) return fail(SPDM_ERR_INVALID, "bench_gemm: weights outside the split format's range");
         std::vector<double> hst((size_t)(row_ln ? M : B) * 2);
         for (size_t b = 0; b < hst.size() / 2; ++b) { hst[2 * b] = 0.0; hst[2 * b + 1] = (double)Cin * (row_ln ? 1 : HW) / 3.0; }
         HIP_TRY(hipMemcpy(src, hsrc.data(), nsrc * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(wgt, hw.data(), nw * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(gb, hgb.data(), hgb.size() * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(st_in, hst.data(), hst.size() * 8, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(resid, hres.data(), ndst * 4, hipMemcpyHostToDevice));
@@ -2970,8 +2993,8 @@ extern "C" int spdm_bench_gemm(int32_t device, int32_t B, int32_t H, int32_t W, 
         }
         (void)hipFree(d_stamps);
     }
-    (void)hipFree(wgt32); (void)hipFree(dst2); (void)hipFree(wfrag); (void)hipFree(d_part);
-    (void)hipFree(src); (void)hipFree(wgt); (void)hipFree(dst); (void)hipFree(resid); (void)hipFree(gb); (void)hipFree(st_in); (void)hipFree(st_out); (void)hipFree(st_out2);
+    (void)hipFree(dst2); (void)hipFree(d_part);
+    (void)hipFree(src); (void)hipFree(dst); (void)hipFree(resid); (void)hipFree(gb); (void)hipFree(st_in); (void)hipFree(st_out); (void)hipFree(st_out2);
     if (e != hipSuccess) return fail(SPDM_ERR_HIP, "bench_gemm: %s", hipGetErrorString(e));
     *ms_out = ms / iters;
     return SPDM_OK;
@@ -2986,7 +3009,9 @@ struct spdm_encoder {
     float* feat = nullptr;            // [chunk][9216] flattened conv-3 maps of the chunk in flight
     int chunk = 0;
     std::vector<void*> owned;
+    WeightTable wt;                   // the eight tensors above and, once the handle trains, the three transposed copies below
     long long off[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // blob offset of 0.weight 0.bias 2.* 4.* 7.* (the index given to create)
+    size_t numel[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // ... and their sizes
     size_t blob_floats = 0;
     // ---- training (spdm_encoder_train_forward / _backward; nothing below is allocated by a handle that never trains) ----
     float *wlT = nullptr, *w3T = nullptr, *w2T = nullptr;     // transposed copies: the data gradients' launch_gemm weights
@@ -3000,6 +3025,13 @@ static constexpr int ENC_FEAT = 64 * 12 * 12, ENC_LATENT = 128, ENC_CHUNK = 2048
 static constexpr int ENC_X3 = 144 * 128, ENC_X2 = 576 * 64;      // floats per frame of the conv-2 / conv-1 map
 static constexpr size_t ENC_WG_FLOATS = (size_t)8 * ENC_LATENT * ENC_FEAT;     // launch_wgrad's partial slabs (7.weight: <= 7)
 
+// nn.Sequential indices of Autoencoder.encoder: 0, 2, 4 = Conv2d; 7 = Linear
+static const struct { const char* name; std::vector<int> shape; float* spdm_encoder::*dst; } ENC_ITEMS[8] = {
+    {"0.weight", {16, 3, 2, 2}, &spdm_encoder::w1}, {"0.bias", {16}, &spdm_encoder::b1},
+    {"2.weight", {32, 16, 2, 2}, &spdm_encoder::w2}, {"2.bias", {32}, &spdm_encoder::b2},
+    {"4.weight", {64, 32, 2, 2}, &spdm_encoder::w3}, {"4.bias", {64}, &spdm_encoder::b3},
+    {"7.weight", {ENC_LATENT, ENC_FEAT}, &spdm_encoder::wl}, {"7.bias", {ENC_LATENT}, &spdm_encoder::bl}};
+
 extern "C" void spdm_encoder_destroy(spdm_encoder* e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
@@ -3011,38 +3043,24 @@ extern "C" int spdm_encoder_create(int32_t device, const float* blob, size_t n, 
                                    spdm_encoder** out) {
     if (!blob || !index || n_index <= 0 || !out) return fail(SPDM_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(device));
-    Loader L{nullptr, blob, n};
-    for (int i = 0; i < n_index; ++i) {
-        char name[SPDM_NAME_MAX + 1];
-        memcpy(name, index[i].name, SPDM_NAME_MAX);
-        name[SPDM_NAME_MAX] = 0;
-        L.idx[name] = &index[i];
-    }
-    // nn.Sequential indices of Autoencoder.encoder: 0, 2, 4 = Conv2d; 7 = Linear
-    struct Item { const char* name; std::initializer_list<int> shape; float* spdm_encoder::*dst; };
-    const Item items[8] = {{"0.weight", {16, 3, 2, 2}, &spdm_encoder::w1}, {"0.bias", {16}, &spdm_encoder::b1},
-                           {"2.weight", {32, 16, 2, 2}, &spdm_encoder::w2}, {"2.bias", {32}, &spdm_encoder::b2},
-                           {"4.weight", {64, 32, 2, 2}, &spdm_encoder::w3}, {"4.bias", {64}, &spdm_encoder::b3},
-                           {"7.weight", {ENC_LATENT, ENC_FEAT}, &spdm_encoder::wl}, {"7.bias", {ENC_LATENT}, &spdm_encoder::bl}};
     spdm_encoder* e = new spdm_encoder();
     e->device = device;
-    for (const Item& it : items) {
-        const long long off = L.at(it.name, it.shape);
-        if (off < 0) { spdm_encoder_destroy(e); return L.err; }
-        const float* src = blob + off;
-        size_t numel = 1;
-        for (int d : it.shape) numel *= (size_t)d;
-        void* p = nullptr;
-        if (hipMalloc(&p, numel * sizeof(float)) != hipSuccess || hipMemcpy(p, src, numel * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-            if (p) (void)hipFree(p);
-            spdm_encoder_destroy(e);
-            return fail(SPDM_ERR_HIP, "encoder weight upload failed");
-        }
-        e->owned.push_back(p);
-        e->*(it.dst) = (float*)p;
-        e->off[&it - items] = off;
-    }
     e->blob_floats = n;
+    Recorder R(e->wt, n, index, n_index);
+    R.plan = false;                        // fp32 copies only: nothing to ask the device first
+    for (int k = 0; k < 8; ++k) {
+        const long long off = R.at(ENC_ITEMS[k].name, ENC_ITEMS[k].shape);
+        if (off < 0) break;
+        e->off[k] = off;
+        e->numel[k] = 1;
+        for (int d : ENC_ITEMS[k].shape) e->numel[k] *= (size_t)d;
+        e->*(ENC_ITEMS[k].dst) = R.f32(Recorder::dense(off, 1, 1, (int)e->numel[k]));
+    }
+    DevBlob db;
+    int rc = R.err;
+    if (rc == SPDM_OK) rc = db.upload(blob, n);
+    if (rc == SPDM_OK) rc = R.finish(db.p);
+    if (rc != SPDM_OK) { spdm_encoder_destroy(e); return rc; }
     *out = e;
     return SPDM_OK;
 }
@@ -3061,14 +3079,6 @@ static void enc_release(spdm_encoder* e, float** p) {
     (void)hipFree(*p);
     *p = nullptr;
 }
-// the transposed copies the data gradients read: dx = dy W is the forward GEMM on W^T ([N = in][K = out], k contiguous)
-static int enc_transposes(spdm_encoder* e, hipStream_t s) {
-    HIP_TRY(launch_transpose(e->wl, ENC_LATENT, ENC_FEAT, e->wlT, s));      // (128, 9216) -> [9216][128]
-    HIP_TRY(launch_transpose(e->w3, 64, 128, e->w3T, s));                   // (64, 32*4)  -> [128][64]
-    HIP_TRY(launch_transpose(e->w2, 32, 64, e->w2T, s));                    // (32, 16*4)  -> [64][32]
-    return SPDM_OK;
-}
-
 extern "C" int spdm_encoder_forward(spdm_encoder* e, int32_t n_images, const float* d_images, float* d_latent, void* stream) {
     if (!e || !d_images || !d_latent || n_images <= 0) return fail(SPDM_ERR_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(e->device));
@@ -3101,13 +3111,23 @@ extern "C" int spdm_encoder_train_forward(spdm_encoder* e, int32_t n_images, con
     hipStream_t s = (hipStream_t)stream;
     e->sv_n = 0;
     if (!e->wlT) {
-        SPDM_TRY(enc_alloc(e, &e->wlT, (size_t)ENC_LATENT * ENC_FEAT));
-        SPDM_TRY(enc_alloc(e, &e->w3T, 128 * 64));
-        SPDM_TRY(enc_alloc(e, &e->w2T, 64 * 32));
         SPDM_TRY(enc_alloc(e, &e->wg_part, ENC_WG_FLOATS));
         SPDM_TRY(enc_alloc(e, &e->c1_part, (size_t)encoder_conv1_wgrad_blocks(ENC_CHUNK) * 208));
         SPDM_TRY(enc_alloc(e, &e->g_tmp, e->blob_floats));
-        SPDM_TRY(enc_transposes(e, s));
+        // the transposed copies the data gradients read: dx = dy W is the forward GEMM on W^T ([N = in][K = out], k contiguous)
+        Recorder R(e->wt, e->blob_floats);
+        R.plan = false;
+        float* const w2T = R.transposed(e->off[2], 32, 64);                   // (32, 16*4)  -> [64][32]
+        float* const w3T = R.transposed(e->off[4], 64, 128);                  // (64, 32*4)  -> [128][64]
+        float* const wlT = R.transposed(e->off[6], ENC_LATENT, ENC_FEAT);     // (128, 9216) -> [9216][128]
+        SPDM_TRY(R.err);
+        SPDM_TRY(e->wt.upload(false));
+        // the handle keeps no blob: the weights go back to their blob offsets in g_tmp (scratch until a backward pass), and laying
+        // that out again fills the new copies
+        for (int k = 0; k < 8; ++k)
+            HIP_TRY(hipMemcpyAsync(e->g_tmp + e->off[k], e->*(ENC_ITEMS[k].dst), e->numel[k] * sizeof(float), hipMemcpyDeviceToDevice, s));
+        SPDM_TRY(e->wt.relayout(e->g_tmp, s));
+        e->w2T = w2T; e->w3T = w3T; e->wlT = wlT;
     }
     if (e->sv_cap < n_images) {
         HIP_TRY(hipDeviceSynchronize());      // (an earlier call's kernels may still read the buffers being replaced)
@@ -3195,8 +3215,7 @@ extern "C" int spdm_encoder_backward(spdm_encoder* e, int32_t n_images, const fl
         // ---- conv 1: K = 3 * 4, no data gradient (nothing is differentiated with respect to the frames) ----
         HIP_TRY(launch_encoder_conv1_wgrad(img, dx2, e->bw_x2, m, e->c1_part, G + e->off[0], G + e->off[1], s));
         if (i0 != 0) {
-            const int shape_n[8] = {16 * 12, 16, 32 * 64, 32, 64 * 128, 64, ENC_LATENT * ENC_FEAT, ENC_LATENT};
-            for (int k = 0; k < 8; ++k) HIP_TRY(launch_add(e->g_tmp + e->off[k], shape_n[k], d_grad + e->off[k], s));
+            for (int k = 0; k < 8; ++k) HIP_TRY(launch_add(e->g_tmp + e->off[k], e->numel[k], d_grad + e->off[k], s));
         }
     }
     if (!stream) HIP_TRY(hipStreamSynchronize(s));
@@ -3210,18 +3229,14 @@ extern "C" int spdm_encoder_update_weights(spdm_encoder* e, const float* d_blob,
     if (n != e->blob_floats) return fail(SPDM_ERR_INVALID, "blob has %zu floats; the one given to spdm_encoder_create had %zu", n, e->blob_floats);
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
-    float* const dst[8] = {e->w1, e->b1, e->w2, e->b2, e->w3, e->b3, e->wl, e->bl};
-    const size_t cnt[8] = {16 * 12, 16, 32 * 64, 32, 64 * 128, 64, (size_t)ENC_LATENT * ENC_FEAT, ENC_LATENT};
     e->sv_n = 0;                               // saved maps belong to the old weights
-    for (int k = 0; k < 8; ++k)
-        HIP_TRY(hipMemcpyAsync(dst[k], d_blob + e->off[k], cnt[k] * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (e->wlT) SPDM_TRY(enc_transposes(e, s));
+    SPDM_TRY(e->wt.relayout(d_blob, s));
     if (!stream) HIP_TRY(hipStreamSynchronize(s));
     return SPDM_OK;
 }
 
 // Host-only introspection (no GPU): the launch geometry gemm_geometry picks for a statistics-epilogue convolution, plus the
-// statistics-slot reservation the plan makes for it (Ctx::salloc).  tests/test_geometry.py checks the invariants between the
+// statistics-slot reservation the plan makes for it (stats_slots_reserved, as Ctx::salloc).  tests/test_geometry.py checks the invariants between the
 // two on a grid of shapes (a mismatch is a silent wrong-statistics bug on the GPU).
 extern "C" int spdm_debug_geometry(int32_t M, int32_t N, int32_t K, int32_t HW, int32_t W, int32_t taps, uint32_t switches,
                                    int32_t out[10]) {
@@ -3229,8 +3244,7 @@ extern "C" int spdm_debug_geometry(int32_t M, int32_t N, int32_t K, int32_t HW, 
     const GemmGeom g = gemm_geometry(M, N, K, HW, W, taps, /*split=*/1, switches, /*stats_epi=*/true);
     out[0] = g.m_tile; out[1] = g.n_tile; out[2] = g.n_tiles; out[3] = g.slots; out[4] = g.ksplit; out[5] = g.skinny | (g.reg << 1);
     out[6] = g.st_m_tile; out[7] = g.st_n_tiles;
-    out[8] = std::max(std::max(std::max(g.slots, stats_slots(HW, 128, std::max(1, N / 64))), stats_slots(HW, combine_rows(HW, N), 1)),
-                      std::max(stats_slots(HW, 16, std::max(1, N / 16)), stats_slots(HW, std::max(HW / 4, 1), 1)));   // = Ctx::salloc's reservation
+    out[8] = stats_slots_reserved(HW, N, g.slots);
     out[9] = combine_rows(HW, N);
     return SPDM_OK;
 }
@@ -3275,11 +3289,22 @@ extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {
     const int M = q.B * HW;
     const int src_rows = q.pro == PRO_POOL ? 4 * HW : q.pro == PRO_UPCAT ? HW / 4 : HW;      // rows per sample of src
     if (q.pro == PRO_UPCAT && ((q.H & 1) || (q.W & 1))) return fail(SPDM_ERR_INVALID, "op_gemm: upsample read-through needs an even map");
-    const std::vector<float> w32 = q.taps == 1 ? std::vector<float>(q.h_weight, q.h_weight + (size_t)q.N * q.K)
-                                               : host_conv_taps(q.h_weight, q.N, q.K, q.taps);
-    if (q.split && !host_split_range_ok(w32)) return fail(SPDM_ERR_INVALID, "op_gemm: weights outside the split format's range (the loader keeps such a layer on the exact path)");
-    const unsigned sw = switches_from_env();
     const int split = q.split ? 1 : 0;
+    // the weights as the loader lays them out: the caller's torch-layout tensor is the blob of a table of its own
+    DevBlob db;
+    WeightTable wt;
+    Recorder R(wt, (size_t)q.N * q.K * (q.taps == 1 ? 1 : 9));
+    float *dw = nullptr, *dwf = nullptr;
+    auto walk = [&]() {                    // Loader::linear / Loader::conv (Cout % 64 == 0 here: a fragment-order copy)
+        const WeightCopy v = q.taps == 1 ? Recorder::dense(0, 1, q.N, q.K) : Recorder::conv_taps(0, q.N, q.K, q.taps);
+        dw = split ? R.split(v, q.K, "weight") : R.f32(v);
+        dwf = (split && dw && q.taps != 1) ? R.frag(v, q.taps, q.N, q.K) : nullptr;
+        return R.err;
+    };
+    SPDM_TRY(db.upload(q.h_weight, R.n));
+    SPDM_TRY(R.both_passes(db.p, walk));
+    if (!dw) return fail(SPDM_ERR_INVALID, "op_gemm: weights outside the split format's range (the loader keeps such a layer on the exact path)");
+    const unsigned sw = switches_from_env();
     // as the plan: a split-precision convolution may split K unless switched off (the handle then holds no partial buffer)
     const bool may_partial = split && q.taps != 1 && q.epi == EPI_STATS && !(sw & SW_NO_SPLITK);
     const GemmGeom g = gemm_geometry(M, q.N, q.K, HW, q.W, q.taps, split, sw, may_partial);
@@ -3289,30 +3314,8 @@ extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {
         return fail(SPDM_ERR_INVALID, "op_gemm: row statistics buffer needs %zu doubles", (size_t)M * g.n_tiles * 2);
     if (g.ksplit > 1 && (size_t)g.ksplit * M * q.N * sizeof(float) > SPLITK_WORKSPACE_BYTES)
         return fail(SPDM_ERR_INVALID, "op_gemm: split-K slabs exceed the workspace");
-    std::vector<void*> owned;
-    auto release = [&]() { for (void* v : owned) (void)hipFree(v); };
-    auto upload = [&](const void* h, size_t bytes, void** d) -> hipError_t {
-        hipError_t e = hipMalloc(d, std::max<size_t>(bytes, 256));
-        if (e != hipSuccess) return e;
-        owned.push_back(*d);
-        return h ? hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice) : hipSuccess;
-    };
-    hipError_t e = hipSuccess;
-    void* dw = nullptr;
-    void* dwf = nullptr;
-    void* dp = nullptr;
-    if (split) {
-        const std::vector<float> ws = host_split_format(w32);
-        e = upload(ws.data(), ws.size() * 4, &dw);
-        if (e == hipSuccess && q.taps != 1) {       // the loader's fragment-order copy (Cout % 64 == 0 here)
-            const std::vector<float> wf = frag_order_weights(ws, q.taps, q.N, q.K);
-            e = upload(wf.data(), wf.size() * 4, &dwf);
-        }
-    } else {
-        e = upload(w32.data(), w32.size() * 4, &dw);
-    }
-    if (e == hipSuccess && may_partial) e = upload(nullptr, g.ksplit > 1 ? (size_t)g.ksplit * M * q.N * sizeof(float) : 0, &dp);
-    if (e != hipSuccess) { release(); return fail(SPDM_ERR_HIP, "op_gemm: %s", hipGetErrorString(e)); }
+    float* dp = nullptr;                   // (freed with the table)
+    if (may_partial) SPDM_TRY(wt.alloc((void**)&dp, g.ksplit > 1 ? (size_t)g.ksplit * M * q.N * sizeof(float) : 0));
     // the caller's tensors as the plan's sources, pending GroupNorms from the raw partials; then the plan's own builder
     auto ref = [](const double* st, int slots, int m_tile, int n_tiles, int rows, int cnorm) {
         return StatsRef{st, slots, m_tile, n_tiles, rows, 1.0 / ((double)cnorm * rows)};
@@ -3326,27 +3329,21 @@ extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {
         skip = AffineSrc{q.d_skip, q.skip_ld, ref(q.d_skip_stats, q.skip_slots, q.skip_m_tile, q.skip_n_tiles, HW,
                                                   q.skip_cnorm > 0 ? q.skip_cnorm : q.K - q.up_C), q.d_skip_gamma, q.d_skip_beta};
     const int pro = (two && q.d_skip_stats) ? PRO_GN : q.pro;         // (Ctx::two_args)
-    GemmArgs a = gemm_args(M, M, q.H, q.W, q.K, q.N, q.taps, split, sw, (float*)dp, pro, src, q.up_C, skip, (const float*)dw,
-                           (const float*)dwf, q.d_dst, q.dst_ld, q.epi, q.epi == EPI_STATS ? q.d_stats : nullptr, q.d_bias,
+    GemmArgs a = gemm_args(M, M, q.H, q.W, q.K, q.N, q.taps, split, sw, dp, pro, src, q.up_C, skip, dw,
+                           dwf, q.d_dst, q.dst_ld, q.epi, q.epi == EPI_STATS ? q.d_stats : nullptr, q.d_bias,
                            q.d_resid, q.resid_ld, q.d_row_stats);
-    if (fused && !gemm_takes_fused_source(a)) {
-        release();
+    if (fused && !gemm_takes_fused_source(a))
         return fail(SPDM_ERR_INVALID, "op_gemm: this launch does not take a fused source (the plan materialises it)");
-    }
-    if (two && !gemm_takes_two_sources(a)) {
-        release();
+    if (two && !gemm_takes_two_sources(a))
         return fail(SPDM_ERR_INVALID, "op_gemm: this launch does not take a two-source input (the plan concatenates)");
-    }
     GemmRoute r{-1, -1, -1, -1};
     a.route = &r;                 // the launch records what it dispatched
     // unwritten partials read as NaN
-    if (q.epi == EPI_STATS) e = hipMemset(q.d_stats, 0xff, (size_t)q.B * g.slots * 2 * sizeof(double));
-    if (e == hipSuccess && q.d_row_stats) e = hipMemset(q.d_row_stats, 0xff, (size_t)M * g.n_tiles * 2 * sizeof(double));
-    if (e != hipSuccess) { release(); return fail(SPDM_ERR_HIP, "op_gemm: %s", hipGetErrorString(e)); }
+    if (q.epi == EPI_STATS) HIP_TRY(hipMemset(q.d_stats, 0xff, (size_t)q.B * g.slots * 2 * sizeof(double)));
+    if (q.d_row_stats) HIP_TRY(hipMemset(q.d_row_stats, 0xff, (size_t)M * g.n_tiles * 2 * sizeof(double)));
     const hipError_t el = launch_gemm(a, nullptr);
     // (the split-K main kernel may have been launched before the combine reported an error: always drain the device first)
     const hipError_t es = hipDeviceSynchronize();
-    release();
     if (el != hipSuccess)
         return fail(el == hipErrorInvalidValue && r.kernel < 0 ? SPDM_ERR_INVALID : SPDM_ERR_HIP,
                     "op_gemm: launch_gemm failed (%s) %s; device: %s", hipGetErrorString(el),

@@ -85,7 +85,11 @@ __global__ __launch_bounds__(WL_THREADS) void weight_copy_kernel(const float* __
         } else if constexpr (FMT == WL_SPLIT) {
             v = wl_split_float(c, blob, tabs, d);
         } else if constexpr (FMT == WL_FRAG) {
-            // frag_order_weights (kernels.h) inverted: destination float d <- split float s of [taps][N][K]
+            // Fragment-order copy of split-format weights [taps][N][K] for conv_wide.hip (v_mfma_f32_16x16x32_f16 B operands):
+            //   block ((tap K/32 + chunk) N/16 + nb16) x {hi, lo} of 1 KiB; lane (kg 16 + l16) -> 16 bytes = 8 fp16 of row
+            //   nb16 16 + l16, k = chunk 32 + kg 8 .. -- so a wave's operand load is one coalesced global_load_dwordx4.
+            //   Same bytes as the split array, permuted.  (N % 16 == 0, K % 32 == 0.)
+            // Inverted here: destination float d <- split float s of [taps][N][K]
             const int nch = c.K / 32, nbn = c.N / 16;
             const int jj = (int)(d & 3);
             long long r = d >> 2;

@@ -478,3 +478,23 @@ def test_invalid_combinations_are_refused():
     assert rc == -1 and b"fused source" in msg
     rc, msg = op_gemm(2, 8, 8, 64, 64, 9, 1, PRO_GN, EPI_STATS, x, w, check=False)
     assert rc == -1
+
+
+def test_split_range_verdict_at_the_smallest_conv_shape():
+    """spdm_op_gemm lays its weights out through the device weight-copy table, so the split format's range verdict is the
+    WL_RANGE kernel's (weight_layout.hip): !(|w| < 511), NaN included, refuses the launch; 510 is accepted and the output meets
+    this file's bound.  The marked weight sits in the centre column, the one a 3-tap launch reads."""
+    B, H, W, K, N, taps = 1, 8, 1, 32, 64, 3
+    x = activations(B, H * W, K, 2, "unit")
+    w = weights(N, K, taps, 3)
+    for bad in (600.0, float("nan")):
+        wb = w.clone()
+        wb[5, 7, 2, 1] = bad
+        rc, msg = op_gemm(B, H, W, K, N, taps, 1, PRO_NONE, EPI_STATS, x, wb, check=False)
+        assert rc == -1 and b"op_gemm: weights outside the split format's range" in msg, (bad, rc, msg)
+    centre = w[:, :, :, 1]
+    centre.view(-1)[centre.abs().argmax()] = 510.0           # (a view: w itself changes)
+    assert float(w.abs().max()) == 510.0
+    r = op_gemm(B, H, W, K, N, taps, 1, PRO_NONE, EPI_STATS, x, w)
+    want, scale = ref_launch(PRO_NONE, EPI_STATS, x, w, H, W, taps=taps)
+    compare(r, want, scale, floor_terms(PRO_NONE, x, w, H, W, taps=taps), 1, list(range(B)), "range: |w| max 510")
