@@ -333,6 +333,51 @@ int  spdm_encoder_backward(spdm_encoder* e, int32_t n_images, const float* d_ima
                            float* d_grad, void* stream);
 int  spdm_encoder_update_weights(spdm_encoder* e, const float* d_blob, size_t n_floats, void* stream);
 
+/* The autoencoder's decoder and its reconstruction training: the stage that produces the encoder
+ * checkpoint Diffusion_DDPM loads (models/diffusion_ddpm.py:84-88), models/encoder/train_autoencoder.py on
+ * models/encoder/autoencoder.py.  Autoencoder.decoder (:23-32) is Linear(128,9216) Unflatten(64,12,12)
+ * ConvTranspose2d(64,32,2,2) ReLU ConvTranspose2d(32,16,2,2) ReLU ConvTranspose2d(16,3,2,2) Sigmoid; the loss is
+ * MSELoss(recon, batch) (:48,55-58).  Every contraction is exact fp32 and every reduction runs in a fixed order without
+ * atomics: two calls on the same inputs give the same bits.  A handle that never trains allocates nothing for training.
+ * The saved maps' ReLU masks are settled by a second, float64 evaluation of the pre-activations, as the encoder's are.
+ *
+ * spdm_decoder_create.  Replaces: the construction of Autoencoder.decoder (:23-32) and load_state_dict on it.  Weights: the
+ * decoder's own state_dict (names "0.weight" (9216,128) "0.bias" "2.weight" (64,32,2,2) "2.bias" "4.weight" (32,16,2,2)
+ * "4.bias" "6.weight" (16,3,2,2) "6.bias", torch layouts) as a host blob + index, like spdm_encoder_create.
+ * SPDM_ERR_INVALID: null pointer, or a name or shape that is not the decoder's.
+ *
+ * spdm_decoder_forward.  Replaces: self.decoder(encoded) of Autoencoder.forward (:34-37), as eval_autoencoder.py uses it.
+ * d_latent (n,128) -> d_recon (n,3,96,96), fp32 on the device.
+ *
+ * spdm_decoder_train_loss.  Replaces: recon = self.model(batch) past the encoder and loss = self.loss(recon, batch) of
+ * onepass (:55-58).  d_target (n,3,96,96); d_loss one float on the device = sum (recon - target)^2 / (n 27648), the squares
+ * added in float64 in a fixed order; d_recon NULL or (n,3,96,96): the reconstruction, spdm_decoder_forward's bit for bit.
+ * Keeps per frame the Linear's output, the two post-ReLU maps and the reconstruction (37 + 74 + 147 + 111 KB) for ONE
+ * following spdm_decoder_backward.
+ *
+ * spdm_decoder_backward.  Replaces: loss.backward() through the decoder (training_step :61-65 under Lightning's automatic
+ * optimisation).  d_latent and d_target are those of the pending train_loss.  d_grad: device blob of the n_floats given to
+ * create, every tensor's gradient at that tensor's offset in torch layout, zeros between.  d_grad_latent (n,128):
+ * d loss / d latent, what spdm_encoder_backward takes.  Frames go through in chunks of 2048 whose gradients are added in
+ * chunk order.  SPDM_ERR_STATE: no train_loss pending (none yet, already consumed by a backward, or followed by
+ * spdm_decoder_update_weights), or n differs from it.
+ *
+ * spdm_decoder_update_weights.  Replaces: optimizer.step() on the decoder's parameters (configure_optimizers :73-74).
+ * d_blob is a DEVICE blob in the layout given to create; afterwards spdm_decoder_forward equals a new handle created on
+ * those values, bit for bit.  A pending train_loss is dropped.
+ *
+ * All: SPDM_ERR_INVALID on a null pointer (d_recon of train_loss excepted), n <= 0, or an n_floats that differs from create's. */
+typedef struct spdm_decoder spdm_decoder;
+int  spdm_decoder_create(int32_t device, const float* h_blob, size_t n_floats, const spdm_tensor_index* h_index,
+                         int32_t n_index, spdm_decoder** out);
+int  spdm_decoder_forward(spdm_decoder* d, int32_t n, const float* d_latent, float* d_recon, void* stream);
+int  spdm_decoder_train_loss(spdm_decoder* d, int32_t n, const float* d_latent, const float* d_target,
+                             float* d_recon /* may be NULL */, float* d_loss, void* stream);
+int  spdm_decoder_backward(spdm_decoder* d, int32_t n, const float* d_latent, const float* d_target, float* d_grad,
+                           float* d_grad_latent, void* stream);
+int  spdm_decoder_update_weights(spdm_decoder* d, const float* d_blob, size_t n_floats, void* stream);
+void spdm_decoder_destroy(spdm_decoder* d);
+
 /* Host-only test hook (no GPU call): the launch geometry chosen for a split-precision 3x3 / 3x1 convolution with the
  * statistics epilogue -- out = {m_tile, n_tile, n_tiles, slots, ksplit, kernel, st_m_tile, st_n_tiles, reserved_slots,
  * combine_rows}; kernel: bit 0 = the small-grid kernel (conv_skinny.hip), bit 1 = the register-resident kernel (conv_reg.hip).

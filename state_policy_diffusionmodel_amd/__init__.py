@@ -2,4 +2,4 @@
 
 Importing the package is cheap and GPU-free; the HIP library is bound on first use
 (``_lib.load()``) and there is no CPU fallback."""
-__all__ = ["build", "weights", "schedulers", "engine", "diffusion", "distributed"]
+__all__ = ["build", "weights", "schedulers", "engine", "diffusion", "distributed", "autoencoder"]

@@ -19,6 +19,7 @@ SPDM_FLAG_SIMPLE_UNET = 4
 SPDM_FLAG_TRAIN = 8
 SPDM_FLAG_TRAIN_ATTENTION = 16
 SPDM_FLAG_TRAIN_SIMPLE = 32
+SPDM_ERR_INVALID = -1
 SPDM_ERR_STATE = -3
 ABI_VERSION = 2
 
@@ -81,6 +82,12 @@ SYMBOLS = {
     "spdm_encoder_train_forward": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "spdm_encoder_backward": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "spdm_encoder_update_weights": (c_int32, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "spdm_decoder_create": (c_int32, [c_int32, c_void_p, c_size_t, POINTER(TensorIndex), c_int32, POINTER(c_void_p)]),
+    "spdm_decoder_forward": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "spdm_decoder_train_loss": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "spdm_decoder_backward": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "spdm_decoder_update_weights": (c_int32, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "spdm_decoder_destroy": (None, [c_void_p]),
     "spdm_op_gelu": (c_int32, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "spdm_op_gemm": (c_int32, [POINTER(SpdmOpGemmArgs)]),
     "spdm_debug_geometry": (c_int32, [c_int32] * 6 + [ctypes.c_uint32, POINTER(c_int32 * 10)]),

@@ -1,0 +1,269 @@
+"""The reference's lightweight autoencoder on the GPU: the stage that produces the encoder checkpoint
+``Diffusion_DDPM`` loads (models/diffusion_ddpm.py:84-88).
+
+Mirror of models/encoder/autoencoder.py: ``Autoencoder`` (:7-37, encoder -> decoder) inside the LightningModule
+``autoencoder`` (:40-83, ``MSELoss(recon, batch)``, Adam + ReduceLROnPlateau), which models/encoder/train_autoencoder.py
+trains with ``gradient_clip_val=0.5``.  The encoder half is ``vision.VisionEncoder``; ``Decoder`` here is
+``Autoencoder.decoder`` (:23-32), an ``nn.Sequential`` whose state_dict keys are ``0.weight 0.bias 2.* 4.* 6.*``.  All
+compute is in libspdm_hip.so (``spdm_decoder_*``, csrc/decoder.hip); there is no CPU path here and the
+optimiser stays in torch.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Dict, Optional
+
+import torch
+
+from . import _lib
+from .vision import ENCODER_KEYS, LATENT_DIM, VisionEncoder, encoder_state_dict_from
+from .weights import pack_state_dict, safe_load_state_dict
+
+DECODER_KEYS = ("0.weight", "0.bias", "2.weight", "2.bias", "4.weight", "4.bias", "6.weight", "6.bias")
+DECODER_SHAPES = {"0.weight": (9216, 128), "0.bias": (9216,), "2.weight": (64, 32, 2, 2), "2.bias": (32,),
+                  "4.weight": (32, 16, 2, 2), "4.bias": (16,), "6.weight": (16, 3, 2, 2), "6.bias": (3,)}
+FRAME = (3, 96, 96)
+
+
+def decoder_state_dict_from(sd, prefix: str = "decoder."):
+    """Pick the decoder's tensors out of an autoencoder checkpoint's state_dict (``decoder.N.*`` /
+    ``model.decoder.N.*``) or a bare decoder state_dict.  Returns None when they are not there."""
+    for pre in (prefix, "decoder.", "model.decoder.", ""):
+        if all((pre + k) in sd for k in DECODER_KEYS):
+            return {k: sd[pre + k] for k in DECODER_KEYS}
+    return None
+
+
+def _default_init() -> Dict[str, torch.Tensor]:
+    """Both halves with torch's default initialisers for these layers, in checkpoint key names (``encoder.N.*`` /
+    ``decoder.N.*``).  Parameter creation only: the modules are never run."""
+    nn = torch.nn
+    enc = nn.Sequential(nn.Conv2d(3, 16, 2, stride=2, padding=1), nn.ReLU(), nn.Conv2d(16, 32, 2, stride=2), nn.ReLU(),
+                        nn.Conv2d(32, 64, 2, stride=2), nn.ReLU(), nn.Flatten(), nn.Linear(64 * 12 * 12, LATENT_DIM))
+    dec = nn.Sequential(nn.Linear(LATENT_DIM, 64 * 12 * 12), nn.Unflatten(1, (64, 12, 12)),
+                        nn.ConvTranspose2d(64, 32, 2, stride=2), nn.ReLU(), nn.ConvTranspose2d(32, 16, 2, stride=2), nn.ReLU(),
+                        nn.ConvTranspose2d(16, 3, 2, stride=2), nn.Sigmoid())
+    sd = {"encoder." + k: v.detach().clone() for k, v in enc.state_dict().items()}
+    sd.update({"decoder." + k: v.detach().clone() for k, v in dec.state_dict().items()})
+    return sd
+
+
+class Decoder:
+    """``Decoder(state_dict)(latents)`` == ``Autoencoder().decoder(latents)``, latents ``(N,128)`` fp32 on the GPU ->
+    reconstructions ``(N,3,96,96)``."""
+
+    def __init__(self, state_dict, device: int = 0):
+        self.lib = _lib.load()
+        if not torch.cuda.is_available():
+            raise RuntimeError("Decoder needs a visible MI355X (HIP device); there is no CPU fallback")
+        sd = {k: state_dict[k] for k in DECODER_KEYS}
+        for k, shp in DECODER_SHAPES.items():
+            if tuple(sd[k].shape) != shp:
+                raise ValueError(f"decoder tensor {k}: shape {tuple(sd[k].shape)}, expected {shp}")
+        self.device = torch.device("cuda", device)
+        blob, idx = pack_state_dict(sd)
+        self._index = [(e.name.decode(), int(e.offset), tuple(e.shape[d] for d in range(e.ndim))) for e in idx]
+        self._blob = blob                      # host values at creation; the device copy below follows updates
+        self._n_floats = int(blob.size)
+        self._flat = None                      # flat_parameter()
+        self._grad = None                      # flat gradient of the last backward
+        self._pending = None                   # (latents, target) of the pending train_loss
+        self.recon = None                      # reconstruction of the last train_loss
+        h = ctypes.c_void_p()
+        _lib.check(self.lib.spdm_decoder_create(device, blob.ctypes.data_as(ctypes.c_void_p), blob.size, idx, len(idx),
+                                                ctypes.byref(h)), "spdm_decoder_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.spdm_decoder_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def eval(self):
+        return self
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _latents(self, latents: torch.Tensor) -> torch.Tensor:
+        if latents.dim() != 2 or latents.shape[1] != LATENT_DIM:
+            raise ValueError(f"expected (N,{LATENT_DIM}) latents, got {tuple(latents.shape)}")
+        return latents.detach().to(self.device, torch.float32).contiguous()
+
+    def __call__(self, latents: torch.Tensor) -> torch.Tensor:
+        z = self._latents(latents)
+        out = torch.empty(z.shape[0], *FRAME, device=self.device, dtype=torch.float32)
+        if z.shape[0] == 0:
+            return out
+        _lib.check(self.lib.spdm_decoder_forward(self._h, z.shape[0], ctypes.c_void_p(z.data_ptr()),
+                                                 ctypes.c_void_p(out.data_ptr()), self._stream()), "spdm_decoder_forward")
+        return out
+
+    def train_loss(self, latents: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        """``MSELoss(decoder(latents), target)`` as a device scalar, with the activations kept for ONE following
+        ``backward``.  ``self.recon`` is the reconstruction, ``__call__``'s bit for bit."""
+        z = self._latents(latents)
+        if z.shape[0] == 0 or tuple(target.shape) != (z.shape[0], *FRAME):
+            raise ValueError(f"expected N > 0 latents and (N,3,96,96) targets, got {tuple(z.shape)} and {tuple(target.shape)}")
+        t = target.detach().to(self.device, torch.float32).contiguous()
+        recon = torch.empty_like(t)
+        loss = torch.empty((), device=self.device, dtype=torch.float32)
+        _lib.check(self.lib.spdm_decoder_train_loss(self._h, z.shape[0], ctypes.c_void_p(z.data_ptr()), ctypes.c_void_p(t.data_ptr()),
+                                                    ctypes.c_void_p(recon.data_ptr()), ctypes.c_void_p(loss.data_ptr()),
+                                                    self._stream()), "spdm_decoder_train_loss")
+        self._pending = (z, t)
+        self.recon = recon
+        return loss
+
+    def backward(self):
+        """``(flat_grad, grad_latent)`` of the pending ``train_loss``: d loss / d parameters as ONE flat tensor in the
+        packed layout (``grads()`` are views of it) and d loss / d latents ``(N,128)``, what ``VisionEncoder.backward``
+        takes.  Sets ``flat_parameter().grad``."""
+        if self._pending is None:              # (the library answers SPDM_ERR_STATE; pass valid pointers to reach that answer)
+            z = torch.zeros(1, LATENT_DIM, device=self.device)
+            t = torch.zeros(1, *FRAME, device=self.device)
+        else:
+            z, t = self._pending
+        flat = torch.empty(self._n_floats, device=self.device, dtype=torch.float32)
+        gl = torch.empty(z.shape[0], LATENT_DIM, device=self.device, dtype=torch.float32)
+        _lib.check(self.lib.spdm_decoder_backward(self._h, z.shape[0], ctypes.c_void_p(z.data_ptr()), ctypes.c_void_p(t.data_ptr()),
+                                                  ctypes.c_void_p(flat.data_ptr()), ctypes.c_void_p(gl.data_ptr()), self._stream()),
+                   "spdm_decoder_backward")
+        self._pending = None
+        self._grad = flat
+        if self._flat is not None:
+            self._flat.grad = flat
+        return flat, gl
+
+    def grads(self):
+        """state_dict name -> gradient of the last ``backward`` (torch layout, views of the flat gradient)."""
+        if self._grad is None:
+            raise RuntimeError("no gradients: call train_loss and backward first")
+        return {name: self._grad[off:off + int(torch.Size(shape).numel())].view(shape) for name, off, shape in self._index}
+
+    def flat_parameter(self) -> torch.nn.Parameter:
+        """The weights as ONE device parameter in the packed layout (see ``VisionEncoder.flat_parameter``)."""
+        if self._flat is None:
+            self._flat = torch.nn.Parameter(torch.from_numpy(self._blob).to(self.device))
+        return self._flat
+
+    def update_weights(self, dev_blob: torch.Tensor) -> None:
+        """Put new values (a device blob in the packed layout, e.g. ``flat_parameter().detach()``) into the handle in
+        place; a pending ``train_loss`` is dropped."""
+        b = dev_blob.detach()
+        if b.device != self.device or b.dtype != torch.float32 or not b.is_contiguous() or b.numel() != self._n_floats:
+            raise ValueError(f"expected a contiguous fp32 blob of {self._n_floats} floats on {self.device}")
+        _lib.check(self.lib.spdm_decoder_update_weights(self._h, ctypes.c_void_p(b.data_ptr()), b.numel(), self._stream()),
+                   "spdm_decoder_update_weights")
+        self._pending = None
+        if self._flat is None:
+            self._blob = b.cpu().numpy()
+        elif b.data_ptr() != self._flat.data_ptr():      # values from elsewhere: the parameter follows the handle
+            with torch.no_grad():
+                self._flat.copy_(b)
+
+    def state_dict(self):
+        """Current values under the nn.Sequential's key names (host tensors)."""
+        host = self._flat.detach().cpu().numpy() if self._flat is not None else self._blob
+        return {name: torch.from_numpy(host[off:off + int(torch.Size(shape).numel())].reshape(shape).copy())
+                for name, off, shape in self._index}
+
+
+class autoencoder:
+    """The reference's LightningModule surface (models/encoder/autoencoder.py:40-83) over the two HIP handles.
+
+    ``state_dict``: an autoencoder checkpoint's (``encoder.N.*`` / ``model.encoder.N.*`` and the decoder's likewise) or
+    None for torch's default initialisation of these layers."""
+
+    def __init__(self, learning_rate: float = 1e-3, state_dict=None, device: int = 0):
+        self.lr = learning_rate
+        sd = _default_init() if state_dict is None else state_dict
+        enc_sd, dec_sd = encoder_state_dict_from(sd, "encoder."), decoder_state_dict_from(sd)
+        if enc_sd is None or dec_sd is None:
+            raise ValueError("state_dict holds no autoencoder: expected encoder.N.* (0, 2, 4, 7) and decoder.N.* (0, 2, 4, 6)")
+        self.encoder = VisionEncoder(enc_sd, device=device)
+        self.decoder = Decoder(dec_sd, device=device)
+        self.device = self.decoder.device
+
+    @classmethod
+    def load_from_checkpoint(cls, checkpoint_path, learning_rate: float = 1e-3, device: int = 0):
+        """From a Lightning ``.ckpt`` of the reference's ``autoencoder`` (or a bare state_dict file), read with
+        ``torch.load(weights_only=True)`` only."""
+        return cls(learning_rate, safe_load_state_dict(str(checkpoint_path)), device)
+
+    def close(self):
+        self.encoder.close()
+        self.decoder.close()
+
+    def eval(self):
+        return self
+
+    # ==================== Forward (Autoencoder.forward, :34-37) ====================
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.decoder(self.encoder(x))
+
+    __call__ = forward
+
+    # ==================== Training (:55-71) ====================
+    def training_step(self, batch: torch.Tensor, batch_idx: int = 0, *, backward: bool = False) -> torch.Tensor:
+        """``MSELoss(decoder(encoder(batch)), batch)`` as a device scalar.  ``backward=True`` also backpropagates: the
+        gradients are then in ``encoder.grads()`` / ``decoder.grads()`` and on both flat parameters' ``.grad``."""
+        x = batch.detach().to(self.device, torch.float32).contiguous()
+        if not backward:
+            return self.decoder.train_loss(self.encoder(x), x)
+        self._params()                          # (the flat parameters exist before the backward passes: both get their .grad)
+        loss = self.decoder.train_loss(self.encoder.train_forward(x), x)
+        _, grad_latent = self.decoder.backward()
+        self.encoder.backward(grad_latent)
+        return loss
+
+    def validation_step(self, batch: torch.Tensor, batch_idx: int = 0) -> torch.Tensor:
+        return self.training_step(batch, batch_idx)
+
+    # ==================== Optimisation (:73-83, train_autoencoder.py) ====================
+    def _params(self):
+        return [self.encoder.flat_parameter(), self.decoder.flat_parameter()]
+
+    def configure_optimizers(self):
+        """Adam(lr) over the two flat device parameters -- Adam is elementwise, so this is ``Adam(self.parameters())`` --
+        and ReduceLROnPlateau('min', patience=5) on ``val_loss``, in Lightning's dict shape."""
+        optimizer = torch.optim.Adam(self._params(), lr=self.lr)
+        scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, "min", patience=5)
+        return {
+            "optimizer": optimizer,
+            "lr_scheduler": {
+                "scheduler": scheduler,
+                "monitor": "val_loss",
+                "frequency": 1
+            },
+        }
+
+    def optimizer_step(self, optimizer, gradient_clip_val: Optional[float] = 0.5) -> None:
+        """One optimiser step after ``training_step(backward=True)``: clip the global gradient norm over both halves
+        (Lightning's ``gradient_clip_val``, 0.5 in train_autoencoder.py), ``optimizer.step()``, then put the new weights
+        into both handles in place."""
+        params = self._params()
+        if gradient_clip_val:
+            torch.nn.utils.clip_grad_norm_(params, gradient_clip_val)
+        optimizer.step()
+        self.encoder.update_weights(params[0].detach())
+        self.decoder.update_weights(params[1].detach())
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        """The Lightning checkpoint's keys: ``model.encoder.N.*`` / ``model.decoder.N.*`` and the aliases
+        ``encoder.N.*`` / ``decoder.N.*`` (:49-51 registers the same modules twice).  ``Diffusion_DDPM(...,
+        vision_encoder_state_dict=...)`` accepts it as it is."""
+        out = {}
+        for pre in ("model.", ""):
+            out.update({f"{pre}encoder.{k}": v for k, v in self.encoder.state_dict().items()})
+            out.update({f"{pre}decoder.{k}": v for k, v in self.decoder.state_dict().items()})
+        return out
+
+
+__all__ = ["DECODER_KEYS", "DECODER_SHAPES", "ENCODER_KEYS", "Decoder", "autoencoder", "decoder_state_dict_from"]

@@ -231,6 +231,36 @@ int encoder_conv1_wgrad_blocks(int n_images);
 hipError_t launch_encoder_conv1_wgrad(const float* img, const float* dx2, const float* x2, int n_images, float* part,
                                       float* dw, float* db, hipStream_t s);
 hipError_t launch_add(const float* src, size_t n, float* dst, hipStream_t s);               // dst += src
+// decoder.hip: the autoencoder's decoder (models/encoder/autoencoder.py:23-32) and its reconstruction training.
+// Row layouts, channels-last: h0 [n*144][64] (the Linear's output, column q*64 + c of its [n][9216] rows), a1 [n*576][32] with row
+// (n*144 + q)*4 + kk1, a2 [n*2304][16] with row r2*4 + kk2; weights w2 [64][4][32], w4 [32][4][16], w6 [16][4][3] = [ci][kk][co].
+// the three transposed convolutions + ReLU / sigmoid of n frames -> recon (n,3,96,96)
+hipError_t launch_decoder_convs(const float* h0, const float* w2, const float* b2, const float* w4, const float* b4,
+                                const float* w6, const float* b6, float* recon, int n_frames, hipStream_t s);
+// ... bit for bit the same reconstruction, which also keeps a1, a2 and sq[frame] = sum (recon - target)^2
+hipError_t launch_decoder_train_convs(const float* h0, const float* w2, const float* b2, const float* w4, const float* b4,
+                                      const float* w6, const float* b6, float* recon, const float* target, float* a1, float* a2,
+                                      double* sq, int n_frames, hipStream_t s);
+// the Linear and the two ReLU layers again in float64 from the latents (w0 / b0: the Linear in its kernel layout, rows q*64 + c);
+// a saved value (a1, a2) on the other side of its ReLU kink is rewritten so that "saved > 0" is the exact network's mask
+hipError_t launch_decoder_kinks(const float* latent, const float* w0, const float* b0, const float* w2, const float* b2,
+                                const float* w4, const float* b4, float* a1, float* a2, int n_frames, hipStream_t s);
+// loss = sum_frames sq / (n 27648), fixed order
+hipError_t launch_decoder_loss(const double* sq, int n_frames, float* loss, hipStream_t s);
+// layer 6 backwards: dw (16,3,2,2) and db (3) of these frames, dz4 [n*576][64] (column kk2*16 + co) under a2's ReLU mask;
+// scale = 2 / (N 27648) with N the frames of the whole loss; part: [n_frames][208]
+hipError_t launch_decoder_bwd6(const float* recon, const float* target, const float* a2, const float* w6, float scale,
+                               int n_frames, float* dz4, float* part, float* dw, float* db, hipStream_t s);
+// dz2 [n*576][32] = dz4 w4^T under a1's ReLU mask
+hipError_t launch_decoder_dgrad4(const float* dz4, const float* a1, const float* w4, int n_frames, float* dz2, hipStream_t s);
+// two-level column sum of src [M][C] (C % 64 == 0); fold 4: dst[co] = sum_kk column kk*n_out + co (n_out = C / 4); fold 1: the
+// Linear's 9216 columns q*64 + c back to Flatten order c*144 + q.  part: [decoder_colsum_slabs(M)][C]
+int decoder_colsum_slab_rows(long long M);
+int decoder_colsum_slabs(long long M);
+hipError_t launch_decoder_colsum(const float* src, int C, long long M, int n_out, int fold, float* part, float* dst, hipStream_t s);
+// weight gradients back in torch layout: [cin][kk*cout + co] -> (cin, cout, 2, 2); [q*64 + c][128] -> (9216, 128)
+hipError_t launch_decoder_unperm_conv(const float* src, int cin, int cout, float* dst, hipStream_t s);
+hipError_t launch_decoder_unperm_linear(const float* src, float* dst, hipStream_t s);
 // plain GN apply (materialise): y = GN(x)
 hipError_t launch_gn_apply(const AffineSrc& src, float* dst, int B, int HW, hipStream_t s);
 hipError_t launch_layernorm(const float* x, const float* g, const float* b, float* y, int rows, int C,

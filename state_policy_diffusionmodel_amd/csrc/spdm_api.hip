@@ -3235,6 +3235,273 @@ extern "C" int spdm_encoder_update_weights(spdm_encoder* e, const float* d_blob,
     return SPDM_OK;
 }
 
+// -------------------------------------------------------------------------------------------------
+// The autoencoder's decoder and its reconstruction training: Autoencoder.decoder of
+// models/encoder/autoencoder.py:23-32 under MSELoss(recon, batch) (:48,55-58).  Kernels and row layouts: decoder.hip.
+struct spdm_decoder {
+    int device = 0;
+    // kernel-layout copies (WeightTable): the Linear with its rows in channels-last order q*64 + c, the transposed
+    // convolutions as [ci][kk][co] -- which is also what their data gradients read -- and the biases
+    float *w0 = nullptr, *b0 = nullptr, *w2 = nullptr, *b2 = nullptr, *w4 = nullptr, *b4 = nullptr, *w6 = nullptr, *b6 = nullptr;
+    float* h0 = nullptr;              // [chunk][9216] the Linear's output of the chunk in flight (spdm_decoder_forward)
+    int chunk = 0;
+    std::vector<void*> owned;
+    WeightTable wt;
+    long long off[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // blob offset of 0.weight 0.bias 2.* 4.* 6.* (the index given to create)
+    size_t numel[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    size_t blob_floats = 0;
+    // ---- training (nothing below is allocated by a handle that never trains) ----
+    float* w0g = nullptr;             // [128][9216 as q*64 + c]: the weights of d loss / d latent
+    float *sv_h0 = nullptr, *sv_a1 = nullptr, *sv_a2 = nullptr, *sv_recon = nullptr;   // saved maps of ALL frames
+    double* sv_sq = nullptr;          // per-frame sums of squared errors
+    int sv_cap = 0, sv_n = 0;         // frames they hold room for / frames of the train_loss awaiting its backward
+    float *bw_dz4 = nullptr, *bw_dz2 = nullptr, *bw_dh0 = nullptr;     // backward scratch of one chunk
+    int bw_cap = 0;
+    float *wg_part = nullptr, *wg_tmp = nullptr, *cs_part = nullptr, *w6_part = nullptr, *g_tmp = nullptr;
+};
+static constexpr int DEC_FEAT = 64 * 12 * 12, DEC_LATENT = 128, DEC_PIX = 3 * 96 * 96;
+static constexpr int DEC_A1 = 576 * 32, DEC_A2 = 2304 * 16;       // floats per frame of the two post-ReLU maps
+static constexpr size_t DEC_WG_FLOATS = (size_t)8 * DEC_LATENT * DEC_FEAT;     // launch_wgrad's partial slabs (0.weight: <= 7)
+// launch_wgrad cuts the rows of a thin layer into as many slabs as its budget holds, down to 64 rows each, and one thread per
+// weight then adds them; 256 slabs (one per compute unit) keep that sum short
+static constexpr size_t DEC_WG_SLABS = 256;
+
+// nn.Sequential indices of Autoencoder.decoder: 0 = Linear; 2, 4, 6 = ConvTranspose2d (in, out, kH, kW)
+static const struct { const char* name; std::vector<int> shape; } DEC_ITEMS[8] = {
+    {"0.weight", {DEC_FEAT, DEC_LATENT}}, {"0.bias", {DEC_FEAT}}, {"2.weight", {64, 32, 2, 2}}, {"2.bias", {32}},
+    {"4.weight", {32, 16, 2, 2}}, {"4.bias", {16}}, {"6.weight", {16, 3, 2, 2}}, {"6.bias", {3}}};
+
+// (cin, cout, 2, 2) at src as [ci][kk][co]
+static WeightCopy convt_copy(long long src, int cin, int cout) {
+    WeightCopy c = Recorder::dense(src, cin, 4, cout);
+    c.stride[0] = (long long)cout * 4; c.stride[1] = 1; c.stride[2] = 4;
+    return c;
+}
+
+extern "C" void spdm_decoder_destroy(spdm_decoder* d) {
+    if (!d) return;
+    (void)hipSetDevice(d->device);
+    for (void* p : d->owned) (void)hipFree(p);
+    delete d;
+}
+
+extern "C" int spdm_decoder_create(int32_t device, const float* blob, size_t n, const spdm_tensor_index* index, int32_t n_index,
+                                   spdm_decoder** out) {
+    if (!blob || !index || n_index <= 0 || !out) return fail(SPDM_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(device));
+    spdm_decoder* d = new spdm_decoder();
+    d->device = device;
+    d->blob_floats = n;
+    Recorder R(d->wt, n, index, n_index);
+    R.plan = false;                        // fp32 copies only
+    bool ok = true;
+    for (int k = 0; k < 8 && ok; ++k) {
+        const long long off = R.at(DEC_ITEMS[k].name, DEC_ITEMS[k].shape);
+        if (off < 0) { ok = false; break; }
+        d->off[k] = off;
+        d->numel[k] = 1;
+        for (int v : DEC_ITEMS[k].shape) d->numel[k] *= (size_t)v;
+    }
+    if (ok) {
+        // Linear (9216, 128): row c*144 + q -> row q*64 + c, the bias likewise
+        WeightCopy w0 = Recorder::dense(d->off[0], 144, 64, DEC_LATENT);
+        w0.stride[0] = DEC_LATENT; w0.stride[1] = (long long)144 * DEC_LATENT; w0.stride[2] = 1;
+        WeightCopy b0 = Recorder::dense(d->off[1], 1, 144, 64);
+        b0.stride[1] = 1; b0.stride[2] = 144;
+        d->w0 = R.f32(w0);
+        d->b0 = R.f32(b0);
+        d->w2 = R.f32(convt_copy(d->off[2], 64, 32));
+        d->b2 = R.f32(Recorder::dense(d->off[3], 1, 1, 32));
+        d->w4 = R.f32(convt_copy(d->off[4], 32, 16));
+        d->b4 = R.f32(Recorder::dense(d->off[5], 1, 1, 16));
+        d->w6 = R.f32(convt_copy(d->off[6], 16, 3));
+        d->b6 = R.f32(Recorder::dense(d->off[7], 1, 1, 3));
+    }
+    DevBlob db;
+    int rc = R.err;
+    if (rc == SPDM_OK) rc = db.upload(blob, n);
+    if (rc == SPDM_OK) rc = R.finish(db.p);
+    if (rc != SPDM_OK) {
+        spdm_decoder_destroy(d);
+        return rc == SPDM_ERR_MISSING ? SPDM_ERR_INVALID : rc;      // (a decoder's eight names are its shape: one answer for both)
+    }
+    *out = d;
+    return SPDM_OK;
+}
+
+static int dec_alloc(spdm_decoder* d, float** p, size_t floats) {
+    void* q = nullptr;
+    if (hipMalloc(&q, floats * sizeof(float)) != hipSuccess) return fail(SPDM_ERR_NOMEM, "decoder workspace (%zu floats)", floats);
+    d->owned.push_back(q);
+    *p = (float*)q;
+    return SPDM_OK;
+}
+static void dec_release(spdm_decoder* d, float** p) {
+    if (!*p) return;
+    for (auto it = d->owned.begin(); it != d->owned.end(); ++it)
+        if (*it == (void*)*p) { d->owned.erase(it); break; }
+    (void)hipFree(*p);
+    *p = nullptr;
+}
+// h0 [m][9216] = latent W0^T + b0 on the exact fp32 MFMA path, columns in channels-last order
+static int dec_linear(spdm_decoder* d, const float* latent, int m, float* h0, hipStream_t s) {
+    const LinW lin{d->w0, nullptr, d->b0, DEC_LATENT, DEC_FEAT};
+    HIP_TRY(launch_gemm(linear_args(AffineSrc{latent, DEC_LATENT}, m, 0, lin, /*split=*/false, /*sw=*/0, EPI_BIAS, h0), s));
+    return SPDM_OK;
+}
+
+extern "C" int spdm_decoder_forward(spdm_decoder* d, int32_t n, const float* d_latent, float* d_recon, void* stream) {
+    if (!d || !d_latent || !d_recon || n <= 0) return fail(SPDM_ERR_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(d->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int chunk = std::min<int>(n, ENC_CHUNK);
+    if (d->chunk < chunk) {             // (grown lazily; the old buffer stays owned until destroy: at most two sizes ever exist)
+        SPDM_TRY(dec_alloc(d, &d->h0, (size_t)chunk * DEC_FEAT));
+        d->chunk = chunk;
+    }
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+        const int m = std::min(chunk, n - i0);
+        SPDM_TRY(dec_linear(d, d_latent + (size_t)i0 * DEC_LATENT, m, d->h0, s));
+        HIP_TRY(launch_decoder_convs(d->h0, d->w2, d->b2, d->w4, d->b4, d->w6, d->b6, d_recon + (size_t)i0 * DEC_PIX, m, s));
+    }
+    if (!stream) HIP_TRY(hipStreamSynchronize(s));
+    return SPDM_OK;
+}
+
+extern "C" int spdm_decoder_train_loss(spdm_decoder* d, int32_t n, const float* d_latent, const float* d_target, float* d_recon,
+                                       float* d_loss, void* stream) {
+    if (!d || !d_latent || !d_target || !d_loss || n <= 0) return fail(SPDM_ERR_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(d->device));
+    hipStream_t s = (hipStream_t)stream;
+    d->sv_n = 0;
+    if (!d->w0g) {
+        SPDM_TRY(dec_alloc(d, &d->wg_part, DEC_WG_FLOATS));
+        SPDM_TRY(dec_alloc(d, &d->wg_tmp, (size_t)DEC_FEAT * DEC_LATENT));
+        SPDM_TRY(dec_alloc(d, &d->cs_part, (size_t)decoder_colsum_slabs(ENC_CHUNK) * DEC_FEAT));      // (the widest: 0.bias)
+        SPDM_TRY(dec_alloc(d, &d->w6_part, (size_t)ENC_CHUNK * 208));
+        SPDM_TRY(dec_alloc(d, &d->g_tmp, d->blob_floats));
+        // d loss / d latent = dh0 W0 is the forward GEMM on [N = 128][K = 9216], k in h0's column order q*64 + c
+        Recorder R(d->wt, d->blob_floats);
+        R.plan = false;
+        WeightCopy g = Recorder::dense(d->off[0], DEC_LATENT, 144, 64);
+        g.stride[0] = 1; g.stride[1] = DEC_LATENT; g.stride[2] = (long long)144 * DEC_LATENT;
+        float* const w0g = R.f32(g);
+        SPDM_TRY(R.err);
+        SPDM_TRY(d->wt.upload(false));
+        // the handle keeps no blob: the weights go back to their blob offsets in g_tmp (scratch until a backward pass) through
+        // the inverse permutations, and laying that out again fills the new copy
+        float* const T = d->g_tmp;
+        HIP_TRY(launch_decoder_unperm_linear(d->w0, T + d->off[0], s));
+        HIP_TRY(launch_decoder_colsum(d->b0, DEC_FEAT, 1, DEC_FEAT, 1, d->cs_part, T + d->off[1], s));      // (one row: a permutation)
+        HIP_TRY(launch_decoder_unperm_conv(d->w2, 64, 32, T + d->off[2], s));
+        HIP_TRY(launch_decoder_unperm_conv(d->w4, 32, 16, T + d->off[4], s));
+        HIP_TRY(launch_decoder_unperm_conv(d->w6, 16, 3, T + d->off[6], s));
+        const float* const bias[3] = {d->b2, d->b4, d->b6};
+        for (int k = 0; k < 3; ++k)
+            HIP_TRY(hipMemcpyAsync(T + d->off[3 + 2 * k], bias[k], d->numel[3 + 2 * k] * sizeof(float), hipMemcpyDeviceToDevice, s));
+        SPDM_TRY(d->wt.relayout(T, s));
+        d->w0g = w0g;
+    }
+    if (d->sv_cap < n) {
+        HIP_TRY(hipDeviceSynchronize());      // (an earlier call's kernels may still read the buffers being replaced)
+        dec_release(d, &d->sv_h0); dec_release(d, &d->sv_a1); dec_release(d, &d->sv_a2); dec_release(d, &d->sv_recon);
+        dec_release(d, (float**)&d->sv_sq);
+        d->sv_cap = 0;
+        SPDM_TRY(dec_alloc(d, &d->sv_h0, (size_t)n * DEC_FEAT));
+        SPDM_TRY(dec_alloc(d, &d->sv_a1, (size_t)n * DEC_A1));
+        SPDM_TRY(dec_alloc(d, &d->sv_a2, (size_t)n * DEC_A2));
+        SPDM_TRY(dec_alloc(d, &d->sv_recon, (size_t)n * DEC_PIX));
+        SPDM_TRY(dec_alloc(d, (float**)&d->sv_sq, (size_t)n * 2));
+        d->sv_cap = n;
+    }
+    const int chunk = std::min<int>(n, ENC_CHUNK);
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+        const int m = std::min(chunk, n - i0);
+        float* h0 = d->sv_h0 + (size_t)i0 * DEC_FEAT;
+        SPDM_TRY(dec_linear(d, d_latent + (size_t)i0 * DEC_LATENT, m, h0, s));
+        HIP_TRY(launch_decoder_train_convs(h0, d->w2, d->b2, d->w4, d->b4, d->w6, d->b6, d->sv_recon + (size_t)i0 * DEC_PIX,
+                                           d_target + (size_t)i0 * DEC_PIX, d->sv_a1 + (size_t)i0 * DEC_A1,
+                                           d->sv_a2 + (size_t)i0 * DEC_A2, d->sv_sq + i0, m, s));
+        // the saved maps' ReLU masks from a float64 evaluation (the reconstruction and the loss stay the fp32 forward's)
+        HIP_TRY(launch_decoder_kinks(d_latent + (size_t)i0 * DEC_LATENT, d->w0, d->b0, d->w2, d->b2, d->w4, d->b4,
+                                     d->sv_a1 + (size_t)i0 * DEC_A1, d->sv_a2 + (size_t)i0 * DEC_A2, m, s));
+    }
+    HIP_TRY(launch_decoder_loss(d->sv_sq, n, d_loss, s));
+    if (d_recon) HIP_TRY(hipMemcpyAsync(d_recon, d->sv_recon, (size_t)n * DEC_PIX * sizeof(float), hipMemcpyDeviceToDevice, s));
+    d->sv_n = n;
+    if (!stream) HIP_TRY(hipStreamSynchronize(s));
+    return SPDM_OK;
+}
+
+extern "C" int spdm_decoder_backward(spdm_decoder* d, int32_t n, const float* d_latent, const float* d_target, float* d_grad,
+                                     float* d_grad_latent, void* stream) {
+    if (!d || !d_latent || !d_target || !d_grad || !d_grad_latent || n <= 0) return fail(SPDM_ERR_INVALID, "bad argument");
+    if (d->sv_n == 0) return fail(SPDM_ERR_STATE, "decoder_backward: no spdm_decoder_train_loss is pending");
+    if (d->sv_n != n) return fail(SPDM_ERR_STATE, "decoder_backward: %d frames, the pending train_loss had %d", n, d->sv_n);
+    HIP_TRY(hipSetDevice(d->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int chunk = std::min<int>(n, ENC_CHUNK);
+    if (d->bw_cap < chunk) {
+        HIP_TRY(hipDeviceSynchronize());
+        dec_release(d, &d->bw_dz4); dec_release(d, &d->bw_dz2); dec_release(d, &d->bw_dh0);
+        d->bw_cap = 0;
+        SPDM_TRY(dec_alloc(d, &d->bw_dz4, (size_t)chunk * DEC_A2));
+        SPDM_TRY(dec_alloc(d, &d->bw_dz2, (size_t)chunk * DEC_A1));
+        SPDM_TRY(dec_alloc(d, &d->bw_dh0, (size_t)chunk * DEC_FEAT));
+        d->bw_cap = chunk;
+    }
+    d->sv_n = 0;                               // the saved maps serve ONE backward
+    const float scale = (float)(2.0 / ((double)n * DEC_PIX));          // d mean((recon - target)^2) / d recon = scale (recon - target)
+    HIP_TRY(hipMemsetAsync(d_grad, 0, d->blob_floats * sizeof(float), s));
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+        const int m = std::min(chunk, n - i0);
+        float* G = i0 == 0 ? d_grad : d->g_tmp;           // a later chunk's gradient is added to the sum in chunk order
+        const float* lat = d_latent + (size_t)i0 * DEC_LATENT;
+        const float* h0 = d->sv_h0 + (size_t)i0 * DEC_FEAT;
+        const float* a1 = d->sv_a1 + (size_t)i0 * DEC_A1;
+        const float* a2 = d->sv_a2 + (size_t)i0 * DEC_A2;
+        const long long M1 = (long long)m * 144, M2 = (long long)m * 576;
+        // ---- ConvTranspose2d(16, 3) + Sigmoid + MSE: dz6 from recon and target, 6.weight / 6.bias, dz4 ----
+        HIP_TRY(launch_decoder_bwd6(d->sv_recon + (size_t)i0 * DEC_PIX, d_target + (size_t)i0 * DEC_PIX, a2, d->w6, scale, m,
+                                    d->bw_dz4, d->w6_part, G + d->off[6], G + d->off[7], s));
+        // ---- ConvTranspose2d(32, 16): rows r2, dz4 [M2][64], x = a1 [M2][32] ----
+        HIP_TRY(launch_wgrad(a1, 32, d->bw_dz4, 64, M2, 1, 1, 1, 32, 64, 0, d->wg_part, DEC_WG_SLABS * 32 * 64, d->wg_tmp, s));
+        HIP_TRY(launch_decoder_unperm_conv(d->wg_tmp, 32, 16, G + d->off[4], s));
+        HIP_TRY(launch_decoder_colsum(d->bw_dz4, 64, M2, 16, 4, d->cs_part, G + d->off[5], s));
+        HIP_TRY(launch_decoder_dgrad4(d->bw_dz4, a1, d->w4, m, d->bw_dz2, s));
+        // ---- ConvTranspose2d(64, 32): rows r1, dz2 [M1][128], x = h0 [M1][64] ----
+        HIP_TRY(launch_wgrad(h0, 64, d->bw_dz2, 128, M1, 1, 1, 1, 64, 128, 0, d->wg_part, DEC_WG_SLABS * 64 * 128, d->wg_tmp, s));
+        HIP_TRY(launch_decoder_unperm_conv(d->wg_tmp, 64, 32, G + d->off[2], s));
+        HIP_TRY(launch_decoder_colsum(d->bw_dz2, 128, M1, 32, 4, d->cs_part, G + d->off[3], s));
+        HIP_TRY(launch_gemm(gemm_args((int)M1, 0, 1, 1, 128, 64, 1, 0, 0, nullptr, PRO_NONE, AffineSrc{d->bw_dz2, 128}, 0, AffineSrc{},
+                                      d->w2, nullptr, d->bw_dh0, 64, EPI_PLAIN, nullptr), s));      // (no activation follows the Linear)
+        // ---- Linear(128, 9216): dh0 [m][9216] in channels-last columns ----
+        HIP_TRY(launch_wgrad(d->bw_dh0, DEC_FEAT, lat, DEC_LATENT, m, 1, 1, 1, DEC_FEAT, DEC_LATENT, 0, d->wg_part, DEC_WG_FLOATS,
+                             d->wg_tmp, s));
+        HIP_TRY(launch_decoder_unperm_linear(d->wg_tmp, G + d->off[0], s));
+        HIP_TRY(launch_decoder_colsum(d->bw_dh0, DEC_FEAT, m, DEC_FEAT, 1, d->cs_part, G + d->off[1], s));
+        HIP_TRY(launch_gemm(gemm_args(m, 0, 1, 1, DEC_FEAT, DEC_LATENT, 1, 0, 0, nullptr, PRO_NONE, AffineSrc{d->bw_dh0, DEC_FEAT}, 0,
+                                      AffineSrc{}, d->w0g, nullptr, d_grad_latent + (size_t)i0 * DEC_LATENT, DEC_LATENT, EPI_PLAIN,
+                                      nullptr), s));
+        if (i0 != 0) {
+            for (int k = 0; k < 8; ++k) HIP_TRY(launch_add(d->g_tmp + d->off[k], d->numel[k], d_grad + d->off[k], s));
+        }
+    }
+    if (!stream) HIP_TRY(hipStreamSynchronize(s));
+    return SPDM_OK;
+}
+
+extern "C" int spdm_decoder_update_weights(spdm_decoder* d, const float* d_blob, size_t n, void* stream) {
+    if (!d || !d_blob) return fail(SPDM_ERR_INVALID, "null argument");
+    if (n != d->blob_floats) return fail(SPDM_ERR_INVALID, "blob has %zu floats; the one given to spdm_decoder_create had %zu", n, d->blob_floats);
+    HIP_TRY(hipSetDevice(d->device));
+    hipStream_t s = (hipStream_t)stream;
+    d->sv_n = 0;                               // saved maps belong to the old weights
+    SPDM_TRY(d->wt.relayout(d_blob, s));
+    if (!stream) HIP_TRY(hipStreamSynchronize(s));
+    return SPDM_OK;
+}
+
 // Host-only introspection (no GPU): the launch geometry gemm_geometry picks for a statistics-epilogue convolution, plus the
 // statistics-slot reservation the plan makes for it (stats_slots_reserved, as Ctx::salloc).  tests/test_geometry.py checks the invariants between the
 // two on a grid of shapes (a mismatch is a silent wrong-statistics bug on the GPU).

@@ -193,6 +193,9 @@ class Diffusion_DDPM:
         # (N,3,96,96) -> (N,128) can be plugged in instead, or the batch may carry 'image_features'
         self.vision_encoder = vision_encoder
         self._vision_sd = vision_encoder_state_dict
+        if vision_encoder_state_dict is not None:     # ... or a whole autoencoder checkpoint's state_dict (autoencoder.state_dict())
+            from .vision import encoder_state_dict_from
+            self._vision_sd = encoder_state_dict_from(vision_encoder_state_dict) or vision_encoder_state_dict
         # train_vision_encoder: the reference's behaviour -- its encoder is a registered submodule, so Adam(self.parameters())
         # (:115-116) optimises it with the U-Net.  Off (this project's default) the encoder stays frozen.
         self.train_vision_encoder = bool(train_vision_encoder)
