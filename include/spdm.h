@@ -378,6 +378,48 @@ int  spdm_decoder_backward(spdm_decoder* d, int32_t n, const float* d_latent, co
 int  spdm_decoder_update_weights(spdm_decoder* d, const float* d_blob, size_t n_floats, void* stream);
 void spdm_decoder_destroy(spdm_decoder* d);
 
+/* The optimiser step on the device.  Replaces: configure_optimizers' torch.optim.Adam(self.parameters(),
+ * lr) (models/diffusion_ddpm.py:114-124; models/encoder/autoencoder.py:73-74) as Lightning steps it, preceded by the
+ * global-norm gradient clipping that train.py / train_autoencoder.py ask for with gradient_clip_val=0.5
+ * (torch.nn.utils.clip_grad_norm_).  Stateless: there is no handle; the moments are the caller's arrays (torch.optim.Adam's
+ * exp_avg / exp_avg_sq, so checkpoints interchange) and the step count is an argument.
+ *
+ * A segment is one flat fp32 device array of numel floats with its gradient and its two moments: the U-Net blob of
+ * spdm_train_loss_grad, the encoder's of spdm_encoder_backward, the decoder's of spdm_decoder_backward.  All four pointers
+ * must be 16-byte aligned.
+ *
+ * spdm_adam_workspace_doubles.  Pure host call: the doubles the caller provides as d_workspace (16-byte aligned, contents
+ * need not be initialised): one partial sum of g^2 per workgroup, then the gradient norm at spdm_adam_norm_index().
+ *
+ * spdm_adam_step.  One step over h_segments[0 .. n_segments) (a HOST array), enqueued on `stream` (NULL: the null stream,
+ * and the call synchronises).  `step` >= 1 is the count INCLUDING this step (state['step'] after torch's increment).
+ *  max_norm > 0: the norm of ALL segments' gradients together is taken in float64 -- per-workgroup partial sums over ranges
+ *    that depend on the segment sizes only, added in index order -- stored at d_workspace[spdm_adam_norm_index()], and every
+ *    gradient enters the update as g * coef with coef = min(1, max_norm / (norm + 1e-6)) evaluated in float64 and rounded once:
+ *    clip_grad_norm_'s semantics, a non-finite norm propagating as there.  d_grad itself is only read and is NOT rescaled
+ *    (clip_grad_norm_ rescales .grad in place).
+ *  max_norm <= 0: no clipping, one launch, the workspace is not written.
+ *  Then per element in fp32 (torch's Adam with amsgrad=False, weight_decay=0; each of the three right-hand sides ends in ONE
+ *  fused multiply-add, division and square root are correctly rounded):
+ *    m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2;
+ *    p = p - (lr / bc1) * (m / (sqrt(v) / sqrt(bc2) + eps)),   bc1 = 1 - beta1^step, bc2 = 1 - beta2^step,
+ *  with 1 - beta, lr / bc1 and sqrt(bc2) evaluated on the host in double and rounded once.  A beta is read as the shortest
+ *  decimal that rounds to the given float (0.999f is 0.999): 1 - beta would otherwise carry beta's own rounding, 1e-5
+ *  relative; and it multiplies m and v as an fp32 pair hi + lo, so that its rounding does not bias every step the same way.  d_param, d_exp_avg and d_exp_avg_sq are updated in place; an element with g = m = v = 0 keeps its bits (the
+ *  `pos_encoding.pos_encoding` slot of a simple_Unet.py blob).
+ * Deterministic: no atomics; two calls on the same inputs give bit-identical results.
+ * SPDM_ERR_INVALID, before the GPU is touched: a null pointer; n_segments outside 1 .. SPDM_OPTIM_MAX_SEGMENTS; numel == 0;
+ * step < 1; a pointer that is not 16-byte aligned; lr, eps or a beta that is not finite; a beta outside [0, 1); max_norm NaN.
+ *
+ * spdm_adam_norm_index.  Pure host call: the index (in doubles) of the gradient norm inside the workspace. */
+#define SPDM_OPTIM_MAX_SEGMENTS 4
+typedef struct { float* d_param; const float* d_grad; float* d_exp_avg; float* d_exp_avg_sq; uint64_t numel; } spdm_optim_segment;
+size_t spdm_adam_workspace_doubles(void);
+int  spdm_adam_step(int32_t device, const spdm_optim_segment* h_segments, int32_t n_segments, int64_t step,
+                    float lr, float beta1, float beta2, float eps, float max_norm,
+                    double* d_workspace, void* stream);
+size_t spdm_adam_norm_index(void);
+
 /* Host-only test hook (no GPU call): the launch geometry chosen for a split-precision 3x3 / 3x1 convolution with the
  * statistics epilogue -- out = {m_tile, n_tile, n_tiles, slots, ksplit, kernel, st_m_tile, st_n_tiles, reserved_slots,
  * combine_rows}; kernel: bit 0 = the small-grid kernel (conv_skinny.hip), bit 1 = the register-resident kernel (conv_reg.hip).

@@ -39,6 +39,12 @@ class SpdmOpGemmArgs(ctypes.Structure):
                  ("out", c_int32 * 10)])
 
 
+class SpdmOptimSegment(ctypes.Structure):
+    """spdm_optim_segment (include/spdm.h)."""
+    _fields_ = [("d_param", c_void_p), ("d_grad", c_void_p), ("d_exp_avg", c_void_p), ("d_exp_avg_sq", c_void_p),
+                ("numel", c_uint64)]
+
+
 class SpdmConfig(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("horizon", "state_dim", "cond_dim", "time_dim", "attention", "max_batch",
                                         "device", "num_train_timesteps", "flags")]
@@ -88,6 +94,10 @@ SYMBOLS = {
     "spdm_decoder_backward": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "spdm_decoder_update_weights": (c_int32, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "spdm_decoder_destroy": (None, [c_void_p]),
+    "spdm_adam_workspace_doubles": (c_size_t, []),
+    "spdm_adam_step": (c_int32, [c_int32, POINTER(SpdmOptimSegment), c_int32, c_int64, c_float, c_float, c_float, c_float, c_float,
+                                 c_void_p, c_void_p]),
+    "spdm_adam_norm_index": (c_size_t, []),
     "spdm_op_gelu": (c_int32, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "spdm_op_gemm": (c_int32, [POINTER(SpdmOpGemmArgs)]),
     "spdm_debug_geometry": (c_int32, [c_int32] * 6 + [ctypes.c_uint32, POINTER(c_int32 * 10)]),

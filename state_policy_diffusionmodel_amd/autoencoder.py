@@ -5,8 +5,8 @@ Mirror of models/encoder/autoencoder.py: ``Autoencoder`` (:7-37, encoder -> deco
 ``autoencoder`` (:40-83, ``MSELoss(recon, batch)``, Adam + ReduceLROnPlateau), which models/encoder/train_autoencoder.py
 trains with ``gradient_clip_val=0.5``.  The encoder half is ``vision.VisionEncoder``; ``Decoder`` here is
 ``Autoencoder.decoder`` (:23-32), an ``nn.Sequential`` whose state_dict keys are ``0.weight 0.bias 2.* 4.* 6.*``.  All
-compute is in libspdm_hip.so (``spdm_decoder_*``, csrc/decoder.hip); there is no CPU path here and the
-optimiser stays in torch.
+compute is in libspdm_hip.so (``spdm_decoder_*``, csrc/decoder.hip); there is no CPU path here; the
+optimiser is torch's or, ``configure_optimizers(device_optimizer=True)``, ``optim.DeviceAdam``.
 """
 from __future__ import annotations
 
@@ -230,10 +230,15 @@ class autoencoder:
     def _params(self):
         return [self.encoder.flat_parameter(), self.decoder.flat_parameter()]
 
-    def configure_optimizers(self):
+    def configure_optimizers(self, device_optimizer: bool = False):
         """Adam(lr) over the two flat device parameters -- Adam is elementwise, so this is ``Adam(self.parameters())`` --
-        and ReduceLROnPlateau('min', patience=5) on ``val_loss``, in Lightning's dict shape."""
-        optimizer = torch.optim.Adam(self._params(), lr=self.lr)
+        and ReduceLROnPlateau('min', patience=5) on ``val_loss``, in Lightning's dict shape.  ``device_optimizer=True``:
+        the same dict with ``optim.DeviceAdam`` (clip + Adam in HIP) in torch.optim.Adam's place."""
+        if device_optimizer:
+            from .optim import DeviceAdam
+            optimizer = DeviceAdam(self._params(), lr=self.lr)
+        else:
+            optimizer = torch.optim.Adam(self._params(), lr=self.lr)
         scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, "min", patience=5)
         return {
             "optimizer": optimizer,
@@ -249,6 +254,12 @@ class autoencoder:
         (Lightning's ``gradient_clip_val``, 0.5 in train_autoencoder.py), ``optimizer.step()``, then put the new weights
         into both handles in place."""
         params = self._params()
+        from .optim import DeviceAdam
+        if isinstance(optimizer, DeviceAdam):       # clip over both halves + Adam in two HIP launches
+            optimizer.step(max_norm=gradient_clip_val or None)
+            self.encoder.update_weights(params[0].detach())
+            self.decoder.update_weights(params[1].detach())
+            return
         if gradient_clip_val:
             torch.nn.utils.clip_grad_norm_(params, gradient_clip_val)
         optimizer.step()

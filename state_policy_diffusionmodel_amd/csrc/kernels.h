@@ -371,6 +371,25 @@ hipError_t launch_attn_fwd_lse(const float* qkv, float* out, float* lse, int B, 
 hipError_t launch_attn_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int B, int L,
                            int C, int heads, hipStream_t s);
 
+// ---- gradient clipping + Adam (optim.hip; spdm_adam_step) ------------------------------------------------
+// Workgroups of both launches, a compile-time constant: 4 per CU.  The workspace is ADAM_GRID fp64 partial sums of g^2
+// followed by the gradient norm.
+constexpr int ADAM_GRID = 1024;
+constexpr int OPTIM_MAX_SEGMENTS = 4;
+struct OptimSeg { float* p; const float* g; float* m; float* v; unsigned long long n; };     // flat fp32 arrays of n floats, 16-byte aligned
+struct OptimArgs {
+    OptimSeg seg[OPTIM_MAX_SEGMENTS];
+    int nseg;
+    int clip;                          // 1: the norm launch runs and the update scales g by min(1, max_norm / (norm + 1e-6))
+    float max_norm;
+    float beta1, beta1_lo, one_minus_beta1, beta2, beta2_lo, one_minus_beta2, eps;     // beta = hi + lo, 1 - beta rounded once from double
+    float step_size;                   // lr / (1 - beta1^step), evaluated in double
+    float bc2_sqrt;                    // sqrt(1 - beta2^step), evaluated in double
+    unsigned long long quads, per;     // filled by the launch: 4-float pieces of all segments, and pieces per workgroup
+};
+// one or two launches on s: [partial sums of g^2 ->] Adam on every segment in place; workspace: ADAM_GRID + 1 doubles
+hipError_t launch_adam_step(OptimArgs a, double* workspace, hipStream_t s);
+
 hipError_t launch_advance(int* step_dev, int* t_dev, const int* timesteps_dev, int n_steps, hipStream_t s);
 hipError_t launch_set_step(int* step_dev, int* t_dev, const int* timesteps_dev, int n_steps, int i, hipStream_t s);
 

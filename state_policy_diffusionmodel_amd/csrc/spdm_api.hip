@@ -3502,6 +3502,61 @@ extern "C" int spdm_decoder_update_weights(spdm_decoder* d, const float* d_blob,
     return SPDM_OK;
 }
 
+// -------------------------------------------------------------------------------------------------
+// Gradient clipping + Adam (include/spdm.h, optim.hip).  Stateless: the moments are the caller's arrays.
+extern "C" size_t spdm_adam_workspace_doubles(void) { return (size_t)ADAM_GRID + 1; }
+extern "C" size_t spdm_adam_norm_index(void) { return (size_t)ADAM_GRID; }
+
+// A beta arrives as a float, and 1 - (double)0.999f is 1.3e-5 away from 1 - 0.999 in relative terms: two hundred fp32 roundings
+// on every second moment.  So a beta is read as the shortest decimal that rounds to the given float (0.999f is 0.999), which
+// is what its caller wrote; a float with no short decimal comes back as itself to nine digits.
+static double beta_as_written(float b) {
+    char buf[40];
+    for (int prec = 1; prec <= 9; ++prec) {
+        snprintf(buf, sizeof(buf), "%.*g", prec, (double)b);
+        const double d = strtod(buf, nullptr);
+        if ((float)d == b) return d;
+    }
+    return (double)b;
+}
+
+extern "C" int spdm_adam_step(int32_t device, const spdm_optim_segment* h_segments, int32_t n_segments, int64_t step, float lr,
+                              float beta1, float beta2, float eps, float max_norm, double* d_workspace, void* stream) {
+    if (!h_segments || !d_workspace) return fail(SPDM_ERR_INVALID, "adam_step: null argument");
+    if (n_segments < 1 || n_segments > SPDM_OPTIM_MAX_SEGMENTS)
+        return fail(SPDM_ERR_INVALID, "adam_step: %d segments (1 .. %d)", n_segments, SPDM_OPTIM_MAX_SEGMENTS);
+    if (step < 1) return fail(SPDM_ERR_INVALID, "adam_step: step %lld (the count including this step, >= 1)", (long long)step);
+    if (!std::isfinite(lr) || !std::isfinite(eps) || !std::isfinite(beta1) || !std::isfinite(beta2))
+        return fail(SPDM_ERR_INVALID, "adam_step: lr, eps and the betas must be finite");
+    if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f))
+        return fail(SPDM_ERR_INVALID, "adam_step: betas (%g, %g) outside [0, 1)", (double)beta1, (double)beta2);
+    if (std::isnan(max_norm)) return fail(SPDM_ERR_INVALID, "adam_step: max_norm is NaN");
+    if ((uintptr_t)d_workspace % 16) return fail(SPDM_ERR_INVALID, "adam_step: d_workspace is not 16-byte aligned");
+    OptimArgs a = {};
+    for (int i = 0; i < n_segments; ++i) {
+        const spdm_optim_segment& g = h_segments[i];
+        if (!g.d_param || !g.d_grad || !g.d_exp_avg || !g.d_exp_avg_sq) return fail(SPDM_ERR_INVALID, "adam_step: segment %d: null pointer", i);
+        if (g.numel == 0) return fail(SPDM_ERR_INVALID, "adam_step: segment %d is empty", i);
+        if (((uintptr_t)g.d_param | (uintptr_t)g.d_grad | (uintptr_t)g.d_exp_avg | (uintptr_t)g.d_exp_avg_sq) % 16)
+            return fail(SPDM_ERR_INVALID, "adam_step: segment %d: a pointer is not 16-byte aligned", i);
+        a.seg[i] = {g.d_param, g.d_grad, g.d_exp_avg, g.d_exp_avg_sq, (unsigned long long)g.numel};
+    }
+    const double b1 = beta_as_written(beta1), b2 = beta_as_written(beta2);
+    const double bc1 = 1.0 - std::pow(b1, (double)step), bc2 = 1.0 - std::pow(b2, (double)step);
+    a.nseg = n_segments;
+    a.clip = max_norm > 0.f;
+    a.max_norm = max_norm;
+    a.beta1 = (float)b1;  a.beta1_lo = (float)(b1 - (double)a.beta1);  a.one_minus_beta1 = (float)(1.0 - b1);
+    a.beta2 = (float)b2;  a.beta2_lo = (float)(b2 - (double)a.beta2);  a.one_minus_beta2 = (float)(1.0 - b2);
+    a.eps = eps;
+    a.step_size = (float)((double)lr / bc1);
+    a.bc2_sqrt = (float)std::sqrt(bc2);
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(launch_adam_step(a, d_workspace, (hipStream_t)stream));
+    if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));
+    return SPDM_OK;
+}
+
 // Host-only introspection (no GPU): the launch geometry gemm_geometry picks for a statistics-epilogue convolution, plus the
 // statistics-slot reservation the plan makes for it (stats_slots_reserved, as Ctx::salloc).  tests/test_geometry.py checks the invariants between the
 // two on a grid of shapes (a mismatch is a silent wrong-statistics bug on the GPU).

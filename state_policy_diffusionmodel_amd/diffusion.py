@@ -12,7 +12,7 @@ types -- so ``generate.py``'s idiom
     history = model.sample(batch=obs, option='sample_history')            # generate.py:73-76
 
 works unchanged.  What runs underneath is libspdm_hip.so (no torch compute in the loop).
-The optimiser, validation plots and the Lightning plumbing are out of scope.
+Validation plots and the Lightning plumbing are out of scope.
 
 All three noise predictors of ``__init__`` (models/diffusion_ddpm.py:53-62) run on that path: ``model='UNet_Film'``,
 ``'UNet_FilmnoAttention'``, and every other value -- the constructor's own default ``'UNet'`` -- for
@@ -22,7 +22,8 @@ the reference's ``training_step`` runs it with dropout p = 0.1, which ``training
 time_scale=mask)`` reproduces when the caller draws the mask (otherwise its forward half is the eval-mode network).
 ``training_step(..., backward=True)`` also computes the gradients, for ``'UNet_FilmnoAttention'``
 (``spdm_train_loss_grad``), for simple_Unet.py's ``'UNet'`` and -- constructed with
-``train_attention=True`` -- ``'UNet_Film'``; the optimiser stays in torch.  ``train_vision_encoder=True`` is the reference's
+``train_attention=True`` -- ``'UNet_Film'``; the optimiser is torch's, or -- ``configure_optimizers(device_optimizer=True)`` --
+``optim.DeviceAdam`` in HIP.  ``train_vision_encoder=True`` is the reference's
 joint training of the frame encoder (``Adam(self.parameters())``, :115-116): the step then also
 backpropagates into ``vision_encoder`` and the optimiser steps both.
 
@@ -509,14 +510,19 @@ class Diffusion_DDPM:
         return self.training_step(batch, batch_idx, **kw)
 
     # ==================== Optimisation (models/diffusion_ddpm.py:114-124, train.py) ====================
-    def configure_optimizers(self):
+    def configure_optimizers(self, device_optimizer: bool = False):
         """The reference's optimiser: Adam(lr) over the weights -- here the one flat device parameter
         (``noise_estimator.flat_parameter()``) -- and ReduceLROnPlateau('min', patience=5) on ``val_loss``, in
-        Lightning's dict shape."""
+        Lightning's dict shape.  ``device_optimizer=True``: the same dict with ``optim.DeviceAdam`` (clip + Adam in HIP,
+        DESIGN.md 8.8) over the same parameters in torch.optim.Adam's place; its state dicts load into Adam and back."""
         params = [self.noise_estimator.flat_parameter()]
         if self.train_vision_encoder:       # Adam is elementwise: one Adam over both flat parameters == Adam(self.parameters())
             params.append(self._trainable_encoder().flat_parameter())
-        optimizer = torch.optim.Adam(params, lr=self.lr)
+        if device_optimizer:
+            from .optim import DeviceAdam
+            optimizer = DeviceAdam(params, lr=self.lr)
+        else:
+            optimizer = torch.optim.Adam(params, lr=self.lr)
         scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, "min", patience=5)
         return {
             "optimizer": optimizer,
@@ -531,6 +537,13 @@ class Diffusion_DDPM:
         """One optimiser step after ``training_step(backward=True)``: clip the global gradient norm (Lightning's
         ``gradient_clip_val``, 0.5 in train.py), ``optimizer.step()``, then put the new weights into every cached engine
         in place (``SpdmEngine.update_weights``) -- no host round trip of the weights."""
+        from .optim import DeviceAdam
+        if isinstance(optimizer, DeviceAdam):       # clip (over all its parameters together) + Adam in two HIP launches
+            optimizer.step(max_norm=gradient_clip_val or None)
+            self.noise_estimator._push()
+            if self.train_vision_encoder:
+                self.vision_encoder.update_weights(self._trainable_encoder().flat_parameter().detach())
+            return
         params = [self.noise_estimator.flat_parameter()]
         if self.train_vision_encoder:       # Lightning clips the norm over ALL parameters together
             params.append(self._trainable_encoder().flat_parameter())

@@ -3,7 +3,9 @@
 512 frames: the HIP step -- autoencoder.training_step(backward=True) + optimizer_step (global-norm clip 0.5, Adam, both
 in-place weight updates) -- against torch-ROCm autograd of the same two nn.Sequentials with the same clip and Adam.  The
 two alternate on one device, each run synchronised; medians of 10.  Also the HIP step's parts (encoder forward, decoder
-loss, decoder backward, encoder backward, optimiser step), each synchronised, as shares of their sum.
+loss, decoder backward, encoder backward, optimiser step), each synchronised, as shares of their sum, and the optimiser step with both optimisers on
+the same gradients in the same run: torch's clip + Adam (optimizer_step_ms, the one in the parts) and optim.DeviceAdam
+(device_optimizer_step_ms), both including the two in-place weight updates.
 One JSON line per n.
 usage: python tools/bench_autoencoder.py [--iters N] [n ...]"""
 import json
@@ -46,6 +48,7 @@ def bench(n, iters):
     params = list(enc.parameters()) + list(dec.parameters())
     ref_opt = torch.optim.Adam(params, lr=1e-3)
     opt = ae.configure_optimizers()["optimizer"]
+    dopt = ae.configure_optimizers(device_optimizer=True)["optimizer"]       # optim.DeviceAdam over the same two parameters
     x = torch.rand(n, 3, 96, 96, generator=torch.Generator().manual_seed(n)).cuda()
 
     def hip():
@@ -67,18 +70,22 @@ def bench(n, iters):
             ms[fn].append(timed(fn))
     # the HIP step's parts, each synchronised (their sum exceeds the step by the extra synchronisations)
     parts = {k: [] for k in ("encoder_forward", "decoder_loss", "decoder_backward", "encoder_backward", "optimizer_step")}
-    for _ in range(iters):
+    dev_opt = []
+    for it in range(iters):
         state = {}
         parts["encoder_forward"].append(timed(lambda: state.update(z=ae.encoder.train_forward(x))))
         parts["decoder_loss"].append(timed(lambda: ae.decoder.train_loss(state["z"], x)))
         parts["decoder_backward"].append(timed(lambda: state.update(gl=ae.decoder.backward()[1])))
         parts["encoder_backward"].append(timed(lambda: ae.encoder.backward(state["gl"])))
-        parts["optimizer_step"].append(timed(lambda: ae.optimizer_step(opt, 0.5)))
+        # both optimisers on this step's gradients, in alternating order (each keeps its own moments)
+        for which in ((opt, dopt) if it % 2 == 0 else (dopt, opt)):
+            (parts["optimizer_step"] if which is opt else dev_opt).append(timed(lambda: ae.optimizer_step(which, 0.5)))
     med = {k: statistics.median(v) for k, v in parts.items()}
     total = sum(med.values())
     h, t = statistics.median(ms[hip]), statistics.median(ms[torch_rocm])
     ae.close()
     return {"n": n, "hip_step_ms": round(h, 3), "torch_rocm_step_ms": round(t, 3), "hip_over_torch": round(h / t, 2),
+            "optimizer_step_ms": round(med["optimizer_step"], 3), "device_optimizer_step_ms": round(statistics.median(dev_opt), 3),
             "parts_ms": {k: round(v, 3) for k, v in med.items()}, "parts_share": {k: round(v / total, 3) for k, v in med.items()}}
 
 

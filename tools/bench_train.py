@@ -5,7 +5,9 @@ CPU side: tests/simple_unet_ref.py) -- (H = 32, D = 3) at B = 16, 64, 256: the H
 forward, MSE loss, full backward), the ways an optimiser step's weights reach the handle -- a rebuild of the handle from a host
 state_dict (SpdmEngine.refresh_weights: handle creation + spdm_load_weights), the in-place update from a device flat tensor
 (SpdmEngine.update_weights, synchronised), and a whole optimiser step through the facade (Diffusion_DDPM.optimizer_step:
-gradient clip + Adam + update_weights) -- and torch-CPU fp32 autograd of the oracle on 16 threads for the same step
+gradient clip + Adam + update_weights) with torch's optimiser (optimizer_step_ms) and with optim.DeviceAdam
+(device_optimizer_step_ms; torch_clip_adam_ms / device_clip_adam_ms: the same two without the weight update; the four
+alternate in one run, medians) -- and torch-CPU fp32 autograd of the oracle on 16 threads for the same step
 (--no-cpu skips it).  --frames adds raw frames (obs_horizon 10: 10 B frames per step) and the jointly trained observation
 encoder: encoder_train_ms (VisionEncoder.train_forward + backward, synchronised), the same encoder's
 forward + backward through torch-ROCm autograd on an nn.Sequential (torch_encoder_ms; the two alternate, medians), and
@@ -156,19 +158,37 @@ def main():
                            state_dict=sd, max_batch=B, train_attention=attention,
                            **{k: extra.pop(k) for k in ("vision_encoder_state_dict", "train_vision_encoder") if k in extra})
         teng = m._train_engine_for(B, H, D)
+        # both optimisers over the SAME flat parameter(s), alternating (each keeps its own moments; the weights just wander):
+        # torch's clip_grad_norm_ + Adam and optim.DeviceAdam
         opt = m.configure_optimizers()["optimizer"]
+        dopt = m.configure_optimizers(device_optimizer=True)["optimizer"]
+        params = opt.param_groups[0]["params"]
         p = m.noise_estimator.flat_parameter()
-        opt_ms = []
-        for _ in range(max(5, iters)):
+
+        def set_grads():
             p.grad = teng.loss_and_grad(xd, t, cd, nd, flat=True)[2]
             if frames_opt:      # the joint step: the encoder's gradient is there too
                 m.vision_encoder.train_forward(frames)
                 m.vision_encoder.backward(cd.reshape(B, 10, 135)[..., -128:].reshape(-1, 128).contiguous() * 1e-4)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            m.optimizer_step(opt, 0.5)
-            torch.cuda.synchronize()
-            opt_ms.append((time.perf_counter() - t0) * 1e3)
+
+        def torch_only():
+            torch.nn.utils.clip_grad_norm_(params, 0.5)
+            opt.step()
+
+        arms = {"optimizer_step_ms": lambda: m.optimizer_step(opt, 0.5),               # clip + Adam + weight update(s)
+                "device_optimizer_step_ms": lambda: m.optimizer_step(dopt, 0.5),
+                "torch_clip_adam_ms": torch_only,                                        # ... without the weight update(s)
+                "device_clip_adam_ms": lambda: dopt.step(max_norm=0.5)}
+        opt_ms = {k: [] for k in arms}
+        for it in range(max(10, iters) + 2):
+            for k, fn in arms.items():
+                set_grads()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                if it >= 2:     # (two warm-up rounds)
+                    opt_ms[k].append((time.perf_counter() - t0) * 1e3)
         teng.close()
         cpu = float("nan") if no_cpu else cpu_step(sd, x, t, cond, noise, attention, simple)
         hip = statistics.median(step)
@@ -176,7 +196,7 @@ def main():
         print(json.dumps({"model": model, "B": B, "H": H, "D": D, "hip_step_ms": round(hip, 3), "hip_step_min_ms": round(min(step), 3),
                           "weight_refresh_ms": round(statistics.median(refresh), 2),
                           "weight_update_ms": round(statistics.median(update), 3),
-                          "optimizer_step_ms": round(statistics.median(opt_ms), 3), **extra, "device_bytes": ws,
+                          **{k: round(statistics.median(v), 3) for k, v in opt_ms.items()}, **extra, "device_bytes": ws,
                           "cpu_autograd_ms": None if no_cpu else round(cpu, 1), "cpu_threads": 16, "cpu_over_hip": None if no_cpu else round(cpu / hip, 1)}),
               flush=True)
 
