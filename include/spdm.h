@@ -427,6 +427,12 @@ size_t spdm_adam_norm_index(void);
 int  spdm_debug_geometry(int32_t M, int32_t N, int32_t K, int32_t HW, int32_t W, int32_t taps, uint32_t switches,
                          int32_t out[10]);
 
+/* Host-only test hook (no GPU call): how the launch of the most recent spdm_op_gemm call on this process staged its input
+ * slab -- 0: with halo rows (every kernel but conv_wide.hip's, its ragged or non-dividing tilings, SPDM_NO_WHOLE_TILES);
+ * 1: whole-sample tiles (the tile is a whole number of samples: no halo rows, no clamps); 2: the same with ONE sample per tile
+ * and a GroupNorm prologue (its statistics in scalar registers); -1: no spdm_op_gemm call has launched yet. */
+int  spdm_debug_whole_tiles(void);
+
 /* Op-level test hook: d_y = GELU(d_x) evaluated with the device erf that the conv prologues use
  * (nn.GELU(), models/Unet_FiLmLayer.py:104). */
 int  spdm_op_gelu(const float* d_x, float* d_y, size_t n, void* stream);

@@ -116,7 +116,14 @@ __device__ __forceinline__ f32x2 split2(float a, float b) {
 // G2 (experiment, opt-in SPDM_G2=1; see launch_conv_wide for the measurement): two 32-channel chunks per slab hand-over on the
 // 64-row-per-wave variants of the tap loop -- the loads of both chunks in flight together, one round trip and one barrier pair
 // per 64 channels.  Neutral to slower: the round trip is not what the hand-over costs.
-template <int NT, int PRO, bool W2, int RT, int WN, bool PIPE, bool TWO = false, int WP = 0, bool G2 = false>
+// WH (whole-sample tiles; host: M_T % HW == 0 and M % M_T == 0, launch_wide_sel): every tile holds whole samples, so the rows
+// above and below it belong to other samples and every tap that would reach them is masked (it reads the all-zero row).  The
+// slab is then the tile's own M_T rows: no halo, M_T / 32 staging passes instead of (M_T + 18 + 31) / 32 (8 for 9, 4 for 5), no
+// address clamp, no validity select, no dump row, and the sample of a staged row follows from its index (HW is a power of two:
+// it divides M_T) -- the packed tables avalid / abidx are not built.  WH == 2: HW == M_T, ONE sample per tile: its mean and
+// rstd sit in scalar registers and rs gamma is formed once per chunk instead of once per pass.  The arithmetic per element is
+// (v - mu) (rs gamma) + beta on the same operands either way: bit-identical to WH == 0 (tests/test_gpu_conv_whole_tiles.py).
+template <int NT, int PRO, bool W2, int RT, int WN, bool PIPE, bool TWO = false, int WP = 0, bool G2 = false, int WH = 0>
 // launch bound (256, 2): a 256-register budget.  The 8 x 2 variants with a prologue then carry 88-128 bytes of scratch per lane
 // (stats finalisation state parked across the main loop); with (256, 1) the compiler allocates 203-250 registers and no scratch,
 // but schedules the loop worse: measured 10.5 vs 9.6-9.9 ms per step (same box, alternating).  Keep 2.
@@ -131,7 +138,9 @@ __global__ __launch_bounds__(256, WIDE_MINB) void conv3x3_wide_kernel(const Gemm
     constexpr int NTHR = 256;
     constexpr int RP = NTHR / 8;
     constexpr int M_T = WM * RW, N_T = WN * NT * 32;
-    constexpr int APASS = (M_T + 18 + RP - 1) / RP;
+    constexpr bool WHOLE = (WH != 0);                      // whole-sample tiles: the slab is the tile itself
+    constexpr bool ONE = (WH == 2);                     // ... and the tile is one sample
+    constexpr int APASS = WHOLE ? M_T / RP : (M_T + 18 + RP - 1) / RP;
     constexpr int FAR = (W2 || WP) ? 4 : 3;             // A-fragment ring (row tiles)
     constexpr int FBR = (NT == 2) ? 2 : 3;              // B-fragment ring (phases)
     constexpr int PH = 3 * NT;                          // phases per kernel row (generic layout)
@@ -151,16 +160,19 @@ __global__ __launch_bounds__(256, WIDE_MINB) void conv3x3_wide_kernel(const Gemm
     // CONSECUTIVE LDS rows, and a tap (dh, dw) is the uniform shift dw NI8 + dh -- in the natural layout the stride-8 fragment
     // read would be 4-way bank-conflicted at any 16-byte-aligned pitch and the LDS array would become the bound.
     constexpr int NI8 = (M_T + 18 + 6) / 8 + 1;
+    // (WHOLE: class q % 8 = w, index q / 8.  NI8 stays 36: the eight rows a wave stages in one pass are NI8 LDS rows apart, and
+    //  36 x 36 floats = 16 banks mod 64 spreads them; 32 would put all eight on the same banks.)
     static_assert(!G2 || (NT == 2 && RT == 4 && !W2 && !PIPE && !WP && !WIDE_DB), "two chunks per hand-over: the plain tap loop, 64 rows per wave");
+    static_assert(!WHOLE || (!G2 && !WIDE_DB && !WIDE_EARLY), "whole-sample staging: not in the hand-over experiments");
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN, l16 = lane & 15, kg = lane >> 4;
     const int HW = a.HW, W = a.W, H = a.H, M = a.M, K = a.K, N = a.N;
-    const int halo = W + 1;
+    const int halo = WHOLE ? 0 : W + 1;
     const int QA = M_T + 2 * halo;
-    const int QZ = WP8 ? 8 * NI8 + 2 : QA + 2;  // + the all-zero row (masked taps read it) + a dump row
+    const int QZ = WP8 ? 8 * NI8 + 2 : QA + 2;  // + the all-zero row (masked taps read it) + a dump row (WHOLE: unused)
 
     // ---- tile of this workgroup (XCD-aware, bijective remap: the n-tiles of an m-tile share an XCD's L2) ----
     const int n_ntiles = N / N_T;
@@ -208,7 +220,13 @@ __global__ __launch_bounds__(256, WIDE_MINB) void conv3x3_wide_kernel(const Gemm
     constexpr bool pro = (PRO != PRO_NONE);
     constexpr bool pro_gelu = (PRO == PRO_GN_GELU);
     int bh_first = 0;
-    if (pro) {
+    float mu1 = 0.f, rs1 = 1.f;                 // ONE: the tile's sample, wave-uniform
+    const int lhw = WHOLE ? __builtin_ctz((unsigned)HW) : 0;
+    if constexpr (pro && ONE) {
+        sample_mean_rstd(a.pro_stats, m0 / HW, mu1, rs1);          // (every thread: the same few partials; no LDS table, no barrier)
+        mu1 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, mu1)));
+        rs1 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, rs1)));
+    } else if (pro) {
         const int lo = max(m0 - halo, 0), hi = min(m0 + M_T + halo, M) - 1;
         bh_first = lo / HW;
         const int bh_last = hi / HW;
@@ -227,7 +245,7 @@ __global__ __launch_bounds__(256, WIDE_MINB) void conv3x3_wide_kernel(const Gemm
     unsigned avalid = 0u;
     unsigned long long abidx = 0ull;
 #pragma unroll
-    for (int p = 0; p < APASS; ++p) {
+    for (int p = 0; p < (WHOLE ? 0 : APASS); ++p) {
         const int q = p * RP + srow_t;
         const int m = m0 - halo + q;
         const bool v = (q < QA) && (m >= 0) && (m < M);
@@ -247,7 +265,7 @@ __global__ __launch_bounds__(256, WIDE_MINB) void conv3x3_wide_kernel(const Gemm
 #define WIDE_ROWOFF(rt_) (W2 ? (((rt_) >> 1) * 32 + ((rt_) & 1)) : WP8 ? (rt_) : WP ? (((rt_) >> 2) * 64 + ((rt_) & 3)) : (rt_) * 16)
 #define WIDE_LDSOFF(rt_) (WP8 ? (rt_) * NI8 : WIDE_ROWOFF(rt_))      /* LDS row offset of row tile rt_ from the lane's base row */
     const int rowlane = W2 ? 2 * l16 : WP ? WP * l16 : PERM ? (l16 < 4 ? l16 : l16 < 12 ? l16 + 4 : l16 - 8) : l16;
-    const int aoff0 = WP8 ? (2 + wm * 16 + l16) * LDK + kg * 4 : (wm * RW + rowlane + halo) * LDK + kg * 4;
+    const int aoff0 = WP8 ? ((WHOLE ? 0 : 2) + wm * 16 + l16) * LDK + kg * 4 : (wm * RW + rowlane + halo) * LDK + kg * 4;
     const int zoff = zrow * LDK + kg * 4;
     unsigned am[(RT + 2) / 3] = {};
 #pragma unroll
@@ -301,7 +319,7 @@ __global__ __launch_bounds__(256, WIDE_MINB) void conv3x3_wide_kernel(const Gemm
         const float* ab_ = (first_ ? abase : abase1) + cc_ * CK;                                     \
         const int ld_ = first_ ? a.src_ld : a.skip_ld;                                               \
         _Pragma("unroll") for (int p_ = 0; p_ < APASS; ++p_) {                                      \
-            const int mc_ = min(max(m0 - halo + p_ * RP + srow_o, 0), M - 1);                        \
+            const int mc_ = WHOLE ? m0 + p_ * RP + srow_o : min(max(m0 - halo + p_ * RP + srow_o, 0), M - 1); \
             areg_[p_] = *reinterpret_cast<const f32x4*>(ab_ + (size_t)mc_ * ld_);                     \
         }                                                                                            \
         if (pro) {                                                                                   \
@@ -309,30 +327,39 @@ __global__ __launch_bounds__(256, WIDE_MINB) void conv3x3_wide_kernel(const Gemm
             g4r_ = *reinterpret_cast<const f32x4*>(a.pro_gamma + cc_ * CK + c4 * 4);                  \
             b4r_ = *reinterpret_cast<const f32x4*>(a.pro_beta + cc_ * CK + c4 * 4);                   \
             if (TWO && first_) { g4r_ = f32x4{1.f, 1.f, 1.f, 1.f}; b4r_ = f32x4{0.f, 0.f, 0.f, 0.f}; } \
+            else if (ONE) g4r_ = rs1 * g4r_;                        /* rs gamma, once per chunk */   \
         }                                                                                            \
     }
 #define WIDE_STAGE_A_(areg_, g4r_, b4r_, ident_, dst_)                                                                             \
     {                                                                                                \
         _Pragma("unroll") for (int p_ = 0; p_ < APASS; ++p_) {                                      \
             f32x4 v_ = areg_[p_];                                                                     \
-            if (pro) {                                                                               \
-                const int bi_ = (int)((abidx >> (BB * p_)) & ((1ull << BB) - 1));                                  \
+            if (pro && ONE) {                                        /* g4r_ already holds rs gamma */ \
+                const float mu_ = (TWO && ident_) ? 0.f : mu1;                                       \
+                v_.x = (v_.x - mu_) * g4r_.x + b4r_.x;                                                \
+                v_.y = (v_.y - mu_) * g4r_.y + b4r_.y;                                                \
+                v_.z = (v_.z - mu_) * g4r_.z + b4r_.z;                                                \
+                v_.w = (v_.w - mu_) * g4r_.w + b4r_.w;                                                \
+            } else if (pro) {                                                                        \
+                const int bi_ = WHOLE ? (p_ * RP + srow_o) >> lhw : (int)((abidx >> (BB * p_)) & ((1ull << BB) - 1)); \
                 float rs_ = srstd[bi_], mu_ = smean[bi_];                                            \
                 if (TWO && ident_) { rs_ = 1.f; mu_ = 0.f; }       /* (v - 0) (1 x 1) + 0 == v, bit for bit */ \
                 v_.x = (v_.x - mu_) * (rs_ * g4r_.x) + b4r_.x;                                         \
                 v_.y = (v_.y - mu_) * (rs_ * g4r_.y) + b4r_.y;                                         \
                 v_.z = (v_.z - mu_) * (rs_ * g4r_.z) + b4r_.z;                                         \
                 v_.w = (v_.w - mu_) * (rs_ * g4r_.w) + b4r_.w;                                         \
+            }                                                                                        \
+            if (pro) {                                                                               \
                 if (pro_gelu) {                                                                      \
                     v_.x = gelu_erf(v_.x); v_.y = gelu_erf(v_.y);                                    \
                     v_.z = gelu_erf(v_.z); v_.w = gelu_erf(v_.w);                                    \
                 }                                                                                    \
             }                                                                                        \
-            if (!((avalid >> p_) & 1u)) v_ = f32x4{0.f, 0.f, 0.f, 0.f};                              \
+            if (!WHOLE && !((avalid >> p_) & 1u)) v_ = f32x4{0.f, 0.f, 0.f, 0.f};                       \
             const f32x2 p0_ = split2(v_.x, v_.y), p1_ = split2(v_.z, v_.w);                          \
             {   /* rows past the slab go to a dump row: no branch (see the header) */                 \
                 const int q_ = p_ * RP + srow_o;                                                     \
-                float* row_ = (dst_) + (WP8 ? (q_ < QA ? ((q_ + 7) & 7) * NI8 + ((q_ + 7) >> 3) : 8 * NI8 + 1) : min(q_, QA + 1)) * LDK; \
+                float* row_ = (dst_) + (WHOLE ? (WP8 ? (q_ & 7) * NI8 + (q_ >> 3) : q_) : WP8 ? (q_ < QA ? ((q_ + 7) & 7) * NI8 + ((q_ + 7) >> 3) : 8 * NI8 + 1) : min(q_, QA + 1)) * LDK; \
                 *reinterpret_cast<f32x2*>(row_ + c4 * 2) = f32x2{p0_.x, p1_.x};       /* hi */       \
                 *reinterpret_cast<f32x2*>(row_ + 16 + c4 * 2) = f32x2{p0_.y, p1_.y};  /* lo */       \
             }                                                                                        \
@@ -486,32 +513,40 @@ __global__ __launch_bounds__(256, WIDE_MINB) void conv3x3_wide_kernel(const Gemm
             }
 #define PIPE_LOAD(slot_, chunk_, pass_)                                                              \
             {                                                                                        \
-                const int mc_ = min(max(pm0 + (pass_) * RP, 0), M - 1);                              \
+                const int mc_ = WHOLE ? pm0 + (pass_) * RP : min(max(pm0 + (pass_) * RP, 0), M - 1);    \
                 ar[slot_] = *reinterpret_cast<const f32x4*>(abase + (size_t)mc_ * a.src_ld + (chunk_) * CK); \
             }
 #define PIPE_GB(chunk_)                                                                              \
             if (pro) {                                                                               \
                 g4r = *reinterpret_cast<const f32x4*>(a.pro_gamma + (chunk_) * CK + c4 * 4);         \
                 b4r = *reinterpret_cast<const f32x4*>(a.pro_beta + (chunk_) * CK + c4 * 4);          \
+                if (ONE) g4r = rs1 * g4r;                                                            \
             }
 #define PIPE_STAGE(slot_, pass_)                                                                     \
             {                                                                                        \
                 f32x4 v_ = ar[slot_];                                                                \
-                if (pro) {                                                                           \
-                    const int bi_ = (int)((abidx >> (BB * (pass_))) & ((1ull << BB) - 1));           \
+                if (pro && ONE) {                                                                    \
+                    v_.x = (v_.x - mu1) * g4r.x + b4r.x;                                             \
+                    v_.y = (v_.y - mu1) * g4r.y + b4r.y;                                             \
+                    v_.z = (v_.z - mu1) * g4r.z + b4r.z;                                             \
+                    v_.w = (v_.w - mu1) * g4r.w + b4r.w;                                             \
+                } else if (pro) {                                                                    \
+                    const int bi_ = WHOLE ? ((pass_) * RP + srow_p) >> lhw : (int)((abidx >> (BB * (pass_))) & ((1ull << BB) - 1)); \
                     const float rs_ = srstd[bi_], mu_ = smean[bi_];                                  \
                     v_.x = (v_.x - mu_) * (rs_ * g4r.x) + b4r.x;                                     \
                     v_.y = (v_.y - mu_) * (rs_ * g4r.y) + b4r.y;                                     \
                     v_.z = (v_.z - mu_) * (rs_ * g4r.z) + b4r.z;                                     \
                     v_.w = (v_.w - mu_) * (rs_ * g4r.w) + b4r.w;                                     \
+                }                                                                                    \
+                if (pro) {                                                                           \
                     if (pro_gelu) {                                                                  \
                         v_.x = gelu_erf(v_.x); v_.y = gelu_erf(v_.y);                                \
                         v_.z = gelu_erf(v_.z); v_.w = gelu_erf(v_.w);                                \
                     }                                                                                \
                 }                                                                                    \
-                if (!((avalid >> (pass_)) & 1u)) v_ = f32x4{0.f, 0.f, 0.f, 0.f};                     \
+                if (!WHOLE && !((avalid >> (pass_)) & 1u)) v_ = f32x4{0.f, 0.f, 0.f, 0.f};              \
                 const f32x2 p0_ = split2(v_.x, v_.y), p1_ = split2(v_.z, v_.w);                      \
-                float* row_ = Awr + min((pass_) * RP + srow_p, QA + 1) * LDK;                        \
+                float* row_ = Awr + (WHOLE ? (pass_) * RP + srow_p : min((pass_) * RP + srow_p, QA + 1)) * LDK; \
                 *reinterpret_cast<f32x2*>(row_ + c4 * 2) = f32x2{p0_.x, p1_.x};                      \
                 *reinterpret_cast<f32x2*>(row_ + 16 + c4 * 2) = f32x2{p0_.y, p1_.y};                 \
             }
@@ -1049,11 +1084,12 @@ __global__ __launch_bounds__(256, WIDE_MINB) void conv3x3_wide_kernel(const Gemm
 #undef WIDE_ROWOFF
 }
 
-template <int NT, int PRO, bool W2 = false, int RT = 8, int WN = 2, bool PIPE = false, bool TWO = false, int WP = 0, bool G2 = false>
+template <int NT, int PRO, bool W2 = false, int RT = 8, int WN = 2, bool PIPE = false, bool TWO = false, int WP = 0, bool G2 = false, int WH = 0>
 hipError_t launch_wide_cfg(const GemmArgs& a, const GemmGeom& g, hipStream_t s) {
     constexpr int M_T = (4 / WN) * RT * 16, N_T = WN * 32 * NT, NTHR = 256;
-    constexpr int APASS = (M_T + 18 + 31) / 32, NSMAX = (APASS <= 9) ? 128 : (APASS <= 10) ? 64 : 32;
-    const int halo = a.W + 1;
+    constexpr int APASS = WH ? M_T / 32 : (M_T + 18 + 31) / 32, NSMAX = (APASS <= 9) ? 128 : (APASS <= 10) ? 64 : 32;
+    if (WH && (M_T % a.HW != 0 || a.M % M_T != 0 || (WH == 2 && a.HW != M_T))) return hipErrorInvalidValue;
+    const int halo = WH ? 0 : a.W + 1;
     const int QA = M_T + 2 * halo;
     const int NS = (((QA - 1) / a.HW + 2) + 3) & ~3;
     if (NS > NSMAX || g.m_tile != M_T || g.n_tile != N_T) return hipErrorInvalidValue;
@@ -1065,13 +1101,28 @@ hipError_t launch_wide_cfg(const GemmArgs& a, const GemmGeom& g, hipStream_t s) 
     size_t lds = (size_t)(((DB || G2) ? 2 : 1) * QZ * LDK + 2 * NS) * sizeof(float);
     lds = std::max(lds, (size_t)((M_T / (W2 ? 2 : WP ? RT / 4 : WIDE_NH)) * N_T + (M_T / 4) * WN * 2) * sizeof(float));
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    auto kern = conv3x3_wide_kernel<NT, PRO, W2, RT, WN, PIPE, TWO, WP, G2>;
+    auto kern = conv3x3_wide_kernel<NT, PRO, W2, RT, WN, PIPE, TWO, WP, G2, WH>;
     if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return e;
     const int n_mtiles = (a.M + M_T - 1) / M_T;
     if (a.ksplit > 1 && a.K % 64 != 0) return hipErrorInvalidValue;          // split-K walks even chunk ranges
-    if (a.route) *a.route = GemmRoute{ROUTE_WIDE, WP == 4 ? VAR_WP4 : WP == 8 ? VAR_WP8 : W2 ? VAR_W2 : PIPE ? VAR_PIPE : G2 ? VAR_G2 : VAR_PLAIN, M_T, N_T};
+    if (a.route) *a.route = GemmRoute{ROUTE_WIDE, WP == 4 ? VAR_WP4 : WP == 8 ? VAR_WP8 : W2 ? VAR_W2 : PIPE ? VAR_PIPE : G2 ? VAR_G2 : VAR_PLAIN, M_T, N_T, WH};
     hipLaunchKernelGGL(kern, dim3(n_mtiles * g.n_tiles * std::max(a.ksplit, 1)), dim3(NTHR), lds, s, a, g.slots, NS);
     return hipGetLastError();
+}
+
+// Whole-sample staging (WH, see the kernel) where the tile grid allows it: every tile a whole number of samples and no ragged
+// last tile.  MODES: bit 0 = the configuration has a WH = 1 instantiation, bit 1 = a WH = 2 one (one sample per tile: the
+// level-0 configurations); a one-sample tile of a configuration without it takes WH = 1, which covers it.  Everything else --
+// ragged tiles, HW not dividing the tile, SPDM_NO_WHOLE_TILES -- keeps the halo'd slab.
+template <int MODES, int NT, int PRO, bool W2 = false, int RT = 8, int WN = 2, bool PIPE = false, bool TWO = false, int WP = 0>
+hipError_t launch_wide_sel(const GemmArgs& a, const GemmGeom& g, hipStream_t s) {
+    constexpr int M_T = (4 / WN) * RT * 16;
+    const bool whole = !(a.sw & SW_NO_WHOLE_TILES) && M_T % a.HW == 0 && a.M % M_T == 0;
+    if constexpr ((MODES & 2) != 0 && PRO != PRO_NONE)       // (without a prologue the two are the same code)
+        if (whole && a.HW == M_T) return launch_wide_cfg<NT, PRO, W2, RT, WN, PIPE, TWO, WP, false, 2>(a, g, s);
+    if constexpr ((MODES & 1) != 0)
+        if (whole) return launch_wide_cfg<NT, PRO, W2, RT, WN, PIPE, TWO, WP, false, 1>(a, g, s);
+    return launch_wide_cfg<NT, PRO, W2, RT, WN, PIPE, TWO, WP, false, 0>(a, g, s);
 }
 
 }  // namespace
@@ -1116,39 +1167,39 @@ hipError_t launch_conv_wide(const GemmArgs& a, const GemmGeom& g, hipStream_t s)
         const bool two = a.skip != nullptr;
         if (g.m_tile == 128) {
             if (two) {
-                if (a.pro == PRO_NONE) return launch_wide_cfg<2, PRO_NONE, false, 4, 2, false, true, 4>(a, g, s);
-                return launch_wide_cfg<2, PRO_GN, false, 4, 2, false, true, 4>(a, g, s);
+                if (a.pro == PRO_NONE) return launch_wide_sel<1, 2, PRO_NONE, false, 4, 2, false, true, 4>(a, g, s);
+                return launch_wide_sel<1, 2, PRO_GN, false, 4, 2, false, true, 4>(a, g, s);
             }
-            if (a.pro == PRO_NONE) return launch_wide_cfg<2, PRO_NONE, false, 4, 2, false, false, 4>(a, g, s);
-            if (a.pro == PRO_GN) return launch_wide_cfg<2, PRO_GN, false, 4, 2, false, false, 4>(a, g, s);
-            return launch_wide_cfg<2, PRO_GN_GELU, false, 4, 2, false, false, 4>(a, g, s);
+            if (a.pro == PRO_NONE) return launch_wide_sel<1, 2, PRO_NONE, false, 4, 2, false, false, 4>(a, g, s);
+            if (a.pro == PRO_GN) return launch_wide_sel<1, 2, PRO_GN, false, 4, 2, false, false, 4>(a, g, s);
+            return launch_wide_sel<1, 2, PRO_GN_GELU, false, 4, 2, false, false, 4>(a, g, s);
         }
         if (two) {
-            if (a.pro == PRO_NONE) return launch_wide_cfg<2, PRO_NONE, false, 8, 2, false, true, 4>(a, g, s);
-            return launch_wide_cfg<2, PRO_GN, false, 8, 2, false, true, 4>(a, g, s);
+            if (a.pro == PRO_NONE) return launch_wide_sel<1, 2, PRO_NONE, false, 8, 2, false, true, 4>(a, g, s);
+            return launch_wide_sel<1, 2, PRO_GN, false, 8, 2, false, true, 4>(a, g, s);
         }
-        if (a.pro == PRO_NONE) return launch_wide_cfg<2, PRO_NONE, false, 8, 2, false, false, 4>(a, g, s);
-        if (a.pro == PRO_GN) return launch_wide_cfg<2, PRO_GN, false, 8, 2, false, false, 4>(a, g, s);
-        return launch_wide_cfg<2, PRO_GN_GELU, false, 8, 2, false, false, 4>(a, g, s);
+        if (a.pro == PRO_NONE) return launch_wide_sel<1, 2, PRO_NONE, false, 8, 2, false, false, 4>(a, g, s);
+        if (a.pro == PRO_GN) return launch_wide_sel<1, 2, PRO_GN, false, 8, 2, false, false, 4>(a, g, s);
+        return launch_wide_sel<1, 2, PRO_GN_GELU, false, 8, 2, false, false, 4>(a, g, s);
     }
     // width-8 maps (level 0), 256-row tiles: the same with eight classes on a class-major slab (44 of 48 tile steps per kernel row)
     if (a.W == 8 && a.taps == 9 && g.n_tile == 128 && g.m_tile == 256 && a.HW % 32 == 0 && a.K % 64 == 0 && !(a.sw & SW_NO_WP8)) {
         if (a.skip != nullptr) {
-            if (a.pro == PRO_NONE) return launch_wide_cfg<2, PRO_NONE, false, 8, 2, false, true, 8>(a, g, s);
-            return launch_wide_cfg<2, PRO_GN, false, 8, 2, false, true, 8>(a, g, s);
+            if (a.pro == PRO_NONE) return launch_wide_sel<3, 2, PRO_NONE, false, 8, 2, false, true, 8>(a, g, s);
+            return launch_wide_sel<3, 2, PRO_GN, false, 8, 2, false, true, 8>(a, g, s);
         }
-        if (a.pro == PRO_NONE) return launch_wide_cfg<2, PRO_NONE, false, 8, 2, false, false, 8>(a, g, s);
-        if (a.pro == PRO_GN) return launch_wide_cfg<2, PRO_GN, false, 8, 2, false, false, 8>(a, g, s);
-        return launch_wide_cfg<2, PRO_GN_GELU, false, 8, 2, false, false, 8>(a, g, s);
+        if (a.pro == PRO_NONE) return launch_wide_sel<3, 2, PRO_NONE, false, 8, 2, false, false, 8>(a, g, s);
+        if (a.pro == PRO_GN) return launch_wide_sel<3, 2, PRO_GN, false, 8, 2, false, false, 8>(a, g, s);
+        return launch_wide_sel<3, 2, PRO_GN_GELU, false, 8, 2, false, false, 8>(a, g, s);
     }
     if (a.skip != nullptr) {        // two-source input: the three 128-wide configurations
         if (g.m_tile == 128) {
-            if (a.pro == PRO_NONE) return launch_wide_cfg<2, PRO_NONE, false, 4, 2, false, true>(a, g, s);
-            return launch_wide_cfg<2, PRO_GN, false, 4, 2, false, true>(a, g, s);
+            if (a.pro == PRO_NONE) return launch_wide_sel<1, 2, PRO_NONE, false, 4, 2, false, true>(a, g, s);
+            return launch_wide_sel<1, 2, PRO_GN, false, 4, 2, false, true>(a, g, s);
         }
         if (wide_w2(a)) {
-            if (a.pro == PRO_NONE) return launch_wide_cfg<2, PRO_NONE, true, 8, 2, false, true>(a, g, s);
-            return launch_wide_cfg<2, PRO_GN, true, 8, 2, false, true>(a, g, s);
+            if (a.pro == PRO_NONE) return launch_wide_sel<1, 2, PRO_NONE, true, 8, 2, false, true>(a, g, s);
+            return launch_wide_sel<1, 2, PRO_GN, true, 8, 2, false, true>(a, g, s);
         }
         if (a.pro == PRO_NONE) return launch_wide_cfg<2, PRO_NONE, false, 8, 2, false, true>(a, g, s);
         return launch_wide_cfg<2, PRO_GN, false, 8, 2, false, true>(a, g, s);
@@ -1165,14 +1216,14 @@ hipError_t launch_conv_wide(const GemmArgs& a, const GemmGeom& g, hipStream_t s)
             if (a.pro == PRO_GN) return launch_wide_cfg<2, PRO_GN, false, 4, 2, false, false, false, true>(a, g, s);
             return launch_wide_cfg<2, PRO_GN_GELU, false, 4, 2, false, false, false, true>(a, g, s);
         }
-        if (a.pro == PRO_NONE) return launch_wide_cfg<2, PRO_NONE, false, 4>(a, g, s);
-        if (a.pro == PRO_GN) return launch_wide_cfg<2, PRO_GN, false, 4>(a, g, s);
-        return launch_wide_cfg<2, PRO_GN_GELU, false, 4>(a, g, s);
+        if (a.pro == PRO_NONE) return launch_wide_sel<1, 2, PRO_NONE, false, 4>(a, g, s);
+        if (a.pro == PRO_GN) return launch_wide_sel<1, 2, PRO_GN, false, 4>(a, g, s);
+        return launch_wide_sel<1, 2, PRO_GN_GELU, false, 4>(a, g, s);
     }
     if (wide_w2(a)) {
-        if (a.pro == PRO_NONE) return launch_wide_cfg<2, PRO_NONE, true>(a, g, s);
-        if (a.pro == PRO_GN) return launch_wide_cfg<2, PRO_GN, true>(a, g, s);
-        return launch_wide_cfg<2, PRO_GN_GELU, true>(a, g, s);
+        if (a.pro == PRO_NONE) return launch_wide_sel<1, 2, PRO_NONE, true>(a, g, s);
+        if (a.pro == PRO_GN) return launch_wide_sel<1, 2, PRO_GN, true>(a, g, s);
+        return launch_wide_sel<1, 2, PRO_GN_GELU, true>(a, g, s);
     }
     if (g.n_tile == 128) {
         // (not for the 128-row-per-wave variants: at 256 registers the pipelined loop spills -- 965 vs 931 us on up3.dc1a,
@@ -1186,18 +1237,18 @@ hipError_t launch_conv_wide(const GemmArgs& a, const GemmGeom& g, hipStream_t s)
     // tiles), tap-pair loop; K % 64 != 0 keeps the 2 x 2 arrangement with 128 x 32 waves
     if (a.K % 64 == 0 && !(a.sw & SW_WIDE_N64_2X2)) {
         if (pipe) {
-            if (a.pro == PRO_NONE) return launch_wide_cfg<2, PRO_NONE, false, 4, 1, true>(a, g, s);
-            if (a.pro == PRO_GN) return launch_wide_cfg<2, PRO_GN, false, 4, 1, true>(a, g, s);
-            return launch_wide_cfg<2, PRO_GN_GELU, false, 4, 1, true>(a, g, s);
+            if (a.pro == PRO_NONE) return launch_wide_sel<3, 2, PRO_NONE, false, 4, 1, true>(a, g, s);
+            if (a.pro == PRO_GN) return launch_wide_sel<3, 2, PRO_GN, false, 4, 1, true>(a, g, s);
+            return launch_wide_sel<3, 2, PRO_GN_GELU, false, 4, 1, true>(a, g, s);
         }
         if (g2) {
             if (a.pro == PRO_NONE) return launch_wide_cfg<2, PRO_NONE, false, 4, 1, false, false, false, true>(a, g, s);
             if (a.pro == PRO_GN) return launch_wide_cfg<2, PRO_GN, false, 4, 1, false, false, false, true>(a, g, s);
             return launch_wide_cfg<2, PRO_GN_GELU, false, 4, 1, false, false, false, true>(a, g, s);
         }
-        if (a.pro == PRO_NONE) return launch_wide_cfg<2, PRO_NONE, false, 4, 1>(a, g, s);
-        if (a.pro == PRO_GN) return launch_wide_cfg<2, PRO_GN, false, 4, 1>(a, g, s);
-        return launch_wide_cfg<2, PRO_GN_GELU, false, 4, 1>(a, g, s);
+        if (a.pro == PRO_NONE) return launch_wide_sel<3, 2, PRO_NONE, false, 4, 1>(a, g, s);
+        if (a.pro == PRO_GN) return launch_wide_sel<3, 2, PRO_GN, false, 4, 1>(a, g, s);
+        return launch_wide_sel<3, 2, PRO_GN_GELU, false, 4, 1>(a, g, s);
     }
     if (a.pro == PRO_NONE) return launch_wide_cfg<1, PRO_NONE>(a, g, s);
     if (a.pro == PRO_GN) return launch_wide_cfg<1, PRO_GN>(a, g, s);

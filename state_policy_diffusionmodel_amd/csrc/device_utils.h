@@ -204,23 +204,26 @@ __device__ __forceinline__ float erf_bf(float x) {
 
 // exact (erf) GELU, nn.GELU() default -- models/Unet_FiLmLayer.py:104,65:  v * Phi(v),
 // Phi(v) = 0.5 (1 + erf(v / sqrt 2)).
-// Evaluated through the complementary form  0.5 erfc(z) = 0.5 t P(t) exp(-z^2),  t = 1 / (1 + p z),  z = |v| / sqrt 2
-// (Abramowitz & Stegun 7.1.26, |error of erf| <= 1.5e-7), which needs ONE branch-free piece, one v_rcp_f32 and
-// one v_exp_f32: 13 VALU instructions against 34 for the two-piece erf_bf above.  Both signs are covered by
-// max(v, 0) - |v| 0.5 erfc(z) (for v < 0 that is v * 0.5 erfc(z): no 1 - x cancellation in the tail).  |GELU error| <= 0.5 |v| * 1.5e-7 + rounding:
-// measured <= 4e-7 against fp64 on [-12, 12] (tests/test_gpu_ops.py), the same level as torch's own fp32 kernel.
+// Evaluated through the complementary form  v Phi(v) = max(v, 0) - |v| q(|v|),  q(x) = Phi(-x) = 0.5 erfc(x / sqrt 2)  (for
+// v < 0 that is v q: no 1 - x cancellation in the tail), with  q(x) = 2^E(x),  E a degree-6 polynomial in x = min(|v|, 6):
+// the Gaussian factor of erfc is part of the polynomial, so ONE transcendental (v_exp_f32) and no reciprocal -- min, 6 fma,
+// exp2, max, fma = 10 VALU instructions (Abramowitz & Stegun 7.1.26, which this replaces, took 13 with v_rcp_f32 and
+// v_exp_f32; the two-piece erf_bf above 34).  VALU time is not hidden under the MFMAs and transcendentals least of all.
+// The clamped x is used in BOTH places: past the knee the result is max(v, 0) - 6 q(6), off by at most 6e-9 for any |v|.
+// Coefficients: tools/fit_gelu.py (weighted least squares of log2 Phi(-x) on [0, 6]); float32-emulated max error against
+// fp64 2.6e-7 on [-12, 12]; on the GPU tests/test_gpu_gelu_one_exp.py and tests/test_gpu_ops.py bound it by 6e-7.
+// The clamp is the NaN-propagating minimum (v_minimum3_f32), so NaN in gives NaN out: out_step_kernel's non-finite flag relies on it.
 // The GroupNorm -> GELU prologue of every second convolution runs this once per activation element.
 __device__ __forceinline__ float gelu_erf(float v) {
-    const float z = fabsf(v);
-    const float t = __builtin_amdgcn_rcpf(__fmaf_rn(0.3275911f * 0.70710678118654752440f, z, 1.0f));
-    float p = __fmaf_rn(0.5f * 1.061405429f, t, 0.5f * -1.453152027f);
-    p = __fmaf_rn(p, t, 0.5f * 1.421413741f);
-    p = __fmaf_rn(p, t, 0.5f * -0.284496736f);
-    p = __fmaf_rn(p, t, 0.5f * 0.254829592f);
-    const float e = __builtin_amdgcn_exp2f(v * v * -0.72134752044448170368f);     // exp(-v^2 / 2)
-    const float q = (p * t) * e;                                                   // 0.5 erfc(|v| / sqrt 2)
-    // v Phi(v) = v (1 - q) for v >= 0 and v q for v < 0, i.e. max(v, 0) - |v| q in both cases: no select
-    return __fmaf_rn(-z, q, fmaxf(v, 0.f));
+    const float x = __builtin_elementwise_minimum(fabsf(v), 6.0f);
+    float e = __fmaf_rn(__builtin_bit_cast(float, 0x3811502cu), x, __builtin_bit_cast(float, 0xba4d288bu));
+    e = __fmaf_rn(e, x, __builtin_bit_cast(float, 0x3c051b28u));
+    e = __fmaf_rn(e, x, __builtin_bit_cast(float, 0xbd5b0c46u));
+    e = __fmaf_rn(e, x, __builtin_bit_cast(float, 0xbeeadd98u));
+    e = __fmaf_rn(e, x, __builtin_bit_cast(float, 0xbf935b1au));
+    e = __fmaf_rn(e, x, __builtin_bit_cast(float, 0xbf7fff70u));
+    const float q = __builtin_amdgcn_exp2f(e);                                     // Phi(-x); E >= -30: no denormal
+    return __fmaf_rn(-x, q, fmaxf(v, 0.f));
 }
 
 __device__ __forceinline__ float wave_sum(float v) {

@@ -58,7 +58,7 @@ enum : unsigned {
     SW_NO_SA_TAIL = 1u << 9, SW_ATTN_VALU = 1u << 10, SW_SA_NO_WLDS = 1u << 11, SW_NO_FILM_FOLD = 1u << 12,
     SW_NO_GRAPH = 1u << 13, SW_NO_SPLITK = 1u << 14, SW_ARENA_TRACE = 1u << 15, SW_NO_WIDE_PIPE = 1u << 16, SW_NO_SKINNY = 1u << 17, SW_DEEP = 1u << 18,
     SW_NO_FILM_LOCAL = 1u << 19, SW_NO_FUSED_SRC = 1u << 20, SW_FILM_LOCAL = 1u << 21, SW_PIN_GEOMETRY = 1u << 22, SW_NO_WP4 = 1u << 23, SW_G2 = 1u << 24, SW_NO_WP8 = 1u << 25, SW_NO_SA_HEAD = 1u << 26, SW_SA_HEAD = 1u << 27, SW_NO_REG64 = 1u << 28,
-    SW_NO_SA_CROP = 1u << 29, SW_NO_SA_OUTC = 1u << 30,
+    SW_NO_SA_CROP = 1u << 29, SW_NO_SA_OUTC = 1u << 30, SW_NO_WHOLE_TILES = 1u << 31,
 };
 struct SwitchName { const char* env; unsigned bit; };
 inline const SwitchName* switch_table(int* n) {
@@ -72,7 +72,7 @@ inline const SwitchName* switch_table(int* n) {
         {"SPDM_FILM_LOCAL", SW_FILM_LOCAL}, {"SPDM_PIN_GEOMETRY", SW_PIN_GEOMETRY},
         {"SPDM_NO_WP4", SW_NO_WP4}, {"SPDM_G2", SW_G2}, {"SPDM_NO_WP8", SW_NO_WP8},
         {"SPDM_NO_SA_HEAD", SW_NO_SA_HEAD}, {"SPDM_SA_HEAD", SW_SA_HEAD}, {"SPDM_NO_REG64", SW_NO_REG64},
-        {"SPDM_NO_SA_CROP", SW_NO_SA_CROP}, {"SPDM_NO_SA_OUTC", SW_NO_SA_OUTC}};
+        {"SPDM_NO_SA_CROP", SW_NO_SA_CROP}, {"SPDM_NO_SA_OUTC", SW_NO_SA_OUTC}, {"SPDM_NO_WHOLE_TILES", SW_NO_WHOLE_TILES}};
     *n = (int)(sizeof(t) / sizeof(t[0]));
     return t;
 }
@@ -89,7 +89,7 @@ enum { ROUTE_GEMM = 0, ROUTE_SKINNY = 1, ROUTE_REG = 2, ROUTE_WIDE = 3 };
 // variant: 0 plain; 1 width-2 zero-tap skipping; 2 / 3 width-4 / width-8 row classes (conv_wide); 4 pipelined slab hand-over
 // (conv_wide); 5 two chunks per hand-over (conv_wide, SPDM_G2)
 enum { VAR_PLAIN = 0, VAR_W2 = 1, VAR_WP4 = 2, VAR_WP8 = 3, VAR_PIPE = 4, VAR_G2 = 5 };
-struct GemmRoute { int kernel, variant, m_tile, n_tile; };
+struct GemmRoute { int kernel, variant, m_tile, n_tile, whole; };      // whole: conv_wide's staging (0 halo'd slab, 1 whole-sample tiles, 2 one sample per tile)
 
 struct GemmArgs {
     const float* src;  int src_ld;     // [M][src_ld], K valid channels

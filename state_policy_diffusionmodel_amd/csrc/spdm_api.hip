@@ -3579,8 +3579,13 @@ extern "C" int spdm_op_gelu(const float* d_x, float* d_y, size_t n, void* stream
     return SPDM_OK;
 }
 
+// Host-only introspection: how the launch of the most recent spdm_op_gemm call staged its input slab (GemmRoute::whole)
+static int g_op_gemm_whole = -1;
+extern "C" int spdm_debug_whole_tiles(void) { return g_op_gemm_whole; }
+
 // op-level test hook: one launch_gemm exactly as the plan builds it, on the caller's tensors (include/spdm.h)
 extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {
+    g_op_gemm_whole = -1;
     if (!p) return fail(SPDM_ERR_INVALID, "op_gemm: null argument");
     spdm_op_gemm_args& q = *p;
     for (int i = 0; i < 10; ++i) q.out[i] = -1;
@@ -3658,7 +3663,7 @@ extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {
         return fail(SPDM_ERR_INVALID, "op_gemm: this launch does not take a fused source (the plan materialises it)");
     if (two && !gemm_takes_two_sources(a))
         return fail(SPDM_ERR_INVALID, "op_gemm: this launch does not take a two-source input (the plan concatenates)");
-    GemmRoute r{-1, -1, -1, -1};
+    GemmRoute r{-1, -1, -1, -1, 0};
     a.route = &r;                 // the launch records what it dispatched
     // unwritten partials read as NaN
     if (q.epi == EPI_STATS) HIP_TRY(hipMemset(q.d_stats, 0xff, (size_t)q.B * g.slots * 2 * sizeof(double)));
@@ -3672,6 +3677,7 @@ extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {
                     r.kernel < 0 ? "before any kernel was dispatched (a host-side shape contract)" : "after a kernel was dispatched",
                     hipGetErrorString(es));
     if (es != hipSuccess) return fail(SPDM_ERR_HIP, "op_gemm: %s", hipGetErrorString(es));
+    g_op_gemm_whole = (r.kernel == ROUTE_WIDE) ? r.whole : 0;
     q.out[0] = r.kernel; q.out[1] = r.variant; q.out[2] = r.m_tile; q.out[3] = r.n_tile; q.out[4] = g.ksplit;
     q.out[5] = two ? 1 : 0; q.out[6] = fused ? 1 : 0; q.out[7] = g.slots; q.out[8] = g.st_m_tile; q.out[9] = g.st_n_tiles;
     return SPDM_OK;
