@@ -221,6 +221,71 @@ int  spdm_train_loss_grad(spdm_handle* h, int32_t B, const float* d_x_noisy, con
                           const float* d_cond, const float* d_noise, float* d_loss, float* d_eps, float* d_grad,
                           float* d_grad_cond, void* stream);
 
+/* spdm_train_loss_grad with the timesteps where a device-side forward process leaves them: d_t[t_count] is a DEVICE array.
+ * Checks, results and the consumption of a pending spdm_train_set_time_scale are spdm_train_loss_grad's, except that there is
+ * no host range check: a stream-ordered kernel copies d_t into the handle, clamped into [0, num_train_timesteps), so an
+ * out-of-range value can never index a table.  For in-range timesteps every output equals spdm_train_loss_grad's bit for
+ * bit.  What the entry removes is the host copy of t and the host range check; the waits inside the pass itself remain
+ * (the training pass waits for the upload of its row index, and the time-embedding tables are rebuilt with a wait after a
+ * weight update), so the call is NOT free of host synchronisation.  A NULL stream synchronises on return, as everywhere. */
+int  spdm_train_loss_grad_dt(spdm_handle* h, int32_t B, const float* d_x_noisy, const int32_t* d_t, int32_t t_count,
+                             const float* d_cond, const float* d_noise, float* d_loss, float* d_eps, float* d_grad,
+                             float* d_grad_cond, void* stream);
+
+/* The forward (noising) process of a training step in ONE launch.  Replaces: the head of training_step
+ * (models/diffusion_ddpm.py:128-173) -- t = torch.randint(0, noise_steps, (B,)); noise = torch.randn_like(x);
+ * x_noisy = noise_scheduler.add_noise(x, noise, t); add_constraints(x_noisy, x_0_inpaint) (:216-219) -- and, optionally, the
+ * Dropout(p) mask of simple_Unet.py's PositionalEncoding (:226-257) in the form spdm_train_set_time_scale takes.
+ * Stateless: there is no handle.  Enqueued on `stream` (NULL: the null stream, and the call synchronises).
+ *
+ * Randomness: Philox4x32-10, key = (seed low word, seed high word), counter = (q, sample, step, purpose) with
+ * sample = (uint32)(sample_offset + b) the GLOBAL sample index -- a shard of a batch draws what the whole batch would -- and
+ * `step` the caller's training-step counter.  purpose 0 is spdm_sample's stream and is never drawn here.
+ *   purpose 2, q = 0:            t_b = (int32)(((uint64)w0 * T) >> 32), in [0, T);
+ *   purpose 1, q = e / 4:        the four words give the normals of elements 4q .. 4q+3 of the sample's (H, D) window (in-painted
+ *                                rows included) by Box-Muller, (w0, w1) -> r cos, r sin and (w2, w3) likewise,
+ *                                u = ((w >> 8) + 0.5) 2^-24;
+ *   purpose 3, q = j / 4:        column j of the mask row uses word j & 3: d_time_scale[b][j] = u(w) >= dropout_p ? s : 0 with
+ *                                s = (float)(1 / (1 - (double)dropout_p)).
+ * Arithmetic: x_noisy = fl(fl(sa x0) + fl(sb z)), sa = d_sqrt_abar[t_b], sb = d_sqrt_1m_abar[t_b], three separately rounded
+ * fp32 operations: torch's `sa * x0 + sb * noise` bit for bit.  Rows h < inp_h of x_noisy are then d_inpaint's; their d_noise
+ * rows keep the noise (the reference's loss covers them).
+ *   d_x0 (B,H,D): the clean window, cat([x_0_inpaint, x_0], dim=2);  d_inpaint (B,inp_h,D), NULL exactly when inp_h == 0;
+ *   d_sqrt_abar, d_sqrt_1m_abar: T floats each, the caller's tables;
+ *   d_t_in (B) / d_noise_in (B,H,D): NULL = drawn; non-NULL = the caller's values enter the arithmetic instead.  A given t
+ *     outside [0, T) is clamped into range before any table is read;
+ *   d_t (B, int32) / d_noise (B,H,D): the values used (a given t after the clamp).  Required when the value is drawn; may be
+ *     NULL, or the input array itself, when it was given (the input is then left as it is);
+ *   d_x_noisy (B,H,D);  d_time_scale NULL or (B,time_dim) with time_dim >= 1;
+ *   d_clamped NULL or one int32: the number of entries of d_t_in outside [0, T) (0 when t is drawn).
+ * Deterministic: no atomics; two calls with the same arguments give the same bits.
+ * SPDM_ERR_INVALID, before the GPU is touched: a null required pointer; B, H, D or T < 1; inp_h outside [0, H]; d_inpaint
+ * NULL with inp_h > 0 (or set with inp_h == 0); time_dim < 1 with d_time_scale set; dropout_p outside [0, 1) or NaN. */
+typedef struct {
+    int32_t B;
+    int32_t H;
+    int32_t D;
+    int32_t inp_h;
+    int32_t T;
+    int32_t time_dim;
+    const float* d_x0;
+    const float* d_inpaint;
+    const float* d_sqrt_abar;
+    const float* d_sqrt_1m_abar;
+    uint64_t seed;
+    uint64_t sample_offset;
+    uint32_t step;
+    float dropout_p;
+    const int32_t* d_t_in;
+    const float* d_noise_in;
+    int32_t* d_t;
+    float* d_noise;
+    float* d_x_noisy;
+    float* d_time_scale;
+    int32_t* d_clamped;
+} spdm_forward_process_args;
+int  spdm_train_forward_process(int32_t device, const spdm_forward_process_args* a, void* stream);
+
 /* PositionalEncoding's Dropout(p) in training mode (simple_Unet.py:226-257) for the NEXT spdm_train_loss_grad call on a
  * SPDM_FLAG_TRAIN_SIMPLE handle (SPDM_ERR_STATE on any other): d_scale is a (B, time_dim) device array -- the dropout mask
  * divided by (1 - p) -- and that call evaluates the network on pe[t_b] * d_scale[b].  The call consumes the setting, whatever

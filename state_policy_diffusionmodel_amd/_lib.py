@@ -45,6 +45,14 @@ class SpdmOptimSegment(ctypes.Structure):
                 ("numel", c_uint64)]
 
 
+class SpdmForwardProcessArgs(ctypes.Structure):
+    """spdm_forward_process_args (include/spdm.h)."""
+    _fields_ = ([(n, c_int32) for n in ("B", "H", "D", "inp_h", "T", "time_dim")] +
+                [(n, c_void_p) for n in ("d_x0", "d_inpaint", "d_sqrt_abar", "d_sqrt_1m_abar")] +
+                [("seed", c_uint64), ("sample_offset", c_uint64), ("step", ctypes.c_uint32), ("dropout_p", c_float)] +
+                [(n, c_void_p) for n in ("d_t_in", "d_noise_in", "d_t", "d_noise", "d_x_noisy", "d_time_scale", "d_clamped")])
+
+
 class SpdmConfig(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("horizon", "state_dim", "cond_dim", "time_dim", "attention", "max_batch",
                                         "device", "num_train_timesteps", "flags")]
@@ -68,6 +76,9 @@ SYMBOLS = {
                               c_uint64, c_void_p, c_void_p, c_void_p]),
     "spdm_train_loss_grad": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p]),
+    "spdm_train_loss_grad_dt": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p]),
+    "spdm_train_forward_process": (c_int32, [c_int32, POINTER(SpdmForwardProcessArgs), c_void_p]),
     "spdm_train_set_time_scale": (c_int32, [c_void_p, c_void_p, c_int32]),
     "spdm_sample_begin": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                     c_uint64, c_uint64, c_void_p, c_void_p]),

@@ -390,6 +390,28 @@ struct OptimArgs {
 // one or two launches on s: [partial sums of g^2 ->] Adam on every segment in place; workspace: ADAM_GRID + 1 doubles
 hipError_t launch_adam_step(OptimArgs a, double* workspace, hipStream_t s);
 
+// ---- the forward (noising) process of a training step (train_noise.hip; spdm_train_forward_process) --------
+struct ForwardProcessArgs {
+    int B, H, D, inp_h, T;
+    const float* x0;                   // (B, H, D) clean window
+    const float* inpaint;              // (B, inp_h, D); null iff inp_h == 0
+    const float* sqrt_abar;            // [T]
+    const float* sqrt_1m_abar;         // [T]
+    unsigned long long seed, sample_offset;
+    unsigned step;
+    const int* t_in;                   // (B) or null: drawn (Philox purpose 2)
+    const float* noise_in;             // (B, H, D) or null: drawn (Philox purpose 1)
+    int* t_out;                        // (B): the timesteps used (a given one clamped into [0, T)); may be null when t_in is set
+    float* noise_out;                  // (B, H, D): the noise used; may be null when noise_in is set
+    float* x_noisy;                    // (B, H, D)
+    float* time_scale;  int time_dim;  float dropout_p, keep_scale;     // optional (B, time_dim) dropout mask x keep_scale (purpose 3)
+    int* clamped;                      // optional: entries of t_in outside [0, T)
+};
+// one launch of B workgroups
+hipError_t launch_forward_process(const ForwardProcessArgs& a, hipStream_t s);
+// dst[i] = min(max(src[i], 0), T - 1), i < n (spdm_train_loss_grad_dt: the caller's device timesteps into the handle's)
+hipError_t launch_copy_t_clamped(const int* src, int n, int T, int* dst, hipStream_t s);
+
 hipError_t launch_advance(int* step_dev, int* t_dev, const int* timesteps_dev, int n_steps, hipStream_t s);
 hipError_t launch_set_step(int* step_dev, int* t_dev, const int* timesteps_dev, int n_steps, int i, hipStream_t s);
 

@@ -2765,9 +2765,11 @@ static size_t train_workspace_floats(spdm_handle* h) {
     return T.used;
 }
 
-extern "C" int spdm_train_loss_grad(spdm_handle* h, int32_t B, const float* d_x, const int32_t* h_t, int32_t t_count,
-                                    const float* d_cond, const float* d_noise, float* d_loss, float* d_eps, float* d_grad,
-                                    float* d_grad_cond, void* stream) {
+// spdm_train_loss_grad (h_t: the timesteps on the host, range-checked here) and spdm_train_loss_grad_dt (d_t: on the device,
+// clamped into range by the kernel that copies them) are this one body; exactly one of h_t / d_t is set by the entries.
+static int train_loss_grad(spdm_handle* h, int32_t B, const float* d_x, const int32_t* h_t, const int32_t* d_t, int32_t t_count,
+                           const float* d_cond, const float* d_noise, float* d_loss, float* d_eps, float* d_grad,
+                           float* d_grad_cond, void* stream) {
     if (!h) return fail(SPDM_ERR_INVALID, "null handle");
     const float* tscale = h->t_scale;     // spdm_train_set_time_scale: consumed by this call, whatever its outcome
     const int tscale_B = h->t_scale_B;
@@ -2775,17 +2777,18 @@ extern "C" int spdm_train_loss_grad(spdm_handle* h, int32_t B, const float* d_x,
     h->t_scale_B = 0;
     if (!h->train) return fail(SPDM_ERR_STATE, "spdm_train_loss_grad needs a handle created with SPDM_FLAG_TRAIN");
     SPDM_TRY(check_ready(h, B));
-    if (!d_x || !h_t || !d_noise || !d_loss || !d_grad) return fail(SPDM_ERR_INVALID, "null argument");
+    if (!d_x || (!h_t && !d_t) || !d_noise || !d_loss || !d_grad) return fail(SPDM_ERR_INVALID, "null argument");
     if (h->simple && !d_cond) return fail(SPDM_ERR_INVALID, "SPDM_FLAG_SIMPLE_UNET: d_cond is required (simple_Unet.py's UNet is only defined with conditioning)");
     if (tscale && tscale_B != B)
         return fail(SPDM_ERR_INVALID, "spdm_train_set_time_scale was given %d rows, this call has B = %d", tscale_B, B);
     if (t_count != 1 && t_count != B) return fail(SPDM_ERR_INVALID, "t_count must be 1 or B");
-    for (int i = 0; i < t_count; ++i)
+    for (int i = 0; h_t && i < t_count; ++i)
         if (h_t[i] < 0 || h_t[i] >= h->cfg.num_train_timesteps) return fail(SPDM_ERR_INVALID, "t = %d outside [0,%d)", h_t[i], h->cfg.num_train_timesteps);
     HIP_TRY(hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     SPDM_TRY(ensure_temb(h, s));
-    HIP_TRY(hipMemcpyAsync(h->d_t, h_t, sizeof(int) * t_count, hipMemcpyHostToDevice, s));
+    if (h_t) HIP_TRY(hipMemcpyAsync(h->d_t, h_t, sizeof(int) * t_count, hipMemcpyHostToDevice, s));
+    else HIP_TRY(launch_copy_t_clamped(d_t, t_count, h->cfg.num_train_timesteps, h->d_t, s));
     SPDM_TRY(compute_film(h, B, d_cond, s));
     TrainPass T{h, B, t_count, d_cond != nullptr && h->cfg.cond_dim > 0, false, s, d_grad};
     T.tscale = tscale;
@@ -2793,6 +2796,48 @@ extern "C" int spdm_train_loss_grad(spdm_handle* h, int32_t B, const float* d_x,
                              : train_pass(T, d_x, d_cond, d_noise, d_loss, d_eps, d_grad_cond));
     h->session = false;
     if (!stream) HIP_TRY(hipStreamSynchronize(s));
+    return SPDM_OK;
+}
+
+extern "C" int spdm_train_loss_grad(spdm_handle* h, int32_t B, const float* d_x, const int32_t* h_t, int32_t t_count,
+                                    const float* d_cond, const float* d_noise, float* d_loss, float* d_eps, float* d_grad,
+                                    float* d_grad_cond, void* stream) {
+    return train_loss_grad(h, B, d_x, h_t, nullptr, t_count, d_cond, d_noise, d_loss, d_eps, d_grad, d_grad_cond, stream);
+}
+
+extern "C" int spdm_train_loss_grad_dt(spdm_handle* h, int32_t B, const float* d_x, const int32_t* d_t, int32_t t_count,
+                                       const float* d_cond, const float* d_noise, float* d_loss, float* d_eps, float* d_grad,
+                                       float* d_grad_cond, void* stream) {
+    return train_loss_grad(h, B, d_x, nullptr, d_t, t_count, d_cond, d_noise, d_loss, d_eps, d_grad, d_grad_cond, stream);
+}
+
+// The forward (noising) process of a training step in one launch (include/spdm.h, train_noise.hip).  Stateless, like spdm_adam_step.
+extern "C" int spdm_train_forward_process(int32_t device, const spdm_forward_process_args* a, void* stream) {
+    if (!a) return fail(SPDM_ERR_INVALID, "forward_process: null argument");
+    if (a->B < 1 || a->H < 1 || a->D < 1 || a->T < 1)
+        return fail(SPDM_ERR_INVALID, "forward_process: B, H, D, T = %d, %d, %d, %d must all be >= 1", a->B, a->H, a->D, a->T);
+    if ((long long)a->H * a->D > 0x7fffffffLL - 3)       // the kernel rounds H x D up to whole quads in int
+        return fail(SPDM_ERR_INVALID, "forward_process: H x D does not fit 31 bits");
+    if (a->d_time_scale && a->time_dim > 0x7fffffff - 3) return fail(SPDM_ERR_INVALID, "forward_process: time_dim does not fit 31 bits");
+    if (a->inp_h < 0 || a->inp_h > a->H) return fail(SPDM_ERR_INVALID, "forward_process: inp_h = %d outside [0, H = %d]", a->inp_h, a->H);
+    if (!a->d_x0 || !a->d_sqrt_abar || !a->d_sqrt_1m_abar || !a->d_x_noisy) return fail(SPDM_ERR_INVALID, "forward_process: null pointer");
+    if ((a->inp_h > 0) != (a->d_inpaint != nullptr)) return fail(SPDM_ERR_INVALID, "forward_process: d_inpaint must be NULL exactly when inp_h == 0");
+    if (!a->d_t_in && !a->d_t) return fail(SPDM_ERR_INVALID, "forward_process: d_t is required when the timesteps are drawn");
+    if (!a->d_noise_in && !a->d_noise) return fail(SPDM_ERR_INVALID, "forward_process: d_noise is required when the noise is drawn");
+    if (a->d_time_scale && a->time_dim < 1) return fail(SPDM_ERR_INVALID, "forward_process: time_dim = %d with d_time_scale set", a->time_dim);
+    if (!(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return fail(SPDM_ERR_INVALID, "forward_process: dropout_p = %g outside [0, 1)", (double)a->dropout_p);
+    ForwardProcessArgs k = {};
+    k.B = a->B; k.H = a->H; k.D = a->D; k.inp_h = a->inp_h; k.T = a->T;
+    k.x0 = a->d_x0; k.inpaint = a->d_inpaint; k.sqrt_abar = a->d_sqrt_abar; k.sqrt_1m_abar = a->d_sqrt_1m_abar;
+    k.seed = a->seed; k.sample_offset = a->sample_offset; k.step = a->step;
+    k.t_in = a->d_t_in; k.noise_in = a->d_noise_in; k.t_out = a->d_t; k.noise_out = a->d_noise; k.x_noisy = a->d_x_noisy;
+    k.time_scale = a->d_time_scale; k.time_dim = a->d_time_scale ? a->time_dim : 0;
+    k.dropout_p = a->dropout_p;
+    k.keep_scale = (float)(1.0 / (1.0 - (double)a->dropout_p));
+    k.clamped = a->d_clamped;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(launch_forward_process(k, (hipStream_t)stream));
+    if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));
     return SPDM_OK;
 }
 

@@ -180,6 +180,8 @@ class Diffusion_DDPM:
         self.simple = is_simple_model(model)
         self.attention = model == "UNet_Film"
         self.train_attention = bool(train_attention)      # training_step(backward=True) for UNet_Film (SPDM_FLAG_TRAIN_ATTENTION)
+        self._noise_step = 0                               # training_step(device_noise=True, noise_step=None): its own step counter
+        self._fp_spec = (None, None)                       # forward_process: (noise_scheduler object, its _LinearBetaScheduler)
         # --- scheduler (:65-70); beta schedule is hard-coded 'linear' there, noise_scheduler_type unused
         self.noise_scheduler = DDPMScheduler(num_train_timesteps=self.noise_steps, beta_schedule="linear",
                                              clip_sample=False, prediction_type="epsilon")
@@ -445,9 +447,23 @@ class Diffusion_DDPM:
         return x_0, observation_batch, inpaint_vector
 
     # ==================== Training (models/diffusion_ddpm.py:128-173) ====================
+    def forward_process(self, prediction_vector: torch.Tensor, x_0_inpaint: Optional[torch.Tensor], **kw):
+        """``noising.forward_process`` with this model's scheduler tables: timesteps, noise, ``add_noise`` and
+        ``add_constraints`` (and, with ``time_dim`` / ``dropout_p``, the time-embedding dropout mask) in one HIP launch.
+        The tables are cached per scheduler OBJECT and device: assign a new ``noise_scheduler`` rather than editing one's
+        ``config`` in place.  Returns ``(x_noisy, noise, t[, time_scale])`` on the device; keywords as there (``t``, ``noise``, ``seed``, ``step``,
+        ``sample_offset``, ``time_dim``, ``dropout_p``)."""
+        from .noising import forward_process
+        if self._fp_spec[0] is not self.noise_scheduler:   # a diffusers-like scheduler is restated once per object, not per
+            self._fp_spec = (self.noise_scheduler, _as_spec(self.noise_scheduler))      # call: the device tables stay cached
+        sa, sb = self._fp_spec[1].device_tables(prediction_vector.device)
+        T = min(int(self.noise_steps), sa.numel())         # the reference draws t in [0, noise_steps)
+        return forward_process(prediction_vector, x_0_inpaint, sa[:T], sb[:T], **kw)
+
     def training_step(self, batch, batch_idx: int = 0, *, t: Optional[torch.Tensor] = None,
                       noise: Optional[torch.Tensor] = None, return_parts: bool = False, backward: bool = False,
-                      time_scale: Optional[torch.Tensor] = None):
+                      time_scale: Optional[torch.Tensor] = None, device_noise: bool = False, seed: int = 0,
+                      noise_step: Optional[int] = None, sample_offset: int = 0, time_dropout: Optional[float] = None):
         """The reference's ``training_step``: noising of the target window at a per-sample timestep (``add_noise``),
         in-painting of the observed rows, ONE U-Net evaluation with ``t`` of shape (B,), MSE against the noise.  The U-Net
         runs on the HIP path (``spdm_unet_forward`` with per-sample t); the returned loss carries no torch graph.
@@ -460,9 +476,26 @@ class Diffusion_DDPM:
         ``time_scale`` (model='UNet' with ``backward=True`` only; ValueError otherwise): the (B, time_dim) multiplier of
         pe[t] that PositionalEncoding's Dropout(p=0.1) applies in training mode.  The caller draws it as the reference's
         dropout would: ``F.dropout(torch.ones(B, 256, device='cuda'), 0.1, True)``.  Without it the step is the eval-mode
-        network's (no dropout)."""
+        network's (no dropout).
+        ``device_noise=True``: timesteps, noise, ``add_noise`` and ``add_constraints`` are ONE HIP launch
+        (``forward_process``) instead of torch's global RNG and a dozen small launches, and ``t`` reaches the
+        engine as a device tensor: with ``backward=True`` the step then runs no torch-side ``.cpu()`` of ``t`` and no host
+        range check (the library's own waits inside the training pass remain).  The randomness is a pure function of ``(seed, noise_step, sample_offset + b)``; ``noise_step=None``
+        takes a counter of this object that advances by one per such call; a rank of a sharded batch passes
+        ``sample_offset = rank * B`` (distributed.py's convention).  ``t`` / ``noise`` are still honoured.
+        ``time_dropout=p`` (with ``device_noise=True``, model='UNet' and ``backward=True`` only; ValueError otherwise, and
+        with ``time_scale`` as well): the dropout mask is drawn in the same launch and used as ``time_scale``."""
         if time_scale is not None and not (backward and self.simple):
             raise ValueError("time_scale applies to model='UNet' (simple_Unet.py's dropout on pe[t]) with backward=True only")
+        if time_dropout is not None:
+            if time_scale is not None:
+                raise ValueError("pass time_scale (a drawn mask) or time_dropout (a probability), not both")
+            if not (backward and self.simple):
+                raise ValueError("time_dropout applies to model='UNet' (simple_Unet.py's dropout on pe[t]) with backward=True only")
+            if not device_noise:
+                raise ValueError("time_dropout draws its mask in the device forward process: it needs device_noise=True")
+            if not 0.0 <= float(time_dropout) < 1.0:
+                raise ValueError(f"time_dropout must be a probability in [0, 1), got {time_dropout}")
         if backward:
             self._check_trainable()
         observation_batch = self.prepare_observation_batch(batch)
@@ -475,15 +508,30 @@ class Diffusion_DDPM:
         x_0 = self.prepare_prediction_vectors(prediction_batch).unsqueeze(1)               # (B,1,pred_h,pred_dim)
         x_0_inpaint = self.prepare_inpaint_vectors(observation_batch).unsqueeze(1)         # (B,1,inp_h,pred_dim)
         B = x_0.shape[0]
-        if t is None:
-            t = torch.randint(0, self.noise_steps, (B,), device=self.device)
-        t = t.to(self.device).long()
-        prediction_vector = torch.cat([x_0_inpaint, x_0], dim=2)                           # concat in time
-        if noise is None:
-            noise = torch.randn_like(prediction_vector)
-        noise = noise.to(self.device).float()
-        x_noisy = _as_spec(self.noise_scheduler).add_noise(prediction_vector, noise, t)
-        x_noisy = self.add_constraints(x_noisy, x_0_inpaint)
+        if device_noise:
+            prediction_vector = torch.cat([x_0_inpaint, x_0], dim=2)                       # concat in time
+            if noise_step is None:
+                noise_step, self._noise_step = self._noise_step, self._noise_step + 1
+            kw = dict(t=t, noise=noise, seed=seed, step=noise_step, sample_offset=sample_offset)
+            if time_dropout is not None:
+                eng = self._train_engine_for(B, prediction_vector.shape[-2], prediction_vector.shape[-1])
+                kw.update(time_dim=eng.time_dim, dropout_p=float(time_dropout))
+            out = self.forward_process(prediction_vector, x_0_inpaint, **kw)
+            x_noisy, noise, t = out[:3]                                                    # t: device int32
+            if time_dropout is not None:
+                time_scale = out[3]
+            if not backward:
+                t = t.long()
+        else:
+            if t is None:
+                t = torch.randint(0, self.noise_steps, (B,), device=self.device)
+            t = t.to(self.device).long()
+            prediction_vector = torch.cat([x_0_inpaint, x_0], dim=2)                       # concat in time
+            if noise is None:
+                noise = torch.randn_like(prediction_vector)
+            noise = noise.to(self.device).float()
+            x_noisy = _as_spec(self.noise_scheduler).add_noise(prediction_vector, noise, t)
+            x_noisy = self.add_constraints(x_noisy, x_0_inpaint)
         if backward:
             eng = self._train_engine_for(B, x_noisy.shape[-2], x_noisy.shape[-1])
             loss, noise_estimated, g, grad_cond = eng.loss_and_grad(x_noisy, t, obs_cond, noise, flat=True, time_scale=time_scale)

@@ -291,7 +291,9 @@ class SpdmEngine:
         out as the packed state_dict; ``grad_cond`` is d loss / d cond (None without cond).  For simple_Unet.py's UNet
         (``train_simple=True``) ``grads`` covers its parameters only (not the ``pos_encoding.pos_encoding`` buffer, whose
         slot of the flat tensor holds zeros), and ``time_scale`` (B, time_dim) -- PositionalEncoding's dropout mask over
-        (1 - p), e.g. ``F.dropout(torch.ones(B, 256, device='cuda'), 0.1, True)`` -- multiplies pe[t_b] (training mode)."""
+        (1 - p), e.g. ``F.dropout(torch.ones(B, 256, device='cuda'), 0.1, True)`` -- multiplies pe[t_b] (training mode).
+        ``t`` as a device int32 tensor of B or 1 elements (``noising.forward_process`` returns one) stays on the device
+        (``spdm_train_loss_grad_dt``): no host copy, values outside [0, T) are clamped into range instead of rejected."""
         if not self.train:
             raise RuntimeError("loss_and_grad needs an engine created with train=True")
         if time_scale is not None and not self.train_simple:
@@ -303,7 +305,12 @@ class SpdmEngine:
         xs = self._dev(x_noisy, (B, H, D))
         ns = self._dev(noise, (B, H, D))
         cs = self._dev(cond, (B, self.cond_dim)) if cond is not None else None
-        tt = np.ascontiguousarray(torch.as_tensor(t).reshape(-1).cpu().numpy().astype(np.int32))
+        # a device int32 t of B or 1 elements stays where it is (spdm_train_loss_grad_dt: no .cpu() of t and no host range check; the pass's own waits remain)
+        td = None
+        if isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.numel() in (1, B):
+            td = t.to(self.device).reshape(-1).contiguous()
+        else:
+            tt = np.ascontiguousarray(torch.as_tensor(t).reshape(-1).cpu().numpy().astype(np.int32))
         loss = torch.empty((), device=self.device, dtype=torch.float32)
         eps = torch.empty((B, 1, H, D), device=self.device, dtype=torch.float32)
         g = torch.empty(self._blob_floats, device=self.device, dtype=torch.float32)
@@ -313,9 +320,14 @@ class SpdmEngine:
                 raise ValueError(f"time_scale must be (B, time_dim) = ({B}, {self.time_dim}), got {tuple(time_scale.shape)}")
             ts = self._dev(time_scale)
             _lib.check(self.lib.spdm_train_set_time_scale(self._h, _ptr(ts), B), "spdm_train_set_time_scale")
-        _lib.check(self.lib.spdm_train_loss_grad(self._h, B, _ptr(xs), tt.ctypes.data_as(ctypes.c_void_p), int(tt.size),
-                                                 _ptr(cs), _ptr(ns), _ptr(loss), _ptr(eps), _ptr(g), _ptr(gc),
-                                                 self._stream()), "spdm_train_loss_grad")
+        if td is not None:
+            _lib.check(self.lib.spdm_train_loss_grad_dt(self._h, B, _ptr(xs), _ptr(td), int(td.numel()), _ptr(cs), _ptr(ns),
+                                                        _ptr(loss), _ptr(eps), _ptr(g), _ptr(gc), self._stream()),
+                       "spdm_train_loss_grad_dt")
+        else:
+            _lib.check(self.lib.spdm_train_loss_grad(self._h, B, _ptr(xs), tt.ctypes.data_as(ctypes.c_void_p), int(tt.size),
+                                                     _ptr(cs), _ptr(ns), _ptr(loss), _ptr(eps), _ptr(g), _ptr(gc),
+                                                     self._stream()), "spdm_train_loss_grad")
         if flat:
             return loss, eps, g, gc
         grads = {}

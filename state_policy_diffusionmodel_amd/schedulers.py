@@ -43,6 +43,7 @@ class _LinearBetaScheduler:
         self.init_noise_sigma = 1.0
         self.num_inference_steps = T
         self.timesteps = torch.from_numpy(np.arange(0, T)[::-1].copy().astype(np.int64))
+        self._device_tables = {}               # device_tables(): torch.device -> (sqrt(abar), sqrt(1 - abar))
 
     def set_timesteps(self, num_inference_steps: int, device=None):
         T = self.config.num_train_timesteps
@@ -63,6 +64,16 @@ class _LinearBetaScheduler:
         while sa.dim() < original.dim():
             sa, sb = sa.unsqueeze(-1), sb.unsqueeze(-1)
         return sa * original + sb * noise
+
+    def device_tables(self, device):
+        """``(sqrt(abar), sqrt(1 - abar))`` as (T,) fp32 tensors on ``device``, cached per device: ``add_noise``'s own
+        expressions evaluated there over the whole table, so a gathered entry carries the bits ``add_noise`` computes."""
+        device = torch.device(device)
+        cache = self._device_tables
+        if device not in cache:
+            acp = self.alphas_cumprod.to(device)
+            cache[device] = (acp ** 0.5, (1 - acp) ** 0.5)
+        return cache[device]
 
     def coefficient_table(self) -> np.ndarray:
         """(n, 6) fp32: [sqrt(1-abar_t), sqrt(abar_t), k_x0, k_x, k_eps, k_noise] per loop iteration."""

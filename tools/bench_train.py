@@ -11,8 +11,13 @@ alternate in one run, medians) -- and torch-CPU fp32 autograd of the oracle on 1
 (--no-cpu skips it).  --frames adds raw frames (obs_horizon 10: 10 B frames per step) and the jointly trained observation
 encoder: encoder_train_ms (VisionEncoder.train_forward + backward, synchronised), the same encoder's
 forward + backward through torch-ROCm autograd on an nn.Sequential (torch_encoder_ms; the two alternate, medians), and
-optimizer_step_ms becomes the joint step (clip over both parameters + Adam + both weight updates).  One JSON line per batch size.
-usage: python tools/bench_train.py [--attention | --simple] [--frames] [--iters N] [--no-cpu] [B ...]"""
+optimizer_step_ms becomes the joint step (clip over both parameters + Adam + both weight updates).  Without --frames also the
+head of the step: torch_forward_process_ms (randint + randn_like + add_noise + add_constraints in torch)
+against device_forward_process_ms (Diffusion_DDPM.forward_process: one HIP launch), and the whole
+training_step(backward=True) on a device-resident batch without and with device_noise (training_step_ms /
+training_step_device_noise_ms); the four alternate in one run, each synchronised, medians (and minima, *_min_ms).
+--forward-process-only prints just those.  One JSON line per batch size.
+usage: python tools/bench_train.py [--attention | --simple] [--frames] [--forward-process-only] [--iters N] [--no-cpu] [B ...]"""
 import json
 import os
 import statistics
@@ -87,9 +92,54 @@ def encoder_times(B, iters):
     return statistics.median(ms[hip]), statistics.median(ms[torch_rocm]), enc_sd, frames
 
 
+def facade_model(sd, B, simple, attention, **kw):
+    return Diffusion_DDPM(obs_horizon=10, pred_horizon=H - 10, observation_dim=135, prediction_dim=D, inpaint_horizon=10,
+                          model="UNet" if simple else "UNet_Film" if attention else "UNet_FilmnoAttention",
+                          state_dict=sd, max_batch=B, train_attention=attention, **kw)
+
+
+def forward_process_times(m, B, iters):
+    """The head of a training step in torch and as the one HIP launch, and the whole training_step(backward=True) without and
+    with device_noise: the four alternate, every call synchronised; {name: ms} medians and minima."""
+    g = torch.Generator().manual_seed(B + 1)
+    T = 32          # windows of obs_horizon 10 + pred_horizon 22 steps; observation_dim 135 = 2 + 1 + 4 + 128
+    batch = {"position": torch.randn(B, T, 2, generator=g).cuda(), "action": torch.randn(B, T, 1, generator=g).cuda(),
+             "velocity": torch.randn(B, T, 4, generator=g).cuda(), "image_features": torch.randn(B, T, 128, generator=g).cuda()}
+    obs = m.prepare_observation_batch(batch)
+    x_0 = m.prepare_prediction_vectors(m.prepare_prediction_batch(batch)).unsqueeze(1)
+    inp = m.prepare_inpaint_vectors(obs).unsqueeze(1)
+    window = torch.cat([inp, x_0], dim=2)
+    assert tuple(window.shape) == (B, 1, H, D)
+
+    def torch_fp():
+        t = torch.randint(0, m.noise_steps, (B,), device=m.device)
+        noise = torch.randn_like(window)
+        m.add_constraints(m.noise_scheduler.add_noise(window, noise, t), inp)
+
+    arms = {"torch_forward_process_ms": torch_fp,
+            "device_forward_process_ms": lambda: m.forward_process(window, inp, seed=1, step=0),
+            "training_step_ms": lambda: m.training_step(batch, backward=True),
+            "training_step_device_noise_ms": lambda: m.training_step(batch, backward=True, device_noise=True, seed=1)}
+    ms = {k: [] for k in arms}
+    for it in range(max(20, iters) + 3):
+        for k, fn in arms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if it >= 3:     # (three warm-up rounds)
+                ms[k].append((time.perf_counter() - t0) * 1e3)
+    out = {k: round(statistics.median(v), 4) for k, v in ms.items()}
+    out.update({k.replace("_ms", "_min_ms"): round(min(v), 4) for k, v in ms.items()})
+    return out
+
+
 def main():
     args = sys.argv[1:]
     iters = 20
+    fp_only = "--forward-process-only" in args
+    if fp_only:
+        args.remove("--forward-process-only")
     frames_opt = "--frames" in args
     if frames_opt:
         args.remove("--frames")
@@ -110,6 +160,14 @@ def main():
     torch.set_num_threads(16)
     sd = (random_state_dict(COND, seed=0, model="UNet", noise_steps=1000) if simple else
           random_state_dict(COND, seed=0, attention=attention))
+    model = "UNet (simple_Unet.py)" if simple else "UNet_Film" if attention else "UNet_Film_noAttention"
+    if fp_only:
+        for B in batches:
+            m = facade_model(sd, B, simple, attention)
+            teng = m._train_engine_for(B, H, D)
+            print(json.dumps({"model": model, "B": B, "H": H, "D": D, **forward_process_times(m, B, iters)}), flush=True)
+            teng.close()
+        return
     for B in batches:
         g = torch.Generator().manual_seed(B)
         x = torch.randn(B, 1, H, D, generator=g)
@@ -153,10 +211,8 @@ def main():
             enc_ms, torch_ms, enc_sd, frames = encoder_times(B, iters)
             extra = {"frames": B * 10, "encoder_train_ms": round(enc_ms, 3), "torch_encoder_ms": round(torch_ms, 3),
                      "vision_encoder_state_dict": enc_sd, "train_vision_encoder": True}
-        m = Diffusion_DDPM(obs_horizon=10, pred_horizon=H - 10, observation_dim=135, prediction_dim=D, inpaint_horizon=10,
-                           model="UNet" if simple else "UNet_Film" if attention else "UNet_FilmnoAttention",
-                           state_dict=sd, max_batch=B, train_attention=attention,
-                           **{k: extra.pop(k) for k in ("vision_encoder_state_dict", "train_vision_encoder") if k in extra})
+        m = facade_model(sd, B, simple, attention,
+                         **{k: extra.pop(k) for k in ("vision_encoder_state_dict", "train_vision_encoder") if k in extra})
         teng = m._train_engine_for(B, H, D)
         # both optimisers over the SAME flat parameter(s), alternating (each keeps its own moments; the weights just wander):
         # torch's clip_grad_norm_ + Adam and optim.DeviceAdam
@@ -189,10 +245,11 @@ def main():
                 torch.cuda.synchronize()
                 if it >= 2:     # (two warm-up rounds)
                     opt_ms[k].append((time.perf_counter() - t0) * 1e3)
+        if not frames_opt:
+            extra.update(forward_process_times(m, B, iters))
         teng.close()
         cpu = float("nan") if no_cpu else cpu_step(sd, x, t, cond, noise, attention, simple)
         hip = statistics.median(step)
-        model = "UNet (simple_Unet.py)" if simple else "UNet_Film" if attention else "UNet_Film_noAttention"
         print(json.dumps({"model": model, "B": B, "H": H, "D": D, "hip_step_ms": round(hip, 3), "hip_step_min_ms": round(min(step), 3),
                           "weight_refresh_ms": round(statistics.median(refresh), 2),
                           "weight_update_ms": round(statistics.median(update), 3),
