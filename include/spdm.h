@@ -286,6 +286,67 @@ typedef struct {
 } spdm_forward_process_args;
 int  spdm_train_forward_process(int32_t device, const spdm_forward_process_args* a, void* stream);
 
+/* A training batch gathered from a dataset that lives on the device, in ONE launch.  Replaces:
+ * CarRacingDataset.__getitem__ (utils/load_data.py:91-99) -- sample_sequence_sparse (utils/data_utils.py:58-62) and
+ * _normalize_position (utils/load_data.py:85-89; the inference flavour's translation, :127-143) -- the np.moveaxis of
+ * _load_data (:47), the DataLoader's collate (:173-177) and the .float() casts of models/diffusion_ddpm.py:287-290.
+ * Stateless: there is no handle.  Enqueued on `stream` (NULL: the null stream, and the call synchronises).
+ *
+ * Batch slot b holds window w = clamp(d_window_id[b], 0, n_windows - 1); its rows are s + r step_size, r < seq_len, with
+ * s = clamp(start of w, 0, T - 1 - (seq_len - 1) step_size).  The kernel uses no row number but these, so it cannot read
+ * outside the stores whatever d_window_id and d_window_start hold.
+ *   T: rows in every store;  n_windows: entries of the window table;  B: batch slots;  seq_len, step_size: rows per window and
+ *     their spacing;  n_frames in [0, seq_len]: frames emitted per slot, the window's FIRST n_frames rows;
+ *   img_dtype: 0 = d_img holds uint8 pixels, emitted as (float)k / 255.0f, one correctly rounded fp32 division (which equals
+ *     (float)((double)k / 255.0) for every byte k);  1 = d_img holds float32, copied;  reserved: ignored (keeps the pointers
+ *     8-byte aligned without implicit padding);
+ *   d_img (T,96,96,3): frames as they are stored, channels interleaved;  16-byte aligned;  may be NULL when n_frames == 0;
+ *   d_position (T,2) float64, RAW;  d_velocity (T,2), d_action (T,3) float32, already normalised;  each may be NULL when no
+ *     output reads it;
+ *   d_window_start (n_windows) int32 and h_window_start, the same table in HOST memory: both or neither.  The host copy is
+ *     checked on every call, before the GPU is touched: each start in [0, T - 1 - (seq_len - 1) step_size].  Neither:
+ *     window i starts at row i, and n_windows <= T - (seq_len - 1) step_size is required;
+ *   d_window_id (B) int32, device;
+ *   pos_min, pos_max: the scalar position statistics.  In float64, every operation rounded on its own (no FMA):
+ *     sn = (x - pos_min) / (pos_max - pos_min) * 2 - 1;  translation = sn of the window's first row;
+ *     position = (float)((sn - translation) / 2): numpy's float64 result rounded once to fp32;
+ *   outputs, each may be NULL to skip it:  d_image_out (B,n_frames,3,96,96) fp32, planar, 16-byte aligned (NULL exactly
+ *     when n_frames == 0);  d_position_out (B,seq_len,2), d_velocity_out (B,seq_len,2), d_action_out (B,seq_len,3) fp32;
+ *     d_translation_out (B,2) float64;  d_start_out (B) int32: s;
+ *     d_bad, one int32: SET (not added) to the number of slots whose id or table start had to be clamped.
+ * Duplicate ids are legal: outputs are indexed by slot.  Deterministic: no atomics.
+ * SPDM_ERR_INVALID, before the GPU is touched: NULL args; T, n_windows, B, seq_len or step_size < 1; n_frames outside
+ * [0, seq_len]; an unknown img_dtype; (seq_len - 1) step_size >= T; a NULL d_window_id; d_image_out set without n_frames
+ * (or the reverse); a NULL store that a requested output reads; a misaligned d_img or d_image_out; one table pointer
+ * without the other; a table start outside its range. */
+typedef struct {
+    int32_t T;
+    int32_t n_windows;
+    int32_t B;
+    int32_t seq_len;
+    int32_t step_size;
+    int32_t n_frames;
+    int32_t img_dtype;
+    int32_t reserved;
+    const void* d_img;
+    const double* d_position;
+    const float* d_velocity;
+    const float* d_action;
+    const int32_t* d_window_start;
+    const int32_t* h_window_start;
+    const int32_t* d_window_id;
+    double pos_min;
+    double pos_max;
+    float* d_image_out;
+    float* d_position_out;
+    float* d_velocity_out;
+    float* d_action_out;
+    double* d_translation_out;
+    int32_t* d_start_out;
+    int32_t* d_bad;
+} spdm_dataset_gather_args;
+int  spdm_dataset_gather(int32_t device, const spdm_dataset_gather_args* a, void* stream);
+
 /* PositionalEncoding's Dropout(p) in training mode (simple_Unet.py:226-257) for the NEXT spdm_train_loss_grad call on a
  * SPDM_FLAG_TRAIN_SIMPLE handle (SPDM_ERR_STATE on any other): d_scale is a (B, time_dim) device array -- the dropout mask
  * divided by (1 - p) -- and that call evaluates the network on pe[t_b] * d_scale[b].  The call consumes the setting, whatever

@@ -53,6 +53,16 @@ class SpdmForwardProcessArgs(ctypes.Structure):
                 [(n, c_void_p) for n in ("d_t_in", "d_noise_in", "d_t", "d_noise", "d_x_noisy", "d_time_scale", "d_clamped")])
 
 
+class SpdmDatasetGatherArgs(ctypes.Structure):
+    """spdm_dataset_gather_args (include/spdm.h)."""
+    _fields_ = ([(n, c_int32) for n in ("T", "n_windows", "B", "seq_len", "step_size", "n_frames", "img_dtype", "reserved")] +
+                [(n, c_void_p) for n in ("d_img", "d_position", "d_velocity", "d_action", "d_window_start", "h_window_start",
+                                         "d_window_id")] +
+                [("pos_min", c_double), ("pos_max", c_double)] +
+                [(n, c_void_p) for n in ("d_image_out", "d_position_out", "d_velocity_out", "d_action_out", "d_translation_out",
+                                         "d_start_out", "d_bad")])
+
+
 class SpdmConfig(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("horizon", "state_dim", "cond_dim", "time_dim", "attention", "max_batch",
                                         "device", "num_train_timesteps", "flags")]
@@ -79,6 +89,7 @@ SYMBOLS = {
     "spdm_train_loss_grad_dt": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p]),
     "spdm_train_forward_process": (c_int32, [c_int32, POINTER(SpdmForwardProcessArgs), c_void_p]),
+    "spdm_dataset_gather": (c_int32, [c_int32, POINTER(SpdmDatasetGatherArgs), c_void_p]),
     "spdm_train_set_time_scale": (c_int32, [c_void_p, c_void_p, c_int32]),
     "spdm_sample_begin": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                     c_uint64, c_uint64, c_void_p, c_void_p]),

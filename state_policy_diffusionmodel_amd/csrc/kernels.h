@@ -412,6 +412,29 @@ hipError_t launch_forward_process(const ForwardProcessArgs& a, hipStream_t s);
 // dst[i] = min(max(src[i], 0), T - 1), i < n (spdm_train_loss_grad_dt: the caller's device timesteps into the handle's)
 hipError_t launch_copy_t_clamped(const int* src, int n, int T, int* dst, hipStream_t s);
 
+// ---- training batches gathered from a device-resident dataset (dataset.hip; spdm_dataset_gather) ----------
+struct DatasetGatherArgs {
+    int n_windows, B, seq_len, step_size, n_frames, img_dtype;      // img_dtype: 0 uint8 (divided by 255), 1 fp32
+    int max_start;                     // T - 1 - (seq_len - 1) step_size >= 0: the last start whose window ends inside the stores
+    int img_blocks;                    // filled by the launch: B n_frames x 3 frame slices (0 without d_image_out)
+    const void* img;                   // (T, 96, 96, 3), 16-byte aligned
+    const double* position;            // (T, 2) raw
+    const float* velocity;             // (T, 2) normalised
+    const float* action;               // (T, 3) normalised
+    const int* window_start;           // (n_windows), or null: window i starts at row i
+    const int* window_id;              // (B): clamped into [0, n_windows) before use
+    double pos_min, pos_max;
+    float* image_out;                  // (B, n_frames, 3, 96, 96), 16-byte aligned, or null
+    float* position_out;               // (B, seq_len, 2) or null
+    float* velocity_out;               // (B, seq_len, 2) or null
+    float* action_out;                 // (B, seq_len, 3) or null
+    double* translation_out;           // (B, 2) or null
+    int* start_out;                    // (B) or null
+    int* bad;                          // one int or null: SET to the number of batch slots whose id or start was clamped
+};
+// one launch of B n_frames x 3 + ceil(B seq_len / 256) workgroups
+hipError_t launch_dataset_gather(DatasetGatherArgs a, hipStream_t s);
+
 hipError_t launch_advance(int* step_dev, int* t_dev, const int* timesteps_dev, int n_steps, hipStream_t s);
 hipError_t launch_set_step(int* step_dev, int* t_dev, const int* timesteps_dev, int n_steps, int i, hipStream_t s);
 

@@ -2841,6 +2841,51 @@ extern "C" int spdm_train_forward_process(int32_t device, const spdm_forward_pro
     return SPDM_OK;
 }
 
+// A training batch gathered from device-resident stores in one launch (include/spdm.h, dataset.hip).  Stateless.
+extern "C" int spdm_dataset_gather(int32_t device, const spdm_dataset_gather_args* a, void* stream) {
+    if (!a) return fail(SPDM_ERR_INVALID, "dataset_gather: null argument");
+    if (a->T < 1 || a->n_windows < 1 || a->B < 1 || a->seq_len < 1 || a->step_size < 1)
+        return fail(SPDM_ERR_INVALID, "dataset_gather: T, n_windows, B, seq_len, step_size = %d, %d, %d, %d, %d must all be >= 1",
+                    a->T, a->n_windows, a->B, a->seq_len, a->step_size);
+    if (a->n_frames < 0 || a->n_frames > a->seq_len)
+        return fail(SPDM_ERR_INVALID, "dataset_gather: n_frames = %d outside [0, seq_len = %d]", a->n_frames, a->seq_len);
+    if (a->img_dtype != 0 && a->img_dtype != 1) return fail(SPDM_ERR_INVALID, "dataset_gather: img_dtype = %d is neither 0 (uint8) nor 1 (float32)", a->img_dtype);
+    const long long span = (long long)(a->seq_len - 1) * a->step_size;       // rows between a window's first and last
+    if (span >= a->T) return fail(SPDM_ERR_INVALID, "dataset_gather: a window spans %lld rows, the stores hold T = %d", span + 1, a->T);
+    const long long max_start = a->T - 1 - span;
+    if ((long long)a->B * a->seq_len > 0x7fffffffLL || (long long)a->B * a->n_frames * 3 > 0x7fffffffLL - 0x800000)
+        return fail(SPDM_ERR_INVALID, "dataset_gather: B x seq_len does not fit 31 bits");
+    if (!a->d_window_id) return fail(SPDM_ERR_INVALID, "dataset_gather: d_window_id is NULL");
+    if ((a->n_frames > 0) != (a->d_image_out != nullptr)) return fail(SPDM_ERR_INVALID, "dataset_gather: d_image_out must be NULL exactly when n_frames == 0");
+    if (a->d_image_out && !a->d_img) return fail(SPDM_ERR_INVALID, "dataset_gather: d_img is NULL");
+    if (a->d_image_out && (((uintptr_t)a->d_img | (uintptr_t)a->d_image_out) & 15))
+        return fail(SPDM_ERR_INVALID, "dataset_gather: d_img and d_image_out must be 16-byte aligned");
+    if ((a->d_position_out || a->d_translation_out) && !a->d_position) return fail(SPDM_ERR_INVALID, "dataset_gather: d_position is NULL");
+    if (a->d_velocity_out && !a->d_velocity) return fail(SPDM_ERR_INVALID, "dataset_gather: d_velocity is NULL");
+    if (a->d_action_out && !a->d_action) return fail(SPDM_ERR_INVALID, "dataset_gather: d_action is NULL");
+    if ((a->d_window_start != nullptr) != (a->h_window_start != nullptr))
+        return fail(SPDM_ERR_INVALID, "dataset_gather: d_window_start and its host copy h_window_start go together");
+    if (a->h_window_start) {
+        for (int i = 0; i < a->n_windows; ++i)
+            if (a->h_window_start[i] < 0 || a->h_window_start[i] > max_start)
+                return fail(SPDM_ERR_INVALID, "dataset_gather: window %d starts at row %d: it must lie in [0, %lld] to end inside T = %d rows",
+                            i, a->h_window_start[i], max_start, a->T);
+    } else if (a->n_windows - 1 > max_start) {
+        return fail(SPDM_ERR_INVALID, "dataset_gather: without a table window i starts at row i: n_windows = %d must be <= %lld", a->n_windows, max_start + 1);
+    }
+    DatasetGatherArgs k = {};
+    k.n_windows = a->n_windows; k.B = a->B; k.seq_len = a->seq_len; k.step_size = a->step_size; k.n_frames = a->n_frames;
+    k.img_dtype = a->img_dtype; k.max_start = (int)max_start;
+    k.img = a->d_img; k.position = a->d_position; k.velocity = a->d_velocity; k.action = a->d_action;
+    k.window_start = a->d_window_start; k.window_id = a->d_window_id; k.pos_min = a->pos_min; k.pos_max = a->pos_max;
+    k.image_out = a->d_image_out; k.position_out = a->d_position_out; k.velocity_out = a->d_velocity_out; k.action_out = a->d_action_out;
+    k.translation_out = a->d_translation_out; k.start_out = a->d_start_out; k.bad = a->d_bad;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(launch_dataset_gather(k, (hipStream_t)stream));
+    if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));
+    return SPDM_OK;
+}
+
 extern "C" int spdm_train_set_time_scale(spdm_handle* h, const float* d_scale, int32_t B) {
     if (!h) return fail(SPDM_ERR_INVALID, "null handle");
     if (!h->train_simple) return fail(SPDM_ERR_STATE, "spdm_train_set_time_scale needs a handle created with SPDM_FLAG_TRAIN_SIMPLE");
