@@ -347,6 +347,85 @@ typedef struct {
 } spdm_dataset_gather_args;
 int  spdm_dataset_gather(int32_t device, const spdm_dataset_gather_args* a, void* stream);
 
+/* The error of sampled trajectories against the windows they were conditioned on, in ONE launch and without the
+ * trajectories leaving the device.  Replaces the per-window body of the reference's
+ * evaluation/eval_acurracy_diffusion_positions.py:118-140 and evaluation/eval_consistency_diffusion_positions.py:
+ * unnormalize_position (utils/data_utils.py:35-40) of truth and prediction, and
+ * np.linalg.norm(gt[0, obs_horizon:] - pred[inpaint_horizon:], axis=1).  Stateless.  Enqueued on `stream` (NULL: the null
+ * stream, and the call synchronises); it does not synchronise otherwise and uses no atomics.
+ *
+ * Trajectory g = window k x runs + run r: the runs of a window are consecutive trajectories.  Prediction row b of this call is
+ * trajectory first_traj + b and reads the truth of slot (first_traj + b) / runs - window_base, so a call may begin and end
+ * inside a window's runs and the truth is never replicated.
+ *   B: prediction rows;  H, D: the sampler's horizon and state dimension;  n_slots: truth windows passed;  seq: rows per
+ *     truth window;  obs_h: truth rows before the first predicted step;  inp_h: prediction rows before it;  P: predicted
+ *     steps compared;  runs >= 1;  window_base: the window number of slot 0;  first_traj >= 0;
+ *   d_pred (B,H,D) fp32: x_0;  d_truth_pos (n_slots,seq,2), d_truth_act (n_slots,seq,3) fp32, normalised as
+ *     spdm_dataset_gather emits them;  d_translation (n_slots,2) float64;
+ *   pos_min, pos_max: the scalar position statistics;  act_min, act_max: the action statistics per channel.
+ * d_pos_err (B,P) float64: for step j,  || U(truth[slot, obs_h + j]) - U(pred[b, inp_h + j, 0:2]) ||_2  with
+ *     U(n) = (((double)n * 2 + translation) + 1) / 2 * (pos_max - pos_min) + pos_min  and the norm sqrt(dx dx + dy dy);
+ *     every operation is a float64 operation rounded on its own (no FMA), which is numpy's result bit for bit.
+ * d_act_err (B,P,3) float64, optional (NULL skips it; then d_truth_act may be NULL):  | A(truth) - A(pred[b, inp_h + j, 2:5]) |
+ *     per channel with  A(n) = (double)((n + 1.0f) / 2.0f) * (act_max - act_min) + act_min:  the reference's unnormalize_data
+ *     on a float32 array, whose first two operations stay float32.
+ * SPDM_ERR_INVALID, before the GPU is touched: NULL args or a NULL d_pred, d_truth_pos, d_translation or d_pos_err; d_act_err
+ * without d_truth_act; B, P, runs, n_slots or seq < 1; H != inp_h + P; D < 2, or D < 5 with d_act_err; seq < obs_h + P;
+ * obs_h or inp_h < 0; inp_h > obs_h; first_traj < 0; a slot of row 0 or of row B - 1 outside [0, n_slots); B x P beyond 31
+ * bits. */
+typedef struct {
+    int32_t B;
+    int32_t H;
+    int32_t D;
+    int32_t n_slots;
+    int32_t seq;
+    int32_t obs_h;
+    int32_t inp_h;
+    int32_t P;
+    int32_t runs;
+    int32_t window_base;
+    int64_t first_traj;
+    const float* d_pred;
+    const float* d_truth_pos;
+    const float* d_truth_act;
+    const double* d_translation;
+    double pos_min;
+    double pos_max;
+    double act_min[3];
+    double act_max[3];
+    double* d_pos_err;
+    double* d_act_err;
+} spdm_eval_errors_args;
+int  spdm_eval_errors(int32_t device, const spdm_eval_errors_args* a, void* stream);
+
+/* Mean and population standard deviation of an error buffer d_err (N,C) float64, N = windows x runs rows in trajectory order
+ * (np.mean / np.std of the reference's evaluation scripts).  Five launches on `stream`, no atomics, no host synchronisation
+ * between them (NULL stream: the call synchronises at its end).  Every sum is two-pass: the mean first, then the squared
+ * deviations from it.
+ *   d_window_mean, d_window_std (N / runs, C): over the runs of each window, summed sequentially in run order -- bit for bit
+ *     np.mean / np.std(axis=0) of the window's (runs, C) rows, which numpy reduces row by row;
+ *   d_mean, d_std (C): over all N rows, in a fixed order that is a function of (N, C) alone (blocks of 1024 rows reduced
+ *     in-thread, by wave shuffles and through LDS; the block partials added in block order), so two calls on the same
+ *     input give the same bits;
+ *   d_workspace: at least spdm_eval_reduce_workspace_doubles(N, C) doubles, its capacity in workspace_doubles.
+ * SPDM_ERR_INVALID, before the GPU is touched: NULL args or any NULL pointer; N, C or runs < 1; N not a multiple of runs;
+ * C > 65535; a workspace that is too small. */
+typedef struct {
+    int64_t N;
+    int32_t C;
+    int32_t runs;
+    const double* d_err;
+    double* d_window_mean;
+    double* d_window_std;
+    double* d_mean;
+    double* d_std;
+    double* d_workspace;
+    uint64_t workspace_doubles;
+} spdm_eval_reduce_args;
+int  spdm_eval_reduce(int32_t device, const spdm_eval_reduce_args* a, void* stream);
+/* doubles of workspace spdm_eval_reduce needs for (N, C); 0 for N or C < 1 */
+size_t spdm_eval_reduce_workspace_doubles(int64_t N, int32_t C);
+
 /* PositionalEncoding's Dropout(p) in training mode (simple_Unet.py:226-257) for the NEXT spdm_train_loss_grad call on a
  * SPDM_FLAG_TRAIN_SIMPLE handle (SPDM_ERR_STATE on any other): d_scale is a (B, time_dim) device array -- the dropout mask
  * divided by (1 - p) -- and that call evaluates the network on pe[t_b] * d_scale[b].  The call consumes the setting, whatever

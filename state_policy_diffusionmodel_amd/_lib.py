@@ -63,6 +63,22 @@ class SpdmDatasetGatherArgs(ctypes.Structure):
                                          "d_start_out", "d_bad")])
 
 
+class SpdmEvalErrorsArgs(ctypes.Structure):
+    """spdm_eval_errors_args (include/spdm.h)."""
+    _fields_ = ([(n, c_int32) for n in ("B", "H", "D", "n_slots", "seq", "obs_h", "inp_h", "P", "runs", "window_base")] +
+                [("first_traj", c_int64)] +
+                [(n, c_void_p) for n in ("d_pred", "d_truth_pos", "d_truth_act", "d_translation")] +
+                [("pos_min", c_double), ("pos_max", c_double), ("act_min", c_double * 3), ("act_max", c_double * 3)] +
+                [("d_pos_err", c_void_p), ("d_act_err", c_void_p)])
+
+
+class SpdmEvalReduceArgs(ctypes.Structure):
+    """spdm_eval_reduce_args (include/spdm.h)."""
+    _fields_ = ([("N", c_int64), ("C", c_int32), ("runs", c_int32)] +
+                [(n, c_void_p) for n in ("d_err", "d_window_mean", "d_window_std", "d_mean", "d_std", "d_workspace")] +
+                [("workspace_doubles", c_uint64)])
+
+
 class SpdmConfig(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("horizon", "state_dim", "cond_dim", "time_dim", "attention", "max_batch",
                                         "device", "num_train_timesteps", "flags")]
@@ -90,6 +106,9 @@ SYMBOLS = {
                                           c_void_p, c_void_p, c_void_p]),
     "spdm_train_forward_process": (c_int32, [c_int32, POINTER(SpdmForwardProcessArgs), c_void_p]),
     "spdm_dataset_gather": (c_int32, [c_int32, POINTER(SpdmDatasetGatherArgs), c_void_p]),
+    "spdm_eval_errors": (c_int32, [c_int32, POINTER(SpdmEvalErrorsArgs), c_void_p]),
+    "spdm_eval_reduce": (c_int32, [c_int32, POINTER(SpdmEvalReduceArgs), c_void_p]),
+    "spdm_eval_reduce_workspace_doubles": (c_size_t, [c_int64, c_int32]),
     "spdm_train_set_time_scale": (c_int32, [c_void_p, c_void_p, c_int32]),
     "spdm_sample_begin": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                     c_uint64, c_uint64, c_void_p, c_void_p]),

@@ -435,6 +435,36 @@ struct DatasetGatherArgs {
 // one launch of B n_frames x 3 + ceil(B seq_len / 256) workgroups
 hipError_t launch_dataset_gather(DatasetGatherArgs a, hipStream_t s);
 
+// ---- position / action error of sampled trajectories and its statistics (evaluation.hip; spdm_eval_*) -----
+struct EvalErrorsArgs {
+    int B, H, D, seq, obs_h, inp_h, P, runs;
+    long long first_traj, window_base; // row b belongs to truth slot (first_traj + b) / runs - window_base, in [0, n_slots)
+    const float* pred;                 // (B, H, D): the sampler's x_0
+    const float* truth_pos;            // (n_slots, seq, 2) normalised
+    const float* truth_act;            // (n_slots, seq, 3) normalised; null iff act_err is null
+    const double* translation;         // (n_slots, 2)
+    double pos_min, pos_max, act_min[3], act_max[3];
+    double* pos_err;                   // (B, P)
+    double* act_err;                   // (B, P, 3) or null
+};
+// one launch of ceil(B P / 256) workgroups
+hipError_t launch_eval_errors(const EvalErrorsArgs& a, hipStream_t s);
+
+constexpr int EVAL_ROWS_PER_BLOCK = 1024;      // rows one workgroup of the all-rows reduction sums for one column
+inline long long eval_reduce_blocks(long long N) { return (N + EVAL_ROWS_PER_BLOCK - 1) / EVAL_ROWS_PER_BLOCK; }
+struct EvalReduceArgs {
+    long long N, windows;              // N = windows x runs rows
+    int C, runs;
+    const double* err;                 // (N, C)
+    double* window_mean;               // (windows, C)
+    double* window_std;                // (windows, C)
+    double* mean;                      // (C)
+    double* std;                       // (C)
+    double* workspace;                 // eval_reduce_blocks(N) x C doubles
+};
+// five launches on s, each ordered behind the one before: per-window statistics, then sum / mean / squares / std over all rows
+hipError_t launch_eval_reduce(const EvalReduceArgs& a, hipStream_t s);
+
 hipError_t launch_advance(int* step_dev, int* t_dev, const int* timesteps_dev, int n_steps, hipStream_t s);
 hipError_t launch_set_step(int* step_dev, int* t_dev, const int* timesteps_dev, int n_steps, int i, hipStream_t s);
 

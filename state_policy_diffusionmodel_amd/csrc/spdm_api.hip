@@ -2886,6 +2886,66 @@ extern "C" int spdm_dataset_gather(int32_t device, const spdm_dataset_gather_arg
     return SPDM_OK;
 }
 
+// Errors of sampled trajectories against their windows in one launch (include/spdm.h, evaluation.hip).  Stateless.
+extern "C" int spdm_eval_errors(int32_t device, const spdm_eval_errors_args* a, void* stream) {
+    if (!a) return fail(SPDM_ERR_INVALID, "eval_errors: null argument");
+    if (a->B < 1 || a->P < 1 || a->runs < 1 || a->n_slots < 1 || a->seq < 1)
+        return fail(SPDM_ERR_INVALID, "eval_errors: B, P, runs, n_slots, seq = %d, %d, %d, %d, %d must all be >= 1", a->B, a->P, a->runs,
+                    a->n_slots, a->seq);
+    if (a->obs_h < 0 || a->inp_h < 0) return fail(SPDM_ERR_INVALID, "eval_errors: obs_h = %d and inp_h = %d must be >= 0", a->obs_h, a->inp_h);
+    if (a->inp_h > a->obs_h) return fail(SPDM_ERR_INVALID, "eval_errors: inp_h = %d exceeds obs_h = %d", a->inp_h, a->obs_h);
+    if ((long long)a->H != (long long)a->inp_h + a->P) return fail(SPDM_ERR_INVALID, "eval_errors: H = %d is not inp_h + P = %d + %d", a->H, a->inp_h, a->P);
+    if (a->D < 2 || (a->d_act_err && a->D < 5))
+        return fail(SPDM_ERR_INVALID, "eval_errors: D = %d holds no %s", a->D, a->D < 2 ? "position (2 columns)" : "action (columns 2..4)");
+    if ((long long)a->seq < (long long)a->obs_h + a->P) return fail(SPDM_ERR_INVALID, "eval_errors: seq = %d is shorter than obs_h + P = %d + %d", a->seq, a->obs_h, a->P);
+    if ((long long)a->B * a->P > 0x7fffffffLL) return fail(SPDM_ERR_INVALID, "eval_errors: B x P does not fit 31 bits");
+    if (!a->d_pred || !a->d_truth_pos || !a->d_translation || !a->d_pos_err) return fail(SPDM_ERR_INVALID, "eval_errors: null pointer");
+    if (a->d_act_err && !a->d_truth_act) return fail(SPDM_ERR_INVALID, "eval_errors: d_act_err needs d_truth_act");
+    if (a->first_traj < 0 || a->first_traj > INT64_MAX - a->B) return fail(SPDM_ERR_INVALID, "eval_errors: first_traj = %lld is negative or overflows", (long long)a->first_traj);
+    const long long lo = a->first_traj / a->runs - a->window_base, hi = (a->first_traj + a->B - 1) / a->runs - a->window_base;
+    if (lo < 0 || hi >= a->n_slots)
+        return fail(SPDM_ERR_INVALID, "eval_errors: rows [%lld, %lld) at %d runs from window %d read slots [%lld, %lld], outside [0, n_slots = %d)",
+                    (long long)a->first_traj, (long long)a->first_traj + a->B, a->runs, a->window_base, lo, hi, a->n_slots);
+    EvalErrorsArgs k = {};
+    k.B = a->B; k.H = a->H; k.D = a->D; k.seq = a->seq; k.obs_h = a->obs_h; k.inp_h = a->inp_h; k.P = a->P; k.runs = a->runs;
+    k.first_traj = a->first_traj; k.window_base = a->window_base;
+    k.pred = a->d_pred; k.truth_pos = a->d_truth_pos; k.truth_act = a->d_act_err ? a->d_truth_act : nullptr; k.translation = a->d_translation;
+    k.pos_min = a->pos_min; k.pos_max = a->pos_max;
+    for (int c = 0; c < 3; ++c) { k.act_min[c] = a->act_min[c]; k.act_max[c] = a->act_max[c]; }
+    k.pos_err = a->d_pos_err; k.act_err = a->d_act_err;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(launch_eval_errors(k, (hipStream_t)stream));
+    if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));
+    return SPDM_OK;
+}
+
+extern "C" size_t spdm_eval_reduce_workspace_doubles(int64_t N, int32_t C) {
+    return (N < 1 || C < 1) ? 0 : (size_t)eval_reduce_blocks(N) * (size_t)C;
+}
+
+// Statistics of an error buffer per window and over all rows (include/spdm.h, evaluation.hip).  Stateless.
+extern "C" int spdm_eval_reduce(int32_t device, const spdm_eval_reduce_args* a, void* stream) {
+    if (!a) return fail(SPDM_ERR_INVALID, "eval_reduce: null argument");
+    if (a->N < 1 || a->C < 1 || a->runs < 1)
+        return fail(SPDM_ERR_INVALID, "eval_reduce: N, C, runs = %lld, %d, %d must all be >= 1", (long long)a->N, a->C, a->runs);
+    if (a->N % a->runs != 0) return fail(SPDM_ERR_INVALID, "eval_reduce: N = %lld is not a multiple of runs = %d", (long long)a->N, a->runs);
+    if (a->C > 65535) return fail(SPDM_ERR_INVALID, "eval_reduce: C = %d exceeds 65535", a->C);
+    if (a->N > (1LL << 40)) return fail(SPDM_ERR_INVALID, "eval_reduce: N = %lld exceeds 2^40 rows", (long long)a->N);
+    if (!a->d_err || !a->d_window_mean || !a->d_window_std || !a->d_mean || !a->d_std || !a->d_workspace)
+        return fail(SPDM_ERR_INVALID, "eval_reduce: null pointer");
+    const size_t need = spdm_eval_reduce_workspace_doubles(a->N, a->C);
+    if (a->workspace_doubles < need)
+        return fail(SPDM_ERR_INVALID, "eval_reduce: workspace of %llu doubles, %zu needed", (unsigned long long)a->workspace_doubles, need);
+    EvalReduceArgs k = {};
+    k.N = a->N; k.windows = a->N / a->runs; k.C = a->C; k.runs = a->runs;
+    k.err = a->d_err; k.window_mean = a->d_window_mean; k.window_std = a->d_window_std; k.mean = a->d_mean; k.std = a->d_std;
+    k.workspace = a->d_workspace;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(launch_eval_reduce(k, (hipStream_t)stream));
+    if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));
+    return SPDM_OK;
+}
+
 extern "C" int spdm_train_set_time_scale(spdm_handle* h, const float* d_scale, int32_t B) {
     if (!h) return fail(SPDM_ERR_INVALID, "null handle");
     if (!h->train_simple) return fail(SPDM_ERR_STATE, "spdm_train_set_time_scale needs a handle created with SPDM_FLAG_TRAIN_SIMPLE");

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .weights import normalize_data, unnormalize_data  # noqa: F401  (re-exported: the reference's formulas, written once)
+from .weights import normalize_data, unnormalize_data, unnormalize_position  # noqa: F401  (re-exported: the reference's formulas, written once)
 
 FRAME_SHAPE = (96, 96, 3)
 _CHUNK_ROWS = 256        # frames per piece of the uint8 check and of the upload: 28 MB of float32
@@ -280,5 +280,5 @@ class CarRacingDataModule:
             pickle.dump([self.stats], f)
 
 
-__all__ = ["create_sample_indices_sparse", "compute_stats", "normalize_data", "unnormalize_data", "split_indices",
+__all__ = ["create_sample_indices_sparse", "compute_stats", "normalize_data", "unnormalize_data", "unnormalize_position", "split_indices",
            "choose_image_storage", "DeviceDataset", "CarRacingDataModule"]
