@@ -186,6 +186,14 @@ int  spdm_schedule_tables(int32_t kind, int32_t num_train_timesteps, int32_t num
 int  spdm_unet_forward(spdm_handle* h, int32_t B, const float* d_x, const int32_t* h_t,
                        int32_t t_count, const float* d_cond, float* d_eps, void* stream);
 
+/* spdm_unet_forward with the timesteps where a device-side forward process leaves them: d_t[t_count] is a DEVICE array.
+ * Checks and results are spdm_unet_forward's, except that there is no host copy of t and no host range check: a
+ * stream-ordered kernel copies d_t into the handle, clamped into [0, num_train_timesteps), exactly as spdm_train_loss_grad_dt
+ * does, so an out-of-range value can never index a table.  For in-range timesteps d_eps equals spdm_unet_forward's bit for
+ * bit.  The time-embedding tables are still rebuilt with a wait after a weight update. */
+int  spdm_unet_forward_dt(spdm_handle* h, int32_t B, const float* d_x, const int32_t* d_t,
+                          int32_t t_count, const float* d_cond, float* d_eps, void* stream);
+
 /* Replaces: the body of Diffusion_DDPM.sample / Diffusion_DDIM.sample after the
  * conditioning vectors are built (models/diffusion_ddpm.py:252-277,
  * models/diffusion_ddim.py:52-74): for t in timesteps: eps = unet(x,t,cond);
@@ -425,6 +433,37 @@ typedef struct {
 int  spdm_eval_reduce(int32_t device, const spdm_eval_reduce_args* a, void* stream);
 /* doubles of workspace spdm_eval_reduce needs for (N, C); 0 for N or C < 1 */
 size_t spdm_eval_reduce_workspace_doubles(int64_t N, int32_t C);
+
+/* The per-sample terms of a validation pass's loss in ONE launch (train_metrics.hip).  Replaces: nn.MSELoss
+ * of the reference's validation_step (models/diffusion_ddpm.py:175-214, :49) as Lightning averages it over an epoch, weighted by
+ * batch size: with H x D elements in every sample that is the mean over the samples of each sample's own mean squared error.
+ * Stateless: there is no handle.  Enqueued on `stream`, no atomics, no host synchronisation (NULL stream: the null stream, and
+ * the call synchronises).
+ *   d_eps, d_noise (B,H,D) fp32: the predicted and the drawn noise of one batch;
+ *   d_terms (n_slots) float64: sample b writes d_terms[slot_offset + b] = (sum over its H x D elements e of
+ *     ((double)noise[e] - (double)eps[e])^2) / (double)(H x D);  slots outside [slot_offset, slot_offset + B) are not touched;
+ *   d_t_in (B) int32 with d_slot_t (n_slots) int32, both or neither: d_slot_t[slot_offset + b] = d_t_in[b].
+ * Every operation is a float64 operation rounded on its own (no FMA).  The summation order is a function of H x D alone: element
+ * e (row-major in the sample) belongs to partial e mod 64; a partial adds its elements in ascending order starting from 0.0; the
+ * 64 partials p[0..63] are combined by  for off in 32, 16, 8, 4, 2, 1: p[i] = p[i] + p[i + off], i < off;  the term is
+ * p[0] / (double)(H x D).  (One wave per sample, lane = partial, the tree by wave shuffles; several samples per workgroup.)
+ * The mean over a pass is spdm_eval_reduce over the (N, 1) terms with runs = 1: its d_mean.
+ * SPDM_ERR_INVALID, before the GPU is touched: NULL args or a NULL d_eps, d_noise or d_terms; B, H or D < 1; H x D beyond 31
+ * bits; slot_offset < 0; slot_offset + B > n_slots; exactly one of d_t_in / d_slot_t set. */
+typedef struct {
+    int32_t B;
+    int32_t H;
+    int32_t D;
+    int32_t reserved;
+    const float* d_eps;
+    const float* d_noise;
+    int64_t slot_offset;
+    int64_t n_slots;
+    double* d_terms;
+    const int32_t* d_t_in;
+    int32_t* d_slot_t;
+} spdm_loss_terms_args;
+int  spdm_loss_terms(int32_t device, const spdm_loss_terms_args* a, void* stream);
 
 /* PositionalEncoding's Dropout(p) in training mode (simple_Unet.py:226-257) for the NEXT spdm_train_loss_grad call on a
  * SPDM_FLAG_TRAIN_SIMPLE handle (SPDM_ERR_STATE on any other): d_scale is a (B, time_dim) device array -- the dropout mask

@@ -79,6 +79,13 @@ class SpdmEvalReduceArgs(ctypes.Structure):
                 [("workspace_doubles", c_uint64)])
 
 
+class SpdmLossTermsArgs(ctypes.Structure):
+    """spdm_loss_terms_args (include/spdm.h)."""
+    _fields_ = ([(n, c_int32) for n in ("B", "H", "D", "reserved")] + [("d_eps", c_void_p), ("d_noise", c_void_p)] +
+                [("slot_offset", c_int64), ("n_slots", c_int64)] +
+                [(n, c_void_p) for n in ("d_terms", "d_t_in", "d_slot_t")])
+
+
 class SpdmConfig(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("horizon", "state_dim", "cond_dim", "time_dim", "attention", "max_batch",
                                         "device", "num_train_timesteps", "flags")]
@@ -98,6 +105,7 @@ SYMBOLS = {
     "spdm_set_schedule_tables": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "spdm_schedule_tables": (c_int32, [c_int32, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p]),
     "spdm_unet_forward": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "spdm_unet_forward_dt": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "spdm_sample": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_uint64,
                               c_uint64, c_void_p, c_void_p, c_void_p]),
     "spdm_train_loss_grad": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -109,6 +117,7 @@ SYMBOLS = {
     "spdm_eval_errors": (c_int32, [c_int32, POINTER(SpdmEvalErrorsArgs), c_void_p]),
     "spdm_eval_reduce": (c_int32, [c_int32, POINTER(SpdmEvalReduceArgs), c_void_p]),
     "spdm_eval_reduce_workspace_doubles": (c_size_t, [c_int64, c_int32]),
+    "spdm_loss_terms": (c_int32, [c_int32, POINTER(SpdmLossTermsArgs), c_void_p]),
     "spdm_train_set_time_scale": (c_int32, [c_void_p, c_void_p, c_int32]),
     "spdm_sample_begin": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                     c_uint64, c_uint64, c_void_p, c_void_p]),

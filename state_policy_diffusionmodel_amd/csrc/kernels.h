@@ -465,6 +465,20 @@ struct EvalReduceArgs {
 // five launches on s, each ordered behind the one before: per-window statistics, then sum / mean / squares / std over all rows
 hipError_t launch_eval_reduce(const EvalReduceArgs& a, hipStream_t s);
 
+// ---- per-sample terms of a validation pass's loss (train_metrics.hip; spdm_loss_terms) -------------------
+constexpr int LOSS_WAVES = 4;          // samples (one wave each) per workgroup
+struct LossTermsArgs {
+    int B, n;                          // samples, elements per sample (H x D)
+    long long slot_offset;             // sample b writes slot slot_offset + b, inside [0, n_slots): checked by the host
+    const float* eps;                  // (B, n)
+    const float* noise;                // (B, n)
+    double* terms;                     // (n_slots)
+    const int* t_in;                   // (B) or null
+    int* slot_t;                       // (n_slots) or null; null iff t_in is null
+};
+// one launch of ceil(B / LOSS_WAVES) workgroups
+hipError_t launch_loss_terms(const LossTermsArgs& a, hipStream_t s);
+
 hipError_t launch_advance(int* step_dev, int* t_dev, const int* timesteps_dev, int n_steps, hipStream_t s);
 hipError_t launch_set_step(int* step_dev, int* t_dev, const int* timesteps_dev, int n_steps, int i, hipStream_t s);
 

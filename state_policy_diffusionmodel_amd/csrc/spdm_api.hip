@@ -1950,18 +1950,21 @@ static StepArgs step_args(spdm_handle* h, int B, const Tensor& feat, bool eps_re
     return a;
 }
 
-extern "C" int spdm_unet_forward(spdm_handle* h, int32_t B, const float* d_x, const int32_t* h_t, int32_t t_count,
-                                 const float* d_cond, float* d_eps, void* stream) {
+// spdm_unet_forward (h_t: the timesteps on the host, range-checked here) and spdm_unet_forward_dt (d_t: on the device, clamped
+// into range by the kernel that copies them) are this one body; exactly one of h_t / d_t is set by the entries.
+static int unet_forward(spdm_handle* h, int32_t B, const float* d_x, const int32_t* h_t, const int32_t* d_t, int32_t t_count,
+                        const float* d_cond, float* d_eps, void* stream) {
     SPDM_TRY(check_ready(h, B));
-    if (!d_x || !h_t || !d_eps) return fail(SPDM_ERR_INVALID, "null argument");
+    if (!d_x || (!h_t && !d_t) || !d_eps) return fail(SPDM_ERR_INVALID, "null argument");
     if (t_count != 1 && t_count != B) return fail(SPDM_ERR_INVALID, "t_count must be 1 or B");
-    for (int i = 0; i < t_count; ++i)
+    for (int i = 0; h_t && i < t_count; ++i)
         if (h_t[i] < 0 || h_t[i] >= h->cfg.num_train_timesteps) return fail(SPDM_ERR_INVALID, "t = %d outside [0,%d)", h_t[i], h->cfg.num_train_timesteps);
     if (h->simple && !d_cond) return fail(SPDM_ERR_INVALID, "d_cond is null: models/simple_Unet.py's UNet needs its conditioning");
     HIP_TRY(hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     SPDM_TRY(ensure_temb(h, s));
-    HIP_TRY(hipMemcpyAsync(h->d_t, h_t, sizeof(int) * t_count, hipMemcpyHostToDevice, s));
+    if (h_t) HIP_TRY(hipMemcpyAsync(h->d_t, h_t, sizeof(int) * t_count, hipMemcpyHostToDevice, s));
+    else HIP_TRY(launch_copy_t_clamped(d_t, t_count, h->cfg.num_train_timesteps, h->d_t, s));
     HIP_TRY(hipMemsetAsync(h->d_step + 2, 0, sizeof(int), s));
     HIP_TRY(hipMemcpyAsync(h->d_x, d_x, sizeof(float) * (size_t)B * h->cfg.horizon * h->cfg.state_dim, hipMemcpyDeviceToDevice, s));
     SPDM_TRY(compute_film(h, B, d_cond, s));
@@ -1978,6 +1981,16 @@ extern "C" int spdm_unet_forward(spdm_handle* h, int32_t B, const float* d_x, co
     h->session = false;
     if (!stream) HIP_TRY(hipStreamSynchronize(s));
     return SPDM_OK;
+}
+
+extern "C" int spdm_unet_forward(spdm_handle* h, int32_t B, const float* d_x, const int32_t* h_t, int32_t t_count,
+                                 const float* d_cond, float* d_eps, void* stream) {
+    return unet_forward(h, B, d_x, h_t, nullptr, t_count, d_cond, d_eps, stream);
+}
+
+extern "C" int spdm_unet_forward_dt(spdm_handle* h, int32_t B, const float* d_x, const int32_t* d_t, int32_t t_count,
+                                    const float* d_cond, float* d_eps, void* stream) {
+    return unet_forward(h, B, d_x, nullptr, d_t, t_count, d_cond, d_eps, stream);
 }
 
 extern "C" int spdm_sample_begin(spdm_handle* h, int32_t B, const float* d_cond, const float* d_inpaint, int32_t inp_h,
@@ -2942,6 +2955,26 @@ extern "C" int spdm_eval_reduce(int32_t device, const spdm_eval_reduce_args* a, 
     k.workspace = a->d_workspace;
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(launch_eval_reduce(k, (hipStream_t)stream));
+    if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));
+    return SPDM_OK;
+}
+
+// The per-sample terms of a validation pass's loss in one launch (include/spdm.h, train_metrics.hip).  Stateless.
+extern "C" int spdm_loss_terms(int32_t device, const spdm_loss_terms_args* a, void* stream) {
+    if (!a) return fail(SPDM_ERR_INVALID, "loss_terms: null argument");
+    if (a->B < 1 || a->H < 1 || a->D < 1) return fail(SPDM_ERR_INVALID, "loss_terms: B, H, D = %d, %d, %d must all be >= 1", a->B, a->H, a->D);
+    if ((long long)a->H * a->D > 0x7fffffffLL - 64) return fail(SPDM_ERR_INVALID, "loss_terms: H x D does not fit 31 bits");
+    if (!a->d_eps || !a->d_noise || !a->d_terms) return fail(SPDM_ERR_INVALID, "loss_terms: null pointer");
+    if (a->slot_offset < 0) return fail(SPDM_ERR_INVALID, "loss_terms: slot_offset = %lld is negative", (long long)a->slot_offset);
+    if (a->n_slots < a->B || a->slot_offset > a->n_slots - a->B)
+        return fail(SPDM_ERR_INVALID, "loss_terms: slots [%lld, %lld + %d) lie outside [0, n_slots = %lld)", (long long)a->slot_offset,
+                    (long long)a->slot_offset, a->B, (long long)a->n_slots);
+    if ((a->d_t_in != nullptr) != (a->d_slot_t != nullptr)) return fail(SPDM_ERR_INVALID, "loss_terms: d_t_in and d_slot_t go together");
+    LossTermsArgs k = {};
+    k.B = a->B; k.n = a->H * a->D; k.slot_offset = a->slot_offset;
+    k.eps = a->d_eps; k.noise = a->d_noise; k.terms = a->d_terms; k.t_in = a->d_t_in; k.slot_t = a->d_slot_t;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(launch_loss_terms(k, (hipStream_t)stream));
     if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));
     return SPDM_OK;
 }

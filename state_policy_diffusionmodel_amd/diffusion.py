@@ -101,6 +101,11 @@ class NoiseEstimator:
     def state_dict(self):
         return {k: torch.from_numpy(v) for k, v in self._sd.items()}
 
+    def mark_moved(self) -> None:
+        """``flat_parameter()`` was written behind torch's back (``DeviceAdam`` steps it through its pointer, which does not
+        advance the tensor's version): the host copy is fetched again on its next use."""
+        self._flat_version = None
+
     def _engines(self):
         return [e for e in (self._owner._engine, self._owner._train_engine) if e is not None]
 
@@ -175,6 +180,8 @@ class Diffusion_DDPM:
         self.prediction_dim = prediction_dim
         self.inpaint_horizon = inpaint_horizon
         self.lr = learning_rate
+        self.noise_scheduler_type = noise_scheduler_type   # (kept for hparams.yaml only: the reference ignores it, :65-70)
+        self.step_size = step_size
         # --- architecture switch (:54-62): every name but the two FiLM ones builds simple_Unet.UNet
         self.model_name = model
         self.simple = is_simple_model(model)
@@ -253,7 +260,7 @@ class Diffusion_DDPM:
         if self.simple:
             # simple_Unet.py: the time table is the network's own pos_encoding buffer (noise_steps + 1 rows at construction);
             # a schedule reaching past it is refused when it is installed, as the reference's pe[t] would fail
-            T = int(self.noise_estimator._sd["pos_encoding.pos_encoding"].shape[0])
+            T = int(self.noise_estimator._host_sd["pos_encoding.pos_encoding"].shape[0])      # (a shape: no refresh from the device)
         else:
             T = max(int(spec.config.num_train_timesteps), int(self.noise_steps))
         key = ("UNet" if self.simple else self.attention, H, D, T, batch if pin else 0)   # (a pinned engine: ONE global batch)
@@ -278,7 +285,7 @@ class Diffusion_DDPM:
     def _train_engine_for(self, batch: int, H: int, D: int) -> SpdmEngine:
         self._check_trainable()
         if self.simple:      # simple_Unet.py: the time table is the network's own pos_encoding buffer (as in _engine_for)
-            T = int(self.noise_estimator._sd["pos_encoding.pos_encoding"].shape[0])
+            T = int(self.noise_estimator._host_sd["pos_encoding.pos_encoding"].shape[0])      # (a shape: no refresh from the device)
         else:
             T = max(int(_as_spec(self.noise_scheduler).config.num_train_timesteps), int(self.noise_steps))
         key = (H, D, T)
@@ -557,6 +564,115 @@ class Diffusion_DDPM:
     def validation_step(self, batch, batch_idx: int = 0, **kw):
         return self.training_step(batch, batch_idx, **kw)
 
+    def validation_loss(self, batches, *, seed: int = 0, noise_step: int = 0xFFFFFFFF, return_terms: bool = False):
+        """The reference's ``val_loss`` (``validation_step`` over a ``val_dataloader()``, averaged by Lightning over the epoch
+        with batch-size weights) as a deterministic function of the weights, formed on the device.
+
+        Every batch of ``batches`` goes through ONE ``forward_process`` keyed by ``(seed, noise_step, sample_offset = the
+        number of validation samples before the batch)`` -- so a sample's noise and timestep depend on its position in the
+        validation order, not on the batch size or on how often validation runs; ``noise_step`` is a value no training step
+        uses -- then through the forward-only engine with ``t`` left on the device (``spdm_unet_forward_dt``; for
+        model='UNet' the eval-mode network, no dropout) and through ``spdm_loss_terms``, which writes each sample's mean
+        squared error to its slot of a float64 buffer.  After the last batch one ``spdm_eval_reduce`` takes the mean and ONE
+        read-back returns it as a Python float: every element weighs equally.  ``return_terms=True``: ``(val_loss, terms (N)
+        float64, t (N) int32)``, the last two on the device.  Forward-only: it serves all three models, ``'UNet_Film'``
+        without ``train_attention`` included."""
+        from .evaluation import reduce_errors
+        from .train_metrics import loss_terms_into
+        ids = getattr(batches, "window_ids", None)
+        cap = len(ids) if ids is not None else 1024
+        terms = torch.empty(max(cap, 1), dtype=torch.float64, device=self.device)
+        slot_t = torch.empty(max(cap, 1), dtype=torch.int32, device=self.device)
+        count = 0
+        for batch in batches:
+            observation_batch = self.prepare_observation_batch(batch)
+            prediction_batch = self.prepare_prediction_batch(batch)
+            obs_cond = self.prepare_obs_cond_vectors(observation_batch).unsqueeze(1)
+            x_0 = self.prepare_prediction_vectors(prediction_batch).unsqueeze(1)
+            x_0_inpaint = self.prepare_inpaint_vectors(observation_batch).unsqueeze(1)
+            prediction_vector = torch.cat([x_0_inpaint, x_0], dim=2)
+            B = prediction_vector.shape[0]
+            if count + B > terms.numel():       # a source of unknown length: the buffers grow on the device
+                grow = max(terms.numel(), count + B - terms.numel())
+                terms = torch.cat([terms, torch.empty(grow, dtype=torch.float64, device=self.device)])
+                slot_t = torch.cat([slot_t, torch.empty(grow, dtype=torch.int32, device=self.device)])
+            x_noisy, noise, t = self.forward_process(prediction_vector, x_0_inpaint, seed=seed, step=noise_step, sample_offset=count)
+            eng = self._engine_for(B, x_noisy.shape[-2], x_noisy.shape[-1])
+            eps = eng.unet_forward(x_noisy, t, obs_cond)
+            loss_terms_into(eps, noise, terms, count, t=t, slot_t=slot_t)
+            count += B
+        if count == 0:
+            raise ValueError("validation_loss: no batches")
+        terms, slot_t = terms[:count], slot_t[:count]
+        mean = reduce_errors(terms.view(count, 1), 1)[2]
+        val_loss = float(mean.item())           # the one read-back
+        return (val_loss, terms, slot_t) if return_terms else val_loss
+
+    # ==================== Checkpoints (Lightning's layout; train.py's ModelCheckpoint) ====================
+    def hparams(self) -> dict:
+        """The constructor arguments ``save_hyperparameters()`` records (models/diffusion_ddpm.py:37)."""
+        hp = {"noise_steps": self.noise_steps, "obs_horizon": self.obs_horizon, "pred_horizon": self.pred_horizon,
+              "observation_dim": self.observation_dim, "prediction_dim": self.prediction_dim, "learning_rate": self.lr,
+              "model": self.model_name, "noise_scheduler_type": self.noise_scheduler_type,
+              "inpaint_horizon": self.inpaint_horizon, "step_size": self.step_size}
+        hp = {k: (v.item() if hasattr(v, "item") else v) for k, v in hp.items()}
+        assert tuple(hp) == self._HPARAM_KEYS
+        hp["vision_encoder"] = None
+        return hp
+
+    def save_hparams(self, path) -> None:
+        """The ``hparams.yaml`` that ``load_from_checkpoint(hparams_file=)`` reads."""
+        import yaml
+        with open(path, "w") as fh:
+            fh.write(yaml.safe_dump(self.hparams(), sort_keys=False))
+
+    def save_checkpoint(self, path, *, optimizer=None, scheduler=None, trainer_state: Optional[dict] = None) -> None:
+        """Write ``path`` with ``torch.save`` in the layout of a Lightning checkpoint: ``state_dict`` (``noise_estimator.<name>``
+        for every tensor of the network at its CURRENT value -- pulled from the flat device parameter if an optimiser has
+        moved it -- the ``pos_encoding.pos_encoding`` buffer of model='UNet' included, and ``vision_encoder.<name>`` when the
+        model has encoder weights), ``hyper_parameters``, ``epoch``, ``global_step``, ``optimizer_states``, ``lr_schedulers``,
+        and this project's own counters under ``'spdm_trainer'`` (``trainer_state``; ``epoch`` and ``global_step`` are taken
+        from it).  Tensors are saved from the host; the file holds nothing ``torch.load(weights_only=True)`` refuses."""
+        def host(v):
+            if isinstance(v, torch.Tensor):
+                return v.detach().cpu()
+            if isinstance(v, dict):
+                return {k: host(x) for k, x in v.items()}
+            if isinstance(v, (list, tuple)):
+                return [host(x) for x in v]
+            if isinstance(v, np.generic):
+                return v.item()
+            return v
+
+        self.noise_estimator.mark_moved()       # whoever stepped the flat parameter, and however: the file holds its values
+        sd = {"noise_estimator." + k: v.clone() for k, v in self.noise_estimator.state_dict().items()}
+        enc = None
+        if hasattr(self.vision_encoder, "state_dict"):
+            enc = self.vision_encoder.state_dict()
+        elif self._vision_sd is not None:
+            enc = self._vision_sd
+        for k, v in (enc or {}).items():
+            sd["vision_encoder." + k] = v.detach().cpu().clone() if hasattr(v, "detach") else torch.from_numpy(np.array(v))
+        ts = host(dict(trainer_state or {}))
+        ckpt = {"epoch": int(ts.get("epoch", 0)), "global_step": int(ts.get("global_step", 0)),
+                "pytorch-lightning_version": "2.0.0",
+                "state_dict": sd, "hyper_parameters": self.hparams(),
+                "optimizer_states": [host(optimizer.state_dict())] if optimizer is not None else [],
+                "lr_schedulers": [host(scheduler.state_dict())] if scheduler is not None else [],
+                "spdm_trainer": ts}
+        torch.save(ckpt, str(path))
+
+    def restore_checkpoint(self, ckpt: dict) -> None:
+        """Take the ``noise_estimator.*`` tensors of a loaded checkpoint dict (``train.fit(ckpt_path=)``): host copy, flat
+        parameter and every cached engine follow.  A jointly trained encoder is not restored here."""
+        if self.train_vision_encoder:
+            raise NotImplementedError("resuming a run with train_vision_encoder=True is not supported: the encoder's "
+                                      "weights would not be restored")
+        sd = {k[len("noise_estimator."):]: v for k, v in ckpt["state_dict"].items() if k.startswith("noise_estimator.")}
+        if not sd:
+            raise ValueError("the checkpoint's state_dict holds no noise_estimator.* tensors")
+        self.noise_estimator.load_state_dict(sd)
+
     # ==================== Optimisation (models/diffusion_ddpm.py:114-124, train.py) ====================
     def configure_optimizers(self, device_optimizer: bool = False):
         """The reference's optimiser: Adam(lr) over the weights -- here the one flat device parameter
@@ -588,6 +704,7 @@ class Diffusion_DDPM:
         from .optim import DeviceAdam
         if isinstance(optimizer, DeviceAdam):       # clip (over all its parameters together) + Adam in two HIP launches
             optimizer.step(max_norm=gradient_clip_val or None)
+            self.noise_estimator.mark_moved()
             self.noise_estimator._push()
             if self.train_vision_encoder:
                 self.vision_encoder.update_weights(self._trainable_encoder().flat_parameter().detach())

@@ -272,12 +272,19 @@ class SpdmEngine:
 
     # -- the noise predictor ------------------------------------------------------------------
     def unet_forward(self, x: torch.Tensor, t, cond: Optional[torch.Tensor]) -> torch.Tensor:
-        """eps = noise_estimator(x, t, cond); x (B,1,H,D), t (1,)|(B,) ints, cond (B,1,obs_h,obs_dim)."""
+        """eps = noise_estimator(x, t, cond); x (B,1,H,D), t (1,)|(B,) ints, cond (B,1,obs_h,obs_dim).
+        ``t`` as a device int32 tensor of B or 1 elements (``noising.forward_process`` returns one) stays on the device
+        (``spdm_unet_forward_dt``): no host copy, values outside [0, T) are clamped into range instead of rejected."""
         B = x.shape[0]
         xs = self._dev(x, (B, self.horizon, self.state_dim))
         cs = self._dev(cond, (B, self.cond_dim)) if cond is not None else None
-        tt = np.ascontiguousarray(torch.as_tensor(t).reshape(-1).cpu().numpy().astype(np.int32))
         eps = torch.empty((B, 1, self.horizon, self.state_dim), device=self.device, dtype=torch.float32)
+        if isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.numel() in (1, B):
+            td = t.to(self.device).reshape(-1).contiguous()
+            _lib.check(self.lib.spdm_unet_forward_dt(self._h, B, _ptr(xs), _ptr(td), int(td.numel()), _ptr(cs), _ptr(eps),
+                                                     self._stream()), "spdm_unet_forward_dt")
+            return eps
+        tt = np.ascontiguousarray(torch.as_tensor(t).reshape(-1).cpu().numpy().astype(np.int32))
         _lib.check(self.lib.spdm_unet_forward(self._h, B, _ptr(xs), tt.ctypes.data_as(ctypes.c_void_p), int(tt.size),
                                               _ptr(cs), _ptr(eps), self._stream()), "spdm_unet_forward")
         return eps
