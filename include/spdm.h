@@ -434,6 +434,45 @@ int  spdm_eval_reduce(int32_t device, const spdm_eval_reduce_args* a, void* stre
 /* doubles of workspace spdm_eval_reduce needs for (N, C); 0 for N or C < 1 */
 size_t spdm_eval_reduce_workspace_doubles(int64_t N, int32_t C);
 
+/* Uniform noise added to the observations of a batch of windows in ONE launch (obs_noise.hip).  Replaces the
+ * four `batch[k] = batch[k] + torch.rand_like(batch[k]) * scaling_factor` of evaluation/eval_robustness.py:180-190.
+ * Stateless: there is no handle.  Enqueued on `stream`, no atomics, no host synchronisation (NULL stream: the null stream,
+ * and the call synchronises).
+ *
+ * For each tensor i < n_tensors, each row < n_rows and each element e < inner:
+ *     d_dst[row dst_stride + e] = d_src[row src_stride + e] + alpha u(row_offset + row, e)
+ * in float32 with two roundings, the product and then the sum (no FMA).  Elements at or beyond inner are neither read nor
+ * written, so a tensor can be cut to its first rows on the fly (position: inner = obs_h 2, src_stride = seq 2,
+ * dst_stride = obs_h 2).  d_dst == d_src is allowed; any other overlap of the two is not.
+ *   u: Philox4x32-10, key (seed lo, seed hi), counter (e / 4, row_offset + row, draw, 4 + i); element e takes word w = e % 4
+ *     of its quad and u = (float)(w >> 8) 2^-24, exact and in [0, 1): the values torch.rand produces.  Purposes 0 .. 3 belong
+ *     to the sampler and to spdm_train_forward_process.  The value of an element depends on (seed, draw, i, row_offset + row,
+ *     e) alone: not on alignment, strides, n_rows or the other tensors, so rows [r0, r1) with row_offset + r0 equal the rows
+ *     of the whole.
+ *   Where d_src, d_dst are 16-byte aligned and inner and both strides are multiples of 4 the tensor moves in 16-byte
+ *     accesses; otherwise element by element.  The values are the same.
+ * SPDM_ERR_INVALID, before the GPU is touched: NULL args; n_rows < 1; n_tensors outside [1, 4]; an inner < 0; a stride below
+ * its inner; inner / 4 + 1 beyond 32 bits; row_offset < 0 or row_offset + n_rows beyond 32 bits; a NULL d_src or d_dst where
+ * inner > 0; alpha negative or not finite; a grid beyond 2^31 - 1 workgroups (1024 quads each). */
+typedef struct {
+    const float* d_src;
+    float* d_dst;
+    int64_t inner;
+    int64_t src_stride;
+    int64_t dst_stride;
+} spdm_obs_noise_tensor;
+typedef struct {
+    int64_t n_rows;
+    int64_t row_offset;
+    uint64_t seed;
+    uint32_t draw;
+    float alpha;
+    int32_t n_tensors;
+    int32_t reserved;
+    spdm_obs_noise_tensor tensors[4];
+} spdm_obs_noise_args;
+int  spdm_obs_noise(int32_t device, const spdm_obs_noise_args* a, void* stream);
+
 /* The per-sample terms of a validation pass's loss in ONE launch (train_metrics.hip).  Replaces: nn.MSELoss
  * of the reference's validation_step (models/diffusion_ddpm.py:175-214, :49) as Lightning averages it over an epoch, weighted by
  * batch size: with H x D elements in every sample that is the mean over the samples of each sample's own mean squared error.

@@ -79,6 +79,17 @@ class SpdmEvalReduceArgs(ctypes.Structure):
                 [("workspace_doubles", c_uint64)])
 
 
+class SpdmObsNoiseTensor(ctypes.Structure):
+    """spdm_obs_noise_tensor (include/spdm.h)."""
+    _fields_ = [("d_src", c_void_p), ("d_dst", c_void_p), ("inner", c_int64), ("src_stride", c_int64), ("dst_stride", c_int64)]
+
+
+class SpdmObsNoiseArgs(ctypes.Structure):
+    """spdm_obs_noise_args (include/spdm.h)."""
+    _fields_ = [("n_rows", c_int64), ("row_offset", c_int64), ("seed", c_uint64), ("draw", ctypes.c_uint32), ("alpha", c_float),
+                ("n_tensors", c_int32), ("reserved", c_int32), ("tensors", SpdmObsNoiseTensor * 4)]
+
+
 class SpdmLossTermsArgs(ctypes.Structure):
     """spdm_loss_terms_args (include/spdm.h)."""
     _fields_ = ([(n, c_int32) for n in ("B", "H", "D", "reserved")] + [("d_eps", c_void_p), ("d_noise", c_void_p)] +
@@ -117,6 +128,7 @@ SYMBOLS = {
     "spdm_eval_errors": (c_int32, [c_int32, POINTER(SpdmEvalErrorsArgs), c_void_p]),
     "spdm_eval_reduce": (c_int32, [c_int32, POINTER(SpdmEvalReduceArgs), c_void_p]),
     "spdm_eval_reduce_workspace_doubles": (c_size_t, [c_int64, c_int32]),
+    "spdm_obs_noise": (c_int32, [c_int32, POINTER(SpdmObsNoiseArgs), c_void_p]),
     "spdm_loss_terms": (c_int32, [c_int32, POINTER(SpdmLossTermsArgs), c_void_p]),
     "spdm_train_set_time_scale": (c_int32, [c_void_p, c_void_p, c_int32]),
     "spdm_sample_begin": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,

@@ -465,6 +465,35 @@ struct EvalReduceArgs {
 // five launches on s, each ordered behind the one before: per-window statistics, then sum / mean / squares / std over all rows
 hipError_t launch_eval_reduce(const EvalReduceArgs& a, hipStream_t s);
 
+// ---- uniform noise on the observations of a batch of windows (obs_noise.hip; spdm_obs_noise) ---------------
+constexpr int OBS_NOISE_MAX_TENSORS = 4;
+constexpr int OBS_NOISE_ITEMS = 1024;  // quads (of four elements) one workgroup perturbs
+struct ObsNoiseTensor {
+    const float* src;                  // rows of src_stride elements; may equal dst
+    float* dst;                        // rows of dst_stride elements
+    long long inner, src_stride, dst_stride;       // 0 <= inner <= both strides: elements [0, inner) of a row are perturbed
+    // filled by plan_obs_noise:
+    unsigned nq;                       // quads per row, ceil(inner / 4)
+    unsigned block_begin;              // first workgroup of this tensor
+    unsigned chunks_per_row;           // nq >= OBS_NOISE_ITEMS: workgroups a row is cut into; else 1
+    unsigned rows_per_block;           // nq <  OBS_NOISE_ITEMS: whole rows a workgroup takes; else 1
+    int vec;                           // both pointers 16-byte aligned, inner and both strides multiples of 4: 16-byte accesses
+};
+struct ObsNoiseArgs {
+    unsigned long long n_rows, row_offset;         // row_offset + n_rows <= 2^32: checked by the host
+    unsigned long long seed;
+    unsigned draw;
+    float alpha;
+    int n_tensors;                     // 1 .. OBS_NOISE_MAX_TENSORS; tensor i draws from Philox purpose 4 + i
+    unsigned blocks;                   // filled by plan_obs_noise
+    ObsNoiseTensor t[OBS_NOISE_MAX_TENSORS];
+};
+// host only: the launch geometry of a; false when a row has 2^32 quads or more, a stride is below inner, or the grid would
+// exceed 2^31 - 1 workgroups
+bool plan_obs_noise(ObsNoiseArgs& a);
+// one launch of a.blocks workgroups (none when every inner is 0); a has been through plan_obs_noise
+hipError_t launch_obs_noise(const ObsNoiseArgs& a, hipStream_t s);
+
 // ---- per-sample terms of a validation pass's loss (train_metrics.hip; spdm_loss_terms) -------------------
 constexpr int LOSS_WAVES = 4;          // samples (one wave each) per workgroup
 struct LossTermsArgs {

@@ -2959,6 +2959,36 @@ extern "C" int spdm_eval_reduce(int32_t device, const spdm_eval_reduce_args* a, 
     return SPDM_OK;
 }
 
+// Uniform noise on up to four observation tensors in one launch (include/spdm.h, obs_noise.hip).  Stateless.
+extern "C" int spdm_obs_noise(int32_t device, const spdm_obs_noise_args* a, void* stream) {
+    if (!a) return fail(SPDM_ERR_INVALID, "obs_noise: null argument");
+    if (a->n_rows < 1) return fail(SPDM_ERR_INVALID, "obs_noise: n_rows = %lld must be >= 1", (long long)a->n_rows);
+    if (a->n_tensors < 1 || a->n_tensors > OBS_NOISE_MAX_TENSORS)
+        return fail(SPDM_ERR_INVALID, "obs_noise: n_tensors = %d outside [1, %d]", a->n_tensors, OBS_NOISE_MAX_TENSORS);
+    if (a->row_offset < 0 || a->row_offset > (1LL << 32) || a->n_rows > (1LL << 32) - a->row_offset)
+        return fail(SPDM_ERR_INVALID, "obs_noise: rows [%lld, %lld + %lld) do not fit 32 bits", (long long)a->row_offset,
+                    (long long)a->row_offset, (long long)a->n_rows);
+    if (!(a->alpha >= 0.f && a->alpha <= 3.402823466e+38f)) return fail(SPDM_ERR_INVALID, "obs_noise: alpha = %g must be finite and >= 0", (double)a->alpha);
+    ObsNoiseArgs k = {};
+    k.n_rows = (unsigned long long)a->n_rows; k.row_offset = (unsigned long long)a->row_offset; k.seed = a->seed; k.draw = a->draw;
+    k.alpha = a->alpha; k.n_tensors = a->n_tensors;
+    for (int i = 0; i < a->n_tensors; ++i) {
+        const spdm_obs_noise_tensor& t = a->tensors[i];
+        if (t.inner < 0) return fail(SPDM_ERR_INVALID, "obs_noise: tensor %d: inner = %lld is negative", i, (long long)t.inner);
+        if (t.src_stride < t.inner || t.dst_stride < t.inner)
+            return fail(SPDM_ERR_INVALID, "obs_noise: tensor %d: strides %lld and %lld are below inner = %lld", i, (long long)t.src_stride,
+                        (long long)t.dst_stride, (long long)t.inner);
+        if (t.inner / 4 + 1 > 0xffffffffLL) return fail(SPDM_ERR_INVALID, "obs_noise: tensor %d: inner = %lld holds more than 2^32 - 2 quads", i, (long long)t.inner);
+        if (t.inner > 0 && (!t.d_src || !t.d_dst)) return fail(SPDM_ERR_INVALID, "obs_noise: tensor %d: null pointer", i);
+        k.t[i].src = t.d_src; k.t[i].dst = t.d_dst; k.t[i].inner = t.inner; k.t[i].src_stride = t.src_stride; k.t[i].dst_stride = t.dst_stride;
+    }
+    if (!plan_obs_noise(k)) return fail(SPDM_ERR_INVALID, "obs_noise: the launch would exceed 2^31 - 1 workgroups of %d quads", OBS_NOISE_ITEMS);
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(launch_obs_noise(k, (hipStream_t)stream));
+    if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));
+    return SPDM_OK;
+}
+
 // The per-sample terms of a validation pass's loss in one launch (include/spdm.h, train_metrics.hip).  Stateless.
 extern "C" int spdm_loss_terms(int32_t device, const spdm_loss_terms_args* a, void* stream) {
     if (!a) return fail(SPDM_ERR_INVALID, "loss_terms: null argument");

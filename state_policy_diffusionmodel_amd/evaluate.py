@@ -9,10 +9,15 @@ answered for every window of a dataset, ``--runs`` times each, on the device.
 ``episode_ends``; any other path is opened as a zarr store with the reference's layout, which needs the zarr package and is
 NOT covered by the tests.  ``--stats`` is the ``[stats]`` pickle the training run saved (``CarRacingDataModule.save_stats``,
 utils/data_utils.py:42-44); it is read by an unpickler that admits numpy arrays and plain containers only.  Without it the
-statistics are computed from the data."""
+statistics are computed from the data.
+
+``--noise_levels 0,0.01,0.05`` also asks the question of evaluation/eval_robustness.py -- how much worse does the prediction get
+when the observations are noisy? -- with ``evaluation.robustness`` at ``--runs`` runs per window, and writes its report under
+``"robustness"`` in the JSON.  Without the flag the output is what it was."""
 from __future__ import annotations
 
 import argparse
+import json
 import pickle
 import time
 
@@ -64,6 +69,8 @@ def parse_arguments(argv=None):
     p.add_argument("--batch_size", type=int, default=4096)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--no_actions", action="store_true", help="position error only")
+    p.add_argument("--noise_levels", type=str, default=None, help="comma-separated alphas: also measure the error under alpha * U[0,1) "
+                                                                    "added to the observations (evaluation.robustness)")
     p.add_argument("--out", type=str, default=None, help="report.json")
     return p.parse_args(argv)
 
@@ -72,7 +79,7 @@ def main(argv=None):
     args = parse_arguments(argv)
     from .dataset import DeviceDataset
     from .diffusion import load_model
-    from .evaluation import evaluate
+    from .evaluation import evaluate, robustness
     from .weights import fetch_hyperparams_from_yaml
     model = load_model(args.model_name, args.checkpoint, args.hparams, num_of_ddim_steps=args.ddim_steps, max_batch=args.batch_size)
     step_size = int(args.step_size or dict(fetch_hyperparams_from_yaml(args.hparams)).get("step_size", 1))
@@ -85,9 +92,17 @@ def main(argv=None):
     print(f"*** {len(dataset)} windows x {args.runs} runs in {time.time() - start:.2f} s")
     print("mean position error per step:", np.array2string(report.mean_error, precision=4))
     print("std  position error per step:", np.array2string(report.std_error, precision=4))
+    robust = None
+    if args.noise_levels is not None:
+        levels = [float(v) for v in args.noise_levels.split(",")]
+        start = time.time()
+        robust = robustness(model, dataset, levels=levels, runs=args.runs, batch_size=args.batch_size, seed=args.seed)
+        print(f"*** {len(levels)} noise levels in {time.time() - start:.2f} s")
+        for name in ("mse_position", "mse_action"):
+            print(f"{name} per level:", np.array2string(getattr(robust, name), precision=6))
     if args.out:
         with open(args.out, "w") as f:
-            f.write(report.to_json())
+            f.write(report.to_json() if robust is None else json.dumps({**report.to_dict(), "robustness": robust.to_dict()}))
     return report
 
 

@@ -7,10 +7,15 @@ Replaces the head of the reference's ``training_step`` (models/diffusion_ddpm.py
 ``(seed, step, global sample index)``: Philox4x32-10 streams apart from the sampler's, so a shard of a batch
 (``sample_offset = rank * B``, distributed.py's convention) draws exactly what the whole batch would.  Given device
 tensors, the call is that one launch on torch's current stream (a host ``t`` or ``noise`` is uploaded first, which waits),
-and every result stays on the device."""
+and every result stays on the device.
+
+``perturb_observations`` adds ``alpha * U[0, 1)`` to the observed part of a batch of windows, as the reference's
+evaluation/eval_robustness.py:180-190 does with four ``torch.rand_like``, in ONE HIP launch (``spdm_obs_noise``, DESIGN.md
+8.13); its randomness is a pure function of ``(seed, draw, tensor, global row, element)``."""
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Optional
 
 import torch
@@ -83,4 +88,64 @@ def forward_process(x0: torch.Tensor, inpaint: Optional[torch.Tensor], sqrt_abar
     return out + (ts,) if ts is not None else out
 
 
-__all__ = ["forward_process"]
+OBSERVATION_KEYS = ("image", "position", "velocity", "action")      # in this order: Philox purposes 4, 5, 6, 7
+
+
+def add_uniform_noise(tensors, alpha: float, *, n_rows: int, seed: int = 0, draw: int = 0, row_offset: int = 0) -> None:
+    """One ``spdm_obs_noise`` launch on torch's current stream.  ``tensors``: up to four ``(src, dst, inner, src_stride,
+    dst_stride)`` with ``src`` / ``dst`` contiguous float32 device tensors read as ``n_rows`` rows of ``*_stride`` elements from
+    their first element (``dst`` may be ``src``; a view that starts anywhere is fine): ``dst[row][e] = src[row][e] + alpha *
+    u(row_offset + row, e)`` for ``e < inner``, nothing else is read or written.  Tensor ``i`` draws Philox purpose ``4 + i``."""
+    tensors = list(tensors)
+    if not 1 <= len(tensors) <= 4:
+        raise ValueError(f"{len(tensors)} tensors: one launch takes 1 to 4")
+    n_rows = int(n_rows)
+    if n_rows < 1:
+        raise ValueError(f"n_rows = {n_rows} must be >= 1")
+    dev = tensors[0][0].device
+    if dev.type != "cuda":
+        raise ValueError("add_uniform_noise runs on the GPU: it takes device tensors (there is no CPU fallback)")
+    a = _lib.SpdmObsNoiseArgs(n_rows=n_rows, row_offset=int(row_offset), seed=int(seed) & 0xFFFFFFFFFFFFFFFF, draw=int(draw) & 0xFFFFFFFF,
+                              alpha=float(alpha), n_tensors=len(tensors), reserved=0)
+    for i, (src, dst, inner, src_stride, dst_stride) in enumerate(tensors):
+        inner, src_stride, dst_stride = int(inner), int(src_stride), int(dst_stride)
+        if inner < 0 or src_stride < inner or dst_stride < inner:
+            raise ValueError(f"tensor {i}: inner = {inner} must be >= 0 and at most the strides {src_stride} and {dst_stride}")
+        for name, t, stride in (("src", src, src_stride), ("dst", dst, dst_stride)):
+            if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"tensor {i}: {name} must be a contiguous float32 tensor on {dev}")
+            if inner and (n_rows - 1) * stride + inner > t.numel():
+                raise ValueError(f"tensor {i}: {n_rows} rows of stride {stride} and {inner} elements do not fit {name}'s {t.numel()} elements")
+        a.tensors[i] = _lib.SpdmObsNoiseTensor(d_src=src.data_ptr(), d_dst=dst.data_ptr(), inner=inner, src_stride=src_stride,
+                                               dst_stride=dst_stride)
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(_lib.load().spdm_obs_noise(index, ctypes.byref(a), stream), "spdm_obs_noise")
+
+
+def perturb_observations(batch: dict, alpha: float, *, obs_horizon: int, seed: int = 0, draw: int = 0, row_offset: int = 0) -> dict:
+    """A new dict with ``image``, ``position``, ``velocity`` and ``action`` of ``batch`` (a ``DeviceDataset.batch`` dict: float32
+    device tensors ``(B, n, ...)`` with ``n >= obs_horizon``) cut to their first ``obs_horizon`` rows and perturbed:
+    ``out[k] = batch[k][:, :obs_horizon] + alpha * u`` with ``u`` uniform in [0, 1), in one ``spdm_obs_noise`` launch on torch's
+    current stream.  ``batch`` itself is not written.  Window ``b`` of the batch draws the stream of row ``row_offset + b``,
+    ``draw`` selects an independent set of streams (``evaluation.robustness`` passes the noise level's number)."""
+    obs_h = int(obs_horizon)
+    if obs_h < 1:
+        raise ValueError(f"obs_horizon = {obs_h} must be >= 1")
+    missing = [k for k in OBSERVATION_KEYS if k not in batch]
+    if missing:
+        raise KeyError(f"batch holds no {missing}")
+    B = batch[OBSERVATION_KEYS[0]].shape[0]
+    out, tensors = {}, []
+    for k in OBSERVATION_KEYS:
+        t = batch[k]
+        if t.dim() < 3 or t.shape[0] != B or t.shape[1] < obs_h:
+            raise ValueError(f"batch[{k!r}] is {tuple(t.shape)}: expected {B} windows of at least {obs_h} rows")
+        per_row = math.prod(t.shape[2:])
+        out[k] = torch.empty((B, obs_h) + tuple(t.shape[2:]), dtype=torch.float32, device=t.device)
+        tensors.append((t, out[k], obs_h * per_row, t.shape[1] * per_row, obs_h * per_row))
+    add_uniform_noise(tensors, alpha, n_rows=B, seed=seed, draw=draw, row_offset=row_offset)
+    return out
+
+
+__all__ = ["forward_process", "add_uniform_noise", "perturb_observations", "OBSERVATION_KEYS"]
