@@ -473,6 +473,114 @@ typedef struct {
 } spdm_obs_noise_args;
 int  spdm_obs_noise(int32_t device, const spdm_obs_noise_args* a, void* stream);
 
+/* The closed-loop caller's host side for E environments in lockstep (policy.hip): the observation history as
+ * rings in device memory, the conditioning batch built from them, and the plan back in the dataset's units.  Replaces the four
+ * deque(maxlen = obs_horizon step_size) of run_predictions.py:112-124 and :145-148, prepare_diffusion_batch (:30-60) and the
+ * .cpu() + unnormalize_position of :158-164.  The three entry points are stateless: the rings are the caller's device memory
+ * and the push count n is the caller's.  Each is ONE launch enqueued on `stream` (NULL: the null stream, and the call
+ * synchronises), with no atomics and no host synchronisation otherwise.  L slots per environment; the reference has
+ * L = obs_horizon step_size.
+ *
+ * spdm_policy_push writes push number n (0-based) of all E environments into slot n mod L.
+ *   img_dtype: 0 = frames are uint8, 1 = float32, in d_img_in and in d_ring_img alike;  reserved: ignored;
+ *   d_img_in (E,96,96,3), d_pos_in (E,2), d_vel_in (E,2), d_act_in (E,3) float32: one observation per environment, RAW;
+ *   d_ring_img (E,L,96,96,3), d_ring_pos (E,L,2), d_ring_vel (E,L,2), d_ring_act (E,L,3): the rings, RAW copies;
+ *   d_fill (E) int32, read only: where it is non-zero the observation goes into ALL L slots of that environment -- the initial
+ *     fill of run_predictions.py:120-124, and what a reset means.  The caller clears it after the push.
+ *   A frame moves in 16-byte pieces on both sides, 1728 (uint8) or 6912 (float32) of them; d_img_in and d_ring_img must be
+ *   16-byte aligned (every frame then is: a frame is a whole number of pieces).
+ * SPDM_ERR_INVALID, before the GPU is touched: NULL args; E or L < 1; E x L beyond 31 bits; n < 0; an unknown img_dtype; any
+ * NULL pointer; a misaligned d_img_in or d_ring_img. */
+typedef struct {
+    int32_t E;
+    int32_t L;
+    int32_t img_dtype;
+    int32_t reserved;
+    int64_t n;
+    const void* d_img_in;
+    const float* d_pos_in;
+    const float* d_vel_in;
+    const float* d_act_in;
+    const int32_t* d_fill;
+    void* d_ring_img;
+    float* d_ring_pos;
+    float* d_ring_vel;
+    float* d_ring_act;
+} spdm_policy_push_args;
+int  spdm_policy_push(int32_t device, const spdm_policy_push_args* a, void* stream);
+
+/* spdm_policy_window builds the batch of list(deque)[::step_size] after n pushes (n >= 1): entry k < obs_h of environment e
+ * is slot (n + k step_size) mod L.  Entry 0 is the oldest one, the slot the next push overwrites; with L = obs_h step_size
+ * the entries are the deque's elements 0, step_size, 2 step_size, ...  L >= (obs_h - 1) step_size + 1 is required, so that the
+ * entries are distinct slots.
+ *   stats_f32: bit 0 set = the velocity statistics are float32 arrays, bit 1 set = the action statistics are;
+ *   pos_min, pos_max: the scalar position statistics;  vel_min, vel_max, act_min, act_max: per channel (float32 statistics
+ *     widened to double, which is exact).
+ * Outputs, float32, each may be NULL to skip it:
+ *   d_image_out (E,obs_h,3,96,96), planar, 16-byte aligned: (float)k / 255.0f, one correctly rounded division, for uint8; a
+ *     copy for float32;
+ *   d_position_out (E,obs_h,2), d_translation_out (E,2): in float32, every operation rounded on its own (no FMA), as
+ *     normalize_position (utils/data_utils.py:28-33) computes on a CPU float32 tensor with scalar float64 statistics:
+ *       sn = ((x - (float)pos_min) / (float)(pos_max - pos_min)) * 2.0f - 1.0f, the range formed in float64 and rounded once;
+ *       translation = sn of entry 0;  position = (sn - translation) / 2.0f;
+ *   d_velocity_out (E,obs_h,2), d_action_out (E,obs_h,3): normalize_data (utils/data_utils.py:18-21) per channel.  torch
+ *     promotes by the dtype of the statistics ARRAYS:
+ *       float64 statistics: (float)((((double)x - min) / (max - min)) * 2.0 - 1.0), float64 operations rounded on their own,
+ *         the result rounded once to float32 (the model's .float());
+ *       float32 statistics: ((x - min) / (max - min)) * 2.0f - 1.0f in float32, every operation rounded on its own.
+ * SPDM_ERR_INVALID, before the GPU is touched: NULL args; E, L, obs_h or step_size < 1; (obs_h - 1) step_size >= L; E x L or
+ * E x obs_h x 3 beyond 31 bits; n < 1; an unknown img_dtype; stats_f32 outside [0, 3]; no output at all; a NULL ring that a
+ * requested output reads; a misaligned d_ring_img or d_image_out. */
+typedef struct {
+    int32_t E;
+    int32_t L;
+    int32_t obs_h;
+    int32_t step_size;
+    int32_t img_dtype;
+    int32_t stats_f32;
+    int64_t n;
+    const void* d_ring_img;
+    const float* d_ring_pos;
+    const float* d_ring_vel;
+    const float* d_ring_act;
+    double pos_min;
+    double pos_max;
+    double vel_min[2];
+    double vel_max[2];
+    double act_min[3];
+    double act_max[3];
+    float* d_image_out;
+    float* d_position_out;
+    float* d_velocity_out;
+    float* d_action_out;
+    float* d_translation_out;
+} spdm_policy_window_args;
+int  spdm_policy_window(int32_t device, const spdm_policy_window_args* a, void* stream);
+
+/* spdm_policy_unnormalize turns the sampler's x_0 into way-points and actions in the dataset's units.
+ *   d_x0 (E,H,D) float32;  d_translation (E,2) float32, as spdm_policy_window emits it;  inp_h: rows of x_0 before the first
+ *     predicted step;  P = H - inp_h;
+ *   d_waypoints (E,P,2) float64: U(x0[e, inp_h + j, 0:2]) with the U of spdm_eval_errors and (double)translation;
+ *   d_actions (E,P,3) float64, optional (NULL skips it): A(x0[e, inp_h + j, 2:5]) with the A of spdm_eval_errors.
+ * The two entry points share the device functions (csrc/unnormalize.h).
+ * SPDM_ERR_INVALID, before the GPU is touched: NULL args or a NULL d_x0, d_translation or d_waypoints; E < 1; inp_h < 0;
+ * H <= inp_h; D < 2, or D < 5 with d_actions; E x P beyond 31 bits. */
+typedef struct {
+    int32_t E;
+    int32_t H;
+    int32_t D;
+    int32_t inp_h;
+    const float* d_x0;
+    const float* d_translation;
+    double pos_min;
+    double pos_max;
+    double act_min[3];
+    double act_max[3];
+    double* d_waypoints;
+    double* d_actions;
+} spdm_policy_unnormalize_args;
+int  spdm_policy_unnormalize(int32_t device, const spdm_policy_unnormalize_args* a, void* stream);
+
 /* The per-sample terms of a validation pass's loss in ONE launch (train_metrics.hip).  Replaces: nn.MSELoss
  * of the reference's validation_step (models/diffusion_ddpm.py:175-214, :49) as Lightning averages it over an epoch, weighted by
  * batch size: with H x D elements in every sample that is the mean over the samples of each sample's own mean squared error.

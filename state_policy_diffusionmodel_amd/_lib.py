@@ -90,6 +90,29 @@ class SpdmObsNoiseArgs(ctypes.Structure):
                 ("n_tensors", c_int32), ("reserved", c_int32), ("tensors", SpdmObsNoiseTensor * 4)]
 
 
+class SpdmPolicyPushArgs(ctypes.Structure):
+    """spdm_policy_push_args (include/spdm.h)."""
+    _fields_ = ([(n, c_int32) for n in ("E", "L", "img_dtype", "reserved")] + [("n", c_int64)] +
+                [(n, c_void_p) for n in ("d_img_in", "d_pos_in", "d_vel_in", "d_act_in", "d_fill", "d_ring_img", "d_ring_pos",
+                                         "d_ring_vel", "d_ring_act")])
+
+
+class SpdmPolicyWindowArgs(ctypes.Structure):
+    """spdm_policy_window_args (include/spdm.h)."""
+    _fields_ = ([(n, c_int32) for n in ("E", "L", "obs_h", "step_size", "img_dtype", "stats_f32")] + [("n", c_int64)] +
+                [(n, c_void_p) for n in ("d_ring_img", "d_ring_pos", "d_ring_vel", "d_ring_act")] +
+                [("pos_min", c_double), ("pos_max", c_double), ("vel_min", c_double * 2), ("vel_max", c_double * 2),
+                 ("act_min", c_double * 3), ("act_max", c_double * 3)] +
+                [(n, c_void_p) for n in ("d_image_out", "d_position_out", "d_velocity_out", "d_action_out", "d_translation_out")])
+
+
+class SpdmPolicyUnnormalizeArgs(ctypes.Structure):
+    """spdm_policy_unnormalize_args (include/spdm.h)."""
+    _fields_ = ([(n, c_int32) for n in ("E", "H", "D", "inp_h")] + [("d_x0", c_void_p), ("d_translation", c_void_p)] +
+                [("pos_min", c_double), ("pos_max", c_double), ("act_min", c_double * 3), ("act_max", c_double * 3)] +
+                [("d_waypoints", c_void_p), ("d_actions", c_void_p)])
+
+
 class SpdmLossTermsArgs(ctypes.Structure):
     """spdm_loss_terms_args (include/spdm.h)."""
     _fields_ = ([(n, c_int32) for n in ("B", "H", "D", "reserved")] + [("d_eps", c_void_p), ("d_noise", c_void_p)] +
@@ -129,6 +152,9 @@ SYMBOLS = {
     "spdm_eval_reduce": (c_int32, [c_int32, POINTER(SpdmEvalReduceArgs), c_void_p]),
     "spdm_eval_reduce_workspace_doubles": (c_size_t, [c_int64, c_int32]),
     "spdm_obs_noise": (c_int32, [c_int32, POINTER(SpdmObsNoiseArgs), c_void_p]),
+    "spdm_policy_push": (c_int32, [c_int32, POINTER(SpdmPolicyPushArgs), c_void_p]),
+    "spdm_policy_window": (c_int32, [c_int32, POINTER(SpdmPolicyWindowArgs), c_void_p]),
+    "spdm_policy_unnormalize": (c_int32, [c_int32, POINTER(SpdmPolicyUnnormalizeArgs), c_void_p]),
     "spdm_loss_terms": (c_int32, [c_int32, POINTER(SpdmLossTermsArgs), c_void_p]),
     "spdm_train_set_time_scale": (c_int32, [c_void_p, c_void_p, c_int32]),
     "spdm_sample_begin": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,

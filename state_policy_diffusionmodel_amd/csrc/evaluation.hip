@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "unnormalize.h"
 
 #pragma clang fp contract(off)
 
@@ -26,18 +27,6 @@ namespace spdm {
 namespace {
 
 constexpr int THREADS = 256;
-
-// utils/data_utils.py:35-40 in float64: ((n 2 + translation) + 1) / 2 (max - min) + min
-__device__ __forceinline__ double unnormalize_position(float n, double tr, double lo, double range) {
-    const double s = (double)n * 2.0 + tr;
-    return (s + 1.0) / 2.0 * range + lo;
-}
-
-// utils/data_utils.py:23-26 on a float32 array with float64 statistics: (n + 1) / 2 stays float32, the rest is float64
-__device__ __forceinline__ double unnormalize_action(float n, double lo, double range) {
-    const float h = (n + 1.0f) / 2.0f;
-    return (double)h * range + lo;
-}
 
 __global__ __launch_bounds__(THREADS) void eval_errors_kernel(const EvalErrorsArgs a) {
     const long long g = (long long)blockIdx.x * THREADS + threadIdx.x;        // (trajectory, prediction step)

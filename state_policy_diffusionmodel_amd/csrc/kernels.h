@@ -494,6 +494,57 @@ bool plan_obs_noise(ObsNoiseArgs& a);
 // one launch of a.blocks workgroups (none when every inner is 0); a has been through plan_obs_noise
 hipError_t launch_obs_noise(const ObsNoiseArgs& a, hipStream_t s);
 
+// ---- the closed-loop policy's observation history and plan (policy.hip; spdm_policy_*) --------------------
+constexpr int POLICY_PUSH_PIECES = 1024;           // 16-byte pieces of one frame a workgroup of the push copies (4 per thread)
+struct PolicyPushArgs {
+    int E, L, img_dtype;               // environments, ring slots per environment, 0 uint8 / 1 fp32
+    int slot;                          // n % L: the slot push n goes to
+    int frame_pieces;                  // filled by the launch: 1728 (uint8) or 6912 (fp32) 16-byte pieces per frame
+    int chunks;                        // filled by the launch: ceil(frame_pieces / POLICY_PUSH_PIECES) workgroups per environment
+    int img_blocks;                    // filled by the launch: E x chunks
+    const void* img_in;                // (E, 96, 96, 3), 16-byte aligned
+    const float* pos_in;               // (E, 2)
+    const float* vel_in;               // (E, 2)
+    const float* act_in;               // (E, 3)
+    const int* fill;                   // (E): non-zero -> the observation goes into all L slots
+    void* ring_img;                    // (E, L, 96, 96, 3), 16-byte aligned
+    float* ring_pos;                   // (E, L, 2)
+    float* ring_vel;                   // (E, L, 2)
+    float* ring_act;                   // (E, L, 3)
+};
+// one launch of E x chunks + ceil(E / 256) workgroups
+hipError_t launch_policy_push(PolicyPushArgs a, hipStream_t s);
+
+struct PolicyWindowArgs {
+    int E, L, obs_h, step_size, img_dtype;
+    int first;                         // n % L: the slot of the oldest entry (the one the next push overwrites)
+    int vel_f32, act_f32;              // the statistics arrays' precision: 1 float32 arithmetic, 0 float64 rounded once
+    int img_blocks;                    // filled by the launch: E obs_h x 3 frame slices (0 without image_out)
+    const void* ring_img;
+    const float* ring_pos;
+    const float* ring_vel;
+    const float* ring_act;
+    double pos_min, pos_max, vel_min[2], vel_max[2], act_min[3], act_max[3];
+    float* image_out;                  // (E, obs_h, 3, 96, 96), 16-byte aligned, or null
+    float* position_out;               // (E, obs_h, 2) or null
+    float* velocity_out;               // (E, obs_h, 2) or null
+    float* action_out;                 // (E, obs_h, 3) or null
+    float* translation_out;            // (E, 2) or null
+};
+// one launch of E obs_h x 3 + ceil(E obs_h / 256) workgroups
+hipError_t launch_policy_window(PolicyWindowArgs a, hipStream_t s);
+
+struct PolicyUnnormalizeArgs {
+    int E, H, D, inp_h;
+    const float* x0;                   // (E, H, D)
+    const float* translation;          // (E, 2)
+    double pos_min, pos_max, act_min[3], act_max[3];
+    double* waypoints;                 // (E, H - inp_h, 2)
+    double* actions;                   // (E, H - inp_h, 3) or null
+};
+// one launch of ceil(E (H - inp_h) / 256) workgroups
+hipError_t launch_policy_unnormalize(const PolicyUnnormalizeArgs& a, hipStream_t s);
+
 // ---- per-sample terms of a validation pass's loss (train_metrics.hip; spdm_loss_terms) -------------------
 constexpr int LOSS_WAVES = 4;          // samples (one wave each) per workgroup
 struct LossTermsArgs {

@@ -1,0 +1,181 @@
+// policy.hip -- the closed-loop caller's host side on the device: the observation history of E environments as rings in HBM,
+// the conditioning batch built from them, and the plan back in the dataset's units (spdm_policy_push, spdm_policy_window,
+// spdm_policy_unnormalize).
+//
+// Replaces: the four deque(maxlen = obs_horizon step_size) of run_predictions.py:112-124 and their appends (:145-148),
+// prepare_diffusion_batch (:30-60: list(deque)[::s], torch.tensor(..., float32) over every frame of the window, / 255, permute,
+// normalize_data, normalize_position, all on the host, and the host-to-device copy of the result), and the .cpu() and
+// unnormalize_position of :158-164.
+//
+// Push: ONE launch.  Workgroups [0, E x chunks) each copy up to 1024 16-byte pieces of one environment's frame, four per
+// thread with all four loads in flight before the first store, into slot n % L of that environment's ring -- or, where the
+// environment's fill word is set, into all L slots (the value is loaded once).  The workgroups after them write the seven
+// low-dimensional floats, one thread per environment.
+// Window: ONE launch.  Workgroups [0, E obs_h x 3) each turn a third of one ring frame into planar CHW fp32 (frame_tiles.h,
+// shared with dataset.hip); the workgroups after them normalise the low-dimensional rows, one thread per (environment, entry).
+// Unnormalise: ONE launch, one thread per (environment, predicted step), with the U and A of spdm_eval_errors (unnormalize.h).
+//
+// Arithmetic of the window: that of utils/data_utils.py:18-33 on CPU float32 torch tensors (include/spdm.h), written with the
+// _rn intrinsics so that no two operations are ever contracted into an FMA.
+//
+// Safety: every index is built from scalars the host entry points have validated (include/spdm.h); a slot is (first + k
+// step_size) mod L with first in [0, L), so it lies in [0, L).  The fill words are read, never used as an index.  No atomics.
+#include <hip/hip_runtime.h>
+
+#include "frame_tiles.h"
+#include "kernels.h"
+#include "unnormalize.h"
+
+namespace spdm {
+
+namespace {
+
+using frame_tiles::FRAME_PIX;
+using frame_tiles::SLICES;
+constexpr int THREADS = frame_tiles::THREADS;
+constexpr int PUSH_PER_THREAD = POLICY_PUSH_PIECES / THREADS;          // 4
+static_assert(POLICY_PUSH_PIECES % THREADS == 0, "push chunk shape");
+
+__global__ __launch_bounds__(THREADS) void policy_push_kernel(const PolicyPushArgs a) {
+    const int blk = blockIdx.x;
+    if (blk < a.img_blocks) {                                          // uniform per workgroup
+        const int e = blk / a.chunks, chunk = blk - e * a.chunks;      // e < E
+        const bool fill = a.fill[e] != 0;
+        const uint4* src = static_cast<const uint4*>(a.img_in) + (size_t)e * a.frame_pieces;
+        uint4* ring = static_cast<uint4*>(a.ring_img) + (size_t)e * a.L * a.frame_pieces;
+        uint4 v[PUSH_PER_THREAD] = {};
+        int p[PUSH_PER_THREAD];
+#pragma unroll
+        for (int k = 0; k < PUSH_PER_THREAD; ++k) {
+            p[k] = chunk * POLICY_PUSH_PIECES + k * THREADS + threadIdx.x;
+            if (p[k] < a.frame_pieces) v[k] = src[p[k]];
+        }
+        const int s0 = fill ? 0 : a.slot, s1 = fill ? a.L : a.slot + 1;        // slot < L: checked by the host
+        for (int s = s0; s < s1; ++s) {
+            uint4* dst = ring + (size_t)s * a.frame_pieces;
+#pragma unroll
+            for (int k = 0; k < PUSH_PER_THREAD; ++k)
+                if (p[k] < a.frame_pieces) dst[p[k]] = v[k];
+        }
+        return;
+    }
+    const int e = (blk - a.img_blocks) * THREADS + threadIdx.x;
+    if (e >= a.E) return;
+    const bool fill = a.fill[e] != 0;
+    const size_t e2 = (size_t)e * 2, e3 = (size_t)e * 3;
+    const float px = a.pos_in[e2], py = a.pos_in[e2 + 1], vx = a.vel_in[e2], vy = a.vel_in[e2 + 1];
+    const float a0 = a.act_in[e3], a1 = a.act_in[e3 + 1], a2 = a.act_in[e3 + 2];
+    const int s0 = fill ? 0 : a.slot, s1 = fill ? a.L : a.slot + 1;
+    for (int s = s0; s < s1; ++s) {
+        const size_t i = (size_t)e * a.L + s;
+        a.ring_pos[i * 2] = px; a.ring_pos[i * 2 + 1] = py;
+        a.ring_vel[i * 2] = vx; a.ring_vel[i * 2 + 1] = vy;
+        a.ring_act[i * 3] = a0; a.ring_act[i * 3 + 1] = a1; a.ring_act[i * 3 + 2] = a2;
+    }
+}
+
+// normalize_data on a float32 tensor with float32 statistics: every operation a float32 operation rounded on its own
+__device__ __forceinline__ float normalize_f32(float x, float lo, float range) {
+    return __fsub_rn(__fmul_rn(__fdiv_rn(__fsub_rn(x, lo), range), 2.0f), 1.0f);
+}
+
+// ... with float64 statistics arrays: torch promotes to float64; the model's .float() rounds once
+__device__ __forceinline__ float normalize_f64(float x, double lo, double range) {
+    return (float)__dsub_rn(__dmul_rn(__ddiv_rn(__dsub_rn((double)x, lo), range), 2.0), 1.0);
+}
+
+__device__ __forceinline__ float normalize_channel(float x, double lo, double hi, int f32) {
+    if (f32) return normalize_f32(x, (float)lo, __fsub_rn((float)hi, (float)lo));       // the statistics are float32 values: exact
+    return normalize_f64(x, lo, __dsub_rn(hi, lo));
+}
+
+template <typename T>                                                  // T: the ring's frame element, unsigned char or float
+__global__ __launch_bounds__(THREADS) void policy_window_kernel(const PolicyWindowArgs a) {
+    __shared__ uint4 lds[frame_tiles::slice_pieces<T>()];              // one slice: 9 KiB (uint8) or 36 KiB (fp32)
+    const int blk = blockIdx.x;
+    if (blk < a.img_blocks) {                                          // uniform per workgroup
+        const int f = blk / SLICES, slice = blk - f * SLICES;          // f = e * obs_h + k < E * obs_h
+        const int e = f / a.obs_h, k = f - e * a.obs_h;
+        const int slot = (int)(((long long)a.first + (long long)k * a.step_size) % a.L);
+        const size_t frame = (size_t)e * a.L + slot;
+        frame_tiles::slice_to_planar<T>(static_cast<const char*>(a.ring_img) + frame * FRAME_PIX * 3 * sizeof(T), slice,
+                                        a.image_out + (size_t)f * 3 * FRAME_PIX, lds);
+        return;
+    }
+    const int g = (blk - a.img_blocks) * THREADS + threadIdx.x;        // (environment, entry)
+    if (g >= a.E * a.obs_h) return;
+    const int e = g / a.obs_h, k = g - e * a.obs_h;
+    const size_t row0 = (size_t)e * a.L + a.first;                                       // entry 0: the oldest
+    const size_t row = (size_t)e * a.L + (int)(((long long)a.first + (long long)k * a.step_size) % a.L);
+    if (a.position_out != nullptr || a.translation_out != nullptr) {
+        const float lo = (float)a.pos_min, range = (float)__dsub_rn(a.pos_max, a.pos_min);       // the range is formed in float64
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const float sn0 = normalize_f32(a.ring_pos[row0 * 2 + c], lo, range);           // translation = sn of entry 0
+            const float sn = normalize_f32(a.ring_pos[row * 2 + c], lo, range);
+            if (a.position_out != nullptr) a.position_out[(size_t)g * 2 + c] = __fdiv_rn(__fsub_rn(sn, sn0), 2.0f);
+            if (k == 0 && a.translation_out != nullptr) a.translation_out[(size_t)e * 2 + c] = sn0;
+        }
+    }
+    if (a.velocity_out != nullptr) {
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+            a.velocity_out[(size_t)g * 2 + c] = normalize_channel(a.ring_vel[row * 2 + c], a.vel_min[c], a.vel_max[c], a.vel_f32);
+    }
+    if (a.action_out != nullptr) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            a.action_out[(size_t)g * 3 + c] = normalize_channel(a.ring_act[row * 3 + c], a.act_min[c], a.act_max[c], a.act_f32);
+    }
+}
+
+__global__ __launch_bounds__(THREADS) void policy_unnormalize_kernel(const PolicyUnnormalizeArgs a) {
+    const int P = a.H - a.inp_h;
+    const long long g = (long long)blockIdx.x * THREADS + threadIdx.x;        // (environment, predicted step)
+    if (g >= (long long)a.E * P) return;
+    const int e = (int)(g / P), j = (int)(g - (long long)e * P);
+    const float* x = a.x0 + ((size_t)e * a.H + a.inp_h + j) * a.D;            // inp_h + j < H
+    const double range = __dsub_rn(a.pos_max, a.pos_min);
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+        a.waypoints[(size_t)g * 2 + c] = unnormalize_position(x[c], (double)a.translation[(size_t)e * 2 + c], a.pos_min, range);
+    if (a.actions != nullptr) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            a.actions[(size_t)g * 3 + c] = unnormalize_action(x[2 + c], a.act_min[c], __dsub_rn(a.act_max[c], a.act_min[c]));
+    }
+}
+
+}  // namespace
+
+hipError_t launch_policy_push(PolicyPushArgs a, hipStream_t s) {
+    if (a.E < 1 || a.L < 1 || a.slot < 0 || a.slot >= a.L || (a.img_dtype != 0 && a.img_dtype != 1)) return hipErrorInvalidValue;
+    a.frame_pieces = FRAME_PIX * 3 * (a.img_dtype == 0 ? 1 : 4) / 16;
+    a.chunks = (a.frame_pieces + POLICY_PUSH_PIECES - 1) / POLICY_PUSH_PIECES;
+    const long long img_blocks = (long long)a.E * a.chunks, low_blocks = ((long long)a.E + THREADS - 1) / THREADS;
+    if (img_blocks + low_blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    a.img_blocks = (int)img_blocks;
+    hipLaunchKernelGGL(policy_push_kernel, dim3((unsigned)(img_blocks + low_blocks)), dim3(THREADS), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_window(PolicyWindowArgs a, hipStream_t s) {
+    if (a.E < 1 || a.L < 1 || a.obs_h < 1 || a.step_size < 1 || a.first < 0 || a.first >= a.L) return hipErrorInvalidValue;
+    const long long img_blocks = a.image_out != nullptr ? (long long)a.E * a.obs_h * SLICES : 0;
+    const long long low_blocks = ((long long)a.E * a.obs_h + THREADS - 1) / THREADS;
+    if (img_blocks + low_blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    a.img_blocks = (int)img_blocks;
+    const dim3 grid((unsigned)(img_blocks + low_blocks));
+    if (a.img_dtype == 0) hipLaunchKernelGGL(policy_window_kernel<unsigned char>, grid, dim3(THREADS), 0, s, a);
+    else hipLaunchKernelGGL(policy_window_kernel<float>, grid, dim3(THREADS), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_unnormalize(const PolicyUnnormalizeArgs& a, hipStream_t s) {
+    const long long n = (long long)a.E * (a.H - a.inp_h);
+    if (a.E < 1 || a.inp_h < 0 || a.H <= a.inp_h || n > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(policy_unnormalize_kernel, dim3((unsigned)((n + THREADS - 1) / THREADS)), dim3(THREADS), 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace spdm

@@ -2989,6 +2989,82 @@ extern "C" int spdm_obs_noise(int32_t device, const spdm_obs_noise_args* a, void
     return SPDM_OK;
 }
 
+// One observation per environment into the history rings in one launch (include/spdm.h, policy.hip).  Stateless.
+extern "C" int spdm_policy_push(int32_t device, const spdm_policy_push_args* a, void* stream) {
+    if (!a) return fail(SPDM_ERR_INVALID, "policy_push: null argument");
+    if (a->E < 1 || a->L < 1) return fail(SPDM_ERR_INVALID, "policy_push: E, L = %d, %d must both be >= 1", a->E, a->L);
+    if ((long long)a->E * a->L > 0x7fffffffLL) return fail(SPDM_ERR_INVALID, "policy_push: E x L does not fit 31 bits");
+    if (a->n < 0) return fail(SPDM_ERR_INVALID, "policy_push: n = %lld is negative", (long long)a->n);
+    if (a->img_dtype != 0 && a->img_dtype != 1) return fail(SPDM_ERR_INVALID, "policy_push: img_dtype = %d is neither 0 (uint8) nor 1 (float32)", a->img_dtype);
+    if (!a->d_img_in || !a->d_pos_in || !a->d_vel_in || !a->d_act_in || !a->d_fill || !a->d_ring_img || !a->d_ring_pos || !a->d_ring_vel ||
+        !a->d_ring_act)
+        return fail(SPDM_ERR_INVALID, "policy_push: null pointer");
+    if (((uintptr_t)a->d_img_in | (uintptr_t)a->d_ring_img) & 15) return fail(SPDM_ERR_INVALID, "policy_push: d_img_in and d_ring_img must be 16-byte aligned");
+    PolicyPushArgs k = {};
+    k.E = a->E; k.L = a->L; k.img_dtype = a->img_dtype; k.slot = (int)(a->n % a->L);
+    k.img_in = a->d_img_in; k.pos_in = a->d_pos_in; k.vel_in = a->d_vel_in; k.act_in = a->d_act_in; k.fill = a->d_fill;
+    k.ring_img = a->d_ring_img; k.ring_pos = a->d_ring_pos; k.ring_vel = a->d_ring_vel; k.ring_act = a->d_ring_act;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(launch_policy_push(k, (hipStream_t)stream));
+    if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));
+    return SPDM_OK;
+}
+
+// The conditioning batch of the observation history in one launch (include/spdm.h, policy.hip).  Stateless.
+extern "C" int spdm_policy_window(int32_t device, const spdm_policy_window_args* a, void* stream) {
+    if (!a) return fail(SPDM_ERR_INVALID, "policy_window: null argument");
+    if (a->E < 1 || a->L < 1 || a->obs_h < 1 || a->step_size < 1)
+        return fail(SPDM_ERR_INVALID, "policy_window: E, L, obs_h, step_size = %d, %d, %d, %d must all be >= 1", a->E, a->L, a->obs_h, a->step_size);
+    if ((long long)(a->obs_h - 1) * a->step_size >= a->L)
+        return fail(SPDM_ERR_INVALID, "policy_window: %d entries %d slots apart do not fit a ring of L = %d", a->obs_h, a->step_size, a->L);
+    if ((long long)a->E * a->L > 0x7fffffffLL || (long long)a->E * a->obs_h * 3 > 0x7fffffffLL - 0x800000)
+        return fail(SPDM_ERR_INVALID, "policy_window: E x L or E x obs_h does not fit 31 bits");
+    if (a->n < 1) return fail(SPDM_ERR_INVALID, "policy_window: n = %lld: nothing has been pushed", (long long)a->n);
+    if (a->img_dtype != 0 && a->img_dtype != 1) return fail(SPDM_ERR_INVALID, "policy_window: img_dtype = %d is neither 0 (uint8) nor 1 (float32)", a->img_dtype);
+    if (a->stats_f32 < 0 || a->stats_f32 > 3) return fail(SPDM_ERR_INVALID, "policy_window: stats_f32 = %d outside [0, 3]", a->stats_f32);
+    if (!a->d_image_out && !a->d_position_out && !a->d_velocity_out && !a->d_action_out && !a->d_translation_out)
+        return fail(SPDM_ERR_INVALID, "policy_window: no output requested");
+    if (a->d_image_out && !a->d_ring_img) return fail(SPDM_ERR_INVALID, "policy_window: d_ring_img is NULL");
+    if (a->d_image_out && (((uintptr_t)a->d_ring_img | (uintptr_t)a->d_image_out) & 15))
+        return fail(SPDM_ERR_INVALID, "policy_window: d_ring_img and d_image_out must be 16-byte aligned");
+    if ((a->d_position_out || a->d_translation_out) && !a->d_ring_pos) return fail(SPDM_ERR_INVALID, "policy_window: d_ring_pos is NULL");
+    if (a->d_velocity_out && !a->d_ring_vel) return fail(SPDM_ERR_INVALID, "policy_window: d_ring_vel is NULL");
+    if (a->d_action_out && !a->d_ring_act) return fail(SPDM_ERR_INVALID, "policy_window: d_ring_act is NULL");
+    PolicyWindowArgs k = {};
+    k.E = a->E; k.L = a->L; k.obs_h = a->obs_h; k.step_size = a->step_size; k.img_dtype = a->img_dtype; k.first = (int)(a->n % a->L);
+    k.vel_f32 = a->stats_f32 & 1; k.act_f32 = (a->stats_f32 >> 1) & 1;
+    k.ring_img = a->d_ring_img; k.ring_pos = a->d_ring_pos; k.ring_vel = a->d_ring_vel; k.ring_act = a->d_ring_act;
+    k.pos_min = a->pos_min; k.pos_max = a->pos_max;
+    for (int c = 0; c < 2; ++c) { k.vel_min[c] = a->vel_min[c]; k.vel_max[c] = a->vel_max[c]; }
+    for (int c = 0; c < 3; ++c) { k.act_min[c] = a->act_min[c]; k.act_max[c] = a->act_max[c]; }
+    k.image_out = a->d_image_out; k.position_out = a->d_position_out; k.velocity_out = a->d_velocity_out; k.action_out = a->d_action_out;
+    k.translation_out = a->d_translation_out;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(launch_policy_window(k, (hipStream_t)stream));
+    if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));
+    return SPDM_OK;
+}
+
+// The sampler's x_0 as way-points and actions in the dataset's units in one launch (include/spdm.h, policy.hip).  Stateless.
+extern "C" int spdm_policy_unnormalize(int32_t device, const spdm_policy_unnormalize_args* a, void* stream) {
+    if (!a) return fail(SPDM_ERR_INVALID, "policy_unnormalize: null argument");
+    if (a->E < 1) return fail(SPDM_ERR_INVALID, "policy_unnormalize: E = %d must be >= 1", a->E);
+    if (a->inp_h < 0 || a->H <= a->inp_h) return fail(SPDM_ERR_INVALID, "policy_unnormalize: inp_h = %d outside [0, H = %d)", a->inp_h, a->H);
+    if (a->D < 2 || (a->d_actions && a->D < 5))
+        return fail(SPDM_ERR_INVALID, "policy_unnormalize: D = %d holds no %s", a->D, a->D < 2 ? "position (2 columns)" : "action (columns 2..4)");
+    if ((long long)a->E * (a->H - a->inp_h) > 0x7fffffffLL) return fail(SPDM_ERR_INVALID, "policy_unnormalize: E x P does not fit 31 bits");
+    if (!a->d_x0 || !a->d_translation || !a->d_waypoints) return fail(SPDM_ERR_INVALID, "policy_unnormalize: null pointer");
+    PolicyUnnormalizeArgs k = {};
+    k.E = a->E; k.H = a->H; k.D = a->D; k.inp_h = a->inp_h; k.x0 = a->d_x0; k.translation = a->d_translation;
+    k.pos_min = a->pos_min; k.pos_max = a->pos_max;
+    for (int c = 0; c < 3; ++c) { k.act_min[c] = a->act_min[c]; k.act_max[c] = a->act_max[c]; }
+    k.waypoints = a->d_waypoints; k.actions = a->d_actions;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(launch_policy_unnormalize(k, (hipStream_t)stream));
+    if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));
+    return SPDM_OK;
+}
+
 // The per-sample terms of a validation pass's loss in one launch (include/spdm.h, train_metrics.hip).  Stateless.
 extern "C" int spdm_loss_terms(int32_t device, const spdm_loss_terms_args* a, void* stream) {
     if (!a) return fail(SPDM_ERR_INVALID, "loss_terms: null argument");

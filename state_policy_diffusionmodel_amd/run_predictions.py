@@ -1,0 +1,116 @@
+"""CLI of ``policy.ClosedLoopPolicy``: the loop of the reference's run_predictions.py:112-175 replayed over recorded episodes.
+
+    python -m state_policy_diffusionmodel_amd.run_predictions --model_name DDIM --checkpoint epoch=39.ckpt --hparams hparams.yaml \\
+        --stats STATS.pkl --data arrays.npz --replan_every 50 --seed 0 --out report.json
+
+The reference drives its simulator (gym 0.21 / Box2D), which this project does not ship; the recorded episodes of ``--data``
+(the ``.npz`` / zarr layout of ``evaluate``) stand in for it.  Per episode: ``reset()``, then ``observe()`` row by row, and a
+``plan()`` on every ``--replan_every``-th row of the episode (:151).  Way-point j of a plan made at row t lies ``(j + 1)
+step_size`` rows after the newest observation's window slot, at row ``t - step_size + 1 + (j + 1) step_size`` -- the row a
+dataset window starting at ``t - L + 1`` predicts at step j -- and is compared with the recorded position there by the 2-norm
+in float64.  Steps past the episode's end are left out and counted.
+
+The report holds per plan its row, its errors and the wall-clock seconds of ``plan()`` (synchronised), and over all plans the
+mean and population std of the error per step."""
+from __future__ import annotations
+
+import argparse
+import json
+import time
+from typing import List, Tuple
+
+import numpy as np
+
+
+def plan_rows(t: int, first: int, end: int, obs_horizon: int, pred_horizon: int, step_size: int) -> Tuple[List[int], List[int], int]:
+    """The store rows a plan made after observing row ``t`` of the episode ``[first, end)`` involves: ``(observed, predicted,
+    left_out)``.  ``observed``: the rows of the ``obs_horizon`` history entries, oldest first -- ``t - L + 1 + k step_size``
+    with ``L = obs_horizon step_size``, or ``first`` where the history still holds the initial fill.  ``predicted``: the rows
+    ``t - step_size + 1 + (j + 1) step_size`` of the way-points ``j < pred_horizon`` that lie before ``end``; ``left_out``: how
+    many do not."""
+    if not first <= t < end:
+        raise ValueError(f"row {t} outside the episode [{first}, {end})")
+    if obs_horizon < 1 or pred_horizon < 1 or step_size < 1:
+        raise ValueError("obs_horizon, pred_horizon and step_size must be >= 1")
+    L = obs_horizon * step_size
+    observed = [max(first, t - L + 1 + k * step_size) for k in range(obs_horizon)]
+    rows = [t - step_size + 1 + (j + 1) * step_size for j in range(pred_horizon)]
+    predicted = [r for r in rows if r < end]
+    return observed, predicted, len(rows) - len(predicted)
+
+
+def parse_arguments(argv=None):
+    p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    p.add_argument("--model_name", type=str, default="DDIM", choices=("DDPM", "DDIM"))
+    p.add_argument("--checkpoint", type=str, required=True, help="state_dict file with noise_estimator.* (and vision_encoder.*) tensors")
+    p.add_argument("--hparams", type=str, required=True, help="hparams.yaml written next to the checkpoint")
+    p.add_argument("--stats", type=str, required=True, help="STATS.pkl of the training run")
+    p.add_argument("--data", type=str, required=True, help="arrays.npz (or a zarr store, if zarr is installed)")
+    p.add_argument("--ddim_steps", type=int, default=100)
+    p.add_argument("--replan_every", type=int, default=50, help="plan on every n-th row of an episode (run_predictions.py:151)")
+    p.add_argument("--seed", type=int, default=0, help="plan i samples with seed + i and its x_T from a generator seeded alike")
+    p.add_argument("--out", type=str, default=None, help="report.json")
+    return p.parse_args(argv)
+
+
+def main(argv=None) -> dict:
+    args = parse_arguments(argv)
+    if args.replan_every < 1:
+        raise SystemExit("--replan_every must be >= 1")
+    import torch
+    from .dataset import choose_image_storage
+    from .diffusion import load_model
+    from .evaluate import load_arrays, load_stats
+    from .policy import ClosedLoopPolicy
+    model = load_model(args.model_name, args.checkpoint, args.hparams, num_of_ddim_steps=args.ddim_steps, max_batch=1)
+    stats = load_stats(args.stats)
+    arrays = load_arrays(args.data)
+    storage = choose_image_storage(arrays["img"])
+    policy = ClosedLoopPolicy(model, stats, n_envs=1, image_storage=storage, device=model.device.index)
+    obs_h, P, s = policy.obs_horizon, policy.pred_horizon, policy.step_size
+    H, D = P + policy.inpaint_horizon, policy.prediction_dim
+    position = np.asarray(arrays["position"], dtype=np.float64)
+    u8 = storage == "uint8"
+    plans, left_out, first = [], 0, 0
+    for end in (int(e) for e in np.asarray(arrays["episode_ends"]).reshape(-1)):
+        policy.reset()
+        for t in range(first, end):
+            img = arrays["img"][t:t + 1]
+            if u8 and img.dtype != np.uint8:
+                img = np.rint(img * 255).astype(np.uint8)                      # the store holds pixel / 255.0 (dataset.py)
+            policy.observe(np.ascontiguousarray(img, dtype=np.uint8 if u8 else np.float32), arrays["position"][t:t + 1],
+                           arrays["velocity"][t:t + 1], arrays["action"][t:t + 1])
+            if (t - first) % args.replan_every:
+                continue
+            seed = args.seed + len(plans)
+            x_T = torch.rand(1, 1, H, D, device=model.device, generator=torch.Generator(device=model.device).manual_seed(seed))
+            torch.cuda.synchronize(model.device)
+            start = time.perf_counter()
+            plan = policy.plan(seed=seed, x_T=x_T)
+            torch.cuda.synchronize(model.device)
+            seconds = time.perf_counter() - start
+            _, rows, out = plan_rows(t, first, end, obs_h, P, s)
+            way = plan.waypoints[0, :len(rows)].cpu().numpy()
+            d = position[rows] - way
+            plans.append({"row": t, "episode_end": end, "errors": np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]).tolist(),
+                          "left_out": out, "seconds": seconds})
+            left_out += out
+        first = end
+    mean, std = [], []
+    for j in range(P):
+        col = np.array([p["errors"][j] for p in plans if len(p["errors"]) > j], dtype=np.float64)
+        mean.append(float(col.mean()) if col.size else None)
+        std.append(float(col.std()) if col.size else None)
+    report = {"model_name": args.model_name, "obs_horizon": obs_h, "pred_horizon": P, "step_size": s, "replan_every": args.replan_every,
+              "seed": args.seed, "image_storage": storage, "plans": plans, "left_out": left_out, "mean_error": mean, "std_error": std}
+    times = [p["seconds"] for p in plans]
+    print(f"*** {len(plans)} plans, {left_out} way-points past an episode's end left out; plan(): median {np.median(times) * 1e3:.2f} ms")
+    print("mean position error per step:", mean)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(report, f)
+    return report
+
+
+if __name__ == "__main__":
+    main()
