@@ -864,6 +864,73 @@ typedef struct {
 
 int  spdm_op_gemm(spdm_op_gemm_args* args);
 
+/* Op-level test hook: ONE launch of the training pass (launch_* of csrc/train.hip, train_attn.hip, train_simple.hip) exactly
+ * as spdm_train_loss_grad calls it, on caller-supplied tensors, synchronously on the current device.  Not on the product path.
+ * The hook validates, uploads the host integer arrays, calls the launcher and synchronises -- nothing else.
+ *   d_buf[i] / cap[i]   DEVICE float arrays and their capacities in floats; every array an op reads or writes must be non-NULL
+ *                       and at least as large as the extent given below (optional ones may be NULL, cap ignored)
+ *   h_idx[i] / n_idx[i] HOST int32 arrays (indices a kernel dereferences with): range-checked, then uploaded by the hook
+ *   info[]              filled by the hook (-1 where unused)
+ * SPDM_ERR_INVALID, before the GPU is touched: NULL args, an unknown op, a dimension that is not positive or outside the
+ * launcher's limits, a capacity below the extent, an index outside its range, an extent beyond 31 (element counts the kernels
+ * index with int) or 63 bits.  SPDM_ERR_HIP: the launch or the final synchronise failed.
+ * Deterministic: every op gives the same bits on the same inputs.  Tensors are channels-last, rows of `ld` floats.
+ *
+ * op, dim[] (all others 0), buffers with their extents; M = B H W throughout:
+ *  WGRAD         dim {B, H, W, taps, Co, Ci, conv9, ldy, ldx}; taps 9, 3 (W == 1) or 1 (H == W == 1, conv9 == 0); conv9 == 1 for
+ *                taps 9 / 3.  buf {dy [(M-1) ldy + Co], x [(M-1) ldx + Ci], dst [Co Ci (conv9 ? 9 : 1)] out}.
+ *                info {chunks, rows per chunk} as wgrad_chunks chose them under the product's slab budget; the slabs are the hook's.
+ *  WGRAD_MAPPED  dim {B, H, W, taps, Co, Ci, no, ni}; taps 9 or 3 (W == 1).  buf {dy [M Co], x [M Ci], dst [no ni 9] out};
+ *                h_idx {pos_o [no] in [0, Co), pos_i [ni] in [0, Ci)}.  info as WGRAD.
+ *  COLSUM        dim {M, C, ld}, ld >= C.  buf {src [(M-1) ld + C], dst [C] out}.
+ *  GN_STATS      dim {B, n, cnt}; cnt == 0: launch_gn_stats (divisor n), else launch_gn_stats_real with 1 <= cnt <= n.
+ *                buf {y [B n], mean [B] out, rstd [B] out}.
+ *  GN_BWD        dim {B, HW, C, gelu}; C a power of two <= 512.  buf {y [B HW C], mean [B], rstd [B], gamma [C], beta [C],
+ *                g [B HW C], dy [B HW C] out, dgb [B C 2] out}.
+ *  FILM_BWD      dim {B, HW, C, t_count, T}; C as GN_BWD; t_count 1 or B.  buf {z [B HW C], temb [T C], film [B 2C] or NULL,
+ *                dout [B HW C], dz [B HW C] out, de [B C] out, dfilm [B 2C] out (NULL exactly when film is)};
+ *                h_idx {t [t_count] in [0, T)}.
+ *  MSE           dim {B, H0, D, Hp, Wp, lh, lw}; lh, lw >= 0, lh + H0 <= Hp, lw + D <= Wp.  buf {eps_pad [B Hp Wp],
+ *                noise [B H0 D], loss [1] out, deps_pad [B Hp Wp] out, eps_out [B H0 D] out or NULL}.
+ *  POOL_BWD      dim {B, H, W, C}; H, W even.  buf {in [B H W C], dout [B H/2 W/2 C], din [B H W C] in/out (accumulated into)}.
+ *  UP_BWD        dim {B, h, w, C, ld}; ld >= C.  buf {dcat [(4 B h w - 1) ld + C], dx [B h w C] in/out (accumulated into)}.
+ *  MISH_BWD      dim {nblk, B, ld, cond_dim}; ld >= cond_dim.  buf {dm [(nblk B - 1) ld + cond_dim], cond [B cond_dim],
+ *                grad_cond [B cond_dim] out}.
+ *  LN_FWD        dim {rows, C}; C 64, 128 or 256.  buf {x [rows C], gamma [C], beta [C], y [rows C] out, mean [rows] out,
+ *                rstd [rows] out}.
+ *  LN_BWD        dim {rows, C}.  buf {x [rows C], mean [rows], rstd [rows], gamma [C], gy [rows C], add [rows C] or NULL,
+ *                dx [rows C] out, part [blocks 2C] out}.  info {blocks = ln_bwd_blocks(rows)}.
+ *  GELU_BWD      dim {n}.  buf {u [n], dh [n], du [n] out}.
+ *  ATTN_FWD_LSE  dim {B, L, C, heads}; attn_train_supported(L, C, heads).  buf {qkv [B L 3C], out [B L C] out,
+ *                lse [B heads L] out}.
+ *  ATTN_BWD      dim as ATTN_FWD_LSE.  buf {qkv [B L 3C], out [B L C], dout [B L C], lse [B heads L], dqkv [B L 3C] out}.
+ *  GN_BWD_MAPPED dim {B, HW, C, gelu, nreal}; C a multiple of 64 <= 512.  buf as GN_BWD; h_idx {pos [nreal], distinct, in [0, C)}.
+ *  SIMPLE_TAIL_BWD  dim {B, HW, Co, Cr, Cz, cemb_ld}; Co a multiple of 64 <= 512, Cr <= Cz <= Co, Cr + 32 <= Co, cemb_ld >= 32.
+ *                buf {dout [B HW Co], dz [B HW Cz] out, dtemb [B Cr] out, dcemb [(B-1) cemb_ld + 32] out}.
+ *  SILU_BWD      dim {B, cond_dim, ld}; ld >= cond_dim.  buf {ds [(B-1) ld + cond_dim], cond [B cond_dim],
+ *                grad_cond [B cond_dim] out}. */
+enum {
+    SPDM_OPT_WGRAD = 0, SPDM_OPT_WGRAD_MAPPED, SPDM_OPT_COLSUM, SPDM_OPT_GN_STATS, SPDM_OPT_GN_BWD, SPDM_OPT_FILM_BWD,
+    SPDM_OPT_MSE, SPDM_OPT_POOL_BWD, SPDM_OPT_UP_BWD, SPDM_OPT_MISH_BWD, SPDM_OPT_LN_FWD, SPDM_OPT_LN_BWD, SPDM_OPT_GELU_BWD,
+    SPDM_OPT_ATTN_FWD_LSE, SPDM_OPT_ATTN_BWD, SPDM_OPT_GN_BWD_MAPPED, SPDM_OPT_SIMPLE_TAIL_BWD, SPDM_OPT_SILU_BWD,
+    SPDM_OPT_COUNT
+};
+#define SPDM_OP_TRAIN_DIMS 10
+#define SPDM_OP_TRAIN_BUFS 8
+#define SPDM_OP_TRAIN_IDX 2
+typedef struct {
+    int32_t op;
+    int32_t reserved;
+    int64_t dim[SPDM_OP_TRAIN_DIMS];
+    float* d_buf[SPDM_OP_TRAIN_BUFS];
+    uint64_t cap[SPDM_OP_TRAIN_BUFS];
+    const int32_t* h_idx[SPDM_OP_TRAIN_IDX];
+    int64_t n_idx[SPDM_OP_TRAIN_IDX];
+    int32_t info[4];
+} spdm_op_train_args;
+
+int  spdm_op_train(spdm_op_train_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,19 @@ class SpdmOpGemmArgs(ctypes.Structure):
                  ("out", c_int32 * 10)])
 
 
+# spdm_op_train op codes (include/spdm.h: SPDM_OPT_*), in enum order
+OP_TRAIN_OPS = ("wgrad", "wgrad_mapped", "colsum", "gn_stats", "gn_bwd", "film_bwd", "mse", "pool_bwd", "up_bwd", "mish_bwd",
+                "ln_fwd", "ln_bwd", "gelu_bwd", "attn_fwd_lse", "attn_bwd", "gn_bwd_mapped", "simple_tail_bwd", "silu_bwd")
+OP_TRAIN_DIMS, OP_TRAIN_BUFS, OP_TRAIN_IDX = 10, 8, 2
+
+
+class SpdmOpTrainArgs(ctypes.Structure):
+    """spdm_op_train_args (include/spdm.h)."""
+    _fields_ = [("op", c_int32), ("reserved", c_int32), ("dim", c_int64 * OP_TRAIN_DIMS), ("d_buf", c_void_p * OP_TRAIN_BUFS),
+                ("cap", c_uint64 * OP_TRAIN_BUFS), ("h_idx", c_void_p * OP_TRAIN_IDX), ("n_idx", c_int64 * OP_TRAIN_IDX),
+                ("info", c_int32 * 4)]
+
+
 class SpdmOptimSegment(ctypes.Structure):
     """spdm_optim_segment (include/spdm.h)."""
     _fields_ = [("d_param", c_void_p), ("d_grad", c_void_p), ("d_exp_avg", c_void_p), ("d_exp_avg_sq", c_void_p),
@@ -188,6 +201,7 @@ SYMBOLS = {
     "spdm_adam_norm_index": (c_size_t, []),
     "spdm_op_gelu": (c_int32, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "spdm_op_gemm": (c_int32, [POINTER(SpdmOpGemmArgs)]),
+    "spdm_op_train": (c_int32, [POINTER(SpdmOpTrainArgs)]),
     "spdm_debug_geometry": (c_int32, [c_int32] * 6 + [ctypes.c_uint32, POINTER(c_int32 * 10)]),
     "spdm_debug_whole_tiles": (c_int32, []),
     "spdm_bench_gemm": (c_int32, [c_int32] * 12 + [POINTER(c_double)]),   # ms_out[2]: {ms per launch, max|split - fp32|}

@@ -3971,3 +3971,272 @@ extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {
     q.out[5] = two ? 1 : 0; q.out[6] = fused ? 1 : 0; q.out[7] = g.slots; q.out[8] = g.st_m_tile; q.out[9] = g.st_n_tiles;
     return SPDM_OK;
 }
+
+// op-level test hook: one launch_* of the training pass on the caller's tensors (include/spdm.h).  Validate, upload the integer
+// arrays, launch, synchronise.
+namespace {
+struct OpTrainExtent {                     // element counts that must stay within 31 bits; no intermediate can overflow
+    bool ok = true;
+    uint64_t mul(std::initializer_list<int64_t> f) {
+        uint64_t v = 1;
+        for (int64_t x : f) {
+            v *= (uint64_t)x;              // both factors are below 2^31
+            if (v > (uint64_t)INT32_MAX) { ok = false; v = 1; }
+        }
+        return v;
+    }
+    uint64_t strided(uint64_t rows, int64_t ld, int64_t width) {      // rows of ld floats, the last one width long
+        if (rows == 0) { ok = false; return 0; }
+        const uint64_t v = mul({(int64_t)rows - 1, ld}) + (uint64_t)width;
+        if (v > (uint64_t)INT32_MAX) ok = false;
+        return v;
+    }
+};
+struct OpTrainDev {                        // the hook's own device allocations
+    void* p[3] = {nullptr, nullptr, nullptr};
+    ~OpTrainDev() { for (void* q : p) if (q) (void)hipFree(q); }
+};
+}  // namespace
+
+extern "C" int spdm_op_train(spdm_op_train_args* p) {
+    if (!p) return fail(SPDM_ERR_INVALID, "op_train: null argument");
+    spdm_op_train_args& q = *p;
+    for (int i = 0; i < 4; ++i) q.info[i] = -1;
+    if (q.op < 0 || q.op >= SPDM_OPT_COUNT) return fail(SPDM_ERR_INVALID, "op_train: unknown op %d", q.op);
+    static const int n_dims[SPDM_OPT_COUNT] = {9, 8, 3, 3, 4, 5, 7, 4, 5, 4, 2, 2, 1, 4, 4, 5, 6, 3};
+    static const int n_idxs[SPDM_OPT_COUNT] = {0, 2, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0};
+    const int64_t* d = q.dim;
+    for (int i = 0; i < SPDM_OP_TRAIN_DIMS; ++i) {
+        if (d[i] < 0 || d[i] > INT32_MAX) return fail(SPDM_ERR_INVALID, "op_train: dim[%d] = %lld outside [0, 2^31)", i, (long long)d[i]);
+        if (i >= n_dims[q.op] && d[i] != 0) return fail(SPDM_ERR_INVALID, "op_train: op %d takes %d dims; dim[%d] must be 0", q.op, n_dims[q.op], i);
+    }
+    auto positive = [&](std::initializer_list<int> which) {
+        for (int i : which) if (d[i] < 1) return false;
+        return true;
+    };
+    auto pow2_le512 = [](int64_t C) { return C >= 1 && C <= 512 && (C & (C - 1)) == 0; };
+#define OPT_BAD(...) return fail(SPDM_ERR_INVALID, "op_train: " __VA_ARGS__)
+    OpTrainExtent E;
+    uint64_t need[SPDM_OP_TRAIN_BUFS] = {};
+    bool optional[SPDM_OP_TRAIN_BUFS] = {};
+    int nbuf = 0;
+    int64_t idx_n[SPDM_OP_TRAIN_IDX] = {0, 0}, idx_lim[SPDM_OP_TRAIN_IDX] = {0, 0};
+    uint64_t M = 0, slab = 0;
+    int nch = 0, wrows = 0;
+    switch (q.op) {
+        case SPDM_OPT_WGRAD:
+        case SPDM_OPT_WGRAD_MAPPED: {
+            const bool mapped = q.op == SPDM_OPT_WGRAD_MAPPED;
+            if (!positive({0, 1, 2, 3, 4, 5})) OPT_BAD("wgrad: B, H, W, taps, Co, Ci must be positive");
+            const int64_t taps = d[3], Co = d[4], Ci = d[5];
+            if (!(taps == 9 || taps == 3 || (taps == 1 && !mapped))) OPT_BAD("wgrad: taps %lld", (long long)taps);
+            if (taps == 3 && d[2] != 1) OPT_BAD("wgrad: 3-tap layers need W == 1");
+            if (taps == 1 && (d[1] != 1 || d[2] != 1)) OPT_BAD("wgrad: a Linear layer has H == W == 1 (B = rows)");
+            M = E.mul({d[0], d[1], d[2]});
+            int64_t ldy = Co, ldx = Ci;
+            uint64_t ndst;
+            if (mapped) {
+                if (!positive({6, 7}) || d[6] > Co || d[7] > Ci) OPT_BAD("wgrad_mapped: need 1 <= no <= Co and 1 <= ni <= Ci");
+                ndst = E.mul({d[6], d[7], 9});
+                idx_n[0] = d[6]; idx_lim[0] = Co; idx_n[1] = d[7]; idx_lim[1] = Ci;
+            } else {
+                if (d[6] != (taps == 1 ? 0 : 1)) OPT_BAD("wgrad: conv9 is 1 for taps 9 / 3 and 0 for taps 1");
+                ldy = d[7]; ldx = d[8];
+                if (ldy < Co || ldx < Ci) OPT_BAD("wgrad: ldy >= Co and ldx >= Ci required");
+                ndst = E.mul({Co, Ci, d[6] ? 9 : 1});
+            }
+            need[0] = E.strided(M, ldy, Co); need[1] = E.strided(M, ldx, Ci); need[2] = ndst; nbuf = 3;
+            const uint64_t per = E.mul({taps, Co, Ci});
+            if (!E.ok) break;
+            nch = wgrad_chunks((long long)M, (int)taps, (int)Co, (int)Ci, TrainPass::WGRAD_BUDGET);
+            slab = (uint64_t)nch * per;
+            if (nch < 1 || slab > TrainPass::WGRAD_BUDGET) OPT_BAD("wgrad: the partial slabs exceed the budget");
+            wrows = (int)((((long long)M + nch - 1) / nch + 3) / 4 * 4);
+            break;
+        }
+        case SPDM_OPT_COLSUM:
+            if (!positive({0, 1, 2}) || d[2] < d[1]) OPT_BAD("colsum: M, C positive and ld >= C required");
+            need[0] = E.strided((uint64_t)d[0], d[2], d[1]); need[1] = (uint64_t)d[1]; nbuf = 2;
+            break;
+        case SPDM_OPT_GN_STATS:
+            if (!positive({0, 1}) || d[2] > d[1]) OPT_BAD("gn_stats: B, n positive and 0 <= cnt <= n required");
+            need[0] = E.mul({d[0], d[1]}); need[1] = need[2] = (uint64_t)d[0]; nbuf = 3;
+            break;
+        case SPDM_OPT_GN_BWD:
+        case SPDM_OPT_GN_BWD_MAPPED: {
+            if (!positive({0, 1, 2}) || d[3] > 1) OPT_BAD("gn_bwd: B, HW, C positive and gelu 0 / 1 required");
+            const int64_t C = d[2];
+            if (q.op == SPDM_OPT_GN_BWD) {
+                if (!pow2_le512(C)) OPT_BAD("gn_bwd: C must be a power of two <= 512 (got %lld)", (long long)C);
+            } else {
+                if (C % 64 != 0 || C > 512) OPT_BAD("gn_bwd_mapped: C must be a multiple of 64 <= 512 (got %lld)", (long long)C);
+                if (d[4] < 1 || d[4] > C) OPT_BAD("gn_bwd_mapped: need 1 <= nreal <= C");
+                idx_n[0] = d[4]; idx_lim[0] = C;
+            }
+            const uint64_t n = E.mul({d[0], d[1], C});
+            need[0] = n; need[1] = need[2] = (uint64_t)d[0]; need[3] = need[4] = (uint64_t)C; need[5] = need[6] = n;
+            need[7] = E.mul({d[0], C, 2}); nbuf = 8;
+            break;
+        }
+        case SPDM_OPT_FILM_BWD: {
+            if (!positive({0, 1, 2, 3, 4})) OPT_BAD("film_bwd: B, HW, C, t_count, T must be positive");
+            const int64_t B = d[0], C = d[2];
+            if (!pow2_le512(C)) OPT_BAD("film_bwd: C must be a power of two <= 512 (got %lld)", (long long)C);
+            if (d[3] != 1 && d[3] != B) OPT_BAD("film_bwd: t_count must be 1 or B");
+            if ((q.d_buf[2] == nullptr) != (q.d_buf[6] == nullptr)) OPT_BAD("film_bwd: film and dfilm go together");
+            const uint64_t n = E.mul({B, d[1], C});
+            need[0] = n; need[1] = E.mul({d[4], C}); need[2] = E.mul({B, 2, C}); optional[2] = true; need[3] = need[4] = n;
+            need[5] = E.mul({B, C}); need[6] = need[2]; optional[6] = true; nbuf = 7;
+            idx_n[0] = d[3]; idx_lim[0] = d[4];
+            break;
+        }
+        case SPDM_OPT_MSE:
+            if (!positive({0, 1, 2, 3, 4}) || d[5] + d[1] > d[3] || d[6] + d[2] > d[4])
+                OPT_BAD("mse: B, H0, D, Hp, Wp positive, lh + H0 <= Hp and lw + D <= Wp required");
+            need[0] = need[3] = E.mul({d[0], d[3], d[4]}); need[1] = need[4] = E.mul({d[0], d[1], d[2]}); need[2] = 1;
+            optional[4] = true; nbuf = 5;
+            break;
+        case SPDM_OPT_POOL_BWD:
+            if (!positive({0, 1, 2, 3}) || (d[1] & 1) || (d[2] & 1)) OPT_BAD("pool_bwd: B, H, W, C positive and H, W even required");
+            need[0] = need[2] = E.mul({d[0], d[1], d[2], d[3]}); need[1] = E.mul({d[0], d[1] / 2, d[2] / 2, d[3]}); nbuf = 3;
+            break;
+        case SPDM_OPT_UP_BWD:
+            if (!positive({0, 1, 2, 3, 4}) || d[4] < d[3]) OPT_BAD("up_bwd: B, h, w, C positive and ld >= C required");
+            need[0] = E.strided(E.mul({4, d[0], d[1], d[2]}), d[4], d[3]); need[1] = E.mul({d[0], d[1], d[2], d[3]}); nbuf = 2;
+            break;
+        case SPDM_OPT_MISH_BWD:
+            if (!positive({0, 1, 2, 3}) || d[2] < d[3]) OPT_BAD("mish_bwd: nblk, B, cond_dim positive and ld >= cond_dim required");
+            need[0] = E.strided(E.mul({d[0], d[1]}), d[2], d[3]); need[1] = need[2] = E.mul({d[1], d[3]}); nbuf = 3;
+            break;
+        case SPDM_OPT_LN_FWD:
+        case SPDM_OPT_LN_BWD: {
+            if (!positive({0, 1})) OPT_BAD("layernorm: rows and C must be positive");
+            const int64_t rows = d[0], C = d[1];
+            if (C != 64 && C != 128 && C != 256) OPT_BAD("layernorm: C must be 64, 128 or 256 (got %lld)", (long long)C);
+            const uint64_t n = E.mul({rows, C});
+            if (q.op == SPDM_OPT_LN_FWD) {
+                need[0] = n; need[1] = need[2] = (uint64_t)C; need[3] = n; need[4] = need[5] = (uint64_t)rows; nbuf = 6;
+            } else {
+                need[0] = n; need[1] = need[2] = (uint64_t)rows; need[3] = (uint64_t)C; need[4] = need[5] = need[6] = n;
+                optional[5] = true;
+                need[7] = E.mul({(int64_t)ln_bwd_blocks(rows), 2, C}); nbuf = 8;
+            }
+            break;
+        }
+        case SPDM_OPT_GELU_BWD:
+            if (!positive({0})) OPT_BAD("gelu_bwd: n must be positive");
+            need[0] = need[1] = need[2] = (uint64_t)d[0]; nbuf = 3;
+            break;
+        case SPDM_OPT_ATTN_FWD_LSE:
+        case SPDM_OPT_ATTN_BWD: {
+            if (!positive({0, 1, 2, 3})) OPT_BAD("attention: B, L, C, heads must be positive");
+            if (!attn_train_supported((int)d[1], (int)d[2], (int)d[3]))
+                OPT_BAD("attention: L %lld, C %lld, heads %lld not supported (L <= 512, C / heads in {16, 32, 64}, LDS)",
+                        (long long)d[1], (long long)d[2], (long long)d[3]);
+            const uint64_t nq = E.mul({d[0], d[1], 3, d[2]}), no = E.mul({d[0], d[1], d[2]}), nl = E.mul({d[0], d[3], d[1]});
+            if (q.op == SPDM_OPT_ATTN_FWD_LSE) { need[0] = nq; need[1] = no; need[2] = nl; nbuf = 3; }
+            else { need[0] = nq; need[1] = need[2] = no; need[3] = nl; need[4] = nq; nbuf = 5; }
+            break;
+        }
+        case SPDM_OPT_SIMPLE_TAIL_BWD: {
+            if (!positive({0, 1, 2, 3, 4, 5})) OPT_BAD("simple_tail_bwd: B, HW, Co, Cr, Cz, cemb_ld must be positive");
+            const int64_t Co = d[2], Cr = d[3], Cz = d[4];
+            if (Co % 64 != 0 || Co > 512 || Cr > Cz || Cz > Co || Cr + 32 > Co || d[5] < 32)
+                OPT_BAD("simple_tail_bwd: Co a multiple of 64 <= 512, Cr <= Cz <= Co, Cr + 32 <= Co and cemb_ld >= 32 required");
+            need[0] = E.mul({d[0], d[1], Co}); need[1] = E.mul({d[0], d[1], Cz}); need[2] = E.mul({d[0], Cr});
+            need[3] = E.strided((uint64_t)d[0], d[5], 32); nbuf = 4;
+            break;
+        }
+        case SPDM_OPT_SILU_BWD:
+            if (!positive({0, 1, 2}) || d[2] < d[1]) OPT_BAD("silu_bwd: B, cond_dim positive and ld >= cond_dim required");
+            need[0] = E.strided((uint64_t)d[0], d[2], d[1]); need[1] = need[2] = E.mul({d[0], d[1]}); nbuf = 3;
+            break;
+    }
+    if (!E.ok) OPT_BAD("op %d: a tensor extent is beyond 31 bits", q.op);
+    for (int i = 0; i < SPDM_OP_TRAIN_BUFS; ++i) {
+        if (i >= nbuf) {
+            if (q.d_buf[i]) OPT_BAD("op %d takes %d buffers; d_buf[%d] must be null", q.op, nbuf, i);
+            continue;
+        }
+        if (!q.d_buf[i]) {
+            if (!optional[i]) OPT_BAD("op %d: d_buf[%d] is null", q.op, i);
+            continue;
+        }
+        if (q.cap[i] < need[i])
+            OPT_BAD("op %d: d_buf[%d] holds %llu floats, the launch needs %llu", q.op, i, (unsigned long long)q.cap[i], (unsigned long long)need[i]);
+    }
+    for (int k = 0; k < SPDM_OP_TRAIN_IDX; ++k) {
+        if (k >= n_idxs[q.op]) {
+            if (q.h_idx[k] || q.n_idx[k]) OPT_BAD("op %d takes %d index arrays; h_idx[%d] must be null", q.op, n_idxs[q.op], k);
+            continue;
+        }
+        if (!q.h_idx[k] || q.n_idx[k] != idx_n[k]) OPT_BAD("op %d: h_idx[%d] must hold %lld entries", q.op, k, (long long)idx_n[k]);
+        for (int64_t i = 0; i < idx_n[k]; ++i)
+            if (q.h_idx[k][i] < 0 || q.h_idx[k][i] >= idx_lim[k])
+                OPT_BAD("op %d: h_idx[%d][%lld] = %d outside [0, %lld)", q.op, k, (long long)i, q.h_idx[k][i], (long long)idx_lim[k]);
+    }
+    if (q.op == SPDM_OPT_GN_BWD_MAPPED) {                                   // a channel map names each storage lane once
+        bool seen[512] = {};
+        for (int64_t i = 0; i < idx_n[0]; ++i) {
+            if (seen[q.h_idx[0][i]]) OPT_BAD("gn_bwd_mapped: pos names lane %d twice", q.h_idx[0][i]);
+            seen[q.h_idx[0][i]] = true;
+        }
+    }
+#undef OPT_BAD
+    // ---- the device from here on ----
+    OpTrainDev dev;
+    const int* di[SPDM_OP_TRAIN_IDX] = {nullptr, nullptr};
+    for (int k = 0; k < n_idxs[q.op]; ++k) {
+        HIP_TRY(hipMalloc(&dev.p[k], sizeof(int) * (size_t)idx_n[k]));
+        HIP_TRY(hipMemcpy(dev.p[k], q.h_idx[k], sizeof(int) * (size_t)idx_n[k], hipMemcpyHostToDevice));
+        di[k] = (const int*)dev.p[k];
+    }
+    float* partial = nullptr;
+    if (slab) {
+        HIP_TRY(hipMalloc(&dev.p[2], sizeof(float) * (size_t)slab));
+        HIP_TRY(hipMemset(dev.p[2], 0xff, sizeof(float) * (size_t)slab));   // an unwritten partial reads as NaN
+        partial = (float*)dev.p[2];
+    }
+    float* const* b = q.d_buf;
+    const int i0 = (int)d[0], i1 = (int)d[1], i2 = (int)d[2], i3 = (int)d[3], i4 = (int)d[4], i5 = (int)d[5], i6 = (int)d[6];
+    hipStream_t s = nullptr;
+    hipError_t el = hipSuccess;
+    switch (q.op) {
+        case SPDM_OPT_WGRAD:
+            el = launch_wgrad(b[0], (int)d[7], b[1], (int)d[8], (long long)M, i1, i2, i3, i4, i5, i6, partial, TrainPass::WGRAD_BUDGET, b[2], s);
+            q.info[0] = nch; q.info[1] = wrows;
+            break;
+        case SPDM_OPT_WGRAD_MAPPED:
+            el = launch_wgrad_mapped(b[0], b[1], (long long)M, i1, i2, i3, i4, i5, di[0], i6, di[1], (int)d[7], partial,
+                                     TrainPass::WGRAD_BUDGET, b[2], s);
+            q.info[0] = nch; q.info[1] = wrows;
+            break;
+        case SPDM_OPT_COLSUM: el = launch_colsum(b[0], i2, (long long)d[0], i1, b[1], s); break;
+        case SPDM_OPT_GN_STATS:
+            el = i2 == 0 ? launch_gn_stats(b[0], i0, i1, b[1], b[2], s) : launch_gn_stats_real(b[0], i0, i1, i2, b[1], b[2], s);
+            break;
+        case SPDM_OPT_GN_BWD: el = launch_gn_bwd(b[0], b[1], b[2], b[3], b[4], b[5], i3, i0, i1, i2, b[6], b[7], s); break;
+        case SPDM_OPT_FILM_BWD: el = launch_film_bwd(b[0], b[1], di[0], i3, b[2], b[3], i0, i1, i2, b[4], b[5], b[6], s); break;
+        case SPDM_OPT_MSE: el = launch_mse(b[0], b[1], i0, i1, i2, i3, i4, i5, i6, b[2], b[3], b[4], s); break;
+        case SPDM_OPT_POOL_BWD: el = launch_pool_bwd(b[0], b[1], i0, i1, i2, i3, b[2], s); break;
+        case SPDM_OPT_UP_BWD: el = launch_up_bwd(b[0], i4, i0, i1, i2, i3, b[1], s); break;
+        case SPDM_OPT_MISH_BWD: el = launch_mish_bwd(b[0], i0, i1, i2, b[1], i3, b[2], s); break;
+        case SPDM_OPT_LN_FWD: el = launch_ln_fwd(b[0], b[1], b[2], (long long)d[0], i1, b[3], b[4], b[5], s); break;
+        case SPDM_OPT_LN_BWD:
+            el = launch_ln_bwd(b[0], b[1], b[2], b[3], b[4], b[5], (long long)d[0], i1, b[6], b[7], s);
+            q.info[0] = ln_bwd_blocks((long long)d[0]);
+            break;
+        case SPDM_OPT_GELU_BWD: el = launch_gelu_bwd(b[0], b[1], (size_t)d[0], b[2], s); break;
+        case SPDM_OPT_ATTN_FWD_LSE: el = launch_attn_fwd_lse(b[0], b[1], b[2], i0, i1, i2, i3, s); break;
+        case SPDM_OPT_ATTN_BWD: el = launch_attn_bwd(b[0], b[1], b[2], b[3], b[4], i0, i1, i2, i3, s); break;
+        case SPDM_OPT_GN_BWD_MAPPED:
+            el = launch_gn_bwd_mapped(b[0], b[1], b[2], b[3], b[4], b[5], i3, i0, i1, i2, di[0], i4, b[6], b[7], s);
+            break;
+        case SPDM_OPT_SIMPLE_TAIL_BWD: el = launch_simple_tail_bwd(b[0], i0, i1, i2, i3, i4, b[1], b[2], b[3], i5, s); break;
+        case SPDM_OPT_SILU_BWD: el = launch_silu_bwd(b[0], i2, b[1], i0, i1, b[2], s); break;
+    }
+    const hipError_t es = hipDeviceSynchronize();
+    if (el != hipSuccess) return fail(SPDM_ERR_HIP, "op_train: op %d: launch failed: %s; device: %s", q.op, hipGetErrorString(el), hipGetErrorString(es));
+    if (es != hipSuccess) return fail(SPDM_ERR_HIP, "op_train: op %d: %s", q.op, hipGetErrorString(es));
+    return SPDM_OK;
+}
