@@ -931,6 +931,105 @@ typedef struct {
 
 int  spdm_op_train(spdm_op_train_args* args);
 
+/* Op-level test hook: ONE launch of a streaming kernel of the forward / sampling path (launch_* of csrc/elementwise.hip) exactly
+ * as the plan calls it, on caller-supplied tensors, synchronously on the current device.  Not on the product path.
+ * The hook validates, uploads the host integers (index arrays, the step word, the Philox words, the ptrs_dev block), builds
+ * AffineSrc / StatsRef / StepArgs, calls the launcher and synchronises -- nothing else; it has no arithmetic of its own.
+ *   d_buf[i] / cap[i]   DEVICE float arrays and capacities in floats, as for spdm_op_train (optional ones may be NULL)
+ *   h_idx[i] / n_idx[i] HOST int32 arrays: range-checked where a kernel dereferences with them, then uploaded
+ *   gn[k]               a GroupNorm(1, C) still pending on source k, described as spdm_op_gemm describes it: d_stats the raw
+ *                       fp64 partials [B][slots][2] a producer left (NULL: no GroupNorm; every other field of gn[k] then 0 / NULL),
+ *                       stats_cap in doubles, the producer's m_tile and n_tiles, cnorm the channels the statistics divide by
+ *                       (1 <= cnorm <= C; inv_count = 1 / (cnorm HW)), gamma and beta of affine_cap floats each (>= the channels
+ *                       the op applies them to).  The consumer reads, for sample b, slots [0, ((b HW + HW - 1) / m_tile -
+ *                       b HW / m_tile + 1) n_tiles): `slots` must be at least the largest such count.
+ *   d_stats_out / stats_out_cap   DEVICE fp64 partials a producer op writes (capacity in doubles)
+ *   d_words             DEVICE int32[3] = {step word, t word, flag}: written by the hook before the launch ({step0 or step, -1, 0}),
+ *                       then by the kernel; required by CONV_IN (adv >= -1) and OUT_STEP, NULL otherwise
+ *   info[]              filled by the hook (-1 where unused)
+ * SPDM_ERR_INVALID, before the GPU is touched: NULL args, an unknown op, a dimension that is not positive or outside its range
+ * below, a capacity below the extent, a buffer an op does not take, an index or timestep outside its range, a slot count smaller
+ * than the consumer reads, an extent beyond 31 bits, anything the launcher refuses -- and what a launcher accepts but its kernel
+ * cannot run (DESIGN.md 8.16 lists those).  SPDM_ERR_HIP: the launch or the final synchronise failed.
+ * Deterministic: every op gives the same bits on the same inputs.  Tensors are channels-last.
+ *
+ * op, dim[] (all others 0), buffers with their extents:
+ *  CONV_IN       dim {B, H0, D, Hp, Wp, lh, lw, B_geom, adv, n_steps, step0}; lh, lw >= 0, lh + H0 <= Hp, lw + D <= Wp,
+ *                (Hp Wp + 8) floats within 64 KiB of LDS; B_geom >= 0 (0: row parts as for B); adv -2 (no bookkeeping: n_steps =
+ *                step0 = 0, no h_idx, no d_words), -1 (step <- step0 + 1) or 0 .. n_steps (step <- adv); 0 <= step0 < n_steps.
+ *                buf {x [B H0 D], w [9 64] = [tap][channel], dst [B Hp Wp 64] out}; h_idx {timesteps [n_steps], >= 0};
+ *                d_stats_out [B slots 2], of which the kernel writes slots [0, parts) of each sample.  info {parts, slots}.
+ *  POOL          dim {B, H, W, C}; H, W even, C a multiple of 4 <= 1024.  buf {src [B H W C], dst [B H/2 W/2 C] out}; gn[0].
+ *  UPCAT         dim {B, Hin, Win, Cu, Cs}; Cu >= 4, Cs >= 0 (0: no skip source), both multiples of 4, Cu + Cs <= 1024.
+ *                buf {up [B Hin Win Cu], skip [B 4 Hin Win Cs] (NULL exactly when Cs == 0), dst [B 4 Hin Win (Cu + Cs)] out};
+ *                gn[0] on up (HW = Hin Win), gn[1] on skip (HW = 4 Hin Win).
+ *  FILM_APPLY    dim {B, HW, C, t_count, T}; C in {4, 8, ..., 1024} (C / 4 divides 256); t_count 1 or B.
+ *                buf {src [B HW C], temb [T C] or NULL, film [B 2C] or NULL, dst [B HW C] out}; h_idx {t [t_count] in [0, T)}
+ *                exactly when temb is given (without temb: t_count = T = 1); gn[0]; d_stats_out [B HW 2] or NULL: per-row
+ *                {sum, sum^2} of dst, C in {64, 128, 256} only.  With temb, film, gn[0] and d_stats_out all absent: launch_gn_apply.
+ *  FILM_COEF     dim as FILM_APPLY, any C >= 1.  buf {temb [T C] or NULL, film [B 2C] or NULL, ab [B 2C] out}; h_idx as FILM_APPLY;
+ *                gn[0] (no tensor is read: the statistics, gamma and beta only).
+ *  LAYERNORM     dim {rows, C}; C 64, 128, 256 or 512.  buf {x [rows C], gamma [C], beta [C], y [rows C] out}.
+ *  MISH_PAD, SILU_PAD  dim {B, cond_dim, Kp}; Kp >= cond_dim.  buf {cond [B cond_dim], dst [B Kp] out}.
+ *  SILU          dim {n}.  buf {x [n], y [n] out}.
+ *  DC_FINISH     dim {B, HW, C}; C a multiple of 4 <= 1024.  buf {src [B HW C], res [B HW C] or NULL, dst [B HW C] out}; gn[0].
+ *  SIMPLE_TAIL   dim {B, HW, Co, Cr, src_C, temb_ld, cemb_ld, t_count, T}; Co, Cr, src_C, temb_ld, cemb_ld multiples of 4,
+ *                Co <= 1024, 4 <= Cr <= src_C, Cr + 32 <= Co, temb_ld >= Cr, cemb_ld >= 32, t_count 1 or B.
+ *                buf {src [B HW src_C], temb [(T-1) temb_ld + Cr], cemb [(B-1) cemb_ld + 32], dst [B HW Co] out};
+ *                h_idx {t [t_count] in [0, T)}; gn[0] (gamma, beta: >= Cr floats; cnorm <= src_C).
+ *  SPLITK_COMBINE  dim {B, HW, N, ksplit}; N a multiple of 4, ksplit >= 2.  buf {partial [ksplit][B HW N], dst [B HW N] out};
+ *                d_stats_out [B slots 2], of which the kernel writes slots [0, HW / rows).  info {rows = combine_rows(HW, N), slots}.
+ *  OUT_STEP      dim {B, H0, D, Hp, Wp, lh, lw, kind, mode, step, n_steps, inp_h, inpaint_per_sample, indirect}; padding as
+ *                CONV_IN; kind 0 DDPM, 1 DDIM; mode 0 eps only (eps written, nothing else touched), 1 the full step from the
+ *                features, 2 the full step from a given eps; 0 <= step < n_steps; 0 <= inp_h <= H0; the two flags 0 / 1.
+ *                buf {feat [B Hp Wp 64] (modes 0, 1), w [64] (modes 0, 1), eps [B H0 D] (mode 0: out, mode 2: in, mode 1: NULL),
+ *                x [B H0 D] in/out (modes 1, 2), coef [n_steps 6] (modes 1, 2), noise [n_steps B H0 D] or NULL (NULL: the Philox
+ *                stream {seed, first_index} is handed to the kernel instead), inpaint [inp_h D], or [B inp_h D] with
+ *                inpaint_per_sample (exactly when inp_h > 0), history [(n_steps + 1) B H0 D] in/out or NULL}; `bias` is outc's.
+ *                indirect 1 hands inpaint / noise / history to the kernel through a ptrs_dev block the hook writes.
+ *                d_words: {step (unchanged), -1, flag}. */
+enum {
+    SPDM_OPS_CONV_IN = 0, SPDM_OPS_POOL, SPDM_OPS_UPCAT, SPDM_OPS_FILM_APPLY, SPDM_OPS_FILM_COEF, SPDM_OPS_LAYERNORM,
+    SPDM_OPS_MISH_PAD, SPDM_OPS_SILU_PAD, SPDM_OPS_SILU, SPDM_OPS_DC_FINISH, SPDM_OPS_SIMPLE_TAIL, SPDM_OPS_SPLITK_COMBINE,
+    SPDM_OPS_OUT_STEP,
+    SPDM_OPS_COUNT
+};
+#define SPDM_OP_STREAM_DIMS 14
+#define SPDM_OP_STREAM_BUFS 8
+#define SPDM_OP_STREAM_IDX 1
+#define SPDM_OP_STREAM_GN 2
+typedef struct {
+    const double* d_stats;
+    uint64_t stats_cap;
+    int32_t slots;
+    int32_t m_tile;
+    int32_t n_tiles;
+    int32_t cnorm;
+    const float* d_gamma;
+    const float* d_beta;
+    uint64_t affine_cap;
+} spdm_op_stream_gn;
+typedef struct {
+    int32_t op;
+    int32_t reserved;
+    int64_t dim[SPDM_OP_STREAM_DIMS];
+    float* d_buf[SPDM_OP_STREAM_BUFS];
+    uint64_t cap[SPDM_OP_STREAM_BUFS];
+    const int32_t* h_idx[SPDM_OP_STREAM_IDX];
+    int64_t n_idx[SPDM_OP_STREAM_IDX];
+    spdm_op_stream_gn gn[SPDM_OP_STREAM_GN];
+    double* d_stats_out;
+    uint64_t stats_out_cap;
+    int32_t* d_words;
+    uint64_t seed;
+    uint64_t first_index;
+    float bias;
+    int32_t info[4];
+    int32_t reserved2;
+} spdm_op_stream_args;
+
+int  spdm_op_stream(spdm_op_stream_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,27 @@ class SpdmOpTrainArgs(ctypes.Structure):
                 ("info", c_int32 * 4)]
 
 
+# spdm_op_stream op codes (include/spdm.h: SPDM_OPS_*), in enum order
+OP_STREAM_OPS = ("conv_in", "pool", "upcat", "film_apply", "film_coef", "layernorm", "mish_pad", "silu_pad", "silu", "dc_finish",
+                 "simple_tail", "splitk_combine", "out_step")
+OP_STREAM_DIMS, OP_STREAM_BUFS, OP_STREAM_IDX, OP_STREAM_GN = 14, 8, 1, 2
+
+
+class SpdmOpStreamGn(ctypes.Structure):
+    """spdm_op_stream_gn (include/spdm.h)."""
+    _fields_ = [("d_stats", c_void_p), ("stats_cap", c_uint64), ("slots", c_int32), ("m_tile", c_int32), ("n_tiles", c_int32),
+                ("cnorm", c_int32), ("d_gamma", c_void_p), ("d_beta", c_void_p), ("affine_cap", c_uint64)]
+
+
+class SpdmOpStreamArgs(ctypes.Structure):
+    """spdm_op_stream_args (include/spdm.h)."""
+    _fields_ = [("op", c_int32), ("reserved", c_int32), ("dim", c_int64 * OP_STREAM_DIMS), ("d_buf", c_void_p * OP_STREAM_BUFS),
+                ("cap", c_uint64 * OP_STREAM_BUFS), ("h_idx", c_void_p * OP_STREAM_IDX), ("n_idx", c_int64 * OP_STREAM_IDX),
+                ("gn", SpdmOpStreamGn * OP_STREAM_GN), ("d_stats_out", c_void_p), ("stats_out_cap", c_uint64),
+                ("d_words", c_void_p), ("seed", c_uint64), ("first_index", c_uint64), ("bias", c_float), ("info", c_int32 * 4),
+                ("reserved2", c_int32)]
+
+
 class SpdmOptimSegment(ctypes.Structure):
     """spdm_optim_segment (include/spdm.h)."""
     _fields_ = [("d_param", c_void_p), ("d_grad", c_void_p), ("d_exp_avg", c_void_p), ("d_exp_avg_sq", c_void_p),
@@ -202,6 +223,7 @@ SYMBOLS = {
     "spdm_op_gelu": (c_int32, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "spdm_op_gemm": (c_int32, [POINTER(SpdmOpGemmArgs)]),
     "spdm_op_train": (c_int32, [POINTER(SpdmOpTrainArgs)]),
+    "spdm_op_stream": (c_int32, [POINTER(SpdmOpStreamArgs)]),
     "spdm_debug_geometry": (c_int32, [c_int32] * 6 + [ctypes.c_uint32, POINTER(c_int32 * 10)]),
     "spdm_debug_whole_tiles": (c_int32, []),
     "spdm_bench_gemm": (c_int32, [c_int32] * 12 + [POINTER(c_double)]),   # ms_out[2]: {ms per launch, max|split - fp32|}

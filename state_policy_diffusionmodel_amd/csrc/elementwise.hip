@@ -615,7 +615,22 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned
 // each reads 4 of the 64 feature channels, a 4-step xor-shuffle finishes the dot product.  The
 // scheduler arithmetic uses explicitly rounded fp32 operations (no FMA contraction) in the
 // library's operation order, so that with identical eps the update is bit-identical to torch's.
+// The operations are mul_rn / sub_rn / add_rn below, NOT hipcc's __fmul_rn / __fsub_rn / __fadd_rn: those are plain operators in
+// an inline header function, compiled under the default -ffp-contract=fast, and after inlining x - c0 * eps became one FMA
+// (tests/test_gpu_stream_ops_fp64.py, out_step: 2 of 144 elements one ulp off the individually rounded form).
 // EPS_IN: eps was computed by sa6's epilogue (StepArgs::eps_in, one thread per element): everything after the dot product.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
 template <bool EPS_IN>
 __global__ __launch_bounds__(256) void out_step_kernel(const StepArgs a) {
     const size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -658,19 +673,19 @@ __global__ __launch_bounds__(256) void out_step_kernel(const StepArgs a) {
         noise = static_cast<const float*>(a.ptrs_dev[1]);
         history = const_cast<float*>(static_cast<const float*>(a.ptrs_dev[2]));
     }
-    const float x0 = __fdiv_rn(__fsub_rn(x, __fmul_rn(c[0], eps)), c[1]);
+    const float x0 = __fdiv_rn(sub_rn(x, mul_rn(c[0], eps)), c[1]);
     float prev;
     if (a.kind == 0) {   // DDPM
-        prev = __fadd_rn(__fmul_rn(c[2], x0), __fmul_rn(c[3], x));
+        prev = add_rn(mul_rn(c[2], x0), mul_rn(c[3], x));
         if (c[5] != 0.f) {
             const float z = (noise != nullptr)
                                 ? noise[((size_t)i * a.B + b) * HD + he]
                                 : philox_normal(a.rng_dev[0], (unsigned)(a.rng_dev[1] + (unsigned long long)b),
                                                 (unsigned)i, (unsigned)he);
-            prev = __fadd_rn(prev, __fmul_rn(c[5], z));
+            prev = add_rn(prev, mul_rn(c[5], z));
         }
     } else {             // DDIM, eta = 0
-        prev = __fadd_rn(__fmul_rn(c[2], x0), __fmul_rn(c[4], eps));
+        prev = add_rn(mul_rn(c[2], x0), mul_rn(c[4], eps));
     }
     if (h0 < a.inp_h && inpaint != nullptr)
         prev = inpaint[(a.inpaint_per_sample ? (size_t)b * a.inp_h * a.D : 0) + (size_t)h0 * a.D + d];

@@ -4240,3 +4240,285 @@ extern "C" int spdm_op_train(spdm_op_train_args* p) {
     if (es != hipSuccess) return fail(SPDM_ERR_HIP, "op_train: op %d: %s", q.op, hipGetErrorString(es));
     return SPDM_OK;
 }
+
+// op-level test hook: one launch_* of elementwise.hip (the streaming kernels of the forward / sampling path) on the caller's tensors
+// (include/spdm.h).  Validate, upload the host integers, build AffineSrc / StatsRef / StepArgs, launch, synchronise.
+extern "C" int spdm_op_stream(spdm_op_stream_args* p) {
+    if (!p) return fail(SPDM_ERR_INVALID, "op_stream: null argument");
+    spdm_op_stream_args& q = *p;
+    for (int i = 0; i < 4; ++i) q.info[i] = -1;
+    if (q.op < 0 || q.op >= SPDM_OPS_COUNT) return fail(SPDM_ERR_INVALID, "op_stream: unknown op %d", q.op);
+    static const int n_dims[SPDM_OPS_COUNT] = {11, 4, 5, 5, 5, 2, 3, 3, 1, 3, 9, 4, 14};
+    const int64_t* d = q.dim;
+    for (int i = 0; i < SPDM_OP_STREAM_DIMS; ++i) {
+        const bool may_be_negative = q.op == SPDM_OPS_CONV_IN && i == 8;      // adv
+        if (d[i] < (may_be_negative ? -2 : 0) || d[i] > INT32_MAX)
+            return fail(SPDM_ERR_INVALID, "op_stream: dim[%d] = %lld outside [%d, 2^31)", i, (long long)d[i], may_be_negative ? -2 : 0);
+        if (i >= n_dims[q.op] && d[i] != 0) return fail(SPDM_ERR_INVALID, "op_stream: op %d takes %d dims; dim[%d] must be 0", q.op, n_dims[q.op], i);
+    }
+    auto positive = [&](std::initializer_list<int> which) {
+        for (int i : which) if (d[i] < 1) return false;
+        return true;
+    };
+#define OPS_BAD(...) return fail(SPDM_ERR_INVALID, "op_stream: " __VA_ARGS__)
+    OpTrainExtent E;
+    uint64_t need[SPDM_OP_STREAM_BUFS] = {};
+    bool optional[SPDM_OP_STREAM_BUFS] = {}, absent[SPDM_OP_STREAM_BUFS] = {};
+    int nbuf = 0;
+    int64_t idx_n = 0, idx_lim = 0;                 // entries of h_idx[0] (0: the op takes none); idx_lim > 0: entries below it
+    int64_t gn_C[SPDM_OP_STREAM_GN] = {0, 0}, gn_HW[SPDM_OP_STREAM_GN] = {0, 0}, gn_aff[SPDM_OP_STREAM_GN] = {0, 0};   // gn_C == 0: not taken
+    int64_t B = d[0];
+    uint64_t stats_need = 0;                        // doubles of d_stats_out (0: the op writes none)
+    bool stats_optional = false, words = false;
+    int parts = 0, slots_out = 0, rows = 0;
+    switch (q.op) {
+        case SPDM_OPS_CONV_IN: {
+            if (!positive({0, 1, 2, 3, 4})) OPS_BAD("conv_in: B, H0, D, Hp, Wp must be positive");
+            if (d[5] + d[1] > d[3] || d[6] + d[2] > d[4]) OPS_BAD("conv_in: lh + H0 <= Hp and lw + D <= Wp required");
+            const uint64_t HW = E.mul({d[3], d[4]});
+            if (!E.ok || (HW + 8) * sizeof(float) > 64 * 1024) OPS_BAD("conv_in: the padded image exceeds the LDS (Hp Wp + 8 floats in 64 KiB)");
+            if (d[8] == -2) {
+                if (d[9] != 0 || d[10] != 0) OPS_BAD("conv_in: adv -2 takes n_steps = step0 = 0");
+            } else {
+                if (d[9] < 1 || d[10] >= d[9] || d[8] > d[9]) OPS_BAD("conv_in: n_steps >= 1, 0 <= step0 < n_steps and adv <= n_steps required");
+                idx_n = d[9];
+                words = true;
+            }
+            need[0] = E.mul({B, d[1], d[2]}); need[1] = 9 * 64; need[2] = E.mul({B, (int64_t)HW, 64}); nbuf = 3;
+            parts = conv_in_parts((int)d[3], (int)d[4], (int)(d[7] > 0 ? d[7] : B));
+            slots_out = stats_slots((int)HW, (int)HW / parts, 1);
+            stats_need = E.mul({B, slots_out, 2});
+            break;
+        }
+        case SPDM_OPS_POOL:
+            if (!positive({0, 1, 2, 3}) || (d[1] & 1) || (d[2] & 1)) OPS_BAD("pool: B, H, W, C positive and H, W even required");
+            if (d[3] % 4 != 0 || d[3] > 1024) OPS_BAD("pool: C must be a multiple of 4 <= 1024 (got %lld)", (long long)d[3]);
+            need[0] = E.mul({B, d[1], d[2], d[3]}); need[1] = E.mul({B, d[1] / 2, d[2] / 2, d[3]}); nbuf = 2;
+            gn_C[0] = gn_aff[0] = d[3]; gn_HW[0] = (int64_t)E.mul({d[1], d[2]});
+            break;
+        case SPDM_OPS_UPCAT: {
+            if (!positive({0, 1, 2, 3})) OPS_BAD("upcat: B, Hin, Win, Cu must be positive");
+            const int64_t Cu = d[3], Cs = d[4];
+            if (Cu % 4 != 0 || Cs % 4 != 0 || Cu + Cs > 1024) OPS_BAD("upcat: Cu and Cs must be multiples of 4 with Cu + Cs <= 1024");
+            const int64_t HWi = (int64_t)E.mul({d[1], d[2]}), HWo = (int64_t)E.mul({4, d[1], d[2]});
+            need[0] = E.mul({B, HWi, Cu}); need[1] = Cs ? E.mul({B, HWo, Cs}) : 0; absent[1] = Cs == 0;
+            need[2] = E.mul({B, HWo, Cu + Cs}); nbuf = 3;
+            gn_C[0] = gn_aff[0] = Cu; gn_HW[0] = HWi;
+            gn_C[1] = gn_aff[1] = Cs; gn_HW[1] = HWo;
+            break;
+        }
+        case SPDM_OPS_FILM_APPLY:
+        case SPDM_OPS_FILM_COEF: {
+            if (!positive({0, 1, 2, 3, 4})) OPS_BAD("film: B, HW, C, t_count, T must be positive");
+            const int64_t C = d[2];
+            const bool apply = q.op == SPDM_OPS_FILM_APPLY;
+            if (apply && (C % 4 != 0 || C > 1024 || 256 % (C / 4) != 0)) OPS_BAD("film_apply: C / 4 must divide 256 (got C = %lld)", (long long)C);
+            if (d[3] != 1 && d[3] != B) OPS_BAD("film: t_count must be 1 or B");
+            const int it = apply ? 1 : 0;                                       // buffer index of temb
+            if (apply) need[0] = E.mul({B, d[1], C});
+            need[it] = E.mul({d[4], C}); optional[it] = true;
+            need[it + 1] = E.mul({B, 2, C}); optional[it + 1] = true;
+            need[it + 2] = apply ? need[0] : need[it + 1]; nbuf = it + 3;
+            if (q.d_buf[it]) { idx_n = d[3]; idx_lim = d[4]; }
+            else if (d[3] != 1 || d[4] != 1) OPS_BAD("film: without temb, t_count = T = 1");
+            gn_C[0] = gn_aff[0] = C; gn_HW[0] = d[1];
+            if (apply) {
+                stats_need = E.mul({B, d[1], 2}); stats_optional = true;
+                if (q.d_stats_out && !(C == 64 || C == 128 || C == 256)) OPS_BAD("film_apply: row statistics need C 64, 128 or 256 (got %lld)", (long long)C);
+            }
+            break;
+        }
+        case SPDM_OPS_LAYERNORM:
+            if (!positive({0, 1})) OPS_BAD("layernorm: rows and C must be positive");
+            if (d[1] != 64 && d[1] != 128 && d[1] != 256 && d[1] != 512) OPS_BAD("layernorm: C must be 64, 128, 256 or 512 (got %lld)", (long long)d[1]);
+            need[0] = need[3] = E.mul({d[0], d[1]}); need[1] = need[2] = (uint64_t)d[1]; nbuf = 4;
+            break;
+        case SPDM_OPS_MISH_PAD:
+        case SPDM_OPS_SILU_PAD:
+            if (!positive({0, 1, 2}) || d[2] < d[1]) OPS_BAD("mish_pad / silu_pad: B, cond_dim positive and Kp >= cond_dim required");
+            need[0] = E.mul({B, d[1]}); need[1] = E.mul({B, d[2]}); nbuf = 2;
+            break;
+        case SPDM_OPS_SILU:
+            if (!positive({0})) OPS_BAD("silu: n must be positive");
+            need[0] = need[1] = (uint64_t)d[0]; nbuf = 2;
+            break;
+        case SPDM_OPS_DC_FINISH:
+            if (!positive({0, 1, 2})) OPS_BAD("dc_finish: B, HW, C must be positive");
+            if (d[2] % 4 != 0 || d[2] > 1024) OPS_BAD("dc_finish: C must be a multiple of 4 <= 1024 (got %lld)", (long long)d[2]);
+            need[0] = need[1] = need[2] = E.mul({B, d[1], d[2]}); optional[1] = true; nbuf = 3;
+            gn_C[0] = gn_aff[0] = d[2]; gn_HW[0] = d[1];
+            break;
+        case SPDM_OPS_SIMPLE_TAIL: {
+            if (!positive({0, 1, 2, 3, 4, 5, 6, 7, 8})) OPS_BAD("simple_tail: every dimension must be positive");
+            const int64_t Co = d[2], Cr = d[3], Cs = d[4], tld = d[5], cld = d[6];
+            if (Co % 4 || Cr % 4 || Cs % 4 || tld % 4 || cld % 4) OPS_BAD("simple_tail: Co, Cr, src_C, temb_ld, cemb_ld must be multiples of 4");
+            if (Co > 1024 || Cr > Cs || Cr + 32 > Co || tld < Cr || cld < 32)
+                OPS_BAD("simple_tail: Co <= 1024, Cr <= src_C, Cr + 32 <= Co, temb_ld >= Cr and cemb_ld >= 32 required");
+            if (d[7] != 1 && d[7] != B) OPS_BAD("simple_tail: t_count must be 1 or B");
+            need[0] = E.mul({B, d[1], Cs}); need[1] = E.strided((uint64_t)d[8], tld, Cr); need[2] = E.strided((uint64_t)B, cld, 32);
+            need[3] = E.mul({B, d[1], Co}); nbuf = 4;
+            idx_n = d[7]; idx_lim = d[8];
+            gn_C[0] = Cs; gn_aff[0] = Cr; gn_HW[0] = d[1];
+            break;
+        }
+        case SPDM_OPS_SPLITK_COMBINE: {
+            if (!positive({0, 1, 2}) || d[3] < 2) OPS_BAD("splitk_combine: B, HW, N positive and ksplit >= 2 required");
+            if (d[2] % 4 != 0) OPS_BAD("splitk_combine: N must be a multiple of 4 (got %lld)", (long long)d[2]);
+            need[1] = E.mul({B, d[1], d[2]}); need[0] = E.mul({d[3], B, d[1], d[2]}); nbuf = 2;
+            rows = combine_rows((int)d[1], (int)d[2]);
+            if (d[1] % rows != 0) OPS_BAD("splitk_combine: rows per workgroup do not divide HW");
+            slots_out = stats_slots((int)d[1], rows, 1);
+            stats_need = E.mul({B, slots_out, 2});
+            break;
+        }
+        case SPDM_OPS_OUT_STEP: {
+            if (!positive({0, 1, 2, 3, 4, 10})) OPS_BAD("out_step: B, H0, D, Hp, Wp, n_steps must be positive");
+            if (d[5] + d[1] > d[3] || d[6] + d[2] > d[4]) OPS_BAD("out_step: lh + H0 <= Hp and lw + D <= Wp required");
+            const int64_t mode = d[8], inp_h = d[11];
+            if (d[7] > 1 || mode > 2 || d[12] > 1 || d[13] > 1) OPS_BAD("out_step: kind, inpaint_per_sample, indirect are 0 / 1 and mode 0, 1 or 2");
+            if (d[9] >= d[10]) OPS_BAD("out_step: step %lld outside [0, %lld)", (long long)d[9], (long long)d[10]);
+            if (inp_h > d[1]) OPS_BAD("out_step: inp_h must not exceed H0");
+            const uint64_t El = E.mul({B, d[1], d[2]});
+            need[0] = E.mul({B, d[3], d[4], 64}); need[1] = 64; need[2] = need[3] = El; need[4] = E.mul({d[10], 6});
+            need[5] = E.mul({d[10], (int64_t)El}); need[6] = E.mul({d[12] ? B : 1, inp_h ? inp_h : 1, d[2]}); need[7] = E.mul({d[10] + 1, (int64_t)El});
+            nbuf = 8;
+            absent[0] = absent[1] = mode == 2;
+            absent[2] = mode == 1;
+            for (int i = 3; i < 8; ++i) absent[i] = mode == 0;
+            optional[5] = optional[7] = true;
+            if (mode != 0 && inp_h == 0) absent[6] = true;
+            words = true;
+            break;
+        }
+    }
+    if (!E.ok) OPS_BAD("op %d: a tensor extent is beyond 31 bits", q.op);
+    for (int i = 0; i < SPDM_OP_STREAM_BUFS; ++i) {
+        if (i >= nbuf || absent[i]) {
+            if (q.d_buf[i]) OPS_BAD("op %d with these dimensions does not take d_buf[%d]; it must be null", q.op, i);
+            continue;
+        }
+        if (!q.d_buf[i]) {
+            if (!optional[i]) OPS_BAD("op %d: d_buf[%d] is null", q.op, i);
+            continue;
+        }
+        if (q.cap[i] < need[i])
+            OPS_BAD("op %d: d_buf[%d] holds %llu floats, the launch needs %llu", q.op, i, (unsigned long long)q.cap[i], (unsigned long long)need[i]);
+    }
+    if (idx_n == 0) {
+        if (q.h_idx[0] || q.n_idx[0]) OPS_BAD("op %d with these arguments takes no index arrays; h_idx[0] must be null", q.op);
+    } else {
+        if (!q.h_idx[0] || q.n_idx[0] != idx_n) OPS_BAD("op %d: h_idx[0] must hold %lld entries", q.op, (long long)idx_n);
+        for (int64_t i = 0; i < idx_n; ++i)
+            if (q.h_idx[0][i] < 0 || (idx_lim > 0 && q.h_idx[0][i] >= idx_lim))
+                OPS_BAD("op %d: h_idx[0][%lld] = %d outside [0, %lld)", q.op, (long long)i, q.h_idx[0][i], (long long)(idx_lim > 0 ? idx_lim : (int64_t)INT32_MAX + 1));
+    }
+    StatsRef st[SPDM_OP_STREAM_GN];
+    for (int k = 0; k < SPDM_OP_STREAM_GN; ++k) {
+        const spdm_op_stream_gn& g = q.gn[k];
+        st[k] = StatsRef{nullptr, 0, 1, 1, (int)gn_HW[k], 0.0};
+        if (gn_C[k] == 0 || !g.d_stats) {
+            if (g.d_stats) OPS_BAD("op %d takes no pending GroupNorm on source %d; gn[%d] must be empty", q.op, k, k);
+            if (g.stats_cap || g.slots || g.m_tile || g.n_tiles || g.cnorm || g.d_gamma || g.d_beta || g.affine_cap)
+                OPS_BAD("op %d: gn[%d] has no statistics; its other fields must be empty", q.op, k);
+            continue;
+        }
+        if (g.slots < 1 || g.m_tile < 1 || g.n_tiles < 1) OPS_BAD("op %d: gn[%d] needs slots, m_tile and n_tiles >= 1", q.op, k);
+        if (g.cnorm < 1 || g.cnorm > gn_C[k]) OPS_BAD("op %d: gn[%d].cnorm %d outside [1, %lld]", q.op, k, g.cnorm, (long long)gn_C[k]);
+        if (!g.d_gamma || !g.d_beta) OPS_BAD("op %d: gn[%d] needs gamma and beta", q.op, k);
+        if (g.affine_cap < (uint64_t)gn_aff[k])
+            OPS_BAD("op %d: gn[%d] gamma / beta hold %llu floats, the launch needs %lld", q.op, k, (unsigned long long)g.affine_cap, (long long)gn_aff[k]);
+        // the slots sample b's consumer adds: tiles first .. last of its rows, n_tiles each (sample_mean_rstd_wave)
+        const int64_t HW = gn_HW[k], mt = g.m_tile;
+        int64_t reads = ((HW + mt - 2) / mt + 1) * g.n_tiles;                  // the bound over every alignment
+        if (std::min<int64_t>(B, mt) <= (1 << 20)) {                            // the alignments repeat with period <= m_tile
+            reads = 0;
+            for (int64_t b = 0; b < std::min<int64_t>(B, mt); ++b)
+                reads = std::max<int64_t>(reads, ((b * HW + HW - 1) / mt - (b * HW) / mt + 1) * g.n_tiles);
+        }
+        if (g.slots < reads) OPS_BAD("op %d: gn[%d] has %d slots per sample, the consumer reads %lld", q.op, k, g.slots, (long long)reads);
+        const uint64_t cap = E.mul({B, g.slots, 2});
+        if (!E.ok) OPS_BAD("op %d: a tensor extent is beyond 31 bits", q.op);
+        if (g.stats_cap < cap) OPS_BAD("op %d: gn[%d] statistics hold %llu doubles, the launch needs %llu", q.op, k, (unsigned long long)g.stats_cap, (unsigned long long)cap);
+        st[k] = StatsRef{g.d_stats, g.slots, g.m_tile, g.n_tiles, (int)HW, 1.0 / ((double)g.cnorm * (double)HW)};
+    }
+    if (stats_need == 0) {
+        if (q.d_stats_out || q.stats_out_cap) OPS_BAD("op %d writes no statistics; d_stats_out must be null", q.op);
+    } else if (!q.d_stats_out) {
+        if (!stats_optional) OPS_BAD("op %d: d_stats_out is null", q.op);
+    } else if (q.stats_out_cap < stats_need) {
+        OPS_BAD("op %d: d_stats_out holds %llu doubles, the launch needs %llu", q.op, (unsigned long long)q.stats_out_cap, (unsigned long long)stats_need);
+    }
+    if (words != (q.d_words != nullptr)) OPS_BAD("op %d with these arguments %s d_words", q.op, words ? "needs" : "does not take");
+#undef OPS_BAD
+    // ---- the device from here on ----
+    OpTrainDev dev;
+    const int* di = nullptr;
+    if (idx_n) {
+        HIP_TRY(hipMalloc(&dev.p[0], sizeof(int) * (size_t)idx_n));
+        HIP_TRY(hipMemcpy(dev.p[0], q.h_idx[0], sizeof(int) * (size_t)idx_n, hipMemcpyHostToDevice));
+        di = (const int*)dev.p[0];
+    }
+    if (words) {
+        const int w3[3] = {(int)(q.op == SPDM_OPS_CONV_IN ? d[10] : d[9]), -1, 0};
+        HIP_TRY(hipMemcpy(q.d_words, w3, sizeof(w3), hipMemcpyHostToDevice));
+    }
+    float* const* b = q.d_buf;
+    const int i0 = (int)d[0], i1 = (int)d[1], i2 = (int)d[2], i3 = (int)d[3], i4 = (int)d[4], i5 = (int)d[5], i6 = (int)d[6];
+    auto asrc = [&](int k, const float* x, int C) { return AffineSrc{x, C, st[k], q.gn[k].d_gamma, q.gn[k].d_beta}; };
+    hipStream_t s = nullptr;
+    hipError_t el = hipSuccess;
+    switch (q.op) {
+        case SPDM_OPS_CONV_IN:
+            el = launch_conv_in(b[0], b[1], b[2], q.d_stats_out, i0, i1, i2, i3, i4, i5, i6, q.d_words, q.d_words ? q.d_words + 1 : nullptr, di,
+                                (int)d[9], (int)d[8], s, (int)d[7]);
+            q.info[0] = parts; q.info[1] = slots_out;
+            break;
+        case SPDM_OPS_POOL: el = launch_pool(asrc(0, b[0], i3), b[1], i0, i1, i2, s); break;
+        case SPDM_OPS_UPCAT: el = launch_upcat(asrc(0, b[0], i3), asrc(1, b[1], i4), b[2], i0, i1, i2, s); break;
+        case SPDM_OPS_FILM_APPLY:
+            if (!b[1] && !b[2] && !q.gn[0].d_stats && !q.d_stats_out) el = launch_gn_apply(asrc(0, b[0], i2), b[3], i0, i1, s);
+            else el = launch_film_apply(asrc(0, b[0], i2), b[1], di, i3, b[2], b[3], q.d_stats_out, i0, i1, s);
+            break;
+        case SPDM_OPS_FILM_COEF: el = launch_film_coef(asrc(0, nullptr, i2), b[0], di, i3, b[1], b[2], i0, s); break;
+        case SPDM_OPS_LAYERNORM: el = launch_layernorm(b[0], b[1], b[2], b[3], i0, i1, s); break;
+        case SPDM_OPS_MISH_PAD: el = launch_mish_pad(b[0], b[1], i0, i1, i2, s); break;
+        case SPDM_OPS_SILU_PAD: el = launch_silu_pad(b[0], b[1], i0, i1, i2, s); break;
+        case SPDM_OPS_SILU: el = launch_silu(b[0], b[1], (size_t)d[0], s); break;
+        case SPDM_OPS_DC_FINISH: el = launch_dc_finish(asrc(0, b[0], i2), b[1], b[2], i0, i1, s); break;
+        case SPDM_OPS_SIMPLE_TAIL:
+            el = launch_simple_tail(asrc(0, b[0], i4), i3, b[1], i5, di, (int)d[7], b[2], i6, b[3], i2, i0, i1, s);
+            break;
+        case SPDM_OPS_SPLITK_COMBINE:
+            el = launch_splitk_combine(b[0], i3, b[1], i0 * i1, i2, i1, q.d_stats_out, s);
+            q.info[0] = rows; q.info[1] = slots_out;
+            break;
+        case SPDM_OPS_OUT_STEP: {
+            const unsigned long long rng[2] = {q.seed, q.first_index};
+            HIP_TRY(hipMalloc(&dev.p[1], sizeof(rng)));
+            HIP_TRY(hipMemcpy(dev.p[1], rng, sizeof(rng), hipMemcpyHostToDevice));
+            StepArgs a{};
+            a.feat = b[0]; a.w = b[1]; a.bias = q.bias; a.x = b[3];
+            a.eps_out = d[8] == 0 ? b[2] : nullptr;
+            a.eps_in = d[8] == 2 ? b[2] : nullptr;
+            a.coef = b[4]; a.step_dev = q.d_words; a.kind = (int)d[7];
+            a.rng_dev = (const unsigned long long*)dev.p[1];
+            a.flag_dev = q.d_words + 2;
+            a.inp_h = (int)d[11]; a.inpaint_per_sample = (int)d[12];
+            if (d[13]) {
+                const void* ptrs[3] = {b[6], b[5], b[7]};
+                HIP_TRY(hipMalloc(&dev.p[2], sizeof(ptrs)));
+                HIP_TRY(hipMemcpy(dev.p[2], ptrs, sizeof(ptrs), hipMemcpyHostToDevice));
+                a.ptrs_dev = (const void* const*)dev.p[2];
+            } else {
+                a.inpaint = b[6]; a.noise = b[5]; a.history = b[7];
+            }
+            a.B = i0; a.H0 = i1; a.D = i2; a.Hp = i3; a.Wp = i4; a.lh = i5; a.lw = i6;
+            el = launch_out_step(a, s);
+            break;
+        }
+    }
+    const hipError_t es = hipDeviceSynchronize();
+    if (el != hipSuccess) return fail(SPDM_ERR_HIP, "op_stream: op %d: launch failed: %s; device: %s", q.op, hipGetErrorString(el), hipGetErrorString(es));
+    if (es != hipSuccess) return fail(SPDM_ERR_HIP, "op_stream: op %d: %s", q.op, hipGetErrorString(es));
+    return SPDM_OK;
+}

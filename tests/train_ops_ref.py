@@ -612,8 +612,10 @@ def worst_ratio(got, ref, scale, tau):
     return worst
 
 
-def tau(op, inp, r64=None, s64=None):
-    """4 x the sequential float32 reference's own worst error in units of S, floored for the math-library ops."""
+def tau(op, inp, r64=None, s64=None, refs=None):
+    """4 x the sequential float32 reference's own worst error in units of S, floored for the math-library ops.
+    refs: (ref64, scale64, ref32, FLOOR_U) of another family of ops (tests/stream_ops_ref.py); None: this module's."""
+    ref64, scale64, ref32, FLOOR_U = refs or (globals()[k] for k in ("ref64", "scale64", "ref32", "FLOOR_U"))
     r64 = ref64(op, inp) if r64 is None else r64
     s64 = scale64(op, inp) if s64 is None else s64
     r32 = ref32(op, inp)
