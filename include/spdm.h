@@ -1030,6 +1030,75 @@ typedef struct {
 
 int  spdm_op_stream(spdm_op_stream_args* args);
 
+/* Op-level test hook: ONE launch of the observation encoder or of the autoencoder's decoder (launch_* of csrc/encoder.hip,
+ * csrc/encoder_train.hip, csrc/decoder.hip, and launch_wgrad under the slab budgets of the two passes) exactly as
+ * spdm_encoder_* / spdm_decoder_* call it, on caller-supplied tensors, synchronously on the current device.  Not on the
+ * product path.  The hook validates, allocates the scratch the product allocates (the partial rows of conv 1 and of layer 6,
+ * the column-sum slabs, the weight gradient's slabs: its own, within the product's sizes, filled with NaN first), calls the
+ * launcher and synchronises -- nothing else; it has no arithmetic of its own.
+ *   d_buf[i] / cap[i]   DEVICE float arrays and capacities in floats, as for spdm_op_train (optional ones may be NULL)
+ *   d_sq / sq_cap       DEVICE float64 array: the per-frame sums of squared errors (DEC_CONVS with train: out; DEC_LOSS: in)
+ *   scale               DEC_BWD6: the factor of (recon - target), 2 / (n 27648) in the product
+ *   info[]              filled by the hook (-1 where unused)
+ * SPDM_ERR_INVALID, before the GPU is touched: NULL args, an unknown op, a dimension that is not positive or outside what the
+ * two passes produce, a capacity below the extent, a buffer the op does not take, an extent beyond 31 bits, a scale that is
+ * not finite.  SPDM_ERR_HIP: the launch or the final synchronise failed.  Deterministic: the same bits on the same inputs.
+ * Weights are in the KERNEL layouts the launchers read.  Encoder: torch's own (cout, cin, 2, 2).  Decoder: a transposed
+ * convolution (cin, cout, 2, 2) as w[ci][kk][co], kk = ky 2 + kx; the Linear's rows and bias as q 64 + c (Flatten order is
+ * c 144 + q).  Row orders (csrc/decoder.hip): h0 [n 144][64], a1 [n 576][32] with row r2 = (n 144 + q) 4 + kk1, a2 [n 2304][16]
+ * with row r3 = r2 4 + kk2, recon NCHW.  Encoder (csrc/encoder_train.hip): feat [n][co 144 + q], x3 [n 144][ci 4 + ky 2 + kx],
+ * x2 [(n 144 + q) 4 + kk][c1 4 + ky 2 + kx].  n <= 2048 frames (one chunk of the passes) for every per-frame op but DEC_LOSS.
+ *
+ * op, dim[] (all others 0), buffers with their extents:
+ *  ENC_CONVS     dim {n, train}; train 0: launch_encoder_convs, 1: launch_encoder_train_convs.  buf {img [n 27648], w1 [192],
+ *                b1 [16], w2 [2048], b2 [32], w3 [8192], b3 [64], feat [n 9216] out, x3 [n 18432] out (train == 1, else NULL)}.
+ *  ENC_KINKS     dim {n}.  buf as ENC_CONVS with train; feat and x3 in/out.
+ *  ENC_X2        dim {n}.  buf {img [n 27648], w1 [192], b1 [16], x2 [n 36864] out}.
+ *  ENC_DZ3       dim {n}.  buf {dfeat [n 9216], feat [n 9216], dz3 [n 9216] out}.
+ *  ENC_DZ2       dim {n}.  buf {dx3 [n 18432], x3 [n 18432], dz2 [n 18432] out}.
+ *  ENC_CONV1_WGRAD  dim {n}.  buf {img [n 27648], dx2 [n 36864], x2 [n 36864], dw [192] out, db [16] out}.  info {blocks}.
+ *  ADD           dim {n} (elements, not frames).  buf {src [n], dst [n] in/out}.
+ *  DEC_CONVS     dim {n, train}; train 0: launch_decoder_convs, 1: launch_decoder_train_convs.  buf {h0 [n 9216], w2 [8192],
+ *                b2 [32], w4 [2048], b4 [16], w6 [192], b6 [3], recon [n 27648] out, target [n 27648], a1 [n 18432] out,
+ *                a2 [n 36864] out}; d_sq [n] out.  target, a1, a2 and d_sq go with train == 1 and must be NULL otherwise.
+ *  DEC_KINKS     dim {n}.  buf {latent [n 128], w0 [9216 128], b0 [9216], w2, b2, w4, b4, a1 [n 18432] in/out,
+ *                a2 [n 36864] in/out}.
+ *  DEC_LOSS      dim {n}, any n > 0 (the loss is formed over all frames of a call).  d_sq [n] in; buf {loss [1] out}.
+ *  DEC_BWD6      dim {n}; scale.  buf {recon [n 27648], target [n 27648], a2 [n 36864], w6 [192], dz4 [n 36864] out,
+ *                dw [192] out (torch order ci 12 + co 4 + kk), db [3] out}.
+ *  DEC_DGRAD4    dim {n}.  buf {dz4 [n 576 64], a1 [n 576 32], w4 [2048], dz2 [n 576 32] out}.
+ *  DEC_COLSUM    dim {M, C, fold}; fold 4: C 64 (M <= 2048 576) or 128 (M <= 2048 144), dst [C / 4]; fold 1: C 9216, M <= 2048,
+ *                dst [9216] in Flatten order.  buf {src [M C], dst out}.  info {slab_rows, slabs}.
+ *  DEC_UNPERM_CONV    dim {cin, cout}: (64, 32), (32, 16) or (16, 3).  buf {src [cin 4 cout], dst [cin cout 4] out}.
+ *  DEC_UNPERM_LINEAR  no dims.  buf {src [9216 128], dst [9216 128] out}.
+ *  FRAME_WGRAD   dim {M, which}; launch_wgrad with taps 1 on dy [M Co], x [M Ci] under the budget of the pass that runs it:
+ *                which 0 encoder Linear (Co 128, Ci 9216, M <= 2048), 1 encoder conv 3 (64, 128, M <= 2048 144), 2 encoder
+ *                conv 2 (32, 64, M <= 2048 576) -- all under ENC_WG_FLOATS; 3 decoder layer 4 (32, 64, M <= 2048 576, 256 slabs),
+ *                4 decoder layer 2 (64, 128, M <= 2048 144, 256 slabs), 5 decoder Linear (9216, 128, M <= 2048, DEC_WG_FLOATS).
+ *                buf {dy [M Co], x [M Ci], dst [Co Ci] out}.  info {chunks, rows per chunk, Co, Ci}. */
+enum {
+    SPDM_OPF_ENC_CONVS = 0, SPDM_OPF_ENC_KINKS, SPDM_OPF_ENC_X2, SPDM_OPF_ENC_DZ3, SPDM_OPF_ENC_DZ2, SPDM_OPF_ENC_CONV1_WGRAD,
+    SPDM_OPF_ADD, SPDM_OPF_DEC_CONVS, SPDM_OPF_DEC_KINKS, SPDM_OPF_DEC_LOSS, SPDM_OPF_DEC_BWD6, SPDM_OPF_DEC_DGRAD4,
+    SPDM_OPF_DEC_COLSUM, SPDM_OPF_DEC_UNPERM_CONV, SPDM_OPF_DEC_UNPERM_LINEAR, SPDM_OPF_FRAME_WGRAD,
+    SPDM_OPF_COUNT
+};
+#define SPDM_OP_FRAME_DIMS 4
+#define SPDM_OP_FRAME_BUFS 11
+typedef struct {
+    int32_t op;
+    int32_t reserved;
+    int64_t dim[SPDM_OP_FRAME_DIMS];
+    float* d_buf[SPDM_OP_FRAME_BUFS];
+    uint64_t cap[SPDM_OP_FRAME_BUFS];
+    double* d_sq;
+    uint64_t sq_cap;
+    float scale;
+    int32_t info[4];
+    int32_t reserved2;
+} spdm_op_frame_args;
+
+int  spdm_op_frame(spdm_op_frame_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,19 @@ class SpdmOpStreamArgs(ctypes.Structure):
                 ("reserved2", c_int32)]
 
 
+# spdm_op_frame op codes (include/spdm.h: SPDM_OPF_*), in enum order
+OP_FRAME_OPS = ("enc_convs", "enc_kinks", "enc_x2", "enc_dz3", "enc_dz2", "enc_conv1_wgrad", "add", "dec_convs", "dec_kinks",
+                "dec_loss", "dec_bwd6", "dec_dgrad4", "dec_colsum", "dec_unperm_conv", "dec_unperm_linear", "frame_wgrad")
+OP_FRAME_DIMS, OP_FRAME_BUFS = 4, 11
+
+
+class SpdmOpFrameArgs(ctypes.Structure):
+    """spdm_op_frame_args (include/spdm.h)."""
+    _fields_ = [("op", c_int32), ("reserved", c_int32), ("dim", c_int64 * OP_FRAME_DIMS), ("d_buf", c_void_p * OP_FRAME_BUFS),
+                ("cap", c_uint64 * OP_FRAME_BUFS), ("d_sq", c_void_p), ("sq_cap", c_uint64), ("scale", c_float),
+                ("info", c_int32 * 4), ("reserved2", c_int32)]
+
+
 class SpdmOptimSegment(ctypes.Structure):
     """spdm_optim_segment (include/spdm.h)."""
     _fields_ = [("d_param", c_void_p), ("d_grad", c_void_p), ("d_exp_avg", c_void_p), ("d_exp_avg_sq", c_void_p),
@@ -224,6 +237,7 @@ SYMBOLS = {
     "spdm_op_gemm": (c_int32, [POINTER(SpdmOpGemmArgs)]),
     "spdm_op_train": (c_int32, [POINTER(SpdmOpTrainArgs)]),
     "spdm_op_stream": (c_int32, [POINTER(SpdmOpStreamArgs)]),
+    "spdm_op_frame": (c_int32, [POINTER(SpdmOpFrameArgs)]),
     "spdm_debug_geometry": (c_int32, [c_int32] * 6 + [ctypes.c_uint32, POINTER(c_int32 * 10)]),
     "spdm_debug_whole_tiles": (c_int32, []),
     "spdm_bench_gemm": (c_int32, [c_int32] * 12 + [POINTER(c_double)]),   # ms_out[2]: {ms per launch, max|split - fp32|}

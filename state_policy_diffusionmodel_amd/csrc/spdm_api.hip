@@ -4522,3 +4522,187 @@ extern "C" int spdm_op_stream(spdm_op_stream_args* p) {
     if (es != hipSuccess) return fail(SPDM_ERR_HIP, "op_stream: op %d: %s", q.op, hipGetErrorString(es));
     return SPDM_OK;
 }
+
+// op-level test hook: one launch_* of the autoencoder's decoder stage (decoder.hip), launch_add, or launch_wgrad under the slab
+// budgets of the encoder / decoder passes, on the caller's tensors (include/spdm.h).  Validate, allocate the product's scratch
+// (NaN-filled), launch, synchronise.
+extern "C" int spdm_op_frame(spdm_op_frame_args* p) {
+    if (!p) return fail(SPDM_ERR_INVALID, "op_frame: null argument");
+    spdm_op_frame_args& q = *p;
+    for (int i = 0; i < 4; ++i) q.info[i] = -1;
+    if (q.op < 0 || q.op >= SPDM_OPF_COUNT) return fail(SPDM_ERR_INVALID, "op_frame: unknown op %d", q.op);
+    static const int n_dims[SPDM_OPF_COUNT] = {2, 1, 1, 1, 1, 1, 1, 2, 1, 1, 1, 1, 3, 2, 0, 2};
+    const int64_t* d = q.dim;
+    for (int i = 0; i < SPDM_OP_FRAME_DIMS; ++i) {
+        if (d[i] < 0 || d[i] > INT32_MAX) return fail(SPDM_ERR_INVALID, "op_frame: dim[%d] = %lld outside [0, 2^31)", i, (long long)d[i]);
+        if (i >= n_dims[q.op] && d[i] != 0) return fail(SPDM_ERR_INVALID, "op_frame: op %d takes %d dims; dim[%d] must be 0", q.op, n_dims[q.op], i);
+    }
+#define OPF_BAD(...) return fail(SPDM_ERR_INVALID, "op_frame: " __VA_ARGS__)
+    OpTrainExtent E;
+    uint64_t need[SPDM_OP_FRAME_BUFS] = {};
+    bool absent[SPDM_OP_FRAME_BUFS] = {};          // a buffer that must be NULL in this call (DEC_CONVS without train)
+    int nbuf = 0;
+    uint64_t need_sq = 0;                          // extent of d_sq; 0: the op does not take it
+    uint64_t scratch = 0;                          // floats of the hook's own scratch
+    // (the loss is formed once over ALL frames of a call, not per chunk)
+    const bool frames = q.op <= SPDM_OPF_ENC_CONV1_WGRAD || (q.op >= SPDM_OPF_DEC_CONVS && q.op <= SPDM_OPF_DEC_DGRAD4 && q.op != SPDM_OPF_DEC_LOSS);
+    if (frames && (d[0] < 1 || d[0] > ENC_CHUNK)) OPF_BAD("op %d: n = %lld outside [1, %d] frames", q.op, (long long)d[0], ENC_CHUNK);
+    const int64_t n = d[0];
+    int wCo = 0, wCi = 0, nch = 0, wrows = 0;
+    size_t budget = 0;
+    switch (q.op) {
+        case SPDM_OPF_ENC_CONVS:
+        case SPDM_OPF_ENC_KINKS: {
+            if (q.op == SPDM_OPF_ENC_CONVS && d[1] > 1) OPF_BAD("enc_convs: train must be 0 or 1");
+            const uint64_t w[9] = {E.mul({n, DEC_PIX}), 16 * 3 * 4, 16, 32 * 16 * 4, 32, 64 * 32 * 4, 64, E.mul({n, ENC_FEAT}), E.mul({n, ENC_X3})};
+            for (int i = 0; i < 9; ++i) need[i] = w[i];
+            nbuf = 9;
+            if (q.op == SPDM_OPF_ENC_CONVS && d[1] == 0) absent[8] = true;
+            break;
+        }
+        case SPDM_OPF_ENC_X2: need[0] = E.mul({n, DEC_PIX}); need[1] = 192; need[2] = 16; need[3] = E.mul({n, ENC_X2}); nbuf = 4; break;
+        case SPDM_OPF_ENC_DZ3: need[0] = need[1] = need[2] = E.mul({n, ENC_FEAT}); nbuf = 3; break;
+        case SPDM_OPF_ENC_DZ2: need[0] = need[1] = need[2] = E.mul({n, ENC_X3}); nbuf = 3; break;
+        case SPDM_OPF_ENC_CONV1_WGRAD:
+            need[0] = E.mul({n, DEC_PIX}); need[1] = need[2] = E.mul({n, ENC_X2}); need[3] = 192; need[4] = 16; nbuf = 5;
+            scratch = (uint64_t)encoder_conv1_wgrad_blocks((int)n) * 208;           // c1_part: [blocks(ENC_CHUNK)][208] in the product
+            break;
+        case SPDM_OPF_DEC_CONVS: {
+            if (d[1] > 1) OPF_BAD("dec_convs: train must be 0 or 1");
+            const uint64_t w[7] = {E.mul({n, DEC_FEAT}), 64 * 4 * 32, 32, 32 * 4 * 16, 16, 16 * 4 * 3, 3};
+            for (int i = 0; i < 7; ++i) need[i] = w[i];
+            need[7] = need[8] = E.mul({n, DEC_PIX}); need[9] = E.mul({n, DEC_A1}); need[10] = E.mul({n, DEC_A2}); nbuf = 11;
+            if (d[1] == 0) absent[8] = absent[9] = absent[10] = true;
+            else need_sq = (uint64_t)n;
+            if (d[1] == 0 && q.d_sq) OPF_BAD("dec_convs: d_sq must be null without train");
+            break;
+        }
+        case SPDM_OPF_DEC_KINKS: {
+            const uint64_t w[9] = {E.mul({n, DEC_LATENT}), (uint64_t)DEC_FEAT * DEC_LATENT, DEC_FEAT, 64 * 4 * 32, 32, 32 * 4 * 16, 16,
+                                   E.mul({n, DEC_A1}), E.mul({n, DEC_A2})};
+            for (int i = 0; i < 9; ++i) need[i] = w[i];
+            nbuf = 9;
+            break;
+        }
+        case SPDM_OPF_DEC_LOSS:
+            if (n < 1) OPF_BAD("dec_loss: n must be positive");
+            need[0] = 1; nbuf = 1; need_sq = (uint64_t)n;
+            break;
+        case SPDM_OPF_DEC_BWD6:
+            if (!std::isfinite(q.scale)) OPF_BAD("dec_bwd6: scale is not finite");
+            need[0] = need[1] = E.mul({n, DEC_PIX}); need[2] = need[4] = E.mul({n, DEC_A2}); need[3] = need[5] = 192; need[6] = 3; nbuf = 7;
+            scratch = (uint64_t)n * 208;                                          // w6_part: [ENC_CHUNK][208] in the product
+            break;
+        case SPDM_OPF_DEC_DGRAD4:
+            need[0] = E.mul({n, 576, 64}); need[1] = need[3] = E.mul({n, DEC_A1}); need[2] = 32 * 64; nbuf = 4;
+            break;
+        case SPDM_OPF_DEC_COLSUM: {
+            const int64_t M = d[0], C = d[1], fold = d[2];
+            if (M < 1) OPF_BAD("dec_colsum: M must be positive");
+            if (!((fold == 4 && (C == 64 || C == 128)) || (fold == 1 && C == DEC_FEAT)))
+                OPF_BAD("dec_colsum: (C, fold) must be (64, 4), (128, 4) or (9216, 1)");
+            const int64_t max_m = (int64_t)ENC_CHUNK * (fold == 1 ? 1 : C == 64 ? 576 : 144);
+            if (M > max_m) OPF_BAD("dec_colsum: M = %lld beyond the %lld rows of one chunk", (long long)M, (long long)max_m);
+            need[0] = E.mul({M, C}); need[1] = (uint64_t)(C / fold); nbuf = 2;
+            scratch = (uint64_t)decoder_colsum_slabs(M) * (uint64_t)C;
+            if (scratch > (uint64_t)decoder_colsum_slabs(ENC_CHUNK) * DEC_FEAT) OPF_BAD("dec_colsum: the slabs exceed cs_part");
+            break;
+        }
+        case SPDM_OPF_DEC_UNPERM_CONV:
+            if (!((d[0] == 64 && d[1] == 32) || (d[0] == 32 && d[1] == 16) || (d[0] == 16 && d[1] == 3)))
+                OPF_BAD("dec_unperm_conv: (cin, cout) must be (64, 32), (32, 16) or (16, 3)");
+            need[0] = need[1] = (uint64_t)(d[0] * d[1] * 4); nbuf = 2;
+            break;
+        case SPDM_OPF_DEC_UNPERM_LINEAR: need[0] = need[1] = (uint64_t)DEC_FEAT * DEC_LATENT; nbuf = 2; break;
+        case SPDM_OPF_ADD:
+            if (d[0] < 1) OPF_BAD("add: n must be positive");
+            need[0] = need[1] = (uint64_t)d[0]; nbuf = 2;
+            break;
+        case SPDM_OPF_FRAME_WGRAD: {
+            static const struct { int Co, Ci, rows_per_frame; } W[6] = {{ENC_LATENT, ENC_FEAT, 1}, {64, 128, 144}, {32, 64, 576},
+                                                                        {32, 64, 576}, {64, 128, 144}, {DEC_FEAT, DEC_LATENT, 1}};
+            if (d[0] < 1) OPF_BAD("frame_wgrad: M must be positive");
+            if (d[1] > 5) OPF_BAD("frame_wgrad: which = %lld outside [0, 5]", (long long)d[1]);
+            const int k = (int)d[1];
+            wCo = W[k].Co; wCi = W[k].Ci;
+            const size_t budgets[6] = {ENC_WG_FLOATS, ENC_WG_FLOATS, ENC_WG_FLOATS, DEC_WG_SLABS * 32 * 64, DEC_WG_SLABS * 64 * 128, DEC_WG_FLOATS};
+            budget = budgets[k];
+            if (d[0] > (int64_t)ENC_CHUNK * W[k].rows_per_frame)
+                OPF_BAD("frame_wgrad: M = %lld beyond the %lld rows of one chunk", (long long)d[0], (long long)ENC_CHUNK * W[k].rows_per_frame);
+            need[0] = E.mul({d[0], wCo}); need[1] = E.mul({d[0], wCi}); need[2] = (uint64_t)wCo * wCi; nbuf = 3;
+            if (!E.ok) break;
+            nch = wgrad_chunks((long long)d[0], 1, wCo, wCi, budget);
+            scratch = (uint64_t)nch * wCo * wCi;
+            if (nch < 1 || scratch > budget) OPF_BAD("frame_wgrad: the partial slabs exceed the budget");
+            wrows = (int)((((long long)d[0] + nch - 1) / nch + 3) / 4 * 4);
+            break;
+        }
+    }
+    if (!E.ok) OPF_BAD("op %d: a tensor extent is beyond 31 bits", q.op);
+    for (int i = 0; i < SPDM_OP_FRAME_BUFS; ++i) {
+        if (i >= nbuf || absent[i]) {
+            if (q.d_buf[i]) OPF_BAD("op %d does not take d_buf[%d] here; it must be null", q.op, i);
+            continue;
+        }
+        if (!q.d_buf[i]) OPF_BAD("op %d: d_buf[%d] is null", q.op, i);
+        if (q.cap[i] < need[i])
+            OPF_BAD("op %d: d_buf[%d] holds %llu floats, the launch needs %llu", q.op, i, (unsigned long long)q.cap[i], (unsigned long long)need[i]);
+    }
+    if (need_sq) {
+        if (!q.d_sq) OPF_BAD("op %d: d_sq is null", q.op);
+        if (q.sq_cap < need_sq) OPF_BAD("op %d: d_sq holds %llu doubles, the launch needs %llu", q.op, (unsigned long long)q.sq_cap, (unsigned long long)need_sq);
+    } else if (q.d_sq) {
+        OPF_BAD("op %d does not take d_sq here; it must be null", q.op);
+    }
+    if (q.op != SPDM_OPF_DEC_BWD6 && q.scale != 0.f) OPF_BAD("op %d does not take a scale; it must be 0", q.op);
+#undef OPF_BAD
+    // ---- the device from here on ----
+    OpTrainDev dev;
+    float* part = nullptr;
+    if (scratch) {
+        HIP_TRY(hipMalloc(&dev.p[0], sizeof(float) * (size_t)scratch));
+        HIP_TRY(hipMemset(dev.p[0], 0xff, sizeof(float) * (size_t)scratch));    // an unwritten partial reads as NaN
+        part = (float*)dev.p[0];
+    }
+    float* const* b = q.d_buf;
+    const int ni = (int)n;
+    hipStream_t s = nullptr;
+    hipError_t el = hipSuccess;
+    switch (q.op) {
+        case SPDM_OPF_ENC_CONVS:
+            el = d[1] ? launch_encoder_train_convs(b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], b[8], ni, s)
+                      : launch_encoder_convs(b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], ni, s);
+            break;
+        case SPDM_OPF_ENC_KINKS: el = launch_encoder_kinks(b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], b[8], ni, s); break;
+        case SPDM_OPF_ENC_X2: el = launch_encoder_x2(b[0], b[1], b[2], ni, b[3], s); break;
+        case SPDM_OPF_ENC_DZ3: el = launch_encoder_dz3(b[0], b[1], ni, b[2], s); break;
+        case SPDM_OPF_ENC_DZ2: el = launch_encoder_dz2(b[0], b[1], ni, b[2], s); break;
+        case SPDM_OPF_ENC_CONV1_WGRAD:
+            el = launch_encoder_conv1_wgrad(b[0], b[1], b[2], ni, part, b[3], b[4], s);
+            q.info[0] = encoder_conv1_wgrad_blocks(ni);
+            break;
+        case SPDM_OPF_DEC_CONVS:
+            el = d[1] ? launch_decoder_train_convs(b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], b[8], b[9], b[10], q.d_sq, ni, s)
+                      : launch_decoder_convs(b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], ni, s);
+            break;
+        case SPDM_OPF_DEC_KINKS: el = launch_decoder_kinks(b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], b[8], ni, s); break;
+        case SPDM_OPF_DEC_LOSS: el = launch_decoder_loss(q.d_sq, ni, b[0], s); break;
+        case SPDM_OPF_DEC_BWD6: el = launch_decoder_bwd6(b[0], b[1], b[2], b[3], q.scale, ni, b[4], part, b[5], b[6], s); break;
+        case SPDM_OPF_DEC_DGRAD4: el = launch_decoder_dgrad4(b[0], b[1], b[2], ni, b[3], s); break;
+        case SPDM_OPF_DEC_COLSUM:
+            el = launch_decoder_colsum(b[0], (int)d[1], (long long)d[0], (int)(d[1] / d[2]), (int)d[2], part, b[1], s);
+            q.info[0] = decoder_colsum_slab_rows((long long)d[0]); q.info[1] = decoder_colsum_slabs((long long)d[0]);
+            break;
+        case SPDM_OPF_DEC_UNPERM_CONV: el = launch_decoder_unperm_conv(b[0], (int)d[0], (int)d[1], b[1], s); break;
+        case SPDM_OPF_DEC_UNPERM_LINEAR: el = launch_decoder_unperm_linear(b[0], b[1], s); break;
+        case SPDM_OPF_ADD: el = launch_add(b[0], (size_t)d[0], b[1], s); break;
+        case SPDM_OPF_FRAME_WGRAD:
+            el = launch_wgrad(b[0], wCo, b[1], wCi, (long long)d[0], 1, 1, 1, wCo, wCi, 0, part, budget, b[2], s);
+            q.info[0] = nch; q.info[1] = wrows; q.info[2] = wCo; q.info[3] = wCi;
+            break;
+    }
+    const hipError_t es = hipDeviceSynchronize();
+    if (el != hipSuccess) return fail(SPDM_ERR_HIP, "op_frame: op %d: launch failed: %s; device: %s", q.op, hipGetErrorString(el), hipGetErrorString(es));
+    if (es != hipSuccess) return fail(SPDM_ERR_HIP, "op_frame: op %d: %s", q.op, hipGetErrorString(es));
+    return SPDM_OK;
+}

@@ -120,3 +120,45 @@ def autoencoder_grads(enc_sd, dec_sd, frames, dtype=torch.float64, chunk=64):
             part.backward()
         loss += float(part.detach())
     return loss, {k: p.grad.detach() for k, p in pe.items()}, {k: p.grad.detach() for k, p in pd.items()}
+
+
+# ---- trained-scale data: saturated sigmoid, 8-bit frames with flat patches, dead channels ------------------
+TRAINED_CASES = (("trained40", 6), ("trained40", 40), ("trained120", 6), ("trained120", 40))
+
+
+def case_id(v):
+    """pytest id of an ``n`` parameter that is a frame count (today's data) or a (flavour, n) pair of TRAINED_CASES"""
+    return str(v) if isinstance(v, int) else f"{v[0]}-{v[1]}"
+
+
+def trained_decoder_state_dict(seed, k6):
+    """``make_decoder_state_dict`` with the last layer scaled by ``k6``: recon from 1e-3 to 0.9996 at 40, from 1e-9 to exactly
+    1.0f at 120, where torch's default initialisation keeps it in [0.457, 0.549]."""
+    sd = make_decoder_state_dict(seed)
+    sd["6.weight"] = sd["6.weight"] * k6
+    sd["6.bias"] = sd["6.bias"] * k6
+    return sd
+
+
+def trained_encoder_state_dict(enc_sd):
+    """The three convolutions scaled by 3 (latents of std 0.7 instead of 0.026) and a few channels of every ReLU layer dead
+    (bias -50: whole columns exactly zero)."""
+    sd = {k: v.clone() for k, v in enc_sd.items()}
+    for k in ("0.weight", "2.weight", "4.weight"):
+        sd[k] = sd[k] * 3
+    sd["0.bias"][[2, 9]] = -50.0
+    sd["2.bias"][[3, 17, 31]] = -50.0
+    sd["4.bias"][[4, 40, 63]] = -50.0
+    return sd
+
+
+def trained_frames(n, seed):
+    """8-bit frames k / 255 with a black band that touches the padded border (rows 0-19), a white 20 x 20 patch and a flat grey
+    patch."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.round(torch.rand(n, 3, 96, 96, generator=g) * 255) / 255
+    x[:, :, 0:20, :] = 0.0
+    x[:, :, 40:60, 30:50] = 1.0
+    x[:, :, 70:90, 60:90] = 128.0 / 255
+    return x
+

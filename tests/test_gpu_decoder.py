@@ -15,6 +15,11 @@ Measured (MI355X), worst ratio per tensor.  Decoder alone over n = 1, 6, 40, 130
 <= 4.0e-6, decoder tensors <= 1.1e-6, loss <= 2.1e-8.  n = 2100 against its 128-frame pieces: tensors <= 4.2e-7,
 grad_latent 2.4e-6, loss 2.3e-8.  After update_weights <= 2.8e-7 (grad_latent 1.8e-6).  Adam run: 0, 0, 8.8e-8, 8.8e-8, 0
 relative over its five steps.
+
+The (flavour, n) cases run the same two gradient tests on trained-scale data (autoencoder_ref.TRAINED_CASES):
+layer 6 scaled by 40 / 120 so that the sigmoid saturates, the encoder's convolutions by 3 with dead channels, 8-bit frames with a
+black band on the padded border and flat patches.  Measured: decoder tensors <= 7.8e-7, grad_latent 1.9e-6, loss 4.5e-8;
+through the facade all 16 tensors <= 1.3e-6, loss 4.6e-8.
 """
 import ctypes
 import functools
@@ -22,8 +27,8 @@ import functools
 import pytest
 import torch
 
-from autoencoder_ref import (DEC_KEYS, autoencoder_grads, decoder_forward_any, decoder_grads, latents,
-                             make_decoder_state_dict)
+from autoencoder_ref import (DEC_KEYS, TRAINED_CASES, autoencoder_grads, case_id, decoder_forward_any, decoder_grads, latents,
+                             make_decoder_state_dict, trained_decoder_state_dict, trained_encoder_state_dict, trained_frames)
 from encoder_train_ref import KEYS as ENC_KEYS
 from encoder_train_ref import encoder_forward_any, images
 from oracle.encoder_ref import make_encoder_state_dict
@@ -48,16 +53,23 @@ def _checkpoint(enc_sd, dec_sd):
     return sd
 
 
-@functools.lru_cache(maxsize=None)
-def _inputs(n):
-    return latents(n, 10 + n), images(n, 200 + n)
+def _dec_sd(case):
+    """torch's default initialisation for a frame count; layer 6 scaled by 40 / 120 for a (flavour, n) pair of TRAINED_CASES"""
+    return make_decoder_state_dict(DEC_SEED) if isinstance(case, int) else trained_decoder_state_dict(DEC_SEED, int(case[0][7:]))
 
 
 @functools.lru_cache(maxsize=None)
-def _ref64(n):
-    """float64 reconstruction, loss, gradients and grad_latent of the decoder on _inputs(n): computed once, read only."""
-    z, tgt = _inputs(n)
-    sd = make_decoder_state_dict(DEC_SEED)
+def _inputs(case):
+    if isinstance(case, int):
+        return latents(case, 10 + case), images(case, 200 + case)
+    return latents(case[1], 10 + case[1]), trained_frames(case[1], 200 + case[1])
+
+
+@functools.lru_cache(maxsize=None)
+def _ref64(case):
+    """float64 reconstruction, loss, gradients and grad_latent of the decoder on _inputs(case): computed once, read only."""
+    z, tgt = _inputs(case)
+    sd = _dec_sd(case)
     recon = decoder_forward_any({k: v.double() for k, v in sd.items()}, z.double())
     loss, grads, gl = decoder_grads(sd, z, tgt)
     return recon, loss, grads, gl
@@ -123,9 +135,11 @@ def test_train_loss_recon_equals_forward_bit_for_bit(n):
         dec.close()
 
 
-@pytest.mark.parametrize("n", [1, 6, 40, 130])
+@pytest.mark.parametrize("n", [1, 6, 40, 130, *TRAINED_CASES], ids=case_id)
 def test_decoder_gradients_match_float64_autograd(n):
-    sd, dec = _decoder()
+    """The (flavour, n) cases: layer 6 scaled by 40 / 120 (a saturated sigmoid) against 8-bit frames with flat patches."""
+    from state_policy_diffusionmodel_amd.autoencoder import Decoder
+    dec = Decoder(_dec_sd(n))
     try:
         z, tgt = _inputs(n)
         recon64, loss64, g64, gl64 = _ref64(n)
@@ -141,21 +155,25 @@ def test_decoder_gradients_match_float64_autograd(n):
         assert int(sum(v.numel() for v in grads.values())) == flat.numel()
         worst = _ratios(grads, g64, DEC_KEYS)
         worst.update(_ratios({"grad_latent": gl}, {"grad_latent": gl64}, ["grad_latent"]))
-        print(f"\nDECODER LOSS n={n}: rel {rel:.2e}")
-        _assert_within(f"n={n}", worst)
+        print(f"\nDECODER LOSS n={case_id(n)}: rel {rel:.2e}")
+        _assert_within(f"n={case_id(n)}", worst)
         assert rel <= LOSS_REL
     finally:
         dec.close()
 
 
-@pytest.mark.parametrize("n", [1, 6, 40, 130])
+@pytest.mark.parametrize("n", [1, 6, 40, 130, *TRAINED_CASES], ids=case_id)
 def test_autoencoder_step_matches_float64_autograd(n):
-    """The whole reconstruction step through the facade: all 16 tensors."""
+    """The whole reconstruction step through the facade: all 16 tensors.  The (flavour, n) cases: encoder convolutions scaled by
+    3 with dead channels, layer 6 scaled by 40 / 120, 8-bit frames with a black band on the border and flat patches."""
     from state_policy_diffusionmodel_amd.autoencoder import autoencoder
-    enc_sd, dec_sd = make_encoder_state_dict(ENC_SEED), make_decoder_state_dict(DEC_SEED)
+    enc_sd, dec_sd = make_encoder_state_dict(ENC_SEED), _dec_sd(n)
+    tag = case_id(n)
+    if not isinstance(n, int):
+        enc_sd, n = trained_encoder_state_dict(enc_sd), n[1]
     ae = autoencoder(state_dict=_checkpoint(enc_sd, dec_sd))
     try:
-        x = images(n, 100 + n)
+        x = images(n, 100 + n) if tag == str(n) else trained_frames(n, 100 + n)
         loss64, e64, d64 = autoencoder_grads(enc_sd, dec_sd, x)
         loss = ae.training_step(x.cuda(), backward=True)
         torch.cuda.synchronize()
@@ -169,8 +187,8 @@ def test_autoencoder_step_matches_float64_autograd(n):
             assert all(lo <= g.data_ptr() < hi for g in grads.values())           # views of the flat gradients
         worst = _ratios(eg, e64, ENC_KEYS, "enc/")
         worst.update(_ratios(dg, d64, DEC_KEYS, "dec/"))
-        print(f"\nAUTOENCODER LOSS n={n}: rel {rel:.2e}")
-        _assert_within(f"autoencoder n={n}", worst)
+        print(f"\nAUTOENCODER LOSS n={tag}: rel {rel:.2e}")
+        _assert_within(f"autoencoder n={tag}", worst)
         assert rel <= LOSS_REL
         # validation_step / forward: the same loss without a backward pass, reconstructions in [0, 1]
         assert abs(float(ae.validation_step(x.cuda())) - float(loss)) <= LOSS_REL * float(loss)
