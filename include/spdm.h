@@ -248,7 +248,8 @@ int  spdm_train_loss_grad_dt(spdm_handle* h, int32_t B, const float* d_x_noisy, 
  *
  * Randomness: Philox4x32-10, key = (seed low word, seed high word), counter = (q, sample, step, purpose) with
  * sample = (uint32)(sample_offset + b) the GLOBAL sample index -- a shard of a batch draws what the whole batch would -- and
- * `step` the caller's training-step counter.  purpose 0 is spdm_sample's stream and is never drawn here.
+ * `step` the caller's training-step counter.  purpose 0 is spdm_sample's stream and is never drawn here (4-7: spdm_obs_noise, 8:
+ * spdm_policy_warm_start).
  *   purpose 2, q = 0:            t_b = (int32)(((uint64)w0 * T) >> 32), in [0, T);
  *   purpose 1, q = e / 4:        the four words give the normals of elements 4q .. 4q+3 of the sample's (H, D) window (in-painted
  *                                rows included) by Box-Muller, (w0, w1) -> r cos, r sin and (w2, w3) likewise,
@@ -446,7 +447,7 @@ size_t spdm_eval_reduce_workspace_doubles(int64_t N, int32_t C);
  * dst_stride = obs_h 2).  d_dst == d_src is allowed; any other overlap of the two is not.
  *   u: Philox4x32-10, key (seed lo, seed hi), counter (e / 4, row_offset + row, draw, 4 + i); element e takes word w = e % 4
  *     of its quad and u = (float)(w >> 8) 2^-24, exact and in [0, 1): the values torch.rand produces.  Purposes 0 .. 3 belong
- *     to the sampler and to spdm_train_forward_process.  The value of an element depends on (seed, draw, i, row_offset + row,
+ *     to the sampler and to spdm_train_forward_process, 8 to spdm_policy_warm_start.  The value of an element depends on (seed, draw, i, row_offset + row,
  *     e) alone: not on alignment, strides, n_rows or the other tensors, so rows [r0, r1) with row_offset + r0 equal the rows
  *     of the whole.
  *   Where d_src, d_dst are 16-byte aligned and inner and both strides are multiples of 4 the tensor moves in 16-byte
@@ -580,6 +581,72 @@ typedef struct {
     double* d_actions;
 } spdm_policy_unnormalize_args;
 int  spdm_policy_unnormalize(int32_t device, const spdm_policy_unnormalize_args* a, void* stream);
+
+/* spdm_policy_warm_start builds the starting iterate of a warm-started plan: the previous plan, shifted by the
+ * time that has passed, re-centred on the new window and noised to an intermediate level of the schedule -- the forward process
+ * of training (spdm_train_forward_process) applied to a guess instead of data.  spdm_sample_begin with this iterate as d_xT
+ * and spdm_sample_run(h, i0, n_steps) then run only the last n_steps - i0 denoise steps.  Stateless, ONE launch on `stream`
+ * (NULL: the null stream, and the call synchronises), no atomics, no host synchronisation otherwise.
+ *   E, H, D, inp_h: environments, rows and columns of a plan, in-painted rows (0 <= inp_h <= H); D >= 2, columns 0 and 1 are
+ *     the position;  step_size >= 1: pushes between two rows of a plan;
+ *   delta >= 0: pushes (environment steps) between the previous plan and this one;
+ *   sa, sb: sqrt(abar_t) and sqrt(1 - abar_t) of the timestep t the first executed loop iteration i0 denoises from: row i0,
+ *     columns 1 and 0, of the [n][6] coefficient table of spdm_set_schedule_tables;
+ *   seed, env_offset, draw: the noise stream (below); env_offset is the GLOBAL index of environment 0, so that a shard of the
+ *     environments draws what the whole would; draw is the caller's plan counter;
+ *   d_prev_x0 (E,H,D) float32: the previous plan as the sampler returned it;
+ *   d_prev_translation, d_translation (E,2) float32: the translations of the previous and of the new window, as
+ *     spdm_policy_window emits them;
+ *   d_inpaint (E,inp_h,D) float32, NULL exactly when inp_h == 0;
+ *   d_noise_in (E,H,D) float32: NULL = the noise is drawn; non-NULL = the caller's values enter the arithmetic instead
+ *     (spdm_train_forward_process's convention);
+ *   d_x (E,H,D) float32, required: the starting iterate;  d_guess (E,H,D), optional: the shifted, re-centred plan before
+ *     noising;  d_noise (E,H,D), optional: the noise used (may be d_noise_in itself, which is then left as it is).  No output
+ *     may overlap d_prev_x0.
+ * Time alignment (run_predictions.plan_rows): a plan made after n pushes has its row r at push index n + (r - inp_h) step_size
+ * -- row inp_h - 1 is the newest window entry, way-point j lies 1 + j step_size pushes after the latest observation -- so a plan
+ * made delta pushes later wants, at its row r, the old plan at row r + delta / step_size.
+ * Per element (e, r, c), every float32 operation rounded on its own (no FMA); q = delta / step_size, f = delta % step_size in
+ * integers:
+ *   1. r0 = min(r + q, H - 1), r1 = min(r + q + (f > 0), H - 1);  a = prev[e, r0, c], b = prev[e, r1, c]: past the end of the
+ *      old plan its last row is held;
+ *   2. f == 0: g = a, no arithmetic.  Otherwise w = (float)f / (float)step_size, one correctly rounded division, and
+ *      g = a + w (b - a): subtract, multiply, add, three roundings (also where r0 == r1);
+ *   3. c < 2 only: g <- (((2.0f g) + T0[e,c]) - T1[e,c]) / 2.0f with T0 = d_prev_translation, T1 = d_translation --
+ *      normalize_position centres a window on its own first entry, so the two plans live in different frames.  The scalings by
+ *      2 are exact, the sum and the difference round;
+ *   4. z = d_noise_in[e,r,c] if given; otherwise Philox4x32-10 with key (seed low word, seed high word) and counter
+ *      (k, (uint32)(env_offset + e), draw, 8), k = (r D + c) / 4: the four words give the normals of elements 4k .. 4k+3 of the
+ *      environment's (H, D) window by Box-Muller exactly as purpose 1 of spdm_train_forward_process does.  Purposes: 0 the
+ *      sampler, 1-3 spdm_train_forward_process, 4-7 spdm_obs_noise, 8 this entry;
+ *   5. x = (sa g) + (sb z): three roundings, torch's add_noise;
+ *   6. rows r < inp_h of d_x are d_inpaint's, exactly (add_constraints); d_guess and d_noise are not in-painted.
+ * Deterministic: two calls with the same arguments give the same bits.
+ * SPDM_ERR_INVALID, before the GPU is touched: NULL args; a NULL d_prev_x0, d_prev_translation, d_translation or d_x; E, H or
+ * step_size < 1; D < 2; inp_h outside [0, H]; d_inpaint NULL with inp_h > 0 (or set with inp_h == 0); delta < 0; E x H x D
+ * beyond 31 bits; sa or sb not finite. */
+typedef struct {
+    int32_t E;
+    int32_t H;
+    int32_t D;
+    int32_t inp_h;
+    int32_t step_size;
+    uint32_t draw;
+    int64_t delta;
+    uint64_t seed;
+    uint64_t env_offset;
+    float sa;
+    float sb;
+    const float* d_prev_x0;
+    const float* d_prev_translation;
+    const float* d_translation;
+    const float* d_inpaint;
+    const float* d_noise_in;
+    float* d_x;
+    float* d_guess;
+    float* d_noise;
+} spdm_policy_warm_start_args;
+int  spdm_policy_warm_start(int32_t device, const spdm_policy_warm_start_args* a, void* stream);
 
 /* The per-sample terms of a validation pass's loss in ONE launch (train_metrics.hip).  Replaces: nn.MSELoss
  * of the reference's validation_step (models/diffusion_ddpm.py:175-214, :49) as Lightning averages it over an epoch, weighted by

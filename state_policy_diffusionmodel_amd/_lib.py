@@ -160,6 +160,14 @@ class SpdmPolicyUnnormalizeArgs(ctypes.Structure):
                 [("d_waypoints", c_void_p), ("d_actions", c_void_p)])
 
 
+class SpdmPolicyWarmStartArgs(ctypes.Structure):
+    """spdm_policy_warm_start_args (include/spdm.h)."""
+    _fields_ = ([(n, c_int32) for n in ("E", "H", "D", "inp_h", "step_size")] + [("draw", ctypes.c_uint32)] +
+                [("delta", c_int64), ("seed", c_uint64), ("env_offset", c_uint64), ("sa", c_float), ("sb", c_float)] +
+                [(n, c_void_p) for n in ("d_prev_x0", "d_prev_translation", "d_translation", "d_inpaint", "d_noise_in", "d_x", "d_guess",
+                                         "d_noise")])
+
+
 class SpdmLossTermsArgs(ctypes.Structure):
     """spdm_loss_terms_args (include/spdm.h)."""
     _fields_ = ([(n, c_int32) for n in ("B", "H", "D", "reserved")] + [("d_eps", c_void_p), ("d_noise", c_void_p)] +
@@ -202,6 +210,7 @@ SYMBOLS = {
     "spdm_policy_push": (c_int32, [c_int32, POINTER(SpdmPolicyPushArgs), c_void_p]),
     "spdm_policy_window": (c_int32, [c_int32, POINTER(SpdmPolicyWindowArgs), c_void_p]),
     "spdm_policy_unnormalize": (c_int32, [c_int32, POINTER(SpdmPolicyUnnormalizeArgs), c_void_p]),
+    "spdm_policy_warm_start": (c_int32, [c_int32, POINTER(SpdmPolicyWarmStartArgs), c_void_p]),
     "spdm_loss_terms": (c_int32, [c_int32, POINTER(SpdmLossTermsArgs), c_void_p]),
     "spdm_train_set_time_scale": (c_int32, [c_void_p, c_void_p, c_int32]),
     "spdm_sample_begin": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,

@@ -545,6 +545,25 @@ struct PolicyUnnormalizeArgs {
 // one launch of ceil(E (H - inp_h) / 256) workgroups
 hipError_t launch_policy_unnormalize(const PolicyUnnormalizeArgs& a, hipStream_t s);
 
+// the starting iterate of a warm-started plan (spdm_policy_warm_start)
+struct PolicyWarmStartArgs {
+    int E, H, D, inp_h;
+    int q, f, step_size;               // delta / step_size (clamped to H: beyond that every row is the held last one), delta % step_size
+    float sa, sb;                      // sqrt(abar_t), sqrt(1 - abar_t) of the first timestep the loop denoises from
+    unsigned long long seed, env_offset;
+    unsigned draw;
+    const float* prev_x0;              // (E, H, D)
+    const float* prev_translation;     // (E, 2)
+    const float* translation;          // (E, 2)
+    const float* inpaint;              // (E, inp_h, D); null iff inp_h == 0
+    const float* noise_in;             // (E, H, D) or null: drawn
+    float* x;                          // (E, H, D)
+    float* guess;                      // (E, H, D) or null
+    float* noise;                      // (E, H, D) or null
+};
+// one launch of ceil(E ceil(H D / 4) / 256) workgroups
+hipError_t launch_policy_warm_start(const PolicyWarmStartArgs& a, hipStream_t s);
+
 // ---- per-sample terms of a validation pass's loss (train_metrics.hip; spdm_loss_terms) -------------------
 constexpr int LOSS_WAVES = 4;          // samples (one wave each) per workgroup
 struct LossTermsArgs {

@@ -1,6 +1,6 @@
 // policy.hip -- the closed-loop caller's host side on the device: the observation history of E environments as rings in HBM,
 // the conditioning batch built from them, and the plan back in the dataset's units (spdm_policy_push, spdm_policy_window,
-// spdm_policy_unnormalize).
+// spdm_policy_unnormalize), and the starting iterate of a warm-started plan (spdm_policy_warm_start; 8.18).
 //
 // Replaces: the four deque(maxlen = obs_horizon step_size) of run_predictions.py:112-124 and their appends (:145-148),
 // prepare_diffusion_batch (:30-60: list(deque)[::s], torch.tensor(..., float32) over every frame of the window, / 255, permute,
@@ -14,6 +14,9 @@
 // Window: ONE launch.  Workgroups [0, E obs_h x 3) each turn a third of one ring frame into planar CHW fp32 (frame_tiles.h,
 // shared with dataset.hip); the workgroups after them normalise the low-dimensional rows, one thread per (environment, entry).
 // Unnormalise: ONE launch, one thread per (environment, predicted step), with the U and A of spdm_eval_errors (unnormalize.h).
+// Warm start: ONE launch, one thread per four consecutive elements of an environment's (H, D) window: the previous plan shifted
+// by the time that has passed, re-centred on the new window's first entry and noised to the level the loop's suffix starts
+// from, with the Philox / Box-Muller stream of train_noise.hip (philox_normal.h) under purpose 8.
 //
 // Arithmetic of the window: that of utils/data_utils.py:18-33 on CPU float32 torch tensors (include/spdm.h), written with the
 // _rn intrinsics so that no two operations are ever contracted into an FMA.
@@ -24,6 +27,7 @@
 
 #include "frame_tiles.h"
 #include "kernels.h"
+#include "philox_normal.h"
 #include "unnormalize.h"
 
 namespace spdm {
@@ -146,7 +150,65 @@ __global__ __launch_bounds__(THREADS) void policy_unnormalize_kernel(const Polic
     }
 }
 
+// One thread per Philox quad: four consecutive elements of one environment's (H, D) window (the last quad of a window may be
+// short).  No LDS, no barrier.  Rows: r + q + 1 <= 2 (H - 1) + 1 fits an int (q <= H - 1 and H D < 2^31 with D >= 2: the launch).
+__global__ __launch_bounds__(THREADS) void policy_warm_start_kernel(const PolicyWarmStartArgs a) {
+// every float operation written in this body is rounded on its own.  The _rn intrinsics do not promise that here: they are
+// inline functions of plain operators, which the compiler contracts after inlining (it fused a + w (b - a) into an FMA)
+#pragma clang fp contract(off)
+    const int HD = a.H * a.D, nq = (HD >> 2) + ((HD & 3) != 0);                // HD < 2^31: the launch
+    const long long g = (long long)blockIdx.x * THREADS + threadIdx.x;        // (environment, quad)
+    if (g >= (long long)a.E * nq) return;
+    const int e = (int)(g / nq), i = (int)(g - (long long)e * nq);             // e < E, i < nq
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (a.noise_in == nullptr) {
+        unsigned w[4];
+        philox4x32_10((unsigned)i, (unsigned)(a.env_offset + (unsigned long long)e), a.draw, 8u, (unsigned)a.seed,
+                      (unsigned)(a.seed >> 32), w);
+        box_muller(w[0], w[1], z[0], z[1]);
+        box_muller(w[2], w[3], z[2], z[3]);
+    }
+    const float w01 = a.f > 0 ? (float)a.f / (float)a.step_size : 0.0f;        // correctly rounded: hipcc's default for float division
+    const int inp_e = a.inp_h * a.D;                     // elements [0, inp_e) of a window are the in-painted rows
+    const size_t base = (size_t)e * HD;
+    const float* prev = a.prev_x0 + base;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const unsigned el = ((unsigned)i << 2) + k;      // <= HD + 2: unsigned, so that a window of 2^31 - 1 elements cannot wrap
+        if (el >= (unsigned)HD) break;
+        const int r = (int)(el / (unsigned)a.D), c = (int)(el - (unsigned)r * a.D);      // r < H, c < D
+        const int r0 = min(r + a.q, a.H - 1), r1 = min(r + a.q + (a.f > 0 ? 1 : 0), a.H - 1);
+        float gs = prev[(size_t)r0 * a.D + c];
+        if (a.f > 0) {                                   // uniform
+            const float d = prev[(size_t)r1 * a.D + c] - gs;
+            const float wd = w01 * d;
+            gs = gs + wd;
+        }
+        if (c < 2) {                                     // the old plan's frame into the new one's: the scalings by 2 are exact
+            const float sn = 2.0f * gs + a.prev_translation[(size_t)e * 2 + c];
+            gs = (sn - a.translation[(size_t)e * 2 + c]) / 2.0f;
+        }
+        const size_t idx = base + el;
+        const float zz = a.noise_in != nullptr ? a.noise_in[idx] : z[k];
+        if (a.guess != nullptr) a.guess[idx] = gs;
+        if (a.noise != nullptr && a.noise != a.noise_in) a.noise[idx] = zz;
+        const float xa = a.sa * gs, xb = a.sb * zz;
+        float x = xa + xb;
+        if (el < (unsigned)inp_e) x = a.inpaint[(size_t)e * inp_e + el];       // add_constraints
+        a.x[idx] = x;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_policy_warm_start(const PolicyWarmStartArgs& a, hipStream_t s) {
+    const long long HD = (long long)a.H * a.D, n = (long long)a.E * ((HD + 3) / 4);
+    if (a.E < 1 || a.H < 1 || a.D < 2 || a.inp_h < 0 || a.inp_h > a.H || a.step_size < 1 || a.q < 0 || a.q > a.H - 1 || a.f < 0 ||
+        a.f >= a.step_size || (long long)a.E * HD > 0x7fffffffLL)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(policy_warm_start_kernel, dim3((unsigned)((n + THREADS - 1) / THREADS)), dim3(THREADS), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_policy_push(PolicyPushArgs a, hipStream_t s) {
     if (a.E < 1 || a.L < 1 || a.slot < 0 || a.slot >= a.L || (a.img_dtype != 0 && a.img_dtype != 1)) return hipErrorInvalidValue;

@@ -3065,6 +3065,35 @@ extern "C" int spdm_policy_unnormalize(int32_t device, const spdm_policy_unnorma
     return SPDM_OK;
 }
 
+// The starting iterate of a warm-started plan in one launch (include/spdm.h, policy.hip).  Stateless.
+extern "C" int spdm_policy_warm_start(int32_t device, const spdm_policy_warm_start_args* a, void* stream) {
+    if (!a) return fail(SPDM_ERR_INVALID, "policy_warm_start: null argument");
+    if (a->E < 1 || a->H < 1 || a->step_size < 1)
+        return fail(SPDM_ERR_INVALID, "policy_warm_start: E, H, step_size = %d, %d, %d must all be >= 1", a->E, a->H, a->step_size);
+    if (a->D < 2) return fail(SPDM_ERR_INVALID, "policy_warm_start: D = %d holds no position (2 columns)", a->D);
+    if (a->inp_h < 0 || a->inp_h > a->H) return fail(SPDM_ERR_INVALID, "policy_warm_start: inp_h = %d outside [0, H = %d]", a->inp_h, a->H);
+    if ((a->d_inpaint != nullptr) != (a->inp_h > 0))
+        return fail(SPDM_ERR_INVALID, "policy_warm_start: d_inpaint must be NULL exactly when inp_h == 0 (inp_h = %d)", a->inp_h);
+    if (a->delta < 0) return fail(SPDM_ERR_INVALID, "policy_warm_start: delta = %lld is negative", (long long)a->delta);
+    if ((long long)a->H * a->D > 0x7fffffffLL || (long long)a->E * a->H * a->D > 0x7fffffffLL)
+        return fail(SPDM_ERR_INVALID, "policy_warm_start: E x H x D does not fit 31 bits");
+    if (!(fabsf(a->sa) <= 3.402823466e+38f) || !(fabsf(a->sb) <= 3.402823466e+38f))
+        return fail(SPDM_ERR_INVALID, "policy_warm_start: sa, sb = %g, %g must be finite", (double)a->sa, (double)a->sb);
+    if (!a->d_prev_x0 || !a->d_prev_translation || !a->d_translation || !a->d_x) return fail(SPDM_ERR_INVALID, "policy_warm_start: null pointer");
+    PolicyWarmStartArgs k = {};
+    k.E = a->E; k.H = a->H; k.D = a->D; k.inp_h = a->inp_h; k.step_size = a->step_size;
+    const long long q = a->delta / a->step_size;         // rows the old plan is ahead; from H - 1 on every row is the held last one
+    k.q = (int)(q < a->H - 1 ? q : a->H - 1);
+    k.f = (int)(a->delta % a->step_size);
+    k.sa = a->sa; k.sb = a->sb; k.seed = a->seed; k.env_offset = a->env_offset; k.draw = a->draw;
+    k.prev_x0 = a->d_prev_x0; k.prev_translation = a->d_prev_translation; k.translation = a->d_translation;
+    k.inpaint = a->d_inpaint; k.noise_in = a->d_noise_in; k.x = a->d_x; k.guess = a->d_guess; k.noise = a->d_noise;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(launch_policy_warm_start(k, (hipStream_t)stream));
+    if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));
+    return SPDM_OK;
+}
+
 // The per-sample terms of a validation pass's loss in one launch (include/spdm.h, train_metrics.hip).  Stateless.
 extern "C" int spdm_loss_terms(int32_t device, const spdm_loss_terms_args* a, void* stream) {
     if (!a) return fail(SPDM_ERR_INVALID, "loss_terms: null argument");

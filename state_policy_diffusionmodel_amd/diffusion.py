@@ -309,7 +309,7 @@ class Diffusion_DDPM:
     def sample(self, batch: Dict[str, torch.Tensor], option: Optional[str] = None, *,
                x_T: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                batched: bool = False, seed: Optional[int] = None, sample_offset: int = 0, every: int = 1,
-               sharded: Optional[bool] = None, group=None, shard_exact: bool = False):
+               sharded: Optional[bool] = None, group=None, shard_exact: bool = False, start_step: int = 0):
         """``option``: None -> x_0 (B,1,H,D); 'sample_history' -> list of the N+1 iterates (the reference's form);
         'sample_history_stream' -> a generator of ``(i, x_i)`` host tensors handed out while the loop runs
         (``every``: stride in steps; SpdmEngine.sample_stream).
@@ -326,11 +326,23 @@ class Diffusion_DDPM:
         initialised.  ``x_T`` and ``seed`` left at None are drawn on rank 0 and broadcast.  A shard's trajectories agree
         with the single-GPU run to fp32 rounding (<= 1e-5 over a loop: a small shard selects other kernels for the coarse
         levels); ``shard_exact=True`` pins every rank's kernel selection to that of the GLOBAL batch instead -- bit-identical
-        to the single-GPU run, at the price of small-batch kernels not being used on small shards."""
+        to the single-GPU run, at the price of small-batch kernels not being used on small shards.
+
+        ``start_step = i0 > 0`` runs a suffix of the loop: ``x_T``, then required, is the iterate the loop
+        has after ``i0`` of its ``noise_steps`` iterations, and only iterations ``[i0, noise_steps)`` run -- bit for bit the
+        tail of the whole loop from that iterate.  Not available with a history option or ``sharded=True``."""
         from .distributed import ShardedSampler, shard_bounds, world_and_rank
+        if isinstance(start_step, bool) or not isinstance(start_step, (int, np.integer)) or not 0 <= start_step < int(self.noise_steps):
+            raise ValueError(f"start_step = {start_step!r} must be an integer in [0, noise_steps = {self.noise_steps})")
+        start_step = int(start_step)
+        if start_step and x_T is None:
+            raise ValueError("start_step > 0 needs x_T: the iterate the loop has after start_step steps")
         world, rank = world_and_rank(group)
         if sharded is None:
             sharded = batched and world > 1
+        if start_step and (option in ("sample_history", "sample_history_stream") or sharded):
+            raise ValueError("start_step > 0 runs a suffix of the loop on this process: not available with option='sample_history', "
+                             "'sample_history_stream' or sharded=True")
         if sharded and not batched:
             raise ValueError("sharded=True needs batched=True (the reference's B = 1 form has nothing to shard)")
         if sharded and option == "sample_history_stream":
@@ -368,7 +380,8 @@ class Diffusion_DDPM:
                 raise ValueError("sample_offset is the shard's own bookkeeping when sharded=True")
             res = ShardedSampler(eng, group).sample(obs_cond, x_T, noise=noise, inpaint=ip, seed=seed, history=want_hist)
         else:
-            res = eng.sample(obs_cond, x_T, noise=noise, inpaint=ip, seed=seed, sample_offset=sample_offset, history=want_hist)
+            extra = {"start_step": start_step} if start_step else {}              # 0: exactly the call without the keyword
+            res = eng.sample(obs_cond, x_T, noise=noise, inpaint=ip, seed=seed, sample_offset=sample_offset, history=want_hist, **extra)
         if want_hist:
             _, hist = res
             return [hist[i] for i in range(hist.shape[0])]                    # list of N+1 (B,1,H,D), :256-265

@@ -380,12 +380,17 @@ class SpdmEngine:
         return out
 
     def sample(self, cond, x_T, noise=None, inpaint=None, seed: int = 0, sample_offset: int = 0,
-               history: bool = False, check_finite: bool = True):
+               history: bool = False, check_finite: bool = True, start_step: int = 0):
         """x_0 (B,1,H,D); with history=True also the (n_steps+1,B,1,H,D) stack x_T..x_0.  Raises if an iterate left
         the finite range (the split-precision contractions overflow beyond |activation| 4094: re-create the engine
-        with exact_fp32=True for such a model)."""
+        with exact_fp32=True for such a model).  ``start_step = i0``: ``x_T`` is the iterate after ``i0`` steps and only
+        steps ``[i0, n_steps)`` run; there is no history of such a run."""
+        if not 0 <= start_step <= self.n_steps:
+            raise ValueError(f"start_step = {start_step} outside [0, {self.n_steps}]")
+        if start_step and history:
+            raise ValueError("history=True needs the whole loop (start_step = 0)")
         hist = self.sample_begin(cond, x_T, noise, inpaint, seed, sample_offset, history)
-        self.sample_run(0, self.n_steps)
+        self.sample_run(start_step, self.n_steps)
         out = self.sample_result()
         if check_finite and self.nonfinite():
             raise FloatingPointError("non-finite iterate in the sampling loop" + (

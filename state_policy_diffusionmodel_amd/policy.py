@@ -7,6 +7,8 @@ step, float32 normalisation on the CPU, a host-to-device copy of the whole windo
 (``spdm_policy_push``: one launch per step), builds the conditioning batch in one launch (``spdm_policy_window``), samples
 with the model's engine and returns way-points and actions in the dataset's units from one more launch
 (``spdm_policy_unnormalize``).  E = 1 is the reference's loop; a larger E drives that many environments in lockstep.
+``plan(warm_start=K)`` replans from the previous plan instead of from noise: one more launch
+(``spdm_policy_warm_start``) shifts, re-centres and re-noises it, and only the last K denoise steps run.
 
 There is no CPU fallback: every method but the constructor's checks needs the GPU."""
 from __future__ import annotations
@@ -27,10 +29,13 @@ FRAME_SHAPE = (96, 96, 3)
 class Plan:
     """Device tensors: ``waypoints`` (E, pred_horizon, 2) float64 positions in the dataset's units, ``actions``
     (E, pred_horizon, 3) float64 or None (a model whose prediction_dim holds no action), ``x_0`` (E, 1, H, D) float32 as the
-    sampler returned it."""
+    sampler returned it.  ``steps``: denoise iterations ``plan()`` ran for it (0: not made by ``plan()``); ``warm``: whether
+    it started from the previous plan."""
     waypoints: torch.Tensor
     actions: Optional[torch.Tensor]
     x_0: torch.Tensor
+    steps: int = 0
+    warm: bool = False
 
 
 def _channel_stats(stats: dict, key: str, n: int):
@@ -80,6 +85,13 @@ class ClosedLoopPolicy:
         self._fill = torch.ones(E, dtype=torch.int32, device=dev)
         self._fill_set = True                                                  # some entry of _fill is non-zero
         self.pushes = 0                                                        # n: observations taken so far
+        # the previous plan, for plan(warm_start=K): x_0 and translation stay on the device
+        self._prev_x0: Optional[torch.Tensor] = None
+        self._prev_translation: Optional[torch.Tensor] = None
+        self._prev_pushes = 0                                                  # the push count it was made at
+        self._prev_usable = False                                              # False again after any reset()
+        self.plans = 0                                                         # plan() calls so far: the warm start's `draw`
+        self._levels = (None, None, None)                                      # (scheduler object, noise_steps, its (n, 6) table)
 
     # ---- history --------------------------------------------------------------------------------------------------------------
     def reset(self, env_ids=None) -> None:
@@ -95,6 +107,7 @@ class ClosedLoopPolicy:
                 return
             self._fill[torch.from_numpy(ids.astype(np.int64)).to(self.device)] = 1
         self._fill_set = True
+        self._prev_usable = False                                              # lockstep: one loop serves all, so all plan cold
 
     def _input(self, name: str, x, shape, dtype) -> torch.Tensor:
         t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
@@ -174,12 +187,89 @@ class ClosedLoopPolicy:
         _lib.check(_lib.load().spdm_policy_unnormalize(self.device.index, ctypes.byref(a), stream), "spdm_policy_unnormalize")
         return Plan(waypoints=way, actions=act, x_0=x_0)
 
-    def plan(self, seed: Optional[int] = None, x_T: Optional[torch.Tensor] = None) -> Plan:
+    def warm_start(self, prev_x0: torch.Tensor, prev_translation: torch.Tensor, translation: torch.Tensor,
+                   inpaint: Optional[torch.Tensor], delta: int, sa: float, sb: float, seed: int, draw: int, *, env_offset: int = 0,
+                   noise: Optional[torch.Tensor] = None, return_parts: bool = False):
+        """The starting iterate (E,1,H,D) of a loop suffix from the plan ``prev_x0`` (E,1,H,D) or (E,H,D) made ``delta``
+        pushes ago: ONE launch (``spdm_policy_warm_start``, include/spdm.h) on torch's current stream.  ``inpaint``
+        (E,inp_h,D) or None when the model in-paints nothing; ``noise`` (E,H,D): the caller's instead of the drawn one.
+        ``return_parts=True``: ``(x, guess, noise)``, the shifted plan before noising and the noise used as well."""
+        x0 = prev_x0[:, 0] if prev_x0.dim() == 4 else prev_x0
+        E, H, D = x0.shape
+        inp_h = self.inpaint_horizon
+        given = [("prev_x0", x0, (E, H, D)), ("prev_translation", prev_translation, (E, 2)), ("translation", translation, (E, 2))]
+        if inp_h > 0:
+            if inpaint is None:
+                raise ValueError(f"inpaint is None with inpaint_horizon = {inp_h}")
+            given.append(("inpaint", inpaint, (E, inp_h, D)))
+        if noise is not None:
+            given.append(("noise", noise, (E, H, D)))
+        for name, t, shape in given:
+            if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError(f"{name} must be a contiguous float32 device tensor of shape {shape}, got {tuple(t.shape)} {t.dtype}")
+        x = torch.empty((E, 1, H, D), dtype=torch.float32, device=self.device)
+        guess = torch.empty((E, H, D), dtype=torch.float32, device=self.device) if return_parts else None
+        used = noise if noise is not None or not return_parts else torch.empty((E, H, D), dtype=torch.float32, device=self.device)
+        a = _lib.SpdmPolicyWarmStartArgs(E=E, H=H, D=D, inp_h=inp_h, step_size=self.step_size, draw=int(draw) & 0xFFFFFFFF,
+                                         delta=int(delta), seed=int(seed), env_offset=int(env_offset), sa=float(sa), sb=float(sb),
+                                         d_prev_x0=x0.data_ptr(), d_prev_translation=prev_translation.data_ptr(),
+                                         d_translation=translation.data_ptr(), d_inpaint=inpaint.data_ptr() if inp_h > 0 else None,
+                                         d_noise_in=noise.data_ptr() if noise is not None else None, d_x=x.data_ptr(),
+                                         d_guess=guess.data_ptr() if guess is not None else None,
+                                         d_noise=used.data_ptr() if return_parts else None)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(_lib.load().spdm_policy_warm_start(self.device.index, ctypes.byref(a), stream), "spdm_policy_warm_start")
+        return (x, guess, used) if return_parts else x
+
+    def _noise_level(self, i0: int):
+        """``(sa, sb)`` = (sqrt(abar_t), sqrt(1 - abar_t)) of the timestep loop iteration ``i0`` denoises from: row ``i0`` of the
+        table ``sample()`` installs in the engine, the same float32 values."""
+        from .diffusion import _as_spec
+        sched, N = self.model.noise_scheduler, int(self.model.noise_steps)
+        if self._levels[0] is not sched or self._levels[1] != N:
+            spec = _as_spec(sched)
+            spec.set_timesteps(N)
+            self._levels = (sched, N, np.ascontiguousarray(spec.coefficient_table(), dtype=np.float32))
+        row = self._levels[2][i0]
+        return float(row[1]), float(row[0])
+
+    def plan(self, seed: Optional[int] = None, x_T: Optional[torch.Tensor] = None, warm_start: Optional[int] = None) -> Plan:
         """``batch()``, ``model.sample(batch, batched=True, sharded=False, seed=seed, x_T=x_T)`` and one unnormalise launch.
-        Nothing is copied to the host.  ``seed`` and ``x_T`` are ``sample``'s: left at None they are drawn per call."""
+        Nothing is copied to the host.  ``seed`` and ``x_T`` are ``sample``'s: left at None they are drawn per call.
+
+        ``warm_start = K`` (1 <= K <= the model's ``noise_steps`` N; ValueError otherwise) asks for the last K iterations of
+        the loop only.  The plan is WARM when there is a previous plan, no ``reset()`` came since (the environments run in
+        lockstep, so one loop serves all) and at most ``(pred_horizon - 1) step_size`` observations did: one
+        ``spdm_policy_warm_start`` launch shifts the previous ``x_0`` by the observations since, re-centres it on the new
+        window and noises it to the level iteration N - K starts from, and ``model.sample(..., start_step=N - K)`` runs the
+        rest.  A warm plan ignores ``x_T``.  Otherwise the plan is COLD: exactly the path above, all N iterations.
+        ``Plan.steps`` and ``Plan.warm`` say which it was."""
+        if warm_start is not None:
+            N = int(self.model.noise_steps)
+            if isinstance(warm_start, bool) or not isinstance(warm_start, (int, np.integer)) or not 1 <= warm_start <= N:
+                raise ValueError(f"warm_start = {warm_start!r} must be an integer in [1, noise_steps = {N}]")
         batch = self.batch()
-        x_0 = self.model.sample(dict(batch), batched=True, sharded=False, seed=seed, x_T=x_T)
-        return self.unnormalize(x_0.contiguous(), batch["translation"])
+        N = int(self.model.noise_steps)
+        if seed is None:                                                       # sample()'s recipe, drawn here so that the warm
+            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())      # start and the loop share one seed
+        draw, delta = self.plans, self.pushes - self._prev_pushes
+        self.plans += 1
+        warm = (warm_start is not None and self._prev_usable and self._prev_x0 is not None
+                and delta <= (self.pred_horizon - 1) * self.step_size)
+        if warm:
+            i0 = N - int(warm_start)
+            sa, sb = self._noise_level(i0)
+            inp = self.model.prepare_inpaint_vectors(batch).contiguous() if self.inpaint_horizon > 0 else None
+            x_start = self.warm_start(self._prev_x0, self._prev_translation, batch["translation"], inp, delta, sa, sb, seed, draw)
+            x_0 = self.model.sample(dict(batch), batched=True, sharded=False, seed=seed, x_T=x_start, start_step=i0)
+        else:
+            x_0 = self.model.sample(dict(batch), batched=True, sharded=False, seed=seed, x_T=x_T)
+        x_0 = x_0.contiguous()
+        self._prev_x0, self._prev_translation = x_0, batch["translation"]
+        self._prev_pushes, self._prev_usable = self.pushes, True
+        out = self.unnormalize(x_0, batch["translation"])
+        out.steps, out.warm = (int(warm_start) if warm else N), warm
+        return out
 
 
 __all__ = ["ClosedLoopPolicy", "Plan"]

@@ -11,7 +11,12 @@ dataset window starting at ``t - L + 1`` predicts at step j -- and is compared w
 in float64.  Steps past the episode's end are left out and counted.
 
 The report holds per plan its row, its errors and the wall-clock seconds of ``plan()`` (synchronised), and over all plans the
-mean and population std of the error per step."""
+mean and population std of the error per step.
+
+``--warm_start K`` replans inside an episode from the previous plan with the last K denoise steps only (``plan(warm_start=K)``,
+DESIGN.md 8.18); the first plan of every episode is cold, because the policy is reset there.  Each plan then also says how many
+steps it ran and whether it was warm, and the report holds the error statistics and the mean seconds of the cold and of the warm
+plans side by side -- what a checkpoint's owner needs to choose K."""
 from __future__ import annotations
 
 import argparse
@@ -49,6 +54,8 @@ def parse_arguments(argv=None):
     p.add_argument("--ddim_steps", type=int, default=100)
     p.add_argument("--replan_every", type=int, default=50, help="plan on every n-th row of an episode (run_predictions.py:151)")
     p.add_argument("--seed", type=int, default=0, help="plan i samples with seed + i and its x_T from a generator seeded alike")
+    p.add_argument("--warm_start", type=int, default=None, metavar="K",
+                   help="replan inside an episode from the previous plan, running the last K denoise steps only (default: off)")
     p.add_argument("--out", type=str, default=None, help="report.json")
     return p.parse_args(argv)
 
@@ -57,6 +64,8 @@ def main(argv=None) -> dict:
     args = parse_arguments(argv)
     if args.replan_every < 1:
         raise SystemExit("--replan_every must be >= 1")
+    if args.warm_start is not None and args.warm_start < 1:
+        raise SystemExit("--warm_start must be >= 1")
     import torch
     from .dataset import choose_image_storage
     from .diffusion import load_model
@@ -86,7 +95,7 @@ def main(argv=None) -> dict:
             x_T = torch.rand(1, 1, H, D, device=model.device, generator=torch.Generator(device=model.device).manual_seed(seed))
             torch.cuda.synchronize(model.device)
             start = time.perf_counter()
-            plan = policy.plan(seed=seed, x_T=x_T)
+            plan = policy.plan(seed=seed, x_T=x_T) if args.warm_start is None else policy.plan(seed=seed, x_T=x_T, warm_start=args.warm_start)
             torch.cuda.synchronize(model.device)
             seconds = time.perf_counter() - start
             _, rows, out = plan_rows(t, first, end, obs_h, P, s)
@@ -94,15 +103,29 @@ def main(argv=None) -> dict:
             d = position[rows] - way
             plans.append({"row": t, "episode_end": end, "errors": np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]).tolist(),
                           "left_out": out, "seconds": seconds})
+            if args.warm_start is not None:
+                plans[-1].update(steps=plan.steps, warm=plan.warm)
             left_out += out
         first = end
-    mean, std = [], []
-    for j in range(P):
-        col = np.array([p["errors"][j] for p in plans if len(p["errors"]) > j], dtype=np.float64)
-        mean.append(float(col.mean()) if col.size else None)
-        std.append(float(col.std()) if col.size else None)
+    def per_step(chosen):
+        mean, std = [], []
+        for j in range(P):
+            col = np.array([p["errors"][j] for p in chosen if len(p["errors"]) > j], dtype=np.float64)
+            mean.append(float(col.mean()) if col.size else None)
+            std.append(float(col.std()) if col.size else None)
+        return mean, std
+
+    mean, std = per_step(plans)
     report = {"model_name": args.model_name, "obs_horizon": obs_h, "pred_horizon": P, "step_size": s, "replan_every": args.replan_every,
               "seed": args.seed, "image_storage": storage, "plans": plans, "left_out": left_out, "mean_error": mean, "std_error": std}
+    if args.warm_start is not None:
+        report["warm_start"] = args.warm_start
+        for name, chosen in (("cold", [p for p in plans if not p["warm"]]), ("warm", [p for p in plans if p["warm"]])):
+            report["mean_error_" + name], report["std_error_" + name] = per_step(chosen)
+            report["seconds_" + name] = float(np.mean([p["seconds"] for p in chosen])) if chosen else None
+        print(f"*** warm_start = {args.warm_start}: plan() mean {report['seconds_cold']} s cold, {report['seconds_warm']} s warm")
+        print("mean position error per step, cold:", report["mean_error_cold"])
+        print("mean position error per step, warm:", report["mean_error_warm"])
     times = [p["seconds"] for p in plans]
     print(f"*** {len(plans)} plans, {left_out} way-points past an episode's end left out; plan(): median {np.median(times) * 1e3:.2f} ms")
     print("mean position error per step:", mean)
