@@ -891,6 +891,12 @@ int  spdm_debug_geometry(int32_t M, int32_t N, int32_t K, int32_t HW, int32_t W,
  * and a GroupNorm prologue (its statistics in scalar registers); -1: no spdm_op_gemm call has launched yet. */
 int  spdm_debug_whole_tiles(void);
 
+/* Host-only test hook (no GPU call): how many implicit-GEMM launches this process has enqueued, from a plan or from
+ * spdm_op_gemm, that read torch.cat([upsample(x), skip]) through conv_wide.hip's slab loader (pro 4 on whole-sample two-source
+ * tiles at large batch) instead of a materialised upsampled tensor.  A captured step counts once, not per replay.
+ * SPDM_TUNE22=0 keeps it at 0. */
+int  spdm_debug_fused_upsample_launches(void);
+
 /* Op-level test hook: d_y = GELU(d_x) evaluated with the device erf that the conv prologues use
  * (nn.GELU(), models/Unet_FiLmLayer.py:104). */
 int  spdm_op_gelu(const float* d_x, float* d_y, size_t n, void* stream);

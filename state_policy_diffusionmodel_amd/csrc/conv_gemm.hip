@@ -859,12 +859,19 @@ GemmGeom gemm_geometry(const GemmArgs& a) {
     return gemm_geometry(a.geom_M > 0 ? a.geom_M : a.M, a.N, a.K, a.HW, a.W, a.taps, a.split, a.sw, a.epi == EPI_STATS && a.partial != nullptr);
 }
 
-// Which launches take a fused source (GemmArgs: PRO_POOL / PRO_UPCAT): the small-grid kernel (conv_skinny.hip) for both modes.
+// Which launches take a fused source (GemmArgs: PRO_POOL / PRO_UPCAT): the small-grid kernel (conv_skinny.hip) for both modes,
+// and, for PRO_UPCAT, conv_wide.hip where it would run the two-source launch on whole-sample 256-row tiles (the large-batch
+// first convolutions of the up blocks).  conv_skinny has priority.
 // The plan (spdm_api.hip) asks before it decides whether to materialise the pooled / concatenated tensor.
 bool gemm_takes_fused_source(const GemmArgs& a) {
     if (!(a.pro == PRO_POOL || a.pro == PRO_UPCAT) || !a.split || a.wgt_frag == nullptr || (a.sw & SW_NO_FUSED_SRC) || a.epi != EPI_STATS) return false;
     if (a.pro == PRO_UPCAT && (a.up_C <= 0 || a.up_C >= a.K || a.up_C % CK != 0 || (a.H & 1) || (a.W & 1))) return false;
-    return gemm_geometry(a).skinny != 0;
+    const GemmGeom g = gemm_geometry(a);
+    if (g.skinny != 0) return true;
+    if (a.pro != PRO_UPCAT || g.reg || g.ksplit > 1) return false;
+    GemmArgs b = a;
+    b.ksplit = 1;
+    return conv_wide_takes_upcat(b, g);
 }
 
 // Two-source input (GemmArgs::skip with pro = PRO_NONE / PRO_GN: channels [0, up_C) from src, the rest from skip): conv_wide.hip's
@@ -898,10 +905,13 @@ static bool uses_wp8(const GemmArgs& a0, const GemmGeom& g) {
     a.ksplit = g.ksplit;
     return conv_wide_supported(a, g);
 }
-double gemm_flops(const GemmArgs& a) {
+double gemm_flops(const GemmArgs& a0) {
     // (unlike gemm_geometry(a), asks for the statistics-epilogue geometry without a partial buffer too -- SPDM_NO_SPLITK, the
     // exact path -- where the launch's tiling can differ: the profiled FLOP count of those runs keeps its present value)
+    GemmArgs a = a0;
     const GemmGeom g = gemm_geometry(a.geom_M > 0 ? a.geom_M : a.M, a.N, a.K, a.HW, a.W, a.taps, a.split, a.sw, a.epi == EPI_STATS);
+    // the upsample read through conv_wide's loader runs the two-source launch's MFMAs: counted as that launch is
+    if (a.pro == PRO_UPCAT && !g.skinny && gemm_takes_fused_source(a0)) a.pro = a.skip_stats.p != nullptr ? PRO_GN : PRO_NONE;
     const double taps = uses_w2(a, g) ? 6.0 : uses_wp4(a, g) ? 7.5 : uses_wp8(a, g) ? 8.25 : (double)a.taps;
     return 2.0 * (double)a.M * (double)a.N * (double)a.K * taps;
 }
@@ -933,12 +943,22 @@ static hipError_t launch_cfg(const GemmArgs& a, const GemmGeom& g, hipStream_t s
 
 static hipError_t launch_gemm_kernel(const GemmArgs& a, const GemmGeom& g, hipStream_t s);
 
+// launches of this process that read the upsample through conv_wide's loader (host-side count: spdm_debug_fused_upsample_launches)
+static int g_wide_upcat_launches = 0;
+int gemm_wide_upcat_launches() { return g_wide_upcat_launches; }
+
 hipError_t launch_gemm(const GemmArgs& a0, hipStream_t s) {
     GemmArgs a = a0;
     a.ksplit = 1;
     const GemmGeom g = gemm_geometry(a);
     const bool fused_src = a.pro == PRO_POOL || a.pro == PRO_UPCAT;
-    if (fused_src && !g.skinny) return hipErrorInvalidValue;                            // (the plan asks gemm_takes_fused_source first)
+    if (fused_src && !g.skinny) {                                                       // (the plan asks gemm_takes_fused_source first)
+        // the upsample read through conv_wide's loader: the shape contract is conv_wide_takes_upcat's (host-checked there)
+        if (a.pro != PRO_UPCAT || !a.split || a.wgt_frag == nullptr || a.epi != EPI_STATS || a.up_C <= 0 || a.up_C >= a.K ||
+            a.up_C % CK != 0 || g.reg || a.dst == nullptr || a.epi_stats == nullptr || !conv_wide_takes_upcat(a, g)) return hipErrorInvalidValue;
+        ++g_wide_upcat_launches;
+        return launch_conv_wide(a, g, s);
+    }
     if (!fused_src && a.skip != nullptr && !gemm_takes_two_sources(a)) return hipErrorInvalidValue;   // (... gemm_takes_two_sources)
     if (g.skinny) return launch_conv_skinny(a, g, s);
     if (g.reg) return launch_conv_reg64(a, g, s);

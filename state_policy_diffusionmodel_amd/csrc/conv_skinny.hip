@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "device_utils.h"
+#include "resample.h"
 
 namespace spdm {
 
@@ -53,7 +54,7 @@ __device__ int g_skinny_sel[2];
 #endif
 
 __device__ __forceinline__ k_f32x4 k_affine(k_f32x4 v, float mu, k_f32x4 sc, k_f32x4 be) {
-    return k_f32x4{(v.x - mu) * sc.x + be.x, (v.y - mu) * sc.y + be.y, (v.z - mu) * sc.z + be.z, (v.w - mu) * sc.w + be.w};
+    return k_f32x4{affine1(v.x, mu, sc.x, be.x), affine1(v.y, mu, sc.y, be.y), affine1(v.z, mu, sc.z, be.z), affine1(v.w, mu, sc.w, be.w)};
 }
 // One 16-byte piece (channels ch 32 + c4 4 ..) of input row m of a FUSED source (kernels.h, GemmArgs): the value the
 // materialising kernels (pool_kernel / upcat_kernel, elementwise.hip) would have written there -- same arithmetic, tap by tap.
@@ -98,23 +99,15 @@ __device__ __forceinline__ k_f32x4 skinny_fused_piece(const GemmArgs& a, int m, 
     }
     // bilinear x2, align_corners=True, of the (H / 2) x (W / 2) map (upcat_kernel's arithmetic)
     const int Hin = H >> 1, Win = W >> 1;
-    const float sch = (H > 1) ? (float)(Hin - 1) / (float)(H - 1) : 0.f;
-    const float scw = (W > 1) ? (float)(Win - 1) / (float)(W - 1) : 0.f;
-    const float fh = sch * (float)h, fw = scw * (float)w;
-    const int h0 = (int)fh, w0 = (int)fw;
-    const int h1 = h0 + (h0 < Hin - 1 ? 1 : 0), w1 = w0 + (w0 < Win - 1 ? 1 : 0);
-    const float lh1 = fminf(fmaxf(fh - (float)h0, 0.f), 1.f), lw1 = fminf(fmaxf(fw - (float)w0, 0.f), 1.f);
-    const float lh0 = 1.f - lh1, lw0 = 1.f - lw1;
+    const UpAxis ah = up_axis(up_scale(Hin, H), h, Hin), aw = up_axis(up_scale(Win, W), w, Win);      // (resample.h)
     const float* base = a.src + (size_t)b * Hin * Win * a.src_ld + c;
-    k_f32x4 v00 = *reinterpret_cast<const k_f32x4*>(base + ((size_t)h0 * Win + w0) * a.src_ld);
-    k_f32x4 v01 = *reinterpret_cast<const k_f32x4*>(base + ((size_t)h0 * Win + w1) * a.src_ld);
-    k_f32x4 v10 = *reinterpret_cast<const k_f32x4*>(base + ((size_t)h1 * Win + w0) * a.src_ld);
-    k_f32x4 v11 = *reinterpret_cast<const k_f32x4*>(base + ((size_t)h1 * Win + w1) * a.src_ld);
+    k_f32x4 v00 = *reinterpret_cast<const k_f32x4*>(base + ((size_t)ah.i0 * Win + aw.i0) * a.src_ld);
+    k_f32x4 v01 = *reinterpret_cast<const k_f32x4*>(base + ((size_t)ah.i0 * Win + aw.i1) * a.src_ld);
+    k_f32x4 v10 = *reinterpret_cast<const k_f32x4*>(base + ((size_t)ah.i1 * Win + aw.i0) * a.src_ld);
+    k_f32x4 v11 = *reinterpret_cast<const k_f32x4*>(base + ((size_t)ah.i1 * Win + aw.i1) * a.src_ld);
     if (gn) { v00 = k_affine(v00, mu, sc, be); v01 = k_affine(v01, mu, sc, be); v10 = k_affine(v10, mu, sc, be); v11 = k_affine(v11, mu, sc, be); }
-    return k_f32x4{lh0 * (lw0 * v00.x + lw1 * v01.x) + lh1 * (lw0 * v10.x + lw1 * v11.x),
-                   lh0 * (lw0 * v00.y + lw1 * v01.y) + lh1 * (lw0 * v10.y + lw1 * v11.y),
-                   lh0 * (lw0 * v00.z + lw1 * v01.z) + lh1 * (lw0 * v10.z + lw1 * v11.z),
-                   lh0 * (lw0 * v00.w + lw1 * v01.w) + lh1 * (lw0 * v10.w + lw1 * v11.w)};
+    return k_f32x4{up_blend(ah, aw, v00.x, v01.x, v10.x, v11.x), up_blend(ah, aw, v00.y, v01.y, v10.y, v11.y),
+                   up_blend(ah, aw, v00.z, v01.z, v10.z, v11.z), up_blend(ah, aw, v00.w, v01.w, v10.w, v11.w)};
 }
 
 // RT row tiles of 16 (M_T = 16 RT), CT column tiles of 16 (N_T = 16 CT)

@@ -35,6 +35,7 @@
 #include <cstdlib>
 
 #include "device_utils.h"
+#include "resample.h"
 
 namespace spdm {
 
@@ -112,7 +113,8 @@ __device__ __forceinline__ f32x2 split2(float a, float b) {
 // TWO: two-source input (the first convolution of an UpSample block, models/Unet_FiLmLayer.py:217-219): the 32-channel chunks
 // [0, up_C / 32) come from a.src -- the upsampled tensor, finished -- and the rest from a.skip, the skip connection, which is
 // what the prologue PRO (its pending GroupNorm) applies to.  torch.cat is then never materialised: upcat_kernel shrinks to the
-// upsample alone (no copy of the skip half: at up3 that copy was 268 MB in + 268 MB out per step at B = 4096).
+// upsample alone (no copy of the skip half: at up3 that copy was 268 MB in + 268 MB out per step at B = 4096) -- and on
+// whole-sample 256-row tiles it does not run at all: see UP below.
 // G2 (experiment, opt-in SPDM_G2=1; see launch_conv_wide for the measurement): two 32-channel chunks per slab hand-over on the
 // 64-row-per-wave variants of the tap loop -- the loads of both chunks in flight together, one round trip and one barrier pair
 // per 64 channels.  Neutral to slower: the round trip is not what the hand-over costs.
@@ -123,7 +125,16 @@ __device__ __forceinline__ f32x2 split2(float a, float b) {
 // it divides M_T) -- the packed tables avalid / abidx are not built.  WH == 2: HW == M_T, ONE sample per tile: its mean and
 // rstd sit in scalar registers and rs gamma is formed once per chunk instead of once per pass.  The arithmetic per element is
 // (v - mu) (rs gamma) + beta on the same operands either way: bit-identical to WH == 0 (tests/test_gpu_conv_whole_tiles.py).
-template <int NT, int PRO, bool W2, int RT, int WN, bool PIPE, bool TWO = false, int WP = 0, bool G2 = false, int WH = 0>
+// UP (PRO_UPCAT on whole-sample two-source tiles, 256 rows, in the three layouts WP8 / WP4 / W2): the chunks [0, up_C / 32) are
+// not read from a materialised upsampled tensor but formed here from a.src, the COARSER level's raw tensor [B][HW / 4][up_C]
+// with its pending GroupNorm in a.pro_* (a.pro_stats.p == nullptr: none); the skip's pending GroupNorm (template PRO) is then
+// in a.skip_*.  A tile holds whole samples, so the coarse map it needs is exactly the M_T / 4 = 64 rows m0 / 4 .. of that
+// tensor: two 32-row load passes per chunk instead of eight, the pending affine applied once per COARSE element, the rows
+// parked in a raw LDS buffer (64 x 144 bytes, in the LDS between the end of the slab and the end of the epilogue's tile: the
+// workgroup's allocation does not grow), and every thread forms its eight staged rows as the align_corners blend of four LDS
+// neighbours (resample.h: upcat_kernel's arithmetic, bit for bit) before the split.  The raw buffer is not what the MFMA loop
+// reads, so it is written BEFORE the hand-over's first barrier, which then also publishes it: no barrier is added.
+template <int NT, int PRO, bool W2, int RT, int WN, bool PIPE, bool TWO = false, int WP = 0, bool G2 = false, int WH = 0, bool UP = false>
 // launch bound (256, 2): a 256-register budget.  The 8 x 2 variants with a prologue then carry 88-128 bytes of scratch per lane
 // (stats finalisation state parked across the main loop); with (256, 1) the compiler allocates 203-250 registers and no scratch,
 // but schedules the loop worse: measured 10.5 vs 9.6-9.9 ms per step (same box, alternating).  Keep 2.
@@ -164,6 +175,10 @@ __global__ __launch_bounds__(256, WIDE_MINB) void conv3x3_wide_kernel(const Gemm
     //  36 x 36 floats = 16 banks mod 64 spreads them; 32 would put all eight on the same banks.)
     static_assert(!G2 || (NT == 2 && RT == 4 && !W2 && !PIPE && !WP && !WIDE_DB), "two chunks per hand-over: the plain tap loop, 64 rows per wave");
     static_assert(!WHOLE || (!G2 && !WIDE_DB && !WIDE_EARLY), "whole-sample staging: not in the hand-over experiments");
+    static_assert(!UP || (TWO && WHOLE && RT == 8 && NT == 2 && WN == 2 && (W2 || WP)), "upsample in the loader: whole-sample two-source 256-row tiles");
+    constexpr int UW = WP8 ? 8 : WP ? 4 : 2;            // UP: the map width is the layout's (host-checked)
+    constexpr int UPASS = M_T / 4 / RP;                 // UP: load passes over the tile's coarse rows
+    constexpr int RAWP = 36;                            // UP: pitch (floats) of the raw coarse rows in LDS
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -196,6 +211,13 @@ __global__ __launch_bounds__(256, WIDE_MINB) void conv3x3_wide_kernel(const Gemm
     float* Awr = smem + (DB ? QZ * LDK : 0);  // the slab being staged (DB: the idle one of two)
     float* smean = smem + ((DB || G2) ? 2 : 1) * QZ * LDK;     // [NS]  (G2: the slab holds two chunks)
     float* srstd = smean + NS;                // [NS]
+    float* cmean = srstd + NS;                // UP: [NS] x 2, mean / rstd of the coarse tensor's samples of this tile
+    float* crstd = cmean + NS;
+    float* rawc = crstd + NS;                 // UP: [M_T / 4][RAWP], the tile's coarse rows of one chunk, finished
+    // the GroupNorm the template prologue PRO applies: the skip's under UP (a.pro_* is then the coarse tensor's)
+    const StatsRef& pst = UP ? a.skip_stats : a.pro_stats;
+    const float* const pgam = UP ? a.skip_gamma : a.pro_gamma;
+    const float* const pbet = UP ? a.skip_beta : a.pro_beta;
 
     // diagnostic builds: per-workgroup timeline {memrealtime, memtime x5, HW_ID, XCC_ID} (tools/bench_gemm.py --stamp)
 #ifdef SPDM_DIAG
@@ -222,8 +244,20 @@ __global__ __launch_bounds__(256, WIDE_MINB) void conv3x3_wide_kernel(const Gemm
     int bh_first = 0;
     float mu1 = 0.f, rs1 = 1.f;                 // ONE: the tile's sample, wave-uniform
     const int lhw = WHOLE ? __builtin_ctz((unsigned)HW) : 0;
+    const bool upgn = UP && a.pro_stats.p != nullptr;               // UP: the coarse tensor carries a pending GroupNorm
+    const float sch = UP ? up_scale(H >> 1, H) : 0.f;               // UP: coarse rows per row (resample.h); wave-uniform
+    if constexpr (UP) {
+        if (upgn) {                            // one wave per sample of the tile, as upcat_kernel sums the partials
+            for (int t = wave; t < (M_T >> lhw); t += NTHR / 64) {
+                float mean, rstd;
+                sample_mean_rstd_wave(a.pro_stats, (m0 >> lhw) + t, lane, mean, rstd);
+                if (lane == 0) { cmean[t] = mean; crstd[t] = rstd; }
+            }
+        }
+        __syncthreads();
+    }
     if constexpr (pro && ONE) {
-        sample_mean_rstd(a.pro_stats, m0 / HW, mu1, rs1);          // (every thread: the same few partials; no LDS table, no barrier)
+        sample_mean_rstd(pst, m0 / HW, mu1, rs1);          // (every thread: the same few partials; no LDS table, no barrier)
         mu1 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, mu1)));
         rs1 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, rs1)));
     } else if (pro) {
@@ -232,7 +266,7 @@ __global__ __launch_bounds__(256, WIDE_MINB) void conv3x3_wide_kernel(const Gemm
         const int bh_last = hi / HW;
         for (int t = tid; t <= bh_last - bh_first; t += NTHR) {
             float mean, rstd;
-            sample_mean_rstd(a.pro_stats, bh_first + t, mean, rstd);
+            sample_mean_rstd(pst, bh_first + t, mean, rstd);
             smean[t] = mean;
             srstd[t] = rstd;
         }
@@ -304,10 +338,11 @@ __global__ __launch_bounds__(256, WIDE_MINB) void conv3x3_wide_kernel(const Gemm
     // integer ops per pass) at each hand-over instead: no scratch, -3 % on up3.dc1.second / up1.dc1.second.  Everywhere
     // else the hoisted form measured 2-5 % FASTER (tools/bench_gemm.py, alternating builds), so it stays.
     int srow_o = srow_t;
+    int c4o = c4;                   // UP: opaque too, so that no address built on it is carried through the main loop
 #ifdef WIDE_NO_OPAQUE
 #define WIDE_OPAQUE_ROW
 #else
-#define WIDE_OPAQUE_ROW if constexpr (PRO != PRO_NONE && RT == 8) asm volatile("" : "+v"(srow_o));
+#define WIDE_OPAQUE_ROW if constexpr ((PRO != PRO_NONE || UP) && RT == 8) { asm volatile("" : "+v"(srow_o)); if constexpr (UP) asm volatile("" : "+v"(c4o)); }
 #endif
 #define WIDE_LOAD_A(chunk_) WIDE_LOAD_A_(chunk_, areg, g4r, b4r, ident)
 #define WIDE_STAGE_A() WIDE_STAGE_A_(areg, g4r, b4r, ident, Awr)
@@ -316,22 +351,64 @@ __global__ __launch_bounds__(256, WIDE_MINB) void conv3x3_wide_kernel(const Gemm
         WIDE_OPAQUE_ROW                                                                              \
         const bool first_ = !TWO || (chunk_) < nc0;                                                  \
         const int cc_ = (TWO && !first_) ? (chunk_) - nc0 : (chunk_);      /* chunk inside its tensor */ \
-        const float* ab_ = (first_ ? abase : abase1) + cc_ * CK;                                     \
+        const float* ab_ = (UP ? (first_ ? a.src : a.skip) + c4o * 4 : (first_ ? abase : abase1)) + cc_ * CK; \
         const int ld_ = first_ ? a.src_ld : a.skip_ld;                                               \
+        if (UP) { ident_ = first_; g4r_ = f32x4{1.f, 1.f, 1.f, 1.f}; b4r_ = f32x4{0.f, 0.f, 0.f, 0.f}; } \
+        if (UP && first_) {                    /* the tile's coarse rows (m0 / 4 ..) of this chunk, raw */ \
+            _Pragma("unroll") for (int p_ = 0; p_ < UPASS; ++p_)                                    \
+                areg_[p_] = *reinterpret_cast<const f32x4*>(ab_ + (size_t)((m0 >> 2) + p_ * RP + srow_o) * ld_); \
+            if (upgn) {                                                                              \
+                g4r_ = *reinterpret_cast<const f32x4*>(a.pro_gamma + cc_ * CK + c4o * 4);             \
+                b4r_ = *reinterpret_cast<const f32x4*>(a.pro_beta + cc_ * CK + c4o * 4);              \
+            }                                                                                        \
+        } else {                                                                                     \
         _Pragma("unroll") for (int p_ = 0; p_ < APASS; ++p_) {                                      \
             const int mc_ = WHOLE ? m0 + p_ * RP + srow_o : min(max(m0 - halo + p_ * RP + srow_o, 0), M - 1); \
             areg_[p_] = *reinterpret_cast<const f32x4*>(ab_ + (size_t)mc_ * ld_);                     \
         }                                                                                            \
         if (pro) {                                                                                   \
             ident_ = TWO && first_;                                                                   \
-            g4r_ = *reinterpret_cast<const f32x4*>(a.pro_gamma + cc_ * CK + c4 * 4);                  \
-            b4r_ = *reinterpret_cast<const f32x4*>(a.pro_beta + cc_ * CK + c4 * 4);                   \
+            g4r_ = *reinterpret_cast<const f32x4*>(pgam + cc_ * CK + (UP ? c4o : c4) * 4);            \
+            b4r_ = *reinterpret_cast<const f32x4*>(pbet + cc_ * CK + (UP ? c4o : c4) * 4);            \
             if (TWO && first_) { g4r_ = f32x4{1.f, 1.f, 1.f, 1.f}; b4r_ = f32x4{0.f, 0.f, 0.f, 0.f}; } \
             else if (ONE) g4r_ = rs1 * g4r_;                        /* rs gamma, once per chunk */   \
         }                                                                                            \
+        }                                                                                            \
     }
 #define WIDE_STAGE_A_(areg_, g4r_, b4r_, ident_, dst_)                                                                             \
-    {                                                                                                \
+    if (UP && ident_) {                                                                              \
+        /* coarse rows -> raw buffer, their pending GroupNorm applied once per element (apply_affine's arithmetic) */ \
+        _Pragma("unroll") for (int p_ = 0; p_ < UPASS; ++p_) {                                      \
+            const int r_ = p_ * RP + srow_o;                                                         \
+            f32x4 v_ = areg_[p_];                                                                     \
+            if (upgn) {                                                                              \
+                const int bi_ = r_ >> (lhw - 2);                                                     \
+                const float rs_ = crstd[bi_], mu_ = cmean[bi_];                                      \
+                v_.x = affine1(v_.x, mu_, rs_ * g4r_.x, b4r_.x);                                      \
+                v_.y = affine1(v_.y, mu_, rs_ * g4r_.y, b4r_.y);                                      \
+                v_.z = affine1(v_.z, mu_, rs_ * g4r_.z, b4r_.z);                                      \
+                v_.w = affine1(v_.w, mu_, rs_ * g4r_.w, b4r_.w);                                      \
+            }                                                                                        \
+            *reinterpret_cast<f32x4*>(rawc + r_ * RAWP + c4o * 4) = v_;                               \
+        }                                                                                            \
+        __syncthreads();        /* the raw rows are complete AND every wave is done reading the slab of the previous chunk */ \
+        const UpAxis aw_ = up_axis(up_scale(UW / 2, UW), srow_o & (UW - 1), UW / 2);      /* (32 % UW == 0: the same column in every pass) */ \
+        _Pragma("unroll") for (int p_ = 0; p_ < APASS; ++p_) {                                      \
+            const int q_ = p_ * RP + srow_o;                                                         \
+            const UpAxis ah_ = up_axis(sch, (q_ & (HW - 1)) / UW, H >> 1);                            \
+            const float* rb_ = rawc + ((q_ >> lhw) << (lhw - 2)) * RAWP + c4o * 4;      /* the sample's coarse map */ \
+            const f32x4 v00_ = *reinterpret_cast<const f32x4*>(rb_ + (ah_.i0 * (UW / 2) + aw_.i0) * RAWP); \
+            const f32x4 v01_ = *reinterpret_cast<const f32x4*>(rb_ + (ah_.i0 * (UW / 2) + aw_.i1) * RAWP); \
+            const f32x4 v10_ = *reinterpret_cast<const f32x4*>(rb_ + (ah_.i1 * (UW / 2) + aw_.i0) * RAWP); \
+            const f32x4 v11_ = *reinterpret_cast<const f32x4*>(rb_ + (ah_.i1 * (UW / 2) + aw_.i1) * RAWP); \
+            const f32x2 p0_ = split2(up_blend(ah_, aw_, v00_.x, v01_.x, v10_.x, v11_.x), up_blend(ah_, aw_, v00_.y, v01_.y, v10_.y, v11_.y)); \
+            const f32x2 p1_ = split2(up_blend(ah_, aw_, v00_.z, v01_.z, v10_.z, v11_.z), up_blend(ah_, aw_, v00_.w, v01_.w, v10_.w, v11_.w)); \
+            float* row_ = (dst_) + (WP8 ? (q_ & 7) * NI8 + (q_ >> 3) : q_) * LDK;                     \
+            *reinterpret_cast<f32x2*>(row_ + c4o * 2) = f32x2{p0_.x, p1_.x};       /* hi */          \
+            *reinterpret_cast<f32x2*>(row_ + 16 + c4o * 2) = f32x2{p0_.y, p1_.y};  /* lo */          \
+            __builtin_amdgcn_sched_barrier(0);                                     /* one pass at a time: register pressure */ \
+        }                                                                                            \
+    } else {                                                                                         \
         _Pragma("unroll") for (int p_ = 0; p_ < APASS; ++p_) {                                      \
             f32x4 v_ = areg_[p_];                                                                     \
             if (pro && ONE) {                                        /* g4r_ already holds rs gamma */ \
@@ -360,8 +437,8 @@ __global__ __launch_bounds__(256, WIDE_MINB) void conv3x3_wide_kernel(const Gemm
             {   /* rows past the slab go to a dump row: no branch (see the header) */                 \
                 const int q_ = p_ * RP + srow_o;                                                     \
                 float* row_ = (dst_) + (WHOLE ? (WP8 ? (q_ & 7) * NI8 + (q_ >> 3) : q_) : WP8 ? (q_ < QA ? ((q_ + 7) & 7) * NI8 + ((q_ + 7) >> 3) : 8 * NI8 + 1) : min(q_, QA + 1)) * LDK; \
-                *reinterpret_cast<f32x2*>(row_ + c4 * 2) = f32x2{p0_.x, p1_.x};       /* hi */       \
-                *reinterpret_cast<f32x2*>(row_ + 16 + c4 * 2) = f32x2{p0_.y, p1_.y};  /* lo */       \
+                *reinterpret_cast<f32x2*>(row_ + (UP ? c4o : c4) * 2) = f32x2{p0_.x, p1_.x};       /* hi */ \
+                *reinterpret_cast<f32x2*>(row_ + 16 + (UP ? c4o : c4) * 2) = f32x2{p0_.y, p1_.y};  /* lo */ \
             }                                                                                        \
             if (pro && (p_ % WIDE_STAGE_GROUP) == WIDE_STAGE_GROUP - 1) __builtin_amdgcn_sched_barrier(0);   /* WIDE_STAGE_GROUP passes at a time: register pressure */ \
         }                                                                                            \
@@ -801,7 +878,7 @@ __global__ __launch_bounds__(256, WIDE_MINB) void conv3x3_wide_kernel(const Gemm
             }
             if (next_A) {
                 WIDE_LOAD_A(nchunk)
-                __syncthreads();
+                if (!(UP && ident)) __syncthreads();       // (an upsampled chunk meets at the barrier inside its staging)
                 WIDE_STAGE_A()
                 __syncthreads();
                 WIDE_LOAD_FA(0, 1, WIDE_SHIFT(0, 1), 0)
@@ -926,7 +1003,7 @@ __global__ __launch_bounds__(256, WIDE_MINB) void conv3x3_wide_kernel(const Gemm
             }
             if (next_A) {
                 WIDE_LOAD_A(nchunk)
-                __syncthreads();
+                if (!(UP && ident)) __syncthreads();       // (an upsampled chunk meets at the barrier inside its staging)
                 WIDE_STAGE_A()
                 __syncthreads();
                 WIDE_LOAD_FA(0, 1, WIDE_SHIFT(0, 1), 0)
@@ -1084,7 +1161,7 @@ __global__ __launch_bounds__(256, WIDE_MINB) void conv3x3_wide_kernel(const Gemm
 #undef WIDE_ROWOFF
 }
 
-template <int NT, int PRO, bool W2 = false, int RT = 8, int WN = 2, bool PIPE = false, bool TWO = false, int WP = 0, bool G2 = false, int WH = 0>
+template <int NT, int PRO, bool W2 = false, int RT = 8, int WN = 2, bool PIPE = false, bool TWO = false, int WP = 0, bool G2 = false, int WH = 0, bool UP = false>
 hipError_t launch_wide_cfg(const GemmArgs& a, const GemmGeom& g, hipStream_t s) {
     constexpr int M_T = (4 / WN) * RT * 16, N_T = WN * 32 * NT, NTHR = 256;
     constexpr int APASS = WH ? M_T / 32 : (M_T + 18 + 31) / 32, NSMAX = (APASS <= 9) ? 128 : (APASS <= 10) ? 64 : 32;
@@ -1099,9 +1176,10 @@ hipError_t launch_wide_cfg(const GemmArgs& a, const GemmGeom& g, hipStream_t s) 
     if (WP && (a.taps != 9 || a.W != WP || a.HW % (4 * WP) != 0)) return hipErrorInvalidValue;
     const int QZ = (WP == 8) ? 8 * ((M_T + 18 + 6) / 8 + 1) + 2 : QA + 2;          // (WP8: the class-major slab)
     size_t lds = (size_t)(((DB || G2) ? 2 : 1) * QZ * LDK + 2 * NS) * sizeof(float);
+    if (UP) lds += (size_t)(2 * NS + (M_T / 4) * 36) * sizeof(float);        // coarse statistics + the raw coarse rows (below the epilogue's size)
     lds = std::max(lds, (size_t)((M_T / (W2 ? 2 : WP ? RT / 4 : WIDE_NH)) * N_T + (M_T / 4) * WN * 2) * sizeof(float));
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    auto kern = conv3x3_wide_kernel<NT, PRO, W2, RT, WN, PIPE, TWO, WP, G2, WH>;
+    auto kern = conv3x3_wide_kernel<NT, PRO, W2, RT, WN, PIPE, TWO, WP, G2, WH, UP>;
     if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return e;
     const int n_mtiles = (a.M + M_T - 1) / M_T;
     if (a.ksplit > 1 && a.K % 64 != 0) return hipErrorInvalidValue;          // split-K walks even chunk ranges
@@ -1114,15 +1192,16 @@ hipError_t launch_wide_cfg(const GemmArgs& a, const GemmGeom& g, hipStream_t s) 
 // last tile.  MODES: bit 0 = the configuration has a WH = 1 instantiation, bit 1 = a WH = 2 one (one sample per tile: the
 // level-0 configurations); a one-sample tile of a configuration without it takes WH = 1, which covers it.  Everything else --
 // ragged tiles, HW not dividing the tile, SPDM_NO_WHOLE_TILES -- keeps the halo'd slab.
-template <int MODES, int NT, int PRO, bool W2 = false, int RT = 8, int WN = 2, bool PIPE = false, bool TWO = false, int WP = 0>
+template <int MODES, int NT, int PRO, bool W2 = false, int RT = 8, int WN = 2, bool PIPE = false, bool TWO = false, int WP = 0, bool UP = false>
 hipError_t launch_wide_sel(const GemmArgs& a, const GemmGeom& g, hipStream_t s) {
     constexpr int M_T = (4 / WN) * RT * 16;
     const bool whole = !(a.sw & SW_NO_WHOLE_TILES) && M_T % a.HW == 0 && a.M % M_T == 0;
     if constexpr ((MODES & 2) != 0 && PRO != PRO_NONE)       // (without a prologue the two are the same code)
-        if (whole && a.HW == M_T) return launch_wide_cfg<NT, PRO, W2, RT, WN, PIPE, TWO, WP, false, 2>(a, g, s);
+        if (whole && a.HW == M_T) return launch_wide_cfg<NT, PRO, W2, RT, WN, PIPE, TWO, WP, false, 2, UP>(a, g, s);
     if constexpr ((MODES & 1) != 0)
-        if (whole) return launch_wide_cfg<NT, PRO, W2, RT, WN, PIPE, TWO, WP, false, 1>(a, g, s);
-    return launch_wide_cfg<NT, PRO, W2, RT, WN, PIPE, TWO, WP, false, 0>(a, g, s);
+        if (whole) return launch_wide_cfg<NT, PRO, W2, RT, WN, PIPE, TWO, WP, false, 1, UP>(a, g, s);
+    if constexpr (UP) return hipErrorInvalidValue;          // (the upsampling loader exists on whole-sample tiles only: conv_wide_takes_upcat)
+    else return launch_wide_cfg<NT, PRO, W2, RT, WN, PIPE, TWO, WP, false, 0>(a, g, s);
 }
 
 }  // namespace
@@ -1155,7 +1234,46 @@ bool conv_wide_supported(const GemmArgs& a, const GemmGeom& g) {
     return true;
 }
 
-hipError_t launch_conv_wide(const GemmArgs& a, const GemmGeom& g, hipStream_t s) {
+// PRO_UPCAT (kernels.h, GemmArgs "fused sources") on the kernel's UP variants: the launch conv_wide would take as a whole-sample
+// two-source tile of 256 rows in one of the three layouts (width 8 class-major, width 4, width 2), were the upsampled tensor
+// materialised.  Everything else -- ragged or halo'd tiles, maps taller than a tile, 128-row tiles, split-K -- keeps
+// upcat_kernel + the two-source launch.  SPDM_TUNE22: bit 0 / 1 / 2 = the width-8 / 4 / 2 level (0: never, today's path).
+static GemmArgs upcat_as_two(const GemmArgs& a0) {
+    GemmArgs a = a0;
+    a.pro = a0.skip_stats.p != nullptr ? PRO_GN : PRO_NONE;      // the template prologue is the skip's pending GroupNorm
+    return a;
+}
+bool conv_wide_takes_upcat(const GemmArgs& a, const GemmGeom& g) {
+    if (a.pro != PRO_UPCAT || a.M <= 0 || a.skip == nullptr || a.src == nullptr || g.skinny || g.reg || g.ksplit > 1 || a.ksplit > 1) return false;
+    if (g.m_tile != 256 || g.n_tile != 128 || a.taps != 9 || (a.H & 1) || a.HW != a.H * a.W || a.HW < 16 || (a.HW & (a.HW - 1)) != 0) return false;
+    if ((a.sw & (SW_NO_WHOLE_TILES | SW_NO_FUSED_SRC)) || 256 % a.HW != 0 || a.M % 256 != 0 || a.K % 64 != 0) return false;
+    const int level = a.W == 8 ? 0 : a.W == 4 ? 1 : a.W == 2 ? 2 : -1;
+    if (level < 0 || !((spdm_tune(22, 7) >> level) & 1)) return false;
+    if ((a.W == 8 && ((a.sw & SW_NO_WP8) || a.HW % 32 != 0)) || (a.W == 4 && ((a.sw & SW_NO_WP4) || a.HW % 16 != 0)) ||
+        (a.W == 2 && (a.sw & SW_NO_W2))) return false;
+    // the pending GroupNorms: of the coarse tensor ([B][HW / 4][up_C]) in pro_*, of the skip in skip_*
+    if (a.pro_stats.p != nullptr && (a.pro_gamma == nullptr || a.pro_beta == nullptr || a.pro_stats.HW * 4 != a.HW)) return false;
+    if (a.skip_stats.p != nullptr && (a.skip_gamma == nullptr || a.skip_beta == nullptr || a.skip_stats.HW != a.HW)) return false;
+    if (a.src_ld % 4 != 0 || a.dst_ld % 4 != 0 || a.N % 128 != 0) return false;      // (dst / epi_stats: the plan asks before it allocates them)
+    return conv_wide_supported(upcat_as_two(a), g);
+}
+
+hipError_t launch_conv_wide(const GemmArgs& a0, const GemmGeom& g, hipStream_t s) {
+    if (a0.pro == PRO_UPCAT) {
+        if (!conv_wide_takes_upcat(a0, g)) return hipErrorInvalidValue;
+        const GemmArgs a = upcat_as_two(a0);
+        if (a.W == 8) {
+            if (a.pro == PRO_NONE) return launch_wide_sel<3, 2, PRO_NONE, false, 8, 2, false, true, 8, true>(a, g, s);
+            return launch_wide_sel<3, 2, PRO_GN, false, 8, 2, false, true, 8, true>(a, g, s);
+        }
+        if (a.W == 4) {
+            if (a.pro == PRO_NONE) return launch_wide_sel<1, 2, PRO_NONE, false, 8, 2, false, true, 4, true>(a, g, s);
+            return launch_wide_sel<1, 2, PRO_GN, false, 8, 2, false, true, 4, true>(a, g, s);
+        }
+        if (a.pro == PRO_NONE) return launch_wide_sel<1, 2, PRO_NONE, true, 8, 2, false, true, 0, true>(a, g, s);
+        return launch_wide_sel<1, 2, PRO_GN, true, 8, 2, false, true, 0, true>(a, g, s);
+    }
+    const GemmArgs& a = a0;
     if (!conv_wide_supported(a, g)) return hipErrorInvalidValue;
     // Pipelined slab hand-over (PIPE: the next chunk's slab is staged one 32-row pass per tap into a second buffer, one barrier
     // per chunk).  Measured per layer at B = 512 and 4096 (tools/bench_convs.py, SPDM_NO_WIDE_PIPE on / off): a win only on the

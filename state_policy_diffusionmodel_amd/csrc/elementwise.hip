@@ -6,6 +6,7 @@
 #include <algorithm>
 
 #include "device_utils.h"
+#include "resample.h"
 
 namespace spdm {
 
@@ -146,10 +147,10 @@ __device__ __forceinline__ Affine4 finish_affine(const AffineParams& p, float me
 }
 __device__ __forceinline__ float4 apply_affine(const Affine4& a, float4 v) {
     if (a.on) {
-        v.x = (v.x - a.mu) * a.sc.x + a.be.x;
-        v.y = (v.y - a.mu) * a.sc.y + a.be.y;
-        v.z = (v.z - a.mu) * a.sc.z + a.be.z;
-        v.w = (v.w - a.mu) * a.sc.w + a.be.w;
+        v.x = affine1(v.x, a.mu, a.sc.x, a.be.x);
+        v.y = affine1(v.y, a.mu, a.sc.y, a.be.y);
+        v.z = affine1(v.z, a.mu, a.sc.z, a.be.z);
+        v.w = affine1(v.w, a.mu, a.sc.w, a.be.w);
     }
     return v;
 }
@@ -247,27 +248,22 @@ __global__ __launch_bounds__(256) void upcat_kernel(const AffineSrc up, const Af
     }
     if (rl >= rpp) return;               // C / 4 need not divide 256 (after the only barrier)
     const Affine4 af = is_up ? finish_affine(ap, mu_u, rs_u) : finish_affine(ap, mu_s, rs_s);
-    const float sch = (Ho > 1) ? (float)(Hin - 1) / (float)(Ho - 1) : 0.f;
-    const float scw = (Wo > 1) ? (float)(Win - 1) / (float)(Wo - 1) : 0.f;
+    const float sch = up_scale(Hin, Ho), scw = up_scale(Win, Wo);
     const int r_end = min(HWo, (int)(blockIdx.y + 1) * rows_per_block);
     for (int ro = blockIdx.y * rows_per_block + rl; ro < r_end; ro += rpp) {
         const int ho = ro / Wo, wo = ro - ho * Wo;
         float4 o;
         if (is_up) {
-            const float fh = sch * (float)ho, fw = scw * (float)wo;
-            const int h0 = (int)fh, w0 = (int)fw;
-            const int h1 = h0 + (h0 < Hin - 1 ? 1 : 0), w1 = w0 + (w0 < Win - 1 ? 1 : 0);
-            const float lh1 = fminf(fmaxf(fh - (float)h0, 0.f), 1.f), lw1 = fminf(fmaxf(fw - (float)w0, 0.f), 1.f);
-            const float lh0 = 1.f - lh1, lw0 = 1.f - lw1;
+            const UpAxis ah = up_axis(sch, ho, Hin), aw = up_axis(scw, wo, Win);      // (resample.h: the one definition of this arithmetic)
             const float* base = up.x + (size_t)b * Hin * Win * Cu + cl;
-            const float4 v00 = apply_affine(af, *reinterpret_cast<const float4*>(base + ((size_t)h0 * Win + w0) * Cu));
-            const float4 v01 = apply_affine(af, *reinterpret_cast<const float4*>(base + ((size_t)h0 * Win + w1) * Cu));
-            const float4 v10 = apply_affine(af, *reinterpret_cast<const float4*>(base + ((size_t)h1 * Win + w0) * Cu));
-            const float4 v11 = apply_affine(af, *reinterpret_cast<const float4*>(base + ((size_t)h1 * Win + w1) * Cu));
-            o.x = lh0 * (lw0 * v00.x + lw1 * v01.x) + lh1 * (lw0 * v10.x + lw1 * v11.x);
-            o.y = lh0 * (lw0 * v00.y + lw1 * v01.y) + lh1 * (lw0 * v10.y + lw1 * v11.y);
-            o.z = lh0 * (lw0 * v00.z + lw1 * v01.z) + lh1 * (lw0 * v10.z + lw1 * v11.z);
-            o.w = lh0 * (lw0 * v00.w + lw1 * v01.w) + lh1 * (lw0 * v10.w + lw1 * v11.w);
+            const float4 v00 = apply_affine(af, *reinterpret_cast<const float4*>(base + ((size_t)ah.i0 * Win + aw.i0) * Cu));
+            const float4 v01 = apply_affine(af, *reinterpret_cast<const float4*>(base + ((size_t)ah.i0 * Win + aw.i1) * Cu));
+            const float4 v10 = apply_affine(af, *reinterpret_cast<const float4*>(base + ((size_t)ah.i1 * Win + aw.i0) * Cu));
+            const float4 v11 = apply_affine(af, *reinterpret_cast<const float4*>(base + ((size_t)ah.i1 * Win + aw.i1) * Cu));
+            o.x = up_blend(ah, aw, v00.x, v01.x, v10.x, v11.x);
+            o.y = up_blend(ah, aw, v00.y, v01.y, v10.y, v11.y);
+            o.z = up_blend(ah, aw, v00.z, v01.z, v10.z, v11.z);
+            o.w = up_blend(ah, aw, v00.w, v01.w, v10.w, v11.w);
         } else {
             // (the last reader of the skip tensor: streamed past the caches)
             typedef float nt_f32x4 __attribute__((ext_vector_type(4)));

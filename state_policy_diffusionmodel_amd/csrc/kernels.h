@@ -103,7 +103,8 @@ struct GemmArgs {
     int taps;                          // 1, 3 (vertical taps, W == 1) or 9
     int H, W, HW;                      // spatial dims of this level
     int pro;  StatsRef pro_stats;  const float* pro_gamma;  const float* pro_beta;
-    // Fused sources (conv_skinny.hip, conv_wide.hip; gemm_takes_fused_source says which launches):
+    // Fused sources (gemm_takes_fused_source says which launches: conv_skinny.hip takes both modes on its small grids,
+    // conv_wide.hip PRO_UPCAT on whole-sample two-source tiles at large batch; PRO_POOL at large batch is refused):
     //   PRO_POOL : the conv input is MaxPool2d(2) (models/Unet_FiLmLayer.py:132,159) of src, src being the FINER level's tensor
     //              [B][4 HW][K] -- a (2 H) x (2 W) map per sample -- with its pending GroupNorm in pro_stats / pro_gamma / pro_beta
     //              (pro_stats.p == nullptr: none; the affine is applied per tap: max does not commute with a negative gain);
@@ -168,6 +169,10 @@ double gemm_flops(const GemmArgs& a);
 // conv_wide.hip: the 4-wave / 128x64-per-wave configuration of the 3x3 implicit GEMM (256 x 128 tiles, two
 // workgroups per CU); launch_gemm routes to it when conv_wide_supported
 bool conv_wide_supported(const GemmArgs& a, const GemmGeom& g);
+// ... and takes pro = PRO_UPCAT itself (the upsample formed in its slab loader) when the launch is a whole-sample two-source
+// tile of 256 rows on a width-8 / 4 / 2 map; a (ksplit as launch_gemm sets it) and the geometry launch_gemm chose
+bool conv_wide_takes_upcat(const GemmArgs& a, const GemmGeom& g);
+int gemm_wide_upcat_launches();        // conv_gemm.hip: how many launches of this process launch_gemm sent that way (host-side count)
 hipError_t launch_conv_wide(const GemmArgs& a, const GemmGeom& g, hipStream_t s);
 
 // ---- streaming / small kernels (elementwise.hip) -------------------------------------------

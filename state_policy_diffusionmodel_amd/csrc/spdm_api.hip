@@ -3900,6 +3900,8 @@ extern "C" int spdm_op_gelu(const float* d_x, float* d_y, size_t n, void* stream
 // Host-only introspection: how the launch of the most recent spdm_op_gemm call staged its input slab (GemmRoute::whole)
 static int g_op_gemm_whole = -1;
 extern "C" int spdm_debug_whole_tiles(void) { return g_op_gemm_whole; }
+// ... how many launches of this process (plan or spdm_op_gemm; a captured step counts once) read the upsample through conv_wide's loader
+extern "C" int spdm_debug_fused_upsample_launches(void) { return gemm_wide_upcat_launches(); }
 
 // op-level test hook: one launch_gemm exactly as the plan builds it, on the caller's tensors (include/spdm.h)
 extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {
