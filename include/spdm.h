@@ -46,7 +46,7 @@ typedef enum {
     SPDM_ERR_NOMEM = -5
 } spdm_status;
 
-typedef enum { SPDM_DDPM = 0, SPDM_DDIM = 1 } spdm_scheduler_kind;
+typedef enum { SPDM_DDPM = 0, SPDM_DDIM = 1, SPDM_DPMPP_2M = 2 } spdm_scheduler_kind;
 
 typedef struct spdm_handle spdm_handle;
 
@@ -170,7 +170,20 @@ int  spdm_set_schedule(spdm_handle* h, int32_t kind, int32_t num_train_timesteps
  *   { sqrt(1-abar_t), sqrt(abar_t), k_x0, k_x, k_eps, k_noise } with
  *   x0   = (x - c0*eps) / c1
  *   prev = k_x0*x0 + k_x*x [+ k_noise*z]   (DDPM)
- *   prev = k_x0*x0 + k_eps*eps              (DDIM, eta = 0)                       */
+ *   prev = k_x0*x0 + k_eps*eps              (DDIM, eta = 0)
+ * SPDM_DPMPP_2M (DPM-Solver++, data prediction, multistep, midpoint) is accepted here only -- spdm_set_schedule
+ * and spdm_schedule_tables refuse it, their signature has no room for the solver's options -- with the row
+ *   { sigma_s, alpha_s, k_x, k0f, k0, k1 }: columns 0 and 1 as above (s: the timestep the iteration denoises from), and
+ *   x0   = (x - c0*eps) / c1
+ *   prev = k_x*x + k0f*x0                    first order: the first iteration a session runs, and every row with k1 == 0
+ *   prev = k_x*x + k0*x0 + k1*x0_prev        second order; x0_prev: the x0 of the iteration before
+ * (spdm_solver_step below is that update).  The first installation of such a schedule allocates two (max_batch,H,D) buffers
+ * and a device word in the handle; a handle that never sees one allocates nothing for it.
+ * A sampling session always starts first order: spdm_sample_begin discards the history.  Within a session
+ * spdm_sample_run(b, e) continues it when the last iteration the session completed was b - 1 -- so run(0, k); run(k, n) equals
+ * run(0, n) bit for bit -- and starts first order at b otherwise.  A loop suffix run from a caller's iterate (spdm_sample_begin,
+ * spdm_sample_run(i0, n)) therefore begins with a first-order step and is NOT the tail of the whole loop from that iterate, as
+ * it is for SPDM_DDPM / SPDM_DDIM. */
 int  spdm_set_schedule_tables(spdm_handle* h, int32_t kind, int32_t n_steps,
                               const int32_t* h_timesteps, const float* h_coef);
 
@@ -647,6 +660,45 @@ typedef struct {
     float* d_noise;
 } spdm_policy_warm_start_args;
 int  spdm_policy_warm_start(int32_t device, const spdm_policy_warm_start_args* a, void* stream);
+
+/* spdm_solver_step is one DPM-Solver++ (2M) update (Lu et al. 2022, Algorithm 2: data prediction, multistep, midpoint) on the
+ * caller's buffers: the launch the SPDM_DPMPP_2M sampling loop makes after each noise prediction.  Stateless,
+ * ONE kernel launch on `stream` behind two stream-ordered 4-byte fills of d_words (NULL: the null stream, and the call
+ * synchronises), one thread per element, no atomics, no host synchronisation otherwise.
+ *   B, H, D: trajectories, rows, columns;  inp_h, inpaint_per_sample, d_inpaint: as spdm_sample ((B,inp_h,D) or (inp_h,D));
+ *   n_steps: rows of d_coef;  step: the loop iteration, 0 <= step < n_steps;  first: the iteration that runs first order
+ *     whatever its row says (the first one after a start: x0_prev holds nothing yet), or -1;
+ *   d_eps (B,H,D): the predicted noise;  d_x (B,H,D): the iterate, updated in place;  d_x0_prev (B,H,D): read on a
+ *     second-order step, always written with this step's x0 (before in-painting);
+ *   d_coef [n_steps][6] DEVICE: rows { sigma_s, alpha_s, k_x, k0f, k0, k1 } (spdm_set_schedule_tables);
+ *   d_history NULL or (n_steps+1,B,H,D): row step + 1 receives the new iterate;
+ *   d_words DEVICE int32[3]: the entry writes {step, first}; word 2 is set to 1 when a new iterate is not finite and is
+ *     otherwise left as it is (the caller clears it).
+ * Per element, every float32 operation rounded on its own (no FMA), c = d_coef[step]:
+ *   1. x0 = (x - c0 eps) / c1;   2. acc = c2 x;
+ *   3. first order (step == first, or c5 == 0): acc = acc + c3 x0;  second order: acc = acc + c4 x0, then acc = acc + c5 x0_prev;
+ *   4. x0_prev <- x0;  rows h < inp_h of the iterate are d_inpaint's, exactly;  x <- the result.
+ * SPDM_ERR_INVALID, before the GPU is touched: NULL args; B, H, D or n_steps < 1; B x H x D beyond 31 bits; inp_h outside
+ * [0, H]; d_inpaint NULL with inp_h > 0 (or set with inp_h == 0); inpaint_per_sample not 0 or 1; step outside [0, n_steps);
+ * first outside [-1, n_steps); a NULL d_eps, d_x, d_x0_prev, d_coef or d_words. */
+typedef struct {
+    int32_t B;
+    int32_t H;
+    int32_t D;
+    int32_t inp_h;
+    int32_t inpaint_per_sample;
+    int32_t n_steps;
+    int32_t step;
+    int32_t first;
+    const float* d_eps;
+    float* d_x;
+    float* d_x0_prev;
+    const float* d_coef;
+    const float* d_inpaint;
+    float* d_history;
+    int32_t* d_words;
+} spdm_solver_step_args;
+int  spdm_solver_step(int32_t device, const spdm_solver_step_args* a, void* stream);
 
 /* The per-sample terms of a validation pass's loss in ONE launch (train_metrics.hip).  Replaces: nn.MSELoss
  * of the reference's validation_step (models/diffusion_ddpm.py:175-214, :49) as Lightning averages it over an epoch, weighted by

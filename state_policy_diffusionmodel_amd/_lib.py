@@ -12,7 +12,7 @@ from .weights import TensorIndex
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPDM_LIB") or os.path.join(HERE, "libspdm_hip.so")     # (SPDM_LIB: A/B builds during kernel tuning)
 
-SPDM_DDPM, SPDM_DDIM = 0, 1
+SPDM_DDPM, SPDM_DDIM, SPDM_DPMPP_2M = 0, 1, 2
 SPDM_FLAG_DEBUG_KEEP = 1
 SPDM_FLAG_EXACT_FP32 = 2
 SPDM_FLAG_SIMPLE_UNET = 4
@@ -168,6 +168,12 @@ class SpdmPolicyWarmStartArgs(ctypes.Structure):
                                          "d_noise")])
 
 
+class SpdmSolverStepArgs(ctypes.Structure):
+    """spdm_solver_step_args (include/spdm.h)."""
+    _fields_ = ([(n, c_int32) for n in ("B", "H", "D", "inp_h", "inpaint_per_sample", "n_steps", "step", "first")] +
+                [(n, c_void_p) for n in ("d_eps", "d_x", "d_x0_prev", "d_coef", "d_inpaint", "d_history", "d_words")])
+
+
 class SpdmLossTermsArgs(ctypes.Structure):
     """spdm_loss_terms_args (include/spdm.h)."""
     _fields_ = ([(n, c_int32) for n in ("B", "H", "D", "reserved")] + [("d_eps", c_void_p), ("d_noise", c_void_p)] +
@@ -211,6 +217,7 @@ SYMBOLS = {
     "spdm_policy_window": (c_int32, [c_int32, POINTER(SpdmPolicyWindowArgs), c_void_p]),
     "spdm_policy_unnormalize": (c_int32, [c_int32, POINTER(SpdmPolicyUnnormalizeArgs), c_void_p]),
     "spdm_policy_warm_start": (c_int32, [c_int32, POINTER(SpdmPolicyWarmStartArgs), c_void_p]),
+    "spdm_solver_step": (c_int32, [c_int32, POINTER(SpdmSolverStepArgs), c_void_p]),
     "spdm_loss_terms": (c_int32, [c_int32, POINTER(SpdmLossTermsArgs), c_void_p]),
     "spdm_train_set_time_scale": (c_int32, [c_void_p, c_void_p, c_int32]),
     "spdm_sample_begin": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,

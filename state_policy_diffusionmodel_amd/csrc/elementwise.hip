@@ -700,6 +700,52 @@ hipError_t launch_out_step(const StepArgs& a, hipStream_t s) {
 }
 
 // -------------------------------------------------------------------------------------------------
+// DPM-Solver++ (2M) update (SPDM_DPMPP_2M, include/spdm.h spdm_solver_step): data prediction, multistep,
+// midpoint.  One thread per (b, h, d) element, no LDS, no atomics.  Table row {sigma_s, alpha_s, k_x, k0f, k0, k1}; the step is
+// first order where the loop counter equals *first_dev (the first step a session runs: there is no history term yet) or the row
+// has k1 == 0.  x0 goes to x0_prev on every step: the thread that writes an element has read it before.  Each operation is
+// rounded on its own (mul_rn / sub_rn / add_rn above), in the order x0; k_x x; + k x0; + k1 x0_prev.  In-painting, the
+// non-finite flag, history row i + 1 and the {inpaint, noise, history} pointer block are out_step_kernel's.
+__global__ __launch_bounds__(256) void solver_step_kernel(const SolverStepArgs a) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (size_t)a.B * a.H0 * a.D) return;
+    const int HD = a.H0 * a.D;
+    const int b = (int)(e / HD), he = (int)(e - (size_t)b * HD);
+    const int h0 = he / a.D, d = he - h0 * a.D;
+    const int i = *a.step_dev;
+    const float* c = a.coef + (size_t)i * 6;
+    const float eps = a.eps[e];
+    const float x = a.x[e];
+    const float* inpaint = a.inpaint;
+    float* history = a.history;
+    if (a.ptrs_dev != nullptr) {           // uniform (scalar) loads of the session's buffers
+        inpaint = static_cast<const float*>(a.ptrs_dev[0]);
+        history = const_cast<float*>(static_cast<const float*>(a.ptrs_dev[2]));
+    }
+    const float x0 = __fdiv_rn(sub_rn(x, mul_rn(c[0], eps)), c[1]);
+    float prev = mul_rn(c[2], x);
+    if (i == *a.first_dev || c[5] == 0.f) {
+        prev = add_rn(prev, mul_rn(c[3], x0));
+    } else {
+        prev = add_rn(prev, mul_rn(c[4], x0));
+        prev = add_rn(prev, mul_rn(c[5], a.x0_prev[e]));
+    }
+    a.x0_prev[e] = x0;
+    if (h0 < a.inp_h && inpaint != nullptr)
+        prev = inpaint[(a.inpaint_per_sample ? (size_t)b * a.inp_h * a.D : 0) + (size_t)h0 * a.D + d];
+    a.x[e] = prev;
+    if (!(fabsf(prev) <= 3.0e38f)) *a.flag_dev = 1;
+    if (history != nullptr) history[((size_t)(i + 1) * a.B + b) * HD + he] = prev;
+}
+
+hipError_t launch_solver_step(const SolverStepArgs& a, hipStream_t s) {
+    const size_t E = (size_t)a.B * a.H0 * a.D;
+    if (E == 0 || !a.eps || !a.x || !a.x0_prev || !a.coef || !a.step_dev || !a.first_dev || !a.flag_dev) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(solver_step_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// -------------------------------------------------------------------------------------------------
 // Split-K combine (kernels.h): dst = sum over ks (ascending: deterministic) of the partial slabs a split-K implicit-GEMM
 // launch left, plus the GroupNorm(1,C) partial sums of dst -- the epilogue the GEMM itself could not run on partial
 // sums.  One workgroup = `rows` consecutive rows of ONE sample x all N channels (a contiguous run of rows * N floats);

@@ -303,6 +303,22 @@ struct StepArgs {
 };
 hipError_t launch_out_step(const StepArgs& a, hipStream_t s);
 
+// the DPM-Solver++ (2M) update on a ready eps (elementwise.hip solver_step_kernel; spdm_solver_step and the SPDM_DPMPP_2M loop)
+struct SolverStepArgs {
+    const float* eps;             // (B, H0, D)
+    float* x;                     // (B, H0, D) current iterate, updated in place
+    float* x0_prev;               // (B, H0, D) the previous step's predicted x0: read on second-order steps, always written
+    const float* coef;            // device [n_steps][6] = {sigma_s, alpha_s, k_x, k0f, k0, k1}
+    const int* step_dev;          // device scalar: loop iteration
+    const int* first_dev;         // device scalar: the iteration that runs first order whatever its row says (-1: none)
+    int* flag_dev;                // as StepArgs
+    const float* inpaint; int inp_h; int inpaint_per_sample;
+    float* history;
+    const void* const* ptrs_dev;  // as StepArgs ({inpaint, noise, history}; the noise entry is not read)
+    int B, H0, D;
+};
+hipError_t launch_solver_step(const SolverStepArgs& a, hipStream_t s);
+
 // train.hip: the training-loss gradient of UNet_Film_noAttention (spdm_train_loss_grad).  Channels-last [B][HW][C] throughout.
 // weight gradient of a 3x3 (taps 9), 3x1 (taps 3, W == 1) or 1x1 / Linear (taps 1) layer: dst = sum_m dy[m][co] x[shift(m)][ci]
 // on fp32 MFMA, rows split into partial slabs (budget_floats of `partial`) added in a fixed order; conv9: (Co, Ci, 3, 3) torch

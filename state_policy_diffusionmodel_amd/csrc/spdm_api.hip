@@ -264,6 +264,10 @@ struct spdm_handle {
     std::vector<int> timesteps;
     int* d_timesteps = nullptr;
     float* d_coef = nullptr;
+    // SPDM_DPMPP_2M only, allocated when such a schedule is first installed (install_schedule)
+    float* d_x0_prev = nullptr;           // [max_batch][H][D] the previous step's predicted x0 (solver_step_kernel)
+    float* d_solver_eps = nullptr;        // [max_batch][H][D] eps of the step on routes where sa6's epilogue has not produced it
+    int* d_first = nullptr;               // the iteration the running spdm_sample_run starts at, or -1 when it continues the history
     // persistent per-call state (sized for max_batch)
     int* d_t = nullptr;                   // [max_batch] timestep(s) of the current evaluation
     int* d_step = nullptr;                // [0] loop iteration, [2] non-finite flag (set by out_step_kernel)
@@ -281,6 +285,7 @@ struct spdm_handle {
     float* s_history = nullptr;
     unsigned long long s_seed = 0, s_offset = 0;
     bool session = false;
+    int s_last_step = -2;                 // the last iteration this session completed (-2: none); SPDM_DPMPP_2M's history is its x0
     // arena
     Arena arena;
     size_t persistent_bytes = 0;
@@ -1224,6 +1229,12 @@ static int install_schedule(spdm_handle* h, int kind, int n, const int* ts, cons
         SPDM_TRY(dev_alloc(h, (void**)&h->d_timesteps, sizeof(int) * n));
         SPDM_TRY(dev_alloc(h, (void**)&h->d_coef, sizeof(float) * 6 * n));
     }
+    if (kind == SPDM_DPMPP_2M && !h->d_x0_prev) {
+        const size_t nx = (size_t)h->cfg.max_batch * h->cfg.horizon * h->cfg.state_dim;
+        SPDM_TRY(dev_alloc(h, (void**)&h->d_x0_prev, sizeof(float) * nx));
+        SPDM_TRY(dev_alloc(h, (void**)&h->d_solver_eps, sizeof(float) * nx));
+        SPDM_TRY(dev_alloc(h, (void**)&h->d_first, sizeof(int)));
+    }
     HIP_TRY(hipMemcpy(h->d_timesteps, ts, sizeof(int) * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->d_coef, coef, sizeof(float) * 6 * n, hipMemcpyHostToDevice));
     h->timesteps.assign(ts, ts + n);
@@ -1244,7 +1255,7 @@ extern "C" int spdm_set_schedule(spdm_handle* h, int32_t kind, int32_t T, int32_
 
 extern "C" int spdm_set_schedule_tables(spdm_handle* h, int32_t kind, int32_t n, const int32_t* ts, const float* coef) {
     if (!h || !ts || !coef || n < 1) return fail(SPDM_ERR_INVALID, "bad argument");
-    if (kind != SPDM_DDPM && kind != SPDM_DDIM) return fail(SPDM_ERR_INVALID, "unknown scheduler kind %d", kind);
+    if (kind != SPDM_DDPM && kind != SPDM_DDIM && kind != SPDM_DPMPP_2M) return fail(SPDM_ERR_INVALID, "unknown scheduler kind %d", kind);
     return install_schedule(h, kind, n, ts, coef);
 }
 
@@ -2024,6 +2035,7 @@ extern "C" int spdm_sample_begin(spdm_handle* h, int32_t B, const float* d_cond,
         HIP_TRY(hipMemsetAsync(h->d_step + 2, 0, sizeof(int), s));
     }
     h->session = true;
+    h->s_last_step = -2;         // SPDM_DPMPP_2M: nothing of an earlier session's x0 is read
     if (!stream) HIP_TRY(hipStreamSynchronize(s));
     return SPDM_OK;
 }
@@ -2038,6 +2050,22 @@ static int enqueue_step(spdm_handle* h, int i, hipStream_t s) {
     Tensor feat;
     SPDM_TRY(plan_net(c, h->d_x, h->have_film, &feat));
     StepArgs a = step_args(h, h->sB, feat, c.eps_ready);
+    if (h->sched_kind == SPDM_DPMPP_2M) {
+        // the two-history-term update is a launch of its own: in out_step's place where sa6's epilogue has eps ready, after
+        // out_step in its eps-only mode elsewhere
+        SolverStepArgs v{};
+        v.eps = a.eps_in;
+        if (!c.eps_ready) {
+            a.eps_out = h->d_solver_eps;
+            HIP_TRY(launch_out_step(a, s));
+            v.eps = h->d_solver_eps;
+        }
+        v.x = h->d_x; v.x0_prev = h->d_x0_prev; v.coef = h->d_coef; v.step_dev = h->d_step; v.first_dev = h->d_first;
+        v.flag_dev = h->d_step + 2; v.inp_h = h->s_inp_h; v.inpaint_per_sample = h->s_inp_per_sample; v.ptrs_dev = h->d_ptrs;
+        v.B = h->sB; v.H0 = h->cfg.horizon; v.D = h->cfg.state_dim;
+        HIP_TRY(launch_solver_step(v, s));
+        return SPDM_OK;
+    }
     HIP_TRY(launch_out_step(a, s));
     return SPDM_OK;
 }
@@ -2084,6 +2112,13 @@ extern "C" int spdm_sample_run(spdm_handle* h, int32_t step_begin, int32_t step_
         if (!h->gstream && hipStreamCreate(&h->gstream) != hipSuccess) { (void)hipGetLastError(); h->gstream = nullptr; use_graph = false; }
         if (use_graph) s = h->gstream;
     }
+    if (h->sched_kind == SPDM_DPMPP_2M && step_begin < step_end) {
+        // the first step of this range is first order unless the session has just completed the step before it: a device
+        // word, written in stream order ahead of the launches, so that the captured step does not depend on the range
+        const int first = (step_begin > 0 && h->s_last_step == step_begin - 1) ? -1 : step_begin;
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)h->d_first, first, 1, s));
+        h->s_last_step = -2;     // (until every launch of the range has been enqueued)
+    }
     int i = step_begin;
     if (use_graph) {
         SPDM_TRY(enqueue_step(h, i, s));         // first step: explicit index; also makes sure every kernel has been launched once
@@ -2100,6 +2135,7 @@ extern "C" int spdm_sample_run(spdm_handle* h, int32_t step_begin, int32_t step_
             for (; i < step_end; ++i) HIP_TRY(hipGraphLaunch(h->step_exec, s));
     }
     for (; i < step_end; ++i) SPDM_TRY(enqueue_step(h, i, s));
+    if (step_begin < step_end) h->s_last_step = step_end - 1;
     if (!stream) HIP_TRY(hipStreamSynchronize(s));
     return SPDM_OK;
 }
@@ -3090,6 +3126,36 @@ extern "C" int spdm_policy_warm_start(int32_t device, const spdm_policy_warm_sta
     k.inpaint = a->d_inpaint; k.noise_in = a->d_noise_in; k.x = a->d_x; k.guess = a->d_guess; k.noise = a->d_noise;
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(launch_policy_warm_start(k, (hipStream_t)stream));
+    if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));
+    return SPDM_OK;
+}
+
+// One DPM-Solver++ (2M) update on the caller's buffers (include/spdm.h, elementwise.hip): the launch the SPDM_DPMPP_2M loop
+// makes after every noise prediction.  Stateless.
+extern "C" int spdm_solver_step(int32_t device, const spdm_solver_step_args* a, void* stream) {
+    if (!a) return fail(SPDM_ERR_INVALID, "solver_step: null argument");
+    if (a->B < 1 || a->H < 1 || a->D < 1 || a->n_steps < 1)
+        return fail(SPDM_ERR_INVALID, "solver_step: B, H, D, n_steps = %d, %d, %d, %d must all be >= 1", a->B, a->H, a->D, a->n_steps);
+    if ((long long)a->H * a->D > 0x7fffffffLL || (long long)a->B * a->H * a->D > 0x7fffffffLL)
+        return fail(SPDM_ERR_INVALID, "solver_step: B x H x D does not fit 31 bits");
+    if (a->inp_h < 0 || a->inp_h > a->H) return fail(SPDM_ERR_INVALID, "solver_step: inp_h = %d outside [0, H = %d]", a->inp_h, a->H);
+    if ((a->d_inpaint != nullptr) != (a->inp_h > 0))
+        return fail(SPDM_ERR_INVALID, "solver_step: d_inpaint must be NULL exactly when inp_h == 0 (inp_h = %d)", a->inp_h);
+    if (a->inpaint_per_sample != 0 && a->inpaint_per_sample != 1)
+        return fail(SPDM_ERR_INVALID, "solver_step: inpaint_per_sample = %d must be 0 or 1", a->inpaint_per_sample);
+    if (a->step < 0 || a->step >= a->n_steps) return fail(SPDM_ERR_INVALID, "solver_step: step %d outside [0, n_steps = %d)", a->step, a->n_steps);
+    if (a->first < -1 || a->first >= a->n_steps) return fail(SPDM_ERR_INVALID, "solver_step: first = %d outside [-1, n_steps = %d)", a->first, a->n_steps);
+    if (!a->d_eps || !a->d_x || !a->d_x0_prev || !a->d_coef || !a->d_words) return fail(SPDM_ERR_INVALID, "solver_step: null pointer");
+    SolverStepArgs k{};
+    k.eps = a->d_eps; k.x = a->d_x; k.x0_prev = a->d_x0_prev; k.coef = a->d_coef;
+    k.step_dev = a->d_words; k.first_dev = a->d_words + 1; k.flag_dev = a->d_words + 2;
+    k.inpaint = a->d_inpaint; k.inp_h = a->inp_h; k.inpaint_per_sample = a->inpaint_per_sample; k.history = a->d_history;
+    k.B = a->B; k.H0 = a->H; k.D = a->D;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)a->d_words, a->step, 1, s));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(a->d_words + 1), a->first, 1, s));
+    HIP_TRY(launch_solver_step(k, s));
     if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));
     return SPDM_OK;
 }

@@ -40,7 +40,7 @@ import numpy as np
 import torch
 
 from .engine import SpdmEngine
-from .schedulers import DDIMScheduler, DDPMScheduler, _LinearBetaScheduler
+from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, _LinearBetaScheduler
 from .weights import is_simple_model, pack_state_dict, random_state_dict, state_dict_to_numpy
 
 
@@ -59,11 +59,18 @@ def _as_spec(sched) -> _LinearBetaScheduler:
               beta_schedule=getattr(cfg, "beta_schedule", "linear"),
               clip_sample=bool(getattr(cfg, "clip_sample", False)),
               prediction_type=getattr(cfg, "prediction_type", "epsilon"))
+    if "DPMSolverMultistep" in name:
+        if getattr(cfg, "use_karras_sigmas", False) or getattr(cfg, "trained_betas", None) is not None:
+            raise NotImplementedError("DPMSolverMultistepScheduler: use_karras_sigmas and trained_betas are not supported")
+        del kw["clip_sample"]
+        opts = {k: getattr(cfg, k) for k in ("solver_order", "algorithm_type", "solver_type", "lower_order_final", "euler_at_final",
+                                             "thresholding") if hasattr(cfg, k)}
+        return DPMSolverMultistepScheduler(**kw, **opts)
     if "DDIM" in name:
         return DDIMScheduler(**kw)
     if "DDPM" in name:
         return DDPMScheduler(**kw)
-    raise TypeError(f"unsupported scheduler class {name} (DDPM / DDIM only)")
+    raise TypeError(f"unsupported scheduler class {name} (DDPM / DDIM / DPMSolverMultistep only)")
 
 
 def _index_of(idx):
@@ -330,7 +337,9 @@ class Diffusion_DDPM:
 
         ``start_step = i0 > 0`` runs a suffix of the loop: ``x_T``, then required, is the iterate the loop
         has after ``i0`` of its ``noise_steps`` iterations, and only iterations ``[i0, noise_steps)`` run -- bit for bit the
-        tail of the whole loop from that iterate.  Not available with a history option or ``sharded=True``."""
+        tail of the whole loop from that iterate under DDPM / DDIM.  Under ``DPMSolverMultistepScheduler`` a suffix is a new
+        session and begins with a first-order step (no previous x_0 exists), so it is NOT the whole loop's tail (DESIGN.md
+        8.19).  Not available with a history option or ``sharded=True``."""
         from .distributed import ShardedSampler, shard_bounds, world_and_rank
         if isinstance(start_step, bool) or not isinstance(start_step, (int, np.integer)) or not 0 <= start_step < int(self.noise_steps):
             raise ValueError(f"start_step = {start_step!r} must be an integer in [0, noise_steps = {self.noise_steps})")
@@ -748,10 +757,12 @@ class Diffusion_DDIM(Diffusion_DDPM):
 
 
 def load_model(model_name: str, checkpoint_path=None, hparams_path=None, num_of_ddim_steps: int = 100, *,
-               state_dict=None, **hparams):
+               state_dict=None, solver_steps: Optional[int] = None, **hparams):
     """generate.py:23-37: build the sampler from a checkpoint + hparams.yaml (same positional signature as the
     reference) -- or from an in-memory ``state_dict`` / random init when no checkpoint is given -- and, for DDIM,
-    overwrite scheduler and noise_steps exactly as the reference's loader does."""
+    overwrite scheduler and noise_steps exactly as the reference's loader does.  ``solver_steps = N`` then assigns
+    ``DPMSolverMultistepScheduler(num_train_timesteps=model.noise_steps)`` and ``noise_steps = N`` in the same way: the
+    loaded model samples with DPM-Solver++ (2M) in N steps."""
     if model_name not in ("DDPM", "DDIM"):
         raise ValueError("model_name must be 'DDPM' or 'DDIM'")
     cls = Diffusion_DDPM if model_name == "DDPM" else Diffusion_DDIM
@@ -765,5 +776,8 @@ def load_model(model_name: str, checkpoint_path=None, hparams_path=None, num_of_
         model.noise_scheduler = DDIMScheduler(num_train_timesteps=num_of_ddim_steps, beta_schedule="linear",
                                               clip_sample=False, prediction_type="epsilon")
         model.noise_steps = num_of_ddim_steps
+    if solver_steps is not None:
+        model.noise_scheduler = DPMSolverMultistepScheduler(num_train_timesteps=model.noise_steps)
+        model.noise_steps = int(solver_steps)
     model.eval()
     return model

@@ -30,6 +30,41 @@ def _ptr(t: Optional[torch.Tensor]):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+def solver_step(eps: torch.Tensor, x: torch.Tensor, x0_prev: torch.Tensor, coef: torch.Tensor, step: int, first: int,
+                words: torch.Tensor, inpaint: Optional[torch.Tensor] = None, history: Optional[torch.Tensor] = None) -> None:
+    """One DPM-Solver++ (2M) update in place on the caller's device tensors (``spdm_solver_step``, include/spdm.h): the launch
+    the library's own loop makes, for callers that drive the loop themselves.  ``eps``, ``x``, ``x0_prev`` (B,H,D) or
+    (B,1,H,D) float32; ``coef`` (n,6) float32, a scheduler's ``coefficient_table()`` on the device; ``words`` int32[3]
+    ({step, first, non-finite flag}: the flag is only ever set); ``inpaint`` (inp_h,D) or (B,inp_h,D); ``history``
+    (n+1,B,H,D), row ``step + 1`` receives the new iterate.  ``first``: the iteration that has no history term, or -1."""
+    B, H, D = x.shape[0], x.shape[-2], x.shape[-1]
+    given = [("eps", eps), ("x", x), ("x0_prev", x0_prev), ("coef", coef)] + ([("inpaint", inpaint)] if inpaint is not None else [])
+    given += [("history", history)] if history is not None else []
+    for name, t in given:
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.device != x.device:
+            raise ValueError(f"{name} must be a contiguous float32 tensor on {x.device}")
+    if eps.numel() != x.numel() or x0_prev.numel() != x.numel() or x.numel() != B * H * D:
+        raise ValueError("eps, x and x0_prev must all be (B,H,D) or (B,1,H,D)")
+    if coef.dim() != 2 or coef.shape[1] != 6:
+        raise ValueError(f"coef must be (n,6), got {tuple(coef.shape)}")
+    if not words.is_cuda or words.dtype != torch.int32 or words.numel() < 3 or not words.is_contiguous() or words.device != x.device:
+        raise ValueError("words must be a contiguous int32 device tensor of 3 elements")
+    n, inp_h, per_sample = int(coef.shape[0]), 0, 0
+    if inpaint is not None:
+        inp_h = int(inpaint.shape[-2])
+        per_sample = int(inpaint.numel() == B * inp_h * D and B > 1)
+        if inpaint.shape[-1] != D or inpaint.numel() not in (inp_h * D, B * inp_h * D):
+            raise ValueError(f"inpaint must be (inp_h,{D}) or ({B},inp_h,{D}), got {tuple(inpaint.shape)}")
+    if history is not None and history.numel() != (n + 1) * B * H * D:
+        raise ValueError(f"history must be ({n + 1},{B},{H},{D})")
+    a = _lib.SpdmSolverStepArgs(B=B, H=H, D=D, inp_h=inp_h, inpaint_per_sample=per_sample, n_steps=n, step=int(step),
+                                first=int(first), d_eps=eps.data_ptr(), d_x=x.data_ptr(), d_x0_prev=x0_prev.data_ptr(),
+                                d_coef=coef.data_ptr(), d_inpaint=inpaint.data_ptr() if inp_h > 0 else None,
+                                d_history=history.data_ptr() if history is not None else None, d_words=words.data_ptr())
+    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    _lib.check(_lib.load().spdm_solver_step(x.device.index, ctypes.byref(a), stream), "spdm_solver_step")
+
+
 class SpdmEngine:
     def __init__(self, horizon: int, state_dim: int, cond_dim: int, max_batch: int, device: int = 0,
                  attention: bool = True, time_dim: int = 256, num_train_timesteps: int = 1000,

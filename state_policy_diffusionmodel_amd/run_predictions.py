@@ -52,6 +52,7 @@ def parse_arguments(argv=None):
     p.add_argument("--stats", type=str, required=True, help="STATS.pkl of the training run")
     p.add_argument("--data", type=str, required=True, help="arrays.npz (or a zarr store, if zarr is installed)")
     p.add_argument("--ddim_steps", type=int, default=100)
+    p.add_argument("--solver_steps", type=int, default=None, metavar="N", help="sample with DPM-Solver++ (2M) in N steps instead of the --model_name schedule (default: off)")
     p.add_argument("--replan_every", type=int, default=50, help="plan on every n-th row of an episode (run_predictions.py:151)")
     p.add_argument("--seed", type=int, default=0, help="plan i samples with seed + i and its x_T from a generator seeded alike")
     p.add_argument("--warm_start", type=int, default=None, metavar="K",
@@ -71,7 +72,8 @@ def main(argv=None) -> dict:
     from .diffusion import load_model
     from .evaluate import load_arrays, load_stats
     from .policy import ClosedLoopPolicy
-    model = load_model(args.model_name, args.checkpoint, args.hparams, num_of_ddim_steps=args.ddim_steps, max_batch=1)
+    model = load_model(args.model_name, args.checkpoint, args.hparams, num_of_ddim_steps=args.ddim_steps, max_batch=1,
+                       solver_steps=args.solver_steps)
     stats = load_stats(args.stats)
     arrays = load_arrays(args.data)
     storage = choose_image_storage(arrays["img"])
@@ -118,6 +120,8 @@ def main(argv=None) -> dict:
     mean, std = per_step(plans)
     report = {"model_name": args.model_name, "obs_horizon": obs_h, "pred_horizon": P, "step_size": s, "replan_every": args.replan_every,
               "seed": args.seed, "image_storage": storage, "plans": plans, "left_out": left_out, "mean_error": mean, "std_error": std}
+    if args.solver_steps is not None:
+        report["solver"] = {"name": "dpmsolver++2m", "steps": args.solver_steps}
     if args.warm_start is not None:
         report["warm_start"] = args.warm_start
         for name, chosen in (("cold", [p for p in plans if not p["warm"]]), ("warm", [p for p in plans if p["warm"]])):
