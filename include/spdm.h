@@ -1224,6 +1224,84 @@ typedef struct {
 
 int  spdm_op_frame(spdm_op_frame_args* args);
 
+/* Op-level test hook: ONE launch of a forward SelfAttention kernel (launch_* of csrc/sa_fused.hip, sa_tail.hip, attention.hip)
+ * exactly as the plan's attention block calls it, on caller-supplied tensors, synchronously on the current device.  Not on the
+ * product path.  The hook validates, lays the block's weights out with the weight loader's own code (as spdm_op_gemm does: the
+ * hi / lo fp16 halves in sa_fused.hip's fragment order for C = 64, the fragment-order split copy for C = 128 / 256), uploads the
+ * host timesteps, builds FilmSpec / SaCrop, calls the launcher and synchronises -- nothing else; no arithmetic of its own.
+ * heads = 4 as in the product; d = C / 4.
+ *   d_buf[i] / cap[i]   DEVICE float arrays and capacities in floats, as for spdm_op_train (a buffer an op does not take: NULL)
+ *   h_w[i]              HOST weights in torch layout: {in_proj (3C, C), out_proj (C, C), ff_self.1 (C, C), ff_self.3 (C, C)};
+ *                       exactly those the op reads (below), the others NULL.  A weight outside the split format's range is
+ *                       refused as the plan refuses it (its block runs on the GEMM chain): SPDM_ERR_INVALID, nothing launched.
+ *   d_vec[i] / vec_cap[i]   DEVICE vectors: {ln gain [C], ln bias [C], in_proj bias [3C], out_proj bias [C], ff_self.0 gain [C],
+ *                       ff_self.0 bias [C], ff_self.1 bias [C], ff_self.3 bias [C]}; exactly those the op reads
+ *   d_ab / ab_cap       optional [B 2C]: the block input is A x + B per (sample, channel), rows [A (C) | B (C)] as FILM_COEF of
+ *                       spdm_op_stream writes them
+ *   film_on             1: the kernel evaluates those coefficients itself (FilmSpec), from what spdm_op_stream's FILM_COEF
+ *                       takes: gn (a pending GroupNorm(1, C) of the raw tensor, HW = L), d_temb [T C] with h_t, t_count (1 or B)
+ *                       HOST timesteps in [0, T) (without temb: h_t NULL, t_count = T = 1), d_film [B 2C] or NULL.
+ *                       d_ab and film_on are mutually exclusive; film_on 0: every FilmSpec field 0 / NULL.  CORE takes neither.
+ *   d_outc_w, outc_b    FUSED64 with outc: outc's weight [64] (DEVICE) and bias
+ *   info[]              filled by the hook (-1 where unused): {kernel (0 sa_fused64, 1 sa_fused64 on two workgroups per sample,
+ *                       2 sa_crop64, 3 sa_qkv, 4 sa_head, 5 sa_tail, 6 attention_ds, 7 attention (VALU), 8 attention_mfma), waves
+ *                       per workgroup, workgroups, wlds (sa_fused64: weights staged in LDS, persistent workgroups), qw (sa_crop64:
+ *                       queries per wave)} -- recorded by the launcher that ran
+ * Row order: every tensor is channels-last with row b L + token (rows = B L); qkv rows are [q (C) | k (C) | v (C)], each head h
+ * in channels [h d, (h + 1) d); the q that QKV writes and CORE reads does NOT carry 1 / sqrt d (the core applies it).
+ * SPDM_ERR_INVALID, before the GPU is touched: NULL args, an unknown op, a dimension outside its range below, a flag that is not
+ * 0 / 1, a capacity below the extent, a buffer, weight or vector the op does not take, a timestep outside [0, T), a pending
+ * GroupNorm with fewer slots than the consumer reads, an extent beyond 31 bits, everything the launcher itself refuses (asked of
+ * the launcher, which decides before it touches the device) and what a launcher accepts but its kernel cannot run.
+ * SPDM_ERR_HIP: the launch or the final synchronise failed.  Deterministic: every op gives the same bits on the same inputs.
+ *
+ * op, dim[] (all others 0), buffers with their extents:
+ *  FUSED64  dim {B, L, no_wlds, crop, H0, D, Wp, lh, lw, outc}; C = 64, 1 <= L <= 512 (with d_ab / film_on: L <= 256).  no_wlds 1 =
+ *           SPDM_SA_NO_WLDS.  crop 0: H0 = D = Wp = lh = lw = outc = 0.  crop 1: the tokens (lh + i) Wp + lw + j, i < H0, j < D only;
+ *           L <= 256, Q = H0 D with 1 <= Q < L and Q <= 32 min(4, ceil(L / 32)), lw + D <= Wp, (lh + H0) Wp <= L.
+ *           buf {x [B L 64], out [B L 64] out (crop: only the rows of the Q tokens are written; NULL with outc),
+ *           eps [B H0 D] out (outc 1: eps = outc_w . out + outc_b; else NULL)}; h_w all four; d_vec all eight.
+ *  QKV      dim {C, B, L}; C 128 or 256.  buf {x [B L C], qkv [B L 3C] out}; h_w {in_proj}; d_vec {0, 1, 2}.  film_on: the
+ *           coefficient rows of the samples a tile touches must fit 24 KiB ((ceil((TM + L - 2) / L)) + 1) 2C floats, TM = 8192 / C).
+ *  HEAD     dim {C, B, L}; C 128 or 256, L divides 8192 / C.  buf {x [B L C], att [B L C] out}; h_w {in_proj}; d_vec {0, 1, 2}.
+ *  TAIL     dim {C, B, L}; C 128 or 256.  buf {att [B L C], x [B L C], out [B L C] out}; h_w {out_proj, ff_self.1, ff_self.3};
+ *           d_vec {3, 4, 5, 6, 7}.  d_ab / film_on as QKV (they finish x, the residual).
+ *  CORE     dim {B, L, C, valu}; C 64, 128 or 256; valu 1 = SPDM_ATTN_VALU.  launch_attention_auto: L >= 32 without valu runs
+ *           attention_mfma, everything else the VALU kernels; a shape beyond 160 KiB of LDS is refused.
+ *           buf {qkv [B L 3C], out [B L C] out}; no weights, no vectors. */
+enum { SPDM_OPA_FUSED64 = 0, SPDM_OPA_QKV, SPDM_OPA_HEAD, SPDM_OPA_TAIL, SPDM_OPA_CORE, SPDM_OPA_COUNT };
+#define SPDM_OP_SA_DIMS 10
+#define SPDM_OP_SA_BUFS 3
+#define SPDM_OP_SA_WEIGHTS 4
+#define SPDM_OP_SA_VECS 8
+typedef struct {
+    int32_t op;
+    int32_t reserved;
+    int64_t dim[SPDM_OP_SA_DIMS];
+    float* d_buf[SPDM_OP_SA_BUFS];
+    uint64_t cap[SPDM_OP_SA_BUFS];
+    const float* h_w[SPDM_OP_SA_WEIGHTS];
+    const float* d_vec[SPDM_OP_SA_VECS];
+    uint64_t vec_cap[SPDM_OP_SA_VECS];
+    const float* d_ab;
+    uint64_t ab_cap;
+    int32_t film_on;
+    int32_t t_count;
+    int64_t T;
+    spdm_op_stream_gn gn;
+    const float* d_temb;
+    uint64_t temb_cap;
+    const int32_t* h_t;
+    const float* d_film;
+    uint64_t film_cap;
+    const float* d_outc_w;
+    uint64_t outc_w_cap;
+    float outc_b;
+    int32_t info[5];
+} spdm_op_sa_args;
+
+int  spdm_op_sa(spdm_op_sa_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,22 @@ class SpdmOpFrameArgs(ctypes.Structure):
                 ("info", c_int32 * 4), ("reserved2", c_int32)]
 
 
+# spdm_op_sa op codes (include/spdm.h: SPDM_OPA_*), in enum order, and the kernels info[0] names
+OP_SA_OPS = ("fused64", "qkv", "head", "tail", "core")
+OP_SA_KERNELS = ("fused", "fused_pair", "crop", "qkv", "head", "tail", "core_ds", "core_valu", "core_mfma")
+OP_SA_DIMS, OP_SA_BUFS, OP_SA_WEIGHTS, OP_SA_VECS = 10, 3, 4, 8
+
+
+class SpdmOpSaArgs(ctypes.Structure):
+    """spdm_op_sa_args (include/spdm.h)."""
+    _fields_ = [("op", c_int32), ("reserved", c_int32), ("dim", c_int64 * OP_SA_DIMS), ("d_buf", c_void_p * OP_SA_BUFS),
+                ("cap", c_uint64 * OP_SA_BUFS), ("h_w", c_void_p * OP_SA_WEIGHTS), ("d_vec", c_void_p * OP_SA_VECS),
+                ("vec_cap", c_uint64 * OP_SA_VECS), ("d_ab", c_void_p), ("ab_cap", c_uint64), ("film_on", c_int32),
+                ("t_count", c_int32), ("T", c_int64), ("gn", SpdmOpStreamGn), ("d_temb", c_void_p), ("temb_cap", c_uint64),
+                ("h_t", c_void_p), ("d_film", c_void_p), ("film_cap", c_uint64), ("d_outc_w", c_void_p), ("outc_w_cap", c_uint64),
+                ("outc_b", c_float), ("info", c_int32 * 5)]
+
+
 class SpdmOptimSegment(ctypes.Structure):
     """spdm_optim_segment (include/spdm.h)."""
     _fields_ = [("d_param", c_void_p), ("d_grad", c_void_p), ("d_exp_avg", c_void_p), ("d_exp_avg_sq", c_void_p),
@@ -254,6 +270,7 @@ SYMBOLS = {
     "spdm_op_train": (c_int32, [POINTER(SpdmOpTrainArgs)]),
     "spdm_op_stream": (c_int32, [POINTER(SpdmOpStreamArgs)]),
     "spdm_op_frame": (c_int32, [POINTER(SpdmOpFrameArgs)]),
+    "spdm_op_sa": (c_int32, [POINTER(SpdmOpSaArgs)]),
     "spdm_debug_geometry": (c_int32, [c_int32] * 6 + [ctypes.c_uint32, POINTER(c_int32 * 10)]),
     "spdm_debug_whole_tiles": (c_int32, []),
     "spdm_debug_fused_upsample_launches": (c_int32, []),

@@ -176,7 +176,7 @@ __global__ __launch_bounds__(256) void attention_ds_kernel(const float* __restri
     }
 }
 
-hipError_t launch_attention(const float* qkv, float* out, int B, int L, int C, int heads, hipStream_t s) {
+hipError_t launch_attention(const float* qkv, float* out, int B, int L, int C, int heads, hipStream_t s, SaRoute* route) {
     if (B <= 0 || L <= 0 || heads <= 0 || C % heads != 0) return hipErrorInvalidValue;
     const int d = C / heads;
     const int npairs = B * heads;
@@ -188,6 +188,7 @@ hipError_t launch_attention(const float* qkv, float* out, int B, int L, int C, i
         const size_t lds = (size_t)2 * G * GS * sizeof(float);
         if (lds <= 64 * 1024) {
             const dim3 grid((npairs + G - 1) / G), block(256);
+            if (route) { route->kernel = SA_ROUTE_CORE_DS; route->waves = 4; route->grid = (int)grid.x; if (route->dry) return hipSuccess; }
             if (d == 64) hipLaunchKernelGGL((attention_ds_kernel<64, 4>), grid, block, lds, s, qkv, out, L, C, heads, G, GS, npairs);
             else hipLaunchKernelGGL((attention_ds_kernel<32, 4>), grid, block, lds, s, qkv, out, L, C, heads, G, GS, npairs);
             return hipGetLastError();
@@ -202,6 +203,8 @@ hipError_t launch_attention(const float* qkv, float* out, int B, int L, int C, i
     if (threads > 256) threads = 256;
     if (G > 1) threads = 64;
     const dim3 grid((npairs + G - 1) / G), block(threads);
+    if (d != 16 && d != 32 && d != 64) return hipErrorInvalidValue;
+    if (route) { route->kernel = SA_ROUTE_CORE_VALU; route->waves = threads / 64; route->grid = (int)grid.x; if (route->dry) return hipSuccess; }
 #define SPDM_ATT(DD)                                                                                          \
     {                                                                                                         \
         auto kern = attention_kernel<DD>;                                                                     \
@@ -422,32 +425,33 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(const float* __rest
 }
 
 template <int D>
-static hipError_t launch_attention_mfma(const float* qkv, float* out, int B, int L, int C, int heads, hipStream_t s) {
+static hipError_t launch_attention_mfma(const float* qkv, float* out, int B, int L, int C, int heads, hipStream_t s, SaRoute* route) {
     const int Lp = (L + 31) & ~31;
     constexpr int MO = (D + 31) / 32;
     const size_t lds = ((size_t)2 * Lp * (D + 8) + (size_t)2 * 32 * MO * (Lp + 8)) * sizeof(_Float16);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     auto kern = (L % 32 == 0) ? attention_mfma_kernel<D, true> : attention_mfma_kernel<D, false>;
-    if (lds > 64 * 1024)
-        if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return e;
     const int qblocks = (L + 127) / 128;
     const int waves = std::min(4, (L + 31) / 32);
+    if (route) { route->kernel = SA_ROUTE_CORE_MFMA; route->waves = waves; route->grid = B * heads * qblocks; if (route->dry) return hipSuccess; }
+    if (lds > 64 * 1024)
+        if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(B * heads * qblocks), dim3(64 * waves), lds, s, qkv, out, L, C, heads, qblocks);
     return hipGetLastError();
 }
 
-hipError_t launch_attention_auto(const float* qkv, float* out, int B, int L, int C, int heads, unsigned sw, hipStream_t s) {
+hipError_t launch_attention_auto(const float* qkv, float* out, int B, int L, int C, int heads, unsigned sw, hipStream_t s, SaRoute* route) {
     if (B <= 0 || L <= 0 || heads <= 0 || C % heads != 0 || C % 4 != 0) return hipErrorInvalidValue;
     const int d = C / heads;
     if (L >= 32 && !(sw & SW_ATTN_VALU)) {
         switch (d) {
-            case 16: return launch_attention_mfma<16>(qkv, out, B, L, C, heads, s);
-            case 32: return launch_attention_mfma<32>(qkv, out, B, L, C, heads, s);
-            case 64: return launch_attention_mfma<64>(qkv, out, B, L, C, heads, s);
+            case 16: return launch_attention_mfma<16>(qkv, out, B, L, C, heads, s, route);
+            case 32: return launch_attention_mfma<32>(qkv, out, B, L, C, heads, s, route);
+            case 64: return launch_attention_mfma<64>(qkv, out, B, L, C, heads, s, route);
             default: break;
         }
     }
-    return launch_attention(qkv, out, B, L, C, heads, s);
+    return launch_attention(qkv, out, B, L, C, heads, s, route);
 }
 
 }  // namespace spdm

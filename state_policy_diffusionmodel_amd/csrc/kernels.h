@@ -602,10 +602,18 @@ hipError_t launch_loss_terms(const LossTermsArgs& a, hipStream_t s);
 hipError_t launch_advance(int* step_dev, int* t_dev, const int* timesteps_dev, int n_steps, hipStream_t s);
 hipError_t launch_set_step(int* step_dev, int* t_dev, const int* timesteps_dev, int n_steps, int i, hipStream_t s);
 
+// What a forward SelfAttention launcher dispatched, recorded by the launcher itself when `route` is given (spdm_op_sa; null in
+// the plan).  dry != 0 on entry: the launcher checks, decides and records as for a launch, then returns before it touches the
+// device (the grid of sa_fused64's persistent walk, which asks the device for its CU count, then stays -1).
+enum { SA_ROUTE_FUSED = 0, SA_ROUTE_FUSED_PAIR, SA_ROUTE_CROP, SA_ROUTE_QKV, SA_ROUTE_HEAD, SA_ROUTE_TAIL, SA_ROUTE_CORE_DS,
+       SA_ROUTE_CORE_VALU, SA_ROUTE_CORE_MFMA };
+struct SaRoute { int dry; int kernel, waves, grid, wlds, qw; };      // waves per workgroup, workgroups; qw: queries per wave (crop)
+
 // ---- attention core (attention.hip): softmax(q k^T / sqrt d) v per (sample, head) -----------
 hipError_t launch_attention(const float* qkv /*[B*L][3C]*/, float* out /*[B*L][C]*/, int B, int L, int C,
-                            int heads, hipStream_t s);        // VALU kernel (small L)
-hipError_t launch_attention_auto(const float* qkv, float* out, int B, int L, int C, int heads, unsigned sw, hipStream_t s);  // MFMA kernel for L >= 32
+                            int heads, hipStream_t s, SaRoute* route = nullptr);        // VALU kernel (small L)
+hipError_t launch_attention_auto(const float* qkv, float* out, int B, int L, int C, int heads, unsigned sw, hipStream_t s,
+                                 SaRoute* route = nullptr);  // MFMA kernel for L >= 32
 
 // ---- fused SelfAttention block for the C = 64 levels (sa_fused.hip) -------------------------------------
 bool sa_fused_supported(int L, int C);
@@ -620,23 +628,26 @@ bool sa_crop_supported(int L, int C, int H0, int D);
 hipError_t launch_sa_fused64(const float* x, float* out, int B, int L, const float* ln1_g, const float* ln1_b,
                              const float* ln2_g, const float* ln2_b, const void* const w_hl[8], const float* bqkv,
                              const float* bo, const float* b1, const float* b2, const float* ab, unsigned sw, hipStream_t s,
-                             const FilmSpec* fs = nullptr, const SaCrop* crop = nullptr);
+                             const FilmSpec* fs = nullptr, const SaCrop* crop = nullptr, SaRoute* route = nullptr);
 
 // ---- row-wise tail of a C = 128 / 256 SelfAttention block (sa_tail.hip): out_proj + x -> LayerNorm -> ff1 -> GELU -> ff2 + av ----
 bool sa_tail_supported(int C, unsigned sw);
 hipError_t launch_sa_tail(int C, const float* o, const float* x, float* out, int rows, const float* wf_o, const float* wf_1,
                           const float* wf_2, const float* b_o, const float* b_1, const float* b_2, const float* ln_g,
-                          const float* ln_b, const float* ab, int L, hipStream_t s, const FilmSpec* fs = nullptr);
+                          const float* ln_b, const float* ab, int L, hipStream_t s, const FilmSpec* fs = nullptr,
+                          SaRoute* route = nullptr);
 // may the two kernels evaluate the FiLM coefficients themselves for samples of L rows?  (their LDS row per touched sample)
 bool sa_tail_film_local(int C, int L);
 // LayerNorm + in_proj + attention core in one kernel (att = softmax(q k^T / sqrt d) v per sample and head, heads concatenated):
 // blocks whose 8192 / C-row tile holds whole samples of L tokens
 bool sa_head_supported(int C, int L, unsigned sw);
 hipError_t launch_sa_head(int C, const float* x, float* att, int rows, const float* wf_in, const float* b_in, const float* ln_g,
-                          const float* ln_b, const float* ab, int L, hipStream_t s, const FilmSpec* fs = nullptr);
+                          const float* ln_b, const float* ab, int L, hipStream_t s, const FilmSpec* fs = nullptr,
+                          SaRoute* route = nullptr);
 // qkv = LayerNorm(x) W_in^T + b_in of the same blocks (LayerNorm from the row itself)
 hipError_t launch_sa_qkv(int C, const float* x, float* qkv, int rows, const float* wf_in, const float* b_in, const float* ln_g,
-                         const float* ln_b, const float* ab, int L, hipStream_t s, const FilmSpec* fs = nullptr);
+                         const float* ln_b, const float* ab, int L, hipStream_t s, const FilmSpec* fs = nullptr,
+                         SaRoute* route = nullptr);
 
 // ---- weight re-layout on the device (weight_layout.hip; spdm_api.hip's Recorder records the copies) ----------------------
 // One kernel-layout copy of a weight as a gather from the torch-layout blob: logical dense array [n0][n1][n2], element

@@ -851,19 +851,19 @@ bool sa_fused_supported(int L, int C) { return C == SA_C && L >= 1 && L <= 512; 
 
 static int sa_crop_waves(int L) { return std::min(4, (L + 31) / 32); }
 bool sa_crop_supported(int L, int C, int H0, int D) {
-    const int Q = H0 * D;
-    return C == SA_C && L >= 1 && L <= 256 && Q >= 1 && Q < L && Q <= 32 * sa_crop_waves(L);
+    const long long Q = (long long)H0 * D;                // (64-bit: two large factors must not wrap into the range)
+    return C == SA_C && L >= 1 && L <= 256 && H0 >= 1 && D >= 1 && Q < L && Q <= 32 * sa_crop_waves(L);
 }
 
 hipError_t launch_sa_fused64(const float* x, float* out, int B, int L, const float* ln1_g, const float* ln1_b,
                              const float* ln2_g, const float* ln2_b, const void* const w_hl[8], const float* bqkv,
                              const float* bo, const float* b1, const float* b2, const float* ab, unsigned sw, hipStream_t s,
-                             const FilmSpec* fs, const SaCrop* crop) {
+                             const FilmSpec* fs, const SaCrop* crop, SaRoute* route) {
     if (!sa_fused_supported(L, SA_C) || B <= 0) return hipErrorInvalidValue;
     if (crop) {
         const SaCrop& c = *crop;
-        if (!sa_crop_supported(L, SA_C, c.H0, c.D) || c.lh < 0 || c.lw < 0 || c.Wp < 1 || c.lw + c.D > c.Wp ||
-            (c.lh + c.H0) * c.Wp > L || (c.eps != nullptr && c.outc_w == nullptr) || (c.eps == nullptr && out == nullptr))
+        if (!sa_crop_supported(L, SA_C, c.H0, c.D) || c.lh < 0 || c.lw < 0 || c.Wp < 1 || (long long)c.lw + c.D > c.Wp ||
+            ((long long)c.lh + c.H0) * c.Wp > L || (c.eps != nullptr && c.outc_w == nullptr) || (c.eps == nullptr && out == nullptr))
             return hipErrorInvalidValue;
     }
     if (fs && (ab != nullptr || fs->C != SA_C)) return hipErrorInvalidValue;
@@ -887,6 +887,7 @@ hipError_t launch_sa_fused64(const float* x, float* out, int B, int L, const flo
         const bool full = (L % 32 == 0), outc = crop->eps != nullptr;
         void (*kern)(const SaFusedArgs) = full ? (outc ? sa_crop64_kernel<true, true> : sa_crop64_kernel<true, false>)
                                                : (outc ? sa_crop64_kernel<false, true> : sa_crop64_kernel<false, false>);
+        if (route) { route->kernel = SA_ROUTE_CROP; route->waves = nw; route->grid = B; route->wlds = 0; route->qw = a.qw; if (route->dry) return hipSuccess; }
         if (lds > 64 * 1024)
             if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return e;
         hipLaunchKernelGGL(kern, dim3(B), dim3(64 * nw), lds, s, a);
@@ -904,6 +905,11 @@ hipError_t launch_sa_fused64(const float* x, float* out, int B, int L, const flo
         pair ? (full ? sa_fused64_kernel<true, false, true> : sa_fused64_kernel<false, false, true>)
              : full ? (wlds ? sa_fused64_kernel<true, true, false> : sa_fused64_kernel<true, false, false>)
                     : (wlds ? sa_fused64_kernel<false, true, false> : sa_fused64_kernel<false, false, false>);
+    if (route) {
+        route->kernel = pair ? SA_ROUTE_FUSED_PAIR : SA_ROUTE_FUSED; route->waves = nwave; route->grid = wlds ? -1 : pair ? 2 * B : B;
+        route->wlds = wlds ? 1 : 0;
+        if (route->dry) return hipSuccess;
+    }
     if (lds > 64 * 1024)
         if (hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kern)); e != hipSuccess) return e;
     int grid = pair ? 2 * B : B;
@@ -915,6 +921,7 @@ hipError_t launch_sa_fused64(const float* x, float* out, int B, int L, const flo
             ncu = n;
         }
         grid = std::min(B, ncu);
+        if (route) route->grid = grid;
     }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nwave), lds, s, a);
     return hipGetLastError();

@@ -729,7 +729,7 @@ bool sa_tail_film_local(int C, int L) {
 
 hipError_t launch_sa_tail(int C, const float* o, const float* x, float* out, int rows, const float* wf_o, const float* wf_1,
                           const float* wf_2, const float* b_o, const float* b_1, const float* b_2, const float* ln_g,
-                          const float* ln_b, const float* ab, int L, hipStream_t s, const FilmSpec* fs) {
+                          const float* ln_b, const float* ab, int L, hipStream_t s, const FilmSpec* fs, SaRoute* route) {
     if (fs && (ab || L <= 0 || !sa_tail_film_local(C, L) || fs->C != C)) return hipErrorInvalidValue;
     if (rows <= 0 || (ab && L <= 0) || !o || !x || !out || !wf_o || !wf_1 || !wf_2 || !b_o || !b_1 || !b_2 || !ln_g || !ln_b)
         return hipErrorInvalidValue;
@@ -742,6 +742,7 @@ hipError_t launch_sa_tail(int C, const float* o, const float* x, float* out, int
     const int TM = 8192 / C;
     const size_t lds = (size_t)(C / 32) * TM * T_LDK * sizeof(float)           // 36.9 KB
                        + (fs ? (size_t)film_rows_cap(TM, L) * 2 * C * sizeof(float) : 0);
+    if (route) { route->kernel = SA_ROUTE_TAIL; route->waves = 4; route->grid = (rows + TM - 1) / TM; if (route->dry) return hipSuccess; }
     if (C == 128) hipLaunchKernelGGL(sa_tail_kernel<128>, dim3((rows + TM - 1) / TM), dim3(256), lds, s, a);
     else hipLaunchKernelGGL(sa_tail_kernel<256>, dim3((rows + TM - 1) / TM), dim3(256), lds, s, a);
     return hipGetLastError();
@@ -753,7 +754,7 @@ bool sa_head_supported(int C, int L, unsigned sw) {
 }
 
 hipError_t launch_sa_head(int C, const float* x, float* att, int rows, const float* wf_in, const float* b_in, const float* ln_g,
-                          const float* ln_b, const float* ab, int L, hipStream_t s, const FilmSpec* fs) {
+                          const float* ln_b, const float* ab, int L, hipStream_t s, const FilmSpec* fs, SaRoute* route) {
     if (rows <= 0 || !x || !att || !wf_in || !b_in || !ln_g || !ln_b || !sa_head_supported(C, L, 0) || rows % L != 0) return hipErrorInvalidValue;
     if (fs && (ab || !sa_tail_film_local(C, L) || fs->C != C)) return hipErrorInvalidValue;
     SaHeadArgs a{};
@@ -764,15 +765,16 @@ hipError_t launch_sa_head(int C, const float* x, float* att, int rows, const flo
     // (in-kernel FiLM coefficient rows sit in the q / k / v^T region, dead until the first head's tiles are written)
     if (fs && (size_t)film_rows_cap(TM, L) * 2 * C * sizeof(float) > ((size_t)2 * TM * (2 * D + 8) + (size_t)D * (2 * TM + 8)) * sizeof(_Float16)) return hipErrorInvalidValue;
     const void* kern = C == 128 ? reinterpret_cast<const void*>(sa_head_kernel<128>) : reinterpret_cast<const void*>(sa_head_kernel<256>);
-    if (hipError_t e = allow_full_lds(kern); e != hipSuccess) return e;
     const int tiles = (rows + TM - 1) / TM;
+    if (route) { route->kernel = SA_ROUTE_HEAD; route->waves = 4; route->grid = tiles; if (route->dry) return hipSuccess; }
+    if (hipError_t e = allow_full_lds(kern); e != hipSuccess) return e;
     if (C == 128) hipLaunchKernelGGL(sa_head_kernel<128>, dim3(tiles), dim3(256), lds, s, a);
     else hipLaunchKernelGGL(sa_head_kernel<256>, dim3(tiles), dim3(256), lds, s, a);
     return hipGetLastError();
 }
 
 hipError_t launch_sa_qkv(int C, const float* x, float* qkv, int rows, const float* wf_in, const float* b_in, const float* ln_g,
-                         const float* ln_b, const float* ab, int L, hipStream_t s, const FilmSpec* fs) {
+                         const float* ln_b, const float* ab, int L, hipStream_t s, const FilmSpec* fs, SaRoute* route) {
     if (fs && (ab || L <= 0 || !sa_tail_film_local(C, L) || fs->C != C)) return hipErrorInvalidValue;
     if (rows <= 0 || (ab && L <= 0) || !x || !qkv || !wf_in || !b_in || !ln_g || !ln_b) return hipErrorInvalidValue;
     if (C != 128 && C != 256) return hipErrorInvalidValue;
@@ -782,9 +784,10 @@ hipError_t launch_sa_qkv(int C, const float* x, float* qkv, int rows, const floa
     const int TM = 8192 / C;
     const size_t lds = (size_t)((C / 32) * TM * T_LDK + TM * C) * sizeof(float);     // slab 36.9 KB + output tile 32 KB
     const void* kern = C == 128 ? reinterpret_cast<const void*>(sa_qkv_kernel<128>) : reinterpret_cast<const void*>(sa_qkv_kernel<256>);
-    if (hipError_t e = allow_full_lds(kern); e != hipSuccess) return e;
     const int tiles = (rows + TM - 1) / TM;
     const int gy = (tiles < spdm_tune(15, 512)) ? 3 : 1;      // q, k, v on a workgroup each while the grid is small
+    if (route) { route->kernel = SA_ROUTE_QKV; route->waves = 4; route->grid = tiles * gy; if (route->dry) return hipSuccess; }
+    if (hipError_t e = allow_full_lds(kern); e != hipSuccess) return e;
     if (C == 128) hipLaunchKernelGGL(sa_qkv_kernel<128>, dim3(tiles, gy), dim3(256), lds, s, a);
     else hipLaunchKernelGGL(sa_qkv_kernel<256>, dim3(tiles, gy), dim3(256), lds, s, a);
     return hipGetLastError();

@@ -762,6 +762,25 @@ struct Recorder {
         c.stride[1] = 1; c.stride[2] = in;
         return f32(c);
     }
+    // (out, 64) fp32 -> two fp16 arrays (hi, lo of 128 x) of [out][64] in MFMA A-fragment order, input axis permuted inside each
+    // group of 16 by perm16 = 0 1 2 3 8 9 10 11 | 4 5 6 7 12 13 14 15: the k-slot order of an accumulator tile used as B operand
+    // (sa_fused.hip)
+    void perm_split(const std::string& wname, int out, void** hi_dev, void** lo_dev) {
+        const long long o = at(wname, {out, 64});
+        if (o < 0) return;
+        const WeightCopy v = dense(o, 1, out, 64);
+        if (!in_range(v, wname)) return;        // block falls back to the GEMM chain
+        *hi_dev = put(v, WL_PERM_HI);
+        *lo_dev = put(v, WL_PERM_LO);
+    }
+    // fragment-order split copy of a (out, in) Linear weight (sa_tail.hip reads its B operands straight from it)
+    float* linear_frag(const std::string& wname, int out, int in) {
+        const long long o = at(wname, {out, in});
+        if (o < 0) return nullptr;
+        const WeightCopy v = dense(o, 1, out, in);
+        if (!in_range(v, wname)) return nullptr;
+        return frag(v, 1, out, in);
+    }
     // walk() records through this Recorder and returns err.  Plan pass; the device answers the range checks on the blob; load pass
     template <class Walk>
     int both_passes(const float* d_blob, Walk walk) {
@@ -853,25 +872,6 @@ struct Loader : Recorder {
         }
         r.cout = cout;
         return r;
-    }
-    // (out, 64) fp32 -> two fp16 arrays (hi, lo of 128 x) of [out][64] in MFMA A-fragment order, input axis permuted inside each
-    // group of 16 by perm16 = 0 1 2 3 8 9 10 11 | 4 5 6 7 12 13 14 15: the k-slot order of an accumulator tile used as B operand
-    // (sa_fused.hip)
-    void perm_split(const std::string& wname, int out, void** hi_dev, void** lo_dev) {
-        const long long o = at(wname, {out, 64});
-        if (o < 0) return;
-        const WeightCopy v = dense(o, 1, out, 64);
-        if (!in_range(v, wname)) return;        // block falls back to the GEMM chain
-        *hi_dev = put(v, WL_PERM_HI);
-        *lo_dev = put(v, WL_PERM_LO);
-    }
-    // fragment-order split copy of a (out, in) Linear weight (sa_tail.hip reads its B operands straight from it)
-    float* linear_frag(const std::string& wname, int out, int in) {
-        const long long o = at(wname, {out, in});
-        if (o < 0) return nullptr;
-        const WeightCopy v = dense(o, 1, out, in);
-        if (!in_range(v, wname)) return nullptr;
-        return frag(v, 1, out, in);
     }
     // ---- models/simple_Unet.py: re-layout into channel-padded storage (ChanMap) ----
     // (Cout, Cin, 3, 3) -> [taps][mo.width][mi.width], real (o, i) at (mo.pos[o], mi.pos[i]), zeros elsewhere
@@ -4338,6 +4338,42 @@ extern "C" int spdm_op_train(spdm_op_train_args* p) {
     return SPDM_OK;
 }
 
+// A pending GroupNorm as the op-level hooks take it (spdm_op_stream_gn, include/spdm.h) -> the StatsRef its consumer reads, checked
+// host-side: source k of op `op` of hook `hook`, B samples of HW rows, C channels (0: the op takes none there), `aff` floats of
+// gamma / beta.  Without statistics *st is the empty reference.
+static int op_pending_gn(const char* hook, int op, int k, const spdm_op_stream_gn& g, int64_t B, int64_t C, int64_t HW, int64_t aff,
+                         StatsRef* st) {
+#define OPG_BAD(fmt, ...) return fail(SPDM_ERR_INVALID, "%s: " fmt, hook, __VA_ARGS__)
+    *st = StatsRef{nullptr, 0, 1, 1, (int)HW, 0.0};
+    if (C == 0 || !g.d_stats) {
+        if (g.d_stats) OPG_BAD("op %d takes no pending GroupNorm on source %d; gn[%d] must be empty", op, k, k);
+        if (g.stats_cap || g.slots || g.m_tile || g.n_tiles || g.cnorm || g.d_gamma || g.d_beta || g.affine_cap)
+            OPG_BAD("op %d: gn[%d] has no statistics; its other fields must be empty", op, k);
+        return SPDM_OK;
+    }
+    if (g.slots < 1 || g.m_tile < 1 || g.n_tiles < 1) OPG_BAD("op %d: gn[%d] needs slots, m_tile and n_tiles >= 1", op, k);
+    if (g.cnorm < 1 || g.cnorm > C) OPG_BAD("op %d: gn[%d].cnorm %d outside [1, %lld]", op, k, g.cnorm, (long long)C);
+    if (!g.d_gamma || !g.d_beta) OPG_BAD("op %d: gn[%d] needs gamma and beta", op, k);
+    if (g.affine_cap < (uint64_t)aff)
+        OPG_BAD("op %d: gn[%d] gamma / beta hold %llu floats, the launch needs %lld", op, k, (unsigned long long)g.affine_cap, (long long)aff);
+    // the slots sample b's consumer adds: tiles first .. last of its rows, n_tiles each (sample_mean_rstd_wave)
+    const int64_t mt = g.m_tile;
+    int64_t reads = ((HW + mt - 2) / mt + 1) * g.n_tiles;                  // the bound over every alignment
+    if (std::min<int64_t>(B, mt) <= (1 << 20)) {                            // the alignments repeat with period <= m_tile
+        reads = 0;
+        for (int64_t b = 0; b < std::min<int64_t>(B, mt); ++b)
+            reads = std::max<int64_t>(reads, ((b * HW + HW - 1) / mt - (b * HW) / mt + 1) * g.n_tiles);
+    }
+    if (g.slots < reads) OPG_BAD("op %d: gn[%d] has %d slots per sample, the consumer reads %lld", op, k, g.slots, (long long)reads);
+    OpTrainExtent E;
+    const uint64_t cap = E.mul({B, g.slots, 2});
+    if (!E.ok) OPG_BAD("op %d: a tensor extent is beyond 31 bits", op);
+    if (g.stats_cap < cap) OPG_BAD("op %d: gn[%d] statistics hold %llu doubles, the launch needs %llu", op, k, (unsigned long long)g.stats_cap, (unsigned long long)cap);
+    *st = StatsRef{g.d_stats, g.slots, g.m_tile, g.n_tiles, (int)HW, 1.0 / ((double)g.cnorm * (double)HW)};
+    return SPDM_OK;
+#undef OPG_BAD
+}
+
 // op-level test hook: one launch_* of elementwise.hip (the streaming kernels of the forward / sampling path) on the caller's tensors
 // (include/spdm.h).  Validate, upload the host integers, build AffineSrc / StatsRef / StepArgs, launch, synchronise.
 extern "C" int spdm_op_stream(spdm_op_stream_args* p) {
@@ -4510,34 +4546,8 @@ extern "C" int spdm_op_stream(spdm_op_stream_args* p) {
                 OPS_BAD("op %d: h_idx[0][%lld] = %d outside [0, %lld)", q.op, (long long)i, q.h_idx[0][i], (long long)(idx_lim > 0 ? idx_lim : (int64_t)INT32_MAX + 1));
     }
     StatsRef st[SPDM_OP_STREAM_GN];
-    for (int k = 0; k < SPDM_OP_STREAM_GN; ++k) {
-        const spdm_op_stream_gn& g = q.gn[k];
-        st[k] = StatsRef{nullptr, 0, 1, 1, (int)gn_HW[k], 0.0};
-        if (gn_C[k] == 0 || !g.d_stats) {
-            if (g.d_stats) OPS_BAD("op %d takes no pending GroupNorm on source %d; gn[%d] must be empty", q.op, k, k);
-            if (g.stats_cap || g.slots || g.m_tile || g.n_tiles || g.cnorm || g.d_gamma || g.d_beta || g.affine_cap)
-                OPS_BAD("op %d: gn[%d] has no statistics; its other fields must be empty", q.op, k);
-            continue;
-        }
-        if (g.slots < 1 || g.m_tile < 1 || g.n_tiles < 1) OPS_BAD("op %d: gn[%d] needs slots, m_tile and n_tiles >= 1", q.op, k);
-        if (g.cnorm < 1 || g.cnorm > gn_C[k]) OPS_BAD("op %d: gn[%d].cnorm %d outside [1, %lld]", q.op, k, g.cnorm, (long long)gn_C[k]);
-        if (!g.d_gamma || !g.d_beta) OPS_BAD("op %d: gn[%d] needs gamma and beta", q.op, k);
-        if (g.affine_cap < (uint64_t)gn_aff[k])
-            OPS_BAD("op %d: gn[%d] gamma / beta hold %llu floats, the launch needs %lld", q.op, k, (unsigned long long)g.affine_cap, (long long)gn_aff[k]);
-        // the slots sample b's consumer adds: tiles first .. last of its rows, n_tiles each (sample_mean_rstd_wave)
-        const int64_t HW = gn_HW[k], mt = g.m_tile;
-        int64_t reads = ((HW + mt - 2) / mt + 1) * g.n_tiles;                  // the bound over every alignment
-        if (std::min<int64_t>(B, mt) <= (1 << 20)) {                            // the alignments repeat with period <= m_tile
-            reads = 0;
-            for (int64_t b = 0; b < std::min<int64_t>(B, mt); ++b)
-                reads = std::max<int64_t>(reads, ((b * HW + HW - 1) / mt - (b * HW) / mt + 1) * g.n_tiles);
-        }
-        if (g.slots < reads) OPS_BAD("op %d: gn[%d] has %d slots per sample, the consumer reads %lld", q.op, k, g.slots, (long long)reads);
-        const uint64_t cap = E.mul({B, g.slots, 2});
-        if (!E.ok) OPS_BAD("op %d: a tensor extent is beyond 31 bits", q.op);
-        if (g.stats_cap < cap) OPS_BAD("op %d: gn[%d] statistics hold %llu doubles, the launch needs %llu", q.op, k, (unsigned long long)g.stats_cap, (unsigned long long)cap);
-        st[k] = StatsRef{g.d_stats, g.slots, g.m_tile, g.n_tiles, (int)HW, 1.0 / ((double)g.cnorm * (double)HW)};
-    }
+    for (int k = 0; k < SPDM_OP_STREAM_GN; ++k)
+        SPDM_TRY(op_pending_gn("op_stream", q.op, k, q.gn[k], B, gn_C[k], gn_HW[k], gn_aff[k], &st[k]));
     if (stats_need == 0) {
         if (q.d_stats_out || q.stats_out_cap) OPS_BAD("op %d writes no statistics; d_stats_out must be null", q.op);
     } else if (!q.d_stats_out) {
@@ -4801,5 +4811,185 @@ extern "C" int spdm_op_frame(spdm_op_frame_args* p) {
     const hipError_t es = hipDeviceSynchronize();
     if (el != hipSuccess) return fail(SPDM_ERR_HIP, "op_frame: op %d: launch failed: %s; device: %s", q.op, hipGetErrorString(el), hipGetErrorString(es));
     if (es != hipSuccess) return fail(SPDM_ERR_HIP, "op_frame: op %d: %s", q.op, hipGetErrorString(es));
+    return SPDM_OK;
+}
+
+// op-level test hook: one forward SelfAttention launch (sa_fused.hip, sa_tail.hip, attention.hip) exactly as Ctx::attention makes
+// it, on the caller's tensors (include/spdm.h).  Validate -- the launcher's own refusals by asking the launcher (SaRoute::dry) --,
+// lay out the weights with the loader's code, upload the timesteps, build FilmSpec / SaCrop, launch, synchronise.
+extern "C" int spdm_op_sa(spdm_op_sa_args* p) {
+    if (!p) return fail(SPDM_ERR_INVALID, "op_sa: null argument");
+    spdm_op_sa_args& q = *p;
+    for (int i = 0; i < 5; ++i) q.info[i] = -1;
+    if (q.op < 0 || q.op >= SPDM_OPA_COUNT) return fail(SPDM_ERR_INVALID, "op_sa: unknown op %d", q.op);
+    static const int n_dims[SPDM_OPA_COUNT] = {10, 3, 3, 3, 4};
+    const int64_t* d = q.dim;
+    for (int i = 0; i < SPDM_OP_SA_DIMS; ++i) {
+        if (d[i] < 0 || d[i] > INT32_MAX) return fail(SPDM_ERR_INVALID, "op_sa: dim[%d] = %lld outside [0, 2^31)", i, (long long)d[i]);
+        if (i >= n_dims[q.op] && d[i] != 0) return fail(SPDM_ERR_INVALID, "op_sa: op %d takes %d dims; dim[%d] must be 0", q.op, n_dims[q.op], i);
+    }
+#define OPA_BAD(...) return fail(SPDM_ERR_INVALID, "op_sa: " __VA_ARGS__)
+    const bool fused = q.op == SPDM_OPA_FUSED64, core = q.op == SPDM_OPA_CORE;
+    const int64_t B = fused || core ? d[0] : d[1], L = fused || core ? d[1] : d[2], C = fused ? 64 : core ? d[2] : d[0];
+    if (B < 1 || L < 1) OPA_BAD("op %d: B and L must be positive", q.op);
+    if (core ? !(C == 64 || C == 128 || C == 256) : !fused && !(C == 128 || C == 256))
+        OPA_BAD("op %d: C = %lld (CORE: 64, 128 or 256; QKV, HEAD, TAIL: 128 or 256)", q.op, (long long)C);
+    const bool crop = fused && d[3] == 1, outc = fused && d[9] == 1;
+    if (fused) {
+        if (d[2] > 1 || d[3] > 1 || d[9] > 1) OPA_BAD("fused64: no_wlds, crop and outc are 0 / 1");
+        if (!crop && (d[4] || d[5] || d[6] || d[7] || d[8] || d[9])) OPA_BAD("fused64: without crop, H0 = D = Wp = lh = lw = outc = 0");
+    }
+    // a hole of launch_sa_fused64 closed here as well as there: its crop checks ran in int, so two large factors could wrap into
+    // the accepted range ((lh + H0) Wp with Wp = 2^31 - 1) and the kernel would read tokens far outside the sample.  Every crop
+    // dimension of an accepted crop is at most L ((lh + H0) Wp <= L, lw + D <= Wp); beyond that nothing is asked of the launcher
+    if (crop)
+        for (int i = 4; i <= 8; ++i)
+            if (d[i] > L) OPA_BAD("fused64: crop dimension dim[%d] = %lld exceeds L = %lld", i, (long long)d[i], (long long)L);
+    if (core && d[3] > 1) OPA_BAD("core: valu is 0 / 1");
+    OpTrainExtent E;
+    uint64_t need[SPDM_OP_SA_BUFS] = {};
+    bool absent[SPDM_OP_SA_BUFS] = {};
+    bool takes_w[SPDM_OP_SA_WEIGHTS] = {}, takes_v[SPDM_OP_SA_VECS] = {};
+    const uint64_t rowsC = E.mul({B, L, C}), rows3C = E.mul({B, L, 3, C});
+    switch (q.op) {
+        case SPDM_OPA_FUSED64:
+            need[0] = need[1] = rowsC; need[2] = crop ? E.mul({B, d[4], d[5]}) : 0;
+            absent[1] = outc; absent[2] = !outc;
+            for (bool& t : takes_w) t = true;
+            for (bool& t : takes_v) t = true;
+            break;
+        case SPDM_OPA_QKV: need[0] = rowsC; need[1] = rows3C; absent[2] = true; takes_w[0] = takes_v[0] = takes_v[1] = takes_v[2] = true; break;
+        case SPDM_OPA_HEAD: need[0] = need[1] = rowsC; absent[2] = true; takes_w[0] = takes_v[0] = takes_v[1] = takes_v[2] = true; break;
+        case SPDM_OPA_TAIL:
+            need[0] = need[1] = need[2] = rowsC;
+            takes_w[1] = takes_w[2] = takes_w[3] = true;
+            for (int i = 3; i < 8; ++i) takes_v[i] = true;
+            break;
+        case SPDM_OPA_CORE: need[0] = rows3C; need[1] = rowsC; absent[2] = true; break;
+    }
+    if (!E.ok) OPA_BAD("op %d: a tensor extent is beyond 31 bits", q.op);
+    for (int i = 0; i < SPDM_OP_SA_BUFS; ++i) {
+        if (absent[i]) {
+            if (q.d_buf[i]) OPA_BAD("op %d with these dimensions does not take d_buf[%d]; it must be null", q.op, i);
+            continue;
+        }
+        if (!q.d_buf[i]) OPA_BAD("op %d: d_buf[%d] is null", q.op, i);
+        if (q.cap[i] < need[i])
+            OPA_BAD("op %d: d_buf[%d] holds %llu floats, the launch needs %llu", q.op, i, (unsigned long long)q.cap[i], (unsigned long long)need[i]);
+    }
+    for (int i = 0; i < SPDM_OP_SA_WEIGHTS; ++i)
+        if ((q.h_w[i] != nullptr) != takes_w[i]) OPA_BAD("op %d %s h_w[%d]", q.op, takes_w[i] ? "needs" : "does not take", i);
+    for (int i = 0; i < SPDM_OP_SA_VECS; ++i) {
+        if ((q.d_vec[i] != nullptr) != takes_v[i]) OPA_BAD("op %d %s d_vec[%d]", q.op, takes_v[i] ? "needs" : "does not take", i);
+        const uint64_t nv = (uint64_t)(i == 2 ? 3 * C : C);
+        if (takes_v[i] ? q.vec_cap[i] < nv : q.vec_cap[i] != 0)
+            OPA_BAD("op %d: d_vec[%d] holds %llu floats, the launch needs %llu", q.op, i, (unsigned long long)q.vec_cap[i], (unsigned long long)(takes_v[i] ? nv : 0));
+    }
+    if (outc ? (!q.d_outc_w || q.outc_w_cap < 64 || !std::isfinite(q.outc_b)) : (q.d_outc_w || q.outc_w_cap || q.outc_b != 0.f))
+        OPA_BAD("op %d: outc's weight [64] and a finite bias go with outc = 1 only", q.op);
+    // the block input's affine: coefficients from memory (ab) or a recipe the kernel evaluates (FilmSpec); a hole of the launchers
+    // closed here: they take any t_count, and the kernels read t_dev[b] for every t_count but 1
+    if (q.film_on != 0 && q.film_on != 1) OPA_BAD("film_on is 0 / 1");
+    if (core && (q.d_ab || q.film_on)) OPA_BAD("core takes neither ab nor a FilmSpec");
+    if (q.d_ab && q.film_on) OPA_BAD("op %d: ab and a FilmSpec are mutually exclusive", q.op);
+    if (q.d_ab ? q.ab_cap < E.mul({B, 2, C}) : q.ab_cap != 0) OPA_BAD("op %d: ab holds %llu floats, [B 2C] are needed", q.op, (unsigned long long)q.ab_cap);
+    StatsRef st{nullptr, 0, 1, 1, (int)L, 0.0};
+    if (!q.film_on) {
+        if (q.t_count || q.T || q.d_temb || q.temb_cap || q.h_t || q.d_film || q.film_cap) OPA_BAD("op %d: film_on 0, its FilmSpec fields must be empty", q.op);
+        SPDM_TRY(op_pending_gn("op_sa", q.op, 0, q.gn, B, 0, L, 0, &st));
+    } else {
+        if (q.t_count != 1 && q.t_count != B) OPA_BAD("film: t_count must be 1 or B");
+        if (q.T < 1 || q.T > INT32_MAX) OPA_BAD("film: T must be positive");
+        if (q.d_temb) {
+            if (q.temb_cap < E.mul({q.T, C})) OPA_BAD("film: temb holds %llu floats, [T C] are needed", (unsigned long long)q.temb_cap);
+            if (!q.h_t) OPA_BAD("film: temb needs the timesteps h_t");
+            for (int64_t i = 0; i < q.t_count; ++i)
+                if (q.h_t[i] < 0 || q.h_t[i] >= q.T) OPA_BAD("film: h_t[%lld] = %d outside [0, %lld)", (long long)i, q.h_t[i], (long long)q.T);
+        } else if (q.h_t || q.temb_cap || q.t_count != 1 || q.T != 1) {
+            OPA_BAD("film: without temb, h_t is null and t_count = T = 1");
+        }
+        if (q.d_film ? q.film_cap < E.mul({B, 2, C}) : q.film_cap != 0) OPA_BAD("film: film holds %llu floats, [B 2C] are needed", (unsigned long long)q.film_cap);
+        SPDM_TRY(op_pending_gn("op_sa", q.op, 0, q.gn, B, C, L, C, &st));
+    }
+    if (!E.ok) OPA_BAD("op %d: a tensor extent is beyond 31 bits", q.op);
+    // ---- the launch, asked of the launcher twice: dry (its own refusals, before the device is touched), then for real ----
+    FilmSpec fs{};
+    fs.st = st; fs.gamma = q.gn.d_gamma; fs.beta = q.gn.d_beta; fs.temb = q.d_temb; fs.t_count = q.t_count; fs.film = q.d_film; fs.C = (int)C;
+    const FilmSpec* fsp = q.film_on ? &fs : nullptr;
+    SaCrop cr{(int)d[4], (int)d[5], (int)d[6], (int)d[7], (int)d[8], q.d_outc_w, q.outc_b, outc ? q.d_buf[2] : nullptr};
+    const SaCrop* crp = crop ? &cr : nullptr;
+    unsigned sw = 0;
+    if (fused && d[2]) sw |= SW_SA_NO_WLDS;
+    if (core && d[3]) sw |= SW_ATTN_VALU;
+    const void* fw[8] = {};
+    const float* wf[4] = {};
+    float* const* b = q.d_buf;
+    const float* const* v = q.d_vec;
+    const int iB = (int)B, iL = (int)L, iC = (int)C, rows = (int)(B * L);
+    hipStream_t s = nullptr;
+    SaRoute r{1, -1, -1, -1, -1, -1};
+    auto launch = [&]() -> hipError_t {
+        switch (q.op) {
+            case SPDM_OPA_FUSED64:
+                return launch_sa_fused64(b[0], b[1], iB, iL, v[0], v[1], v[4], v[5], fw, v[2], v[3], v[6], v[7], q.d_ab, sw, s, fsp, crp, &r);
+            case SPDM_OPA_QKV: return launch_sa_qkv(iC, b[0], b[1], rows, wf[0], v[2], v[0], v[1], q.d_ab, iL, s, fsp, &r);
+            case SPDM_OPA_HEAD: return launch_sa_head(iC, b[0], b[1], rows, wf[0], v[2], v[0], v[1], q.d_ab, iL, s, fsp, &r);
+            case SPDM_OPA_TAIL:
+                return launch_sa_tail(iC, b[0], b[1], b[2], rows, wf[1], wf[2], wf[3], v[3], v[6], v[7], v[4], v[5], q.d_ab, iL, s, fsp, &r);
+            default: return launch_attention_auto(b[0], b[1], iB, iL, iC, 4, sw, s, &r);
+        }
+    };
+    for (int i = 0; i < 4; ++i) wf[i] = takes_w[i] ? q.h_w[i] : nullptr;      // (dry: any non-null pointer; not dereferenced)
+    if (launch() != hipSuccess) OPA_BAD("op %d: the launcher refuses this launch (shape, route or LDS limits; kernels.h)", q.op);
+#undef OPA_BAD
+    // ---- the device from here on ----
+    // the weights as the loader lays them out: the caller's torch-layout tensors are the blob of a table of its own
+    std::vector<float> blob;
+    spdm_tensor_index index[SPDM_OP_SA_WEIGHTS] = {};
+    int n_index = 0;
+    for (int i = 0; i < SPDM_OP_SA_WEIGHTS; ++i) {
+        if (!takes_w[i]) continue;
+        spdm_tensor_index& e = index[n_index++];
+        snprintf(e.name, SPDM_NAME_MAX, "w%d", i);
+        e.offset = blob.size(); e.numel = (uint64_t)(i == 0 ? 3 : 1) * C * C; e.ndim = 2; e.shape[0] = (int)((i == 0 ? 3 : 1) * C); e.shape[1] = (int)C;
+        blob.insert(blob.end(), q.h_w[i], q.h_w[i] + e.numel);
+    }
+    DevBlob db;
+    WeightTable wt;
+    Recorder R(wt, blob.size(), index, n_index);
+    void* dfw[8] = {};
+    float* dwf[4] = {};
+    auto walk = [&]() {                    // Loader::attn, which starts each pass from an empty AttnW: a demoted weight leaves its
+        for (void*& f : dfw) f = nullptr;  // pointers untouched in the load pass, and the plan pass had set them to its stand-in
+        for (int i = 0; i < SPDM_OP_SA_WEIGHTS; ++i) {
+            if (!takes_w[i]) continue;
+            const std::string name = "w" + std::to_string(i);
+            const int out = (int)((i == 0 ? 3 : 1) * C);
+            if (C == 64) R.perm_split(name, out, &dfw[2 * i], &dfw[2 * i + 1]);
+            else dwf[i] = R.linear_frag(name, out, (int)C);
+        }
+        return R.err;
+    };
+    if (n_index) {
+        SPDM_TRY(db.upload(blob.data(), blob.size()));
+        SPDM_TRY(R.both_passes(db.p, walk));
+        for (int i = 0; i < SPDM_OP_SA_WEIGHTS; ++i)
+            if (takes_w[i] && !(C == 64 ? dfw[2 * i] && dfw[2 * i + 1] : dwf[i] != nullptr))
+                return fail(SPDM_ERR_INVALID, "op_sa: h_w[%d] is outside the split format's range (the plan keeps such a block on the GEMM chain)", i);
+    }
+    for (int i = 0; i < 8; ++i) fw[i] = dfw[i];
+    for (int i = 0; i < 4; ++i) wf[i] = dwf[i];
+    OpTrainDev dev;
+    if (q.film_on && q.d_temb) {
+        HIP_TRY(hipMalloc(&dev.p[0], sizeof(int) * (size_t)q.t_count));
+        HIP_TRY(hipMemcpy(dev.p[0], q.h_t, sizeof(int) * (size_t)q.t_count, hipMemcpyHostToDevice));
+        fs.t_dev = (const int*)dev.p[0];
+    }
+    r = SaRoute{0, -1, -1, -1, -1, -1};
+    const hipError_t el = launch();
+    const hipError_t es = hipDeviceSynchronize();
+    if (el != hipSuccess) return fail(SPDM_ERR_HIP, "op_sa: op %d: launch failed: %s; device: %s", q.op, hipGetErrorString(el), hipGetErrorString(es));
+    if (es != hipSuccess) return fail(SPDM_ERR_HIP, "op_sa: op %d: %s", q.op, hipGetErrorString(es));
+    q.info[0] = r.kernel; q.info[1] = r.waves; q.info[2] = r.grid; q.info[3] = r.wlds; q.info[4] = r.qw;
     return SPDM_OK;
 }

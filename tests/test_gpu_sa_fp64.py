@@ -18,7 +18,8 @@ err / (A + SV / 1024), x 1e-9, per route (columns plain / moderate / onehot / on
     exact_fp32                 3.6   4.4   12.5   10.1
 Worst 1.25e-8 -> TAU = 3.5e-8 (2.8 x), TAU_S = TAU / 1024 (sa_ref.py says why the S V term is small); per block the worst is
 sa6 (6.0 / 5.8 / 12.5 / 12.3) and the best sa3 (0.7 / 1.0 / 1.3 / 2.5).  The routes below that a debug handle cannot reach
-(FiLM folded or evaluated in the consumers, cropped sa6 with and without outc) are held on eps of the whole model.
+(FiLM folded or evaluated in the consumers, cropped sa6 with and without outc) are held here on eps of the whole model, and per
+element, one launch at a time, by tests/test_gpu_sa_ops_fp64.py.
 
 Every case prints the kernels each block takes (`block_routes`, restating Ctx::attention's rule in spdm_api.hip) and
   ROUTE <flavour> H D B <route>: max |eps - eps64| / scale, max |eps - eps_default| / scale
