@@ -949,6 +949,12 @@ int  spdm_debug_whole_tiles(void);
  * SPDM_TUNE22=0 keeps it at 0. */
 int  spdm_debug_fused_upsample_launches(void);
 
+/* Host-only test hook (no GPU call): how many launches this process has enqueued from a plan whose epilogue also wrote the
+ * MaxPool2d(2) of their output for the next Down block (conv_reg.hip on width-8 maps at large batch: pool 1, raw with the
+ * GroupNorm still pending; sa_tail.hip: pools 2 and 3), in place of a pool_kernel launch.  A captured step counts once, not
+ * per replay.  SPDM_TUNE23 (read once per process) selects the pools: bit 0, 1, 2 = pool 1, 2, 3; default 7; 0 keeps it at 0. */
+int  spdm_debug_pooled_epilogue_launches(void);
+
 /* Op-level test hook: d_y = GELU(d_x) evaluated with the device erf that the conv prologues use
  * (nn.GELU(), models/Unet_FiLmLayer.py:104). */
 int  spdm_op_gelu(const float* d_x, float* d_y, size_t n, void* stream);

@@ -960,6 +960,7 @@ hipError_t launch_gemm(const GemmArgs& a0, hipStream_t s) {
         return launch_conv_wide(a, g, s);
     }
     if (!fused_src && a.skip != nullptr && !gemm_takes_two_sources(a)) return hipErrorInvalidValue;   // (... gemm_takes_two_sources)
+    if ((a.pro == PRO_GN_POOLED || a.pool_dst != nullptr) && (g.skinny || !g.reg)) return hipErrorInvalidValue;   // (conv_reg.hip only: the plan asks gemm_geometry first)
     if (g.skinny) return launch_conv_skinny(a, g, s);
     if (g.reg) return launch_conv_reg64(a, g, s);
     if (g.ksplit > 1) {

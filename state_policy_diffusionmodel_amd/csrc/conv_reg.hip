@@ -29,6 +29,7 @@
 #include <algorithm>
 
 #include "device_utils.h"
+#include "resample.h"
 
 namespace spdm {
 
@@ -102,9 +103,19 @@ __global__ __launch_bounds__(R_NTHR, 1) void conv_reg64_kernel(const GemmArgs a,
     float* const gb = reinterpret_cast<float*>(r_smem + R_WBYTES);       // gamma[64] | beta[64]
     float* const mr = gb + 128;                                          // [8 waves][R_MAXT tiles] x {mean, rstd}
     constexpr bool pro = (PRO != PRO_NONE), pro_gelu = (PRO == PRO_GN_GELU);
+    constexpr bool pro_pooled = (PRO == PRO_GN_POOLED);      // the finer level's affine in pool_kernel's arithmetic (resample.h affine1)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l16 = lane & 15, kg = lane >> 4;
+    // pooled epilogue (width 8, GemmArgs::pool_dst): which of max / min of a window's raw values the pending GroupNorm turns into
+    // the max of the finished ones -- the sign of the gain of this lane's four output channels, read once
+    const bool pooled = (WD == 8) && a.pool_dst != nullptr;
+    bool pool_max[4] = {true, true, true, true};
+    if (pooled) {
+        const r_f32x4 g4 = *reinterpret_cast<const r_f32x4*>(a.pool_gamma + 4 * l16);
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) pool_max[nb] = g4[nb] >= 0.f;
+    }
 
     const int HW = a.HW, H = a.H;
     constexpr int RPT = 16 / WD, TH = 4 * RPT;      // image rows per row tile / per wave tile (W = 8: 2, 8; W = 4: 4, 16)
@@ -209,7 +220,7 @@ __global__ __launch_bounds__(R_NTHR, 1) void conv_reg64_kernel(const GemmArgs a,
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         sc[4 * q + j] = rstd * g4[j];
-                        sh[4 * q + j] = b4[j] - mean * sc[4 * q + j];
+                        sh[4 * q + j] = pro_pooled ? b4[j] : b4[j] - mean * sc[4 * q + j];
                     }
                 }
             }
@@ -222,7 +233,8 @@ __global__ __launch_bounds__(R_NTHR, 1) void conv_reg64_kernel(const GemmArgs a,
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         float v = raw[ks][t][q][j];
-                        if (pro) v = __fmaf_rn(v, sc[4 * q + j], sh[4 * q + j]);
+                        if (pro_pooled) v = affine1(v, mean, sc[4 * q + j], sh[4 * q + j]);      // (pool_kernel's bits: sh is beta here)
+                        else if (pro) v = __fmaf_rn(v, sc[4 * q + j], sh[4 * q + j]);
 #ifndef REG_ABL_NOGELU
                         if (pro_gelu) v = gelu_erf(v);
 #endif
@@ -333,6 +345,29 @@ __global__ __launch_bounds__(R_NTHR, 1) void conv_reg64_kernel(const GemmArgs a,
                 s1 += (v.x + v.y) + (v.z + v.w);
                 s2 += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
             }
+            // ---- MaxPool2d(2) of the tile, RAW: the window (image rows h0 + t - 1 + 4 js, + 1; columns 2 kg, 2 kg + 1)
+            //      is registers js, js + 2 of row tiles t - 1 (= t ^ 1, t odd) and t of THIS lane.  The GroupNorm pending on the tensor is monotone in
+            //      the raw value -- rising where the channel's gain is >= 0, falling where it is < 0 -- so pool_kernel's max of the
+            //      finished values is the affine of the raw max, or of the raw min: the selected one is stored, the affine stays
+            //      pending on the pooled map (PRO_GN_POOLED in the consumer) ----
+            if constexpr (WD == 8) {
+                if (pooled && (t & 1)) {
+                    float* pbase = a.pool_dst + (size_t)b * (HW / 4) * a.pool_ld + 4 * l16;
+#pragma unroll
+                    for (int js = 0; js < 2; ++js) {
+                        r_f32x4 m;
+#pragma unroll
+                        for (int nb = 0; nb < 4; ++nb) {
+                            const float v00 = acc[t ^ 1][nb][js] * R_DESCALE, v01 = acc[t ^ 1][nb][js + 2] * R_DESCALE;
+                            const float v10 = acc[t][nb][js] * R_DESCALE, v11 = acc[t][nb][js + 2] * R_DESCALE;
+                            const float hi = fmaxf(fmaxf(v00, v01), fmaxf(v10, v11)), lo = fminf(fminf(v00, v01), fminf(v10, v11));
+                            m[nb] = pool_max[nb] ? hi : lo;
+                        }
+                        const int prow = ((h0 + t - 1) >> 1) + 2 * js;
+                        *reinterpret_cast<r_f32x4*>(pbase + (size_t)(prow * (WD / 2) + kg) * a.pool_ld) = m;
+                    }
+                }
+            }
         }
         const double t1 = wave_sum_f64((double)s1), t2 = wave_sum_f64((double)s2);
         if (lane == 0) {
@@ -365,10 +400,16 @@ hipError_t launch_conv_reg64(const GemmArgs& a, const GemmGeom& g, hipStream_t s
     if (!a.split || a.wgt_frag == nullptr || a.taps != 9 || a.N != 64 || a.K != 64 || !(a.W == 8 || a.W == 4) || a.H < 64 / a.W || a.HW != a.H * a.W ||
         a.HW % 64 != 0 || a.M <= 0 || a.M % a.HW != 0 || a.src_ld % 4 != 0 || a.src_ld < 64 || a.dst_ld % 4 != 0 || a.dst_ld < 64 ||
         a.epi != EPI_STATS || a.epi_stats == nullptr || a.row_stats != nullptr || a.skip != nullptr || a.ksplit > 1 || a.debug != 0 ||
-        a.pro < PRO_NONE || a.pro > PRO_GN_GELU || g.m_tile != 64 || g.n_tile != 64 || g.n_tiles != 1)
+        !((a.pro >= PRO_NONE && a.pro <= PRO_GN_GELU) || a.pro == PRO_GN_POOLED) || g.m_tile != 64 || g.n_tile != 64 || g.n_tiles != 1)
         return hipErrorInvalidValue;
-    if (a.pro != PRO_NONE && (a.pro_stats.p == nullptr || a.pro_gamma == nullptr || a.pro_beta == nullptr || a.pro_stats.HW != a.HW))
+    // PRO_GN_POOLED: the statistics are the FINER level's (4 HW rows per sample, same sample index); few enough slots that the
+    // kernel's serial sum is pool_kernel's (sample_mean_rstd_wave adds up to 8 slots in the same order)
+    if (a.pro == PRO_GN_POOLED && (a.W != 4 || a.pro_stats.HW != 4 * a.HW || !pooled_stats_serial(a.pro_stats))) return hipErrorInvalidValue;
+    if (a.pro != PRO_NONE && (a.pro_stats.p == nullptr || a.pro_gamma == nullptr || a.pro_beta == nullptr ||
+                              (a.pro != PRO_GN_POOLED && a.pro_stats.HW != a.HW)))
         return hipErrorInvalidValue;
+    // pooled epilogue: [B][HW / 4][pool_ld] beside dst, width-8 maps only (a window is one lane's registers there)
+    if (a.pool_dst != nullptr && (a.W != 8 || a.pool_gamma == nullptr || a.pool_ld % 4 != 0 || a.pool_ld < 64)) return hipErrorInvalidValue;
     const int n_wt = a.M / 64;
     const int nw = std::min(R_WAVES, (n_wt + 255) / 256);
     const int grid = std::min(256, (n_wt + nw - 1) / nw);
@@ -386,6 +427,7 @@ hipError_t launch_conv_reg64(const GemmArgs& a, const GemmGeom& g, hipStream_t s
         return launch(conv_reg64_kernel<PRO_GN_GELU, 8>);
     }
     if (a.pro == PRO_NONE) return launch(conv_reg64_kernel<PRO_NONE, 4>);
+    if (a.pro == PRO_GN_POOLED) return launch(conv_reg64_kernel<PRO_GN_POOLED, 4>);
     if (a.pro == PRO_GN) return launch(conv_reg64_kernel<PRO_GN, 4>);
     return launch(conv_reg64_kernel<PRO_GN_GELU, 4>);
 }

@@ -81,7 +81,9 @@ int spdm_tune(int idx, int dflt);      // conv_gemm.hip: SPDM_TUNE<idx> (read on
 
 // Load prologue of a convolution.  PRO_POOL / PRO_UPCAT: the FIRST convolution of a Down / UpSample block reads the block's input
 // through the resampling op itself (GemmArgs: "fused sources") instead of a materialised pooled / concatenated tensor.
-enum { PRO_NONE = 0, PRO_GN = 1, PRO_GN_GELU = 2, PRO_POOL = 3, PRO_UPCAT = 4 };
+// PRO_GN_POOLED (conv_reg.hip on width-4 maps, plan only): src is the RAW MaxPool2d(2) map a producer's epilogue wrote
+// (GemmArgs::pool_dst) and pro_* the FINER level's pending GroupNorm, applied in pool_kernel's arithmetic (resample.h affine1).
+enum { PRO_NONE = 0, PRO_GN = 1, PRO_GN_GELU = 2, PRO_POOL = 3, PRO_UPCAT = 4, PRO_GN_POOLED = 5 };
 enum { EPI_STATS = 0, EPI_BIAS = 1, EPI_BIAS_GELU = 2, EPI_BIAS_RESID = 3, EPI_PLAIN = 4 };
 
 // The kernel configuration a launch dispatched, recorded by the launch itself when GemmArgs::route is set (spdm_op_gemm).
@@ -113,6 +115,10 @@ struct GemmArgs {
     //              channels [up_C, K) are skip [B][HW][K - up_C] (pending GroupNorm in skip_*; skip_stats.p == nullptr: none).
     int up_C;  const float* skip;  int skip_ld;  StatsRef skip_stats;  const float* skip_gamma;  const float* skip_beta;
     int epi;  double* epi_stats;   const float* bias;  const float* resid;  int resid_ld;
+    // Pooled epilogue (conv_reg.hip, width-8 maps; null everywhere but the plan's inc.second): the launch also writes
+    // MaxPool2d(2) of dst as a RAW map [B][HW / 4][pool_ld] -- per channel the max of a window's raw values where pool_gamma, the
+    // gain of the GroupNorm pending on dst, is >= 0, and the min where it is < 0 -- for a PRO_GN_POOLED consumer.
+    float* pool_dst;  int pool_ld;  const float* pool_gamma;
     double* row_stats;                 // optional: per-row {sum, sum^2} of the STORED values, [row][n_tiles][2] (LayerNorm of the consumer)
     // Split-K (small grids: few rows, long K).  ksplit > 1: the launch has ksplit x as many workgroups; workgroup (tile, ks)
     // walks the 32-channel chunks [ks nchunks / ksplit, (ks + 1) nchunks / ksplit) of every tap and stores its raw fp32
@@ -156,6 +162,11 @@ hipError_t launch_conv_skinny(const GemmArgs& a, const GemmGeom& g, hipStream_t 
 // conv_reg.hip: 3x3 convolutions 64 -> 64 on width-8 maps at large batch (64-row wave tiles; one statistics slot per wave tile)
 bool conv_reg_geometry(int M, int N, int K, int HW, int W, int taps, int split, unsigned sw);
 hipError_t launch_conv_reg64(const GemmArgs& a, const GemmGeom& g, hipStream_t s);
+// PRO_GN_POOLED sums the finer tensor's statistics slots serially (sample_mean_rstd); pool_kernel does so for whole-tile samples
+// of up to 8 slots (sample_mean_rstd_wave), and only then are the two means bit-identical
+inline bool pooled_stats_serial(const StatsRef& st) {
+    return st.m_tile > 0 && st.HW % st.m_tile == 0 && (st.HW / st.m_tile) * st.n_tiles <= 8;
+}
 hipError_t launch_splitk_combine(const float* partial, int ksplit, float* dst, int M, int N, int HW, double* stats,
                                  hipStream_t s);
 hipError_t launch_gemm(const GemmArgs& a, hipStream_t s);
@@ -635,7 +646,10 @@ bool sa_tail_supported(int C, unsigned sw);
 hipError_t launch_sa_tail(int C, const float* o, const float* x, float* out, int rows, const float* wf_o, const float* wf_1,
                           const float* wf_2, const float* b_o, const float* b_1, const float* b_2, const float* ln_g,
                           const float* ln_b, const float* ab, int L, hipStream_t s, const FilmSpec* fs = nullptr,
-                          SaRoute* route = nullptr);
+                          SaRoute* route = nullptr, float* pool = nullptr, int W = 0);
+// pool (optional, null from spdm_op_sa): the launch also writes MaxPool2d(2) of out, [rows / 4][C], the samples being L-row maps W
+// columns wide -- where sa_tail_pools says every window lies inside one workgroup's rows
+bool sa_tail_pools(int C, int L, int W, int rows);
 // may the two kernels evaluate the FiLM coefficients themselves for samples of L rows?  (their LDS row per touched sample)
 bool sa_tail_film_local(int C, int L);
 // LayerNorm + in_proj + attention core in one kernel (att = softmax(q k^T / sqrt d) v per sample and head, heads concatenated):

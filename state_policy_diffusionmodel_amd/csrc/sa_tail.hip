@@ -53,6 +53,7 @@ struct SaTailArgs {
     const float *b_o, *b_1, *b_2, *ln_g, *ln_b;
     const float* ab; int L;                     // optional [M / L][2][C]: x is y = A x + B per sample of L rows (FiLM tail folded in)
     FilmSpec fs;                                // fs.on: the coefficients are evaluated here, into LDS (ab is null then)
+    float* pool; int W;                         // optional [M / 4][C]: MaxPool2d(2) of out, whose samples are L-row maps W columns wide
 };
 
 // (plain C++ form: two more instructions per pair, but fewer live registers -- sa_head_kernel sits exactly at the 128-register
@@ -331,6 +332,29 @@ __global__ __launch_bounds__(256, 2) void sa_tail_kernel(const SaTailArgs a) {
                 t += b2;
                 t += av[i];
                 *reinterpret_cast<tf32x4*>(a.out + (size_t)(m0 + r) * T_C + c16 * 4) = t;
+                if (a.pool != nullptr) *reinterpret_cast<tf32x4*>(otile + r * T_C + c16 * 4) = t;      // (this thread's own piece of the tile)
+            }
+        }
+    }
+    // ---- MaxPool2d(2) of the finished tile (the launcher checks that TM and L are multiples of 2 W: every window lies inside the
+    //      tile and inside one sample).  The four rows of a window belong to threads of different waves, so they meet in the tile:
+    //      ONE barrier, then pool_kernel's max(max(v00, v01), max(v10, v11)) per 16-byte piece, TM / 4 pooled rows = 512 pieces ----
+    if (a.pool != nullptr) {
+        __syncthreads();
+        const int W = a.W, Wo = W >> 1;
+#pragma unroll
+        for (int k = 0; k < (T_M / 4) * TPR / 256; ++k) {
+            const int item = tid + 256 * k;
+            const int prow = item / TPR, cq = item % TPR;
+            const int r0 = (prow / Wo) * 2 * W + 2 * (prow % Wo);
+            if (m0 + r0 < M) {
+                const float* p = otile + r0 * T_C + cq * 4;
+                const tf32x4 v00 = *reinterpret_cast<const tf32x4*>(p), v01 = *reinterpret_cast<const tf32x4*>(p + T_C);
+                const tf32x4 v10 = *reinterpret_cast<const tf32x4*>(p + W * T_C), v11 = *reinterpret_cast<const tf32x4*>(p + (W + 1) * T_C);
+                tf32x4 m;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) m[e] = fmaxf(fmaxf(v00[e], v01[e]), fmaxf(v10[e], v11[e]));
+                *reinterpret_cast<tf32x4*>(a.pool + (size_t)(m0 / 4 + prow) * T_C + cq * 4) = m;
             }
         }
     }
@@ -727,17 +751,27 @@ bool sa_tail_film_local(int C, int L) {
     return (size_t)film_rows_cap(8192 / C, L) * 2 * C * sizeof(float) <= (size_t)24 * 1024;
 }
 
+// May sa_tail's epilogue write MaxPool2d(2) of its output (samples of L rows = maps W columns wide)?  Every 2 x 2 window must lie
+// inside one workgroup's tile and one sample: the tile's 8192 / C rows and L are multiples of two image rows, which start even.
+bool sa_tail_pools(int C, int L, int W, int rows) {
+    if (!(C == 128 || C == 256) || W < 2 || (W & 1) || L <= 0 || rows <= 0) return false;
+    return L % (2 * W) == 0 && (8192 / C) % (2 * W) == 0 && rows % L == 0;
+}
+
 hipError_t launch_sa_tail(int C, const float* o, const float* x, float* out, int rows, const float* wf_o, const float* wf_1,
                           const float* wf_2, const float* b_o, const float* b_1, const float* b_2, const float* ln_g,
-                          const float* ln_b, const float* ab, int L, hipStream_t s, const FilmSpec* fs, SaRoute* route) {
+                          const float* ln_b, const float* ab, int L, hipStream_t s, const FilmSpec* fs, SaRoute* route, float* pool,
+                          int W) {
     if (fs && (ab || L <= 0 || !sa_tail_film_local(C, L) || fs->C != C)) return hipErrorInvalidValue;
     if (rows <= 0 || (ab && L <= 0) || !o || !x || !out || !wf_o || !wf_1 || !wf_2 || !b_o || !b_1 || !b_2 || !ln_g || !ln_b)
         return hipErrorInvalidValue;
     if (C != 128 && C != 256) return hipErrorInvalidValue;
+    if (pool && !sa_tail_pools(C, L, W, rows)) return hipErrorInvalidValue;
     SaTailArgs a{};
     a.o = o; a.x = x; a.out = out; a.M = rows;
     a.wf_o = wf_o; a.wf_1 = wf_1; a.wf_2 = wf_2;
     a.b_o = b_o; a.b_1 = b_1; a.b_2 = b_2; a.ln_g = ln_g; a.ln_b = ln_b; a.ab = ab; a.L = L;
+    a.pool = pool; a.W = W;
     if (fs) { a.fs = *fs; a.fs.on = 1; }
     const int TM = 8192 / C;
     const size_t lds = (size_t)(C / 32) * TM * T_LDK * sizeof(float)           // 36.9 KB

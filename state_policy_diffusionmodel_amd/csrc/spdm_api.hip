@@ -308,7 +308,8 @@ struct spdm_handle {
     long long graph_captures = 0;         // step graphs built so far (spdm_graph_captures)
     int dry_fuse_mask = 0;                // dry runs only: bit k set = resampling op k (pool 0-2, upsample+concat 3-5) is read through
                                           // by its consumer (Ctx::conv_fused), bits 6-8 = up block k - 6 takes the two-source
-                                          // conv (Ctx::conv_two) -- the workspace is sized for every combination
+                                          // conv (Ctx::conv_two), bits 9-11 = pool k - 9 is written by its producer's epilogue
+                                          // (Ctx::pool_by_producer) -- the workspace is sized for every combination
     hipGraph_t step_graph = nullptr;
     hipGraphExec_t step_exec = nullptr;
     hipStream_t gstream = nullptr;        // blocking stream the loop runs on when the caller passes the NULL stream
@@ -415,8 +416,9 @@ static int plan_forward(spdm_handle* h, int B, bool use_cond, hipStream_t s, Ten
 // arena.peak ends as the largest of them (arena.dry must be set by the caller)
 static int dry_plan_all(spdm_handle* h) {
     size_t peak = 0;
-    for (int mask = 0; mask < 512; ++mask) {      // bits 0-2 pool read through, 3-5 upsample + concat read through, 6-8 two-source conv
-        if (((mask >> 3) & (mask >> 6) & 7) != 0) continue;       // (a block is one or the other)
+    for (int mask = 0; mask < 4096; ++mask) {     // bits 0-2 pool read through, 3-5 upsample + concat read through, 6-8 two-source conv,
+                                                  // 9-11 pool written by the producer's epilogue (Ctx::pool_by_producer)
+        if (((mask >> 3) & (mask >> 6) & 7) != 0 || (mask & (mask >> 9) & 7) != 0) continue;       // (a block is one or the other)
         if (h->simple && mask != 0) break;                         // (plan_simple materialises every resampling op)
         h->dry_fuse_mask = mask;
         h->arena.peak = 0;
@@ -1308,6 +1310,10 @@ static int stats_slots_reserved(int HW, int C, int slots) {
                              stats_slots(HW, std::max(HW / 4, 1), 1)));             // conv_in_kernel's four row parts
 }
 
+// launches of this process whose epilogue also wrote the MaxPool2d(2) of their output (host-side count:
+// spdm_debug_pooled_epilogue_launches)
+static int g_pooled_epilogue_launches = 0;
+
 struct Ctx {
     spdm_handle* h;
     int B;
@@ -1413,18 +1419,56 @@ struct Ctx {
     }
     // one 3x3 conv: reads `in` (finishing its pending GroupNorm, + GELU if asked, in the load
     // prologue), writes the raw output and its GroupNorm partial sums
-    Value conv(const Value& in, const ConvW& w, int level, bool gelu, const float* gamma, const float* beta) {
+    // pool_out (pool_by_producer said yes): the launch also writes the RAW MaxPool2d(2) map of its output there (GemmArgs::pool_dst);
+    // pooled_of: `in` is such a map, and the GroupNorm pending on it is that of the finer level's value *pooled_of (PRO_GN_POOLED)
+    Value conv(const Value& in, const ConvW& w, int level, bool gelu, const float* gamma, const float* beta,
+               const Tensor* pool_out = nullptr, const Value* pooled_of = nullptr) {
         // by shape before the weights are known (the dry run at create); afterwards a tensor outside the split format's
         // range has no split copy and stays on the exact fp32 kernel (Loader::conv)
         const int split = (h->split && w.cin % 32 == 0 && (!h->weights_loaded || w.ws)) ? 1 : 0;
-        const int pro = in.pending_gn() ? (gelu ? PRO_GN_GELU : PRO_GN) : PRO_NONE;
-        auto args = [&](const Value* out) { return conv_args(w, level, split, pro, asrc(in), 0, AffineSrc{}, out); };
+        const int pro = pooled_of ? PRO_GN_POOLED : in.pending_gn() ? (gelu ? PRO_GN_GELU : PRO_GN) : PRO_NONE;
+        AffineSrc src = asrc(in);
+        if (pooled_of) { src.st = pooled_of->st.ref; src.gamma = pooled_of->gamma; src.beta = pooled_of->beta; }
+        auto args = [&](const Value* out) {
+            GemmArgs a = conv_args(w, level, split, pro, src, 0, AffineSrc{}, out);
+            if (pool_out && out) { a.pool_dst = pool_out->p; a.pool_ld = pool_out->C; a.pool_gamma = gamma; }
+            return a;
+        };
         Value out = conv_out(w, level, gemm_geometry(args(nullptr)), gamma, beta, w.cnorm);
         if (err || dry) return out;
         if ((split ? w.ws : w.w) == nullptr) { err = fail(SPDM_ERR_STATE, "plan: conv weights missing"); return out; }
         if (in.t.C != w.cin) { err = fail(SPDM_ERR_INVALID, "plan: conv input has %d channels, weight expects %d", in.t.C, w.cin); return out; }
         gemm(args(&out), "conv3x3 implicit GEMM");
+        if (pool_out) ++g_pooled_epilogue_launches;
         return out;
+    }
+    // ---- MaxPool2d(2) written by the epilogue of the kernel that produces the pooled tensor: no pool_kernel launch,
+    //      the tensor is not read back.  Asked BEFORE the producer is launched.  SPDM_TUNE23 (read once per process): bit i = pool i;
+    //      default 7, 0 = pool_kernel everywhere ----
+    // would conv_fused(PRO_POOL) take this block's first convolution?  (conv_skinny at small batch: it keeps priority)
+    bool pool_read_through(const ConvW& w, int level, int C_in) const {
+        if (err || !h->split || (h->sw & SW_NO_FUSED_SRC) || h->arena.keep || h->d_partial == nullptr) return false;
+        if (dry) return (h->dry_fuse_mask >> (level - 1)) & 1;
+        if (!h->weights_loaded || !w.ws || !w.wf || C_in != w.cin) return false;
+        return gemm_takes_fused_source(conv_args(w, level, 1, PRO_POOL, AffineSrc{nullptr, C_in}, 0, AffineSrc{}, nullptr));
+    }
+    // common part: pool i (level i -> i + 1), consumer w_next = the first convolution of down block i
+    bool pool_by_producer(int i, const ConvW& w_next, int C_in) const {
+        if (err || !h->split || h->arena.keep || !((spdm_tune(23, 7) >> i) & 1) || (Hl(i) & 1) || (Wl(i) & 1)) return false;
+        if (pool_read_through(w_next, i + 1, C_in)) return false;
+        if (dry) return (h->dry_fuse_mask >> (9 + i)) & 1;
+        return h->weights_loaded;
+    }
+    // pool 1: inc's second convolution (w, level 0) on conv_reg.hip at width 8 writes the RAW pooled map (the GroupNorm pending on
+    // x1 stays pending on it), and down1's first convolution, on conv_reg.hip too, applies it on load (PRO_GN_POOLED)
+    bool pool_by_conv_reg(const ConvW& w, const ConvW& w_next) const {
+        if (!pool_by_producer(0, w_next, w.cout) || Wl(0) != 8 || w.cout != w_next.cin) return false;
+        if (dry) return true;
+        if (!w.ws || !w.wf || !w_next.ws || !w_next.wf) return false;
+        const AffineSrc none{};
+        return gemm_geometry(conv_args(w, 0, 1, PRO_GN_GELU, none, 0, none, nullptr)).reg &&
+               gemm_geometry(conv_args(w_next, 1, 1, PRO_GN_POOLED, none, 0, none, nullptr)).reg &&
+               pooled_stats_serial(StatsRef{nullptr, 0, 64, 1, HWl(0), 0.0});       // (x1's slots, one per 64-row wave tile)
     }
     void prof_begin() {
         if (!h->prof || h->prof_open >= 0 || dry || err) return;
@@ -1597,9 +1641,18 @@ struct Ctx {
         if (h->split && sa_tail_supported(C, h->sw) && (!h->weights_loaded || w.tail_wf[0])) {
             // out_proj + residual + LayerNorm + ff_self + residual in one kernel (sa_tail.hip)
             Tensor out = talloc(C, level);
-            if (!err && !dry)
+            // pools 2 and 3: the block output is finished, so the tail's epilogue writes its plain MaxPool2d(2) (pool_want: the
+            // plan asked for it; taken where every window lies inside one workgroup's rows)
+            float* pool = nullptr;
+            if (pool_want && sa_tail_pools(C, L, Wl(level), rows)) {
+                *pool_want = talloc(C, level + 1);
+                pool = pool_want->p;
+            }
+            if (!err && !dry) {
                 check(launch_sa_tail(C, att.p, x.p, out.p, rows, w.tail_wf[0], w.tail_wf[1], w.tail_wf[2], w.out_proj.b, w.ff1.b,
-                                        w.ff2.b, w.ff_ln_g, w.ff_ln_b, abp, L, s, fs), "attention tail");
+                                        w.ff2.b, w.ff_ln_g, w.ff_ln_b, abp, L, s, fs, nullptr, pool, Wl(level)), "attention tail");
+                if (pool) ++g_pooled_epilogue_launches;
+            }
             free(att);
             free(x);
             if (ab) free(*ab);
@@ -1699,6 +1752,7 @@ struct Ctx {
         tap(name, m);
     }
     int h_tcount = 1;
+    Tensor* pool_want = nullptr;      // set around film_attention: sa_tail may write the MaxPool2d(2) of the block output here
     int fuse_slot = 0;     // which resampling op conv_fused is being asked about (dry runs: bit of dry_fuse_mask)
     int adv = -2;          // loop bookkeeping done by conv_in_kernel: -2 none, -1 advance, >= 0 set
 };
@@ -1715,7 +1769,11 @@ static int plan_unet(Ctx& c, const float* x, bool use_cond, Tensor* feat_out) {
     if (!c.err && !c.dry)
         c.check(launch_conv_in(x, h->w_inc_first, v0.t.p, v0.st.p, B, h->cfg.horizon, h->cfg.state_dim, h->Hp, h->Wp,
                                h->lh, h->lw, h->d_step, h->d_t, h->d_timesteps, h->n_steps, c.adv, c.s, c.Bg()), "conv_in");
-    Value x1 = c.conv(v0, h->inc.second, 0, /*gelu=*/true, h->inc.gamma, h->inc.beta);   // x1 = GN(raw), pending
+    // (pooled[i]: the input of down block i where its producer wrote it -- reserved before that launch)
+    Tensor pooled[3];
+    const bool pool1 = c.pool_by_conv_reg(h->inc.second, h->down[0].dc1.first);
+    if (pool1) pooled[0] = c.talloc(64, 1);
+    Value x1 = c.conv(v0, h->inc.second, 0, /*gelu=*/true, h->inc.gamma, h->inc.beta, pool1 ? &pooled[0] : nullptr);   // x1 = GN(raw), pending
     c.free(v0);
     c.tap_gn("x1", x1, 0);
 
@@ -1730,7 +1788,17 @@ static int plan_unet(Ctx& c, const float* x, bool use_cond, Tensor* feat_out) {
         // `cur` stays alive: it is a skip connection
         Value a, mid;
         c.fuse_slot = i;
-        if (c.conv_fused(PRO_POOL, cur, nullptr, h->down[i].dc1.first, lout, h->down[i].dc1.gamma, h->down[i].dc1.beta, &mid)) {
+        if (pooled[i].valid) {
+            // MaxPool2d(2) written by cur's producer: raw with cur's GroupNorm pending (pool 1), or finished (pools 2 and 3)
+            Value p;
+            p.t = pooled[i];
+            c.prof_begin();
+            mid = c.conv(p, h->down[i].dc1.first, lout, /*gelu=*/false, h->down[i].dc1.gamma, h->down[i].dc1.beta, nullptr,
+                         cur.pending_gn() ? &cur : nullptr);
+            c.free(p);
+            a = c.conv(mid, h->down[i].dc1.second, lout, /*gelu=*/true, h->down[i].dc1.gamma, h->down[i].dc1.beta);
+            c.free(mid);
+        } else if (c.conv_fused(PRO_POOL, cur, nullptr, h->down[i].dc1.first, lout, h->down[i].dc1.gamma, h->down[i].dc1.beta, &mid)) {
             c.prof_begin();      // MaxPool2d(2) read through by the block's first conv (small grids)
             a = c.conv(mid, h->down[i].dc1.second, lout, /*gelu=*/true, h->down[i].dc1.gamma, h->down[i].dc1.beta);
             c.free(mid);
@@ -1744,7 +1812,9 @@ static int plan_unet(Ctx& c, const float* x, bool use_cond, Tensor* feat_out) {
         }
         Value b2 = c.double_conv(a, h->down[i].dc2, lout);
         c.prof_end();
+        if (i < 2 && c.pool_by_producer(i + 1, h->down[i + 1].dc1.first, h->down[i].cout)) c.pool_want = &pooled[i + 1];
         const Tensor y = c.film_attention(b2, h->down[i], i, lout, use_cond, dn[i]);
+        c.pool_want = nullptr;
         c.tap(xn[i], y);
         Value nv;
         nv.t = y;
@@ -3968,6 +4038,7 @@ static int g_op_gemm_whole = -1;
 extern "C" int spdm_debug_whole_tiles(void) { return g_op_gemm_whole; }
 // ... how many launches of this process (plan or spdm_op_gemm; a captured step counts once) read the upsample through conv_wide's loader
 extern "C" int spdm_debug_fused_upsample_launches(void) { return gemm_wide_upcat_launches(); }
+extern "C" int spdm_debug_pooled_epilogue_launches(void) { return g_pooled_epilogue_launches; }
 
 // op-level test hook: one launch_gemm exactly as the plan builds it, on the caller's tensors (include/spdm.h)
 extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {

@@ -1,0 +1,201 @@
+"""MaxPool2d(2) written by the producer's epilogue against the pool_kernel launch it replaces.
+
+At large batch the three pooled tensors of the encoder are written by the kernels that produce the tensor being pooled:
+  pool 1  conv_reg64_kernel<., 8> (inc's second conv) stores, beside x1, the per-window max or min of the RAW values -- whichever
+          the sign of the channel's GroupNorm gain turns into the max of the finished ones -- and down1's first conv, on
+          conv_reg64 too, applies x1's pending GroupNorm on load in pool_kernel's arithmetic (PRO_GN_POOLED);
+  pool 2, 3  sa_tail_kernel<128> / <256> (sa1, sa2) store the plain 2 x 2 max of the finished block output.
+The consumer's staged input equals pool_kernel's output bit for bit, so every iterate of a sampling loop must be THE SAME BITS
+with the route on (SPDM_TUNE23=7, the default), off (0) and with each single pool (1, 2, 4).  The knob is read once per process:
+one child process per knob value runs every scenario below and the tests compare what they saved.
+spdm_debug_pooled_epilogue_launches() counts the producer launches that wrote a pooled map; the expected count per U-Net
+evaluation is worked out from the launch geometry (spdm_debug_geometry), not assumed.
+
+random_state_dict's GroupNorm gains are all positive, which would leave the min branch of pool 1 idle: the state dict here gets
+inc.norm.weight with mixed signs, an exact zero and a gain small enough to underflow against rstd.
+"""
+import ctypes
+import os
+import subprocess
+import sys
+
+import pytest
+import torch
+
+from state_policy_diffusionmodel_amd import _lib
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KNOB = "SPDM_TUNE23"
+KNOBS = (None, 7, 0, 1, 2, 4)          # None: the variable unset (the default, 7); only the first scenario
+
+# name: (horizon, batch, engine keywords, environment of the handle's creation, scenarios run for single-bit knobs too)
+# The smallest batch at which the plan takes each pool that way, horizon 32: pool 1 from 256 (conv_reg64 needs 256 wave tiles of
+# 64 rows, and level 1 has 64 rows per sample), pool 2 from 257 and pool 3 from 1025 (below, the next block's first convolution
+# is on the small-grid kernel, which reads the MaxPool through itself and keeps priority).  1025 is odd, so sa_tail<256>'s last
+# block -- two samples of 16 rows -- is half empty there.
+SCENARIOS = {
+    "h32": (32, 1025, {}, {}, True),
+    "h32_plain": (32, 1025, {}, {"SPDM_NO_GRAPH": "1"}, False),    # the same without graph replay
+    "h32_even": (32, 1026, {}, {}, False),                # whole sa_tail blocks
+    "h32_b256": (32, 256, {}, {}, False),                 # pool 1 alone, at its threshold
+    "h64": (64, 513, {}, {}, True),                       # Hp = 64: eight wave tiles and eight statistics slots per sample
+    "h16": (16, 2049, {}, {}, True),                      # Hp = 16: level 1 is 8 x 4, below conv_reg64's smallest map (16 x 4)
+    "debug": (32, 1025, {"debug": True}, {}, False),      # debug-tap handle
+    "no_reg64": (32, 1025, {}, {"SPDM_NO_REG64": "1"}, False),
+    "no_attention": (32, 1025, {"attention": False}, {}, False),
+}
+WANT = {"h32": 7, "h32_plain": 7, "h32_even": 7, "h32_b256": 1, "h64": 7, "h16": 6, "debug": 0, "no_reg64": 6, "no_attention": 1}
+
+_CHILD = r"""
+import os, sys
+sys.path.insert(0, sys.argv[1])
+import torch
+from state_policy_diffusionmodel_amd import _lib
+from state_policy_diffusionmodel_amd.engine import SpdmEngine
+from state_policy_diffusionmodel_amd.schedulers import DDPMScheduler
+from state_policy_diffusionmodel_amd.weights import random_state_dict
+scenarios = eval(sys.argv[3])
+D, obs_h, obs_dim, N = 3, 2, 7, 4
+count = _lib.load().spdm_debug_pooled_epilogue_launches
+out = {}
+for name, (H, B, kw, env) in scenarios.items():
+    attention = kw.get("attention", True)
+    sd = random_state_dict(obs_h * obs_dim, seed=5, attention=attention)
+    gain = sd["inc.norm.weight"].copy()        # (numpy float32)
+    gain[1::3] = -gain[1::3]                   # 21 negative channels
+    gain[5] = -2.5
+    gain[8] = 0.0
+    gain[12] = 1e-44                           # rstd * gain underflows towards zero
+    gain[13] = -1e-44
+    sd["inc.norm.weight"] = gain
+    g = torch.Generator().manual_seed(1)
+    cond = torch.randn(B, 1, obs_h, obs_dim, generator=g).cuda()
+    x_T = torch.rand(B, 1, H, D, generator=g).cuda()
+    noise = torch.randn(N, B, 1, H, D, generator=g).cuda()
+    os.environ.update(env)                     # (the switches are read when the handle is created)
+    eng = SpdmEngine(H, D, obs_h * obs_dim, max_batch=B, num_train_timesteps=N, **kw)
+    for k in env:
+        del os.environ[k]
+    eng.load_state_dict(sd)
+    sched = DDPMScheduler(num_train_timesteps=N)
+    sched.set_timesteps(N)
+    eng.set_scheduler(sched)
+    c0 = int(count())
+    eps = eng.unet_forward(x_T, torch.tensor([2]), cond)
+    torch.cuda.synchronize()
+    per_eval = int(count()) - c0
+    _, hist = eng.sample(cond, x_T, noise=noise, history=True)
+    out[name] = {"hist": hist.cpu(), "eps": eps.cpu(), "per_eval": per_eval, "graphs": eng.graph_captures}
+    eng.close()
+torch.save(out, sys.argv[2])
+"""
+
+
+def _geometry(M, N, K, HW, W, taps, sw=0):
+    out = (ctypes.c_int32 * 10)()
+    assert _lib.load().spdm_debug_geometry(M, N, K, HW, W, taps, sw, ctypes.byref(out)) == 0
+    return {"skinny": out[5] & 1, "reg": out[5] >> 1}
+
+
+def expected_pools(H, B, attention=True, no_reg64=False):
+    """Bit mask of the pools whose producer the plan's rule lets write the pooled map (csrc/spdm_api.hip pool_by_conv_reg,
+    pool_by_producer; csrc/sa_tail.hip sa_tail_pools), from the launch geometry."""
+    Hp, Wp = (H + 7) // 8 * 8, 8
+    hw = [Hp * Wp >> (2 * i) for i in range(4)]
+    w = [Wp >> i for i in range(4)]
+    mask = 0
+    # pool 1: inc's second conv (level 0) and down1's first conv (level 1) both on conv_reg64; x1's statistics in at most 8 slots
+    if not no_reg64 and _geometry(B * hw[0], 64, 64, hw[0], w[0], 9)["reg"] and _geometry(B * hw[1], 64, 64, hw[1], w[1], 9)["reg"] \
+            and hw[0] // 64 <= 8:
+        mask |= 1
+    # pools 2, 3: sa_tail's blocks of 8192 / C rows hold whole windows; the consumer is not the small-grid kernel
+    for bit, lvl, C in ((2, 1, 128), (4, 2, 256)):
+        whole = hw[lvl] % (2 * w[lvl]) == 0 and (8192 // C) % (2 * w[lvl]) == 0
+        if attention and whole and not _geometry(B * hw[lvl + 1], C, C, hw[lvl + 1], w[lvl + 1], 9 if w[lvl + 1] > 1 else 3)["skinny"]:
+            mask |= bit
+    return mask
+
+
+@pytest.fixture(scope="module")
+def runs(tmp_path_factory):
+    """One child per knob value, side by side: {knob: {scenario: {hist, eps, per_eval, graphs}}}."""
+    tmp = tmp_path_factory.mktemp("pooled")
+    procs = {}
+    for knob in KNOBS:
+        env = {k: v for k, v in os.environ.items() if k != KNOB and k not in ("SPDM_NO_REG64", "SPDM_NO_GRAPH")}
+        if knob is not None:
+            env[KNOB] = str(knob)
+        sc = {n: s[:4] for n, s in SCENARIOS.items() if knob in (7, 0) or (s[4] and knob is not None) or n == "h32"}
+        out = tmp / f"knob{knob}.pt"
+        procs[knob] = (subprocess.Popen([sys.executable, "-c", _CHILD, ROOT, str(out), repr(sc)], env=env, stdout=subprocess.PIPE,
+                                        stderr=subprocess.PIPE, text=True), out)
+    got = {}
+    for knob, (p, out) in procs.items():
+        _, err = p.communicate(timeout=600)
+        assert p.returncode == 0, (knob, err[-3000:])
+        got[knob] = torch.load(out)
+    return got
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+
+def test_default_is_all_three_pools(runs):
+    """Without the variable the route is on for every pool the rule admits."""
+    assert expected_pools(32, 1025) == 7
+    assert runs[None]["h32"]["per_eval"] == 3
+    assert _same_bits(runs[None]["h32"]["hist"], runs[0]["h32"]["hist"])
+
+
+def test_flagship_shape_takes_all_three_and_below_threshold_none_of_pool_1():
+    assert expected_pools(32, 4096) == 7
+    assert expected_pools(32, 255) == 0              # level 1 has 255 wave tiles: down1's first conv is not on conv_reg64
+    assert expected_pools(32, 1024) == 3             # down3's first conv is still on the small-grid kernel
+
+
+@pytest.mark.parametrize("name", ["h32", "h64", "h16", "h32_even", "h32_b256"])
+def test_iterates_identical_with_the_route_on_and_off(runs, name):
+    on, off = runs[7][name], runs[0][name]
+    assert torch.isfinite(on["hist"]).all() and on["hist"].shape[0] == 5
+    assert _same_bits(on["eps"], off["eps"]), name
+    assert _same_bits(on["hist"], off["hist"]), name
+
+
+@pytest.mark.parametrize("knob", [1, 2, 4])
+@pytest.mark.parametrize("name", ["h32", "h64", "h16"])
+def test_each_single_pool_identical(runs, knob, name):
+    assert _same_bits(runs[knob][name]["eps"], runs[0][name]["eps"]), (knob, name)
+    assert _same_bits(runs[knob][name]["hist"], runs[0][name]["hist"]), (knob, name)
+
+
+@pytest.mark.parametrize("name", ["h32", "h64", "h16", "h32_even", "h32_b256"])
+def test_counter_matches_the_rule(runs, name):
+    H, B = SCENARIOS[name][:2]
+    want = expected_pools(H, B)
+    assert want == WANT[name], (name, want)          # (h16: level 1 is below conv_reg64's smallest map, pool 1 keeps pool_kernel)
+    for knob in KNOBS:
+        if name in runs[knob]:
+            assert runs[knob][name]["per_eval"] == bin(want & (7 if knob is None else knob)).count("1"), (name, knob, runs[knob][name]["per_eval"])
+
+
+@pytest.mark.parametrize("name,kw", [("debug", dict(none=True)), ("no_reg64", dict(no_reg64=True)), ("no_attention", dict(attention=False))])
+def test_negative_routes_keep_pool_kernel(runs, name, kw):
+    """A debug-tap handle keeps every pool_kernel launch, SPDM_NO_REG64 that of pool 1, the model without attention those of pools
+    2 and 3 -- and the results are those of the route switched off."""
+    H, B = SCENARIOS[name][:2]
+    want = 0 if kw.get("none") else expected_pools(H, B, attention=kw.get("attention", True), no_reg64=kw.get("no_reg64", False))
+    assert want == WANT[name]
+    assert runs[7][name]["per_eval"] == bin(want).count("1"), (name, runs[7][name]["per_eval"])
+    assert runs[0][name]["per_eval"] == 0
+    assert _same_bits(runs[7][name]["hist"], runs[0][name]["hist"]), name
+    assert _same_bits(runs[7][name]["eps"], runs[0][name]["eps"]), name
+
+
+def test_graph_replay_equals_plain_launches(runs):
+    g, p = runs[7]["h32"], runs[7]["h32_plain"]
+    assert g["graphs"] >= 1 and p["graphs"] == 0, (g["graphs"], p["graphs"])
+    assert g["per_eval"] == 3 and p["per_eval"] == 3
+    assert _same_bits(g["hist"], p["hist"])
