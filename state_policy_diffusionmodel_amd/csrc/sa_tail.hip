@@ -518,8 +518,25 @@ __device__ __forceinline__ float head_exp_neg(float x) {      // exp(x), x <= 0,
 
 #undef TAIL_SPLIT2
 #define TAIL_SPLIT2 tsplit2_plain
-template <int C>
-__global__ __launch_bounds__(256, 2) void sa_head_kernel(const SaHeadArgs a) {
+__device__ __forceinline__ float max_xor16(float v) {
+    const unsigned u = __builtin_bit_cast(unsigned, v);
+    const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+    return fmaxf(__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1]));
+}
+typedef unsigned tu32x4 __attribute__((ext_vector_type(4)));
+// eight pre-scaled values -> the {hi, lo} fp16 operands of one lane (split_pair_f16: the bits of hi = fp16(x), lo = fp16(x - hi))
+__device__ __forceinline__ void head_split8(const float (&x)[8], tf16x8& hi, tf16x8& lo) {
+    tu32x4 h, l;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { unsigned hh, ll; split_pair_f16(x[2 * i], x[2 * i + 1], hh, ll); h[i] = hh; l[i] = ll; }
+    hi = __builtin_bit_cast(tf16x8, h);
+    lo = __builtin_bit_cast(tf16x8, l);
+}
+
+// Both bodies of sa_head_kernel: the slab stage is common; WAVES = each wave runs one head in registers (sa_head_kernel),
+// !WAVES = the four waves walk the heads together through LDS (sa_head_serial_kernel, SPDM_TUNE24).
+template <int C, bool WAVES>
+__device__ __forceinline__ void sa_head_body(const SaHeadArgs& a) {
     using S = TailShape<C>;
     constexpr int T_C = C, T_M = S::TM, NCH = S::NCH, RPP = S::RPP, TPR = S::TPR;
     constexpr int NP = S::NP;
@@ -585,6 +602,177 @@ __global__ __launch_bounds__(256, 2) void sa_head_kernel(const SaHeadArgs a) {
     }
     __syncthreads();
 
+    if constexpr (WAVES) {
+        // ---- wave w = head w, everything in registers: no LDS write and no barrier from here on.  A 16 x 16 accumulator tile of
+        //      a TRANSPOSED product is lane for lane an operand of the next product (sa_fused64_kernel's mapping):
+        //        k^T, q^T [d x token] = W slab^T  (weights A, slab rows B): lane (l16, kg) holds token l16, d = 4 kg + j
+        //                                -> A operand [key x d] of S^T (k) and B operand [d x query] (q); the 8 k-slots of a lane
+        //                                   are d = 4 kg + j of two consecutive d-tiles, the same order in both operands;
+        //        v [token x d] = slab W^T        (slab rows A, weights B): lane holds d = l16, token = 4 kg + j
+        //                                -> A operand [d x key] of O^T, k-slots = tokens 4 kg + j of two consecutive token tiles;
+        //        S^T [key x query] = k q^T:   lane holds query l16, keys 16 kt + 4 kg + j; softmax of a query = its registers, then
+        //                                   the four lanes l16 + 16 kg (xor 16, xor 32); P split -> B operand [key x query] of
+        //        O^T [d x query] = v^T P^T:   lane holds query l16, d = 16 dt + 4 kg + j: one 16-byte store per lane and d-tile. ----
+        constexpr int NDS = D / 32;                     // 32-wide d steps of the scores (1 | 2)
+        constexpr int NKS = T_M / 32;                   // 32-wide key steps of O^T (2 | 1)
+        constexpr int NCT = 2;                          // 16-column tiles of a product per pass over the slab
+        constexpr int NPS = NDT / NCT;                  // passes of a product (1 | 2)
+        // weight chunks in registers.  3: 166 | 156 registers, three workgroups per CU (<= 168); traced at B = 4096 sa1 / sa2
+        // 2 chunks 127 / 107 us, 3 chunks 125 / 96, 4 chunks at C = 128 (180 registers: two workgroups per CU) 136
+        constexpr int RING = 3;
+        const int h = wave;
+        const float qscale = (D == 32) ? 0.17677669529663687f : 0.125f;         // 1 / sqrt(d)
+        constexpr size_t WCHUNK = (size_t)(3 * C / 16) * 2 * 256;
+        tf16x8 Kop[NKT][NDS][2], Qop[NKT][NDS][2], Vop[NDT][NKS][2];          // {hi, lo}: 3 x 32 registers at either C
+        // weight fragments: two 16-column tiles x {hi, lo} per 32-channel chunk, a ring of RING chunks requested RING - 1 chunks
+        // ahead of their MFMAs, also across passes and products: one chunk is 12-24 MFMAs, an L2 round trip is several times that
+        tf16x8 fbw[RING][NCT][2];
+        // chunk t of the wave's weight stream: product t / (NPS NCH), pass (t / NCH) % NPS, 32-channel chunk t % NCH
+#define HEADW_LOAD_W(t_)                                                                             \
+    {                                                                                                \
+        const float* wp_ = a.wf + ((size_t)(((t_) / (NPS * NCH)) * (C / 16) + h * (D / 16) + (((t_) / NCH) % NPS) * NCT) * 2) * 256 \
+                           + (size_t)((t_) % NCH) * WCHUNK + lane * 4;                               \
+        _Pragma("unroll") for (int ct_ = 0; ct_ < NCT; ++ct_) {                                     \
+            fbw[(t_) % RING][ct_][0] = *reinterpret_cast<const tf16x8*>(wp_ + ct_ * 512);            \
+            fbw[(t_) % RING][ct_][1] = *reinterpret_cast<const tf16x8*>(wp_ + ct_ * 512 + 256);      \
+        }                                                                                            \
+    }
+#pragma unroll
+        for (int t0 = 0; t0 < RING - 1; ++t0) HEADW_LOAD_W(t0)
+#pragma unroll
+        for (int g = 0; g < 3; ++g) {
+#pragma unroll
+            for (int p = 0; p < NPS; ++p) {
+                const float* bp = a.b_in + g * T_C + h * D + 16 * NCT * p;
+                tf32x4 acc[NCT][NKT];                    // [column tile of the pass][token tile]
+#pragma unroll
+                for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+                    for (int tt = 0; tt < NKT; ++tt) acc[ct][tt] = tf32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int kc = 0; kc < NCH; ++kc) {
+                    const int t = (g * NPS + p) * NCH + kc;
+                    if (t + RING - 1 < 3 * NPS * NCH) HEADW_LOAD_W(t + RING - 1)
+#pragma unroll
+                    for (int tt = 0; tt < NKT; ++tt) {
+                        const float* ap = Abuf + (kc * T_M + tt * 16 + l16) * T_LDK + kg * 4;
+                        const tf16x8 x_h = *reinterpret_cast<const tf16x8*>(ap), x_l = *reinterpret_cast<const tf16x8*>(ap + 16);
+#pragma unroll
+                        for (int ct = 0; ct < NCT; ++ct) {
+                            const tf16x8 w_h = fbw[t % RING][ct][0], w_l = fbw[t % RING][ct][1];
+                            if (g < 2) {                // transposed: the accumulator holds token l16, d = 4 kg + j
+                                acc[ct][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w_h, x_h, acc[ct][tt], 0, 0, 0);
+                                acc[ct][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w_l, x_h, acc[ct][tt], 0, 0, 0);
+                                acc[ct][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w_h, x_l, acc[ct][tt], 0, 0, 0);
+                            } else {                    // v: token 4 kg + j, d = l16
+                                acc[ct][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(x_h, w_h, acc[ct][tt], 0, 0, 0);
+                                acc[ct][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(x_h, w_l, acc[ct][tt], 0, 0, 0);
+                                acc[ct][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(x_l, w_h, acc[ct][tt], 0, 0, 0);
+                            }
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);  // (chunk by chunk: loads hoisted across chunks cost registers, then scratch)
+                }
+                // bias (+ 1 / sqrt d on q), x 16, split, into operand order
+                if (g < 2) {
+#pragma unroll
+                    for (int s2 = 0; s2 < NCT / 2; ++s2) {  // two column tiles = one 32-wide d step of the scores
+                        // (x 16 is exact, so it moves: q = (acc DESCALE + b) (16 qscale), k = acc (16 DESCALE) + 16 b -- the same bits)
+                        tf32x4 bias[2] = {*reinterpret_cast<const tf32x4*>(bp + 32 * s2 + 4 * kg), *reinterpret_cast<const tf32x4*>(bp + 32 * s2 + 16 + 4 * kg)};
+                        if (g == 1) { bias[0] *= T_ACT_SCALE; bias[1] *= T_ACT_SCALE; }
+#pragma unroll
+                        for (int tt = 0; tt < NKT; ++tt) {
+                            float xs[8];
+#pragma unroll
+                            for (int c2 = 0; c2 < 2; ++c2)
+#pragma unroll
+                                for (int j = 0; j < 4; ++j)
+                                    xs[4 * c2 + j] = (g == 0) ? __fmaf_rn(acc[2 * s2 + c2][tt][j], T_DESCALE, bias[c2][j]) * (qscale * T_ACT_SCALE)
+                                                              : __fmaf_rn(acc[2 * s2 + c2][tt][j], T_DESCALE * T_ACT_SCALE, bias[c2][j]);
+                            if (g == 0) head_split8(xs, Qop[tt][p * (NCT / 2) + s2][0], Qop[tt][p * (NCT / 2) + s2][1]);
+                            else head_split8(xs, Kop[tt][p * (NCT / 2) + s2][0], Kop[tt][p * (NCT / 2) + s2][1]);
+                        }
+                    }
+                } else {
+#pragma unroll
+                    for (int ct = 0; ct < NCT; ++ct) {
+                        const float bias = bp[16 * ct + l16] * T_ACT_SCALE;
+#pragma unroll
+                        for (int ks = 0; ks < NKS; ++ks) {
+                            float xs[8];
+#pragma unroll
+                            for (int t2 = 0; t2 < 2; ++t2)
+#pragma unroll
+                                for (int j = 0; j < 4; ++j) xs[4 * t2 + j] = __fmaf_rn(acc[ct][2 * ks + t2][j], T_DESCALE * T_ACT_SCALE, bias);
+                            head_split8(xs, Vop[NCT * p + ct][ks][0], Vop[NCT * p + ct][ks][1]);
+                        }
+                    }
+                }
+            }
+        }
+#undef HEADW_LOAD_W
+        // ---- one query tile at a time: S^T, softmax over the keys of the query's own sample, O^T, out of the kernel ----
+#pragma unroll
+        for (int qt = 0; qt < NKT; ++qt) {
+            tf32x4 sc[NKT];
+#pragma unroll
+            for (int kt = 0; kt < NKT; ++kt) {
+                sc[kt] = tf32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int s = 0; s < NDS; ++s) {
+                    sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Kop[kt][s][0], Qop[qt][s][0], sc[kt], 0, 0, 0);
+                    sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Kop[kt][s][1], Qop[qt][s][0], sc[kt], 0, 0, 0);
+                    sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Kop[kt][s][0], Qop[qt][s][1], sc[kt], 0, 0, 0);
+                }
+            }
+            // key and query lie in one sample (L a power of two, samples aligned) <=> key ^ query < L; 16 kt + j and 4 kg share no bit
+            const unsigned qx = (unsigned)((4 * kg) ^ (qt * 16 + l16));
+            float mx = -3.0e38f;
+#pragma unroll
+            for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bool own = ((unsigned)(kt * 16 + j) ^ qx) < (unsigned)L;
+                    sc[kt][j] = own ? sc[kt][j] * (1.0f / 256.0f) : -3.0e38f;
+                    mx = fmaxf(mx, sc[kt][j]);
+                }
+            mx = max_xor32(max_xor16(mx));
+            float sum = 0.f;
+#pragma unroll
+            for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    sc[kt][j] = (sc[kt][j] > -1.0e38f) ? head_exp_neg(sc[kt][j] - mx) : 0.f;
+                    sum += sc[kt][j];
+                }
+            sum = sum_xor32(sum_xor16(sum));
+            const float inv = 1024.0f / sum;
+            tf16x8 Pop[NKS][2];
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) {
+                float ps[8];
+#pragma unroll
+                for (int t2 = 0; t2 < 2; ++t2)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) ps[4 * t2 + j] = sc[2 * ks + t2][j] * inv;
+                head_split8(ps, Pop[ks][0], Pop[ks][1]);
+            }
+            const int row = m0 + qt * 16 + l16;
+#pragma unroll
+            for (int dt = 0; dt < NDT; ++dt) {
+                tf32x4 o = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ks = 0; ks < NKS; ++ks) {
+                    o = __builtin_amdgcn_mfma_f32_16x16x32_f16(Vop[dt][ks][0], Pop[ks][0], o, 0, 0, 0);
+                    o = __builtin_amdgcn_mfma_f32_16x16x32_f16(Vop[dt][ks][1], Pop[ks][0], o, 0, 0, 0);
+                    o = __builtin_amdgcn_mfma_f32_16x16x32_f16(Vop[dt][ks][0], Pop[ks][1], o, 0, 0, 0);
+                }
+                if (row < M) *reinterpret_cast<tf32x4*>(a.att + (size_t)row * T_C + h * D + dt * 16 + 4 * kg) = o * (1.0f / 16384.0f);
+            }
+        }
+        (void)Vt; (void)Ps; (void)Ks;
+    } else {
+    // ---- the head-serial body: the four waves walk the heads together, q / k / v^T and P through LDS ----
     // product tile of this wave: 16 rows x 32 columns of a head's q, k or v  (C = 128: 4 row tiles x the head's 32 columns;
     // C = 256: 2 row tiles x 2 halves of the head's 64 columns)
     const int rtw = (C == 128) ? wave : (wave >> 1);
@@ -725,12 +913,18 @@ __global__ __launch_bounds__(256, 2) void sa_head_kernel(const SaHeadArgs a) {
         }
         __syncthreads();                                // the head's tiles are free for the next head
     }
+    }
 #undef TAIL_LOAD_B
 #undef TAIL_LOAD_FA
 #undef TAIL_WRITE_SLAB
 #undef TAIL_GEMM
 #undef TAIL_ACC_TO_TILE
 }
+
+template <int C>
+__global__ __launch_bounds__(256, 2) void sa_head_kernel(const SaHeadArgs a) { sa_head_body<C, true>(a); }
+template <int C>
+__global__ __launch_bounds__(256, 2) void sa_head_serial_kernel(const SaHeadArgs a) { sa_head_body<C, false>(a); }
 
 }  // namespace
 
@@ -795,15 +989,27 @@ hipError_t launch_sa_head(int C, const float* x, float* att, int rows, const flo
     a.x = x; a.att = att; a.M = rows; a.wf = wf_in; a.b_in = b_in; a.ln_g = ln_g; a.ln_b = ln_b; a.ab = ab; a.L = L;
     if (fs) { a.fs = *fs; a.fs.on = 1; }
     const int TM = 8192 / C, D = C / 4;
-    const size_t lds = (size_t)(C / 32) * TM * T_LDK * sizeof(float) + ((size_t)2 * TM * (2 * D + 8) + (size_t)D * (2 * TM + 8)) * sizeof(_Float16);
-    // (in-kernel FiLM coefficient rows sit in the q / k / v^T region, dead until the first head's tiles are written)
-    if (fs && (size_t)film_rows_cap(TM, L) * 2 * C * sizeof(float) > ((size_t)2 * TM * (2 * D + 8) + (size_t)D * (2 * TM + 8)) * sizeof(_Float16)) return hipErrorInvalidValue;
-    const void* kern = C == 128 ? reinterpret_cast<const void*>(sa_head_kernel<128>) : reinterpret_cast<const void*>(sa_head_kernel<256>);
+    // one head per wave, in registers (default), or the head-serial body: SPDM_TUNE24 bit 0 = C 128, bit 1 = C 256
+    const bool per_wave = (spdm_tune(24, 3) >> (C == 256 ? 1 : 0)) & 1;
+    const size_t slab = (size_t)(C / 32) * TM * T_LDK * sizeof(float);
+    const size_t film = (size_t)film_rows_cap(TM, L) * 2 * C * sizeof(float);
+    const size_t qkv = ((size_t)2 * TM * (2 * D + 8) + (size_t)D * (2 * TM + 8)) * sizeof(_Float16);
+    // in-kernel FiLM coefficient rows sit behind the slab: LDS of their own (per wave: nothing else is there), or the q / k / v^T
+    // region, dead until the first head's tiles are written (head-serial); sa_tail_film_local bounds them by 24 KB, as the tail's
+    const size_t lds = slab + (per_wave ? (fs ? film : 0) : qkv);
+    if (fs && !per_wave && film > qkv) return hipErrorInvalidValue;
+    const void* kern = per_wave ? (C == 128 ? reinterpret_cast<const void*>(sa_head_kernel<128>) : reinterpret_cast<const void*>(sa_head_kernel<256>))
+                                : (C == 128 ? reinterpret_cast<const void*>(sa_head_serial_kernel<128>) : reinterpret_cast<const void*>(sa_head_serial_kernel<256>));
     const int tiles = (rows + TM - 1) / TM;
     if (route) { route->kernel = SA_ROUTE_HEAD; route->waves = 4; route->grid = tiles; if (route->dry) return hipSuccess; }
     if (hipError_t e = allow_full_lds(kern); e != hipSuccess) return e;
-    if (C == 128) hipLaunchKernelGGL(sa_head_kernel<128>, dim3(tiles), dim3(256), lds, s, a);
-    else hipLaunchKernelGGL(sa_head_kernel<256>, dim3(tiles), dim3(256), lds, s, a);
+    if (per_wave) {
+        if (C == 128) hipLaunchKernelGGL(sa_head_kernel<128>, dim3(tiles), dim3(256), lds, s, a);
+        else hipLaunchKernelGGL(sa_head_kernel<256>, dim3(tiles), dim3(256), lds, s, a);
+    } else {
+        if (C == 128) hipLaunchKernelGGL(sa_head_serial_kernel<128>, dim3(tiles), dim3(256), lds, s, a);
+        else hipLaunchKernelGGL(sa_head_serial_kernel<256>, dim3(tiles), dim3(256), lds, s, a);
+    }
     return hipGetLastError();
 }
 
