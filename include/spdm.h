@@ -661,6 +661,65 @@ typedef struct {
 } spdm_policy_warm_start_args;
 int  spdm_policy_warm_start(int32_t device, const spdm_policy_warm_start_args* a, void* stream);
 
+/* spdm_policy_select keeps one of K candidate plans per environment: the one closest to the plan being executed
+ * (COHERENT) or the medoid of the set (MEDOID), and reports the candidates' spread as an uncertainty signal.  Stateless, ONE
+ * launch on `stream` (NULL: the null stream, and the call synchronises), one workgroup per environment, no atomics, no host
+ * synchronisation otherwise, no randomness.
+ *   E environments;  K candidates each, 1 <= K <= 64;  H, D: rows and columns of a plan, D >= 2, columns 0 and 1 are the
+ *     position;  inp_h: in-painted rows, 0 <= inp_h < H;  P = H - inp_h;
+ *   cols, 2 <= cols <= D: the columns of a row that enter a distance (2: positions only; D: positions and actions);
+ *   mode: SPDM_SELECT_MEDOID or SPDM_SELECT_COHERENT;
+ *   d_x0 (E K,H,D) float32: the candidates as the sampler returned them; candidate k of environment e is row e K + k;
+ *   d_guess float32, COHERENT only (NULL otherwise): the previous plan shifted and re-centred into the new window's frame, the
+ *     d_guess of spdm_policy_warm_start.  Row e guess_row_stride (of H D elements) belongs to environment e:
+ *     guess_row_stride = 1 for an (E,H,D) guess, K for the (E K,H,D) guess of a warm start made over K-fold repeated inputs;
+ *   rows, COHERENT only (0 otherwise), 1 <= rows <= P: the predicted rows, from row inp_h, that the previous plan still informs
+ *     (P - delta / step_size - (delta % step_size > 0) for a plan made delta pushes ago);
+ *   d_translation (E,2) float32, pos_min, pos_max: read for d_spread only;
+ *   d_chosen (E) int32, required;  d_x0_out (E,H,D) float32, required: row e is candidate chosen[e], copied exactly; it must
+ *     not overlap d_x0;  d_scores (E,K) float64, optional;  d_spread (E,P) float64, optional.
+ * Arithmetic: float64, every operation rounded on its own (no FMA), every sum serial in the order stated, so the result does not
+ * depend on how the work is spread over threads.  x_k is candidate k of the environment, g its guess row.
+ *   MEDOID distance: d(j,k) = sum over r = inp_h .. H-1 (outer, ascending) and c = 0 .. cols-1 (inner, ascending) of
+ *     ((double)x_j[r,c] - (double)x_k[r,c])^2, from 0.0: per term one subtraction, one multiplication, one addition into the
+ *     running sum.  d(j,k) and d(k,j) are the same bits;
+ *   MEDOID score: s_j = sum over k = 0 .. K-1, ascending, of d(j,k), from 0.0; d(j,j) is included;
+ *   COHERENT score: s_j = sum over r = inp_h .. inp_h+rows-1 and c < cols of ((double)x_j[r,c] - (double)g[r,c])^2, same order;
+ *   choice: chosen[e] = the smallest j whose s_j is minimal.  A NaN score never wins against a non-NaN one; if every score is
+ *     NaN the choice is 0;
+ *   spread[e,p], r = inp_h + p: u_k = U(x_k[r,0]), v_k = U(x_k[r,1]) with the U of spdm_eval_errors and (double)translation[e];
+ *     mu = (sum_k u_k) / (double)K, mv = (sum_k v_k) / (double)K, k ascending from 0.0;
+ *     spread = sqrt((sum_k ((u_k - mu)^2 + (v_k - mv)^2)) / (double)K), k ascending from 0.0; inside a term: square u, square
+ *     v, add.  sqrt is the correctly rounded one.  In words: the RMS distance, in the dataset's units, of the K candidates'
+ *     way-point p from their mean.
+ * Deterministic: two calls with the same arguments give the same bits.
+ * SPDM_ERR_INVALID, before the GPU is touched: NULL args; a NULL d_x0, d_chosen or d_x0_out; E < 1; K outside [1, 64];
+ * inp_h < 0 or H <= inp_h; D < 2; cols outside [2, D]; an unknown mode; COHERENT with a NULL d_guess, rows outside [1, P] or
+ * guess_row_stride < 1; MEDOID with a d_guess or rows != 0; d_spread without d_translation; E x K x H x D beyond 31 bits;
+ * d_x0_out overlapping d_x0. */
+enum { SPDM_SELECT_MEDOID = 0, SPDM_SELECT_COHERENT = 1 };
+typedef struct {
+    int32_t E;
+    int32_t K;
+    int32_t H;
+    int32_t D;
+    int32_t inp_h;
+    int32_t cols;
+    int32_t mode;
+    int32_t rows;
+    int64_t guess_row_stride;
+    const float* d_x0;
+    const float* d_guess;
+    const float* d_translation;
+    double pos_min;
+    double pos_max;
+    int32_t* d_chosen;
+    float* d_x0_out;
+    double* d_scores;
+    double* d_spread;
+} spdm_policy_select_args;
+int  spdm_policy_select(int32_t device, const spdm_policy_select_args* a, void* stream);
+
 /* spdm_solver_step is one DPM-Solver++ (2M) update (Lu et al. 2022, Algorithm 2: data prediction, multistep, midpoint) on the
  * caller's buffers: the launch the SPDM_DPMPP_2M sampling loop makes after each noise prediction.  Stateless,
  * ONE kernel launch on `stream` behind two stream-ordered 4-byte fills of d_words (NULL: the null stream, and the call

@@ -19,6 +19,7 @@ SPDM_FLAG_SIMPLE_UNET = 4
 SPDM_FLAG_TRAIN = 8
 SPDM_FLAG_TRAIN_ATTENTION = 16
 SPDM_FLAG_TRAIN_SIMPLE = 32
+SPDM_SELECT_MEDOID, SPDM_SELECT_COHERENT = 0, 1
 SPDM_ERR_INVALID = -1
 SPDM_ERR_STATE = -3
 ABI_VERSION = 2
@@ -184,6 +185,13 @@ class SpdmPolicyWarmStartArgs(ctypes.Structure):
                                          "d_noise")])
 
 
+class SpdmPolicySelectArgs(ctypes.Structure):
+    """spdm_policy_select_args (include/spdm.h)."""
+    _fields_ = ([(n, c_int32) for n in ("E", "K", "H", "D", "inp_h", "cols", "mode", "rows")] + [("guess_row_stride", c_int64)] +
+                [(n, c_void_p) for n in ("d_x0", "d_guess", "d_translation")] + [("pos_min", c_double), ("pos_max", c_double)] +
+                [(n, c_void_p) for n in ("d_chosen", "d_x0_out", "d_scores", "d_spread")])
+
+
 class SpdmSolverStepArgs(ctypes.Structure):
     """spdm_solver_step_args (include/spdm.h)."""
     _fields_ = ([(n, c_int32) for n in ("B", "H", "D", "inp_h", "inpaint_per_sample", "n_steps", "step", "first")] +
@@ -233,6 +241,7 @@ SYMBOLS = {
     "spdm_policy_window": (c_int32, [c_int32, POINTER(SpdmPolicyWindowArgs), c_void_p]),
     "spdm_policy_unnormalize": (c_int32, [c_int32, POINTER(SpdmPolicyUnnormalizeArgs), c_void_p]),
     "spdm_policy_warm_start": (c_int32, [c_int32, POINTER(SpdmPolicyWarmStartArgs), c_void_p]),
+    "spdm_policy_select": (c_int32, [c_int32, POINTER(SpdmPolicySelectArgs), c_void_p]),
     "spdm_solver_step": (c_int32, [c_int32, POINTER(SpdmSolverStepArgs), c_void_p]),
     "spdm_loss_terms": (c_int32, [c_int32, POINTER(SpdmLossTermsArgs), c_void_p]),
     "spdm_train_set_time_scale": (c_int32, [c_void_p, c_void_p, c_int32]),

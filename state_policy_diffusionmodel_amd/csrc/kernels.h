@@ -596,6 +596,25 @@ struct PolicyWarmStartArgs {
 // one launch of ceil(E ceil(H D / 4) / 256) workgroups
 hipError_t launch_policy_warm_start(const PolicyWarmStartArgs& a, hipStream_t s);
 
+// one of K candidate plans per environment (spdm_policy_select)
+constexpr int POLICY_SELECT_MAX_K = 64;            // an environment's scores fit one wave
+struct PolicySelectArgs {
+    int E, K, H, D, inp_h, cols;
+    int mode;                          // 0 medoid, 1 coherent
+    int rows;                          // coherent: rows [inp_h, inp_h + rows) are scored
+    long long guess_row_stride;        // coherent: environment e's guess is row e x guess_row_stride of `guess`
+    const float* x0;                   // (E K, H, D)
+    const float* guess;                // rows of H D floats, or null (medoid)
+    const float* translation;          // (E, 2); null iff spread is null
+    double pos_min, pos_max;
+    int* chosen;                       // (E)
+    float* x0_out;                     // (E, H, D)
+    double* scores;                    // (E, K) or null
+    double* spread;                    // (E, H - inp_h) or null
+};
+// one launch of E workgroups
+hipError_t launch_policy_select(const PolicySelectArgs& a, hipStream_t s);
+
 // ---- per-sample terms of a validation pass's loss (train_metrics.hip; spdm_loss_terms) -------------------
 constexpr int LOSS_WAVES = 4;          // samples (one wave each) per workgroup
 struct LossTermsArgs {

@@ -1,6 +1,7 @@
 // policy.hip -- the closed-loop caller's host side on the device: the observation history of E environments as rings in HBM,
 // the conditioning batch built from them, and the plan back in the dataset's units (spdm_policy_push, spdm_policy_window,
-// spdm_policy_unnormalize), and the starting iterate of a warm-started plan (spdm_policy_warm_start; 8.18).
+// spdm_policy_unnormalize), the starting iterate of a warm-started plan (spdm_policy_warm_start; 8.18), and the
+// choice of one of K candidate plans per environment (spdm_policy_select; 8.21).
 //
 // Replaces: the four deque(maxlen = obs_horizon step_size) of run_predictions.py:112-124 and their appends (:145-148),
 // prepare_diffusion_batch (:30-60: list(deque)[::s], torch.tensor(..., float32) over every frame of the window, / 255, permute,
@@ -17,6 +18,7 @@
 // Warm start: ONE launch, one thread per four consecutive elements of an environment's (H, D) window: the previous plan shifted
 // by the time that has passed, re-centred on the new window's first entry and noised to the level the loop's suffix starts
 // from, with the Philox / Box-Muller stream of train_noise.hip (philox_normal.h) under purpose 8.
+// Select: ONE launch, one workgroup per environment (described at the kernel).
 //
 // Arithmetic of the window: that of utils/data_utils.py:18-33 on CPU float32 torch tensors (include/spdm.h), written with the
 // _rn intrinsics so that no two operations are ever contracted into an FMA.
@@ -199,7 +201,163 @@ __global__ __launch_bounds__(THREADS) void policy_warm_start_kernel(const Policy
     }
 }
 
+// ---- spdm_policy_select: one of K candidates per environment --------------------------------------------------
+// One workgroup per environment.  Medoid: the K (K + 1) / 2 pairs j <= k are spread over the threads, each pair's distance is a
+// serial float64 sum in one thread (so the bits do not depend on the mapping) and lands in a triangular table in LDS; thread j
+// then adds row j of the table in k order.  Coherent: thread j sums candidate j against the guess.  The K <= 64 scores meet in
+// wave 0, which picks the winner with six shuffle steps under a total order (below), and all threads copy the chosen row.
+// Dynamic LDS: [64 scores][medoid: K (K + 1) / 2 distances] as doubles, then -- when it fits SELECT_LDS_BYTES -- the scored part
+// of the K candidates as floats with an odd candidate stride, so that the threads of a wave, which read the same (r, c) of
+// different candidates, fall on different banks, and the scored part of the guess.  The distance loops and the spread then
+// read LDS; where it does not fit, the same loops read global memory.
+constexpr int SELECT_LDS_BYTES = 64 * 1024;            // what a workgroup may ask for without an opt-in attribute
+
+__host__ __device__ inline int select_pairs(int K) { return K * (K + 1) / 2; }
+// candidate stride of the staged copy, in floats: odd, hence coprime to the bank count
+__host__ __device__ inline int select_stage_stride(int P, int cols) { return (P * cols) | 1; }
+
+// a beats b: the smaller score; a NaN loses against a number; on a tie, and between two NaNs, the lower index
+__device__ __forceinline__ bool select_beats(double sa, int ia, double sb, int ib) {
+    const bool na = sa != sa, nb = sb != sb;
+    if (na != nb) return nb;
+    if (!na && sa != sb) return sa < sb;
+    return ia < ib;
+}
+
+// sum over `rows` rows of `cols` columns of (x - y)^2, r outer and c inner, each term subtract, multiply, add
+template <typename PX, typename PY>
+__device__ __forceinline__ double select_distance(PX x, int x_ld, PY y, int y_ld, int rows, int cols) {
+#pragma clang fp contract(off)
+    double s = 0.0;
+    for (int r = 0; r < rows; ++r)
+        for (int c = 0; c < cols; ++c) {
+            const double d = (double)x[r * x_ld + c] - (double)y[r * y_ld + c];
+            const double dd = d * d;
+            s = s + dd;
+        }
+    return s;
+}
+
+template <bool STAGED>
+__global__ __launch_bounds__(THREADS) void policy_select_kernel(const PolicySelectArgs a) {
+#pragma clang fp contract(off)
+    extern __shared__ double select_lds[];
+    __shared__ int pick;
+    const int e = blockIdx.x, t = threadIdx.x, K = a.K;                    // e < E: the grid
+    const int P = a.H - a.inp_h, HD = a.H * a.D;                           // E K H D < 2^31: the host
+    const float* xe = a.x0 + (size_t)e * K * HD;                           // candidate k: xe + k HD
+    double* sc = select_lds;                                               // [64]
+    double* tri = select_lds + POLICY_SELECT_MAX_K;                        // [K (K + 1) / 2]: row j holds d(j, k), k = j .. K - 1
+    double mine = 0.0;                                                     // thread j < K: s_j
+    const int npairs = a.mode == 0 ? select_pairs(K) : 0, n = P * a.cols;
+    const int cs = select_stage_stride(P, a.cols);
+    float* st = reinterpret_cast<float*>(tri + npairs);                    // [K][cs]: x_k[inp_h + r, c] at k cs + r cols + c
+    float* gs = st + K * cs;                                               // coherent: [rows][cols] of the guess
+    const float* g = a.mode == 1 ? a.guess + (size_t)e * (size_t)a.guess_row_stride * HD + a.inp_h * a.D : nullptr;
+    if (STAGED) {
+        for (int i = t; i < K * n; i += THREADS) {
+            const int k = i / n, w = i - k * n, r = w / a.cols, c = w - r * a.cols;           // k < K, r < P, c < cols <= D
+            st[k * cs + w] = xe[(size_t)k * HD + (a.inp_h + r) * a.D + c];
+        }
+        if (a.mode == 1)
+            for (int i = t; i < a.rows * a.cols; i += THREADS) {
+                const int r = i / a.cols, c = i - r * a.cols;                                 // r < rows <= P
+                gs[i] = g[r * a.D + c];
+            }
+        __syncthreads();
+    }
+    if (a.mode == 0) {
+        for (int p = t; p < npairs; p += THREADS) {
+            int j = 0, rem = p, len = K;                                   // row j of the table has K - j entries
+            while (rem >= len) { rem -= len; ++j; --len; }
+            const int k = j + rem;                                         // j <= k < K
+            if (STAGED) tri[p] = select_distance(st + j * cs, a.cols, st + k * cs, a.cols, P, a.cols);
+            else tri[p] = select_distance(xe + (size_t)j * HD + a.inp_h * a.D, a.D, xe + (size_t)k * HD + a.inp_h * a.D, a.D, P, a.cols);
+        }
+        __syncthreads();
+        if (t < K) {
+            for (int k = 0; k < K; ++k) {
+                const int lo = min(t, k), hi = max(t, k);
+                mine = mine + tri[lo * K - lo * (lo - 1) / 2 + (hi - lo)];
+            }
+        }
+    } else if (t < K) {                                                    // inp_h + rows <= H
+        if (STAGED) mine = select_distance(st + t * cs, a.cols, gs, a.cols, a.rows, a.cols);
+        else mine = select_distance(xe + (size_t)t * HD + a.inp_h * a.D, a.D, g, a.D, a.rows, a.cols);
+    }
+    if (t < K) {
+        sc[t] = mine;
+        if (a.scores != nullptr) a.scores[(size_t)e * K + t] = mine;
+    }
+    if (a.spread != nullptr) {
+        const double range = a.pos_max - a.pos_min;
+        const double tx = (double)a.translation[(size_t)e * 2], ty = (double)a.translation[(size_t)e * 2 + 1];
+        for (int p = t; p < P; p += THREADS) {
+            // candidate k's way-point p: x[k ld], x[k ld + 1] (cols >= 2: the staged copy holds both)
+            const float* x = STAGED ? st + p * a.cols : xe + (a.inp_h + p) * a.D;
+            const size_t ld = STAGED ? (size_t)cs : (size_t)HD;
+            double su = 0.0, sv = 0.0;
+            for (int k = 0; k < K; ++k) {
+                su = su + unnormalize_position(x[k * ld], tx, a.pos_min, range);
+                sv = sv + unnormalize_position(x[k * ld + 1], ty, a.pos_min, range);
+            }
+            const double mu = su / (double)K, mv = sv / (double)K;
+            double q = 0.0;
+            for (int k = 0; k < K; ++k) {
+                const double du = unnormalize_position(x[k * ld], tx, a.pos_min, range) - mu;
+                const double dv = unnormalize_position(x[k * ld + 1], ty, a.pos_min, range) - mv;
+                const double du2 = du * du, dv2 = dv * dv;
+                const double term = du2 + dv2;
+                q = q + term;
+            }
+            a.spread[(size_t)e * P + p] = sqrt(q / (double)K);
+        }
+    }
+    __syncthreads();                                                       // sc[] is complete
+    if (t < 64) {                                                          // wave 0, all 64 lanes: lanes >= K hold a NaN and lose
+        double s = t < K ? sc[t] : __longlong_as_double(0x7ff8000000000000LL);
+        int idx = t;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const double os = __shfl_xor(s, off);
+            const int oi = __shfl_xor(idx, off);
+            if (select_beats(os, oi, s, idx)) { s = os; idx = oi; }
+        }
+        if (t == 0) {
+            idx = min(idx, K - 1);                                         // it is < K already: lane 0 beats every lane >= K
+            pick = idx;
+            a.chosen[e] = idx;
+        }
+    }
+    __syncthreads();
+    const float* src = xe + (size_t)pick * HD;                             // pick < K
+    float* dst = a.x0_out + (size_t)e * HD;
+    for (int i = t; i < HD; i += THREADS) dst[i] = src[i];
+}
+
 }  // namespace
+
+// dynamic LDS of the select launch and whether the candidates are staged
+static size_t select_lds_bytes(const PolicySelectArgs& a, bool& staged) {
+    size_t bytes = sizeof(double) * (POLICY_SELECT_MAX_K + (a.mode == 0 ? select_pairs(a.K) : 0));
+    const size_t stage = sizeof(float) * ((size_t)a.K * select_stage_stride(a.H - a.inp_h, a.cols) + (a.mode == 1 ? (size_t)a.rows * a.cols : 0));
+    staged = bytes + stage <= (size_t)SELECT_LDS_BYTES;
+    return staged ? bytes + stage : bytes;
+}
+
+hipError_t launch_policy_select(const PolicySelectArgs& a, hipStream_t s) {
+    if (a.E < 1 || a.K < 1 || a.K > POLICY_SELECT_MAX_K || a.inp_h < 0 || a.H <= a.inp_h || a.D < 2 || a.cols < 2 || a.cols > a.D ||
+        (a.mode != 0 && a.mode != 1) || (long long)a.H * a.D > 0x7fffffffLL || (long long)a.E * a.K > 0x7fffffffLL ||
+        (long long)a.E * a.K * ((long long)a.H * a.D) > 0x7fffffffLL ||
+        (a.mode == 1 && (a.guess == nullptr || a.rows < 1 || a.rows > a.H - a.inp_h || a.guess_row_stride < 1)) ||
+        (a.spread != nullptr && a.translation == nullptr))
+        return hipErrorInvalidValue;
+    bool staged;
+    const size_t lds = select_lds_bytes(a, staged);
+    if (staged) hipLaunchKernelGGL(policy_select_kernel<true>, dim3((unsigned)a.E), dim3(THREADS), lds, s, a);
+    else hipLaunchKernelGGL(policy_select_kernel<false>, dim3((unsigned)a.E), dim3(THREADS), lds, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_policy_warm_start(const PolicyWarmStartArgs& a, hipStream_t s) {
     const long long HD = (long long)a.H * a.D, n = (long long)a.E * ((HD + 3) / 4);

@@ -3200,6 +3200,45 @@ extern "C" int spdm_policy_warm_start(int32_t device, const spdm_policy_warm_sta
     return SPDM_OK;
 }
 
+// One of K candidate plans per environment, its index, the scores and the spread in one launch (include/spdm.h, policy.hip).
+// Stateless.
+extern "C" int spdm_policy_select(int32_t device, const spdm_policy_select_args* a, void* stream) {
+    if (!a) return fail(SPDM_ERR_INVALID, "policy_select: null argument");
+    if (a->E < 1) return fail(SPDM_ERR_INVALID, "policy_select: E = %d must be >= 1", a->E);
+    if (a->K < 1 || a->K > POLICY_SELECT_MAX_K) return fail(SPDM_ERR_INVALID, "policy_select: K = %d outside [1, %d]", a->K, POLICY_SELECT_MAX_K);
+    if (a->inp_h < 0 || a->H <= a->inp_h) return fail(SPDM_ERR_INVALID, "policy_select: inp_h = %d outside [0, H = %d)", a->inp_h, a->H);
+    if (a->D < 2) return fail(SPDM_ERR_INVALID, "policy_select: D = %d holds no position (2 columns)", a->D);
+    if (a->cols < 2 || a->cols > a->D) return fail(SPDM_ERR_INVALID, "policy_select: cols = %d outside [2, D = %d]", a->cols, a->D);
+    if (a->mode != SPDM_SELECT_MEDOID && a->mode != SPDM_SELECT_COHERENT)
+        return fail(SPDM_ERR_INVALID, "policy_select: mode = %d is neither SPDM_SELECT_MEDOID nor SPDM_SELECT_COHERENT", a->mode);
+    if (a->mode == SPDM_SELECT_COHERENT) {
+        if (!a->d_guess) return fail(SPDM_ERR_INVALID, "policy_select: COHERENT needs d_guess: null pointer");
+        if (a->rows < 1 || a->rows > a->H - a->inp_h)
+            return fail(SPDM_ERR_INVALID, "policy_select: rows = %d outside [1, H - inp_h = %d]", a->rows, a->H - a->inp_h);
+        if (a->guess_row_stride < 1)
+            return fail(SPDM_ERR_INVALID, "policy_select: guess_row_stride = %lld must be >= 1", (long long)a->guess_row_stride);
+    } else if (a->d_guess || a->rows != 0) {
+        return fail(SPDM_ERR_INVALID, "policy_select: MEDOID takes no d_guess and rows = 0 (rows = %d)", a->rows);
+    }
+    if (a->d_spread && !a->d_translation) return fail(SPDM_ERR_INVALID, "policy_select: d_spread needs d_translation");
+    const long long HD = (long long)a->H * a->D, EK = (long long)a->E * a->K;      // each < 2^62
+    if (HD > 0x7fffffffLL || EK > 0x7fffffffLL || EK * HD > 0x7fffffffLL)
+        return fail(SPDM_ERR_INVALID, "policy_select: E x K x H x D does not fit 31 bits");
+    if (!a->d_x0 || !a->d_chosen || !a->d_x0_out) return fail(SPDM_ERR_INVALID, "policy_select: null pointer");
+    const uintptr_t in0 = (uintptr_t)a->d_x0, in1 = in0 + (uintptr_t)(EK * HD) * sizeof(float);
+    const uintptr_t out0 = (uintptr_t)a->d_x0_out, out1 = out0 + (uintptr_t)((long long)a->E * HD) * sizeof(float);
+    if (out0 < in1 && in0 < out1) return fail(SPDM_ERR_INVALID, "policy_select: d_x0_out overlaps d_x0");
+    PolicySelectArgs k = {};
+    k.E = a->E; k.K = a->K; k.H = a->H; k.D = a->D; k.inp_h = a->inp_h; k.cols = a->cols; k.mode = a->mode; k.rows = a->rows;
+    k.guess_row_stride = a->guess_row_stride;
+    k.x0 = a->d_x0; k.guess = a->d_guess; k.translation = a->d_translation; k.pos_min = a->pos_min; k.pos_max = a->pos_max;
+    k.chosen = a->d_chosen; k.x0_out = a->d_x0_out; k.scores = a->d_scores; k.spread = a->d_spread;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(launch_policy_select(k, (hipStream_t)stream));
+    if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));
+    return SPDM_OK;
+}
+
 // One DPM-Solver++ (2M) update on the caller's buffers (include/spdm.h, elementwise.hip): the launch the SPDM_DPMPP_2M loop
 // makes after every noise prediction.  Stateless.
 extern "C" int spdm_solver_step(int32_t device, const spdm_solver_step_args* a, void* stream) {

@@ -316,7 +316,7 @@ class Diffusion_DDPM:
     def sample(self, batch: Dict[str, torch.Tensor], option: Optional[str] = None, *,
                x_T: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                batched: bool = False, seed: Optional[int] = None, sample_offset: int = 0, every: int = 1,
-               sharded: Optional[bool] = None, group=None, shard_exact: bool = False, start_step: int = 0):
+               sharded: Optional[bool] = None, group=None, shard_exact: bool = False, candidates: int = 1, start_step: int = 0):
         """``option``: None -> x_0 (B,1,H,D); 'sample_history' -> list of the N+1 iterates (the reference's form);
         'sample_history_stream' -> a generator of ``(i, x_i)`` host tensors handed out while the loop runs
         (``every``: stride in steps; SpdmEngine.sample_stream).
@@ -339,8 +339,17 @@ class Diffusion_DDPM:
         has after ``i0`` of its ``noise_steps`` iterations, and only iterations ``[i0, noise_steps)`` run -- bit for bit the
         tail of the whole loop from that iterate under DDPM / DDIM.  Under ``DPMSolverMultistepScheduler`` a suffix is a new
         session and begins with a first-order step (no previous x_0 exists), so it is NOT the whole loop's tail (DESIGN.md
-        8.19).  Not available with a history option or ``sharded=True``."""
+        8.19).  Not available with a history option or ``sharded=True``.
+
+        ``candidates = K > 1`` (with ``batched=True``) samples K trajectories per row of the batch: ``obs_cond``
+        and ``inpaint`` are built for the E rows -- the frame encoder runs E obs_h frames -- and each row is then repeated K
+        times on the device, so row ``e K + k`` of the (E K,1,H,D) result is candidate k of row e.  ``x_T``, if given, is
+        (E K,1,H,D).  The device noise is keyed by the row index, so every candidate has a stream of its own.  Not available
+        with a history option or ``sharded=True``."""
         from .distributed import ShardedSampler, shard_bounds, world_and_rank
+        if isinstance(candidates, bool) or not isinstance(candidates, (int, np.integer)) or candidates < 1:
+            raise ValueError(f"candidates = {candidates!r} must be an integer >= 1")
+        candidates = int(candidates)
         if isinstance(start_step, bool) or not isinstance(start_step, (int, np.integer)) or not 0 <= start_step < int(self.noise_steps):
             raise ValueError(f"start_step = {start_step!r} must be an integer in [0, noise_steps = {self.noise_steps})")
         start_step = int(start_step)
@@ -352,6 +361,9 @@ class Diffusion_DDPM:
         if start_step and (option in ("sample_history", "sample_history_stream") or sharded):
             raise ValueError("start_step > 0 runs a suffix of the loop on this process: not available with option='sample_history', "
                              "'sample_history_stream' or sharded=True")
+        if candidates > 1 and (not batched or sharded or option in ("sample_history", "sample_history_stream")):
+            raise ValueError("candidates > 1 repeats the rows of a batch on this process: it needs batched=True and is not available "
+                             "with sharded=True, option='sample_history' or 'sample_history_stream'")
         if sharded and not batched:
             raise ValueError("sharded=True needs batched=True (the reference's B = 1 form has nothing to shard)")
         if sharded and option == "sample_history_stream":
@@ -369,8 +381,13 @@ class Diffusion_DDPM:
             obs_cond, inpaint = obs_cond[0:1], inpaint[0:1]
         obs_cond = obs_cond.unsqueeze(1)                                      # (B,1,obs_h,obs_dim)
         inpaint = inpaint.unsqueeze(1)                                        # (B,1,inp_h,pred_dim)
-        B = obs_cond.shape[0]
         H, D = self.pred_horizon + self.inpaint_horizon, self.prediction_dim
+        if candidates > 1:                                                    # 1: exactly the call without the keyword
+            obs_cond = obs_cond.repeat_interleave(candidates, dim=0)          # row e K + k is row e
+            inpaint = inpaint.repeat_interleave(candidates, dim=0)
+            if x_T is not None and tuple(x_T.shape) != (obs_cond.shape[0], 1, H, D):
+                raise ValueError(f"x_T must be {(obs_cond.shape[0], 1, H, D)} with candidates = {candidates}, got {tuple(x_T.shape)}")
+        B = obs_cond.shape[0]
         if x_T is None:
             x_T = torch.rand(B, 1, H, D, device=self.device)                  # uniform, :252
             if sharded and world > 1:

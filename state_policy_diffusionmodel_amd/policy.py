@@ -9,6 +9,8 @@ with the model's engine and returns way-points and actions in the dataset's unit
 (``spdm_policy_unnormalize``).  E = 1 is the reference's loop; a larger E drives that many environments in lockstep.
 ``plan(warm_start=K)`` replans from the previous plan instead of from noise: one more launch
 (``spdm_policy_warm_start``) shifts, re-centres and re-noises it, and only the last K denoise steps run.
+``plan_candidates(candidates=K)`` samples K candidates per environment and keeps one, chosen on the device: one more
+launch (``spdm_policy_select``) scores them against the plan being executed, or against each other, and reports their spread.
 
 There is no CPU fallback: every method but the constructor's checks needs the GPU."""
 from __future__ import annotations
@@ -36,6 +38,24 @@ class Plan:
     x_0: torch.Tensor
     steps: int = 0
     warm: bool = False
+
+
+@dataclass
+class CandidatePlan(Plan):
+    """What ``plan_candidates()`` returns: a ``Plan`` whose ``x_0``, ``waypoints`` and ``actions`` are the chosen candidate's.
+    ``candidates``: trajectories sampled per environment.  With ``candidates > 1`` (None otherwise): ``selected_by`` what chose
+    among them (``'coherent'``, ``'medoid'`` or ``'first'``), ``chosen`` (E) int32 the index kept, ``scores`` (E, K) float64 the
+    candidates' scores and ``spread`` (E, pred_horizon) float64 the RMS distance of the candidates' way-points from their mean,
+    in the dataset's units: device tensors."""
+    candidates: int = 1
+    selected_by: str = ''
+    chosen: Optional[torch.Tensor] = None
+    scores: Optional[torch.Tensor] = None
+    spread: Optional[torch.Tensor] = None
+
+
+SELECT_MODES = ("coherent", "medoid", "first")
+MAX_CANDIDATES = 64
 
 
 def _channel_stats(stats: dict, key: str, n: int):
@@ -92,6 +112,8 @@ class ClosedLoopPolicy:
         self._prev_usable = False                                              # False again after any reset()
         self.plans = 0                                                         # plan() calls so far: the warm start's `draw`
         self._levels = (None, None, None)                                      # (scheduler object, noise_steps, its (n, 6) table)
+        # how the last plan_candidates(candidates > 1) scored its candidates: {'scored_by': 'coherent' | 'medoid', 'rows', 'cols'}
+        self.last_selection: Optional[dict] = None
 
     # ---- history --------------------------------------------------------------------------------------------------------------
     def reset(self, env_ids=None) -> None:
@@ -221,6 +243,48 @@ class ClosedLoopPolicy:
         _lib.check(_lib.load().spdm_policy_warm_start(self.device.index, ctypes.byref(a), stream), "spdm_policy_warm_start")
         return (x, guess, used) if return_parts else x
 
+    def select(self, x_0: torch.Tensor, candidates: int, mode: str = "medoid", *, guess: Optional[torch.Tensor] = None, rows: int = 0,
+               guess_row_stride: int = 1, cols: int = 2, translation: Optional[torch.Tensor] = None):
+        """One of ``candidates`` = K plans per environment: ONE launch (``spdm_policy_select``, include/spdm.h) on torch's
+        current stream.  ``x_0`` (E K,1,H,D) or (E K,H,D) float32, candidate k of environment e in row e K + k; ``mode``
+        ``'medoid'`` or ``'coherent'``, the latter against ``guess`` (rows of (H,D), environment e's at row e
+        ``guess_row_stride``) over its first ``rows`` predicted rows; ``cols`` columns enter a distance; ``translation`` (E,2)
+        asks for the spread.  Returns ``(chosen (E) int32, x_0 (E,1,H,D) float32, scores (E,K) float64, spread (E,P) float64
+        or None)``, device tensors."""
+        if mode not in ("medoid", "coherent"):
+            raise ValueError(f"mode must be 'medoid' or 'coherent', got {mode!r}")
+        x = x_0[:, 0] if x_0.dim() == 4 else x_0
+        K, E = int(candidates), self.n_envs
+        if x.dim() != 3:
+            raise ValueError(f"x_0 must be (E K, 1, H, D) or (E K, H, D), got {tuple(x_0.shape)}")
+        given = [("x_0", x, (E * K,) + tuple(x.shape[1:]))]
+        if translation is not None:
+            given.append(("translation", translation, (E, 2)))
+        if guess is not None:
+            given.append(("guess", guess, tuple(guess.shape[:1]) + tuple(x.shape[1:])))
+        for name, t, shape in given:
+            if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError(f"{name} must be a contiguous float32 device tensor of shape {shape}, got {tuple(t.shape)} {t.dtype}")
+        if guess is not None and guess_row_stride >= 1 and guess.shape[0] < (E - 1) * guess_row_stride + 1:
+            raise ValueError(f"guess has {guess.shape[0]} rows: environment {E - 1} reads row {(E - 1) * guess_row_stride}")
+        _, H, D = x.shape
+        P = H - self.inpaint_horizon
+        dev = self.device
+        chosen = torch.empty(E, dtype=torch.int32, device=dev)
+        out = torch.empty((E, 1, H, D), dtype=torch.float32, device=dev)
+        scores = torch.empty((E, K), dtype=torch.float64, device=dev)
+        spread = torch.empty((E, max(P, 0)), dtype=torch.float64, device=dev) if translation is not None else None
+        a = _lib.SpdmPolicySelectArgs(E=E, K=K, H=H, D=D, inp_h=self.inpaint_horizon, cols=int(cols),
+                                      mode=_lib.SPDM_SELECT_COHERENT if mode == "coherent" else _lib.SPDM_SELECT_MEDOID,
+                                      rows=int(rows), guess_row_stride=int(guess_row_stride), d_x0=x.data_ptr(),
+                                      d_guess=guess.data_ptr() if guess is not None else None,
+                                      d_translation=translation.data_ptr() if translation is not None else None,
+                                      pos_min=self._pos_min, pos_max=self._pos_max, d_chosen=chosen.data_ptr(), d_x0_out=out.data_ptr(),
+                                      d_scores=scores.data_ptr(), d_spread=spread.data_ptr() if spread is not None else None)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.load().spdm_policy_select(dev.index, ctypes.byref(a), stream), "spdm_policy_select")
+        return chosen, out, scores, spread
+
     def _noise_level(self, i0: int):
         """``(sa, sb)`` = (sqrt(abar_t), sqrt(1 - abar_t)) of the timestep loop iteration ``i0`` denoises from: row ``i0`` of the
         table ``sample()`` installs in the engine, the same float32 values."""
@@ -244,32 +308,90 @@ class ClosedLoopPolicy:
         window and noises it to the level iteration N - K starts from, and ``model.sample(..., start_step=N - K)`` runs the
         rest.  A warm plan ignores ``x_T``.  Otherwise the plan is COLD: exactly the path above, all N iterations.
         ``Plan.steps`` and ``Plan.warm`` say which it was."""
+        return self._plan(seed, x_T, warm_start, 1, "coherent", 2)[0]
+
+    def plan_candidates(self, seed: Optional[int] = None, x_T: Optional[torch.Tensor] = None, warm_start: Optional[int] = None,
+                        candidates: int = 1, select: str = "coherent", cols: int = 2) -> CandidatePlan:
+        """``plan()`` from ``candidates = K`` (1 <= K <= 64) trajectories per environment, one of which is kept:
+        ``sample(..., candidates=K)`` builds and encodes the batch once per environment (``x_T``, if given, is (E K,1,H,D)), ONE
+        ``spdm_policy_select`` launch chooses, and the way-points, the actions, ``x_0`` and the plan the next warm start or
+        selection refers to are the chosen candidate's.  Nothing is copied to the host.  ``select='coherent'`` keeps the
+        candidate closest to the previous chosen plan, shifted and re-centred as a warm start does, over the rows that plan
+        still informs -- when a previous plan is usable, which is ``plan()``'s condition for a warm plan; otherwise, and with
+        ``select='medoid'``, the candidate with the smallest sum of squared distances to the others.  ``select='first'`` keeps
+        candidate 0 whatever the scores say (for A/B runs); scores and spread are still those ``'coherent'`` would have
+        reported.  ``cols``: the columns that enter a distance, 2 (positions) to ``prediction_dim`` (positions and actions).
+        With ``warm_start`` the warm iterate is built for all E K rows, each with noise of its own.  ``candidates = 1`` makes
+        exactly the calls of ``plan()``: no select launch, and the selection's fields stay None.  ``plan()`` and
+        ``plan_candidates()`` share the policy's state and may alternate."""
+        if isinstance(candidates, bool) or not isinstance(candidates, (int, np.integer)) or not 1 <= candidates <= MAX_CANDIDATES:
+            raise ValueError(f"candidates = {candidates!r} must be an integer in [1, {MAX_CANDIDATES}]")
+        if select not in SELECT_MODES:
+            raise ValueError(f"select = {select!r} must be one of {SELECT_MODES}")
+        if isinstance(cols, bool) or not isinstance(cols, (int, np.integer)) or not 2 <= cols <= self.prediction_dim:
+            raise ValueError(f"cols = {cols!r} must be an integer in [2, prediction_dim = {self.prediction_dim}]")
+        plan, picked = self._plan(seed, x_T, warm_start, int(candidates), select, int(cols))
+        return CandidatePlan(waypoints=plan.waypoints, actions=plan.actions, x_0=plan.x_0, steps=plan.steps, warm=plan.warm, **picked)
+
+    def _plan(self, seed, x_T, warm_start, K: int, select: str, cols: int):
+        """``(Plan, the selection's fields)`` of ``plan()`` (K = 1) and ``plan_candidates()``, arguments validated but ``warm_start``."""
         if warm_start is not None:
             N = int(self.model.noise_steps)
             if isinstance(warm_start, bool) or not isinstance(warm_start, (int, np.integer)) or not 1 <= warm_start <= N:
                 raise ValueError(f"warm_start = {warm_start!r} must be an integer in [1, noise_steps = {N}]")
+        H, D = self.pred_horizon + self.inpaint_horizon, self.prediction_dim
+        if K > 1 and x_T is not None and tuple(x_T.shape) != (self.n_envs * K, 1, H, D):
+            raise ValueError(f"x_T must be {(self.n_envs * K, 1, H, D)} with candidates = {K}, got {tuple(x_T.shape)}")
         batch = self.batch()
         N = int(self.model.noise_steps)
         if seed is None:                                                       # sample()'s recipe, drawn here so that the warm
             seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())      # start and the loop share one seed
         draw, delta = self.plans, self.pushes - self._prev_pushes
         self.plans += 1
-        warm = (warm_start is not None and self._prev_usable and self._prev_x0 is not None
-                and delta <= (self.pred_horizon - 1) * self.step_size)
+        usable = self._prev_usable and self._prev_x0 is not None and delta <= (self.pred_horizon - 1) * self.step_size
+        warm = warm_start is not None and usable
+        extra = {"candidates": K} if K > 1 else {}                             # 1: exactly the calls without the keyword
+        guess, stride = None, 1
         if warm:
             i0 = N - int(warm_start)
             sa, sb = self._noise_level(i0)
             inp = self.model.prepare_inpaint_vectors(batch).contiguous() if self.inpaint_horizon > 0 else None
-            x_start = self.warm_start(self._prev_x0, self._prev_translation, batch["translation"], inp, delta, sa, sb, seed, draw)
-            x_0 = self.model.sample(dict(batch), batched=True, sharded=False, seed=seed, x_T=x_start, start_step=i0)
+            if K > 1:                                                          # the previous plan K-fold: env_offset + row gives
+                rep = lambda t: None if t is None else t.repeat_interleave(K, dim=0)  # noqa: E731  -- each candidate its noise
+                x_start, guess, _ = self.warm_start(rep(self._prev_x0), rep(self._prev_translation), rep(batch["translation"]), rep(inp),
+                                                    delta, sa, sb, seed, draw, return_parts=True)
+                stride = K
+            else:
+                x_start = self.warm_start(self._prev_x0, self._prev_translation, batch["translation"], inp, delta, sa, sb, seed, draw)
+            x_0 = self.model.sample(dict(batch), batched=True, sharded=False, seed=seed, x_T=x_start, start_step=i0, **extra)
         else:
-            x_0 = self.model.sample(dict(batch), batched=True, sharded=False, seed=seed, x_T=x_T)
+            x_0 = self.model.sample(dict(batch), batched=True, sharded=False, seed=seed, x_T=x_T, **extra)
         x_0 = x_0.contiguous()
+        picked = {}
+        if K > 1:
+            mode = "coherent" if usable and select != "medoid" else "medoid"
+            rows = 0
+            if mode == "coherent":
+                rows = self.pred_horizon - delta // self.step_size - (1 if delta % self.step_size else 0)      # >= 1: `usable`
+                if guess is None:                                              # the shifted previous plan alone: no noise enters it
+                    inp = self.model.prepare_inpaint_vectors(batch).contiguous() if self.inpaint_horizon > 0 else None
+                    guess = self.warm_start(self._prev_x0, self._prev_translation, batch["translation"], inp, delta, 1.0, 0.0, seed,
+                                            draw, return_parts=True)[1]
+            else:
+                guess = None
+            chosen, kept, scores, spread = self.select(x_0, K, mode, guess=guess, rows=rows, guess_row_stride=stride if guess is not None else 1,
+                                                       cols=int(cols), translation=batch["translation"])
+            if select == "first":
+                chosen = torch.zeros_like(chosen)
+                kept = x_0[0::K].contiguous()
+            self.last_selection = {"scored_by": mode, "rows": rows, "cols": int(cols)}
+            picked = dict(candidates=K, selected_by="first" if select == "first" else mode, chosen=chosen, scores=scores, spread=spread)
+            x_0 = kept
         self._prev_x0, self._prev_translation = x_0, batch["translation"]
         self._prev_pushes, self._prev_usable = self.pushes, True
         out = self.unnormalize(x_0, batch["translation"])
         out.steps, out.warm = (int(warm_start) if warm else N), warm
-        return out
+        return out, picked
 
 
-__all__ = ["ClosedLoopPolicy", "Plan"]
+__all__ = ["CandidatePlan", "ClosedLoopPolicy", "Plan"]

@@ -16,7 +16,14 @@ mean and population std of the error per step.
 ``--warm_start K`` replans inside an episode from the previous plan with the last K denoise steps only (``plan(warm_start=K)``,
 DESIGN.md 8.18); the first plan of every episode is cold, because the policy is reset there.  Each plan then also says how many
 steps it ran and whether it was warm, and the report holds the error statistics and the mean seconds of the cold and of the warm
-plans side by side -- what a checkpoint's owner needs to choose K."""
+plans side by side -- what a checkpoint's owner needs to choose K.
+
+``--candidates K`` samples K candidates per plan and keeps one, chosen on the device (``plan_candidates(candidates=K,
+select=..., cols=...)``).  Each plan then also holds ``chosen``, ``selected_by``, the chosen candidate's ``score`` (what it was
+``scored_by``, over how many ``rows``) and the per-step ``spread`` of the candidates; the report holds ``mean_spread`` per step and
+``mean_jump``: the mean, over the plans scored against their predecessor, of the chosen candidate's coherence score divided by
+``rows x cols`` -- the mean squared step between consecutive plans, in normalised units.  ``--select first`` keeps candidate 0 and
+reports the same numbers for it, so that two runs compare."""
 from __future__ import annotations
 
 import argparse
@@ -57,6 +64,10 @@ def parse_arguments(argv=None):
     p.add_argument("--seed", type=int, default=0, help="plan i samples with seed + i and its x_T from a generator seeded alike")
     p.add_argument("--warm_start", type=int, default=None, metavar="K",
                    help="replan inside an episode from the previous plan, running the last K denoise steps only (default: off)")
+    p.add_argument("--candidates", type=int, default=1, metavar="K", help="sample K candidates per plan and keep one (default: 1, off)")
+    p.add_argument("--select", type=str, default="coherent", choices=("coherent", "medoid", "first"),
+                   help="with --candidates: closest to the previous plan (medoid when there is none), the medoid, or candidate 0")
+    p.add_argument("--select_cols", type=int, default=2, metavar="C", help="columns of a row that enter a distance: 2 positions, 5 with actions")
     p.add_argument("--out", type=str, default=None, help="report.json")
     return p.parse_args(argv)
 
@@ -67,12 +78,14 @@ def main(argv=None) -> dict:
         raise SystemExit("--replan_every must be >= 1")
     if args.warm_start is not None and args.warm_start < 1:
         raise SystemExit("--warm_start must be >= 1")
+    if not 1 <= args.candidates <= 64:
+        raise SystemExit("--candidates must be in [1, 64]")
     import torch
     from .dataset import choose_image_storage
     from .diffusion import load_model
     from .evaluate import load_arrays, load_stats
     from .policy import ClosedLoopPolicy
-    model = load_model(args.model_name, args.checkpoint, args.hparams, num_of_ddim_steps=args.ddim_steps, max_batch=1,
+    model = load_model(args.model_name, args.checkpoint, args.hparams, num_of_ddim_steps=args.ddim_steps, max_batch=args.candidates,
                        solver_steps=args.solver_steps)
     stats = load_stats(args.stats)
     arrays = load_arrays(args.data)
@@ -82,6 +95,8 @@ def main(argv=None) -> dict:
     H, D = P + policy.inpaint_horizon, policy.prediction_dim
     position = np.asarray(arrays["position"], dtype=np.float64)
     u8 = storage == "uint8"
+    K = args.candidates
+    many = {"candidates": K, "select": args.select, "cols": args.select_cols} if K > 1 else {}     # 1: the calls of before
     plans, left_out, first = [], 0, 0
     for end in (int(e) for e in np.asarray(arrays["episode_ends"]).reshape(-1)):
         policy.reset()
@@ -94,10 +109,15 @@ def main(argv=None) -> dict:
             if (t - first) % args.replan_every:
                 continue
             seed = args.seed + len(plans)
-            x_T = torch.rand(1, 1, H, D, device=model.device, generator=torch.Generator(device=model.device).manual_seed(seed))
+            x_T = torch.rand(K, 1, H, D, device=model.device, generator=torch.Generator(device=model.device).manual_seed(seed))
             torch.cuda.synchronize(model.device)
             start = time.perf_counter()
-            plan = policy.plan(seed=seed, x_T=x_T) if args.warm_start is None else policy.plan(seed=seed, x_T=x_T, warm_start=args.warm_start)
+            if K > 1:
+                plan = policy.plan_candidates(seed=seed, x_T=x_T, warm_start=args.warm_start, **many)
+            elif args.warm_start is None:
+                plan = policy.plan(seed=seed, x_T=x_T)
+            else:
+                plan = policy.plan(seed=seed, x_T=x_T, warm_start=args.warm_start)
             torch.cuda.synchronize(model.device)
             seconds = time.perf_counter() - start
             _, rows, out = plan_rows(t, first, end, obs_h, P, s)
@@ -107,6 +127,10 @@ def main(argv=None) -> dict:
                           "left_out": out, "seconds": seconds})
             if args.warm_start is not None:
                 plans[-1].update(steps=plan.steps, warm=plan.warm)
+            if K > 1:                                                          # after the clock has stopped
+                j, how = int(plan.chosen[0].item()), policy.last_selection
+                plans[-1].update(chosen=j, selected_by=plan.selected_by, scored_by=how["scored_by"], rows=how["rows"],
+                                 score=float(plan.scores[0, j].item()), spread=plan.spread[0].cpu().tolist())
             left_out += out
         first = end
     def per_step(chosen):
@@ -130,6 +154,13 @@ def main(argv=None) -> dict:
         print(f"*** warm_start = {args.warm_start}: plan() mean {report['seconds_cold']} s cold, {report['seconds_warm']} s warm")
         print("mean position error per step, cold:", report["mean_error_cold"])
         print("mean position error per step, warm:", report["mean_error_warm"])
+    if K > 1:
+        report["candidates"], report["select"], report["select_cols"] = K, args.select, args.select_cols
+        report["mean_spread"] = np.mean(np.array([p["spread"] for p in plans], dtype=np.float64), axis=0).tolist() if plans else None
+        jumps = [p["score"] / (p["rows"] * args.select_cols) for p in plans if p["scored_by"] == "coherent"]
+        report["mean_jump"] = float(np.mean(jumps)) if jumps else None
+        print(f"*** candidates = {K}, select = {args.select}: mean squared step between consecutive plans {report['mean_jump']}")
+        print("mean spread of the candidates per step:", report["mean_spread"])
     times = [p["seconds"] for p in plans]
     print(f"*** {len(plans)} plans, {left_out} way-points past an episode's end left out; plan(): median {np.median(times) * 1e3:.2f} ms")
     print("mean position error per step:", mean)
