@@ -1014,6 +1014,20 @@ int  spdm_debug_fused_upsample_launches(void);
  * per replay.  SPDM_TUNE23 (read once per process) selects the pools: bit 0, 1, 2 = pool 1, 2, 3; default 7; 0 keeps it at 0. */
 int  spdm_debug_pooled_epilogue_launches(void);
 
+/* Host-only test hook (no GPU call, nothing launched): the kernel routes the plan of one U-Net evaluation at batch B chooses
+ * on this handle (its config, switches and weight copies), as SPDM_PLAN_ROUTES_INTS values in out[0 .. cap):
+ *   [0..2]   pool 1, 2, 3:     0 pool_kernel, 1 read through by the next convolution (pro 3), 2 written by the producer's epilogue
+ *   [3..5]   up block 1, 2, 3: 0 upsample + concat kernel, 1 read through by the next convolution (pro 4), 2 upsample kernel +
+ *            two-source convolution
+ *   [6..11]  the FiLM tail of down1..3, up1..3: 0 film_apply, 1 film_coef, 2 coefficients evaluated in the consumers
+ *   [12..41] sa1..6, five values each: {fused, crop, outc, in, tail} -- fused 1: sa_fused64 takes the block, crop 1: for the
+ *            tokens outc reads only, outc 1: with outc in its epilogue; fused 0: in = 0 in_proj GEMM, 1 sa_qkv, 2 sa_head (core
+ *            included) feeds the attention core, tail = 1 sa_tail, 0 the three GEMMs after it.
+ * All zero for a handle without attention (sa values) or a SPDM_FLAG_SIMPLE_UNET handle (everything).  SPDM_ERR_STATE before
+ * spdm_load_weights, SPDM_ERR_INVALID for a null handle, B outside [1, max_batch] or cap < SPDM_PLAN_ROUTES_INTS. */
+#define SPDM_PLAN_ROUTES_INTS 42
+int  spdm_debug_plan_routes(const spdm_handle* h, int32_t B, int32_t* out, int32_t cap);
+
 /* Op-level test hook: d_y = GELU(d_x) evaluated with the device erf that the conv prologues use
  * (nn.GELU(), models/Unet_FiLmLayer.py:104). */
 int  spdm_op_gelu(const float* d_x, float* d_y, size_t n, void* stream);

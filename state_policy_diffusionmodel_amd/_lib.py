@@ -284,6 +284,7 @@ SYMBOLS = {
     "spdm_debug_whole_tiles": (c_int32, []),
     "spdm_debug_fused_upsample_launches": (c_int32, []),
     "spdm_debug_pooled_epilogue_launches": (c_int32, []),
+    "spdm_debug_plan_routes": (c_int32, [c_void_p, c_int32, POINTER(c_int32), c_int32]),
     "spdm_bench_gemm": (c_int32, [c_int32] * 12 + [POINTER(c_double)]),   # ms_out[2]: {ms per launch, max|split - fp32|}
 }
 

@@ -306,10 +306,6 @@ struct spdm_handle {
         }
     } graph_key;
     long long graph_captures = 0;         // step graphs built so far (spdm_graph_captures)
-    int dry_fuse_mask = 0;                // dry runs only: bit k set = resampling op k (pool 0-2, upsample+concat 3-5) is read through
-                                          // by its consumer (Ctx::conv_fused), bits 6-8 = up block k - 6 takes the two-source
-                                          // conv (Ctx::conv_two), bits 9-11 = pool k - 9 is written by its producer's epilogue
-                                          // (Ctx::pool_by_producer) -- the workspace is sized for every combination
     hipGraph_t step_graph = nullptr;
     hipGraphExec_t step_exec = nullptr;
     hipStream_t gstream = nullptr;        // blocking stream the loop runs on when the caller passes the NULL stream
@@ -411,27 +407,7 @@ extern "C" int spdm_schedule_tables(int32_t kind, int32_t T, int32_t n, float be
     return build_schedule(kind, T, n, beta_start, beta_end, ts, coef);
 }
 
-static int plan_forward(spdm_handle* h, int B, bool use_cond, hipStream_t s, Tensor* feat_out);
-// dry runs of the plan at max_batch for every fused / materialised combination of the six resampling ops (Ctx::conv_fused):
-// arena.peak ends as the largest of them (arena.dry must be set by the caller)
-static int dry_plan_all(spdm_handle* h) {
-    size_t peak = 0;
-    for (int mask = 0; mask < 4096; ++mask) {     // bits 0-2 pool read through, 3-5 upsample + concat read through, 6-8 two-source conv,
-                                                  // 9-11 pool written by the producer's epilogue (Ctx::pool_by_producer)
-        if (((mask >> 3) & (mask >> 6) & 7) != 0 || (mask & (mask >> 9) & 7) != 0) continue;       // (a block is one or the other)
-        if (h->simple && mask != 0) break;                         // (plan_simple materialises every resampling op)
-        h->dry_fuse_mask = mask;
-        h->arena.peak = 0;
-        h->arena.reset();
-        Tensor feat;
-        const int rc = plan_forward(h, h->cfg.max_batch, true, nullptr, &feat);
-        if (rc != SPDM_OK) { h->dry_fuse_mask = 0; return rc; }
-        peak = std::max(peak, h->arena.peak);
-    }
-    h->dry_fuse_mask = 0;
-    h->arena.peak = peak;
-    return SPDM_OK;
-}
+static int dry_plan_all(spdm_handle* h);      // the sizing pass, with the plan below
 
 // ---- models/simple_Unet.py in channel-padded storage ----
 // Every tensor and every convolution of this network is stored with a multiple of 64 channels (the implicit-GEMM kernels need
@@ -1314,6 +1290,23 @@ static int stats_slots_reserved(int HW, int C, int slots) {
 // spdm_debug_pooled_epilogue_launches)
 static int g_pooled_epilogue_launches = 0;
 
+// The kernel routes of one U-Net evaluation: Ctx::choose_routes fills them in before the walk (plan_unet), which then only
+// allocates and launches; spdm_debug_plan_routes reports them field by field in this order (all int: 42 values).
+enum { POOL_KERNEL = 0, POOL_READ_THROUGH = 1, POOL_BY_PRODUCER = 2 };   // pool_kernel | the consumer's PRO_POOL | the producer's epilogue
+enum { UP_UPCAT = 0, UP_READ_THROUGH = 1, UP_TWO_SOURCE = 2 };           // upcat kernel | the consumer's PRO_UPCAT | upsample + two-source conv
+enum { FILM_APPLY = 0, FILM_COEF = 1, FILM_LOCAL = 2 };                  // film_apply | film_coef | coefficients evaluated in the consumers
+enum { SA_IN_GEMM = 0, SA_IN_QKV = 1, SA_IN_HEAD = 2 };                  // what feeds the attention core: in_proj GEMM | sa_qkv | sa_head (core included)
+struct AttnRoute {
+    int fused, crop, outc;     // sa_fused64 takes the whole block; ... for the tokens outc reads only (sa6); ... with outc in its epilogue
+    int in, tail;              // otherwise: SA_IN_*, and sa_tail (1) or the three GEMMs (0) after the core -- decided independently
+};
+struct PlanRoutes {
+    int pool[3];               // POOL_* of pool i + 1 (level i -> i + 1)
+    int up[3];                 // UP_* of up block i + 1
+    int film[6];               // FILM_* of the tail of down1..3, up1..3
+    AttnRoute sa[6];           // sa1..6 (all zero without attention: nothing is launched)
+};
+
 struct Ctx {
     spdm_handle* h;
     int B;
@@ -1327,27 +1320,22 @@ struct Ctx {
     int Hl(int l) const { return h->Hp >> l; }
     int Wl(int l) const { return h->Wp >> l; }
 
-    Tensor talloc(int C, int level) {
+    bool reserve(size_t bytes, size_t* off) {       // room in the slab; false, with err set, when it is exhausted
+        if (h->arena.alloc(bytes, off)) return true;
+        if (!err) err = fail(SPDM_ERR_NOMEM, "workspace exhausted (batch %d)", B);
+        return false;
+    }
+    Tensor ralloc(int rows, int C, int level = -1) {       // [rows][C] scratch (attention path)
         Tensor t;
         t.C = C; t.level = level;
         size_t off = 0;
-        if (!h->arena.alloc(sizeof(float) * (size_t)B * HWl(level) * C, &off)) {
-            if (!err) err = fail(SPDM_ERR_NOMEM, "workspace exhausted (batch %d)", B);
-            return t;
-        }
+        if (!reserve(sizeof(float) * (size_t)rows * C, &off)) return t;
         t.off = off; t.p = (float*)(h->arena.base + off); t.valid = true;
-        if (!dry && (h->sw & SW_ARENA_TRACE)) fprintf(stderr, "[spdm] level %d C %3d at %8.2f MiB (%.1f MiB)\n", level, C, off / 1048576.0, (double)B * HWl(level) * C * 4 / 1048576.0);
         return t;
     }
-    Tensor ralloc(int rows, int C) {       // [rows][C] scratch (attention path)
-        Tensor t;
-        t.C = C; t.level = -1;
-        size_t off = 0;
-        if (!h->arena.alloc(sizeof(float) * (size_t)rows * C, &off)) {
-            if (!err) err = fail(SPDM_ERR_NOMEM, "workspace exhausted (batch %d)", B);
-            return t;
-        }
-        t.off = off; t.p = (float*)(h->arena.base + off); t.valid = true;
+    Tensor talloc(int C, int level) {
+        const Tensor t = ralloc(B * HWl(level), C, level);
+        if (t.valid && !dry && (h->sw & SW_ARENA_TRACE)) fprintf(stderr, "[spdm] level %d C %3d at %8.2f MiB (%.1f MiB)\n", level, C, t.off / 1048576.0, (double)B * HWl(level) * C * 4 / 1048576.0);
         return t;
     }
     StatsBuf salloc(int HW, int C, int m_tile, int n_tiles, int C_norm = 0) {     // C_norm > 0: real channels of padded storage
@@ -1355,10 +1343,7 @@ struct Ctx {
         const int slots = stats_slots(HW, m_tile, n_tiles);
         const int slots_max = stats_slots_reserved(HW, C, slots);
         size_t off = 0;
-        if (!h->arena.alloc(sizeof(double) * 2 * (size_t)B * slots_max, &off)) {
-            if (!err) err = fail(SPDM_ERR_NOMEM, "workspace exhausted (batch %d)", B);
-            return sb;
-        }
+        if (!reserve(sizeof(double) * 2 * (size_t)B * slots_max, &off)) return sb;
         sb.off = off; sb.p = (double*)(h->arena.base + off); sb.valid = true;
         sb.ref.p = sb.p; sb.ref.slots = slots; sb.ref.m_tile = m_tile; sb.ref.n_tiles = n_tiles; sb.ref.HW = HW;
         sb.ref.inv_count = 1.0 / ((double)(C_norm > 0 ? C_norm : C) * (double)HW);
@@ -1419,7 +1404,7 @@ struct Ctx {
     }
     // one 3x3 conv: reads `in` (finishing its pending GroupNorm, + GELU if asked, in the load
     // prologue), writes the raw output and its GroupNorm partial sums
-    // pool_out (pool_by_producer said yes): the launch also writes the RAW MaxPool2d(2) map of its output there (GemmArgs::pool_dst);
+    // pool_out (POOL_BY_PRODUCER): the launch also writes the RAW MaxPool2d(2) map of its output there (GemmArgs::pool_dst);
     // pooled_of: `in` is such a map, and the GroupNorm pending on it is that of the finer level's value *pooled_of (PRO_GN_POOLED)
     Value conv(const Value& in, const ConvW& w, int level, bool gelu, const float* gamma, const float* beta,
                const Tensor* pool_out = nullptr, const Value* pooled_of = nullptr) {
@@ -1442,33 +1427,108 @@ struct Ctx {
         if (pool_out) ++g_pooled_epilogue_launches;
         return out;
     }
-    // ---- MaxPool2d(2) written by the epilogue of the kernel that produces the pooled tensor: no pool_kernel launch,
-    //      the tensor is not read back.  Asked BEFORE the producer is launched.  SPDM_TUNE23 (read once per process): bit i = pool i;
-    //      default 7, 0 = pool_kernel everywhere ----
-    // would conv_fused(PRO_POOL) take this block's first convolution?  (conv_skinny at small batch: it keeps priority)
-    bool pool_read_through(const ConvW& w, int level, int C_in) const {
-        if (err || !h->split || (h->sw & SW_NO_FUSED_SRC) || h->arena.keep || h->d_partial == nullptr) return false;
-        if (dry) return (h->dry_fuse_mask >> (level - 1)) & 1;
-        if (!h->weights_loaded || !w.ws || !w.wf || C_in != w.cin) return false;
-        return gemm_takes_fused_source(conv_args(w, level, 1, PRO_POOL, AffineSrc{nullptr, C_in}, 0, AffineSrc{}, nullptr));
+    // ---- the routes: every rule that picks between kernels, decided here, once, before the walk ----
+    // A stand-in for a tensor of the walk in the kernel-selection queries: they read its width and the GroupNorm pending on it
+    // (gn: the DoubleConvolution whose raw output at `level` it is), never its data (any non-null pointer; not dereferenced)
+    AffineSrc route_src(int C, const DoubleConvW* gn = nullptr, int level = 0) const {
+        AffineSrc a{h->d_x, C};
+        if (gn) { a.st.p = (const double*)h->d_x; a.st.HW = HWl(level); a.gamma = gn->gamma; a.beta = gn->beta; }
+        return a;
     }
-    // common part: pool i (level i -> i + 1), consumer w_next = the first convolution of down block i
-    bool pool_by_producer(int i, const ConvW& w_next, int C_in) const {
-        if (err || !h->split || h->arena.keep || !((spdm_tune(23, 7) >> i) & 1) || (Hl(i) & 1) || (Wl(i) & 1)) return false;
-        if (pool_read_through(w_next, i + 1, C_in)) return false;
-        if (dry) return (h->dry_fuse_mask >> (9 + i)) & 1;
-        return h->weights_loaded;
-    }
-    // pool 1: inc's second convolution (w, level 0) on conv_reg.hip at width 8 writes the RAW pooled map (the GroupNorm pending on
-    // x1 stays pending on it), and down1's first convolution, on conv_reg.hip too, applies it on load (PRO_GN_POOLED)
-    bool pool_by_conv_reg(const ConvW& w, const ConvW& w_next) const {
-        if (!pool_by_producer(0, w_next, w.cout) || Wl(0) != 8 || w.cout != w_next.cin) return false;
-        if (dry) return true;
-        if (!w.ws || !w.wf || !w_next.ws || !w_next.wf) return false;
-        const AffineSrc none{};
-        return gemm_geometry(conv_args(w, 0, 1, PRO_GN_GELU, none, 0, none, nullptr)).reg &&
-               gemm_geometry(conv_args(w_next, 1, 1, PRO_GN_POOLED, none, 0, none, nullptr)).reg &&
-               pooled_stats_serial(StatsRef{nullptr, 0, 64, 1, HWl(0), 0.0});       // (x1's slots, one per 64-row wave tile)
+    // A pure function of the handle (config, switches, which weight copies exist) and Bg().  The route of a resampling op depends
+    // on the launch geometry, so on the batch: the sizing pass (dry_plan_all) passes each combination in as `sized`, which answers
+    // in place of the geometry and the weight copies; a route whose other conditions fail falls to the op's own kernel.
+    PlanRoutes choose_routes(const PlanRoutes* sized = nullptr) const {
+        PlanRoutes r{};
+        const bool loaded = h->weights_loaded, keep = h->arena.keep;
+        const unsigned sw = h->sw;
+        // -- SelfAttention.forward (models/Unet_FiLmLayer.py:71-82) and the FiLM tail in front of it --
+        for (int b = 0; b < 6 && h->cfg.attention; ++b) {
+            const AttnW& w = h->sa[b];
+            const int level = b < 3 ? b + 1 : 5 - b, L = HWl(level), C = w.C;
+            AttnRoute& a = r.sa[b];
+            a.fused = h->split && sa_fused_supported(L, C) && !(sw & SW_NO_SA_FUSED) && (!loaded || w.fw[0]);
+            // The last block (sa6) feeds only outc + unpad, which read the H0 x D tokens of the trajectory: sa_fused64 then computes
+            // the block for those tokens only (SaCrop).  Not in debug runs (the a6 tap keeps its full meaning).
+            a.crop = a.fused && b == 5 && !keep && !(sw & SW_NO_SA_CROP) && sa_crop_supported(L, C, h->cfg.horizon, h->cfg.state_dim);
+            a.outc = a.crop && !(sw & SW_NO_SA_OUTC) && h->outc_w;
+            const bool tail_kernels = h->split && sa_tail_supported(C, sw);       // sa_tail.hip: sa_qkv / sa_head / sa_tail
+            // May the FiLM tail be folded into the block's loads (film_coef)?  Only the kernels that read the block input themselves
+            // take the coefficients: sa_fused64 (the two-workgroup mode for longer sequences has no registers left) and the
+            // sa_qkv / sa_tail pair.
+            const bool fold = !keep && h->split && !(sw & SW_NO_FILM_FOLD) &&
+                              (a.fused ? L <= 256 : tail_kernels && (!loaded || (w.qkv_wf && w.tail_wf[0])));
+            // ... and may those kernels evaluate the coefficients themselves (no film_coef launch)?
+            // Only at the smallest batches (every launch a single workgroup): measured on the whole step (same box, alternating,
+            // graph replay), evaluating the coefficients inside the consumers saves 5 us per step at batch 1-4 (0.490 -> 0.485 ms) and
+            // COSTS 8 us at batch 64, 10-30 us at 512, ~50 us at 4096 -- every workgroup of sa_qkv / sa_tail repeats the statistics
+            // round trip and one barrier that the 5-us film_coef launch does once per sample.  SPDM_FILM_LOCAL=1 forces it on (tests).
+            const bool local = fold && !(sw & SW_NO_FILM_LOCAL) && (Bg() <= 4 || (sw & SW_FILM_LOCAL)) &&
+                               (a.fused || sa_tail_film_local(C, L));
+            r.film[b] = local ? FILM_LOCAL : fold ? FILM_COEF : FILM_APPLY;
+            if (a.fused) continue;
+            // LayerNorm + in_proj + attention core in ONE kernel where the row tile holds whole samples (sa_head_kernel): q, k, v never
+            // reach memory.
+            // Only on large grids: a workgroup of the fused kernel is a 25-30 us chain (LayerNorm, twelve small products, four rounds of
+            // q/k/v tiles -> scores -> softmax -> P v with two to four barriers each) at two workgroups per CU, so it needs many rounds
+            // of workgroups to beat three launches that each fill the chip.  Measured (traced, same box; q/k/v + core launches -> fused):
+            // B = 4096: sa1 281 -> 234 us, sa2 171 -> 164, sa4 75 -> 70, sa3 50 -> 52; B = 512: 35 -> 38, 34 -> 44, 19 -> 32, 17 -> 34;
+            // B = 64: 13-17 -> 26-32 us each.  Rule: at least 2048 row tiles (SPDM_SA_HEAD=1 forces the fused kernel at any size: tests; SPDM_TUNE16: the threshold).
+            const int TMh = 8192 / C;
+            const bool head = tail_kernels && sa_head_supported(C, L, sw) && loaded && w.qkv_wf && (!local || sa_tail_film_local(C, L)) &&
+                              ((Bg() * L + TMh - 1) / TMh) >= ((sw & SW_SA_HEAD) ? 1 : spdm_tune(16, 2048));
+            a.in = head ? SA_IN_HEAD : (tail_kernels && (!loaded || w.qkv_wf)) ? SA_IN_QKV : SA_IN_GEMM;
+            a.tail = tail_kernels && (!loaded || w.tail_wf[0]);
+        }
+        // -- the fused sources of a Down / UpSample block's first convolution (read-through, two-source) --
+        const bool src_ok = h->split && !(sw & SW_NO_FUSED_SRC) && !keep;
+        const int C_x1 = h->inc.second.cout;
+        for (int i = 0; i < 3; ++i) {      // pool i + 1 (level i -> i + 1); consumer wn = the first convolution of down block i + 1
+            const ConvW& wn = h->down[i].dc1.first;
+            const int C_in = i ? h->down[i - 1].cout : C_x1;
+            // MaxPool2d(2) read through by that convolution (PRO_POOL: conv_skinny at small batch; it keeps priority)
+            const bool through = src_ok && h->d_partial != nullptr && C_in == wn.cin &&
+                (sized ? sized->pool[i] == POOL_READ_THROUGH
+                       : loaded && wn.ws && wn.wf && gemm_takes_fused_source(conv_args(wn, i + 1, 1, PRO_POOL, AffineSrc{nullptr, C_in}, 0, AffineSrc{}, nullptr)));
+            // MaxPool2d(2) written by the epilogue of the kernel that produces the tensor being pooled: no pool_kernel launch, the
+            // tensor is not read back.  SPDM_TUNE23 (read once per process): bit i = pool i + 1; default 7, 0 = pool_kernel everywhere
+            bool by_producer = h->split && !keep && ((spdm_tune(23, 7) >> i) & 1) && !(Hl(i) & 1) && !(Wl(i) & 1) && !through &&
+                               (sized ? sized->pool[i] == POOL_BY_PRODUCER : loaded);
+            if (i == 0) {
+                // pool 1: inc's second convolution (w, level 0) on conv_reg.hip at width 8 writes the RAW pooled map (the GroupNorm
+                // pending on x1 stays pending on it), and down1's first convolution, on conv_reg.hip too, applies it on load
+                // (PRO_GN_POOLED)
+                const ConvW& w = h->inc.second;
+                const AffineSrc none{};
+                by_producer = by_producer && Wl(0) == 8 && w.cout == wn.cin &&
+                    (sized || (w.ws && w.wf && wn.ws && wn.wf &&
+                               gemm_geometry(conv_args(w, 0, 1, PRO_GN_GELU, none, 0, none, nullptr)).reg &&
+                               gemm_geometry(conv_args(wn, 1, 1, PRO_GN_POOLED, none, 0, none, nullptr)).reg &&
+                               pooled_stats_serial(StatsRef{nullptr, 0, 64, 1, HWl(0), 0.0})));       // (x1's slots, one per 64-row wave tile)
+            } else {
+                // pools 2 and 3: the block output (sa1, sa2) is finished, so sa_tail's epilogue writes its plain MaxPool2d(2) --
+                // where every window lies inside one workgroup's rows
+                const AttnRoute& a = r.sa[i - 1];
+                by_producer = by_producer && h->cfg.attention && !a.fused && a.tail && sa_tail_pools(h->sa[i - 1].C, HWl(i), Wl(i), B * HWl(i));
+            }
+            r.pool[i] = by_producer ? POOL_BY_PRODUCER : through ? POOL_READ_THROUGH : POOL_KERNEL;
+        }
+        for (int i = 0; i < 3; ++i) {      // up block i + 1 (level 3 - i -> 2 - i): cat([upsample x2 of src, skip]) into w
+            const ConvW& w = h->up[i].dc1.first;
+            const int lout = 2 - i;
+            // src: x5 (its GroupNorm pending), then the up blocks' outputs; skip: x3, x2, then x1 (pending)
+            const AffineSrc src = i ? route_src(h->up[i - 1].cout) : route_src(h->bot[2].second.cout, &h->bot[2], 3);
+            const AffineSrc skip = i < 2 ? route_src(h->down[1 - i].cout) : route_src(C_x1, &h->inc, 0);
+            const bool fits = src_ok && src.C + skip.C == w.cin, copies = loaded && w.ws && w.wf;
+            // upsample + concat read through by the convolution (PRO_UPCAT: conv_skinny, or conv_wide's whole-sample tiles) ...
+            const bool through = fits && h->d_partial != nullptr &&
+                (sized ? sized->up[i] == UP_READ_THROUGH : copies && gemm_takes_fused_source(conv_args(w, lout, 1, PRO_UPCAT, src, src.C, skip, nullptr)));
+            // ... or upsample only: the convolution reads [upsampled | skip] from the two tensors (conv_wide.hip TWO)
+            const bool two = !through && fits &&
+                (sized ? sized->up[i] == UP_TWO_SOURCE : copies && gemm_takes_two_sources(two_args(src.x, skip, w, lout, nullptr)));
+            r.up[i] = through ? UP_READ_THROUGH : two ? UP_TWO_SOURCE : UP_UPCAT;
+        }
+        return r;
     }
     void prof_begin() {
         if (!h->prof || h->prof_open >= 0 || dry || err) return;
@@ -1503,61 +1563,40 @@ struct Ctx {
     }
     // The FIRST convolution of a Down / UpSample block reading its input THROUGH the resampling op (GemmArgs "fused sources":
     // PRO_POOL: MaxPool2d(2) of src0, the finer level's value; PRO_UPCAT: cat([upsample x2 of src0 (coarser level), skip])) --
-    // no pooled / concatenated tensor is written or read back, and one launch less.  Returns false, with nothing allocated or
-    // launched, when the kernel launch_gemm would pick for this shape does not take fused sources (the caller then materialises).
-    bool conv_fused(int mode, const Value& src0, const Value* skip, const ConvW& w, int level, const float* gamma,
-                    const float* beta, Value* out_v) {
-        if (err || !h->split || (h->sw & SW_NO_FUSED_SRC) || h->arena.keep || h->d_partial == nullptr) return false;
-        if (dry) {
-            // sizing pass: the fused / materialised choice of a real run depends on its batch (launch geometry), so the dry runs walk
-            // every combination (spdm_handle::dry_fuse_mask) and the slab is sized for the worst
-            if (!((h->dry_fuse_mask >> fuse_slot) & 1)) return false;
-            *out_v = conv_out(w, level, dry_geometry(w, level), gamma, beta);
-            return true;
-        }
-        if (!h->weights_loaded || !w.ws || !w.wf) return false;
-        const bool upcat = mode == PRO_UPCAT;
-        if (upcat ? (!skip || src0.t.C + skip->t.C != w.cin) : src0.t.C != w.cin) return false;
+    // no pooled / concatenated tensor is written or read back, and one launch less.  Where the route says so (POOL_READ_THROUGH,
+    // UP_READ_THROUGH: choose_routes asked gemm_takes_fused_source about these very arguments).
+    Value conv_fused(int mode, const Value& src0, const Value* skip, const DoubleConvW& dc, int level) {
         auto args = [&](const Value* out) {
-            return conv_args(w, level, 1, mode, asrc(src0), upcat ? src0.t.C : 0, upcat ? asrc(*skip) : AffineSrc{}, out);
+            return conv_args(dc.first, level, 1, mode, asrc(src0), skip ? src0.t.C : 0, skip ? asrc(*skip) : AffineSrc{}, out);
         };
-        if (!gemm_takes_fused_source(args(nullptr))) return false;
-        *out_v = conv_out(w, level, gemm_geometry(args(nullptr)), gamma, beta);
-        if (!err) gemm(args(out_v), "conv3x3 implicit GEMM (fused source)");
-        return true;
+        return conv_first(dc, level, args, "conv3x3 implicit GEMM (fused source)");
+    }
+    // ... on the launch args(out) builds: the output in that launch's statistics layout (sizing pass: by shape), then the launch
+    template <class Args> Value conv_first(const DoubleConvW& dc, int level, Args args, const char* what) {
+        Value out = conv_out(dc.first, level, dry ? dry_geometry(dc.first, level) : gemm_geometry(args(nullptr)), dc.gamma, dc.beta);
+        if (!err && !dry) gemm(args(&out), what);
+        return out;
     }
     // The first convolution of an UpSample block with a TWO-SOURCE input (conv_wide.hip TWO): channels [0, C_up) from `up2x`, the
     // upsampled tensor (finished), the rest from the skip connection, whose pending GroupNorm is the load prologue.  torch.cat
-    // (models/Unet_FiLmLayer.py:218) is never materialised.  Returns false, nothing done, when the launch would not be a
-    // two-source configuration.
-    bool conv_two(const Tensor& up2x, const Value& skip, const ConvW& w, int level, const float* gamma, const float* beta, Value* out_v) {
-        if (!conv_two_ok(up2x.C, skip, w, level)) return false;
-        *out_v = conv_out(w, level, dry ? dry_geometry(w, level) : gemm_geometry(two_args(up2x.p, skip, w, level, nullptr)), gamma, beta);
-        if (!err && !dry) gemm(two_args(up2x.p, skip, w, level, out_v), "conv3x3 implicit GEMM (two-source input)");
-        return true;
-    }
-    // would conv_two take this block?  (asked BEFORE the upsample is launched: C_up channels of it)
-    bool conv_two_ok(int C_up, const Value& skip, const ConvW& w, int level) const {
-        if (err || !h->split || (h->sw & SW_NO_FUSED_SRC) || h->arena.keep || C_up + skip.t.C != w.cin) return false;
-        if (dry) return (h->dry_fuse_mask >> (3 + fuse_slot)) & 1;       // sizing pass (see conv_fused): bit 6 + block of dry_fuse_mask
-        // (up: any non-null pointer; not dereferenced)
-        return h->weights_loaded && w.ws && w.wf && gemm_takes_two_sources(two_args(skip.t.p, skip, w, level, nullptr));
+    // (models/Unet_FiLmLayer.py:218) is never materialised.  Where the route is UP_TWO_SOURCE (choose_routes asked
+    // gemm_takes_two_sources BEFORE the upsample is launched).
+    Value conv_two(const Tensor& up2x, const Value& skip, const DoubleConvW& dc, int level) {
+        return conv_first(dc, level, [&](const Value* out) { return two_args(up2x.p, asrc(skip), dc.first, level, out); },
+                          "conv3x3 implicit GEMM (two-source input)");
     }
     // conv_two's launch: input channels [0, C_up) from `up` (finished), the rest from the skip connection, whose pending GroupNorm
     // is the load prologue
-    GemmArgs two_args(const float* up, const Value& skip, const ConvW& w, int level, const Value* out) const {
-        const int C_up = w.cin - skip.t.C;
-        return conv_args(w, level, 1, skip.pending_gn() ? PRO_GN : PRO_NONE, AffineSrc{up, C_up}, C_up, asrc(skip), out);
+    GemmArgs two_args(const float* up, const AffineSrc& skip, const ConvW& w, int level, const Value* out) const {
+        const int C_up = w.cin - skip.C;
+        return conv_args(w, level, 1, skip.st.p ? PRO_GN : PRO_NONE, AffineSrc{up, C_up}, C_up, skip, out);
     }
     // y[rows][N] = x[rows][K] @ W^T + b  (+GELU | +resid)
     // per-token LayerNorm statistics buffer: [rows][n_tiles][2] fp64 (StatsRef with HW = 1: "sample" = row)
     StatsBuf row_stats_alloc(int rows, int C, int n_tiles) {
         StatsBuf sb;
         size_t off = 0;
-        if (!h->arena.alloc(sizeof(double) * 2 * (size_t)rows * std::max(n_tiles, C / 64), &off)) {   // finest tiling
-            if (!err) err = fail(SPDM_ERR_NOMEM, "workspace exhausted (batch %d)", B);
-            return sb;
-        }
+        if (!reserve(sizeof(double) * 2 * (size_t)rows * std::max(n_tiles, C / 64), &off)) return sb;   // finest tiling
         sb.off = off; sb.p = (double*)(h->arena.base + off); sb.valid = true;
         sb.ref.p = sb.p; sb.ref.slots = n_tiles; sb.ref.m_tile = 1 << 30; sb.ref.n_tiles = n_tiles; sb.ref.HW = 1;
         sb.ref.inv_count = 1.0 / (double)C;
@@ -1572,39 +1611,24 @@ struct Ctx {
     }
     // SelfAttention.forward, models/Unet_FiLmLayer.py:71-82.  Consumes x (and its per-token LayerNorm
     // statistics xs, produced by film_apply), returns the block output.  Both LayerNorms run as the load
-    // prologue of the GEMM that consumes them: self.ln -> in_proj, ff_self[0] -> ff_self[1].
-    bool sa_fused(const AttnW& w, int level) const {
-        return h->split && sa_fused_supported(HWl(level), w.C) && !(h->sw & SW_NO_SA_FUSED) && (!h->weights_loaded || w.fw[0]);
-    }
-    // The last block (sa6) feeds only outc + unpad, which read the H0 x D tokens of the trajectory: sa_fused64 then computes the
-    // block for those tokens only (SaCrop).  Not in debug runs (the a6 tap keeps its full meaning).
-    bool sa_crop(const AttnW& w, int level) const {
-        return sa_fused(w, level) && !h->arena.keep && !(h->sw & SW_NO_SA_CROP) &&
-               sa_crop_supported(HWl(level), w.C, h->cfg.horizon, h->cfg.state_dim);
-    }
-    bool eps_ready = false;    // the plan's final tensor holds eps [B][H0][D] (outc applied by sa6's epilogue): StepArgs::eps_in
+    // prologue of the GEMM that consumes them: self.ln -> in_proj, ff_self[0] -> ff_self[1].  The launches: routes.sa[blk].
     // ab (optional): x is the RAW conv output and the block input is ab-affine of it (film_coef); consumed here.
     // fs (optional, instead of ab): the kernels evaluate those coefficients themselves (FilmSpec, kernels.h)
-    // final_outc: the block's only consumer is outc + unpad (sa6 of plan_unet)
-    Tensor attention(Tensor& x, StatsBuf& xs, const AttnW& w, int level, Tensor* ab = nullptr, const FilmSpec* fs = nullptr,
-                     bool final_outc = false) {
+    // pool_out (POOL_BY_PRODUCER of the next pool): sa_tail also writes the MaxPool2d(2) of the block output, reserved here
+    Tensor attention(Tensor& x, StatsBuf& xs, int blk, int level, Tensor* ab, const FilmSpec* fs, Tensor* pool_out) {
+        const AttnW& w = h->sa[blk];
+        const AttnRoute& route = routes.sa[blk];
         const int L = HWl(level), rows = B * L, C = w.C;
         const float* abp = (ab && ab->valid) ? ab->p : nullptr;
-        if (sa_fused(w, level)) {            // whole block in one kernel (sa_fused.hip)
+        if (route.fused) {                   // whole block in one kernel (sa_fused.hip)
             // (cropped: the same tensor is reserved -- the dry run sizes both routes alike -- and holds the block output at the
             //  query tokens only, or, with outc folded in, eps [B][H0][D] at its start)
             Tensor out = talloc(C, level);
-            SaCrop crop{h->cfg.horizon, h->cfg.state_dim, h->Wp, h->lh, h->lw, nullptr, 0.f, nullptr};
-            const bool cropped = final_outc && sa_crop(w, level);
-            if (cropped && !(h->sw & SW_NO_SA_OUTC) && h->outc_w) {
-                crop.outc_w = h->outc_w;
-                crop.outc_b = h->outc_b;
-                crop.eps = out.p;
-                eps_ready = true;
-            }
+            const bool oc = route.outc;
+            const SaCrop crop{h->cfg.horizon, h->cfg.state_dim, h->Wp, h->lh, h->lw, oc ? h->outc_w : nullptr, oc ? h->outc_b : 0.f, oc ? out.p : nullptr};
             if (!err && !dry)
                 check(launch_sa_fused64(x.p, out.p, B, L, w.ln_g, w.ln_b, w.ff_ln_g, w.ff_ln_b, w.fw, w.in_proj.b,
-                                        w.out_proj.b, w.ff1.b, w.ff2.b, abp, h->sw, s, fs, cropped ? &crop : nullptr),
+                                        w.out_proj.b, w.ff1.b, w.ff2.b, abp, h->sw, s, fs, route.crop ? &crop : nullptr),
                       "fused attention block");
             free(x);
             free(xs);
@@ -1612,25 +1636,12 @@ struct Ctx {
             return out;
         }
         Tensor qkv = ralloc(rows, 3 * C);
-        // LayerNorm + in_proj + attention core in ONE kernel where the row tile holds whole samples (sa_head_kernel): q, k, v never
-        // reach memory.  (The workspace operations stay those of the three-launch path -- qkv is reserved and released unused -- so
-        // the slab sized by the dry run fits whichever path a call takes.)
-        // Only on large grids: a workgroup of the fused kernel is a 25-30 us chain (LayerNorm, twelve small products, four rounds of
-        // q/k/v tiles -> scores -> softmax -> P v with two to four barriers each) at two workgroups per CU, so it needs many rounds
-        // of workgroups to beat three launches that each fill the chip.  Measured (traced, same box; q/k/v + core launches -> fused):
-        // B = 4096: sa1 281 -> 234 us, sa2 171 -> 164, sa4 75 -> 70, sa3 50 -> 52; B = 512: 35 -> 38, 34 -> 44, 19 -> 32, 17 -> 34;
-        // B = 64: 13-17 -> 26-32 us each.  Rule: at least 2048 row tiles (SPDM_SA_HEAD=1 forces the fused kernel at any size: tests; SPDM_TUNE16: the threshold).
-        const int TMh = 8192 / C;
-        const bool head = h->split && sa_tail_supported(C, h->sw) && sa_head_supported(C, L, h->sw) && h->weights_loaded && w.qkv_wf &&
-                          (!fs || sa_tail_film_local(C, L)) && ((Bg() * L + TMh - 1) / TMh) >= ((h->sw & SW_SA_HEAD) ? 1 : spdm_tune(16, 2048));
-        if (!head) {
-            if (h->split && sa_tail_supported(C, h->sw) && (!h->weights_loaded || w.qkv_wf)) {     // LayerNorm + in_proj in one 64-row kernel (sa_tail.hip)
-                if (!err && !dry)
-                    check(launch_sa_qkv(C, x.p, qkv.p, rows, w.qkv_wf, w.in_proj.b, w.ln_g, w.ln_b, abp, L, s, fs), "attention in_proj");
-            } else {
-                linear(x.p, C, rows, w.in_proj, qkv.p, EPI_BIAS, nullptr, &xs, w.ln_g, w.ln_b);
-            }
-        }
+        // (SA_IN_HEAD: the workspace operations stay those of the three-launch path -- qkv is reserved and released unused -- so the
+        // slab sized by the dry run fits whichever path a call takes.)
+        const bool head = route.in == SA_IN_HEAD;
+        if (route.in == SA_IN_QKV && !err && !dry)       // LayerNorm + in_proj in one 64-row kernel (sa_tail.hip)
+            check(launch_sa_qkv(C, x.p, qkv.p, rows, w.qkv_wf, w.in_proj.b, w.ln_g, w.ln_b, abp, L, s, fs), "attention in_proj");
+        if (route.in == SA_IN_GEMM) linear(x.p, C, rows, w.in_proj, qkv.p, EPI_BIAS, nullptr, &xs, w.ln_g, w.ln_b);
         free(xs);
         Tensor att = ralloc(rows, C);
         if (!err && !dry) {
@@ -1638,15 +1649,13 @@ struct Ctx {
             else check(launch_attention_auto(qkv.p, att.p, B, L, C, 4, h->sw, s), "attention core");
         }
         free(qkv);
-        if (h->split && sa_tail_supported(C, h->sw) && (!h->weights_loaded || w.tail_wf[0])) {
+        if (route.tail) {
             // out_proj + residual + LayerNorm + ff_self + residual in one kernel (sa_tail.hip)
             Tensor out = talloc(C, level);
-            // pools 2 and 3: the block output is finished, so the tail's epilogue writes its plain MaxPool2d(2) (pool_want: the
-            // plan asked for it; taken where every window lies inside one workgroup's rows)
             float* pool = nullptr;
-            if (pool_want && sa_tail_pools(C, L, Wl(level), rows)) {
-                *pool_want = talloc(C, level + 1);
-                pool = pool_want->p;
+            if (pool_out) {             // (reserved here, after `out`: the order of the workspace operations decides the offsets)
+                *pool_out = talloc(C, level + 1);
+                pool = pool_out->p;
             }
             if (!err && !dry) {
                 check(launch_sa_tail(C, att.p, x.p, out.p, rows, w.tail_wf[0], w.tail_wf[1], w.tail_wf[2], w.out_proj.b, w.ff1.b,
@@ -1672,23 +1681,6 @@ struct Ctx {
         free(f1);
         free(av);
         return out;
-    }
-    // May the FiLM tail feeding this attention block be folded into the block's loads?  Only the kernels that read the
-    // block input themselves take the coefficients: sa_fused64 and the C = 128 pair sa_qkv128 / sa_tail128.
-    bool film_foldable(const AttnW& w, int level) const {
-        if (!h->cfg.attention || h->arena.keep || !h->split || (h->sw & SW_NO_FILM_FOLD)) return false;
-        if (sa_fused(w, level)) return HWl(level) <= 256;      // (the two-workgroup mode for longer sequences has no registers left)
-        return sa_tail_supported(w.C, h->sw) && (!h->weights_loaded || (w.qkv_wf && w.tail_wf[0]));
-    }
-    // ... and may those kernels evaluate the coefficients themselves (no film_coef launch)?
-    // Only at the smallest batches (every launch a single workgroup): measured on the whole step (same box, alternating,
-    // graph replay), evaluating the coefficients inside the consumers saves 5 us per step at batch 1-4 (0.490 -> 0.485 ms) and
-    // COSTS 8 us at batch 64, 10-30 us at 512, ~50 us at 4096 -- every workgroup of sa_qkv / sa_tail repeats the statistics
-    // round trip and one barrier that the 5-us film_coef launch does once per sample.  SPDM_FILM_LOCAL=1 forces it on (tests).
-    bool film_local(const AttnW& w, int level) const {
-        if (!film_foldable(w, level) || (h->sw & SW_NO_FILM_LOCAL)) return false;
-        if (Bg() > 4 && !(h->sw & SW_FILM_LOCAL)) return false;
-        return sa_fused(w, level) || sa_tail_film_local(w.C, HWl(level));
     }
     FilmSpec film_spec(const Value& v, const ResampleW& w, int blk, bool use_cond) const {
         FilmSpec f{};
@@ -1721,28 +1713,36 @@ struct Ctx {
         return y;
     }
     // the block tail (film_tail; tap `name` where it is materialised) and the SelfAttention block sa[blk] after it.  The attention
-    // kernels finish the tail themselves from the raw tensor (film_local), take it as coefficients on load (film_foldable), or
-    // read the materialised tensor.  Consumes v.
-    Tensor film_attention(Value& v, const ResampleW& w, int blk, int level, bool use_cond, const char* name, bool final_outc = false) {
-        const AttnW& sa = h->sa[blk];
+    // kernels finish the tail themselves from the raw tensor (FILM_LOCAL), take it as coefficients on load (FILM_COEF), or
+    // read the materialised tensor.  Consumes v.  pool_out: see attention.
+    Tensor film_attention(Value& v, const ResampleW& w, int blk, int level, bool use_cond, const char* name, Tensor* pool_out = nullptr) {
+        const bool local = routes.film[blk] == FILM_LOCAL;
+        const FilmSpec fs = local ? film_spec(v, w, blk, use_cond) : FilmSpec{};
         StatsBuf ys;
         Tensor y, ab;
-        if (film_local(sa, level)) {
-            const FilmSpec fs = film_spec(v, w, blk, use_cond);
+        if (local) {
             y = v.t;
             v.t.valid = false;
-            y = attention(y, ys, sa, level, nullptr, &fs, final_outc);
-            free(v);                               // (its statistics: released after the last launch that reads them is enqueued)
-            return y;
-        }
-        if (film_foldable(sa, level)) {
+        } else if (routes.film[blk] == FILM_COEF) {
             y = film_coef(v, w, blk, use_cond, &ab);
         } else {
-            y = film_tail(v, w, blk, level, use_cond, (h->cfg.attention && !sa_fused(sa, level)) ? &ys : nullptr);
+            y = film_tail(v, w, blk, level, use_cond, (h->cfg.attention && !routes.sa[blk].fused) ? &ys : nullptr);
             tap(name, y);
         }
-        if (h->cfg.attention) y = attention(y, ys, sa, level, &ab, nullptr, final_outc);
+        if (h->cfg.attention) y = attention(y, ys, blk, level, &ab, local ? &fs : nullptr, pool_out);
+        if (local) free(v);                        // (its statistics: released after the last launch that reads them is enqueued)
         return y;
+    }
+    // the network's first convolution (1 -> 64 stored channels, C_norm > 0 real ones) on the zero-padded trajectory x
+    Value conv_in(const float* x, int C_norm = 0) {
+        Value v0;
+        v0.t = talloc(64, 0);
+        v0.st = salloc(HWl(0), 64, HWl(0) / conv_in_parts(h->Hp, h->Wp, Bg()), 1, C_norm);
+        v0.gamma = h->inc.gamma; v0.beta = h->inc.beta;
+        if (!err && !dry)
+            check(launch_conv_in(x, h->w_inc_first, v0.t.p, v0.st.p, B, h->cfg.horizon, h->cfg.state_dim, h->Hp, h->Wp,
+                                 h->lh, h->lw, h->d_step, h->d_t, h->d_timesteps, h->n_steps, adv, s, Bg()), "conv_in");
+        return v0;
     }
     // debug runs (arena.keep): the finished tensor of a value with a pending GroupNorm, as tap `name`
     void tap_gn(const char* name, const Value& v, int level) {
@@ -1752,26 +1752,21 @@ struct Ctx {
         tap(name, m);
     }
     int h_tcount = 1;
-    Tensor* pool_want = nullptr;      // set around film_attention: sa_tail may write the MaxPool2d(2) of the block output here
-    int fuse_slot = 0;     // which resampling op conv_fused is being asked about (dry runs: bit of dry_fuse_mask)
+    PlanRoutes routes{};   // of this evaluation (plan_unet: choose_routes); routes.sa[5].outc: the plan's final tensor holds eps
+                           // [B][H0][D] (outc applied by sa6's epilogue): StepArgs::eps_in
     int adv = -2;          // loop bookkeeping done by conv_in_kernel: -2 none, -1 advance, >= 0 set
 };
 
 // one U-Net evaluation on h->d_x... : x (B,H0,D) -> feat (B, Hp*Wp, 64)
-static int plan_unet(Ctx& c, const float* x, bool use_cond, Tensor* feat_out) {
+static int plan_unet(Ctx& c, const float* x, bool use_cond, Tensor* feat_out, const PlanRoutes* sized) {
     spdm_handle* h = c.h;
     const int B = c.B;
+    const PlanRoutes& r = c.routes = c.choose_routes(sized);       // every choice between kernels: the walk allocates and launches
     // ---- inc = DoubleConvolution(1, 64) on the zero-padded trajectory (:286-288) ----
-    Value v0;
-    v0.t = c.talloc(64, 0);
-    v0.st = c.salloc(c.HWl(0), 64, c.HWl(0) / conv_in_parts(h->Hp, h->Wp, c.Bg()), 1);
-    v0.gamma = h->inc.gamma; v0.beta = h->inc.beta;
-    if (!c.err && !c.dry)
-        c.check(launch_conv_in(x, h->w_inc_first, v0.t.p, v0.st.p, B, h->cfg.horizon, h->cfg.state_dim, h->Hp, h->Wp,
-                               h->lh, h->lw, h->d_step, h->d_t, h->d_timesteps, h->n_steps, c.adv, c.s, c.Bg()), "conv_in");
+    Value v0 = c.conv_in(x);
     // (pooled[i]: the input of down block i where its producer wrote it -- reserved before that launch)
     Tensor pooled[3];
-    const bool pool1 = c.pool_by_conv_reg(h->inc.second, h->down[0].dc1.first);
+    const bool pool1 = r.pool[0] == POOL_BY_PRODUCER;
     if (pool1) pooled[0] = c.talloc(64, 1);
     Value x1 = c.conv(v0, h->inc.second, 0, /*gelu=*/true, h->inc.gamma, h->inc.beta, pool1 ? &pooled[0] : nullptr);   // x1 = GN(raw), pending
     c.free(v0);
@@ -1786,40 +1781,32 @@ static int plan_unet(Ctx& c, const float* x, bool use_cond, Tensor* feat_out) {
     for (int i = 0; i < 3; ++i) {
         const int lin = i, lout = i + 1;
         // `cur` stays alive: it is a skip connection
-        Value a, mid;
-        c.fuse_slot = i;
-        if (pooled[i].valid) {
-            // MaxPool2d(2) written by cur's producer: raw with cur's GroupNorm pending (pool 1), or finished (pools 2 and 3)
-            Value p;
-            p.t = pooled[i];
+        const DoubleConvW& dc1 = h->down[i].dc1;
+        Value mid;             // the block's first convolution, of MaxPool2d(2)(cur)
+        if (r.pool[i] == POOL_READ_THROUGH) {        // read through by that convolution (small grids)
+            mid = c.conv_fused(PRO_POOL, cur, nullptr, dc1, lout);
             c.prof_begin();
-            mid = c.conv(p, h->down[i].dc1.first, lout, /*gelu=*/false, h->down[i].dc1.gamma, h->down[i].dc1.beta, nullptr,
-                         cur.pending_gn() ? &cur : nullptr);
-            c.free(p);
-            a = c.conv(mid, h->down[i].dc1.second, lout, /*gelu=*/true, h->down[i].dc1.gamma, h->down[i].dc1.beta);
-            c.free(mid);
-        } else if (c.conv_fused(PRO_POOL, cur, nullptr, h->down[i].dc1.first, lout, h->down[i].dc1.gamma, h->down[i].dc1.beta, &mid)) {
-            c.prof_begin();      // MaxPool2d(2) read through by the block's first conv (small grids)
-            a = c.conv(mid, h->down[i].dc1.second, lout, /*gelu=*/true, h->down[i].dc1.gamma, h->down[i].dc1.beta);
-            c.free(mid);
         } else {
+            // written by cur's producer -- raw with cur's GroupNorm pending (pool 1), or finished (pools 2 and 3) -- or by pool_kernel
+            const bool by_producer = r.pool[i] == POOL_BY_PRODUCER;
             Value p;
-            p.t = c.talloc(cur.t.C, lout);
-            if (!c.err && !c.dry)
+            p.t = by_producer ? pooled[i] : c.talloc(cur.t.C, lout);
+            if (!by_producer && !c.err && !c.dry)
                 c.check(launch_pool(c.asrc(cur), p.t.p, B, c.Hl(lin), c.Wl(lin), c.s), "maxpool");
             c.prof_begin();
-            a = c.double_conv(p, h->down[i].dc1, lout);
+            mid = c.conv(p, dc1.first, lout, /*gelu=*/false, dc1.gamma, dc1.beta, nullptr, (by_producer && cur.pending_gn()) ? &cur : nullptr);
+            c.free(p);
         }
+        Value a = c.conv(mid, dc1.second, lout, /*gelu=*/true, dc1.gamma, dc1.beta);
+        c.free(mid);
         Value b2 = c.double_conv(a, h->down[i].dc2, lout);
         c.prof_end();
-        if (i < 2 && c.pool_by_producer(i + 1, h->down[i + 1].dc1.first, h->down[i].cout)) c.pool_want = &pooled[i + 1];
-        const Tensor y = c.film_attention(b2, h->down[i], i, lout, use_cond, dn[i]);
-        c.pool_want = nullptr;
+        const Tensor y = c.film_attention(b2, h->down[i], i, lout, use_cond, dn[i],
+                                          (i < 2 && r.pool[i + 1] == POOL_BY_PRODUCER) ? &pooled[i + 1] : nullptr);
         c.tap(xn[i], y);
-        Value nv;
-        nv.t = y;
-        cur = nv;
-        if (i < 2) skips[i + 1] = nv;
+        cur = Value{};             // (finished: nothing pending)
+        cur.t = y;
+        if (i < 2) skips[i + 1] = cur;
     }
     // ---- bottleneck (:297-299) ----
     c.prof_begin();
@@ -1835,27 +1822,23 @@ static int plan_unet(Ctx& c, const float* x, bool use_cond, Tensor* feat_out) {
     for (int i = 0; i < 3; ++i) {
         const int lin = 3 - i, lout = 2 - i;
         Value& skip = skips[2 - i];
-        Value a, mid;
-        c.fuse_slot = 3 + i;
-        if (c.conv_fused(PRO_UPCAT, cur, &skip, h->up[i].dc1.first, lout, h->up[i].dc1.gamma, h->up[i].dc1.beta, &mid)) {
-            c.free(cur);         // upsample + concat read through by the block's first conv: released once that launch is enqueued
+        const DoubleConvW& dc1 = h->up[i].dc1;
+        Value mid;             // the block's first convolution, of cat([upsample x2 of cur, skip])
+        if (r.up[i] == UP_READ_THROUGH) {
+            mid = c.conv_fused(PRO_UPCAT, cur, &skip, dc1, lout);
+            c.free(cur);         // upsample + concat read through by that convolution: released once its launch is enqueued
             c.free(skip);
             c.prof_begin();
-            a = c.conv(mid, h->up[i].dc1.second, lout, /*gelu=*/true, h->up[i].dc1.gamma, h->up[i].dc1.beta);
-            c.free(mid);
-        } else if (c.conv_two_ok(cur.t.C, skip, h->up[i].dc1.first, lout)) {
+        } else if (r.up[i] == UP_TWO_SOURCE) {
             // upsample only; the first conv reads [upsampled | skip] from the two tensors (no copy of the skip half)
             Tensor u2 = c.talloc(cur.t.C, lout);
             AffineSrc none{};
             if (!c.err && !c.dry) c.check(launch_upcat(c.asrc(cur), none, u2.p, B, c.Hl(lin), c.Wl(lin), c.s), "upsample");
             c.free(cur);
             c.prof_begin();
-            if (!c.conv_two(u2, skip, h->up[i].dc1.first, lout, h->up[i].dc1.gamma, h->up[i].dc1.beta, &mid) && !c.err)
-                c.err = fail(SPDM_ERR_STATE, "plan: two-source convolution refused after it was offered");
+            mid = c.conv_two(u2, skip, dc1, lout);
             c.free(u2);
             c.free(skip);
-            a = c.conv(mid, h->up[i].dc1.second, lout, /*gelu=*/true, h->up[i].dc1.gamma, h->up[i].dc1.beta);
-            c.free(mid);
         } else {
             Value cat;
             cat.t = c.talloc(cur.t.C + skip.t.C, lout);
@@ -1864,15 +1847,17 @@ static int plan_unet(Ctx& c, const float* x, bool use_cond, Tensor* feat_out) {
             c.free(cur);
             c.free(skip);
             c.prof_begin();
-            a = c.double_conv(cat, h->up[i].dc1, lout);
+            mid = c.conv(cat, dc1.first, lout, /*gelu=*/false, dc1.gamma, dc1.beta);
+            c.free(cat);
         }
+        Value a = c.conv(mid, dc1.second, lout, /*gelu=*/true, dc1.gamma, dc1.beta);
+        c.free(mid);
         Value b3 = c.double_conv(a, h->up[i].dc2, lout);
         c.prof_end();
-        const Tensor y = c.film_attention(b3, h->up[i], 3 + i, lout, use_cond, un[i], /*final_outc=*/i == 2);
+        const Tensor y = c.film_attention(b3, h->up[i], 3 + i, lout, use_cond, un[i]);
         c.tap(an[i], y);
-        Value nv;
-        nv.t = y;
-        cur = nv;
+        cur = Value{};
+        cur.t = y;
     }
     *feat_out = cur.t;
     return c.err;
@@ -1911,13 +1896,7 @@ static int plan_simple(Ctx& c, const float* x, Tensor* feat_out) {
         return y;
     };
     // ---- input_conv = DoubleConvolution(1, 16) on pad_to(x, 8) (:284,289) ----
-    Value v0;
-    v0.t = c.talloc(64, 0);
-    v0.st = c.salloc(c.HWl(0), 64, c.HWl(0) / conv_in_parts(h->Hp, h->Wp, c.Bg()), 1, /*C_norm=*/16);
-    v0.gamma = h->inc.gamma; v0.beta = h->inc.beta;
-    if (!c.err && !c.dry)
-        c.check(launch_conv_in(x, h->w_inc_first, v0.t.p, v0.st.p, B, h->cfg.horizon, h->cfg.state_dim, h->Hp, h->Wp,
-                               h->lh, h->lw, h->d_step, h->d_t, h->d_timesteps, h->n_steps, c.adv, c.s, c.Bg()), "conv_in");
+    Value v0 = c.conv_in(x, /*C_norm=*/16);
     Value r0 = c.conv(v0, h->inc.second, 0, /*gelu=*/true, h->inc.gamma, h->inc.beta);
     c.free(v0);
     Tensor x1 = c.talloc(64, 0);
@@ -1956,14 +1935,29 @@ static int plan_simple(Ctx& c, const float* x, Tensor* feat_out) {
     return c.err;
 }
 
-static int plan_net(Ctx& c, const float* x, bool use_cond, Tensor* feat_out) {
-    return c.h->simple ? plan_simple(c, x, feat_out) : plan_unet(c, x, use_cond, feat_out);
+// sized: the sizing pass's combination of resampling routes (Ctx::choose_routes); null in a real run
+static int plan_net(Ctx& c, const float* x, bool use_cond, Tensor* feat_out, const PlanRoutes* sized = nullptr) {
+    return c.h->simple ? plan_simple(c, x, feat_out) : plan_unet(c, x, use_cond, feat_out, sized);
 }
 
-static int plan_forward(spdm_handle* h, int B, bool use_cond, hipStream_t s, Tensor* feat_out) {
-    Ctx c{h, B, s, h->arena.dry};
-    h->arena.reset();
-    return plan_net(c, h->d_x, use_cond, feat_out);
+// The sizing pass: dry runs of the plan at max_batch for every combination of routes of the three pools and the three up blocks
+// (3^6 walks: which one a real run takes depends on its batch); arena.peak ends as the largest of them (arena.dry must be set
+// by the caller)
+static int dry_plan_all(spdm_handle* h) {
+    size_t peak = 0;
+    for (int k = 0; k < (h->simple ? 1 : 729); ++k) {         // (plan_simple materialises every resampling op)
+        PlanRoutes want{};
+        for (int op = 0, digits = k; op < 6; ++op, digits /= 3) (op < 3 ? want.pool[op] : want.up[op - 3]) = digits % 3;
+        Ctx c{h, h->cfg.max_batch, nullptr, h->arena.dry};
+        h->arena.peak = 0;
+        h->arena.reset();
+        Tensor feat;
+        const int rc = plan_net(c, h->d_x, /*use_cond=*/true, &feat, &want);
+        if (rc != SPDM_OK) return rc;
+        peak = std::max(peak, h->arena.peak);
+    }
+    h->arena.peak = peak;
+    return SPDM_OK;
 }
 
 // time-embedding tables: Linear(SiLU(pos_encoding(t))) for every t (models/Unet_FiLmLayer.py:136-142)
@@ -2055,7 +2049,7 @@ static int unet_forward(spdm_handle* h, int32_t B, const float* d_x, const int32
     h->arena.reset();
     Tensor feat;
     SPDM_TRY(plan_net(c, h->d_x, d_cond != nullptr, &feat));
-    StepArgs a = step_args(h, B, feat, c.eps_ready);
+    StepArgs a = step_args(h, B, feat, c.routes.sa[5].outc);
     a.eps_out = d_eps;
     a.ptrs_dev = nullptr;
     HIP_TRY(launch_out_step(a, s));
@@ -2119,13 +2113,13 @@ static int enqueue_step(spdm_handle* h, int i, hipStream_t s) {
     h->arena.reset();
     Tensor feat;
     SPDM_TRY(plan_net(c, h->d_x, h->have_film, &feat));
-    StepArgs a = step_args(h, h->sB, feat, c.eps_ready);
+    StepArgs a = step_args(h, h->sB, feat, c.routes.sa[5].outc);
     if (h->sched_kind == SPDM_DPMPP_2M) {
         // the two-history-term update is a launch of its own: in out_step's place where sa6's epilogue has eps ready, after
         // out_step in its eps-only mode elsewhere
         SolverStepArgs v{};
         v.eps = a.eps_in;
-        if (!c.eps_ready) {
+        if (!c.routes.sa[5].outc) {
             a.eps_out = h->d_solver_eps;
             HIP_TRY(launch_out_step(a, s));
             v.eps = h->d_solver_eps;
@@ -4078,6 +4072,16 @@ extern "C" int spdm_debug_whole_tiles(void) { return g_op_gemm_whole; }
 // ... how many launches of this process (plan or spdm_op_gemm; a captured step counts once) read the upsample through conv_wide's loader
 extern "C" int spdm_debug_fused_upsample_launches(void) { return gemm_wide_upcat_launches(); }
 extern "C" int spdm_debug_pooled_epilogue_launches(void) { return g_pooled_epilogue_launches; }
+extern "C" int spdm_debug_plan_routes(const spdm_handle* h, int32_t B, int32_t* out, int32_t cap) {
+    static_assert(sizeof(PlanRoutes) == SPDM_PLAN_ROUTES_INTS * sizeof(int32_t), "PlanRoutes is the query's layout");
+    spdm_handle* hm = const_cast<spdm_handle*>(h);       // (Ctx holds a mutable handle; choose_routes is const)
+    SPDM_TRY(check_ready(hm, B));
+    if (!out || cap < SPDM_PLAN_ROUTES_INTS) return fail(SPDM_ERR_INVALID, "out must hold %d values", SPDM_PLAN_ROUTES_INTS);
+    const Ctx c{hm, B, nullptr, false};
+    const PlanRoutes r = h->simple ? PlanRoutes{} : c.choose_routes();
+    memcpy(out, &r, sizeof(r));
+    return SPDM_OK;
+}
 
 // op-level test hook: one launch_gemm exactly as the plan builds it, on the caller's tensors (include/spdm.h)
 extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {

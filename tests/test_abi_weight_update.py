@@ -37,4 +37,5 @@ def test_null_handle_is_invalid(lib):
     assert lib.spdm_update_weights(None, None, 0, None) == -1
     d = ctypes.c_uint64(0)
     assert lib.spdm_debug_weight_digest(None, ctypes.byref(d)) == -1
+    assert lib.spdm_debug_plan_routes(None, 1, (ctypes.c_int32 * 42)(), 42) == _lib.SPDM_ERR_INVALID
     assert b"null" in lib.spdm_last_error()

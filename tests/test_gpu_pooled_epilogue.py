@@ -9,7 +9,8 @@ The consumer's staged input equals pool_kernel's output bit for bit, so every it
 with the route on (SPDM_TUNE23=7, the default), off (0) and with each single pool (1, 2, 4).  The knob is read once per process:
 one child process per knob value runs every scenario below and the tests compare what they saved.
 spdm_debug_pooled_epilogue_launches() counts the producer launches that wrote a pooled map; the expected count per U-Net
-evaluation is worked out from the launch geometry (spdm_debug_geometry), not assumed.
+evaluation is worked out from the launch geometry (spdm_debug_geometry), not assumed, and the pools the planner reports as
+written by their producer (spdm_debug_plan_routes) must be exactly those.
 
 random_state_dict's GroupNorm gains are all positive, which would leave the min branch of pool 1 idle: the state dict here gets
 inc.norm.weight with mixed signs, an exact zero and a gain small enough to underflow against rstd.
@@ -87,7 +88,8 @@ for name, (H, B, kw, env) in scenarios.items():
     torch.cuda.synchronize()
     per_eval = int(count()) - c0
     _, hist = eng.sample(cond, x_T, noise=noise, history=True)
-    out[name] = {"hist": hist.cpu(), "eps": eps.cpu(), "per_eval": per_eval, "graphs": eng.graph_captures}
+    pools = sum(1 << i for i, route in enumerate(eng.plan_routes(B)["pool"]) if route == 2)     # (2: by the producer's epilogue)
+    out[name] = {"hist": hist.cpu(), "eps": eps.cpu(), "per_eval": per_eval, "graphs": eng.graph_captures, "pools": pools}
     eng.close()
 torch.save(out, sys.argv[2])
 """
@@ -99,9 +101,9 @@ def _geometry(M, N, K, HW, W, taps, sw=0):
     return {"skinny": out[5] & 1, "reg": out[5] >> 1}
 
 
-def expected_pools(H, B, attention=True, no_reg64=False):
-    """Bit mask of the pools whose producer the plan's rule lets write the pooled map (csrc/spdm_api.hip pool_by_conv_reg,
-    pool_by_producer; csrc/sa_tail.hip sa_tail_pools), from the launch geometry."""
+def expected_pools(H, B, attention=True, no_reg64=False, no_fused_src=False):
+    """Bit mask of the pools whose producer the plan's rule lets write the pooled map (csrc/spdm_api.hip Ctx::choose_routes;
+    csrc/sa_tail.hip sa_tail_pools), from the launch geometry."""
     Hp, Wp = (H + 7) // 8 * 8, 8
     hw = [Hp * Wp >> (2 * i) for i in range(4)]
     w = [Wp >> i for i in range(4)]
@@ -110,17 +112,20 @@ def expected_pools(H, B, attention=True, no_reg64=False):
     if not no_reg64 and _geometry(B * hw[0], 64, 64, hw[0], w[0], 9)["reg"] and _geometry(B * hw[1], 64, 64, hw[1], w[1], 9)["reg"] \
             and hw[0] // 64 <= 8:
         mask |= 1
-    # pools 2, 3: sa_tail's blocks of 8192 / C rows hold whole windows; the consumer is not the small-grid kernel
+    # pools 2, 3: sa_tail's blocks of 8192 / C rows hold whole windows; the consumer is not the small-grid kernel (which reads the
+    # MaxPool through itself unless SPDM_NO_FUSED_SRC forbids it)
     for bit, lvl, C in ((2, 1, 128), (4, 2, 256)):
         whole = hw[lvl] % (2 * w[lvl]) == 0 and (8192 // C) % (2 * w[lvl]) == 0
-        if attention and whole and not _geometry(B * hw[lvl + 1], C, C, hw[lvl + 1], w[lvl + 1], 9 if w[lvl + 1] > 1 else 3)["skinny"]:
+        skinny = _geometry(B * hw[lvl + 1], C, C, hw[lvl + 1], w[lvl + 1], 9 if w[lvl + 1] > 1 else 3)["skinny"]
+        if attention and whole and (no_fused_src or not skinny):
             mask |= bit
     return mask
 
 
 @pytest.fixture(scope="module")
 def runs(tmp_path_factory):
-    """One child per knob value, side by side: {knob: {scenario: {hist, eps, per_eval, graphs}}}."""
+    """One child per knob value, side by side: {knob: {scenario: {hist, eps, per_eval, graphs, pools}}}; pools: the mask of the
+    pools the planner itself reports as written by their producer (SpdmEngine.plan_routes)."""
     tmp = tmp_path_factory.mktemp("pooled")
     procs = {}
     for knob in KNOBS:
@@ -179,6 +184,7 @@ def test_counter_matches_the_rule(runs, name):
     for knob in KNOBS:
         if name in runs[knob]:
             assert runs[knob][name]["per_eval"] == bin(want & (7 if knob is None else knob)).count("1"), (name, knob, runs[knob][name]["per_eval"])
+            assert runs[knob][name]["pools"] == want & (7 if knob is None else knob), (name, knob, runs[knob][name]["pools"])
 
 
 @pytest.mark.parametrize("name,kw", [("debug", dict(none=True)), ("no_reg64", dict(no_reg64=True)), ("no_attention", dict(attention=False))])
@@ -190,6 +196,7 @@ def test_negative_routes_keep_pool_kernel(runs, name, kw):
     assert want == WANT[name]
     assert runs[7][name]["per_eval"] == bin(want).count("1"), (name, runs[7][name]["per_eval"])
     assert runs[0][name]["per_eval"] == 0
+    assert runs[7][name]["pools"] == want and runs[0][name]["pools"] == 0, (name, runs[7][name]["pools"], runs[0][name]["pools"])
     assert _same_bits(runs[7][name]["hist"], runs[0][name]["hist"]), name
     assert _same_bits(runs[7][name]["eps"], runs[0][name]["eps"]), name
 

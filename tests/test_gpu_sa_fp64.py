@@ -21,7 +21,8 @@ sa6 (6.0 / 5.8 / 12.5 / 12.3) and the best sa3 (0.7 / 1.0 / 1.3 / 2.5).  The rou
 (FiLM folded or evaluated in the consumers, cropped sa6 with and without outc) are held here on eps of the whole model, and per
 element, one launch at a time, by tests/test_gpu_sa_ops_fp64.py.
 
-Every case prints the kernels each block takes (`block_routes`, restating Ctx::attention's rule in spdm_api.hip) and
+Every case prints the kernels each block takes (`block_routes` / `film_routes`, restating Ctx::choose_routes' rules in
+spdm_api.hip, and asserted equal to the planner's own choice, SpdmEngine.plan_routes: `assert_plan`) and
   ROUTE <flavour> H D B <route>: max |eps - eps64| / scale, max |eps - eps_default| / scale
 Tolerances (relative to max(1, max |eps64|)): TOL64 against float64, TOL_ROUTES between routes of the split path.  They were set
 from the first measured run on the MI355X (seeded data, deterministic kernels) with at most 4 x margin over the worst figure,
@@ -100,7 +101,7 @@ def engine(H, D, B, sd, env=None, **kw):
         eng.close()
 
 
-# ---- which kernels a block takes (Ctx::attention, spdm_api.hip; sa_*_supported in sa_fused.hip / sa_tail.hip) ----------
+# ---- which kernels a block takes (Ctx::choose_routes, spdm_api.hip; sa_*_supported in sa_fused.hip / sa_tail.hip) -----
 def block_shapes(H, D):
     Hp, Wp = -(-H // 8) * 8, -(-D // 8) * 8
     hw = lambda lvl: (Hp >> lvl) * (Wp >> lvl)
@@ -131,17 +132,57 @@ def block_routes(H, D, B, env, exact=False, debug=False):
             tail = C in (128, 256) and "SPDM_NO_SA_TAIL" not in env
             tiles = -(-B * L // (8192 // C))
             core = "attn_valu" if L < 32 or "SPDM_ATTN_VALU" in env else "attn_mfma"
-            if tail and sa_head_supported(C, L) and ("SPDM_SA_HEAD" in env or tiles >= 2048):
+            if tail and sa_head_supported(C, L) and "SPDM_NO_SA_HEAD" not in env and ("SPDM_SA_HEAD" in env or tiles >= 2048):
                 out[name] = "sa_head+sa_tail"
             else:
                 out[name] = ("sa_qkv" if tail else "gemm") + "+" + core + "+" + ("sa_tail" if tail else "gemm x3")
     return out
 
 
-def film_route(B, env, debug=False, exact=False):
-    if debug or exact or "SPDM_NO_FILM_FOLD" in env:
-        return "film_apply"
-    return "film_local" if B <= 4 or "SPDM_FILM_LOCAL" in env else "film_coef"
+def sa_tail_film_local(C, L):
+    """sa_tail.hip: one [A | B] row of 2 C floats per sample a tile of 8192 / C rows can touch, within 24 KB of LDS."""
+    return C in (128, 256) and L >= 1 and ((8192 // C + L - 2) // L + 1) * 2 * C * 4 <= 24 * 1024
+
+
+FILM = ("film_apply", "film_coef", "film_local")
+
+
+def film_routes(H, D, B, env, debug=False, exact=False):
+    """The FiLM tail in front of each block: applied by film_apply, folded into the block's loads as film_coef's coefficients
+    (the kernels that read the block input themselves: sa_fused64 up to 256 tokens, sa_qkv / sa_tail), or evaluated inside those
+    kernels (batch <= 4, or SPDM_FILM_LOCAL, where their LDS holds the coefficient rows)."""
+    out = {}
+    for name, (C, L) in block_shapes(H, D).items():
+        fused = not exact and C == 64 and L <= 512 and "SPDM_NO_SA_FUSED" not in env
+        tail = not exact and C in (128, 256) and "SPDM_NO_SA_TAIL" not in env
+        fold = not (debug or exact or "SPDM_NO_FILM_FOLD" in env) and (L <= 256 if fused else tail)
+        local = fold and (B <= 4 or "SPDM_FILM_LOCAL" in env) and (fused or sa_tail_film_local(C, L))
+        out[name] = FILM[2 if local else 1 if fold else 0]
+    return out
+
+
+def route_key(route):
+    """A block_routes string as the planner reports the block (SpdmEngine.plan_routes): (fused, crop, outc, in, tail); the
+    attention core's kernel and sa_fused64's variants are the launchers' choice, not the plan's."""
+    if route.startswith("sa_crop64"):
+        return (1, 1, int(route.endswith("+outc")), 0, 0)
+    if route.startswith("sa_fused64"):
+        return (1, 0, 0, 0, 0)
+    parts = route.split("+")
+    return (0, 0, 0, {"sa_head": 2, "sa_qkv": 1}.get(parts[0], 0), int(parts[-1] == "sa_tail"))
+
+
+def assert_plan(eng, H, D, B, env, exact=False, debug=False, attention=True):
+    """The planner's own choice for this handle equals the restatements above; returns them for printing."""
+    plan = eng.plan_routes(B)
+    blocks, films = block_routes(H, D, B, env, exact, debug), film_routes(H, D, B, env, debug, exact)
+    if not attention:       # no SelfAttention blocks: film_apply finishes every tail, nothing else is launched
+        blocks, films = {name: "none" for name in blocks}, {name: "film_apply" for name in films}
+    for i, name in enumerate(blocks):
+        want = (route_key(blocks[name]), films[name])
+        got = (tuple(plan["sa"][i][k] for k in ("fused", "crop", "outc", "in", "tail")), FILM[plan["film"][i]])
+        assert got == want, (name, got, want, H, D, B, env)
+    return blocks, films
 
 
 # (name, environment, engine keywords)
@@ -202,13 +243,12 @@ def test_routes_against_float64_oracle(flavour, geom):
             got = _run(eng, H, D, B)
             if not kw.get("exact_fp32"):
                 assert eng.split_precision and eng.demoted_tensors == 0, name     # the split path really ran
+            blocks, films = assert_plan(eng, H, D, B, env, kw.get("exact_fp32", False), kw.get("debug", False))
         if base is None:
             base = got
         e64 = float((got - want).abs().max()) / scale
         ert = float((got - base).abs().max()) / scale
-        blocks = block_routes(H, D, B, env, kw.get("exact_fp32", False), kw.get("debug", False))
-        print(f"\nROUTE {flavour} {H} {D} {B} {name}: {e64:.3e} {ert:.3e} scale {scale:.2f} "
-              f"{film_route(B, env, kw.get('debug', False), kw.get('exact_fp32', False))} {blocks}")
+        print(f"\nROUTE {flavour} {H} {D} {B} {name}: {e64:.3e} {ert:.3e} scale {scale:.2f} {films} {blocks}")
         assert e64 <= TOL64, (flavour, geom, name, e64)
         if not kw.get("exact_fp32"):
             assert ert <= TOL_ROUTES, (flavour, geom, name, ert)
@@ -231,11 +271,11 @@ def test_film_coef_and_cropped_sa6_at_batch_300(flavour):
         with engine(H, D, B, sd, env, **kw) as eng:
             got = _run(eng, H, D, B)
             assert eng.demoted_tensors == 0
+            blocks, films = assert_plan(eng, H, D, B, env)
         base = got if base is None else base
         e64 = float((got[idx] - want).abs().max()) / scale
         ert = float((got - base).abs().max()) / scale
-        print(f"\nROUTE {flavour} {H} {D} {B} {name}: {e64:.3e} {ert:.3e} scale {scale:.2f} {film_route(B, env)} "
-              f"{block_routes(H, D, B, env)}")
+        print(f"\nROUTE {flavour} {H} {D} {B} {name}: {e64:.3e} {ert:.3e} scale {scale:.2f} {films} {blocks}")
         assert e64 <= TOL64, (flavour, name, e64)
         assert ert <= TOL_ROUTES, (flavour, name, ert)
         if name in DIFFERENT_KERNELS:
@@ -260,14 +300,63 @@ def test_sa_head_chosen_by_the_plan_at_batch_2048():
     with engine(H, D, B, sd) as eng:
         got = _run(eng, H, D, B)
         assert eng.demoted_tensors == 0
+        assert_plan(eng, H, D, B, {})
     with engine(H, D, B, sd, {"SPDM_NO_SA_HEAD": "1"}) as eng:
         three = _run(eng, H, D, B)
+        assert_plan(eng, H, D, B, {"SPDM_NO_SA_HEAD": "1"})
     e64 = float((got[idx] - want).abs().max()) / scale
     ert = float((got - three).abs().max()) / scale
     print(f"\nROUTE {flavour} {H} {D} {B} plan: {e64:.3e} {ert:.3e} scale {scale:.2f} film_coef {routes}")
     assert ert > 0.0                    # the two paths are different kernels: identical bits would mean the rule did not switch
     assert e64 <= TOL64, e64
     assert ert <= TOL_ROUTES, ert
+
+
+# ---- the planner's choice against the restatements, on both sides of every threshold the rules have ------------------------
+# (id, H, D, B, environment, engine keywords).  H = 32, D = 3: coefficients in the consumers up to B = 4; pool 1 by its producer
+# from 256, pool 2 from 257, pool 3 from 1025 (tests/test_gpu_pooled_epilogue.py); sa_head for sa1 from 2048.  H = 16: pool 1
+# refused below conv_reg64's smallest map.  H = 64, D = 6: the two-workgroup sa_fused64 (no FiLM fold, no crop).
+PLAN_CASES = ([(f"B{B}", 32, 3, B, {}, {}) for B in (4, 5, 255, 256, 257, 1024, 1025, 2047, 2048)] +
+              [("H16", 16, 3, 2049, {}, {}), ("H64", 64, 6, 5, {}, {}),
+               ("debug", 32, 3, 1025, {}, dict(debug=True)), ("no_attention", 32, 3, 1025, {}, dict(attention=False))] +
+              [(name, 32, 3, 1025, env, kw) for name, env, kw in ROUTES if name not in ("default", "debug")] +
+              [("no_reg64", 32, 3, 1025, {"SPDM_NO_REG64": "1"}, {}), ("no_fused_src", 32, 3, 1025, {"SPDM_NO_FUSED_SRC": "1"}, {}),
+               ("no_fused_src-B5", 32, 3, 5, {"SPDM_NO_FUSED_SRC": "1"}, {})])
+
+
+@pytest.mark.parametrize("case", PLAN_CASES, ids=[c[0] for c in PLAN_CASES])
+def test_planner_choice_matches_the_restatements(case):
+    """spdm_debug_plan_routes (host arithmetic) against block_routes / film_routes here and expected_pools of
+    tests/test_gpu_pooled_epilogue.py.  The restatements have no opinion on read-through versus two-source for the up blocks:
+    there, one unet_forward must make as many launches that read the upsample through conv_wide's loader
+    (spdm_debug_fused_upsample_launches counts those, not the small-grid kernel's) as the planner reports up blocks read through
+    whose first convolution spdm_debug_geometry does not put on the small-grid kernel."""
+    from state_policy_diffusionmodel_amd import _lib
+    from state_policy_diffusionmodel_amd.weights import random_state_dict
+    from test_gpu_pooled_epilogue import _geometry, expected_pools
+    _, H, D, B, env, kw = case
+    exact, debug, attention = kw.get("exact_fp32", False), kw.get("debug", False), kw.get("attention", True)
+    count = _lib.load().spdm_debug_fused_upsample_launches
+    with engine(H, D, B, random_state_dict(CD, seed=5, attention=attention), env, **kw) as eng:
+        plan = eng.plan_routes(B)
+        blocks, films = assert_plan(eng, H, D, B, env, exact, debug, attention)
+        print(f"\nPLAN {case[0]} {H} {D} {B}: {plan['pool']} {plan['up']} {films} {blocks}")
+        assert all(r in (0, 1, 2) for r in plan["pool"] + plan["up"])           # exactly one route per resampling op
+        want = 0 if exact or debug else expected_pools(H, B, attention=attention and "SPDM_NO_SA_TAIL" not in env,
+                                                        no_reg64="SPDM_NO_REG64" in env, no_fused_src="SPDM_NO_FUSED_SRC" in env)
+        assert sum(1 << i for i, r in enumerate(plan["pool"]) if r == 2) == want, (plan["pool"], want)
+        if exact or debug or "SPDM_NO_FUSED_SRC" in env:       # nothing is read through or taken from two sources
+            assert 1 not in plan["pool"] + plan["up"] and 2 not in plan["up"], plan
+        c0 = int(count())
+        _run(eng, H, D, B)
+        through_wide = int(count()) - c0
+    Hp, Wp = -(-H // 8) * 8, -(-D // 8) * 8
+    wide = 0
+    for i, (C, lvl) in enumerate(((512, 2), (256, 1), (128, 0))):               # the first convolution of up block i + 1: C -> C
+        hw, w = (Hp >> lvl) * (Wp >> lvl), Wp >> lvl
+        if plan["up"][i] == 1 and not _geometry(B * hw, C, C, hw, w, 9)["skinny"]:
+            wide += 1
+    assert through_wide == wide, (plan["up"], through_wide, wide)
 
 
 # ---- block by block: device input tap -> float64 block -> device output tap ---------------------------------------------------
@@ -284,6 +373,7 @@ def block_taps(flavour, geom, env, kw):
         _run(eng, H, D, B)
         if not kw.get("exact_fp32"):
             assert eng.split_precision and eng.demoted_tensors == 0
+        assert_plan(eng, H, D, B, env, kw.get("exact_fp32", False), debug=True)      # (the routes the caller prints)
         return {b: (eng.debug_tensor(i).cpu(), eng.debug_tensor(o).cpu()) for b, (i, o) in BLOCKS.items()}
 
 
