@@ -3346,6 +3346,55 @@ extern "C" int spdm_profile_read(spdm_handle* h, int64_t* launches, double* tota
 }
 
 // -------------------------------------------------------------------------------------------------
+// What the entry points off the product path share (spdm_bench_gemm below, the op-level test hooks at the end of the file).
+// OpDev: the device allocations of one call, freed on every return.
+struct OpDev {
+    std::vector<void*> owned;
+    OpDev() = default;
+    OpDev(const OpDev&) = delete;
+    OpDev& operator=(const OpDev&) = delete;
+    ~OpDev() { for (void* p : owned) (void)hipFree(p); }
+    template <class T>
+    int alloc(T** p, size_t bytes) {
+        HIP_TRY(hipMalloc((void**)p, bytes));
+        owned.push_back(*p);
+        return SPDM_OK;
+    }
+    template <class T>
+    int upload(const void* host, size_t bytes, const T** dev) {      // (nothing to upload: *dev stays null)
+        T* p = nullptr;
+        if (!bytes) return SPDM_OK;
+        SPDM_TRY(alloc(&p, bytes));
+        HIP_TRY(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
+        *dev = p;
+        return SPDM_OK;
+    }
+    int upload_ints(const int32_t* host, int64_t n, const int** dev) { return upload(host, sizeof(int) * (size_t)n, dev); }
+    int nan_scratch(uint64_t floats, float** dev) {                   // an unwritten partial reads as NaN
+        if (!floats) return SPDM_OK;
+        SPDM_TRY(alloc(dev, sizeof(float) * (size_t)floats));
+        HIP_TRY(hipMemset(*dev, 0xff, sizeof(float) * (size_t)floats));
+        return SPDM_OK;
+    }
+};
+
+// OwnWeights: weights as the loader lays them out, from a torch-layout tensor of the caller's: the blob of a table of its own.
+// walk() records through R as the Loader's walkers do and returns R.err; a split copy it comes back without is outside().
+struct OwnWeights {
+    DevBlob db;
+    WeightTable wt;
+    Recorder R;
+    explicit OwnWeights(size_t blob_floats, const spdm_tensor_index* index = nullptr, int n_index = 0) : R(wt, blob_floats, index, n_index) {}
+    template <class Walk>
+    int lay_out(const float* host_blob, Walk walk) {
+        SPDM_TRY(db.upload(host_blob, R.n));
+        return R.both_passes(db.p, walk);
+    }
+    static int outside(const char* who, const char* what, const char* instead) {
+        return fail(SPDM_ERR_INVALID, "%s: %s outside the split format's range (%s)", who, what, instead);
+    }
+};
+
 // Micro-benchmark of one implicit-GEMM launch shape on synthetic data (tools/bench_gemm.py); not on
 // the product path.  Returns the average device time per launch in *ms_out (HIP events).
 extern "C" int spdm_bench_gemm(int32_t device, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t taps,
@@ -3357,21 +3406,25 @@ extern "C" int spdm_bench_gemm(int32_t device, int32_t B, int32_t H, int32_t W, 
     const bool may_splitk = split && epi == EPI_STATS && !(sw & SW_NO_SPLITK);
     const GemmGeom g = gemm_geometry(M, Cout, Cin, HW, W, taps, split, sw, may_splitk);
     float *src = nullptr, *wgt = nullptr, *wgt32 = nullptr, *dst = nullptr, *dst2 = nullptr, *gb = nullptr, *resid = nullptr, *wfrag = nullptr;
-    DevBlob db;
-    WeightTable wt;                        // wgt32, wgt and wfrag: freed with it
-    double *st_in = nullptr, *st_out = nullptr, *st_out2 = nullptr;
     const size_t nsrc = (size_t)M * Cin, nw = (size_t)taps * Cout * Cin, ndst = (size_t)M * Cout;
-    HIP_TRY(hipMalloc((void**)&src, nsrc * 4));
-    HIP_TRY(hipMalloc((void**)&dst2, ndst * 4));
-    HIP_TRY(hipMalloc((void**)&dst, ndst * 4));
-    HIP_TRY(hipMalloc((void**)&resid, ndst * 4));
-    HIP_TRY(hipMalloc((void**)&gb, (size_t)(Cin + Cout) * 2 * 4));
+    OwnWeights ow(nw);                     // wgt32, wgt and wfrag: freed with it
+    OpDev dev;                             // every other buffer: freed with it
+    struct Events {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    } ev;
+    double *st_in = nullptr, *st_out = nullptr, *st_out2 = nullptr;
+    SPDM_TRY(dev.alloc(&src, nsrc * 4));
+    SPDM_TRY(dev.alloc(&dst2, ndst * 4));
+    SPDM_TRY(dev.alloc(&dst, ndst * 4));
+    SPDM_TRY(dev.alloc(&resid, ndst * 4));
+    SPDM_TRY(dev.alloc(&gb, (size_t)(Cin + Cout) * 2 * 4));
     const bool row_ln = (taps == 1 && pro != 0);           // Linear with a LayerNorm prologue: statistics per ROW
-    HIP_TRY(hipMalloc((void**)&st_in, (size_t)(row_ln ? M : B) * 2 * 8));
-    HIP_TRY(hipMalloc((void**)&st_out, (size_t)B * g.slots * 2 * 8));
+    SPDM_TRY(dev.alloc(&st_in, (size_t)(row_ln ? M : B) * 2 * 8));
+    SPDM_TRY(dev.alloc(&st_out, (size_t)B * g.slots * 2 * 8));
     HIP_TRY(hipMemset(st_out, 0, (size_t)B * g.slots * 2 * 8));
     const GemmGeom g2 = gemm_geometry(M, Cout, Cin, HW, W, taps, 0, sw);
-    HIP_TRY(hipMalloc((void**)&st_out2, (size_t)B * g2.slots * 2 * 8));
+    SPDM_TRY(dev.alloc(&st_out2, (size_t)B * g2.slots * 2 * 8));
     HIP_TRY(hipMemset(st_out2, 0, (size_t)B * g2.slots * 2 * 8));
     {   // deterministic pseudo-random fill (values ~U(-1,1)); the weights are laid out as at load time
         std::vector<float> hsrc(nsrc), hw(nw), hgb((size_t)(Cin + Cout) * 2), hres(ndst);
@@ -3382,7 +3435,7 @@ extern "C" int spdm_bench_gemm(int32_t device, int32_t B, int32_t H, int32_t W, 
         for (auto& v : hgb) v = 1.0f + 0.1f * rnd();
         for (auto& v : hres) v = rnd();           // a non-zero residual: EPI_BIAS_RESID adds something
         // generated in [taps][Cout][Cin] order: a dense source for the copies Loader::conv makes
-        Recorder R(wt, nw);
+        Recorder& R = ow.R;
         auto walk = [&]() {
             const WeightCopy v = Recorder::dense(0, taps, Cout, Cin);
             wgt32 = R.f32(v);
@@ -3390,9 +3443,8 @@ extern "C" int spdm_bench_gemm(int32_t device, int32_t B, int32_t H, int32_t W, 
             wfrag = (split && wgt && (taps == 9 || taps == 3) && Cout % 64 == 0) ? R.frag(v, taps, Cout, Cin) : nullptr;
             return R.err;
         };
-        SPDM_TRY(db.upload(hw.data(), nw));
-        SPDM_TRY(R.both_passes(db.p, walk));
-        if (!wgt) return fail(SPDM_ERR_INVALID, "bench_gemm: weights outside the split format's range");
+        SPDM_TRY(ow.lay_out(hw.data(), walk));
+        if (!wgt) return OwnWeights::outside("bench_gemm", "weights", "run such a layer with split = 0");
         std::vector<double> hst((size_t)(row_ln ? M : B) * 2);
         for (size_t b = 0; b < hst.size() / 2; ++b) { hst[2 * b] = 0.0; hst[2 * b + 1] = (double)Cin * (row_ln ? 1 : HW) / 3.0; }
         HIP_TRY(hipMemcpy(src, hsrc.data(), nsrc * 4, hipMemcpyHostToDevice));
@@ -3401,7 +3453,7 @@ extern "C" int spdm_bench_gemm(int32_t device, int32_t B, int32_t H, int32_t W, 
         HIP_TRY(hipMemcpy(resid, hres.data(), ndst * 4, hipMemcpyHostToDevice));
     }
     float* d_part = nullptr;
-    if (may_splitk) HIP_TRY(hipMalloc((void**)&d_part, SPLITK_WORKSPACE_BYTES));
+    if (may_splitk) SPDM_TRY(dev.alloc(&d_part, SPLITK_WORKSPACE_BYTES));
     // (row_ln: like Ctx::linear, every row is its own LayerNorm "sample")
     const StatsRef st_ref{st_in, 1, row_ln ? (1 << 30) : HW, 1, row_ln ? 1 : HW, 1.0 / ((double)Cin * (row_ln ? 1 : HW))};
     GemmArgs a = gemm_args(M, 0, row_ln ? 1 : H, row_ln ? 1 : W, Cin, Cout, taps, split, sw, d_part, pro,
@@ -3410,11 +3462,11 @@ extern "C" int spdm_bench_gemm(int32_t device, int32_t B, int32_t H, int32_t W, 
     a.debug = debug;
     unsigned long long* d_stamps = nullptr;
     if (debug & DBG_STAMP) {
-        HIP_TRY(hipMalloc((void**)&d_stamps, (size_t)65536 * 8 * 8));      // conv_wide: 8 stamps per workgroup
+        SPDM_TRY(dev.alloc(&d_stamps, (size_t)65536 * 8 * 8));             // conv_wide: 8 stamps per workgroup
         HIP_TRY(hipMemset(d_stamps, 0, (size_t)65536 * 8 * 8));
         a.stamps = d_stamps;
     }
-    hipEvent_t e0, e1;
+    hipEvent_t &e0 = ev.a, &e1 = ev.b;
     HIP_TRY(hipEventCreate(&e0));
     HIP_TRY(hipEventCreate(&e1));
     hipError_t e = launch_gemm(a, nullptr);
@@ -3425,7 +3477,6 @@ extern "C" int spdm_bench_gemm(int32_t device, int32_t B, int32_t H, int32_t W, 
     if (e == hipSuccess) e = hipEventSynchronize(e1);
     float ms = 0.f;
     if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     double maxdiff = -1.0, statdiff = -1.0;
     if (e == hipSuccess && debug == 0) {      // self-check: same data through the exact fp32-MFMA configuration
         GemmArgs b2 = a;
@@ -3466,7 +3517,6 @@ extern "C" int spdm_bench_gemm(int32_t device, int32_t B, int32_t H, int32_t W, 
         if (hipMemcpy(hs.data(), d_stamps, hs.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
             if (FILE* f = fopen(getenv("SPDM_STAMP_DUMP"), "wb")) { fwrite(hs.data(), 8, hs.size(), f); fclose(f); }
         }
-        (void)hipFree(d_stamps);
     } else if (d_stamps) {      // print the stamp deltas of the traced workgroup (cycles between consecutive stamps)
         unsigned long long hs[256];
         if (hipMemcpy(hs, d_stamps, sizeof(hs), hipMemcpyDeviceToHost) == hipSuccess) {
@@ -3478,10 +3528,7 @@ extern "C" int spdm_bench_gemm(int32_t device, int32_t B, int32_t H, int32_t W, 
             }
             fflush(stdout);
         }
-        (void)hipFree(d_stamps);
     }
-    (void)hipFree(dst2); (void)hipFree(d_part);
-    (void)hipFree(src); (void)hipFree(dst); (void)hipFree(resid); (void)hipFree(gb); (void)hipFree(st_in); (void)hipFree(st_out); (void)hipFree(st_out2);
     if (e != hipSuccess) return fail(SPDM_ERR_HIP, "bench_gemm: %s", hipGetErrorString(e));
     *ms_out = ms / iters;
     return SPDM_OK;
@@ -4083,6 +4130,111 @@ extern "C" int spdm_debug_plan_routes(const spdm_handle* h, int32_t B, int32_t* 
     return SPDM_OK;
 }
 
+// op-level test hooks, the frame they share.  Each hook is: validate on the host (OpCheck), upload what the launch dereferences
+// (OpDev), ONE launch_* on the caller's tensors, op_finish.  A hook's per-op switch fills need[] / optional[] / absent[] and
+// states the op's own shape rules; the rules every op shares are the checker's, in one wording each.
+namespace {
+struct OpCheck {
+    static constexpr int MAX_BUFS = 11;                   // the largest hook's (spdm_op_frame)
+    static constexpr int64_t ANY_INDEX = (int64_t)INT32_MAX + 1;     // indices(): a limit no int32 reaches
+    const char* hook;
+    int op;
+    const int64_t* d = nullptr;                           // the hook's dim[] (dims)
+    bool ok = true;                                       // every extent so far fits 31 bits
+    uint64_t need[MAX_BUFS] = {};                         // floats of d_buf[i]
+    bool optional[MAX_BUFS] = {}, absent[MAX_BUFS] = {};  // may be null / must be null in this call
+    int nbuf = 0;                                         // buffers the op takes: those from nbuf on are absent
+    OpCheck(const char* hook_name, int op_id) : hook(hook_name), op(op_id) {}
+    __attribute__((format(printf, 2, 3))) int bad(const char* fmt, ...) const {
+        char msg[sizeof(g_err)];
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(msg, sizeof(msg), fmt, ap);
+        va_end(ap);
+        return fail(SPDM_ERR_INVALID, "%s: %s", hook, msg);
+    }
+    // element counts that must stay within 31 bits; no intermediate can overflow
+    uint64_t mul(std::initializer_list<int64_t> f) {
+        uint64_t v = 1;
+        for (int64_t x : f) {
+            v *= (uint64_t)x;              // both factors are below 2^31
+            if (v > (uint64_t)INT32_MAX) { ok = false; v = 1; }
+        }
+        return v;
+    }
+    uint64_t strided(uint64_t rows, int64_t ld, int64_t width) {      // rows of ld floats, the last one width long
+        if (rows == 0) { ok = false; return 0; }
+        const uint64_t v = mul({(int64_t)rows - 1, ld}) + (uint64_t)width;
+        if (v > (uint64_t)INT32_MAX) ok = false;
+        return v;
+    }
+    int fits() const { return ok ? SPDM_OK : bad("op %d: a tensor extent is beyond 31 bits", op); }
+    // the op is one of the hook's n_ops; every dim in [0, 2^31) -- dim[lo_index] from lo on --, and those beyond the
+    // taken_of[op] the op reads are 0
+    int dims(const int64_t* dim, int total, const int* taken_of, int n_ops, int lo = 0, int lo_index = -1) {
+        if (op < 0 || op >= n_ops) return bad("unknown op %d", op);
+        const int taken = taken_of[op];
+        d = dim;
+        for (int i = 0; i < total; ++i) {
+            const int from = i == lo_index ? lo : 0;
+            if (d[i] < from || d[i] > INT32_MAX) return bad("dim[%d] = %lld outside [%d, 2^31)", i, (long long)d[i], from);
+            if (i >= taken && d[i] != 0) return bad("op %d takes %d dims; dim[%d] must be 0", op, taken, i);
+        }
+        return SPDM_OK;
+    }
+    bool positive(std::initializer_list<int> which) const {
+        for (int i : which) if (d[i] < 1) return false;
+        return true;
+    }
+    // the extents fit; a buffer the call does not take is null, one it takes is there (unless optional) and holds need[i] floats
+    int buffers(float* const* d_buf, const uint64_t* cap, int total) const {
+        SPDM_TRY(fits());
+        for (int i = 0; i < total; ++i) {
+            if (i >= nbuf || absent[i]) {
+                if (d_buf[i]) return bad("op %d does not take d_buf[%d] here; it must be null", op, i);
+            } else if (!d_buf[i]) {
+                if (!optional[i]) return bad("op %d: d_buf[%d] is null", op, i);
+            } else if (cap[i] < need[i]) {
+                return bad("op %d: d_buf[%d] holds %llu floats, the launch needs %llu", op, i, (unsigned long long)cap[i], (unsigned long long)need[i]);
+            }
+        }
+        return SPDM_OK;
+    }
+    // a host index array (`name`: h_idx[k], h_t): `want` entries (0: not taken here), each in [0, lim); ANY_INDEX: no upper bound
+    int indices(const char* name, const int32_t* h_idx, int64_t n_idx, int64_t want, int64_t lim) const {
+        if (want == 0) return h_idx || n_idx ? bad("op %d takes no index arrays at %s here; it must be null", op, name) : SPDM_OK;
+        if (!h_idx || n_idx != want) return bad("op %d: %s must hold %lld entries", op, name, (long long)want);
+        for (int64_t i = 0; i < want; ++i)
+            if (h_idx[i] < 0 || h_idx[i] >= lim) return bad("op %d: %s[%lld] = %d outside [0, %lld)", op, name, (long long)i, h_idx[i], (long long)lim);
+        return SPDM_OK;
+    }
+    // a side buffer of doubles (d_stats_out, d_sq): `want` of them (0: not taken here)
+    int doubles(const char* name, const double* ptr, uint64_t cap, uint64_t want, bool may_be_null) const {
+        if (want == 0) return ptr || cap ? bad("op %d does not take %s here; it must be null", op, name) : SPDM_OK;
+        if (!ptr) return may_be_null ? SPDM_OK : bad("op %d: %s is null", op, name);
+        if (cap < want) return bad("op %d: %s holds %llu doubles, the launch needs %llu", op, name, (unsigned long long)cap, (unsigned long long)want);
+        return SPDM_OK;
+    }
+};
+
+// launch_wgrad's partial slabs under a budget of floats: chunks of M, floats of all slabs (0: they exceed the budget), rows per chunk
+struct WgradSlabs { int nch; uint64_t slab; int wrows; };
+WgradSlabs wgrad_slabs(long long M, int taps, int Co, int Ci, size_t budget) {
+    const int nch = wgrad_chunks(M, taps, Co, Ci, budget);
+    const uint64_t slab = (uint64_t)nch * taps * Co * Ci;
+    if (nch < 1 || slab > budget) return {nch, 0, 0};
+    return {nch, slab, (int)(((M + nch - 1) / nch + 3) / 4 * 4)};
+}
+
+// the hooks' tail: drain the device, then the launch's error with the device's state, or the device's own
+int op_finish(const char* hook, int op, hipError_t el) {
+    const hipError_t es = hipDeviceSynchronize();
+    if (el != hipSuccess) return fail(SPDM_ERR_HIP, "%s: op %d: launch failed: %s; device: %s", hook, op, hipGetErrorString(el), hipGetErrorString(es));
+    if (es != hipSuccess) return fail(SPDM_ERR_HIP, "%s: op %d: %s", hook, op, hipGetErrorString(es));
+    return SPDM_OK;
+}
+}  // namespace
+
 // op-level test hook: one launch_gemm exactly as the plan builds it, on the caller's tensors (include/spdm.h)
 extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {
     g_op_gemm_whole = -1;
@@ -4117,10 +4269,8 @@ extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {
     const int src_rows = q.pro == PRO_POOL ? 4 * HW : q.pro == PRO_UPCAT ? HW / 4 : HW;      // rows per sample of src
     if (q.pro == PRO_UPCAT && ((q.H & 1) || (q.W & 1))) return fail(SPDM_ERR_INVALID, "op_gemm: upsample read-through needs an even map");
     const int split = q.split ? 1 : 0;
-    // the weights as the loader lays them out: the caller's torch-layout tensor is the blob of a table of its own
-    DevBlob db;
-    WeightTable wt;
-    Recorder R(wt, (size_t)q.N * q.K * (q.taps == 1 ? 1 : 9));
+    OwnWeights ow((size_t)q.N * q.K * (q.taps == 1 ? 1 : 9));
+    Recorder& R = ow.R;
     float *dw = nullptr, *dwf = nullptr;
     auto walk = [&]() {                    // Loader::linear / Loader::conv (Cout % 64 == 0 here: a fragment-order copy)
         const WeightCopy v = q.taps == 1 ? Recorder::dense(0, 1, q.N, q.K) : Recorder::conv_taps(0, q.N, q.K, q.taps);
@@ -4128,9 +4278,8 @@ extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {
         dwf = (split && dw && q.taps != 1) ? R.frag(v, q.taps, q.N, q.K) : nullptr;
         return R.err;
     };
-    SPDM_TRY(db.upload(q.h_weight, R.n));
-    SPDM_TRY(R.both_passes(db.p, walk));
-    if (!dw) return fail(SPDM_ERR_INVALID, "op_gemm: weights outside the split format's range (the loader keeps such a layer on the exact path)");
+    SPDM_TRY(ow.lay_out(q.h_weight, walk));
+    if (!dw) return OwnWeights::outside("op_gemm", "weights", "the loader keeps such a layer on the exact path");
     const unsigned sw = switches_from_env();
     // as the plan: a split-precision convolution may split K unless switched off (the handle then holds no partial buffer)
     const bool may_partial = split && q.taps != 1 && q.epi == EPI_STATS && !(sw & SW_NO_SPLITK);
@@ -4142,7 +4291,7 @@ extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {
     if (g.ksplit > 1 && (size_t)g.ksplit * M * q.N * sizeof(float) > SPLITK_WORKSPACE_BYTES)
         return fail(SPDM_ERR_INVALID, "op_gemm: split-K slabs exceed the workspace");
     float* dp = nullptr;                   // (freed with the table)
-    if (may_partial) SPDM_TRY(wt.alloc((void**)&dp, g.ksplit > 1 ? (size_t)g.ksplit * M * q.N * sizeof(float) : 0));
+    if (may_partial) SPDM_TRY(ow.wt.alloc((void**)&dp, g.ksplit > 1 ? (size_t)g.ksplit * M * q.N * sizeof(float) : 0));
     // the caller's tensors as the plan's sources, pending GroupNorms from the raw partials; then the plan's own builder
     auto ref = [](const double* st, int slots, int m_tile, int n_tiles, int rows, int cnorm) {
         return StatsRef{st, slots, m_tile, n_tiles, rows, 1.0 / ((double)cnorm * rows)};
@@ -4169,14 +4318,11 @@ extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {
     if (q.epi == EPI_STATS) HIP_TRY(hipMemset(q.d_stats, 0xff, (size_t)q.B * g.slots * 2 * sizeof(double)));
     if (q.d_row_stats) HIP_TRY(hipMemset(q.d_row_stats, 0xff, (size_t)M * g.n_tiles * 2 * sizeof(double)));
     const hipError_t el = launch_gemm(a, nullptr);
-    // (the split-K main kernel may have been launched before the combine reported an error: always drain the device first)
-    const hipError_t es = hipDeviceSynchronize();
-    if (el != hipSuccess)
-        return fail(el == hipErrorInvalidValue && r.kernel < 0 ? SPDM_ERR_INVALID : SPDM_ERR_HIP,
-                    "op_gemm: launch_gemm failed (%s) %s; device: %s", hipGetErrorString(el),
-                    r.kernel < 0 ? "before any kernel was dispatched (a host-side shape contract)" : "after a kernel was dispatched",
-                    hipGetErrorString(es));
-    if (es != hipSuccess) return fail(SPDM_ERR_HIP, "op_gemm: %s", hipGetErrorString(es));
+    if (el == hipErrorInvalidValue && r.kernel < 0)
+        return fail(SPDM_ERR_INVALID, "op_gemm: launch_gemm failed (%s) before any kernel was dispatched (a host-side shape contract); device: %s",
+                    hipGetErrorString(el), hipGetErrorString(hipDeviceSynchronize()));
+    // (the split-K main kernel may have been launched before the combine reported an error: the tail drains the device first)
+    SPDM_TRY(op_finish("op_gemm", 0, el));                // (its one op)
     g_op_gemm_whole = (r.kernel == ROUTE_WIDE) ? r.whole : 0;
     q.out[0] = r.kernel; q.out[1] = r.variant; q.out[2] = r.m_tile; q.out[3] = r.n_tile; q.out[4] = g.ksplit;
     q.out[5] = two ? 1 : 0; q.out[6] = fused ? 1 : 0; q.out[7] = g.slots; q.out[8] = g.st_m_tile; q.out[9] = g.st_n_tiles;
@@ -4185,103 +4331,67 @@ extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {
 
 // op-level test hook: one launch_* of the training pass on the caller's tensors (include/spdm.h).  Validate, upload the integer
 // arrays, launch, synchronise.
-namespace {
-struct OpTrainExtent {                     // element counts that must stay within 31 bits; no intermediate can overflow
-    bool ok = true;
-    uint64_t mul(std::initializer_list<int64_t> f) {
-        uint64_t v = 1;
-        for (int64_t x : f) {
-            v *= (uint64_t)x;              // both factors are below 2^31
-            if (v > (uint64_t)INT32_MAX) { ok = false; v = 1; }
-        }
-        return v;
-    }
-    uint64_t strided(uint64_t rows, int64_t ld, int64_t width) {      // rows of ld floats, the last one width long
-        if (rows == 0) { ok = false; return 0; }
-        const uint64_t v = mul({(int64_t)rows - 1, ld}) + (uint64_t)width;
-        if (v > (uint64_t)INT32_MAX) ok = false;
-        return v;
-    }
-};
-struct OpTrainDev {                        // the hook's own device allocations
-    void* p[3] = {nullptr, nullptr, nullptr};
-    ~OpTrainDev() { for (void* q : p) if (q) (void)hipFree(q); }
-};
-}  // namespace
-
 extern "C" int spdm_op_train(spdm_op_train_args* p) {
     if (!p) return fail(SPDM_ERR_INVALID, "op_train: null argument");
     spdm_op_train_args& q = *p;
     for (int i = 0; i < 4; ++i) q.info[i] = -1;
-    if (q.op < 0 || q.op >= SPDM_OPT_COUNT) return fail(SPDM_ERR_INVALID, "op_train: unknown op %d", q.op);
+    OpCheck E("op_train", q.op);
     static const int n_dims[SPDM_OPT_COUNT] = {9, 8, 3, 3, 4, 5, 7, 4, 5, 4, 2, 2, 1, 4, 4, 5, 6, 3};
-    static const int n_idxs[SPDM_OPT_COUNT] = {0, 2, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0};
     const int64_t* d = q.dim;
-    for (int i = 0; i < SPDM_OP_TRAIN_DIMS; ++i) {
-        if (d[i] < 0 || d[i] > INT32_MAX) return fail(SPDM_ERR_INVALID, "op_train: dim[%d] = %lld outside [0, 2^31)", i, (long long)d[i]);
-        if (i >= n_dims[q.op] && d[i] != 0) return fail(SPDM_ERR_INVALID, "op_train: op %d takes %d dims; dim[%d] must be 0", q.op, n_dims[q.op], i);
-    }
-    auto positive = [&](std::initializer_list<int> which) {
-        for (int i : which) if (d[i] < 1) return false;
-        return true;
-    };
+    SPDM_TRY(E.dims(d, SPDM_OP_TRAIN_DIMS, n_dims, SPDM_OPT_COUNT));
     auto pow2_le512 = [](int64_t C) { return C >= 1 && C <= 512 && (C & (C - 1)) == 0; };
-#define OPT_BAD(...) return fail(SPDM_ERR_INVALID, "op_train: " __VA_ARGS__)
-    OpTrainExtent E;
-    uint64_t need[SPDM_OP_TRAIN_BUFS] = {};
-    bool optional[SPDM_OP_TRAIN_BUFS] = {};
-    int nbuf = 0;
-    int64_t idx_n[SPDM_OP_TRAIN_IDX] = {0, 0}, idx_lim[SPDM_OP_TRAIN_IDX] = {0, 0};
-    uint64_t M = 0, slab = 0;
-    int nch = 0, wrows = 0;
+    auto& need = E.need;
+    auto& optional = E.optional;
+    int& nbuf = E.nbuf;
+    int64_t idx_n[SPDM_OP_TRAIN_IDX] = {0, 0}, idx_lim[SPDM_OP_TRAIN_IDX] = {0, 0};    // entries of h_idx[k] (0: not taken), each below idx_lim[k]
+    uint64_t M = 0;
+    WgradSlabs ws{0, 0, 0};
     switch (q.op) {
         case SPDM_OPT_WGRAD:
         case SPDM_OPT_WGRAD_MAPPED: {
             const bool mapped = q.op == SPDM_OPT_WGRAD_MAPPED;
-            if (!positive({0, 1, 2, 3, 4, 5})) OPT_BAD("wgrad: B, H, W, taps, Co, Ci must be positive");
+            if (!E.positive({0, 1, 2, 3, 4, 5})) return E.bad("wgrad: B, H, W, taps, Co, Ci must be positive");
             const int64_t taps = d[3], Co = d[4], Ci = d[5];
-            if (!(taps == 9 || taps == 3 || (taps == 1 && !mapped))) OPT_BAD("wgrad: taps %lld", (long long)taps);
-            if (taps == 3 && d[2] != 1) OPT_BAD("wgrad: 3-tap layers need W == 1");
-            if (taps == 1 && (d[1] != 1 || d[2] != 1)) OPT_BAD("wgrad: a Linear layer has H == W == 1 (B = rows)");
+            if (!(taps == 9 || taps == 3 || (taps == 1 && !mapped))) return E.bad("wgrad: taps %lld", (long long)taps);
+            if (taps == 3 && d[2] != 1) return E.bad("wgrad: 3-tap layers need W == 1");
+            if (taps == 1 && (d[1] != 1 || d[2] != 1)) return E.bad("wgrad: a Linear layer has H == W == 1 (B = rows)");
             M = E.mul({d[0], d[1], d[2]});
             int64_t ldy = Co, ldx = Ci;
             uint64_t ndst;
             if (mapped) {
-                if (!positive({6, 7}) || d[6] > Co || d[7] > Ci) OPT_BAD("wgrad_mapped: need 1 <= no <= Co and 1 <= ni <= Ci");
+                if (!E.positive({6, 7}) || d[6] > Co || d[7] > Ci) return E.bad("wgrad_mapped: need 1 <= no <= Co and 1 <= ni <= Ci");
                 ndst = E.mul({d[6], d[7], 9});
                 idx_n[0] = d[6]; idx_lim[0] = Co; idx_n[1] = d[7]; idx_lim[1] = Ci;
             } else {
-                if (d[6] != (taps == 1 ? 0 : 1)) OPT_BAD("wgrad: conv9 is 1 for taps 9 / 3 and 0 for taps 1");
+                if (d[6] != (taps == 1 ? 0 : 1)) return E.bad("wgrad: conv9 is 1 for taps 9 / 3 and 0 for taps 1");
                 ldy = d[7]; ldx = d[8];
-                if (ldy < Co || ldx < Ci) OPT_BAD("wgrad: ldy >= Co and ldx >= Ci required");
+                if (ldy < Co || ldx < Ci) return E.bad("wgrad: ldy >= Co and ldx >= Ci required");
                 ndst = E.mul({Co, Ci, d[6] ? 9 : 1});
             }
             need[0] = E.strided(M, ldy, Co); need[1] = E.strided(M, ldx, Ci); need[2] = ndst; nbuf = 3;
-            const uint64_t per = E.mul({taps, Co, Ci});
+            (void)E.mul({taps, Co, Ci});
             if (!E.ok) break;
-            nch = wgrad_chunks((long long)M, (int)taps, (int)Co, (int)Ci, TrainPass::WGRAD_BUDGET);
-            slab = (uint64_t)nch * per;
-            if (nch < 1 || slab > TrainPass::WGRAD_BUDGET) OPT_BAD("wgrad: the partial slabs exceed the budget");
-            wrows = (int)((((long long)M + nch - 1) / nch + 3) / 4 * 4);
+            ws = wgrad_slabs((long long)M, (int)taps, (int)Co, (int)Ci, TrainPass::WGRAD_BUDGET);
+            if (!ws.slab) return E.bad("wgrad: the partial slabs exceed the budget");
             break;
         }
         case SPDM_OPT_COLSUM:
-            if (!positive({0, 1, 2}) || d[2] < d[1]) OPT_BAD("colsum: M, C positive and ld >= C required");
+            if (!E.positive({0, 1, 2}) || d[2] < d[1]) return E.bad("colsum: M, C positive and ld >= C required");
             need[0] = E.strided((uint64_t)d[0], d[2], d[1]); need[1] = (uint64_t)d[1]; nbuf = 2;
             break;
         case SPDM_OPT_GN_STATS:
-            if (!positive({0, 1}) || d[2] > d[1]) OPT_BAD("gn_stats: B, n positive and 0 <= cnt <= n required");
+            if (!E.positive({0, 1}) || d[2] > d[1]) return E.bad("gn_stats: B, n positive and 0 <= cnt <= n required");
             need[0] = E.mul({d[0], d[1]}); need[1] = need[2] = (uint64_t)d[0]; nbuf = 3;
             break;
         case SPDM_OPT_GN_BWD:
         case SPDM_OPT_GN_BWD_MAPPED: {
-            if (!positive({0, 1, 2}) || d[3] > 1) OPT_BAD("gn_bwd: B, HW, C positive and gelu 0 / 1 required");
+            if (!E.positive({0, 1, 2}) || d[3] > 1) return E.bad("gn_bwd: B, HW, C positive and gelu 0 / 1 required");
             const int64_t C = d[2];
             if (q.op == SPDM_OPT_GN_BWD) {
-                if (!pow2_le512(C)) OPT_BAD("gn_bwd: C must be a power of two <= 512 (got %lld)", (long long)C);
+                if (!pow2_le512(C)) return E.bad("gn_bwd: C must be a power of two <= 512 (got %lld)", (long long)C);
             } else {
-                if (C % 64 != 0 || C > 512) OPT_BAD("gn_bwd_mapped: C must be a multiple of 64 <= 512 (got %lld)", (long long)C);
-                if (d[4] < 1 || d[4] > C) OPT_BAD("gn_bwd_mapped: need 1 <= nreal <= C");
+                if (C % 64 != 0 || C > 512) return E.bad("gn_bwd_mapped: C must be a multiple of 64 <= 512 (got %lld)", (long long)C);
+                if (d[4] < 1 || d[4] > C) return E.bad("gn_bwd_mapped: need 1 <= nreal <= C");
                 idx_n[0] = d[4]; idx_lim[0] = C;
             }
             const uint64_t n = E.mul({d[0], d[1], C});
@@ -4290,11 +4400,11 @@ extern "C" int spdm_op_train(spdm_op_train_args* p) {
             break;
         }
         case SPDM_OPT_FILM_BWD: {
-            if (!positive({0, 1, 2, 3, 4})) OPT_BAD("film_bwd: B, HW, C, t_count, T must be positive");
+            if (!E.positive({0, 1, 2, 3, 4})) return E.bad("film_bwd: B, HW, C, t_count, T must be positive");
             const int64_t B = d[0], C = d[2];
-            if (!pow2_le512(C)) OPT_BAD("film_bwd: C must be a power of two <= 512 (got %lld)", (long long)C);
-            if (d[3] != 1 && d[3] != B) OPT_BAD("film_bwd: t_count must be 1 or B");
-            if ((q.d_buf[2] == nullptr) != (q.d_buf[6] == nullptr)) OPT_BAD("film_bwd: film and dfilm go together");
+            if (!pow2_le512(C)) return E.bad("film_bwd: C must be a power of two <= 512 (got %lld)", (long long)C);
+            if (d[3] != 1 && d[3] != B) return E.bad("film_bwd: t_count must be 1 or B");
+            if ((q.d_buf[2] == nullptr) != (q.d_buf[6] == nullptr)) return E.bad("film_bwd: film and dfilm go together");
             const uint64_t n = E.mul({B, d[1], C});
             need[0] = n; need[1] = E.mul({d[4], C}); need[2] = E.mul({B, 2, C}); optional[2] = true; need[3] = need[4] = n;
             need[5] = E.mul({B, C}); need[6] = need[2]; optional[6] = true; nbuf = 7;
@@ -4302,28 +4412,28 @@ extern "C" int spdm_op_train(spdm_op_train_args* p) {
             break;
         }
         case SPDM_OPT_MSE:
-            if (!positive({0, 1, 2, 3, 4}) || d[5] + d[1] > d[3] || d[6] + d[2] > d[4])
-                OPT_BAD("mse: B, H0, D, Hp, Wp positive, lh + H0 <= Hp and lw + D <= Wp required");
+            if (!E.positive({0, 1, 2, 3, 4}) || d[5] + d[1] > d[3] || d[6] + d[2] > d[4])
+                return E.bad("mse: B, H0, D, Hp, Wp positive, lh + H0 <= Hp and lw + D <= Wp required");
             need[0] = need[3] = E.mul({d[0], d[3], d[4]}); need[1] = need[4] = E.mul({d[0], d[1], d[2]}); need[2] = 1;
             optional[4] = true; nbuf = 5;
             break;
         case SPDM_OPT_POOL_BWD:
-            if (!positive({0, 1, 2, 3}) || (d[1] & 1) || (d[2] & 1)) OPT_BAD("pool_bwd: B, H, W, C positive and H, W even required");
+            if (!E.positive({0, 1, 2, 3}) || (d[1] & 1) || (d[2] & 1)) return E.bad("pool_bwd: B, H, W, C positive and H, W even required");
             need[0] = need[2] = E.mul({d[0], d[1], d[2], d[3]}); need[1] = E.mul({d[0], d[1] / 2, d[2] / 2, d[3]}); nbuf = 3;
             break;
         case SPDM_OPT_UP_BWD:
-            if (!positive({0, 1, 2, 3, 4}) || d[4] < d[3]) OPT_BAD("up_bwd: B, h, w, C positive and ld >= C required");
+            if (!E.positive({0, 1, 2, 3, 4}) || d[4] < d[3]) return E.bad("up_bwd: B, h, w, C positive and ld >= C required");
             need[0] = E.strided(E.mul({4, d[0], d[1], d[2]}), d[4], d[3]); need[1] = E.mul({d[0], d[1], d[2], d[3]}); nbuf = 2;
             break;
         case SPDM_OPT_MISH_BWD:
-            if (!positive({0, 1, 2, 3}) || d[2] < d[3]) OPT_BAD("mish_bwd: nblk, B, cond_dim positive and ld >= cond_dim required");
+            if (!E.positive({0, 1, 2, 3}) || d[2] < d[3]) return E.bad("mish_bwd: nblk, B, cond_dim positive and ld >= cond_dim required");
             need[0] = E.strided(E.mul({d[0], d[1]}), d[2], d[3]); need[1] = need[2] = E.mul({d[1], d[3]}); nbuf = 3;
             break;
         case SPDM_OPT_LN_FWD:
         case SPDM_OPT_LN_BWD: {
-            if (!positive({0, 1})) OPT_BAD("layernorm: rows and C must be positive");
+            if (!E.positive({0, 1})) return E.bad("layernorm: rows and C must be positive");
             const int64_t rows = d[0], C = d[1];
-            if (C != 64 && C != 128 && C != 256) OPT_BAD("layernorm: C must be 64, 128 or 256 (got %lld)", (long long)C);
+            if (C != 64 && C != 128 && C != 256) return E.bad("layernorm: C must be 64, 128 or 256 (got %lld)", (long long)C);
             const uint64_t n = E.mul({rows, C});
             if (q.op == SPDM_OPT_LN_FWD) {
                 need[0] = n; need[1] = need[2] = (uint64_t)C; need[3] = n; need[4] = need[5] = (uint64_t)rows; nbuf = 6;
@@ -4335,14 +4445,14 @@ extern "C" int spdm_op_train(spdm_op_train_args* p) {
             break;
         }
         case SPDM_OPT_GELU_BWD:
-            if (!positive({0})) OPT_BAD("gelu_bwd: n must be positive");
+            if (!E.positive({0})) return E.bad("gelu_bwd: n must be positive");
             need[0] = need[1] = need[2] = (uint64_t)d[0]; nbuf = 3;
             break;
         case SPDM_OPT_ATTN_FWD_LSE:
         case SPDM_OPT_ATTN_BWD: {
-            if (!positive({0, 1, 2, 3})) OPT_BAD("attention: B, L, C, heads must be positive");
+            if (!E.positive({0, 1, 2, 3})) return E.bad("attention: B, L, C, heads must be positive");
             if (!attn_train_supported((int)d[1], (int)d[2], (int)d[3]))
-                OPT_BAD("attention: L %lld, C %lld, heads %lld not supported (L <= 512, C / heads in {16, 32, 64}, LDS)",
+                return E.bad("attention: L %lld, C %lld, heads %lld not supported (L <= 512, C / heads in {16, 32, 64}, LDS)",
                         (long long)d[1], (long long)d[2], (long long)d[3]);
             const uint64_t nq = E.mul({d[0], d[1], 3, d[2]}), no = E.mul({d[0], d[1], d[2]}), nl = E.mul({d[0], d[3], d[1]});
             if (q.op == SPDM_OPT_ATTN_FWD_LSE) { need[0] = nq; need[1] = no; need[2] = nl; nbuf = 3; }
@@ -4350,64 +4460,35 @@ extern "C" int spdm_op_train(spdm_op_train_args* p) {
             break;
         }
         case SPDM_OPT_SIMPLE_TAIL_BWD: {
-            if (!positive({0, 1, 2, 3, 4, 5})) OPT_BAD("simple_tail_bwd: B, HW, Co, Cr, Cz, cemb_ld must be positive");
+            if (!E.positive({0, 1, 2, 3, 4, 5})) return E.bad("simple_tail_bwd: B, HW, Co, Cr, Cz, cemb_ld must be positive");
             const int64_t Co = d[2], Cr = d[3], Cz = d[4];
             if (Co % 64 != 0 || Co > 512 || Cr > Cz || Cz > Co || Cr + 32 > Co || d[5] < 32)
-                OPT_BAD("simple_tail_bwd: Co a multiple of 64 <= 512, Cr <= Cz <= Co, Cr + 32 <= Co and cemb_ld >= 32 required");
+                return E.bad("simple_tail_bwd: Co a multiple of 64 <= 512, Cr <= Cz <= Co, Cr + 32 <= Co and cemb_ld >= 32 required");
             need[0] = E.mul({d[0], d[1], Co}); need[1] = E.mul({d[0], d[1], Cz}); need[2] = E.mul({d[0], Cr});
             need[3] = E.strided((uint64_t)d[0], d[5], 32); nbuf = 4;
             break;
         }
         case SPDM_OPT_SILU_BWD:
-            if (!positive({0, 1, 2}) || d[2] < d[1]) OPT_BAD("silu_bwd: B, cond_dim positive and ld >= cond_dim required");
+            if (!E.positive({0, 1, 2}) || d[2] < d[1]) return E.bad("silu_bwd: B, cond_dim positive and ld >= cond_dim required");
             need[0] = E.strided((uint64_t)d[0], d[2], d[1]); need[1] = need[2] = E.mul({d[0], d[1]}); nbuf = 3;
             break;
     }
-    if (!E.ok) OPT_BAD("op %d: a tensor extent is beyond 31 bits", q.op);
-    for (int i = 0; i < SPDM_OP_TRAIN_BUFS; ++i) {
-        if (i >= nbuf) {
-            if (q.d_buf[i]) OPT_BAD("op %d takes %d buffers; d_buf[%d] must be null", q.op, nbuf, i);
-            continue;
-        }
-        if (!q.d_buf[i]) {
-            if (!optional[i]) OPT_BAD("op %d: d_buf[%d] is null", q.op, i);
-            continue;
-        }
-        if (q.cap[i] < need[i])
-            OPT_BAD("op %d: d_buf[%d] holds %llu floats, the launch needs %llu", q.op, i, (unsigned long long)q.cap[i], (unsigned long long)need[i]);
-    }
-    for (int k = 0; k < SPDM_OP_TRAIN_IDX; ++k) {
-        if (k >= n_idxs[q.op]) {
-            if (q.h_idx[k] || q.n_idx[k]) OPT_BAD("op %d takes %d index arrays; h_idx[%d] must be null", q.op, n_idxs[q.op], k);
-            continue;
-        }
-        if (!q.h_idx[k] || q.n_idx[k] != idx_n[k]) OPT_BAD("op %d: h_idx[%d] must hold %lld entries", q.op, k, (long long)idx_n[k]);
-        for (int64_t i = 0; i < idx_n[k]; ++i)
-            if (q.h_idx[k][i] < 0 || q.h_idx[k][i] >= idx_lim[k])
-                OPT_BAD("op %d: h_idx[%d][%lld] = %d outside [0, %lld)", q.op, k, (long long)i, q.h_idx[k][i], (long long)idx_lim[k]);
-    }
+    SPDM_TRY(E.buffers(q.d_buf, q.cap, SPDM_OP_TRAIN_BUFS));
+    static const char* const idx_name[SPDM_OP_TRAIN_IDX] = {"h_idx[0]", "h_idx[1]"};
+    for (int k = 0; k < SPDM_OP_TRAIN_IDX; ++k) SPDM_TRY(E.indices(idx_name[k], q.h_idx[k], q.n_idx[k], idx_n[k], idx_lim[k]));
     if (q.op == SPDM_OPT_GN_BWD_MAPPED) {                                   // a channel map names each storage lane once
         bool seen[512] = {};
         for (int64_t i = 0; i < idx_n[0]; ++i) {
-            if (seen[q.h_idx[0][i]]) OPT_BAD("gn_bwd_mapped: pos names lane %d twice", q.h_idx[0][i]);
+            if (seen[q.h_idx[0][i]]) return E.bad("gn_bwd_mapped: pos names lane %d twice", q.h_idx[0][i]);
             seen[q.h_idx[0][i]] = true;
         }
     }
-#undef OPT_BAD
     // ---- the device from here on ----
-    OpTrainDev dev;
+    OpDev dev;
     const int* di[SPDM_OP_TRAIN_IDX] = {nullptr, nullptr};
-    for (int k = 0; k < n_idxs[q.op]; ++k) {
-        HIP_TRY(hipMalloc(&dev.p[k], sizeof(int) * (size_t)idx_n[k]));
-        HIP_TRY(hipMemcpy(dev.p[k], q.h_idx[k], sizeof(int) * (size_t)idx_n[k], hipMemcpyHostToDevice));
-        di[k] = (const int*)dev.p[k];
-    }
+    for (int k = 0; k < SPDM_OP_TRAIN_IDX; ++k) SPDM_TRY(dev.upload_ints(q.h_idx[k], idx_n[k], &di[k]));
     float* partial = nullptr;
-    if (slab) {
-        HIP_TRY(hipMalloc(&dev.p[2], sizeof(float) * (size_t)slab));
-        HIP_TRY(hipMemset(dev.p[2], 0xff, sizeof(float) * (size_t)slab));   // an unwritten partial reads as NaN
-        partial = (float*)dev.p[2];
-    }
+    SPDM_TRY(dev.nan_scratch(ws.slab, &partial));
     float* const* b = q.d_buf;
     const int i0 = (int)d[0], i1 = (int)d[1], i2 = (int)d[2], i3 = (int)d[3], i4 = (int)d[4], i5 = (int)d[5], i6 = (int)d[6];
     hipStream_t s = nullptr;
@@ -4415,12 +4496,12 @@ extern "C" int spdm_op_train(spdm_op_train_args* p) {
     switch (q.op) {
         case SPDM_OPT_WGRAD:
             el = launch_wgrad(b[0], (int)d[7], b[1], (int)d[8], (long long)M, i1, i2, i3, i4, i5, i6, partial, TrainPass::WGRAD_BUDGET, b[2], s);
-            q.info[0] = nch; q.info[1] = wrows;
+            q.info[0] = ws.nch; q.info[1] = ws.wrows;
             break;
         case SPDM_OPT_WGRAD_MAPPED:
             el = launch_wgrad_mapped(b[0], b[1], (long long)M, i1, i2, i3, i4, i5, di[0], i6, di[1], (int)d[7], partial,
                                      TrainPass::WGRAD_BUDGET, b[2], s);
-            q.info[0] = nch; q.info[1] = wrows;
+            q.info[0] = ws.nch; q.info[1] = ws.wrows;
             break;
         case SPDM_OPT_COLSUM: el = launch_colsum(b[0], i2, (long long)d[0], i1, b[1], s); break;
         case SPDM_OPT_GN_STATS:
@@ -4446,30 +4527,26 @@ extern "C" int spdm_op_train(spdm_op_train_args* p) {
         case SPDM_OPT_SIMPLE_TAIL_BWD: el = launch_simple_tail_bwd(b[0], i0, i1, i2, i3, i4, b[1], b[2], b[3], i5, s); break;
         case SPDM_OPT_SILU_BWD: el = launch_silu_bwd(b[0], i2, b[1], i0, i1, b[2], s); break;
     }
-    const hipError_t es = hipDeviceSynchronize();
-    if (el != hipSuccess) return fail(SPDM_ERR_HIP, "op_train: op %d: launch failed: %s; device: %s", q.op, hipGetErrorString(el), hipGetErrorString(es));
-    if (es != hipSuccess) return fail(SPDM_ERR_HIP, "op_train: op %d: %s", q.op, hipGetErrorString(es));
-    return SPDM_OK;
+    return op_finish(E.hook, q.op, el);
 }
 
 // A pending GroupNorm as the op-level hooks take it (spdm_op_stream_gn, include/spdm.h) -> the StatsRef its consumer reads, checked
-// host-side: source k of op `op` of hook `hook`, B samples of HW rows, C channels (0: the op takes none there), `aff` floats of
+// host-side: source k of the checker's op, B samples of HW rows, C channels (0: the op takes none there), `aff` floats of
 // gamma / beta.  Without statistics *st is the empty reference.
-static int op_pending_gn(const char* hook, int op, int k, const spdm_op_stream_gn& g, int64_t B, int64_t C, int64_t HW, int64_t aff,
-                         StatsRef* st) {
-#define OPG_BAD(fmt, ...) return fail(SPDM_ERR_INVALID, "%s: " fmt, hook, __VA_ARGS__)
+static int op_pending_gn(const OpCheck& E, int k, const spdm_op_stream_gn& g, int64_t B, int64_t C, int64_t HW, int64_t aff, StatsRef* st) {
+    const int op = E.op;
     *st = StatsRef{nullptr, 0, 1, 1, (int)HW, 0.0};
     if (C == 0 || !g.d_stats) {
-        if (g.d_stats) OPG_BAD("op %d takes no pending GroupNorm on source %d; gn[%d] must be empty", op, k, k);
+        if (g.d_stats) return E.bad("op %d takes no pending GroupNorm on source %d; gn[%d] must be empty", op, k, k);
         if (g.stats_cap || g.slots || g.m_tile || g.n_tiles || g.cnorm || g.d_gamma || g.d_beta || g.affine_cap)
-            OPG_BAD("op %d: gn[%d] has no statistics; its other fields must be empty", op, k);
+            return E.bad("op %d: gn[%d] has no statistics; its other fields must be empty", op, k);
         return SPDM_OK;
     }
-    if (g.slots < 1 || g.m_tile < 1 || g.n_tiles < 1) OPG_BAD("op %d: gn[%d] needs slots, m_tile and n_tiles >= 1", op, k);
-    if (g.cnorm < 1 || g.cnorm > C) OPG_BAD("op %d: gn[%d].cnorm %d outside [1, %lld]", op, k, g.cnorm, (long long)C);
-    if (!g.d_gamma || !g.d_beta) OPG_BAD("op %d: gn[%d] needs gamma and beta", op, k);
+    if (g.slots < 1 || g.m_tile < 1 || g.n_tiles < 1) return E.bad("op %d: gn[%d] needs slots, m_tile and n_tiles >= 1", op, k);
+    if (g.cnorm < 1 || g.cnorm > C) return E.bad("op %d: gn[%d].cnorm %d outside [1, %lld]", op, k, g.cnorm, (long long)C);
+    if (!g.d_gamma || !g.d_beta) return E.bad("op %d: gn[%d] needs gamma and beta", op, k);
     if (g.affine_cap < (uint64_t)aff)
-        OPG_BAD("op %d: gn[%d] gamma / beta hold %llu floats, the launch needs %lld", op, k, (unsigned long long)g.affine_cap, (long long)aff);
+        return E.bad("op %d: gn[%d] gamma / beta hold %llu floats, the launch needs %lld", op, k, (unsigned long long)g.affine_cap, (long long)aff);
     // the slots sample b's consumer adds: tiles first .. last of its rows, n_tiles each (sample_mean_rstd_wave)
     const int64_t mt = g.m_tile;
     int64_t reads = ((HW + mt - 2) / mt + 1) * g.n_tiles;                  // the bound over every alignment
@@ -4478,14 +4555,13 @@ static int op_pending_gn(const char* hook, int op, int k, const spdm_op_stream_g
         for (int64_t b = 0; b < std::min<int64_t>(B, mt); ++b)
             reads = std::max<int64_t>(reads, ((b * HW + HW - 1) / mt - (b * HW) / mt + 1) * g.n_tiles);
     }
-    if (g.slots < reads) OPG_BAD("op %d: gn[%d] has %d slots per sample, the consumer reads %lld", op, k, g.slots, (long long)reads);
-    OpTrainExtent E;
-    const uint64_t cap = E.mul({B, g.slots, 2});
-    if (!E.ok) OPG_BAD("op %d: a tensor extent is beyond 31 bits", op);
-    if (g.stats_cap < cap) OPG_BAD("op %d: gn[%d] statistics hold %llu doubles, the launch needs %llu", op, k, (unsigned long long)g.stats_cap, (unsigned long long)cap);
+    if (g.slots < reads) return E.bad("op %d: gn[%d] has %d slots per sample, the consumer reads %lld", op, k, g.slots, (long long)reads);
+    OpCheck own(E.hook, op);                                               // (this extent alone: the caller reports its own)
+    const uint64_t cap = own.mul({B, g.slots, 2});
+    SPDM_TRY(own.fits());
+    if (g.stats_cap < cap) return E.bad("op %d: gn[%d] statistics hold %llu doubles, the launch needs %llu", op, k, (unsigned long long)g.stats_cap, (unsigned long long)cap);
     *st = StatsRef{g.d_stats, g.slots, g.m_tile, g.n_tiles, (int)HW, 1.0 / ((double)g.cnorm * (double)HW)};
     return SPDM_OK;
-#undef OPG_BAD
 }
 
 // op-level test hook: one launch_* of elementwise.hip (the streaming kernels of the forward / sampling path) on the caller's tensors
@@ -4494,25 +4570,15 @@ extern "C" int spdm_op_stream(spdm_op_stream_args* p) {
     if (!p) return fail(SPDM_ERR_INVALID, "op_stream: null argument");
     spdm_op_stream_args& q = *p;
     for (int i = 0; i < 4; ++i) q.info[i] = -1;
-    if (q.op < 0 || q.op >= SPDM_OPS_COUNT) return fail(SPDM_ERR_INVALID, "op_stream: unknown op %d", q.op);
+    OpCheck E("op_stream", q.op);
     static const int n_dims[SPDM_OPS_COUNT] = {11, 4, 5, 5, 5, 2, 3, 3, 1, 3, 9, 4, 14};
     const int64_t* d = q.dim;
-    for (int i = 0; i < SPDM_OP_STREAM_DIMS; ++i) {
-        const bool may_be_negative = q.op == SPDM_OPS_CONV_IN && i == 8;      // adv
-        if (d[i] < (may_be_negative ? -2 : 0) || d[i] > INT32_MAX)
-            return fail(SPDM_ERR_INVALID, "op_stream: dim[%d] = %lld outside [%d, 2^31)", i, (long long)d[i], may_be_negative ? -2 : 0);
-        if (i >= n_dims[q.op] && d[i] != 0) return fail(SPDM_ERR_INVALID, "op_stream: op %d takes %d dims; dim[%d] must be 0", q.op, n_dims[q.op], i);
-    }
-    auto positive = [&](std::initializer_list<int> which) {
-        for (int i : which) if (d[i] < 1) return false;
-        return true;
-    };
-#define OPS_BAD(...) return fail(SPDM_ERR_INVALID, "op_stream: " __VA_ARGS__)
-    OpTrainExtent E;
-    uint64_t need[SPDM_OP_STREAM_BUFS] = {};
-    bool optional[SPDM_OP_STREAM_BUFS] = {}, absent[SPDM_OP_STREAM_BUFS] = {};
-    int nbuf = 0;
-    int64_t idx_n = 0, idx_lim = 0;                 // entries of h_idx[0] (0: the op takes none); idx_lim > 0: entries below it
+    SPDM_TRY(E.dims(d, SPDM_OP_STREAM_DIMS, n_dims, SPDM_OPS_COUNT, -2, q.op == SPDM_OPS_CONV_IN ? 8 : -1));      // conv_in's adv
+    auto& need = E.need;
+    auto& optional = E.optional;
+    auto& absent = E.absent;
+    int& nbuf = E.nbuf;
+    int64_t idx_n = 0, idx_lim = 0;                 // entries of h_idx[0] (0: the op takes none), each below idx_lim
     int64_t gn_C[SPDM_OP_STREAM_GN] = {0, 0}, gn_HW[SPDM_OP_STREAM_GN] = {0, 0}, gn_aff[SPDM_OP_STREAM_GN] = {0, 0};   // gn_C == 0: not taken
     int64_t B = d[0];
     uint64_t stats_need = 0;                        // doubles of d_stats_out (0: the op writes none)
@@ -4520,15 +4586,15 @@ extern "C" int spdm_op_stream(spdm_op_stream_args* p) {
     int parts = 0, slots_out = 0, rows = 0;
     switch (q.op) {
         case SPDM_OPS_CONV_IN: {
-            if (!positive({0, 1, 2, 3, 4})) OPS_BAD("conv_in: B, H0, D, Hp, Wp must be positive");
-            if (d[5] + d[1] > d[3] || d[6] + d[2] > d[4]) OPS_BAD("conv_in: lh + H0 <= Hp and lw + D <= Wp required");
+            if (!E.positive({0, 1, 2, 3, 4})) return E.bad("conv_in: B, H0, D, Hp, Wp must be positive");
+            if (d[5] + d[1] > d[3] || d[6] + d[2] > d[4]) return E.bad("conv_in: lh + H0 <= Hp and lw + D <= Wp required");
             const uint64_t HW = E.mul({d[3], d[4]});
-            if (!E.ok || (HW + 8) * sizeof(float) > 64 * 1024) OPS_BAD("conv_in: the padded image exceeds the LDS (Hp Wp + 8 floats in 64 KiB)");
+            if (!E.ok || (HW + 8) * sizeof(float) > 64 * 1024) return E.bad("conv_in: the padded image exceeds the LDS (Hp Wp + 8 floats in 64 KiB)");
             if (d[8] == -2) {
-                if (d[9] != 0 || d[10] != 0) OPS_BAD("conv_in: adv -2 takes n_steps = step0 = 0");
+                if (d[9] != 0 || d[10] != 0) return E.bad("conv_in: adv -2 takes n_steps = step0 = 0");
             } else {
-                if (d[9] < 1 || d[10] >= d[9] || d[8] > d[9]) OPS_BAD("conv_in: n_steps >= 1, 0 <= step0 < n_steps and adv <= n_steps required");
-                idx_n = d[9];
+                if (d[9] < 1 || d[10] >= d[9] || d[8] > d[9]) return E.bad("conv_in: n_steps >= 1, 0 <= step0 < n_steps and adv <= n_steps required");
+                idx_n = d[9]; idx_lim = OpCheck::ANY_INDEX;
                 words = true;
             }
             need[0] = E.mul({B, d[1], d[2]}); need[1] = 9 * 64; need[2] = E.mul({B, (int64_t)HW, 64}); nbuf = 3;
@@ -4538,15 +4604,15 @@ extern "C" int spdm_op_stream(spdm_op_stream_args* p) {
             break;
         }
         case SPDM_OPS_POOL:
-            if (!positive({0, 1, 2, 3}) || (d[1] & 1) || (d[2] & 1)) OPS_BAD("pool: B, H, W, C positive and H, W even required");
-            if (d[3] % 4 != 0 || d[3] > 1024) OPS_BAD("pool: C must be a multiple of 4 <= 1024 (got %lld)", (long long)d[3]);
+            if (!E.positive({0, 1, 2, 3}) || (d[1] & 1) || (d[2] & 1)) return E.bad("pool: B, H, W, C positive and H, W even required");
+            if (d[3] % 4 != 0 || d[3] > 1024) return E.bad("pool: C must be a multiple of 4 <= 1024 (got %lld)", (long long)d[3]);
             need[0] = E.mul({B, d[1], d[2], d[3]}); need[1] = E.mul({B, d[1] / 2, d[2] / 2, d[3]}); nbuf = 2;
             gn_C[0] = gn_aff[0] = d[3]; gn_HW[0] = (int64_t)E.mul({d[1], d[2]});
             break;
         case SPDM_OPS_UPCAT: {
-            if (!positive({0, 1, 2, 3})) OPS_BAD("upcat: B, Hin, Win, Cu must be positive");
+            if (!E.positive({0, 1, 2, 3})) return E.bad("upcat: B, Hin, Win, Cu must be positive");
             const int64_t Cu = d[3], Cs = d[4];
-            if (Cu % 4 != 0 || Cs % 4 != 0 || Cu + Cs > 1024) OPS_BAD("upcat: Cu and Cs must be multiples of 4 with Cu + Cs <= 1024");
+            if (Cu % 4 != 0 || Cs % 4 != 0 || Cu + Cs > 1024) return E.bad("upcat: Cu and Cs must be multiples of 4 with Cu + Cs <= 1024");
             const int64_t HWi = (int64_t)E.mul({d[1], d[2]}), HWo = (int64_t)E.mul({4, d[1], d[2]});
             need[0] = E.mul({B, HWi, Cu}); need[1] = Cs ? E.mul({B, HWo, Cs}) : 0; absent[1] = Cs == 0;
             need[2] = E.mul({B, HWo, Cu + Cs}); nbuf = 3;
@@ -4556,52 +4622,52 @@ extern "C" int spdm_op_stream(spdm_op_stream_args* p) {
         }
         case SPDM_OPS_FILM_APPLY:
         case SPDM_OPS_FILM_COEF: {
-            if (!positive({0, 1, 2, 3, 4})) OPS_BAD("film: B, HW, C, t_count, T must be positive");
+            if (!E.positive({0, 1, 2, 3, 4})) return E.bad("film: B, HW, C, t_count, T must be positive");
             const int64_t C = d[2];
             const bool apply = q.op == SPDM_OPS_FILM_APPLY;
-            if (apply && (C % 4 != 0 || C > 1024 || 256 % (C / 4) != 0)) OPS_BAD("film_apply: C / 4 must divide 256 (got C = %lld)", (long long)C);
-            if (d[3] != 1 && d[3] != B) OPS_BAD("film: t_count must be 1 or B");
+            if (apply && (C % 4 != 0 || C > 1024 || 256 % (C / 4) != 0)) return E.bad("film_apply: C / 4 must divide 256 (got C = %lld)", (long long)C);
+            if (d[3] != 1 && d[3] != B) return E.bad("film: t_count must be 1 or B");
             const int it = apply ? 1 : 0;                                       // buffer index of temb
             if (apply) need[0] = E.mul({B, d[1], C});
             need[it] = E.mul({d[4], C}); optional[it] = true;
             need[it + 1] = E.mul({B, 2, C}); optional[it + 1] = true;
             need[it + 2] = apply ? need[0] : need[it + 1]; nbuf = it + 3;
             if (q.d_buf[it]) { idx_n = d[3]; idx_lim = d[4]; }
-            else if (d[3] != 1 || d[4] != 1) OPS_BAD("film: without temb, t_count = T = 1");
+            else if (d[3] != 1 || d[4] != 1) return E.bad("film: without temb, t_count = T = 1");
             gn_C[0] = gn_aff[0] = C; gn_HW[0] = d[1];
             if (apply) {
                 stats_need = E.mul({B, d[1], 2}); stats_optional = true;
-                if (q.d_stats_out && !(C == 64 || C == 128 || C == 256)) OPS_BAD("film_apply: row statistics need C 64, 128 or 256 (got %lld)", (long long)C);
+                if (q.d_stats_out && !(C == 64 || C == 128 || C == 256)) return E.bad("film_apply: row statistics need C 64, 128 or 256 (got %lld)", (long long)C);
             }
             break;
         }
         case SPDM_OPS_LAYERNORM:
-            if (!positive({0, 1})) OPS_BAD("layernorm: rows and C must be positive");
-            if (d[1] != 64 && d[1] != 128 && d[1] != 256 && d[1] != 512) OPS_BAD("layernorm: C must be 64, 128, 256 or 512 (got %lld)", (long long)d[1]);
+            if (!E.positive({0, 1})) return E.bad("layernorm: rows and C must be positive");
+            if (d[1] != 64 && d[1] != 128 && d[1] != 256 && d[1] != 512) return E.bad("layernorm: C must be 64, 128, 256 or 512 (got %lld)", (long long)d[1]);
             need[0] = need[3] = E.mul({d[0], d[1]}); need[1] = need[2] = (uint64_t)d[1]; nbuf = 4;
             break;
         case SPDM_OPS_MISH_PAD:
         case SPDM_OPS_SILU_PAD:
-            if (!positive({0, 1, 2}) || d[2] < d[1]) OPS_BAD("mish_pad / silu_pad: B, cond_dim positive and Kp >= cond_dim required");
+            if (!E.positive({0, 1, 2}) || d[2] < d[1]) return E.bad("mish_pad / silu_pad: B, cond_dim positive and Kp >= cond_dim required");
             need[0] = E.mul({B, d[1]}); need[1] = E.mul({B, d[2]}); nbuf = 2;
             break;
         case SPDM_OPS_SILU:
-            if (!positive({0})) OPS_BAD("silu: n must be positive");
+            if (!E.positive({0})) return E.bad("silu: n must be positive");
             need[0] = need[1] = (uint64_t)d[0]; nbuf = 2;
             break;
         case SPDM_OPS_DC_FINISH:
-            if (!positive({0, 1, 2})) OPS_BAD("dc_finish: B, HW, C must be positive");
-            if (d[2] % 4 != 0 || d[2] > 1024) OPS_BAD("dc_finish: C must be a multiple of 4 <= 1024 (got %lld)", (long long)d[2]);
+            if (!E.positive({0, 1, 2})) return E.bad("dc_finish: B, HW, C must be positive");
+            if (d[2] % 4 != 0 || d[2] > 1024) return E.bad("dc_finish: C must be a multiple of 4 <= 1024 (got %lld)", (long long)d[2]);
             need[0] = need[1] = need[2] = E.mul({B, d[1], d[2]}); optional[1] = true; nbuf = 3;
             gn_C[0] = gn_aff[0] = d[2]; gn_HW[0] = d[1];
             break;
         case SPDM_OPS_SIMPLE_TAIL: {
-            if (!positive({0, 1, 2, 3, 4, 5, 6, 7, 8})) OPS_BAD("simple_tail: every dimension must be positive");
+            if (!E.positive({0, 1, 2, 3, 4, 5, 6, 7, 8})) return E.bad("simple_tail: every dimension must be positive");
             const int64_t Co = d[2], Cr = d[3], Cs = d[4], tld = d[5], cld = d[6];
-            if (Co % 4 || Cr % 4 || Cs % 4 || tld % 4 || cld % 4) OPS_BAD("simple_tail: Co, Cr, src_C, temb_ld, cemb_ld must be multiples of 4");
+            if (Co % 4 || Cr % 4 || Cs % 4 || tld % 4 || cld % 4) return E.bad("simple_tail: Co, Cr, src_C, temb_ld, cemb_ld must be multiples of 4");
             if (Co > 1024 || Cr > Cs || Cr + 32 > Co || tld < Cr || cld < 32)
-                OPS_BAD("simple_tail: Co <= 1024, Cr <= src_C, Cr + 32 <= Co, temb_ld >= Cr and cemb_ld >= 32 required");
-            if (d[7] != 1 && d[7] != B) OPS_BAD("simple_tail: t_count must be 1 or B");
+                return E.bad("simple_tail: Co <= 1024, Cr <= src_C, Cr + 32 <= Co, temb_ld >= Cr and cemb_ld >= 32 required");
+            if (d[7] != 1 && d[7] != B) return E.bad("simple_tail: t_count must be 1 or B");
             need[0] = E.mul({B, d[1], Cs}); need[1] = E.strided((uint64_t)d[8], tld, Cr); need[2] = E.strided((uint64_t)B, cld, 32);
             need[3] = E.mul({B, d[1], Co}); nbuf = 4;
             idx_n = d[7]; idx_lim = d[8];
@@ -4609,22 +4675,22 @@ extern "C" int spdm_op_stream(spdm_op_stream_args* p) {
             break;
         }
         case SPDM_OPS_SPLITK_COMBINE: {
-            if (!positive({0, 1, 2}) || d[3] < 2) OPS_BAD("splitk_combine: B, HW, N positive and ksplit >= 2 required");
-            if (d[2] % 4 != 0) OPS_BAD("splitk_combine: N must be a multiple of 4 (got %lld)", (long long)d[2]);
+            if (!E.positive({0, 1, 2}) || d[3] < 2) return E.bad("splitk_combine: B, HW, N positive and ksplit >= 2 required");
+            if (d[2] % 4 != 0) return E.bad("splitk_combine: N must be a multiple of 4 (got %lld)", (long long)d[2]);
             need[1] = E.mul({B, d[1], d[2]}); need[0] = E.mul({d[3], B, d[1], d[2]}); nbuf = 2;
             rows = combine_rows((int)d[1], (int)d[2]);
-            if (d[1] % rows != 0) OPS_BAD("splitk_combine: rows per workgroup do not divide HW");
+            if (d[1] % rows != 0) return E.bad("splitk_combine: rows per workgroup do not divide HW");
             slots_out = stats_slots((int)d[1], rows, 1);
             stats_need = E.mul({B, slots_out, 2});
             break;
         }
         case SPDM_OPS_OUT_STEP: {
-            if (!positive({0, 1, 2, 3, 4, 10})) OPS_BAD("out_step: B, H0, D, Hp, Wp, n_steps must be positive");
-            if (d[5] + d[1] > d[3] || d[6] + d[2] > d[4]) OPS_BAD("out_step: lh + H0 <= Hp and lw + D <= Wp required");
+            if (!E.positive({0, 1, 2, 3, 4, 10})) return E.bad("out_step: B, H0, D, Hp, Wp, n_steps must be positive");
+            if (d[5] + d[1] > d[3] || d[6] + d[2] > d[4]) return E.bad("out_step: lh + H0 <= Hp and lw + D <= Wp required");
             const int64_t mode = d[8], inp_h = d[11];
-            if (d[7] > 1 || mode > 2 || d[12] > 1 || d[13] > 1) OPS_BAD("out_step: kind, inpaint_per_sample, indirect are 0 / 1 and mode 0, 1 or 2");
-            if (d[9] >= d[10]) OPS_BAD("out_step: step %lld outside [0, %lld)", (long long)d[9], (long long)d[10]);
-            if (inp_h > d[1]) OPS_BAD("out_step: inp_h must not exceed H0");
+            if (d[7] > 1 || mode > 2 || d[12] > 1 || d[13] > 1) return E.bad("out_step: kind, inpaint_per_sample, indirect are 0 / 1 and mode 0, 1 or 2");
+            if (d[9] >= d[10]) return E.bad("out_step: step %lld outside [0, %lld)", (long long)d[9], (long long)d[10]);
+            if (inp_h > d[1]) return E.bad("out_step: inp_h must not exceed H0");
             const uint64_t El = E.mul({B, d[1], d[2]});
             need[0] = E.mul({B, d[3], d[4], 64}); need[1] = 64; need[2] = need[3] = El; need[4] = E.mul({d[10], 6});
             need[5] = E.mul({d[10], (int64_t)El}); need[6] = E.mul({d[12] ? B : 1, inp_h ? inp_h : 1, d[2]}); need[7] = E.mul({d[10] + 1, (int64_t)El});
@@ -4638,47 +4704,16 @@ extern "C" int spdm_op_stream(spdm_op_stream_args* p) {
             break;
         }
     }
-    if (!E.ok) OPS_BAD("op %d: a tensor extent is beyond 31 bits", q.op);
-    for (int i = 0; i < SPDM_OP_STREAM_BUFS; ++i) {
-        if (i >= nbuf || absent[i]) {
-            if (q.d_buf[i]) OPS_BAD("op %d with these dimensions does not take d_buf[%d]; it must be null", q.op, i);
-            continue;
-        }
-        if (!q.d_buf[i]) {
-            if (!optional[i]) OPS_BAD("op %d: d_buf[%d] is null", q.op, i);
-            continue;
-        }
-        if (q.cap[i] < need[i])
-            OPS_BAD("op %d: d_buf[%d] holds %llu floats, the launch needs %llu", q.op, i, (unsigned long long)q.cap[i], (unsigned long long)need[i]);
-    }
-    if (idx_n == 0) {
-        if (q.h_idx[0] || q.n_idx[0]) OPS_BAD("op %d with these arguments takes no index arrays; h_idx[0] must be null", q.op);
-    } else {
-        if (!q.h_idx[0] || q.n_idx[0] != idx_n) OPS_BAD("op %d: h_idx[0] must hold %lld entries", q.op, (long long)idx_n);
-        for (int64_t i = 0; i < idx_n; ++i)
-            if (q.h_idx[0][i] < 0 || (idx_lim > 0 && q.h_idx[0][i] >= idx_lim))
-                OPS_BAD("op %d: h_idx[0][%lld] = %d outside [0, %lld)", q.op, (long long)i, q.h_idx[0][i], (long long)(idx_lim > 0 ? idx_lim : (int64_t)INT32_MAX + 1));
-    }
+    SPDM_TRY(E.buffers(q.d_buf, q.cap, SPDM_OP_STREAM_BUFS));
+    SPDM_TRY(E.indices("h_idx[0]", q.h_idx[0], q.n_idx[0], idx_n, idx_lim));
     StatsRef st[SPDM_OP_STREAM_GN];
-    for (int k = 0; k < SPDM_OP_STREAM_GN; ++k)
-        SPDM_TRY(op_pending_gn("op_stream", q.op, k, q.gn[k], B, gn_C[k], gn_HW[k], gn_aff[k], &st[k]));
-    if (stats_need == 0) {
-        if (q.d_stats_out || q.stats_out_cap) OPS_BAD("op %d writes no statistics; d_stats_out must be null", q.op);
-    } else if (!q.d_stats_out) {
-        if (!stats_optional) OPS_BAD("op %d: d_stats_out is null", q.op);
-    } else if (q.stats_out_cap < stats_need) {
-        OPS_BAD("op %d: d_stats_out holds %llu doubles, the launch needs %llu", q.op, (unsigned long long)q.stats_out_cap, (unsigned long long)stats_need);
-    }
-    if (words != (q.d_words != nullptr)) OPS_BAD("op %d with these arguments %s d_words", q.op, words ? "needs" : "does not take");
-#undef OPS_BAD
+    for (int k = 0; k < SPDM_OP_STREAM_GN; ++k) SPDM_TRY(op_pending_gn(E, k, q.gn[k], B, gn_C[k], gn_HW[k], gn_aff[k], &st[k]));
+    SPDM_TRY(E.doubles("d_stats_out", q.d_stats_out, q.stats_out_cap, stats_need, stats_optional));
+    if (words != (q.d_words != nullptr)) return E.bad("op %d with these arguments %s d_words", q.op, words ? "needs" : "does not take");
     // ---- the device from here on ----
-    OpTrainDev dev;
+    OpDev dev;
     const int* di = nullptr;
-    if (idx_n) {
-        HIP_TRY(hipMalloc(&dev.p[0], sizeof(int) * (size_t)idx_n));
-        HIP_TRY(hipMemcpy(dev.p[0], q.h_idx[0], sizeof(int) * (size_t)idx_n, hipMemcpyHostToDevice));
-        di = (const int*)dev.p[0];
-    }
+    SPDM_TRY(dev.upload_ints(q.h_idx[0], idx_n, &di));
     if (words) {
         const int w3[3] = {(int)(q.op == SPDM_OPS_CONV_IN ? d[10] : d[9]), -1, 0};
         HIP_TRY(hipMemcpy(q.d_words, w3, sizeof(w3), hipMemcpyHostToDevice));
@@ -4715,21 +4750,17 @@ extern "C" int spdm_op_stream(spdm_op_stream_args* p) {
             break;
         case SPDM_OPS_OUT_STEP: {
             const unsigned long long rng[2] = {q.seed, q.first_index};
-            HIP_TRY(hipMalloc(&dev.p[1], sizeof(rng)));
-            HIP_TRY(hipMemcpy(dev.p[1], rng, sizeof(rng), hipMemcpyHostToDevice));
             StepArgs a{};
+            SPDM_TRY(dev.upload(rng, sizeof(rng), &a.rng_dev));
             a.feat = b[0]; a.w = b[1]; a.bias = q.bias; a.x = b[3];
             a.eps_out = d[8] == 0 ? b[2] : nullptr;
             a.eps_in = d[8] == 2 ? b[2] : nullptr;
             a.coef = b[4]; a.step_dev = q.d_words; a.kind = (int)d[7];
-            a.rng_dev = (const unsigned long long*)dev.p[1];
             a.flag_dev = q.d_words + 2;
             a.inp_h = (int)d[11]; a.inpaint_per_sample = (int)d[12];
             if (d[13]) {
                 const void* ptrs[3] = {b[6], b[5], b[7]};
-                HIP_TRY(hipMalloc(&dev.p[2], sizeof(ptrs)));
-                HIP_TRY(hipMemcpy(dev.p[2], ptrs, sizeof(ptrs), hipMemcpyHostToDevice));
-                a.ptrs_dev = (const void* const*)dev.p[2];
+                SPDM_TRY(dev.upload(ptrs, sizeof(ptrs), &a.ptrs_dev));
             } else {
                 a.inpaint = b[6]; a.noise = b[5]; a.history = b[7];
             }
@@ -4738,10 +4769,7 @@ extern "C" int spdm_op_stream(spdm_op_stream_args* p) {
             break;
         }
     }
-    const hipError_t es = hipDeviceSynchronize();
-    if (el != hipSuccess) return fail(SPDM_ERR_HIP, "op_stream: op %d: launch failed: %s; device: %s", q.op, hipGetErrorString(el), hipGetErrorString(es));
-    if (es != hipSuccess) return fail(SPDM_ERR_HIP, "op_stream: op %d: %s", q.op, hipGetErrorString(es));
-    return SPDM_OK;
+    return op_finish(E.hook, q.op, el);
 }
 
 // op-level test hook: one launch_* of the autoencoder's decoder stage (decoder.hip), launch_add, or launch_wgrad under the slab
@@ -4751,30 +4779,26 @@ extern "C" int spdm_op_frame(spdm_op_frame_args* p) {
     if (!p) return fail(SPDM_ERR_INVALID, "op_frame: null argument");
     spdm_op_frame_args& q = *p;
     for (int i = 0; i < 4; ++i) q.info[i] = -1;
-    if (q.op < 0 || q.op >= SPDM_OPF_COUNT) return fail(SPDM_ERR_INVALID, "op_frame: unknown op %d", q.op);
+    OpCheck E("op_frame", q.op);
     static const int n_dims[SPDM_OPF_COUNT] = {2, 1, 1, 1, 1, 1, 1, 2, 1, 1, 1, 1, 3, 2, 0, 2};
     const int64_t* d = q.dim;
-    for (int i = 0; i < SPDM_OP_FRAME_DIMS; ++i) {
-        if (d[i] < 0 || d[i] > INT32_MAX) return fail(SPDM_ERR_INVALID, "op_frame: dim[%d] = %lld outside [0, 2^31)", i, (long long)d[i]);
-        if (i >= n_dims[q.op] && d[i] != 0) return fail(SPDM_ERR_INVALID, "op_frame: op %d takes %d dims; dim[%d] must be 0", q.op, n_dims[q.op], i);
-    }
-#define OPF_BAD(...) return fail(SPDM_ERR_INVALID, "op_frame: " __VA_ARGS__)
-    OpTrainExtent E;
-    uint64_t need[SPDM_OP_FRAME_BUFS] = {};
-    bool absent[SPDM_OP_FRAME_BUFS] = {};          // a buffer that must be NULL in this call (DEC_CONVS without train)
-    int nbuf = 0;
+    SPDM_TRY(E.dims(d, SPDM_OP_FRAME_DIMS, n_dims, SPDM_OPF_COUNT));
+    auto& need = E.need;
+    auto& absent = E.absent;                       // a buffer that must be NULL in this call (DEC_CONVS without train)
+    int& nbuf = E.nbuf;
     uint64_t need_sq = 0;                          // extent of d_sq; 0: the op does not take it
     uint64_t scratch = 0;                          // floats of the hook's own scratch
     // (the loss is formed once over ALL frames of a call, not per chunk)
     const bool frames = q.op <= SPDM_OPF_ENC_CONV1_WGRAD || (q.op >= SPDM_OPF_DEC_CONVS && q.op <= SPDM_OPF_DEC_DGRAD4 && q.op != SPDM_OPF_DEC_LOSS);
-    if (frames && (d[0] < 1 || d[0] > ENC_CHUNK)) OPF_BAD("op %d: n = %lld outside [1, %d] frames", q.op, (long long)d[0], ENC_CHUNK);
+    if (frames && (d[0] < 1 || d[0] > ENC_CHUNK)) return E.bad("op %d: n = %lld outside [1, %d] frames", q.op, (long long)d[0], ENC_CHUNK);
     const int64_t n = d[0];
-    int wCo = 0, wCi = 0, nch = 0, wrows = 0;
+    int wCo = 0, wCi = 0;
+    WgradSlabs ws{0, 0, 0};
     size_t budget = 0;
     switch (q.op) {
         case SPDM_OPF_ENC_CONVS:
         case SPDM_OPF_ENC_KINKS: {
-            if (q.op == SPDM_OPF_ENC_CONVS && d[1] > 1) OPF_BAD("enc_convs: train must be 0 or 1");
+            if (q.op == SPDM_OPF_ENC_CONVS && d[1] > 1) return E.bad("enc_convs: train must be 0 or 1");
             const uint64_t w[9] = {E.mul({n, DEC_PIX}), 16 * 3 * 4, 16, 32 * 16 * 4, 32, 64 * 32 * 4, 64, E.mul({n, ENC_FEAT}), E.mul({n, ENC_X3})};
             for (int i = 0; i < 9; ++i) need[i] = w[i];
             nbuf = 9;
@@ -4789,13 +4813,13 @@ extern "C" int spdm_op_frame(spdm_op_frame_args* p) {
             scratch = (uint64_t)encoder_conv1_wgrad_blocks((int)n) * 208;           // c1_part: [blocks(ENC_CHUNK)][208] in the product
             break;
         case SPDM_OPF_DEC_CONVS: {
-            if (d[1] > 1) OPF_BAD("dec_convs: train must be 0 or 1");
+            if (d[1] > 1) return E.bad("dec_convs: train must be 0 or 1");
             const uint64_t w[7] = {E.mul({n, DEC_FEAT}), 64 * 4 * 32, 32, 32 * 4 * 16, 16, 16 * 4 * 3, 3};
             for (int i = 0; i < 7; ++i) need[i] = w[i];
             need[7] = need[8] = E.mul({n, DEC_PIX}); need[9] = E.mul({n, DEC_A1}); need[10] = E.mul({n, DEC_A2}); nbuf = 11;
             if (d[1] == 0) absent[8] = absent[9] = absent[10] = true;
             else need_sq = (uint64_t)n;
-            if (d[1] == 0 && q.d_sq) OPF_BAD("dec_convs: d_sq must be null without train");
+            if (d[1] == 0 && q.d_sq) return E.bad("dec_convs: d_sq must be null without train");
             break;
         }
         case SPDM_OPF_DEC_KINKS: {
@@ -4806,11 +4830,11 @@ extern "C" int spdm_op_frame(spdm_op_frame_args* p) {
             break;
         }
         case SPDM_OPF_DEC_LOSS:
-            if (n < 1) OPF_BAD("dec_loss: n must be positive");
+            if (n < 1) return E.bad("dec_loss: n must be positive");
             need[0] = 1; nbuf = 1; need_sq = (uint64_t)n;
             break;
         case SPDM_OPF_DEC_BWD6:
-            if (!std::isfinite(q.scale)) OPF_BAD("dec_bwd6: scale is not finite");
+            if (!std::isfinite(q.scale)) return E.bad("dec_bwd6: scale is not finite");
             need[0] = need[1] = E.mul({n, DEC_PIX}); need[2] = need[4] = E.mul({n, DEC_A2}); need[3] = need[5] = 192; need[6] = 3; nbuf = 7;
             scratch = (uint64_t)n * 208;                                          // w6_part: [ENC_CHUNK][208] in the product
             break;
@@ -4819,72 +4843,52 @@ extern "C" int spdm_op_frame(spdm_op_frame_args* p) {
             break;
         case SPDM_OPF_DEC_COLSUM: {
             const int64_t M = d[0], C = d[1], fold = d[2];
-            if (M < 1) OPF_BAD("dec_colsum: M must be positive");
+            if (M < 1) return E.bad("dec_colsum: M must be positive");
             if (!((fold == 4 && (C == 64 || C == 128)) || (fold == 1 && C == DEC_FEAT)))
-                OPF_BAD("dec_colsum: (C, fold) must be (64, 4), (128, 4) or (9216, 1)");
+                return E.bad("dec_colsum: (C, fold) must be (64, 4), (128, 4) or (9216, 1)");
             const int64_t max_m = (int64_t)ENC_CHUNK * (fold == 1 ? 1 : C == 64 ? 576 : 144);
-            if (M > max_m) OPF_BAD("dec_colsum: M = %lld beyond the %lld rows of one chunk", (long long)M, (long long)max_m);
+            if (M > max_m) return E.bad("dec_colsum: M = %lld beyond the %lld rows of one chunk", (long long)M, (long long)max_m);
             need[0] = E.mul({M, C}); need[1] = (uint64_t)(C / fold); nbuf = 2;
             scratch = (uint64_t)decoder_colsum_slabs(M) * (uint64_t)C;
-            if (scratch > (uint64_t)decoder_colsum_slabs(ENC_CHUNK) * DEC_FEAT) OPF_BAD("dec_colsum: the slabs exceed cs_part");
+            if (scratch > (uint64_t)decoder_colsum_slabs(ENC_CHUNK) * DEC_FEAT) return E.bad("dec_colsum: the slabs exceed cs_part");
             break;
         }
         case SPDM_OPF_DEC_UNPERM_CONV:
             if (!((d[0] == 64 && d[1] == 32) || (d[0] == 32 && d[1] == 16) || (d[0] == 16 && d[1] == 3)))
-                OPF_BAD("dec_unperm_conv: (cin, cout) must be (64, 32), (32, 16) or (16, 3)");
+                return E.bad("dec_unperm_conv: (cin, cout) must be (64, 32), (32, 16) or (16, 3)");
             need[0] = need[1] = (uint64_t)(d[0] * d[1] * 4); nbuf = 2;
             break;
         case SPDM_OPF_DEC_UNPERM_LINEAR: need[0] = need[1] = (uint64_t)DEC_FEAT * DEC_LATENT; nbuf = 2; break;
         case SPDM_OPF_ADD:
-            if (d[0] < 1) OPF_BAD("add: n must be positive");
+            if (d[0] < 1) return E.bad("add: n must be positive");
             need[0] = need[1] = (uint64_t)d[0]; nbuf = 2;
             break;
         case SPDM_OPF_FRAME_WGRAD: {
             static const struct { int Co, Ci, rows_per_frame; } W[6] = {{ENC_LATENT, ENC_FEAT, 1}, {64, 128, 144}, {32, 64, 576},
                                                                         {32, 64, 576}, {64, 128, 144}, {DEC_FEAT, DEC_LATENT, 1}};
-            if (d[0] < 1) OPF_BAD("frame_wgrad: M must be positive");
-            if (d[1] > 5) OPF_BAD("frame_wgrad: which = %lld outside [0, 5]", (long long)d[1]);
+            if (d[0] < 1) return E.bad("frame_wgrad: M must be positive");
+            if (d[1] > 5) return E.bad("frame_wgrad: which = %lld outside [0, 5]", (long long)d[1]);
             const int k = (int)d[1];
             wCo = W[k].Co; wCi = W[k].Ci;
             const size_t budgets[6] = {ENC_WG_FLOATS, ENC_WG_FLOATS, ENC_WG_FLOATS, DEC_WG_SLABS * 32 * 64, DEC_WG_SLABS * 64 * 128, DEC_WG_FLOATS};
             budget = budgets[k];
             if (d[0] > (int64_t)ENC_CHUNK * W[k].rows_per_frame)
-                OPF_BAD("frame_wgrad: M = %lld beyond the %lld rows of one chunk", (long long)d[0], (long long)ENC_CHUNK * W[k].rows_per_frame);
+                return E.bad("frame_wgrad: M = %lld beyond the %lld rows of one chunk", (long long)d[0], (long long)ENC_CHUNK * W[k].rows_per_frame);
             need[0] = E.mul({d[0], wCo}); need[1] = E.mul({d[0], wCi}); need[2] = (uint64_t)wCo * wCi; nbuf = 3;
             if (!E.ok) break;
-            nch = wgrad_chunks((long long)d[0], 1, wCo, wCi, budget);
-            scratch = (uint64_t)nch * wCo * wCi;
-            if (nch < 1 || scratch > budget) OPF_BAD("frame_wgrad: the partial slabs exceed the budget");
-            wrows = (int)((((long long)d[0] + nch - 1) / nch + 3) / 4 * 4);
+            ws = wgrad_slabs((long long)d[0], 1, wCo, wCi, budget);
+            scratch = ws.slab;
+            if (!scratch) return E.bad("frame_wgrad: the partial slabs exceed the budget");
             break;
         }
     }
-    if (!E.ok) OPF_BAD("op %d: a tensor extent is beyond 31 bits", q.op);
-    for (int i = 0; i < SPDM_OP_FRAME_BUFS; ++i) {
-        if (i >= nbuf || absent[i]) {
-            if (q.d_buf[i]) OPF_BAD("op %d does not take d_buf[%d] here; it must be null", q.op, i);
-            continue;
-        }
-        if (!q.d_buf[i]) OPF_BAD("op %d: d_buf[%d] is null", q.op, i);
-        if (q.cap[i] < need[i])
-            OPF_BAD("op %d: d_buf[%d] holds %llu floats, the launch needs %llu", q.op, i, (unsigned long long)q.cap[i], (unsigned long long)need[i]);
-    }
-    if (need_sq) {
-        if (!q.d_sq) OPF_BAD("op %d: d_sq is null", q.op);
-        if (q.sq_cap < need_sq) OPF_BAD("op %d: d_sq holds %llu doubles, the launch needs %llu", q.op, (unsigned long long)q.sq_cap, (unsigned long long)need_sq);
-    } else if (q.d_sq) {
-        OPF_BAD("op %d does not take d_sq here; it must be null", q.op);
-    }
-    if (q.op != SPDM_OPF_DEC_BWD6 && q.scale != 0.f) OPF_BAD("op %d does not take a scale; it must be 0", q.op);
-#undef OPF_BAD
+    SPDM_TRY(E.buffers(q.d_buf, q.cap, SPDM_OP_FRAME_BUFS));
+    SPDM_TRY(E.doubles("d_sq", q.d_sq, q.d_sq ? q.sq_cap : 0, need_sq, false));       // (sq_cap without d_sq is not looked at)
+    if (q.op != SPDM_OPF_DEC_BWD6 && q.scale != 0.f) return E.bad("op %d does not take a scale; it must be 0", q.op);
     // ---- the device from here on ----
-    OpTrainDev dev;
+    OpDev dev;
     float* part = nullptr;
-    if (scratch) {
-        HIP_TRY(hipMalloc(&dev.p[0], sizeof(float) * (size_t)scratch));
-        HIP_TRY(hipMemset(dev.p[0], 0xff, sizeof(float) * (size_t)scratch));    // an unwritten partial reads as NaN
-        part = (float*)dev.p[0];
-    }
+    SPDM_TRY(dev.nan_scratch(scratch, &part));
     float* const* b = q.d_buf;
     const int ni = (int)n;
     hipStream_t s = nullptr;
@@ -4919,13 +4923,10 @@ extern "C" int spdm_op_frame(spdm_op_frame_args* p) {
         case SPDM_OPF_ADD: el = launch_add(b[0], (size_t)d[0], b[1], s); break;
         case SPDM_OPF_FRAME_WGRAD:
             el = launch_wgrad(b[0], wCo, b[1], wCi, (long long)d[0], 1, 1, 1, wCo, wCi, 0, part, budget, b[2], s);
-            q.info[0] = nch; q.info[1] = wrows; q.info[2] = wCo; q.info[3] = wCi;
+            q.info[0] = ws.nch; q.info[1] = ws.wrows; q.info[2] = wCo; q.info[3] = wCi;
             break;
     }
-    const hipError_t es = hipDeviceSynchronize();
-    if (el != hipSuccess) return fail(SPDM_ERR_HIP, "op_frame: op %d: launch failed: %s; device: %s", q.op, hipGetErrorString(el), hipGetErrorString(es));
-    if (es != hipSuccess) return fail(SPDM_ERR_HIP, "op_frame: op %d: %s", q.op, hipGetErrorString(es));
-    return SPDM_OK;
+    return op_finish(E.hook, q.op, el);
 }
 
 // op-level test hook: one forward SelfAttention launch (sa_fused.hip, sa_tail.hip, attention.hip) exactly as Ctx::attention makes
@@ -4935,34 +4936,30 @@ extern "C" int spdm_op_sa(spdm_op_sa_args* p) {
     if (!p) return fail(SPDM_ERR_INVALID, "op_sa: null argument");
     spdm_op_sa_args& q = *p;
     for (int i = 0; i < 5; ++i) q.info[i] = -1;
-    if (q.op < 0 || q.op >= SPDM_OPA_COUNT) return fail(SPDM_ERR_INVALID, "op_sa: unknown op %d", q.op);
+    OpCheck E("op_sa", q.op);
     static const int n_dims[SPDM_OPA_COUNT] = {10, 3, 3, 3, 4};
     const int64_t* d = q.dim;
-    for (int i = 0; i < SPDM_OP_SA_DIMS; ++i) {
-        if (d[i] < 0 || d[i] > INT32_MAX) return fail(SPDM_ERR_INVALID, "op_sa: dim[%d] = %lld outside [0, 2^31)", i, (long long)d[i]);
-        if (i >= n_dims[q.op] && d[i] != 0) return fail(SPDM_ERR_INVALID, "op_sa: op %d takes %d dims; dim[%d] must be 0", q.op, n_dims[q.op], i);
-    }
-#define OPA_BAD(...) return fail(SPDM_ERR_INVALID, "op_sa: " __VA_ARGS__)
+    SPDM_TRY(E.dims(d, SPDM_OP_SA_DIMS, n_dims, SPDM_OPA_COUNT));
     const bool fused = q.op == SPDM_OPA_FUSED64, core = q.op == SPDM_OPA_CORE;
     const int64_t B = fused || core ? d[0] : d[1], L = fused || core ? d[1] : d[2], C = fused ? 64 : core ? d[2] : d[0];
-    if (B < 1 || L < 1) OPA_BAD("op %d: B and L must be positive", q.op);
+    if (B < 1 || L < 1) return E.bad("op %d: B and L must be positive", q.op);
     if (core ? !(C == 64 || C == 128 || C == 256) : !fused && !(C == 128 || C == 256))
-        OPA_BAD("op %d: C = %lld (CORE: 64, 128 or 256; QKV, HEAD, TAIL: 128 or 256)", q.op, (long long)C);
+        return E.bad("op %d: C = %lld (CORE: 64, 128 or 256; QKV, HEAD, TAIL: 128 or 256)", q.op, (long long)C);
     const bool crop = fused && d[3] == 1, outc = fused && d[9] == 1;
     if (fused) {
-        if (d[2] > 1 || d[3] > 1 || d[9] > 1) OPA_BAD("fused64: no_wlds, crop and outc are 0 / 1");
-        if (!crop && (d[4] || d[5] || d[6] || d[7] || d[8] || d[9])) OPA_BAD("fused64: without crop, H0 = D = Wp = lh = lw = outc = 0");
+        if (d[2] > 1 || d[3] > 1 || d[9] > 1) return E.bad("fused64: no_wlds, crop and outc are 0 / 1");
+        if (!crop && (d[4] || d[5] || d[6] || d[7] || d[8] || d[9])) return E.bad("fused64: without crop, H0 = D = Wp = lh = lw = outc = 0");
     }
     // a hole of launch_sa_fused64 closed here as well as there: its crop checks ran in int, so two large factors could wrap into
     // the accepted range ((lh + H0) Wp with Wp = 2^31 - 1) and the kernel would read tokens far outside the sample.  Every crop
     // dimension of an accepted crop is at most L ((lh + H0) Wp <= L, lw + D <= Wp); beyond that nothing is asked of the launcher
     if (crop)
         for (int i = 4; i <= 8; ++i)
-            if (d[i] > L) OPA_BAD("fused64: crop dimension dim[%d] = %lld exceeds L = %lld", i, (long long)d[i], (long long)L);
-    if (core && d[3] > 1) OPA_BAD("core: valu is 0 / 1");
-    OpTrainExtent E;
-    uint64_t need[SPDM_OP_SA_BUFS] = {};
-    bool absent[SPDM_OP_SA_BUFS] = {};
+            if (d[i] > L) return E.bad("fused64: crop dimension dim[%d] = %lld exceeds L = %lld", i, (long long)d[i], (long long)L);
+    if (core && d[3] > 1) return E.bad("core: valu is 0 / 1");
+    auto& need = E.need;
+    auto& absent = E.absent;
+    E.nbuf = SPDM_OP_SA_BUFS;                      // every op here says which of the three it does not take
     bool takes_w[SPDM_OP_SA_WEIGHTS] = {}, takes_v[SPDM_OP_SA_VECS] = {};
     const uint64_t rowsC = E.mul({B, L, C}), rows3C = E.mul({B, L, 3, C});
     switch (q.op) {
@@ -4981,51 +4978,40 @@ extern "C" int spdm_op_sa(spdm_op_sa_args* p) {
             break;
         case SPDM_OPA_CORE: need[0] = rows3C; need[1] = rowsC; absent[2] = true; break;
     }
-    if (!E.ok) OPA_BAD("op %d: a tensor extent is beyond 31 bits", q.op);
-    for (int i = 0; i < SPDM_OP_SA_BUFS; ++i) {
-        if (absent[i]) {
-            if (q.d_buf[i]) OPA_BAD("op %d with these dimensions does not take d_buf[%d]; it must be null", q.op, i);
-            continue;
-        }
-        if (!q.d_buf[i]) OPA_BAD("op %d: d_buf[%d] is null", q.op, i);
-        if (q.cap[i] < need[i])
-            OPA_BAD("op %d: d_buf[%d] holds %llu floats, the launch needs %llu", q.op, i, (unsigned long long)q.cap[i], (unsigned long long)need[i]);
-    }
+    SPDM_TRY(E.buffers(q.d_buf, q.cap, SPDM_OP_SA_BUFS));
     for (int i = 0; i < SPDM_OP_SA_WEIGHTS; ++i)
-        if ((q.h_w[i] != nullptr) != takes_w[i]) OPA_BAD("op %d %s h_w[%d]", q.op, takes_w[i] ? "needs" : "does not take", i);
+        if ((q.h_w[i] != nullptr) != takes_w[i]) return E.bad("op %d %s h_w[%d]", q.op, takes_w[i] ? "needs" : "does not take", i);
     for (int i = 0; i < SPDM_OP_SA_VECS; ++i) {
-        if ((q.d_vec[i] != nullptr) != takes_v[i]) OPA_BAD("op %d %s d_vec[%d]", q.op, takes_v[i] ? "needs" : "does not take", i);
+        if ((q.d_vec[i] != nullptr) != takes_v[i]) return E.bad("op %d %s d_vec[%d]", q.op, takes_v[i] ? "needs" : "does not take", i);
         const uint64_t nv = (uint64_t)(i == 2 ? 3 * C : C);
         if (takes_v[i] ? q.vec_cap[i] < nv : q.vec_cap[i] != 0)
-            OPA_BAD("op %d: d_vec[%d] holds %llu floats, the launch needs %llu", q.op, i, (unsigned long long)q.vec_cap[i], (unsigned long long)(takes_v[i] ? nv : 0));
+            return E.bad("op %d: d_vec[%d] holds %llu floats, the launch needs %llu", q.op, i, (unsigned long long)q.vec_cap[i], (unsigned long long)(takes_v[i] ? nv : 0));
     }
     if (outc ? (!q.d_outc_w || q.outc_w_cap < 64 || !std::isfinite(q.outc_b)) : (q.d_outc_w || q.outc_w_cap || q.outc_b != 0.f))
-        OPA_BAD("op %d: outc's weight [64] and a finite bias go with outc = 1 only", q.op);
+        return E.bad("op %d: outc's weight [64] and a finite bias go with outc = 1 only", q.op);
     // the block input's affine: coefficients from memory (ab) or a recipe the kernel evaluates (FilmSpec); a hole of the launchers
     // closed here: they take any t_count, and the kernels read t_dev[b] for every t_count but 1
-    if (q.film_on != 0 && q.film_on != 1) OPA_BAD("film_on is 0 / 1");
-    if (core && (q.d_ab || q.film_on)) OPA_BAD("core takes neither ab nor a FilmSpec");
-    if (q.d_ab && q.film_on) OPA_BAD("op %d: ab and a FilmSpec are mutually exclusive", q.op);
-    if (q.d_ab ? q.ab_cap < E.mul({B, 2, C}) : q.ab_cap != 0) OPA_BAD("op %d: ab holds %llu floats, [B 2C] are needed", q.op, (unsigned long long)q.ab_cap);
+    if (q.film_on != 0 && q.film_on != 1) return E.bad("film_on is 0 / 1");
+    if (core && (q.d_ab || q.film_on)) return E.bad("core takes neither ab nor a FilmSpec");
+    if (q.d_ab && q.film_on) return E.bad("op %d: ab and a FilmSpec are mutually exclusive", q.op);
+    if (q.d_ab ? q.ab_cap < E.mul({B, 2, C}) : q.ab_cap != 0) return E.bad("op %d: ab holds %llu floats, [B 2C] are needed", q.op, (unsigned long long)q.ab_cap);
     StatsRef st{nullptr, 0, 1, 1, (int)L, 0.0};
     if (!q.film_on) {
-        if (q.t_count || q.T || q.d_temb || q.temb_cap || q.h_t || q.d_film || q.film_cap) OPA_BAD("op %d: film_on 0, its FilmSpec fields must be empty", q.op);
-        SPDM_TRY(op_pending_gn("op_sa", q.op, 0, q.gn, B, 0, L, 0, &st));
+        if (q.t_count || q.T || q.d_temb || q.temb_cap || q.h_t || q.d_film || q.film_cap) return E.bad("op %d: film_on 0, its FilmSpec fields must be empty", q.op);
+        SPDM_TRY(op_pending_gn(E, 0, q.gn, B, 0, L, 0, &st));
     } else {
-        if (q.t_count != 1 && q.t_count != B) OPA_BAD("film: t_count must be 1 or B");
-        if (q.T < 1 || q.T > INT32_MAX) OPA_BAD("film: T must be positive");
+        if (q.t_count != 1 && q.t_count != B) return E.bad("film: t_count must be 1 or B");
+        if (q.T < 1 || q.T > INT32_MAX) return E.bad("film: T must be positive");
         if (q.d_temb) {
-            if (q.temb_cap < E.mul({q.T, C})) OPA_BAD("film: temb holds %llu floats, [T C] are needed", (unsigned long long)q.temb_cap);
-            if (!q.h_t) OPA_BAD("film: temb needs the timesteps h_t");
-            for (int64_t i = 0; i < q.t_count; ++i)
-                if (q.h_t[i] < 0 || q.h_t[i] >= q.T) OPA_BAD("film: h_t[%lld] = %d outside [0, %lld)", (long long)i, q.h_t[i], (long long)q.T);
+            if (q.temb_cap < E.mul({q.T, C})) return E.bad("film: temb holds %llu floats, [T C] are needed", (unsigned long long)q.temb_cap);
+            SPDM_TRY(E.indices("h_t", q.h_t, q.t_count, q.t_count, q.T));      // (temb needs the timesteps)
         } else if (q.h_t || q.temb_cap || q.t_count != 1 || q.T != 1) {
-            OPA_BAD("film: without temb, h_t is null and t_count = T = 1");
+            return E.bad("film: without temb, h_t is null and t_count = T = 1");
         }
-        if (q.d_film ? q.film_cap < E.mul({B, 2, C}) : q.film_cap != 0) OPA_BAD("film: film holds %llu floats, [B 2C] are needed", (unsigned long long)q.film_cap);
-        SPDM_TRY(op_pending_gn("op_sa", q.op, 0, q.gn, B, C, L, C, &st));
+        if (q.d_film ? q.film_cap < E.mul({B, 2, C}) : q.film_cap != 0) return E.bad("film: film holds %llu floats, [B 2C] are needed", (unsigned long long)q.film_cap);
+        SPDM_TRY(op_pending_gn(E, 0, q.gn, B, C, L, C, &st));
     }
-    if (!E.ok) OPA_BAD("op %d: a tensor extent is beyond 31 bits", q.op);
+    SPDM_TRY(E.fits());
     // ---- the launch, asked of the launcher twice: dry (its own refusals, before the device is touched), then for real ----
     FilmSpec fs{};
     fs.st = st; fs.gamma = q.gn.d_gamma; fs.beta = q.gn.d_beta; fs.temb = q.d_temb; fs.t_count = q.t_count; fs.film = q.d_film; fs.C = (int)C;
@@ -5054,11 +5040,9 @@ extern "C" int spdm_op_sa(spdm_op_sa_args* p) {
         }
     };
     for (int i = 0; i < 4; ++i) wf[i] = takes_w[i] ? q.h_w[i] : nullptr;      // (dry: any non-null pointer; not dereferenced)
-    if (launch() != hipSuccess) OPA_BAD("op %d: the launcher refuses this launch (shape, route or LDS limits; kernels.h)", q.op);
-#undef OPA_BAD
+    if (launch() != hipSuccess) return E.bad("op %d: the launcher refuses this launch (shape, route or LDS limits; kernels.h)", q.op);
     // ---- the device from here on ----
-    // the weights as the loader lays them out: the caller's torch-layout tensors are the blob of a table of its own
-    std::vector<float> blob;
+    std::vector<float> blob;                // the caller's torch-layout weights, one after the other
     spdm_tensor_index index[SPDM_OP_SA_WEIGHTS] = {};
     int n_index = 0;
     for (int i = 0; i < SPDM_OP_SA_WEIGHTS; ++i) {
@@ -5068,9 +5052,8 @@ extern "C" int spdm_op_sa(spdm_op_sa_args* p) {
         e.offset = blob.size(); e.numel = (uint64_t)(i == 0 ? 3 : 1) * C * C; e.ndim = 2; e.shape[0] = (int)((i == 0 ? 3 : 1) * C); e.shape[1] = (int)C;
         blob.insert(blob.end(), q.h_w[i], q.h_w[i] + e.numel);
     }
-    DevBlob db;
-    WeightTable wt;
-    Recorder R(wt, blob.size(), index, n_index);
+    OwnWeights ow(blob.size(), index, n_index);
+    Recorder& R = ow.R;
     void* dfw[8] = {};
     float* dwf[4] = {};
     auto walk = [&]() {                    // Loader::attn, which starts each pass from an empty AttnW: a demoted weight leaves its
@@ -5085,25 +5068,17 @@ extern "C" int spdm_op_sa(spdm_op_sa_args* p) {
         return R.err;
     };
     if (n_index) {
-        SPDM_TRY(db.upload(blob.data(), blob.size()));
-        SPDM_TRY(R.both_passes(db.p, walk));
+        SPDM_TRY(ow.lay_out(blob.data(), walk));
         for (int i = 0; i < SPDM_OP_SA_WEIGHTS; ++i)
             if (takes_w[i] && !(C == 64 ? dfw[2 * i] && dfw[2 * i + 1] : dwf[i] != nullptr))
-                return fail(SPDM_ERR_INVALID, "op_sa: h_w[%d] is outside the split format's range (the plan keeps such a block on the GEMM chain)", i);
+                return OwnWeights::outside("op_sa", ("h_w[" + std::to_string(i) + "]").c_str(), "the plan keeps such a block on the GEMM chain");
     }
     for (int i = 0; i < 8; ++i) fw[i] = dfw[i];
     for (int i = 0; i < 4; ++i) wf[i] = dwf[i];
-    OpTrainDev dev;
-    if (q.film_on && q.d_temb) {
-        HIP_TRY(hipMalloc(&dev.p[0], sizeof(int) * (size_t)q.t_count));
-        HIP_TRY(hipMemcpy(dev.p[0], q.h_t, sizeof(int) * (size_t)q.t_count, hipMemcpyHostToDevice));
-        fs.t_dev = (const int*)dev.p[0];
-    }
+    OpDev dev;
+    if (q.film_on && q.d_temb) SPDM_TRY(dev.upload_ints(q.h_t, q.t_count, &fs.t_dev));
     r = SaRoute{0, -1, -1, -1, -1, -1};
-    const hipError_t el = launch();
-    const hipError_t es = hipDeviceSynchronize();
-    if (el != hipSuccess) return fail(SPDM_ERR_HIP, "op_sa: op %d: launch failed: %s; device: %s", q.op, hipGetErrorString(el), hipGetErrorString(es));
-    if (es != hipSuccess) return fail(SPDM_ERR_HIP, "op_sa: op %d: %s", q.op, hipGetErrorString(es));
+    SPDM_TRY(op_finish(E.hook, q.op, launch()));
     q.info[0] = r.kernel; q.info[1] = r.waves; q.info[2] = r.grid; q.info[3] = r.wlds; q.info[4] = r.qw;
     return SPDM_OK;
 }
