@@ -10,14 +10,12 @@ optimiser is torch's or, ``configure_optimizers(device_optimizer=True)``, ``opti
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, Optional
 
 import torch
 
-from . import _lib
-from .vision import ENCODER_KEYS, LATENT_DIM, VisionEncoder, encoder_state_dict_from
-from .weights import pack_state_dict, safe_load_state_dict
+from .vision import ENCODER_KEYS, LATENT_DIM, VisionEncoder, _FrameHandle, encoder_state_dict_from
+from .weights import safe_load_state_dict
 
 DECODER_KEYS = ("0.weight", "0.bias", "2.weight", "2.bias", "4.weight", "4.bias", "6.weight", "6.bias")
 DECODER_SHAPES = {"0.weight": (9216, 128), "0.bias": (9216,), "2.weight": (64, 32, 2, 2), "2.bias": (32,),
@@ -48,48 +46,12 @@ def _default_init() -> Dict[str, torch.Tensor]:
     return sd
 
 
-class Decoder:
+class Decoder(_FrameHandle):
     """``Decoder(state_dict)(latents)`` == ``Autoencoder().decoder(latents)``, latents ``(N,128)`` fp32 on the GPU ->
     reconstructions ``(N,3,96,96)``."""
 
-    def __init__(self, state_dict, device: int = 0):
-        self.lib = _lib.load()
-        if not torch.cuda.is_available():
-            raise RuntimeError("Decoder needs a visible MI355X (HIP device); there is no CPU fallback")
-        sd = {k: state_dict[k] for k in DECODER_KEYS}
-        for k, shp in DECODER_SHAPES.items():
-            if tuple(sd[k].shape) != shp:
-                raise ValueError(f"decoder tensor {k}: shape {tuple(sd[k].shape)}, expected {shp}")
-        self.device = torch.device("cuda", device)
-        blob, idx = pack_state_dict(sd)
-        self._index = [(e.name.decode(), int(e.offset), tuple(e.shape[d] for d in range(e.ndim))) for e in idx]
-        self._blob = blob                      # host values at creation; the device copy below follows updates
-        self._n_floats = int(blob.size)
-        self._flat = None                      # flat_parameter()
-        self._grad = None                      # flat gradient of the last backward
-        self._pending = None                   # (latents, target) of the pending train_loss
-        self.recon = None                      # reconstruction of the last train_loss
-        h = ctypes.c_void_p()
-        _lib.check(self.lib.spdm_decoder_create(device, blob.ctypes.data_as(ctypes.c_void_p), blob.size, idx, len(idx),
-                                                ctypes.byref(h)), "spdm_decoder_create")
-        self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self.lib.spdm_decoder_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def eval(self):
-        return self
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+    _keys, _shapes, _what, _pass = DECODER_KEYS, DECODER_SHAPES, "decoder", "train_loss"
+    recon = None                               # reconstruction of the last train_loss
 
     def _latents(self, latents: torch.Tensor) -> torch.Tensor:
         if latents.dim() != 2 or latents.shape[1] != LATENT_DIM:
@@ -99,10 +61,8 @@ class Decoder:
     def __call__(self, latents: torch.Tensor) -> torch.Tensor:
         z = self._latents(latents)
         out = torch.empty(z.shape[0], *FRAME, device=self.device, dtype=torch.float32)
-        if z.shape[0] == 0:
-            return out
-        _lib.check(self.lib.spdm_decoder_forward(self._h, z.shape[0], ctypes.c_void_p(z.data_ptr()),
-                                                 ctypes.c_void_p(out.data_ptr()), self._stream()), "spdm_decoder_forward")
+        if z.shape[0]:
+            self._run("forward", z.shape[0], z, out)
         return out
 
     def train_loss(self, latents: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
@@ -114,9 +74,7 @@ class Decoder:
         t = target.detach().to(self.device, torch.float32).contiguous()
         recon = torch.empty_like(t)
         loss = torch.empty((), device=self.device, dtype=torch.float32)
-        _lib.check(self.lib.spdm_decoder_train_loss(self._h, z.shape[0], ctypes.c_void_p(z.data_ptr()), ctypes.c_void_p(t.data_ptr()),
-                                                    ctypes.c_void_p(recon.data_ptr()), ctypes.c_void_p(loss.data_ptr()),
-                                                    self._stream()), "spdm_decoder_train_loss")
+        self._run("train_loss", z.shape[0], z, t, recon, loss)
         self._pending = (z, t)
         self.recon = recon
         return loss
@@ -132,47 +90,9 @@ class Decoder:
             z, t = self._pending
         flat = torch.empty(self._n_floats, device=self.device, dtype=torch.float32)
         gl = torch.empty(z.shape[0], LATENT_DIM, device=self.device, dtype=torch.float32)
-        _lib.check(self.lib.spdm_decoder_backward(self._h, z.shape[0], ctypes.c_void_p(z.data_ptr()), ctypes.c_void_p(t.data_ptr()),
-                                                  ctypes.c_void_p(flat.data_ptr()), ctypes.c_void_p(gl.data_ptr()), self._stream()),
-                   "spdm_decoder_backward")
-        self._pending = None
-        self._grad = flat
-        if self._flat is not None:
-            self._flat.grad = flat
+        self._run("backward", z.shape[0], z, t, flat, gl)
+        self._backward_done(flat)
         return flat, gl
-
-    def grads(self):
-        """state_dict name -> gradient of the last ``backward`` (torch layout, views of the flat gradient)."""
-        if self._grad is None:
-            raise RuntimeError("no gradients: call train_loss and backward first")
-        return {name: self._grad[off:off + int(torch.Size(shape).numel())].view(shape) for name, off, shape in self._index}
-
-    def flat_parameter(self) -> torch.nn.Parameter:
-        """The weights as ONE device parameter in the packed layout (see ``VisionEncoder.flat_parameter``)."""
-        if self._flat is None:
-            self._flat = torch.nn.Parameter(torch.from_numpy(self._blob).to(self.device))
-        return self._flat
-
-    def update_weights(self, dev_blob: torch.Tensor) -> None:
-        """Put new values (a device blob in the packed layout, e.g. ``flat_parameter().detach()``) into the handle in
-        place; a pending ``train_loss`` is dropped."""
-        b = dev_blob.detach()
-        if b.device != self.device or b.dtype != torch.float32 or not b.is_contiguous() or b.numel() != self._n_floats:
-            raise ValueError(f"expected a contiguous fp32 blob of {self._n_floats} floats on {self.device}")
-        _lib.check(self.lib.spdm_decoder_update_weights(self._h, ctypes.c_void_p(b.data_ptr()), b.numel(), self._stream()),
-                   "spdm_decoder_update_weights")
-        self._pending = None
-        if self._flat is None:
-            self._blob = b.cpu().numpy()
-        elif b.data_ptr() != self._flat.data_ptr():      # values from elsewhere: the parameter follows the handle
-            with torch.no_grad():
-                self._flat.copy_(b)
-
-    def state_dict(self):
-        """Current values under the nn.Sequential's key names (host tensors)."""
-        host = self._flat.detach().cpu().numpy() if self._flat is not None else self._blob
-        return {name: torch.from_numpy(host[off:off + int(torch.Size(shape).numel())].reshape(shape).copy())
-                for name, off, shape in self._index}
 
 
 class autoencoder:

@@ -133,7 +133,8 @@ struct AttnW {
 // -------------------------------------------------------------------------------------------------
 // The device weight-copy table (weight_layout.hip): the recorded copies (a Recorder, below, fills it in), the split format's
 // range checks and the copies' offset tables, their device mirrors and every device allocation made for them, the copies'
-// destinations included.  A spdm_handle and a spdm_encoder hold one each; the standalone GEMM entry points build a temporary one.
+// destinations included.  A spdm_handle and each frame handle (FrameNet: spdm_encoder, spdm_decoder) hold one; the standalone
+// GEMM entry points build a temporary one.
 struct WeightTable {
     std::vector<WeightCopy> copies;       // every copy, in the order it was recorded (spdm_debug_weight_digest)
     std::vector<WeightCopy> ranges;       // the split format's range checks (WL_RANGE)
@@ -3535,103 +3536,215 @@ extern "C" int spdm_bench_gemm(int32_t device, int32_t B, int32_t H, int32_t W, 
 }
 
 // -------------------------------------------------------------------------------------------------
-// Observation front end (SURVEY 8f rank 2): the autoencoder's encoder, models/encoder/autoencoder.py:11-20, applied by
-// prepare_obs_cond_vectors (models/diffusion_ddpm.py:317-321) to every observed frame once per sample() call.
-struct spdm_encoder {
-    int device = 0;
-    float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *w3 = nullptr, *b3 = nullptr, *wl = nullptr, *bl = nullptr;
-    float* feat = nullptr;            // [chunk][9216] flattened conv-3 maps of the chunk in flight
-    int chunk = 0;
-    std::vector<void*> owned;
-    WeightTable wt;                   // the eight tensors above and, once the handle trains, the three transposed copies below
-    long long off[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // blob offset of 0.weight 0.bias 2.* 4.* 7.* (the index given to create)
-    size_t numel[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // ... and their sizes
-    size_t blob_floats = 0;
-    // ---- training (spdm_encoder_train_forward / _backward; nothing below is allocated by a handle that never trains) ----
-    float *wlT = nullptr, *w3T = nullptr, *w2T = nullptr;     // transposed copies: the data gradients' launch_gemm weights
-    float *sv_feat = nullptr, *sv_x3 = nullptr;      // saved conv-3 map [cap][9216] and conv-2 map [cap][144][128] of ALL frames
-    int sv_cap = 0, sv_n = 0;                        // frames they hold room for / frames of the forward awaiting its backward
-    float *bw_a = nullptr, *bw_dz2 = nullptr, *bw_x2 = nullptr;   // backward scratch of one chunk (encoder_backward)
-    int bw_cap = 0;
-    float *wg_part = nullptr, *c1_part = nullptr, *g_tmp = nullptr;   // wgrad slabs, conv 1's partial rows, a later chunk's gradient
-};
-static constexpr int ENC_FEAT = 64 * 12 * 12, ENC_LATENT = 128, ENC_CHUNK = 2048;
-static constexpr int ENC_X3 = 144 * 128, ENC_X2 = 576 * 64;      // floats per frame of the conv-2 / conv-1 map
-static constexpr size_t ENC_WG_FLOATS = (size_t)8 * ENC_LATENT * ENC_FEAT;     // launch_wgrad's partial slabs (7.weight: <= 7)
+// The frame autoencoder (models/encoder/autoencoder.py): 96 x 96 frames <-> 128 latents through a [64][12][12] map.  FrameNet is
+// what its two handles share: the state, the allocations, create / update / destroy, the chunk walk, the pending-pass protocol
+// and the frame of the lazily built training state.  spdm_encoder and spdm_decoder below add their tensors, buffers and launches.
+static constexpr int FRAME_FEAT = 64 * 12 * 12, FRAME_LATENT = 128, FRAME_PIX = 3 * 96 * 96;
+static constexpr int FRAME_CHUNK = 2048;           // frames per walk over the layers: what every per-chunk buffer is sized for
+static constexpr size_t FRAME_WG_FLOATS = (size_t)8 * FRAME_LATENT * FRAME_FEAT;     // launch_wgrad's partial slabs (the Linear: <= 7)
+struct FrameItem { const char* name; std::vector<int> shape; };      // one of a handle's eight tensors: nn.Sequential key, torch shape
+struct FrameBuf { float** p; size_t per_frame; };                     // one of a group of per-frame buffers that grow together
 
-// nn.Sequential indices of Autoencoder.encoder: 0, 2, 4 = Conv2d; 7 = Linear
-static const struct { const char* name; std::vector<int> shape; float* spdm_encoder::*dst; } ENC_ITEMS[8] = {
-    {"0.weight", {16, 3, 2, 2}, &spdm_encoder::w1}, {"0.bias", {16}, &spdm_encoder::b1},
-    {"2.weight", {32, 16, 2, 2}, &spdm_encoder::w2}, {"2.bias", {32}, &spdm_encoder::b2},
-    {"4.weight", {64, 32, 2, 2}, &spdm_encoder::w3}, {"4.bias", {64}, &spdm_encoder::b3},
-    {"7.weight", {ENC_LATENT, ENC_FEAT}, &spdm_encoder::wl}, {"7.bias", {ENC_LATENT}, &spdm_encoder::bl}};
-
-extern "C" void spdm_encoder_destroy(spdm_encoder* e) {
-    if (!e) return;
-    (void)hipSetDevice(e->device);
-    for (void* p : e->owned) (void)hipFree(p);
-    delete e;
+static int frame_chunk(int n) { return std::min<int>(n, FRAME_CHUNK); }
+// body(i0, m) for each chunk of n frames, in order
+template <class Body>
+static int frame_chunks(int n, Body body) {
+    const int chunk = frame_chunk(n);
+    for (int i0 = 0; i0 < n; i0 += chunk) SPDM_TRY(body(i0, std::min(chunk, n - i0)));
+    return SPDM_OK;
+}
+// y [m][out] = x [m][in] W^T + b on the exact fp32 MFMA path: the encoder's Linear(9216, 128), the decoder's Linear(128, 9216)
+static hipError_t frame_linear(const float* x, int m, float* w, float* b, int in, int out, float* y, hipStream_t s) {
+    return launch_gemm(linear_args(AffineSrc{x, in}, m, 0, LinW{w, nullptr, b, in, out}, /*split=*/false, /*sw=*/0, EPI_BIAS, y), s);
+}
+// dx [M][N] = dy [M][K] W: a plain data gradient, the forward GEMM on wT ([N][K], k contiguous) with no prologue or epilogue
+static hipError_t frame_dgrad(const float* dy, long long M, int K, int N, const float* wT, float* dx, hipStream_t s) {
+    return launch_gemm(gemm_args((int)M, 0, 1, 1, K, N, 1, 0, 0, nullptr, PRO_NONE, AffineSrc{dy, K}, 0, AffineSrc{}, wT, nullptr, dx,
+                                 N, EPI_PLAIN, nullptr), s);
 }
 
-extern "C" int spdm_encoder_create(int32_t device, const float* blob, size_t n, const spdm_tensor_index* index, int32_t n_index,
-                                   spdm_encoder** out) {
+struct FrameNet {
+    const char* const what;           // "encoder" / "decoder": the messages and the spdm_<what>_* names are spelt with it
+    const char* const pass;           // the training forward whose saved maps ONE backward consumes: "train_forward" / "train_loss"
+    int device = 0;
+    WeightTable wt;                   // the eight tensors' kernel-layout copies and, once the handle trains, the data gradients'
+    long long off[8] = {};            // blob offsets of the eight tensors (the index given to create)
+    size_t numel[8] = {};             // ... and their sizes
+    size_t blob_floats = 0;
+    std::vector<void*> owned;
+    int sv_n = 0;                     // frames of the training forward awaiting its backward
+    float* g_tmp = nullptr;           // [blob_floats] a later chunk's gradient (training only)
+    bool trains = false;              // the training state below is complete
+    std::string broken;               // why it is not and never will be: every entry but destroy refuses such a handle
+    FrameNet(const char* w, const char* p) : what(w), pass(p) {}
+    virtual ~FrameNet() = default;
+
+    int alloc(float** p, size_t floats) {
+        void* q = nullptr;
+        if (hipMalloc(&q, floats * sizeof(float)) != hipSuccess) return fail(SPDM_ERR_NOMEM, "%s workspace (%zu floats)", what, floats);
+        owned.push_back(q);
+        *p = (float*)q;
+        return SPDM_OK;
+    }
+    void release(float** p) {
+        if (!*p) return;
+        for (auto it = owned.begin(); it != owned.end(); ++it)
+            if (*it == (void*)*p) { owned.erase(it); break; }
+        (void)hipFree(*p);
+        *p = nullptr;
+    }
+    // room for `frames` frames in a group of buffers that holds `*cap`; the steady state returns at once
+    int grow(int* cap, int frames, std::initializer_list<FrameBuf> bufs) {
+        if (*cap >= frames) return SPDM_OK;
+        HIP_TRY(hipDeviceSynchronize());      // (an earlier call's kernels may still read the buffers being replaced)
+        for (const FrameBuf& b : bufs) release(b.p);
+        *cap = 0;
+        for (const FrameBuf& b : bufs) SPDM_TRY(alloc(b.p, (size_t)frames * b.per_frame));
+        *cap = frames;
+        return SPDM_OK;
+    }
+    // every entry but destroy, after its argument checks: a usable handle, its device current
+    int enter() {
+        if (!broken.empty())
+            return fail(SPDM_ERR_STATE, "%s: the handle is unusable, its training state was not completed: %s", what, broken.c_str());
+        HIP_TRY(hipSetDevice(device));
+        return SPDM_OK;
+    }
+    // a backward pass of n frames consumes the pending training forward of the same n; a wrong n leaves it pending
+    int pending(int n) const {
+        if (sv_n == 0) return fail(SPDM_ERR_STATE, "%s_backward: no spdm_%s_%s is pending", what, what, pass);
+        if (sv_n != n) return fail(SPDM_ERR_STATE, "%s_backward: %d frames, the pending %s had %d", what, n, pass, sv_n);
+        return SPDM_OK;
+    }
+    // The training state, built by the first training forward.  record(R) allocates the handle's scratch and records the data
+    // gradients' copies; the handle keeps no blob, so to_blob(T) writes the current weights back to their blob offsets in T
+    // (g_tmp: scratch until a backward pass), and laying that out again fills the new copies.  All or nothing: a step that
+    // fails leaves a table with copies its device mirror may not hold, so the handle is marked broken and never records again.
+    template <class Record, class ToBlob>
+    int train_state(hipStream_t s, Record record, ToBlob to_blob) {
+        if (trains) return SPDM_OK;
+        const int rc = [&]() -> int {
+            Recorder R(wt, blob_floats);
+            R.plan = false;
+            SPDM_TRY(record(R));
+            SPDM_TRY(R.err);
+            SPDM_TRY(alloc(&g_tmp, blob_floats));
+            SPDM_TRY(wt.upload(false));
+            SPDM_TRY(to_blob(g_tmp));
+            return wt.relayout(g_tmp, s);
+        }();
+        if (rc != SPDM_OK) broken = g_err;
+        trains = rc == SPDM_OK;
+        return rc;
+    }
+    // A backward pass over the chunks: body(i0, m, G) writes chunk (i0, m)'s gradient to G in blob order -- d_grad for the first
+    // chunk, g_tmp for a later one, which is then added tensor by tensor: the sum runs in chunk order.
+    template <class Body>
+    int grad_chunks(int n, float* d_grad, hipStream_t s, Body body) {
+        HIP_TRY(hipMemsetAsync(d_grad, 0, blob_floats * sizeof(float), s));
+        return frame_chunks(n, [&](int i0, int m) -> int {
+            SPDM_TRY(body(i0, m, i0 == 0 ? d_grad : g_tmp));
+            if (i0 != 0) {
+                for (int k = 0; k < 8; ++k) HIP_TRY(launch_add(g_tmp + off[k], numel[k], d_grad + off[k], s));
+            }
+            return SPDM_OK;
+        });
+    }
+};
+
+static void frame_destroy(FrameNet* f) {
+    if (!f) return;
+    (void)hipSetDevice(f->device);
+    for (void* p : f->owned) (void)hipFree(p);
+    delete f;
+}
+
+// record(f, R) records the kernel-layout copies of the eight tensors, whose names and shapes have been checked against the index
+template <class Net, class Record>
+static int frame_create(const FrameItem (&items)[8], int32_t device, const float* blob, size_t n, const spdm_tensor_index* index,
+                        int32_t n_index, Net** out, Record record) {
     if (!blob || !index || n_index <= 0 || !out) return fail(SPDM_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(device));
-    spdm_encoder* e = new spdm_encoder();
-    e->device = device;
-    e->blob_floats = n;
-    Recorder R(e->wt, n, index, n_index);
+    Net* f = new Net();
+    f->device = device;
+    f->blob_floats = n;
+    Recorder R(f->wt, n, index, n_index);
     R.plan = false;                        // fp32 copies only: nothing to ask the device first
-    for (int k = 0; k < 8; ++k) {
-        const long long off = R.at(ENC_ITEMS[k].name, ENC_ITEMS[k].shape);
+    int k = 0;
+    for (; k < 8; ++k) {
+        const long long off = R.at(items[k].name, items[k].shape);
         if (off < 0) break;
-        e->off[k] = off;
-        e->numel[k] = 1;
-        for (int d : ENC_ITEMS[k].shape) e->numel[k] *= (size_t)d;
-        e->*(ENC_ITEMS[k].dst) = R.f32(Recorder::dense(off, 1, 1, (int)e->numel[k]));
+        f->off[k] = off;
+        f->numel[k] = 1;
+        for (int d : items[k].shape) f->numel[k] *= (size_t)d;
     }
+    if (k == 8) record(f, R);
     DevBlob db;
     int rc = R.err;
     if (rc == SPDM_OK) rc = db.upload(blob, n);
     if (rc == SPDM_OK) rc = R.finish(db.p);
-    if (rc != SPDM_OK) { spdm_encoder_destroy(e); return rc; }
-    *out = e;
+    if (rc != SPDM_OK) { frame_destroy(f); return rc; }
+    *out = f;
     return SPDM_OK;
 }
 
-static int enc_alloc(spdm_encoder* e, float** p, size_t floats) {
-    void* q = nullptr;
-    if (hipMalloc(&q, floats * sizeof(float)) != hipSuccess) return fail(SPDM_ERR_NOMEM, "encoder training workspace (%zu floats)", floats);
-    e->owned.push_back(q);
-    *p = (float*)q;
+// the new values go into the handle's tensors in place, and into the data gradients' copies of a handle that trains
+static int frame_update_weights(FrameNet* f, const float* d_blob, size_t n, void* stream) {
+    if (!f || !d_blob) return fail(SPDM_ERR_INVALID, "null argument");
+    if (n != f->blob_floats)
+        return fail(SPDM_ERR_INVALID, "blob has %zu floats; the one given to spdm_%s_create had %zu", n, f->what, f->blob_floats);
+    SPDM_TRY(f->enter());
+    hipStream_t s = (hipStream_t)stream;
+    f->sv_n = 0;                               // saved maps belong to the old weights
+    SPDM_TRY(f->wt.relayout(d_blob, s));
+    if (!stream) HIP_TRY(hipStreamSynchronize(s));
     return SPDM_OK;
 }
-static void enc_release(spdm_encoder* e, float** p) {
-    if (!*p) return;
-    for (auto it = e->owned.begin(); it != e->owned.end(); ++it)
-        if (*it == (void*)*p) { e->owned.erase(it); break; }
-    (void)hipFree(*p);
-    *p = nullptr;
+
+// -------------------------------------------------------------------------------------------------
+// Observation front end (SURVEY 8f rank 2): the autoencoder's encoder, models/encoder/autoencoder.py:11-20, applied by
+// prepare_obs_cond_vectors (models/diffusion_ddpm.py:317-321) to every observed frame once per sample() call.
+struct spdm_encoder : FrameNet {
+    spdm_encoder() : FrameNet("encoder", "train_forward") {}
+    float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *w3 = nullptr, *b3 = nullptr, *wl = nullptr, *bl = nullptr;
+    float* feat = nullptr;            // [fw_cap][9216] flattened conv-3 maps of the chunk in flight (spdm_encoder_forward)
+    int fw_cap = 0;
+    // ---- training (spdm_encoder_train_forward / _backward; nothing below is allocated by a handle that never trains) ----
+    float *wlT = nullptr, *w3T = nullptr, *w2T = nullptr;     // transposed copies: the data gradients' launch_gemm weights
+    float *sv_feat = nullptr, *sv_x3 = nullptr;      // saved conv-3 map [sv_cap][9216] and conv-2 map [sv_cap][144][128] of ALL frames
+    int sv_cap = 0;
+    float *bw_a = nullptr, *bw_dz2 = nullptr, *bw_x2 = nullptr;   // backward scratch of one chunk (encoder_backward)
+    int bw_cap = 0;
+    float *wg_part = nullptr, *c1_part = nullptr;    // wgrad slabs, conv 1's partial rows
+};
+static constexpr int ENC_X3 = 144 * 128, ENC_X2 = 576 * 64;      // floats per frame of the conv-2 / conv-1 map
+
+// nn.Sequential indices of Autoencoder.encoder: 0, 2, 4 = Conv2d; 7 = Linear
+static const FrameItem ENC_ITEMS[8] = {{"0.weight", {16, 3, 2, 2}}, {"0.bias", {16}}, {"2.weight", {32, 16, 2, 2}}, {"2.bias", {32}},
+                                       {"4.weight", {64, 32, 2, 2}}, {"4.bias", {64}},
+                                       {"7.weight", {FRAME_LATENT, FRAME_FEAT}}, {"7.bias", {FRAME_LATENT}}};
+static float* spdm_encoder::* const ENC_TENSORS[8] = {&spdm_encoder::w1, &spdm_encoder::b1, &spdm_encoder::w2, &spdm_encoder::b2,
+                                                      &spdm_encoder::w3, &spdm_encoder::b3, &spdm_encoder::wl, &spdm_encoder::bl};
+
+extern "C" void spdm_encoder_destroy(spdm_encoder* e) { frame_destroy(e); }
+
+extern "C" int spdm_encoder_create(int32_t device, const float* blob, size_t n, const spdm_tensor_index* index, int32_t n_index,
+                                   spdm_encoder** out) {
+    return frame_create(ENC_ITEMS, device, blob, n, index, n_index, out, [](spdm_encoder* e, Recorder& R) {
+        for (int k = 0; k < 8; ++k) e->*ENC_TENSORS[k] = R.f32(Recorder::dense(e->off[k], 1, 1, (int)e->numel[k]));
+    });
 }
+
 extern "C" int spdm_encoder_forward(spdm_encoder* e, int32_t n_images, const float* d_images, float* d_latent, void* stream) {
     if (!e || !d_images || !d_latent || n_images <= 0) return fail(SPDM_ERR_INVALID, "bad argument");
-    HIP_TRY(hipSetDevice(e->device));
+    SPDM_TRY(e->enter());
     hipStream_t s = (hipStream_t)stream;
-    const int chunk = std::min<int>(n_images, ENC_CHUNK);
-    if (e->chunk < chunk) {             // (grown lazily; the old buffer stays owned until destroy: at most two sizes ever exist)
-        void* p = nullptr;
-        HIP_TRY(hipMalloc(&p, sizeof(float) * (size_t)chunk * ENC_FEAT));
-        e->owned.push_back(p);
-        e->feat = (float*)p;
-        e->chunk = chunk;
-    }
-    for (int i0 = 0; i0 < n_images; i0 += chunk) {
-        const int m = std::min(chunk, n_images - i0);
-        HIP_TRY(launch_encoder_convs(d_images + (size_t)i0 * 3 * 96 * 96, e->w1, e->b1, e->w2, e->b2, e->w3, e->b3, e->feat, m, s));
-        const LinW lin{e->wl, nullptr, e->bl, ENC_FEAT, ENC_LATENT};      // Linear(9216, 128) on the exact fp32 MFMA path
-        HIP_TRY(launch_gemm(linear_args(AffineSrc{e->feat, ENC_FEAT}, m, 0, lin, /*split=*/false, /*sw=*/0, EPI_BIAS,
-                                        d_latent + (size_t)i0 * ENC_LATENT), s));
-    }
+    SPDM_TRY(e->grow(&e->fw_cap, frame_chunk(n_images), {{&e->feat, FRAME_FEAT}}));
+    SPDM_TRY(frame_chunks(n_images, [&](int i0, int m) -> int {
+        HIP_TRY(launch_encoder_convs(d_images + (size_t)i0 * FRAME_PIX, e->w1, e->b1, e->w2, e->b2, e->w3, e->b3, e->feat, m, s));
+        HIP_TRY(frame_linear(e->feat, m, e->wl, e->bl, FRAME_FEAT, FRAME_LATENT, d_latent + (size_t)i0 * FRAME_LATENT, s));
+        return SPDM_OK;
+    }));
     if (!stream) HIP_TRY(hipStreamSynchronize(s));
     return SPDM_OK;
 }
@@ -3641,50 +3754,34 @@ extern "C" int spdm_encoder_forward(spdm_encoder* e, int32_t n_images, const flo
 // reads the same values in the same geometry: the same bits), with the maps the backward pass needs kept for all frames.
 extern "C" int spdm_encoder_train_forward(spdm_encoder* e, int32_t n_images, const float* d_images, float* d_latent, void* stream) {
     if (!e || !d_images || !d_latent || n_images <= 0) return fail(SPDM_ERR_INVALID, "bad argument");
-    HIP_TRY(hipSetDevice(e->device));
+    SPDM_TRY(e->enter());
     hipStream_t s = (hipStream_t)stream;
     e->sv_n = 0;
-    if (!e->wlT) {
-        SPDM_TRY(enc_alloc(e, &e->wg_part, ENC_WG_FLOATS));
-        SPDM_TRY(enc_alloc(e, &e->c1_part, (size_t)encoder_conv1_wgrad_blocks(ENC_CHUNK) * 208));
-        SPDM_TRY(enc_alloc(e, &e->g_tmp, e->blob_floats));
-        // the transposed copies the data gradients read: dx = dy W is the forward GEMM on W^T ([N = in][K = out], k contiguous)
-        Recorder R(e->wt, e->blob_floats);
-        R.plan = false;
-        float* const w2T = R.transposed(e->off[2], 32, 64);                   // (32, 16*4)  -> [64][32]
-        float* const w3T = R.transposed(e->off[4], 64, 128);                  // (64, 32*4)  -> [128][64]
-        float* const wlT = R.transposed(e->off[6], ENC_LATENT, ENC_FEAT);     // (128, 9216) -> [9216][128]
-        SPDM_TRY(R.err);
-        SPDM_TRY(e->wt.upload(false));
-        // the handle keeps no blob: the weights go back to their blob offsets in g_tmp (scratch until a backward pass), and laying
-        // that out again fills the new copies
-        for (int k = 0; k < 8; ++k)
-            HIP_TRY(hipMemcpyAsync(e->g_tmp + e->off[k], e->*(ENC_ITEMS[k].dst), e->numel[k] * sizeof(float), hipMemcpyDeviceToDevice, s));
-        SPDM_TRY(e->wt.relayout(e->g_tmp, s));
-        e->w2T = w2T; e->w3T = w3T; e->wlT = wlT;
-    }
-    if (e->sv_cap < n_images) {
-        HIP_TRY(hipDeviceSynchronize());      // (an earlier call's kernels may still read the buffers being replaced)
-        enc_release(e, &e->sv_feat);
-        enc_release(e, &e->sv_x3);
-        e->sv_cap = 0;
-        SPDM_TRY(enc_alloc(e, &e->sv_feat, (size_t)n_images * ENC_FEAT));
-        SPDM_TRY(enc_alloc(e, &e->sv_x3, (size_t)n_images * ENC_X3));
-        e->sv_cap = n_images;
-    }
-    const int chunk = std::min<int>(n_images, ENC_CHUNK);
-    for (int i0 = 0; i0 < n_images; i0 += chunk) {
-        const int m = std::min(chunk, n_images - i0);
-        float* feat = e->sv_feat + (size_t)i0 * ENC_FEAT;
-        HIP_TRY(launch_encoder_train_convs(d_images + (size_t)i0 * 3 * 96 * 96, e->w1, e->b1, e->w2, e->b2, e->w3, e->b3, feat,
-                                           e->sv_x3 + (size_t)i0 * ENC_X3, m, s));
-        const LinW lin{e->wl, nullptr, e->bl, ENC_FEAT, ENC_LATENT};
-        HIP_TRY(launch_gemm(linear_args(AffineSrc{feat, ENC_FEAT}, m, 0, lin, /*split=*/false, /*sw=*/0, EPI_BIAS,
-                                        d_latent + (size_t)i0 * ENC_LATENT), s));
+    SPDM_TRY(e->train_state(s,
+        [&](Recorder& R) -> int {
+            SPDM_TRY(e->alloc(&e->wg_part, FRAME_WG_FLOATS));
+            SPDM_TRY(e->alloc(&e->c1_part, (size_t)encoder_conv1_wgrad_blocks(FRAME_CHUNK) * 208));
+            // the transposed copies the data gradients read: dx = dy W is the forward GEMM on W^T ([N = in][K = out], k contiguous)
+            e->w2T = R.transposed(e->off[2], 32, 64);                         // (32, 16*4)  -> [64][32]
+            e->w3T = R.transposed(e->off[4], 64, 128);                        // (64, 32*4)  -> [128][64]
+            e->wlT = R.transposed(e->off[6], FRAME_LATENT, FRAME_FEAT);       // (128, 9216) -> [9216][128]
+            return SPDM_OK;
+        },
+        [&](float* T) -> int {
+            for (int k = 0; k < 8; ++k)
+                HIP_TRY(hipMemcpyAsync(T + e->off[k], e->*ENC_TENSORS[k], e->numel[k] * sizeof(float), hipMemcpyDeviceToDevice, s));
+            return SPDM_OK;
+        }));
+    SPDM_TRY(e->grow(&e->sv_cap, n_images, {{&e->sv_feat, FRAME_FEAT}, {&e->sv_x3, ENC_X3}}));
+    SPDM_TRY(frame_chunks(n_images, [&](int i0, int m) -> int {
+        const float* img = d_images + (size_t)i0 * FRAME_PIX;
+        float *feat = e->sv_feat + (size_t)i0 * FRAME_FEAT, *x3 = e->sv_x3 + (size_t)i0 * ENC_X3;
+        HIP_TRY(launch_encoder_train_convs(img, e->w1, e->b1, e->w2, e->b2, e->w3, e->b3, feat, x3, m, s));
+        HIP_TRY(frame_linear(feat, m, e->wl, e->bl, FRAME_FEAT, FRAME_LATENT, d_latent + (size_t)i0 * FRAME_LATENT, s));
         // the saved maps' ReLU masks from a float64 evaluation (after the GEMM has read feat: the latents are untouched)
-        HIP_TRY(launch_encoder_kinks(d_images + (size_t)i0 * 3 * 96 * 96, e->w1, e->b1, e->w2, e->b2, e->w3, e->b3, feat,
-                                     e->sv_x3 + (size_t)i0 * ENC_X3, m, s));
-    }
+        HIP_TRY(launch_encoder_kinks(img, e->w1, e->b1, e->w2, e->b2, e->w3, e->b3, feat, x3, m, s));
+        return SPDM_OK;
+    }));
     e->sv_n = n_images;
     if (!stream) HIP_TRY(hipStreamSynchronize(s));
     return SPDM_OK;
@@ -3696,114 +3793,77 @@ extern "C" int spdm_encoder_train_forward(spdm_encoder* e, int32_t n_images, con
 extern "C" int spdm_encoder_backward(spdm_encoder* e, int32_t n_images, const float* d_images, const float* d_grad_latent,
                                      float* d_grad, void* stream) {
     if (!e || !d_images || !d_grad_latent || !d_grad || n_images <= 0) return fail(SPDM_ERR_INVALID, "bad argument");
-    if (e->sv_n == 0) return fail(SPDM_ERR_STATE, "encoder_backward: no spdm_encoder_train_forward is pending");
-    if (e->sv_n != n_images)
-        return fail(SPDM_ERR_STATE, "encoder_backward: %d frames, the pending train_forward had %d", n_images, e->sv_n);
-    HIP_TRY(hipSetDevice(e->device));
+    SPDM_TRY(e->enter());
+    SPDM_TRY(e->pending(n_images));
     hipStream_t s = (hipStream_t)stream;
-    const int chunk = std::min<int>(n_images, ENC_CHUNK);
-    if (e->bw_cap < chunk) {
-        HIP_TRY(hipDeviceSynchronize());
-        enc_release(e, &e->bw_a);
-        enc_release(e, &e->bw_dz2);
-        enc_release(e, &e->bw_x2);
-        e->bw_cap = 0;
-        SPDM_TRY(enc_alloc(e, &e->bw_a, (size_t)chunk * ENC_X2));
-        SPDM_TRY(enc_alloc(e, &e->bw_dz2, (size_t)chunk * ENC_X3));
-        SPDM_TRY(enc_alloc(e, &e->bw_x2, (size_t)chunk * ENC_X2));
-        e->bw_cap = chunk;
-    }
+    SPDM_TRY(e->grow(&e->bw_cap, frame_chunk(n_images), {{&e->bw_a, ENC_X2}, {&e->bw_dz2, ENC_X3}, {&e->bw_x2, ENC_X2}}));
     e->sv_n = 0;                               // the saved maps serve ONE backward
-    HIP_TRY(hipMemsetAsync(d_grad, 0, e->blob_floats * sizeof(float), s));
-    for (int i0 = 0; i0 < n_images; i0 += chunk) {
-        const int m = std::min(chunk, n_images - i0);
-        float* G = i0 == 0 ? d_grad : e->g_tmp;           // a later chunk's gradient is added to the sum in chunk order
-        const float* img = d_images + (size_t)i0 * 3 * 96 * 96;
-        const float* g = d_grad_latent + (size_t)i0 * ENC_LATENT;
-        const float* feat = e->sv_feat + (size_t)i0 * ENC_FEAT;
+    SPDM_TRY(e->grad_chunks(n_images, d_grad, s, [&](int i0, int m, float* G) -> int {
+        const float* img = d_images + (size_t)i0 * FRAME_PIX;
+        const float* g = d_grad_latent + (size_t)i0 * FRAME_LATENT;
+        const float* feat = e->sv_feat + (size_t)i0 * FRAME_FEAT;
         const float* x3 = e->sv_x3 + (size_t)i0 * ENC_X3;
         // bw_a holds [dfeat | dz3 | dx3] (9216 + 9216 + 18432 floats per frame) and, once dz2 exists and those three are dead,
         // dx2 (36864 per frame) in the same place
-        float *dfeat = e->bw_a, *dz3 = dfeat + (size_t)m * ENC_FEAT, *dx3 = dz3 + (size_t)m * ENC_FEAT, *dx2 = e->bw_a;
+        float *dfeat = e->bw_a, *dz3 = dfeat + (size_t)m * FRAME_FEAT, *dx3 = dz3 + (size_t)m * FRAME_FEAT, *dx2 = e->bw_a;
         const long long M3 = (long long)m * 144, M2 = (long long)m * 576;
-        auto dgrad = [&](const float* dy, long long M, int K, int N, const float* wT, float* dx) {
-            return launch_gemm(gemm_args((int)M, 0, 1, 1, K, N, 1, 0, 0, nullptr, PRO_NONE, AffineSrc{dy, K}, 0, AffineSrc{}, wT,
-                                         nullptr, dx, N, EPI_PLAIN, nullptr), s);
-        };
         // ---- Linear(9216, 128) ----
-        HIP_TRY(launch_wgrad(g, ENC_LATENT, feat, ENC_FEAT, m, 1, 1, 1, ENC_LATENT, ENC_FEAT, 0, e->wg_part, ENC_WG_FLOATS,
+        HIP_TRY(launch_wgrad(g, FRAME_LATENT, feat, FRAME_FEAT, m, 1, 1, 1, FRAME_LATENT, FRAME_FEAT, 0, e->wg_part, FRAME_WG_FLOATS,
                              G + e->off[6], s));
-        HIP_TRY(launch_colsum(g, ENC_LATENT, m, ENC_LATENT, G + e->off[7], s));
-        HIP_TRY(dgrad(g, m, ENC_LATENT, ENC_FEAT, e->wlT, dfeat));
+        HIP_TRY(launch_colsum(g, FRAME_LATENT, m, FRAME_LATENT, G + e->off[7], s));
+        HIP_TRY(frame_dgrad(g, m, FRAME_LATENT, FRAME_FEAT, e->wlT, dfeat, s));
         // ---- conv 3: rows = windows, K = 32 * 4 ----
         HIP_TRY(launch_encoder_dz3(dfeat, feat, m, dz3, s));
-        HIP_TRY(launch_wgrad(dz3, 64, x3, 128, M3, 1, 1, 1, 64, 128, 0, e->wg_part, ENC_WG_FLOATS, G + e->off[4], s));
+        HIP_TRY(launch_wgrad(dz3, 64, x3, 128, M3, 1, 1, 1, 64, 128, 0, e->wg_part, FRAME_WG_FLOATS, G + e->off[4], s));
         HIP_TRY(launch_colsum(dz3, 64, M3, 64, G + e->off[5], s));
-        HIP_TRY(dgrad(dz3, M3, 64, 128, e->w3T, dx3));
+        HIP_TRY(frame_dgrad(dz3, M3, 64, 128, e->w3T, dx3, s));
         // ---- conv 2: K = 16 * 4, conv 1's map recomputed from the frames ----
         HIP_TRY(launch_encoder_dz2(dx3, x3, m, e->bw_dz2, s));
         HIP_TRY(launch_encoder_x2(img, e->w1, e->b1, m, e->bw_x2, s));
-        HIP_TRY(launch_wgrad(e->bw_dz2, 32, e->bw_x2, 64, M2, 1, 1, 1, 32, 64, 0, e->wg_part, ENC_WG_FLOATS, G + e->off[2], s));
+        HIP_TRY(launch_wgrad(e->bw_dz2, 32, e->bw_x2, 64, M2, 1, 1, 1, 32, 64, 0, e->wg_part, FRAME_WG_FLOATS, G + e->off[2], s));
         HIP_TRY(launch_colsum(e->bw_dz2, 32, M2, 32, G + e->off[3], s));
-        HIP_TRY(dgrad(e->bw_dz2, M2, 32, 64, e->w2T, dx2));
+        HIP_TRY(frame_dgrad(e->bw_dz2, M2, 32, 64, e->w2T, dx2, s));
         // ---- conv 1: K = 3 * 4, no data gradient (nothing is differentiated with respect to the frames) ----
         HIP_TRY(launch_encoder_conv1_wgrad(img, dx2, e->bw_x2, m, e->c1_part, G + e->off[0], G + e->off[1], s));
-        if (i0 != 0) {
-            for (int k = 0; k < 8; ++k) HIP_TRY(launch_add(e->g_tmp + e->off[k], e->numel[k], d_grad + e->off[k], s));
-        }
-    }
+        return SPDM_OK;
+    }));
     if (!stream) HIP_TRY(hipStreamSynchronize(s));
     return SPDM_OK;
 }
 
-// Replaces: optimizer.step() on self.vision_encoder's parameters (Adam(self.parameters()), models/diffusion_ddpm.py:115-116):
-// the new values go into the handle's tensors in place, and into the transposed copies of a handle that trains.
+// Replaces: optimizer.step() on self.vision_encoder's parameters (Adam(self.parameters()), models/diffusion_ddpm.py:115-116)
 extern "C" int spdm_encoder_update_weights(spdm_encoder* e, const float* d_blob, size_t n, void* stream) {
-    if (!e || !d_blob) return fail(SPDM_ERR_INVALID, "null argument");
-    if (n != e->blob_floats) return fail(SPDM_ERR_INVALID, "blob has %zu floats; the one given to spdm_encoder_create had %zu", n, e->blob_floats);
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t s = (hipStream_t)stream;
-    e->sv_n = 0;                               // saved maps belong to the old weights
-    SPDM_TRY(e->wt.relayout(d_blob, s));
-    if (!stream) HIP_TRY(hipStreamSynchronize(s));
-    return SPDM_OK;
+    return frame_update_weights(e, d_blob, n, stream);
 }
 
 // -------------------------------------------------------------------------------------------------
 // The autoencoder's decoder and its reconstruction training: Autoencoder.decoder of
 // models/encoder/autoencoder.py:23-32 under MSELoss(recon, batch) (:48,55-58).  Kernels and row layouts: decoder.hip.
-struct spdm_decoder {
-    int device = 0;
+struct spdm_decoder : FrameNet {
+    spdm_decoder() : FrameNet("decoder", "train_loss") {}
     // kernel-layout copies (WeightTable): the Linear with its rows in channels-last order q*64 + c, the transposed
     // convolutions as [ci][kk][co] -- which is also what their data gradients read -- and the biases
     float *w0 = nullptr, *b0 = nullptr, *w2 = nullptr, *b2 = nullptr, *w4 = nullptr, *b4 = nullptr, *w6 = nullptr, *b6 = nullptr;
-    float* h0 = nullptr;              // [chunk][9216] the Linear's output of the chunk in flight (spdm_decoder_forward)
-    int chunk = 0;
-    std::vector<void*> owned;
-    WeightTable wt;
-    long long off[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // blob offset of 0.weight 0.bias 2.* 4.* 6.* (the index given to create)
-    size_t numel[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    size_t blob_floats = 0;
+    float* h0 = nullptr;              // [fw_cap][9216] the Linear's output of the chunk in flight (spdm_decoder_forward)
+    int fw_cap = 0;
     // ---- training (nothing below is allocated by a handle that never trains) ----
     float* w0g = nullptr;             // [128][9216 as q*64 + c]: the weights of d loss / d latent
     float *sv_h0 = nullptr, *sv_a1 = nullptr, *sv_a2 = nullptr, *sv_recon = nullptr;   // saved maps of ALL frames
     double* sv_sq = nullptr;          // per-frame sums of squared errors
-    int sv_cap = 0, sv_n = 0;         // frames they hold room for / frames of the train_loss awaiting its backward
+    int sv_cap = 0;
     float *bw_dz4 = nullptr, *bw_dz2 = nullptr, *bw_dh0 = nullptr;     // backward scratch of one chunk
     int bw_cap = 0;
-    float *wg_part = nullptr, *wg_tmp = nullptr, *cs_part = nullptr, *w6_part = nullptr, *g_tmp = nullptr;
+    float *wg_part = nullptr, *wg_tmp = nullptr, *cs_part = nullptr, *w6_part = nullptr;
 };
-static constexpr int DEC_FEAT = 64 * 12 * 12, DEC_LATENT = 128, DEC_PIX = 3 * 96 * 96;
 static constexpr int DEC_A1 = 576 * 32, DEC_A2 = 2304 * 16;       // floats per frame of the two post-ReLU maps
-static constexpr size_t DEC_WG_FLOATS = (size_t)8 * DEC_LATENT * DEC_FEAT;     // launch_wgrad's partial slabs (0.weight: <= 7)
 // launch_wgrad cuts the rows of a thin layer into as many slabs as its budget holds, down to 64 rows each, and one thread per
 // weight then adds them; 256 slabs (one per compute unit) keep that sum short
 static constexpr size_t DEC_WG_SLABS = 256;
 
 // nn.Sequential indices of Autoencoder.decoder: 0 = Linear; 2, 4, 6 = ConvTranspose2d (in, out, kH, kW)
-static const struct { const char* name; std::vector<int> shape; } DEC_ITEMS[8] = {
-    {"0.weight", {DEC_FEAT, DEC_LATENT}}, {"0.bias", {DEC_FEAT}}, {"2.weight", {64, 32, 2, 2}}, {"2.bias", {32}},
-    {"4.weight", {32, 16, 2, 2}}, {"4.bias", {16}}, {"6.weight", {16, 3, 2, 2}}, {"6.bias", {3}}};
+static const FrameItem DEC_ITEMS[8] = {{"0.weight", {FRAME_FEAT, FRAME_LATENT}}, {"0.bias", {FRAME_FEAT}}, {"2.weight", {64, 32, 2, 2}},
+                                       {"2.bias", {32}}, {"4.weight", {32, 16, 2, 2}}, {"4.bias", {16}}, {"6.weight", {16, 3, 2, 2}},
+                                       {"6.bias", {3}}};
 
 // (cin, cout, 2, 2) at src as [ci][kk][co]
 static WeightCopy convt_copy(long long src, int cin, int cout) {
@@ -3812,34 +3872,14 @@ static WeightCopy convt_copy(long long src, int cin, int cout) {
     return c;
 }
 
-extern "C" void spdm_decoder_destroy(spdm_decoder* d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    for (void* p : d->owned) (void)hipFree(p);
-    delete d;
-}
+extern "C" void spdm_decoder_destroy(spdm_decoder* d) { frame_destroy(d); }
 
 extern "C" int spdm_decoder_create(int32_t device, const float* blob, size_t n, const spdm_tensor_index* index, int32_t n_index,
                                    spdm_decoder** out) {
-    if (!blob || !index || n_index <= 0 || !out) return fail(SPDM_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(device));
-    spdm_decoder* d = new spdm_decoder();
-    d->device = device;
-    d->blob_floats = n;
-    Recorder R(d->wt, n, index, n_index);
-    R.plan = false;                        // fp32 copies only
-    bool ok = true;
-    for (int k = 0; k < 8 && ok; ++k) {
-        const long long off = R.at(DEC_ITEMS[k].name, DEC_ITEMS[k].shape);
-        if (off < 0) { ok = false; break; }
-        d->off[k] = off;
-        d->numel[k] = 1;
-        for (int v : DEC_ITEMS[k].shape) d->numel[k] *= (size_t)v;
-    }
-    if (ok) {
+    const int rc = frame_create(DEC_ITEMS, device, blob, n, index, n_index, out, [](spdm_decoder* d, Recorder& R) {
         // Linear (9216, 128): row c*144 + q -> row q*64 + c, the bias likewise
-        WeightCopy w0 = Recorder::dense(d->off[0], 144, 64, DEC_LATENT);
-        w0.stride[0] = DEC_LATENT; w0.stride[1] = (long long)144 * DEC_LATENT; w0.stride[2] = 1;
+        WeightCopy w0 = Recorder::dense(d->off[0], 144, 64, FRAME_LATENT);
+        w0.stride[0] = FRAME_LATENT; w0.stride[1] = (long long)144 * FRAME_LATENT; w0.stride[2] = 1;
         WeightCopy b0 = Recorder::dense(d->off[1], 1, 144, 64);
         b0.stride[1] = 1; b0.stride[2] = 144;
         d->w0 = R.f32(w0);
@@ -3850,54 +3890,21 @@ extern "C" int spdm_decoder_create(int32_t device, const float* blob, size_t n, 
         d->b4 = R.f32(Recorder::dense(d->off[5], 1, 1, 16));
         d->w6 = R.f32(convt_copy(d->off[6], 16, 3));
         d->b6 = R.f32(Recorder::dense(d->off[7], 1, 1, 3));
-    }
-    DevBlob db;
-    int rc = R.err;
-    if (rc == SPDM_OK) rc = db.upload(blob, n);
-    if (rc == SPDM_OK) rc = R.finish(db.p);
-    if (rc != SPDM_OK) {
-        spdm_decoder_destroy(d);
-        return rc == SPDM_ERR_MISSING ? SPDM_ERR_INVALID : rc;      // (a decoder's eight names are its shape: one answer for both)
-    }
-    *out = d;
-    return SPDM_OK;
-}
-
-static int dec_alloc(spdm_decoder* d, float** p, size_t floats) {
-    void* q = nullptr;
-    if (hipMalloc(&q, floats * sizeof(float)) != hipSuccess) return fail(SPDM_ERR_NOMEM, "decoder workspace (%zu floats)", floats);
-    d->owned.push_back(q);
-    *p = (float*)q;
-    return SPDM_OK;
-}
-static void dec_release(spdm_decoder* d, float** p) {
-    if (!*p) return;
-    for (auto it = d->owned.begin(); it != d->owned.end(); ++it)
-        if (*it == (void*)*p) { d->owned.erase(it); break; }
-    (void)hipFree(*p);
-    *p = nullptr;
-}
-// h0 [m][9216] = latent W0^T + b0 on the exact fp32 MFMA path, columns in channels-last order
-static int dec_linear(spdm_decoder* d, const float* latent, int m, float* h0, hipStream_t s) {
-    const LinW lin{d->w0, nullptr, d->b0, DEC_LATENT, DEC_FEAT};
-    HIP_TRY(launch_gemm(linear_args(AffineSrc{latent, DEC_LATENT}, m, 0, lin, /*split=*/false, /*sw=*/0, EPI_BIAS, h0), s));
-    return SPDM_OK;
+    });
+    return rc == SPDM_ERR_MISSING ? SPDM_ERR_INVALID : rc;      // (a decoder's eight names are its shape: one answer for both)
 }
 
 extern "C" int spdm_decoder_forward(spdm_decoder* d, int32_t n, const float* d_latent, float* d_recon, void* stream) {
     if (!d || !d_latent || !d_recon || n <= 0) return fail(SPDM_ERR_INVALID, "bad argument");
-    HIP_TRY(hipSetDevice(d->device));
+    SPDM_TRY(d->enter());
     hipStream_t s = (hipStream_t)stream;
-    const int chunk = std::min<int>(n, ENC_CHUNK);
-    if (d->chunk < chunk) {             // (grown lazily; the old buffer stays owned until destroy: at most two sizes ever exist)
-        SPDM_TRY(dec_alloc(d, &d->h0, (size_t)chunk * DEC_FEAT));
-        d->chunk = chunk;
-    }
-    for (int i0 = 0; i0 < n; i0 += chunk) {
-        const int m = std::min(chunk, n - i0);
-        SPDM_TRY(dec_linear(d, d_latent + (size_t)i0 * DEC_LATENT, m, d->h0, s));
-        HIP_TRY(launch_decoder_convs(d->h0, d->w2, d->b2, d->w4, d->b4, d->w6, d->b6, d_recon + (size_t)i0 * DEC_PIX, m, s));
-    }
+    SPDM_TRY(d->grow(&d->fw_cap, frame_chunk(n), {{&d->h0, FRAME_FEAT}}));
+    SPDM_TRY(frame_chunks(n, [&](int i0, int m) -> int {
+        // h0 [m][9216] = latent W0^T + b0, columns in channels-last order
+        HIP_TRY(frame_linear(d_latent + (size_t)i0 * FRAME_LATENT, m, d->w0, d->b0, FRAME_LATENT, FRAME_FEAT, d->h0, s));
+        HIP_TRY(launch_decoder_convs(d->h0, d->w2, d->b2, d->w4, d->b4, d->w6, d->b6, d_recon + (size_t)i0 * FRAME_PIX, m, s));
+        return SPDM_OK;
+    }));
     if (!stream) HIP_TRY(hipStreamSynchronize(s));
     return SPDM_OK;
 }
@@ -3905,63 +3912,46 @@ extern "C" int spdm_decoder_forward(spdm_decoder* d, int32_t n, const float* d_l
 extern "C" int spdm_decoder_train_loss(spdm_decoder* d, int32_t n, const float* d_latent, const float* d_target, float* d_recon,
                                        float* d_loss, void* stream) {
     if (!d || !d_latent || !d_target || !d_loss || n <= 0) return fail(SPDM_ERR_INVALID, "bad argument");
-    HIP_TRY(hipSetDevice(d->device));
+    SPDM_TRY(d->enter());
     hipStream_t s = (hipStream_t)stream;
     d->sv_n = 0;
-    if (!d->w0g) {
-        SPDM_TRY(dec_alloc(d, &d->wg_part, DEC_WG_FLOATS));
-        SPDM_TRY(dec_alloc(d, &d->wg_tmp, (size_t)DEC_FEAT * DEC_LATENT));
-        SPDM_TRY(dec_alloc(d, &d->cs_part, (size_t)decoder_colsum_slabs(ENC_CHUNK) * DEC_FEAT));      // (the widest: 0.bias)
-        SPDM_TRY(dec_alloc(d, &d->w6_part, (size_t)ENC_CHUNK * 208));
-        SPDM_TRY(dec_alloc(d, &d->g_tmp, d->blob_floats));
-        // d loss / d latent = dh0 W0 is the forward GEMM on [N = 128][K = 9216], k in h0's column order q*64 + c
-        Recorder R(d->wt, d->blob_floats);
-        R.plan = false;
-        WeightCopy g = Recorder::dense(d->off[0], DEC_LATENT, 144, 64);
-        g.stride[0] = 1; g.stride[1] = DEC_LATENT; g.stride[2] = (long long)144 * DEC_LATENT;
-        float* const w0g = R.f32(g);
-        SPDM_TRY(R.err);
-        SPDM_TRY(d->wt.upload(false));
-        // the handle keeps no blob: the weights go back to their blob offsets in g_tmp (scratch until a backward pass) through
-        // the inverse permutations, and laying that out again fills the new copy
-        float* const T = d->g_tmp;
-        HIP_TRY(launch_decoder_unperm_linear(d->w0, T + d->off[0], s));
-        HIP_TRY(launch_decoder_colsum(d->b0, DEC_FEAT, 1, DEC_FEAT, 1, d->cs_part, T + d->off[1], s));      // (one row: a permutation)
-        HIP_TRY(launch_decoder_unperm_conv(d->w2, 64, 32, T + d->off[2], s));
-        HIP_TRY(launch_decoder_unperm_conv(d->w4, 32, 16, T + d->off[4], s));
-        HIP_TRY(launch_decoder_unperm_conv(d->w6, 16, 3, T + d->off[6], s));
-        const float* const bias[3] = {d->b2, d->b4, d->b6};
-        for (int k = 0; k < 3; ++k)
-            HIP_TRY(hipMemcpyAsync(T + d->off[3 + 2 * k], bias[k], d->numel[3 + 2 * k] * sizeof(float), hipMemcpyDeviceToDevice, s));
-        SPDM_TRY(d->wt.relayout(T, s));
-        d->w0g = w0g;
-    }
-    if (d->sv_cap < n) {
-        HIP_TRY(hipDeviceSynchronize());      // (an earlier call's kernels may still read the buffers being replaced)
-        dec_release(d, &d->sv_h0); dec_release(d, &d->sv_a1); dec_release(d, &d->sv_a2); dec_release(d, &d->sv_recon);
-        dec_release(d, (float**)&d->sv_sq);
-        d->sv_cap = 0;
-        SPDM_TRY(dec_alloc(d, &d->sv_h0, (size_t)n * DEC_FEAT));
-        SPDM_TRY(dec_alloc(d, &d->sv_a1, (size_t)n * DEC_A1));
-        SPDM_TRY(dec_alloc(d, &d->sv_a2, (size_t)n * DEC_A2));
-        SPDM_TRY(dec_alloc(d, &d->sv_recon, (size_t)n * DEC_PIX));
-        SPDM_TRY(dec_alloc(d, (float**)&d->sv_sq, (size_t)n * 2));
-        d->sv_cap = n;
-    }
-    const int chunk = std::min<int>(n, ENC_CHUNK);
-    for (int i0 = 0; i0 < n; i0 += chunk) {
-        const int m = std::min(chunk, n - i0);
-        float* h0 = d->sv_h0 + (size_t)i0 * DEC_FEAT;
-        SPDM_TRY(dec_linear(d, d_latent + (size_t)i0 * DEC_LATENT, m, h0, s));
-        HIP_TRY(launch_decoder_train_convs(h0, d->w2, d->b2, d->w4, d->b4, d->w6, d->b6, d->sv_recon + (size_t)i0 * DEC_PIX,
-                                           d_target + (size_t)i0 * DEC_PIX, d->sv_a1 + (size_t)i0 * DEC_A1,
-                                           d->sv_a2 + (size_t)i0 * DEC_A2, d->sv_sq + i0, m, s));
+    SPDM_TRY(d->train_state(s,
+        [&](Recorder& R) -> int {
+            SPDM_TRY(d->alloc(&d->wg_part, FRAME_WG_FLOATS));
+            SPDM_TRY(d->alloc(&d->wg_tmp, (size_t)FRAME_FEAT * FRAME_LATENT));
+            SPDM_TRY(d->alloc(&d->cs_part, (size_t)decoder_colsum_slabs(FRAME_CHUNK) * FRAME_FEAT));      // (the widest: 0.bias)
+            SPDM_TRY(d->alloc(&d->w6_part, (size_t)FRAME_CHUNK * 208));
+            // d loss / d latent = dh0 W0 is the forward GEMM on [N = 128][K = 9216], k in h0's column order q*64 + c
+            WeightCopy g = Recorder::dense(d->off[0], FRAME_LATENT, 144, 64);
+            g.stride[0] = 1; g.stride[1] = FRAME_LATENT; g.stride[2] = (long long)144 * FRAME_LATENT;
+            d->w0g = R.f32(g);
+            return SPDM_OK;
+        },
+        [&](float* T) -> int {            // through the inverse permutations
+            HIP_TRY(launch_decoder_unperm_linear(d->w0, T + d->off[0], s));
+            HIP_TRY(launch_decoder_colsum(d->b0, FRAME_FEAT, 1, FRAME_FEAT, 1, d->cs_part, T + d->off[1], s));      // (one row: a permutation)
+            HIP_TRY(launch_decoder_unperm_conv(d->w2, 64, 32, T + d->off[2], s));
+            HIP_TRY(launch_decoder_unperm_conv(d->w4, 32, 16, T + d->off[4], s));
+            HIP_TRY(launch_decoder_unperm_conv(d->w6, 16, 3, T + d->off[6], s));
+            const float* const bias[3] = {d->b2, d->b4, d->b6};
+            for (int k = 0; k < 3; ++k)
+                HIP_TRY(hipMemcpyAsync(T + d->off[3 + 2 * k], bias[k], d->numel[3 + 2 * k] * sizeof(float), hipMemcpyDeviceToDevice, s));
+            return SPDM_OK;
+        }));
+    SPDM_TRY(d->grow(&d->sv_cap, n, {{&d->sv_h0, FRAME_FEAT}, {&d->sv_a1, DEC_A1}, {&d->sv_a2, DEC_A2}, {&d->sv_recon, FRAME_PIX},
+                                     {(float**)&d->sv_sq, 2}}));
+    SPDM_TRY(frame_chunks(n, [&](int i0, int m) -> int {
+        const float* lat = d_latent + (size_t)i0 * FRAME_LATENT;
+        float *h0 = d->sv_h0 + (size_t)i0 * FRAME_FEAT, *a1 = d->sv_a1 + (size_t)i0 * DEC_A1, *a2 = d->sv_a2 + (size_t)i0 * DEC_A2;
+        HIP_TRY(frame_linear(lat, m, d->w0, d->b0, FRAME_LATENT, FRAME_FEAT, h0, s));
+        HIP_TRY(launch_decoder_train_convs(h0, d->w2, d->b2, d->w4, d->b4, d->w6, d->b6, d->sv_recon + (size_t)i0 * FRAME_PIX,
+                                           d_target + (size_t)i0 * FRAME_PIX, a1, a2, d->sv_sq + i0, m, s));
         // the saved maps' ReLU masks from a float64 evaluation (the reconstruction and the loss stay the fp32 forward's)
-        HIP_TRY(launch_decoder_kinks(d_latent + (size_t)i0 * DEC_LATENT, d->w0, d->b0, d->w2, d->b2, d->w4, d->b4,
-                                     d->sv_a1 + (size_t)i0 * DEC_A1, d->sv_a2 + (size_t)i0 * DEC_A2, m, s));
-    }
+        HIP_TRY(launch_decoder_kinks(lat, d->w0, d->b0, d->w2, d->b2, d->w4, d->b4, a1, a2, m, s));
+        return SPDM_OK;
+    }));
     HIP_TRY(launch_decoder_loss(d->sv_sq, n, d_loss, s));
-    if (d_recon) HIP_TRY(hipMemcpyAsync(d_recon, d->sv_recon, (size_t)n * DEC_PIX * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (d_recon) HIP_TRY(hipMemcpyAsync(d_recon, d->sv_recon, (size_t)n * FRAME_PIX * sizeof(float), hipMemcpyDeviceToDevice, s));
     d->sv_n = n;
     if (!stream) HIP_TRY(hipStreamSynchronize(s));
     return SPDM_OK;
@@ -3970,33 +3960,20 @@ extern "C" int spdm_decoder_train_loss(spdm_decoder* d, int32_t n, const float* 
 extern "C" int spdm_decoder_backward(spdm_decoder* d, int32_t n, const float* d_latent, const float* d_target, float* d_grad,
                                      float* d_grad_latent, void* stream) {
     if (!d || !d_latent || !d_target || !d_grad || !d_grad_latent || n <= 0) return fail(SPDM_ERR_INVALID, "bad argument");
-    if (d->sv_n == 0) return fail(SPDM_ERR_STATE, "decoder_backward: no spdm_decoder_train_loss is pending");
-    if (d->sv_n != n) return fail(SPDM_ERR_STATE, "decoder_backward: %d frames, the pending train_loss had %d", n, d->sv_n);
-    HIP_TRY(hipSetDevice(d->device));
+    SPDM_TRY(d->enter());
+    SPDM_TRY(d->pending(n));
     hipStream_t s = (hipStream_t)stream;
-    const int chunk = std::min<int>(n, ENC_CHUNK);
-    if (d->bw_cap < chunk) {
-        HIP_TRY(hipDeviceSynchronize());
-        dec_release(d, &d->bw_dz4); dec_release(d, &d->bw_dz2); dec_release(d, &d->bw_dh0);
-        d->bw_cap = 0;
-        SPDM_TRY(dec_alloc(d, &d->bw_dz4, (size_t)chunk * DEC_A2));
-        SPDM_TRY(dec_alloc(d, &d->bw_dz2, (size_t)chunk * DEC_A1));
-        SPDM_TRY(dec_alloc(d, &d->bw_dh0, (size_t)chunk * DEC_FEAT));
-        d->bw_cap = chunk;
-    }
+    SPDM_TRY(d->grow(&d->bw_cap, frame_chunk(n), {{&d->bw_dz4, DEC_A2}, {&d->bw_dz2, DEC_A1}, {&d->bw_dh0, FRAME_FEAT}}));
     d->sv_n = 0;                               // the saved maps serve ONE backward
-    const float scale = (float)(2.0 / ((double)n * DEC_PIX));          // d mean((recon - target)^2) / d recon = scale (recon - target)
-    HIP_TRY(hipMemsetAsync(d_grad, 0, d->blob_floats * sizeof(float), s));
-    for (int i0 = 0; i0 < n; i0 += chunk) {
-        const int m = std::min(chunk, n - i0);
-        float* G = i0 == 0 ? d_grad : d->g_tmp;           // a later chunk's gradient is added to the sum in chunk order
-        const float* lat = d_latent + (size_t)i0 * DEC_LATENT;
-        const float* h0 = d->sv_h0 + (size_t)i0 * DEC_FEAT;
+    const float scale = (float)(2.0 / ((double)n * FRAME_PIX));        // d mean((recon - target)^2) / d recon = scale (recon - target)
+    SPDM_TRY(d->grad_chunks(n, d_grad, s, [&](int i0, int m, float* G) -> int {
+        const float* lat = d_latent + (size_t)i0 * FRAME_LATENT;
+        const float* h0 = d->sv_h0 + (size_t)i0 * FRAME_FEAT;
         const float* a1 = d->sv_a1 + (size_t)i0 * DEC_A1;
         const float* a2 = d->sv_a2 + (size_t)i0 * DEC_A2;
         const long long M1 = (long long)m * 144, M2 = (long long)m * 576;
         // ---- ConvTranspose2d(16, 3) + Sigmoid + MSE: dz6 from recon and target, 6.weight / 6.bias, dz4 ----
-        HIP_TRY(launch_decoder_bwd6(d->sv_recon + (size_t)i0 * DEC_PIX, d_target + (size_t)i0 * DEC_PIX, a2, d->w6, scale, m,
+        HIP_TRY(launch_decoder_bwd6(d->sv_recon + (size_t)i0 * FRAME_PIX, d_target + (size_t)i0 * FRAME_PIX, a2, d->w6, scale, m,
                                     d->bw_dz4, d->w6_part, G + d->off[6], G + d->off[7], s));
         // ---- ConvTranspose2d(32, 16): rows r2, dz4 [M2][64], x = a1 [M2][32] ----
         HIP_TRY(launch_wgrad(a1, 32, d->bw_dz4, 64, M2, 1, 1, 1, 32, 64, 0, d->wg_part, DEC_WG_SLABS * 32 * 64, d->wg_tmp, s));
@@ -4007,33 +3984,21 @@ extern "C" int spdm_decoder_backward(spdm_decoder* d, int32_t n, const float* d_
         HIP_TRY(launch_wgrad(h0, 64, d->bw_dz2, 128, M1, 1, 1, 1, 64, 128, 0, d->wg_part, DEC_WG_SLABS * 64 * 128, d->wg_tmp, s));
         HIP_TRY(launch_decoder_unperm_conv(d->wg_tmp, 64, 32, G + d->off[2], s));
         HIP_TRY(launch_decoder_colsum(d->bw_dz2, 128, M1, 32, 4, d->cs_part, G + d->off[3], s));
-        HIP_TRY(launch_gemm(gemm_args((int)M1, 0, 1, 1, 128, 64, 1, 0, 0, nullptr, PRO_NONE, AffineSrc{d->bw_dz2, 128}, 0, AffineSrc{},
-                                      d->w2, nullptr, d->bw_dh0, 64, EPI_PLAIN, nullptr), s));      // (no activation follows the Linear)
+        HIP_TRY(frame_dgrad(d->bw_dz2, M1, 128, 64, d->w2, d->bw_dh0, s));      // (no activation follows the Linear)
         // ---- Linear(128, 9216): dh0 [m][9216] in channels-last columns ----
-        HIP_TRY(launch_wgrad(d->bw_dh0, DEC_FEAT, lat, DEC_LATENT, m, 1, 1, 1, DEC_FEAT, DEC_LATENT, 0, d->wg_part, DEC_WG_FLOATS,
-                             d->wg_tmp, s));
+        HIP_TRY(launch_wgrad(d->bw_dh0, FRAME_FEAT, lat, FRAME_LATENT, m, 1, 1, 1, FRAME_FEAT, FRAME_LATENT, 0, d->wg_part,
+                             FRAME_WG_FLOATS, d->wg_tmp, s));
         HIP_TRY(launch_decoder_unperm_linear(d->wg_tmp, G + d->off[0], s));
-        HIP_TRY(launch_decoder_colsum(d->bw_dh0, DEC_FEAT, m, DEC_FEAT, 1, d->cs_part, G + d->off[1], s));
-        HIP_TRY(launch_gemm(gemm_args(m, 0, 1, 1, DEC_FEAT, DEC_LATENT, 1, 0, 0, nullptr, PRO_NONE, AffineSrc{d->bw_dh0, DEC_FEAT}, 0,
-                                      AffineSrc{}, d->w0g, nullptr, d_grad_latent + (size_t)i0 * DEC_LATENT, DEC_LATENT, EPI_PLAIN,
-                                      nullptr), s));
-        if (i0 != 0) {
-            for (int k = 0; k < 8; ++k) HIP_TRY(launch_add(d->g_tmp + d->off[k], d->numel[k], d_grad + d->off[k], s));
-        }
-    }
+        HIP_TRY(launch_decoder_colsum(d->bw_dh0, FRAME_FEAT, m, FRAME_FEAT, 1, d->cs_part, G + d->off[1], s));
+        HIP_TRY(frame_dgrad(d->bw_dh0, m, FRAME_FEAT, FRAME_LATENT, d->w0g, d_grad_latent + (size_t)i0 * FRAME_LATENT, s));
+        return SPDM_OK;
+    }));
     if (!stream) HIP_TRY(hipStreamSynchronize(s));
     return SPDM_OK;
 }
 
 extern "C" int spdm_decoder_update_weights(spdm_decoder* d, const float* d_blob, size_t n, void* stream) {
-    if (!d || !d_blob) return fail(SPDM_ERR_INVALID, "null argument");
-    if (n != d->blob_floats) return fail(SPDM_ERR_INVALID, "blob has %zu floats; the one given to spdm_decoder_create had %zu", n, d->blob_floats);
-    HIP_TRY(hipSetDevice(d->device));
-    hipStream_t s = (hipStream_t)stream;
-    d->sv_n = 0;                               // saved maps belong to the old weights
-    SPDM_TRY(d->wt.relayout(d_blob, s));
-    if (!stream) HIP_TRY(hipStreamSynchronize(s));
-    return SPDM_OK;
+    return frame_update_weights(d, d_blob, n, stream);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -4790,7 +4755,7 @@ extern "C" int spdm_op_frame(spdm_op_frame_args* p) {
     uint64_t scratch = 0;                          // floats of the hook's own scratch
     // (the loss is formed once over ALL frames of a call, not per chunk)
     const bool frames = q.op <= SPDM_OPF_ENC_CONV1_WGRAD || (q.op >= SPDM_OPF_DEC_CONVS && q.op <= SPDM_OPF_DEC_DGRAD4 && q.op != SPDM_OPF_DEC_LOSS);
-    if (frames && (d[0] < 1 || d[0] > ENC_CHUNK)) return E.bad("op %d: n = %lld outside [1, %d] frames", q.op, (long long)d[0], ENC_CHUNK);
+    if (frames && (d[0] < 1 || d[0] > FRAME_CHUNK)) return E.bad("op %d: n = %lld outside [1, %d] frames", q.op, (long long)d[0], FRAME_CHUNK);
     const int64_t n = d[0];
     int wCo = 0, wCi = 0;
     WgradSlabs ws{0, 0, 0};
@@ -4799,31 +4764,31 @@ extern "C" int spdm_op_frame(spdm_op_frame_args* p) {
         case SPDM_OPF_ENC_CONVS:
         case SPDM_OPF_ENC_KINKS: {
             if (q.op == SPDM_OPF_ENC_CONVS && d[1] > 1) return E.bad("enc_convs: train must be 0 or 1");
-            const uint64_t w[9] = {E.mul({n, DEC_PIX}), 16 * 3 * 4, 16, 32 * 16 * 4, 32, 64 * 32 * 4, 64, E.mul({n, ENC_FEAT}), E.mul({n, ENC_X3})};
+            const uint64_t w[9] = {E.mul({n, FRAME_PIX}), 16 * 3 * 4, 16, 32 * 16 * 4, 32, 64 * 32 * 4, 64, E.mul({n, FRAME_FEAT}), E.mul({n, ENC_X3})};
             for (int i = 0; i < 9; ++i) need[i] = w[i];
             nbuf = 9;
             if (q.op == SPDM_OPF_ENC_CONVS && d[1] == 0) absent[8] = true;
             break;
         }
-        case SPDM_OPF_ENC_X2: need[0] = E.mul({n, DEC_PIX}); need[1] = 192; need[2] = 16; need[3] = E.mul({n, ENC_X2}); nbuf = 4; break;
-        case SPDM_OPF_ENC_DZ3: need[0] = need[1] = need[2] = E.mul({n, ENC_FEAT}); nbuf = 3; break;
+        case SPDM_OPF_ENC_X2: need[0] = E.mul({n, FRAME_PIX}); need[1] = 192; need[2] = 16; need[3] = E.mul({n, ENC_X2}); nbuf = 4; break;
+        case SPDM_OPF_ENC_DZ3: need[0] = need[1] = need[2] = E.mul({n, FRAME_FEAT}); nbuf = 3; break;
         case SPDM_OPF_ENC_DZ2: need[0] = need[1] = need[2] = E.mul({n, ENC_X3}); nbuf = 3; break;
         case SPDM_OPF_ENC_CONV1_WGRAD:
-            need[0] = E.mul({n, DEC_PIX}); need[1] = need[2] = E.mul({n, ENC_X2}); need[3] = 192; need[4] = 16; nbuf = 5;
-            scratch = (uint64_t)encoder_conv1_wgrad_blocks((int)n) * 208;           // c1_part: [blocks(ENC_CHUNK)][208] in the product
+            need[0] = E.mul({n, FRAME_PIX}); need[1] = need[2] = E.mul({n, ENC_X2}); need[3] = 192; need[4] = 16; nbuf = 5;
+            scratch = (uint64_t)encoder_conv1_wgrad_blocks((int)n) * 208;           // c1_part: [blocks(FRAME_CHUNK)][208] in the product
             break;
         case SPDM_OPF_DEC_CONVS: {
             if (d[1] > 1) return E.bad("dec_convs: train must be 0 or 1");
-            const uint64_t w[7] = {E.mul({n, DEC_FEAT}), 64 * 4 * 32, 32, 32 * 4 * 16, 16, 16 * 4 * 3, 3};
+            const uint64_t w[7] = {E.mul({n, FRAME_FEAT}), 64 * 4 * 32, 32, 32 * 4 * 16, 16, 16 * 4 * 3, 3};
             for (int i = 0; i < 7; ++i) need[i] = w[i];
-            need[7] = need[8] = E.mul({n, DEC_PIX}); need[9] = E.mul({n, DEC_A1}); need[10] = E.mul({n, DEC_A2}); nbuf = 11;
+            need[7] = need[8] = E.mul({n, FRAME_PIX}); need[9] = E.mul({n, DEC_A1}); need[10] = E.mul({n, DEC_A2}); nbuf = 11;
             if (d[1] == 0) absent[8] = absent[9] = absent[10] = true;
             else need_sq = (uint64_t)n;
             if (d[1] == 0 && q.d_sq) return E.bad("dec_convs: d_sq must be null without train");
             break;
         }
         case SPDM_OPF_DEC_KINKS: {
-            const uint64_t w[9] = {E.mul({n, DEC_LATENT}), (uint64_t)DEC_FEAT * DEC_LATENT, DEC_FEAT, 64 * 4 * 32, 32, 32 * 4 * 16, 16,
+            const uint64_t w[9] = {E.mul({n, FRAME_LATENT}), (uint64_t)FRAME_FEAT * FRAME_LATENT, FRAME_FEAT, 64 * 4 * 32, 32, 32 * 4 * 16, 16,
                                    E.mul({n, DEC_A1}), E.mul({n, DEC_A2})};
             for (int i = 0; i < 9; ++i) need[i] = w[i];
             nbuf = 9;
@@ -4835,8 +4800,8 @@ extern "C" int spdm_op_frame(spdm_op_frame_args* p) {
             break;
         case SPDM_OPF_DEC_BWD6:
             if (!std::isfinite(q.scale)) return E.bad("dec_bwd6: scale is not finite");
-            need[0] = need[1] = E.mul({n, DEC_PIX}); need[2] = need[4] = E.mul({n, DEC_A2}); need[3] = need[5] = 192; need[6] = 3; nbuf = 7;
-            scratch = (uint64_t)n * 208;                                          // w6_part: [ENC_CHUNK][208] in the product
+            need[0] = need[1] = E.mul({n, FRAME_PIX}); need[2] = need[4] = E.mul({n, DEC_A2}); need[3] = need[5] = 192; need[6] = 3; nbuf = 7;
+            scratch = (uint64_t)n * 208;                                          // w6_part: [FRAME_CHUNK][208] in the product
             break;
         case SPDM_OPF_DEC_DGRAD4:
             need[0] = E.mul({n, 576, 64}); need[1] = need[3] = E.mul({n, DEC_A1}); need[2] = 32 * 64; nbuf = 4;
@@ -4844,13 +4809,13 @@ extern "C" int spdm_op_frame(spdm_op_frame_args* p) {
         case SPDM_OPF_DEC_COLSUM: {
             const int64_t M = d[0], C = d[1], fold = d[2];
             if (M < 1) return E.bad("dec_colsum: M must be positive");
-            if (!((fold == 4 && (C == 64 || C == 128)) || (fold == 1 && C == DEC_FEAT)))
+            if (!((fold == 4 && (C == 64 || C == 128)) || (fold == 1 && C == FRAME_FEAT)))
                 return E.bad("dec_colsum: (C, fold) must be (64, 4), (128, 4) or (9216, 1)");
-            const int64_t max_m = (int64_t)ENC_CHUNK * (fold == 1 ? 1 : C == 64 ? 576 : 144);
+            const int64_t max_m = (int64_t)FRAME_CHUNK * (fold == 1 ? 1 : C == 64 ? 576 : 144);
             if (M > max_m) return E.bad("dec_colsum: M = %lld beyond the %lld rows of one chunk", (long long)M, (long long)max_m);
             need[0] = E.mul({M, C}); need[1] = (uint64_t)(C / fold); nbuf = 2;
             scratch = (uint64_t)decoder_colsum_slabs(M) * (uint64_t)C;
-            if (scratch > (uint64_t)decoder_colsum_slabs(ENC_CHUNK) * DEC_FEAT) return E.bad("dec_colsum: the slabs exceed cs_part");
+            if (scratch > (uint64_t)decoder_colsum_slabs(FRAME_CHUNK) * FRAME_FEAT) return E.bad("dec_colsum: the slabs exceed cs_part");
             break;
         }
         case SPDM_OPF_DEC_UNPERM_CONV:
@@ -4858,22 +4823,22 @@ extern "C" int spdm_op_frame(spdm_op_frame_args* p) {
                 return E.bad("dec_unperm_conv: (cin, cout) must be (64, 32), (32, 16) or (16, 3)");
             need[0] = need[1] = (uint64_t)(d[0] * d[1] * 4); nbuf = 2;
             break;
-        case SPDM_OPF_DEC_UNPERM_LINEAR: need[0] = need[1] = (uint64_t)DEC_FEAT * DEC_LATENT; nbuf = 2; break;
+        case SPDM_OPF_DEC_UNPERM_LINEAR: need[0] = need[1] = (uint64_t)FRAME_FEAT * FRAME_LATENT; nbuf = 2; break;
         case SPDM_OPF_ADD:
             if (d[0] < 1) return E.bad("add: n must be positive");
             need[0] = need[1] = (uint64_t)d[0]; nbuf = 2;
             break;
         case SPDM_OPF_FRAME_WGRAD: {
-            static const struct { int Co, Ci, rows_per_frame; } W[6] = {{ENC_LATENT, ENC_FEAT, 1}, {64, 128, 144}, {32, 64, 576},
-                                                                        {32, 64, 576}, {64, 128, 144}, {DEC_FEAT, DEC_LATENT, 1}};
+            static const struct { int Co, Ci, rows_per_frame; } W[6] = {{FRAME_LATENT, FRAME_FEAT, 1}, {64, 128, 144}, {32, 64, 576},
+                                                                        {32, 64, 576}, {64, 128, 144}, {FRAME_FEAT, FRAME_LATENT, 1}};
             if (d[0] < 1) return E.bad("frame_wgrad: M must be positive");
             if (d[1] > 5) return E.bad("frame_wgrad: which = %lld outside [0, 5]", (long long)d[1]);
             const int k = (int)d[1];
             wCo = W[k].Co; wCi = W[k].Ci;
-            const size_t budgets[6] = {ENC_WG_FLOATS, ENC_WG_FLOATS, ENC_WG_FLOATS, DEC_WG_SLABS * 32 * 64, DEC_WG_SLABS * 64 * 128, DEC_WG_FLOATS};
+            const size_t budgets[6] = {FRAME_WG_FLOATS, FRAME_WG_FLOATS, FRAME_WG_FLOATS, DEC_WG_SLABS * 32 * 64, DEC_WG_SLABS * 64 * 128, FRAME_WG_FLOATS};
             budget = budgets[k];
-            if (d[0] > (int64_t)ENC_CHUNK * W[k].rows_per_frame)
-                return E.bad("frame_wgrad: M = %lld beyond the %lld rows of one chunk", (long long)d[0], (long long)ENC_CHUNK * W[k].rows_per_frame);
+            if (d[0] > (int64_t)FRAME_CHUNK * W[k].rows_per_frame)
+                return E.bad("frame_wgrad: M = %lld beyond the %lld rows of one chunk", (long long)d[0], (long long)FRAME_CHUNK * W[k].rows_per_frame);
             need[0] = E.mul({d[0], wCo}); need[1] = E.mul({d[0], wCi}); need[2] = (uint64_t)wCo * wCi; nbuf = 3;
             if (!E.ok) break;
             ws = wgrad_slabs((long long)d[0], 1, wCo, wCi, budget);

@@ -52,18 +52,21 @@ def encoder_state_dict_from(sd, prefix: str = "vision_encoder."):
     return None
 
 
-class VisionEncoder:
-    """``VisionEncoder(state_dict)(images)`` == ``Autoencoder().encoder(images)`` (eval mode), images ``(N,3,96,96)``
-    fp32 on the GPU -> ``(N,128)``."""
+class _FrameHandle:
+    """What ``VisionEncoder`` and ``autoencoder.Decoder`` share: one ``spdm_<_what>_*`` handle (csrc/spdm_api.hip's
+    FrameNet) made from the ``_keys`` / ``_shapes`` tensors of a state_dict, its weights as one flat parameter in the
+    packed layout, the flat gradient of the last ``backward`` and the inputs of the pending ``_pass``."""
+
+    _keys, _shapes, _what, _pass = (), {}, "", ""
 
     def __init__(self, state_dict, device: int = 0):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
-            raise RuntimeError("VisionEncoder needs a visible MI355X (HIP device); there is no CPU fallback")
-        sd = {k: state_dict[k] for k in ENCODER_KEYS}
-        for k, shp in ENCODER_SHAPES.items():
+            raise RuntimeError(f"{type(self).__name__} needs a visible MI355X (HIP device); there is no CPU fallback")
+        sd = {k: state_dict[k] for k in self._keys}
+        for k, shp in self._shapes.items():
             if tuple(sd[k].shape) != shp:
-                raise ValueError(f"encoder tensor {k}: shape {tuple(sd[k].shape)}, expected {shp}")
+                raise ValueError(f"{self._what} tensor {k}: shape {tuple(sd[k].shape)}, expected {shp}")
         self.device = torch.device("cuda", device)
         blob, idx = pack_state_dict(sd)
         self._index = [(e.name.decode(), int(e.offset), tuple(e.shape[d] for d in range(e.ndim))) for e in idx]
@@ -71,15 +74,15 @@ class VisionEncoder:
         self._n_floats = int(blob.size)
         self._flat = None                      # flat_parameter()
         self._grad = None                      # flat gradient of the last backward
-        self._frames = None                    # frames of the pending train_forward
+        self._pending = None                   # inputs of the pending training forward
         h = ctypes.c_void_p()
-        _lib.check(self.lib.spdm_encoder_create(device, blob.ctypes.data_as(ctypes.c_void_p), blob.size, idx, len(idx),
-                                                ctypes.byref(h)), "spdm_encoder_create")
+        _lib.check(getattr(self.lib, f"spdm_{self._what}_create")(device, blob.ctypes.data_as(ctypes.c_void_p), blob.size, idx,
+                                                                 len(idx), ctypes.byref(h)), f"spdm_{self._what}_create")
         self._h = h
 
     def close(self):
         if getattr(self, "_h", None):
-            self.lib.spdm_encoder_destroy(self._h)
+            getattr(self.lib, f"spdm_{self._what}_destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -91,58 +94,25 @@ class VisionEncoder:
     def eval(self):
         return self
 
-    def __call__(self, images: torch.Tensor) -> torch.Tensor:
-        if images.dim() != 4 or tuple(images.shape[1:]) != (3, 96, 96):
-            raise ValueError(f"expected (N,3,96,96) frames, got {tuple(images.shape)}")
-        x = images.to(self.device, torch.float32).contiguous()
-        out = torch.empty(x.shape[0], 128, device=self.device, dtype=torch.float32)
-        if x.shape[0] == 0:
-            return out
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(self.lib.spdm_encoder_forward(self._h, x.shape[0], ctypes.c_void_p(x.data_ptr()),
-                                                 ctypes.c_void_p(out.data_ptr()), stream), "spdm_encoder_forward")
-        return out
-
-    # ---- joint training ----
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def train_forward(self, images: torch.Tensor) -> torch.Tensor:
-        """``__call__``'s latents, bit for bit, with the activations kept for ONE following ``backward``."""
-        if images.dim() != 4 or tuple(images.shape[1:]) != (3, 96, 96) or images.shape[0] == 0:
-            raise ValueError(f"expected (N,3,96,96) frames with N > 0, got {tuple(images.shape)}")
-        x = images.to(self.device, torch.float32).contiguous()
-        out = torch.empty(x.shape[0], LATENT_DIM, device=self.device, dtype=torch.float32)
-        _lib.check(self.lib.spdm_encoder_train_forward(self._h, x.shape[0], ctypes.c_void_p(x.data_ptr()),
-                                                       ctypes.c_void_p(out.data_ptr()), self._stream()),
-                   "spdm_encoder_train_forward")
-        self._frames = x
-        return out
+    def _run(self, entry: str, *args):
+        """``spdm_<_what>_<entry>(handle, *args, stream)`` on the current stream, tensors passed as their device pointers."""
+        args = [ctypes.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args]
+        name = f"spdm_{self._what}_{entry}"
+        _lib.check(getattr(self.lib, name)(self._h, *args, self._stream()), name)
 
-    def backward(self, grad_latent: torch.Tensor) -> torch.Tensor:
-        """d loss / d parameters as ONE flat tensor in the packed layout (``grads()`` are views of it), from
-        d loss / d latents ``(N,128)`` of the frames last given to ``train_forward``.  Sets ``flat_parameter().grad``."""
-        n = 0 if self._frames is None else self._frames.shape[0]
-        g = grad_latent.to(self.device, torch.float32).contiguous()
-        if n and tuple(g.shape) != (n, LATENT_DIM):
-            raise ValueError(f"grad_latent {tuple(g.shape)}; the pending train_forward had {n} frames")
-        if not n:                              # (the library answers SPDM_ERR_STATE; pass valid pointers to reach that answer)
-            n, frames = max(int(g.shape[0]), 1), g
-        else:
-            frames = self._frames
-        flat = torch.empty(self._n_floats, device=self.device, dtype=torch.float32)
-        _lib.check(self.lib.spdm_encoder_backward(self._h, n, ctypes.c_void_p(frames.data_ptr()), ctypes.c_void_p(g.data_ptr()),
-                                                  ctypes.c_void_p(flat.data_ptr()), self._stream()), "spdm_encoder_backward")
-        self._frames = None
+    def _backward_done(self, flat: torch.Tensor) -> None:
+        self._pending = None
         self._grad = flat
         if self._flat is not None:
             self._flat.grad = flat
-        return flat
 
     def grads(self):
         """state_dict name -> gradient of the last ``backward`` (torch layout, views of the flat gradient)."""
         if self._grad is None:
-            raise RuntimeError("no gradients: call train_forward and backward first")
+            raise RuntimeError(f"no gradients: call {self._pass} and backward first")
         return {name: self._grad[off:off + int(torch.Size(shape).numel())].view(shape) for name, off, shape in self._index}
 
     def flat_parameter(self) -> torch.nn.Parameter:
@@ -155,13 +125,12 @@ class VisionEncoder:
 
     def update_weights(self, dev_blob: torch.Tensor) -> None:
         """Put new values (a device blob in the packed layout, e.g. ``flat_parameter().detach()``) into the handle in
-        place; a pending ``train_forward`` is dropped."""
+        place; a pending training forward is dropped."""
         b = dev_blob.detach()
         if b.device != self.device or b.dtype != torch.float32 or not b.is_contiguous() or b.numel() != self._n_floats:
             raise ValueError(f"expected a contiguous fp32 blob of {self._n_floats} floats on {self.device}")
-        _lib.check(self.lib.spdm_encoder_update_weights(self._h, ctypes.c_void_p(b.data_ptr()), b.numel(), self._stream()),
-                   "spdm_encoder_update_weights")
-        self._frames = None
+        self._run("update_weights", b, b.numel())
+        self._pending = None
         if self._flat is None:
             self._blob = b.cpu().numpy()
         elif b.data_ptr() != self._flat.data_ptr():      # values from elsewhere: the parameter follows the handle
@@ -173,3 +142,48 @@ class VisionEncoder:
         host = self._flat.detach().cpu().numpy() if self._flat is not None else self._blob
         return {name: torch.from_numpy(host[off:off + int(torch.Size(shape).numel())].reshape(shape).copy())
                 for name, off, shape in self._index}
+
+
+class VisionEncoder(_FrameHandle):
+    """``VisionEncoder(state_dict)(images)`` == ``Autoencoder().encoder(images)`` (eval mode), images ``(N,3,96,96)``
+    fp32 on the GPU -> ``(N,128)``."""
+
+    _keys, _shapes, _what, _pass = ENCODER_KEYS, ENCODER_SHAPES, "encoder", "train_forward"
+
+    def __call__(self, images: torch.Tensor) -> torch.Tensor:
+        if images.dim() != 4 or tuple(images.shape[1:]) != (3, 96, 96):
+            raise ValueError(f"expected (N,3,96,96) frames, got {tuple(images.shape)}")
+        x = images.to(self.device, torch.float32).contiguous()
+        out = torch.empty(x.shape[0], 128, device=self.device, dtype=torch.float32)
+        if x.shape[0]:
+            self._run("forward", x.shape[0], x, out)
+        return out
+
+    # ---- joint training (DESIGN.md 8.6) ----
+    def train_forward(self, images: torch.Tensor) -> torch.Tensor:
+        """``__call__``'s latents, bit for bit, with the activations kept for ONE following ``backward``."""
+        if images.dim() != 4 or tuple(images.shape[1:]) != (3, 96, 96) or images.shape[0] == 0:
+            raise ValueError(f"expected (N,3,96,96) frames with N > 0, got {tuple(images.shape)}")
+        x = images.to(self.device, torch.float32).contiguous()
+        out = torch.empty(x.shape[0], LATENT_DIM, device=self.device, dtype=torch.float32)
+        self._run("train_forward", x.shape[0], x, out)
+        self._pending = x
+        return out
+
+    def backward(self, grad_latent: torch.Tensor) -> torch.Tensor:
+        """d loss / d parameters as ONE flat tensor in the packed layout (``grads()`` are views of it), from
+        d loss / d latents ``(N,128)`` of the frames last given to ``train_forward``.  Sets ``flat_parameter().grad``."""
+        n = 0 if self._pending is None else self._pending.shape[0]
+        g = grad_latent.to(self.device, torch.float32).contiguous()
+        if n and tuple(g.shape) != (n, LATENT_DIM):
+            raise ValueError(f"grad_latent {tuple(g.shape)}; the pending train_forward had {n} frames")
+        if not n:                              # (the library answers SPDM_ERR_STATE; pass valid pointers to reach that answer)
+            n, frames = max(int(g.shape[0]), 1), g
+        else:
+            frames = self._pending
+        flat = torch.empty(self._n_floats, device=self.device, dtype=torch.float32)
+        self._run("backward", n, frames, g, flat)
+        self._backward_done(flat)
+        return flat
+
+
