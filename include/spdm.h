@@ -853,6 +853,13 @@ size_t spdm_device_bytes(const spdm_handle* h);
 int  spdm_profile_enable(spdm_handle* h, int32_t on);
 int  spdm_profile_read(spdm_handle* h, int64_t* launches, double* total_ms, double* total_flops);
 
+/* Micro-benchmark of ONE fused conv_chain.hip launch on synthetic data (tools/bench_chain.py; kernel tuning only, not on the
+ * product path): B samples of HW rows through the n_layers 3-tap layers of widths chan[0 .. n_layers], the plan's GELU pattern.
+ * debug: ablation bits (1: no MFMAs -- timing only, wrong results), honoured by diagnostic builds (SPDM_DIAG) only.
+ * *ms_out: ms per launch. */
+int  spdm_bench_chain(int32_t device, int32_t B, int32_t HW, int32_t n_layers, const int32_t* chan, int32_t iters,
+                      int32_t debug, double* ms_out);
+
 /* Micro-benchmark of ONE implicit-GEMM launch shape on synthetic data (tools/bench_gemm.py; kernel tuning
  * only, not on the product path): conv taps in {1,3,9} over (B, H*W, Cin) -> (B, H*W, Cout).  pro: 0 none,
  * 1 GroupNorm, 2 GroupNorm+GELU; epi: 0 GN stats, 1 bias, 2 bias+GELU, 3 bias+residual; debug: ablation bits. */
@@ -1023,9 +1030,11 @@ int  spdm_debug_pooled_epilogue_launches(void);
  *   [12..41] sa1..6, five values each: {fused, crop, outc, in, tail} -- fused 1: sa_fused64 takes the block, crop 1: for the
  *            tokens outc reads only, outc 1: with outc in its epilogue; fused 0: in = 0 in_proj GEMM, 1 sa_qkv, 2 sa_head (core
  *            included) feeds the attention core, tail = 1 sa_tail, 0 the three GEMMs after it.
+ *   [42..43] the level-3 convolution chains (conv_chain.hip): down block 3, the bottleneck -- 1: one fused launch, 0: one
+ *            launch per convolution
  * All zero for a handle without attention (sa values) or a SPDM_FLAG_SIMPLE_UNET handle (everything).  SPDM_ERR_STATE before
  * spdm_load_weights, SPDM_ERR_INVALID for a null handle, B outside [1, max_batch] or cap < SPDM_PLAN_ROUTES_INTS. */
-#define SPDM_PLAN_ROUTES_INTS 42
+#define SPDM_PLAN_ROUTES_INTS 44
 int  spdm_debug_plan_routes(const spdm_handle* h, int32_t B, int32_t* out, int32_t cap);
 
 /* Op-level test hook: d_y = GELU(d_x) evaluated with the device erf that the conv prologues use
@@ -1067,6 +1076,40 @@ typedef struct {
 } spdm_op_gemm_args;
 
 int  spdm_op_gemm(spdm_op_gemm_args* args);
+
+/* Op-level test hook: ONE fused launch of csrc/conv_chain.hip -- a list of 3-tap convolutions of a width-1 map (split
+ * precision) with the GroupNorm(1, C) [-> GELU] between two layers applied inside the kernel -- on caller-supplied tensors,
+ * synchronously.  The weights are laid out by the weight loader's own code (the fragment-order split copies).  Not on the
+ * product path.
+ *   B samples of HW rows (HW a power of two in [4, 64]); chan[0 .. n_layers]: the widths, input first (multiples of 64, <= 512);
+ *   layer i maps chan[i] -> chan[i + 1] channels with the HOST weight h_weight[i], laid out [3][chan[i + 1]][chan[i]];
+ *   d_gamma[i] / d_beta[i] (i >= 1, DEVICE, chan[i] floats): the GroupNorm pending on layer i's input; gelu[i] != 0: GELU
+ *   follows it.  Entry 0 of the three is not read: d_src is a finished tensor.
+ *   d_dst: the raw output of the last layer, [B x HW][dst_ld]; d_stats: its GroupNorm partials, [sample][slots][2] fp64 =
+ *   {sum x, sum x^2} in slot 0 (stats m_tile 64, one n-tile), stats_cap in doubles; unwritten slots read as NaN.
+ *   out: {workgroups, slots, stats m_tile, stats n_tiles}.
+ * SPDM_ERR_INVALID, nothing launched, for shapes the kernel's predicate refuses or weights outside the split format's range. */
+#define SPDM_OP_CHAIN_MAX_LAYERS 8
+typedef struct {
+    int32_t B, HW, n_layers;
+    int32_t chan[SPDM_OP_CHAIN_MAX_LAYERS + 1];
+    int32_t gelu[SPDM_OP_CHAIN_MAX_LAYERS];
+    const float* d_src;  int32_t src_ld;
+    const float* h_weight[SPDM_OP_CHAIN_MAX_LAYERS];
+    const float* d_gamma[SPDM_OP_CHAIN_MAX_LAYERS];
+    const float* d_beta[SPDM_OP_CHAIN_MAX_LAYERS];
+    float* d_dst;  int32_t dst_ld;
+    double* d_stats;  size_t stats_cap;
+    int32_t out[4];
+} spdm_op_chain_args;
+
+int  spdm_op_chain(spdm_op_chain_args* args);
+
+/* Host-only test hook (no GPU call): how many fused conv_chain.hip launches this process has enqueued from a plan (down block 3
+ * and the bottleneck of a U-Net evaluation: two per evaluation where both routes are taken).  A captured step counts once, not
+ * per replay.  SPDM_TUNE25 (read once per process) selects the sites: bit 0 down block 3, bit 1 the bottleneck, bit 2 takes
+ * them at any batch (otherwise only from 256 blocks of 64 rows on); 0 keeps it at 0. */
+int  spdm_debug_conv_chain_launches(void);
 
 /* Op-level test hook: ONE launch of the training pass (launch_* of csrc/train.hip, train_attn.hip, train_simple.hip) exactly
  * as spdm_train_loss_grad calls it, on caller-supplied tensors, synchronously on the current device.  Not on the product path.

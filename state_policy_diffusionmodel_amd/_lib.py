@@ -40,6 +40,18 @@ class SpdmOpGemmArgs(ctypes.Structure):
                  ("out", c_int32 * 10)])
 
 
+OP_CHAIN_MAX_LAYERS = 8
+
+
+class SpdmOpChainArgs(ctypes.Structure):
+    """spdm_op_chain_args (include/spdm.h)."""
+    _fields_ = [("B", c_int32), ("HW", c_int32), ("n_layers", c_int32), ("chan", c_int32 * (OP_CHAIN_MAX_LAYERS + 1)),
+                ("gelu", c_int32 * OP_CHAIN_MAX_LAYERS), ("d_src", c_void_p), ("src_ld", c_int32),
+                ("h_weight", c_void_p * OP_CHAIN_MAX_LAYERS), ("d_gamma", c_void_p * OP_CHAIN_MAX_LAYERS),
+                ("d_beta", c_void_p * OP_CHAIN_MAX_LAYERS), ("d_dst", c_void_p), ("dst_ld", c_int32),
+                ("d_stats", c_void_p), ("stats_cap", c_size_t), ("out", c_int32 * 4)]
+
+
 # spdm_op_train op codes (include/spdm.h: SPDM_OPT_*), in enum order
 OP_TRAIN_OPS = ("wgrad", "wgrad_mapped", "colsum", "gn_stats", "gn_bwd", "film_bwd", "mse", "pool_bwd", "up_bwd", "mish_bwd",
                 "ln_fwd", "ln_bwd", "gelu_bwd", "attn_fwd_lse", "attn_bwd", "gn_bwd_mapped", "simple_tail_bwd", "silu_bwd")
@@ -276,6 +288,7 @@ SYMBOLS = {
     "spdm_adam_norm_index": (c_size_t, []),
     "spdm_op_gelu": (c_int32, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "spdm_op_gemm": (c_int32, [POINTER(SpdmOpGemmArgs)]),
+    "spdm_op_chain": (c_int32, [POINTER(SpdmOpChainArgs)]),
     "spdm_op_train": (c_int32, [POINTER(SpdmOpTrainArgs)]),
     "spdm_op_stream": (c_int32, [POINTER(SpdmOpStreamArgs)]),
     "spdm_op_frame": (c_int32, [POINTER(SpdmOpFrameArgs)]),
@@ -284,8 +297,10 @@ SYMBOLS = {
     "spdm_debug_whole_tiles": (c_int32, []),
     "spdm_debug_fused_upsample_launches": (c_int32, []),
     "spdm_debug_pooled_epilogue_launches": (c_int32, []),
+    "spdm_debug_conv_chain_launches": (c_int32, []),
     "spdm_debug_plan_routes": (c_int32, [c_void_p, c_int32, POINTER(c_int32), c_int32]),
-    "spdm_bench_gemm": (c_int32, [c_int32] * 12 + [POINTER(c_double)]),   # ms_out[2]: {ms per launch, max|split - fp32|}
+    "spdm_bench_gemm": (c_int32, [c_int32] * 12 + [POINTER(c_double)]),
+    "spdm_bench_chain": (c_int32, [c_int32] * 4 + [POINTER(c_int32), c_int32, c_int32, POINTER(c_double)]),   # ms_out[2]: {ms per launch, max|split - fp32|}
 }
 
 _lib = None

@@ -186,6 +186,31 @@ bool conv_wide_takes_upcat(const GemmArgs& a, const GemmGeom& g);
 int gemm_wide_upcat_launches();        // conv_gemm.hip: how many launches of this process launch_gemm sent that way (host-side count)
 hipError_t launch_conv_wide(const GemmArgs& a, const GemmGeom& g, hipStream_t s);
 
+// conv_chain.hip: a list of 3-tap convolutions of a width-1 map (split precision) run end to end by one 8-wave workgroup per
+// 64-row block, the GroupNorm [-> GELU] between two layers applied in LDS.  Layer i reads K channels and writes N; gamma / beta /
+// gelu describe the GroupNorm pending on the layer's INPUT (layer 0 reads a finished tensor: they are unused there).
+constexpr int CHAIN_MAX_LAYERS = 8;
+struct ChainLayer {
+    const float* wfrag;                // WL_FRAG copy of the [3][N][K] split weights (weight_layout.hip)
+    const float* gamma;  const float* beta;
+    int K, N, gelu;
+};
+struct ChainArgs {
+    const float* src;  int src_ld;     // [M][src_ld], finished
+    float* dst;        int dst_ld;     // raw output of the last layer
+    double* stats;     int slots;      // its GroupNorm partials, [sample][slots][2]: slot 0 written (StatsRef{m_tile = 64, n_tiles = 1})
+    int M, HW;                         // rows; rows per sample
+    int n_layers;
+    int debug;                         // DBG_NO_MFMA (diagnostic builds only; 0 in the product path)
+    ChainLayer layer[CHAIN_MAX_LAYERS];
+};
+constexpr int CHAIN_M_TILE = 64;
+// the shape rule (false: not here); chan: the n_layers + 1 widths, input first
+bool conv_chain_geometry(int M, int HW, int W, int taps, int split, int n_layers, const int* chan);
+int conv_chain_blocks(int M);
+double conv_chain_flops(const ChainArgs& a);       // the sum of gemm_flops of its layers
+hipError_t launch_conv_chain(const ChainArgs& a, hipStream_t s);
+
 // ---- streaming / small kernels (elementwise.hip) -------------------------------------------
 // first conv, Cin = 1, fused zero-padding of the (H0, D) trajectory to (Hp, Wp)
 // ... and, as the first kernel of a denoise step, the loop bookkeeping (adv: -2 none, -1 advance by one, >= 0 set the step)

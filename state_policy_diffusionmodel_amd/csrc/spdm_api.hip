@@ -1290,9 +1290,14 @@ static int stats_slots_reserved(int HW, int C, int slots) {
 // launches of this process whose epilogue also wrote the MaxPool2d(2) of their output (host-side count:
 // spdm_debug_pooled_epilogue_launches)
 static int g_pooled_epilogue_launches = 0;
+// fused conv_chain.hip launches of this process's plans (host-side count: spdm_debug_conv_chain_launches)
+static int g_conv_chain_launches = 0;
+// SPDM_TUNE25 where the environment does not set it: the sites (bit 0 down block 3, bit 1 the bottleneck) whose fused launch
+// measured faster than their per-layer launches at B = 4096
+constexpr int CHAIN_SITES_DEFAULT = 3;
 
 // The kernel routes of one U-Net evaluation: Ctx::choose_routes fills them in before the walk (plan_unet), which then only
-// allocates and launches; spdm_debug_plan_routes reports them field by field in this order (all int: 42 values).
+// allocates and launches; spdm_debug_plan_routes reports them field by field in this order (all int: 44 values).
 enum { POOL_KERNEL = 0, POOL_READ_THROUGH = 1, POOL_BY_PRODUCER = 2 };   // pool_kernel | the consumer's PRO_POOL | the producer's epilogue
 enum { UP_UPCAT = 0, UP_READ_THROUGH = 1, UP_TWO_SOURCE = 2 };           // upcat kernel | the consumer's PRO_UPCAT | upsample + two-source conv
 enum { FILM_APPLY = 0, FILM_COEF = 1, FILM_LOCAL = 2 };                  // film_apply | film_coef | coefficients evaluated in the consumers
@@ -1306,7 +1311,10 @@ struct PlanRoutes {
     int up[3];                 // UP_* of up block i + 1
     int film[6];               // FILM_* of the tail of down1..3, up1..3
     AttnRoute sa[6];           // sa1..6 (all zero without attention: nothing is launched)
+    int chain[2];              // the level-3 convolutions of down block 3 / of the bottleneck as ONE conv_chain.hip launch each
 };
+// one layer of a fused chain: the convolution and the GroupNorm [-> GELU] pending on its input (gamma null: a finished input)
+struct ChainStep { const ConvW* w; const float* gamma; const float* beta; int gelu; };
 
 struct Ctx {
     spdm_handle* h;
@@ -1481,6 +1489,32 @@ struct Ctx {
             a.in = head ? SA_IN_HEAD : (tail_kernels && (!loaded || w.qkv_wf)) ? SA_IN_QKV : SA_IN_GEMM;
             a.tail = tail_kernels && (!loaded || w.tail_wf[0]);
         }
+        // -- the level-3 convolution chains (conv_chain.hip): the four convolutions of down block 3 and the six of the bottleneck
+        //    as one launch each, the intermediate tensors never leaving LDS.  Only where the handle keeps no intermediate (no
+        //    debug taps), every layer has its split copies, the shape rule holds (3-tap layers on a width-1 map) and the launch
+        //    fills the chip: 64-row blocks, one per CU in a single round, so from 256 blocks on.  SPDM_TUNE25 (read once per
+        //    process): bit 0 / 1 = the site, bit 2 = at any batch (tests).  The sizing pass asks for both states (sized->chain). --
+        {
+            const int tune = spdm_tune(25, CHAIN_SITES_DEFAULT);
+            const int M3 = Bg() * HWl(3);
+            const bool fills = M3 >= 256 * CHAIN_M_TILE || (tune & 4);
+            const DoubleConvW* site[2][3] = {{&h->down[2].dc1, &h->down[2].dc2, nullptr}, {&h->bot[0], &h->bot[1], &h->bot[2]}};
+            for (int i = 0; i < 2; ++i) {
+                int chan[CHAIN_MAX_LAYERS + 1], n = 0;
+                bool ok = h->split && !keep && ((tune >> i) & 1) && fills && (sized ? sized->chain[i] != 0 : loaded);
+                chan[0] = site[i][0]->first.cin;
+                ok = ok && chan[0] == (i ? h->down[2].cout : h->down[1].cout);
+                for (int d = 0; d < 3 && site[i][d]; ++d)
+                    for (const ConvW* w : {&site[i][d]->first, &site[i][d]->second}) {
+                        ok = ok && w->taps == 3 && w->cin == chan[n] && (sized || (w->ws && w->wf));
+                        chan[++n] = w->cout;
+                    }
+                // (both sites read a FINISHED tensor -- the pooled output of sa2's block tail, the output of sa3's -- which is what
+                //  Ctx::conv_chain's first layer takes (no prologue) and checks; an encoder tail that left a GroupNorm pending on
+                //  either would have to switch that site off here)
+                r.chain[i] = ok && conv_chain_geometry(M3, HWl(3), Wl(3), 3, 1, n, chan);
+            }
+        }
         // -- the fused sources of a Down / UpSample block's first convolution (read-through, two-source) --
         const bool src_ok = h->split && !(sw & SW_NO_FUSED_SRC) && !keep;
         const int C_x1 = h->inc.second.cout;
@@ -1488,7 +1522,8 @@ struct Ctx {
             const ConvW& wn = h->down[i].dc1.first;
             const int C_in = i ? h->down[i - 1].cout : C_x1;
             // MaxPool2d(2) read through by that convolution (PRO_POOL: conv_skinny at small batch; it keeps priority)
-            const bool through = src_ok && h->d_partial != nullptr && C_in == wn.cin &&
+            // (not pool 3 in front of a fused down block 3: the chain reads a materialised map)
+            const bool through = src_ok && h->d_partial != nullptr && C_in == wn.cin && !(i == 2 && r.chain[0]) &&
                 (sized ? sized->pool[i] == POOL_READ_THROUGH
                        : loaded && wn.ws && wn.wf && gemm_takes_fused_source(conv_args(wn, i + 1, 1, PRO_POOL, AffineSrc{nullptr, C_in}, 0, AffineSrc{}, nullptr)));
             // MaxPool2d(2) written by the epilogue of the kernel that produces the tensor being pooled: no pool_kernel launch, the
@@ -1560,6 +1595,33 @@ struct Ctx {
         if (!keep_in) free(in);
         Value out = conv(mid, w.second, level, /*gelu=*/true, w.gamma, w.beta);
         free(mid);
+        return out;
+    }
+    // A list of level-3 convolutions as ONE launch (conv_chain.hip; routes.chain): reads the finished tensor `in`, writes the last
+    // layer's raw output and its GroupNorm partials (out_gamma / out_beta pending on it) -- what the per-layer launches leave
+    // behind, without their intermediate tensors.  Inside prof_begin / prof_end it counts as one launch of the layers' FLOPs.
+    Value conv_chain(const Value& in, const ChainStep* st, int n, const float* out_gamma, const float* out_beta, int level) {
+        GemmGeom g{};
+        g.st_m_tile = CHAIN_M_TILE; g.st_n_tiles = 1;
+        Value out = conv_out(*st[n - 1].w, level, g, out_gamma, out_beta);
+        if (err || dry) return out;
+        ChainArgs a{};
+        a.src = in.t.p; a.src_ld = in.t.C; a.dst = out.t.p; a.dst_ld = out.t.C; a.stats = out.st.p; a.slots = out.st.ref.slots;
+        a.M = B * HWl(level); a.HW = HWl(level); a.n_layers = n;
+        for (int i = 0; i < n; ++i) {
+            if (st[i].w->wf == nullptr) { err = fail(SPDM_ERR_STATE, "plan: conv chain weights missing"); return out; }
+            a.layer[i] = ChainLayer{st[i].w->wf, st[i].gamma, st[i].beta, st[i].w->cin, st[i].w->cout, st[i].gelu};
+        }
+        if (in.t.C != a.layer[0].K || in.pending_gn()) { err = fail(SPDM_ERR_INVALID, "plan: conv chain reads a finished tensor of %d channels", a.layer[0].K); return out; }
+        const bool solo = h->prof && h->prof_open < 0;
+        if (solo) prof_begin();
+        if (h->prof && h->prof_open >= 0) {
+            h->prof_evts[h->prof_open].flops += conv_chain_flops(a);
+            h->prof_evts[h->prof_open].launches += 1;
+        }
+        check(launch_conv_chain(a, s), "conv3x1 chain");
+        if (solo) prof_end();
+        ++g_conv_chain_launches;
         return out;
     }
     // The FIRST convolution of a Down / UpSample block reading its input THROUGH the resampling op (GemmArgs "fused sources":
@@ -1783,7 +1845,7 @@ static int plan_unet(Ctx& c, const float* x, bool use_cond, Tensor* feat_out, co
         const int lin = i, lout = i + 1;
         // `cur` stays alive: it is a skip connection
         const DoubleConvW& dc1 = h->down[i].dc1;
-        Value mid;             // the block's first convolution, of MaxPool2d(2)(cur)
+        Value mid, fused;      // the block's first convolution, of MaxPool2d(2)(cur); or (routes.chain) all four of the block
         if (r.pool[i] == POOL_READ_THROUGH) {        // read through by that convolution (small grids)
             mid = c.conv_fused(PRO_POOL, cur, nullptr, dc1, lout);
             c.prof_begin();
@@ -1795,12 +1857,24 @@ static int plan_unet(Ctx& c, const float* x, bool use_cond, Tensor* feat_out, co
             if (!by_producer && !c.err && !c.dry)
                 c.check(launch_pool(c.asrc(cur), p.t.p, B, c.Hl(lin), c.Wl(lin), c.s), "maxpool");
             c.prof_begin();
-            mid = c.conv(p, dc1.first, lout, /*gelu=*/false, dc1.gamma, dc1.beta, nullptr, (by_producer && cur.pending_gn()) ? &cur : nullptr);
+            if (i == 2 && r.chain[0]) {           // down block 3's four convolutions as one launch
+                const DoubleConvW& dc2 = h->down[i].dc2;
+                const ChainStep st[4] = {{&dc1.first, nullptr, nullptr, 0}, {&dc1.second, dc1.gamma, dc1.beta, 1},
+                                         {&dc2.first, dc1.gamma, dc1.beta, 0}, {&dc2.second, dc2.gamma, dc2.beta, 1}};
+                fused = c.conv_chain(p, st, 4, dc2.gamma, dc2.beta, lout);
+            } else {
+                mid = c.conv(p, dc1.first, lout, /*gelu=*/false, dc1.gamma, dc1.beta, nullptr, (by_producer && cur.pending_gn()) ? &cur : nullptr);
+            }
             c.free(p);
         }
-        Value a = c.conv(mid, dc1.second, lout, /*gelu=*/true, dc1.gamma, dc1.beta);
-        c.free(mid);
-        Value b2 = c.double_conv(a, h->down[i].dc2, lout);
+        Value b2;
+        if (i == 2 && r.chain[0]) {
+            b2 = fused;
+        } else {
+            Value a = c.conv(mid, dc1.second, lout, /*gelu=*/true, dc1.gamma, dc1.beta);
+            c.free(mid);
+            b2 = c.double_conv(a, h->down[i].dc2, lout);
+        }
         c.prof_end();
         const Tensor y = c.film_attention(b2, h->down[i], i, lout, use_cond, dn[i],
                                           (i < 2 && r.pool[i + 1] == POOL_BY_PRODUCER) ? &pooled[i + 1] : nullptr);
@@ -1811,9 +1885,19 @@ static int plan_unet(Ctx& c, const float* x, bool use_cond, Tensor* feat_out, co
     }
     // ---- bottleneck (:297-299) ----
     c.prof_begin();
-    Value b1 = c.double_conv(cur, h->bot[0], 3);
-    Value b2 = c.double_conv(b1, h->bot[1], 3);
-    Value x5 = c.double_conv(b2, h->bot[2], 3);         // pending GN
+    Value x5;                                           // pending GN
+    if (r.chain[1]) {                                   // the six convolutions as one launch
+        const DoubleConvW* b = h->bot;
+        const ChainStep st[6] = {{&b[0].first, nullptr, nullptr, 0}, {&b[0].second, b[0].gamma, b[0].beta, 1},
+                                 {&b[1].first, b[0].gamma, b[0].beta, 0}, {&b[1].second, b[1].gamma, b[1].beta, 1},
+                                 {&b[2].first, b[1].gamma, b[1].beta, 0}, {&b[2].second, b[2].gamma, b[2].beta, 1}};
+        x5 = c.conv_chain(cur, st, 6, b[2].gamma, b[2].beta, 3);
+        c.free(cur);
+    } else {
+        Value b1 = c.double_conv(cur, h->bot[0], 3);
+        Value b2 = c.double_conv(b1, h->bot[1], 3);
+        x5 = c.double_conv(b2, h->bot[2], 3);
+    }
     c.prof_end();
     c.tap_gn("x5", x5, 3);
     // ---- decoder: up1..3 (+ sa4..6) ----
@@ -1946,10 +2030,16 @@ static int plan_net(Ctx& c, const float* x, bool use_cond, Tensor* feat_out, con
 // by the caller)
 static int dry_plan_all(spdm_handle* h) {
     size_t peak = 0;
-    for (int k = 0; k < (h->simple ? 1 : 729); ++k) {         // (plan_simple materialises every resampling op)
+    // ... and, where the handle has fused level-3 chains (both sites switch at the same batch), with them on and off
+    for (int k = 0; k < (h->simple ? 1 : 2 * 729); ++k) {     // (plan_simple materialises every resampling op)
         PlanRoutes want{};
-        for (int op = 0, digits = k; op < 6; ++op, digits /= 3) (op < 3 ? want.pool[op] : want.up[op - 3]) = digits % 3;
+        for (int op = 0, digits = k % 729; op < 6; ++op, digits /= 3) (op < 3 ? want.pool[op] : want.up[op - 3]) = digits % 3;
+        want.chain[0] = want.chain[1] = k / 729;
         Ctx c{h, h->cfg.max_batch, nullptr, h->arena.dry};
+        if (k >= 729) {
+            const PlanRoutes got = c.choose_routes(&want);
+            if (!got.chain[0] && !got.chain[1]) break;         // no site on this handle: the walks above cover it
+        }
         h->arena.peak = 0;
         h->arena.reset();
         Tensor feat;
@@ -3535,6 +3625,78 @@ extern "C" int spdm_bench_gemm(int32_t device, int32_t B, int32_t H, int32_t W, 
     return SPDM_OK;
 }
 
+// Micro-benchmark of one fused conv_chain.hip launch on synthetic data (tools/bench_chain.py); not on the product path.
+// debug: DBG_NO_MFMA, honoured by SPDM_DIAG builds only.  *ms_out: average device time per launch (HIP events).
+extern "C" int spdm_bench_chain(int32_t device, int32_t B, int32_t HW, int32_t n_layers, const int32_t* chan, int32_t iters,
+                                int32_t debug, double* ms_out) {
+    if (!ms_out || !chan || iters < 1 || B < 1 || HW < 1 || n_layers < 1 || n_layers > CHAIN_MAX_LAYERS) return fail(SPDM_ERR_INVALID, "bad argument");
+    if ((long long)B * HW > INT32_MAX || !conv_chain_geometry(B * HW, HW, 1, 3, 1, n_layers, chan))
+        return fail(SPDM_ERR_INVALID, "bench_chain: the kernel does not take this chain");
+    HIP_TRY(hipSetDevice(device));
+    const int M = B * HW, n = n_layers;
+    size_t off[CHAIN_MAX_LAYERS], blob = 0, ngb = 0;
+    for (int i = 0; i < n; ++i) { off[i] = blob; blob += (size_t)3 * chan[i + 1] * chan[i]; ngb += 2 * (size_t)chan[i]; }
+    OwnWeights ow(blob);
+    OpDev dev;
+    struct Events {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    } ev;
+    float *src = nullptr, *dst = nullptr, *gb = nullptr;
+    double* st = nullptr;
+    const int slots = stats_slots(HW, CHAIN_M_TILE, 1);
+    SPDM_TRY(dev.alloc(&src, (size_t)M * chan[0] * 4));
+    SPDM_TRY(dev.alloc(&dst, (size_t)M * chan[n] * 4));
+    SPDM_TRY(dev.alloc(&gb, ngb * 4));
+    SPDM_TRY(dev.alloc(&st, (size_t)B * slots * 2 * 8));
+    float* wf[CHAIN_MAX_LAYERS] = {};
+    {   // deterministic pseudo-random fill, as spdm_bench_gemm: inputs ~U(-1, 1), weights at 1 / sqrt(fan-in), gains near 1
+        std::vector<float> hsrc((size_t)M * chan[0]), hw(blob), hgb(ngb);
+        unsigned x = 12345u;
+        auto rnd = [&]() { x = x * 1664525u + 1013904223u; return ((x >> 8) * (1.0f / 8388608.0f)) - 1.0f; };
+        for (auto& v : hsrc) v = rnd();
+        for (int i = 0; i < n; ++i) {
+            const float sc = 1.0f / std::sqrt(9.0f * chan[i]);
+            for (size_t k = off[i]; k < off[i] + (size_t)3 * chan[i + 1] * chan[i]; ++k) hw[k] = rnd() * sc;
+        }
+        for (size_t k = 0; k < ngb; ++k) hgb[k] = (k & 1) ? 0.1f * rnd() : 1.0f + 0.1f * rnd();
+        Recorder& R = ow.R;
+        auto walk = [&]() {
+            for (int i = 0; i < n; ++i) {
+                const WeightCopy v = Recorder::dense((long long)off[i], 3, chan[i + 1], chan[i]);
+                char name[32];
+                snprintf(name, sizeof(name), "weight%d", i);
+                wf[i] = R.split(v, chan[i], name) ? R.frag(v, 3, chan[i + 1], chan[i]) : nullptr;
+            }
+            return R.err;
+        };
+        SPDM_TRY(ow.lay_out(hw.data(), walk));
+        HIP_TRY(hipMemcpy(src, hsrc.data(), hsrc.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(gb, hgb.data(), ngb * 4, hipMemcpyHostToDevice));
+    }
+    ChainArgs a{};
+    a.src = src; a.src_ld = chan[0]; a.dst = dst; a.dst_ld = chan[n]; a.stats = st; a.slots = slots; a.M = M; a.HW = HW; a.n_layers = n;
+    a.debug = debug;
+    const float* g = gb;
+    for (int i = 0; i < n; ++i, g += 2 * chan[i - 1]) {
+        if (!wf[i]) return OwnWeights::outside("bench_chain", "weights", "unreachable for these weights");
+        a.layer[i] = ChainLayer{wf[i], i ? g : nullptr, i ? g + chan[i] : nullptr, chan[i], chan[i + 1], i & 1};      // the plan's GELU pattern
+    }
+    HIP_TRY(hipEventCreate(&ev.a));
+    HIP_TRY(hipEventCreate(&ev.b));
+    hipError_t e = launch_conv_chain(a, nullptr);
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = launch_conv_chain(a, nullptr);
+    if (e == hipSuccess) e = hipEventRecord(ev.a, nullptr);
+    for (int i = 0; i < iters && e == hipSuccess; ++i) e = launch_conv_chain(a, nullptr);
+    if (e == hipSuccess) e = hipEventRecord(ev.b, nullptr);
+    if (e == hipSuccess) e = hipEventSynchronize(ev.b);
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev.a, ev.b);
+    if (e != hipSuccess) return fail(SPDM_ERR_HIP, "bench_chain: %s; device: %s", hipGetErrorString(e), hipGetErrorString(hipDeviceSynchronize()));
+    *ms_out = ms / iters;
+    return SPDM_OK;
+}
+
 // -------------------------------------------------------------------------------------------------
 // The frame autoencoder (models/encoder/autoencoder.py): 96 x 96 frames <-> 128 latents through a [64][12][12] map.  FrameNet is
 // what its two handles share: the state, the allocations, create / update / destroy, the chunk walk, the pending-pass protocol
@@ -4084,6 +4246,7 @@ extern "C" int spdm_debug_whole_tiles(void) { return g_op_gemm_whole; }
 // ... how many launches of this process (plan or spdm_op_gemm; a captured step counts once) read the upsample through conv_wide's loader
 extern "C" int spdm_debug_fused_upsample_launches(void) { return gemm_wide_upcat_launches(); }
 extern "C" int spdm_debug_pooled_epilogue_launches(void) { return g_pooled_epilogue_launches; }
+extern "C" int spdm_debug_conv_chain_launches(void) { return g_conv_chain_launches; }
 extern "C" int spdm_debug_plan_routes(const spdm_handle* h, int32_t B, int32_t* out, int32_t cap) {
     static_assert(sizeof(PlanRoutes) == SPDM_PLAN_ROUTES_INTS * sizeof(int32_t), "PlanRoutes is the query's layout");
     spdm_handle* hm = const_cast<spdm_handle*>(h);       // (Ctx holds a mutable handle; choose_routes is const)
@@ -4291,6 +4454,64 @@ extern "C" int spdm_op_gemm(spdm_op_gemm_args* p) {
     g_op_gemm_whole = (r.kernel == ROUTE_WIDE) ? r.whole : 0;
     q.out[0] = r.kernel; q.out[1] = r.variant; q.out[2] = r.m_tile; q.out[3] = r.n_tile; q.out[4] = g.ksplit;
     q.out[5] = two ? 1 : 0; q.out[6] = fused ? 1 : 0; q.out[7] = g.slots; q.out[8] = g.st_m_tile; q.out[9] = g.st_n_tiles;
+    return SPDM_OK;
+}
+
+// op-level test hook: one launch_conv_chain as the plan builds it, on the caller's tensors (include/spdm.h)
+extern "C" int spdm_op_chain(spdm_op_chain_args* p) {
+    if (!p) return fail(SPDM_ERR_INVALID, "op_chain: null argument");
+    spdm_op_chain_args& q = *p;
+    for (int i = 0; i < 4; ++i) q.out[i] = -1;
+    static_assert(SPDM_OP_CHAIN_MAX_LAYERS == CHAIN_MAX_LAYERS, "the hook's table is the launch's");
+    OpCheck E("op_chain", 0);                             // (its one op)
+    if (q.B < 1 || q.HW < 1 || q.n_layers < 1 || q.n_layers > CHAIN_MAX_LAYERS) return E.bad("B, HW positive and 1 <= n_layers <= %d required", CHAIN_MAX_LAYERS);
+    const int n = q.n_layers;
+    const uint64_t M = E.mul({q.B, q.HW});
+    SPDM_TRY(E.fits());
+    if (!conv_chain_geometry((int)M, q.HW, 1, 3, 1, n, q.chan))
+        return E.bad("the kernel does not take this chain (HW a power of two in [4, 64], widths multiples of 64 up to 512)");
+    const int C0 = q.chan[0], CN = q.chan[n];
+    if (!q.d_src || !q.d_dst) return E.bad("src and dst are required");
+    if (q.src_ld < C0 || q.src_ld % 4 || q.dst_ld < CN || q.dst_ld % 4) return E.bad("bad leading dimension");
+    (void)E.strided(M, q.src_ld, C0);
+    (void)E.strided(M, q.dst_ld, CN);
+    SPDM_TRY(E.fits());
+    size_t blob = 0, off[CHAIN_MAX_LAYERS];
+    for (int i = 0; i < n; ++i) {
+        if (!q.h_weight[i]) return E.bad("h_weight[%d] is null", i);
+        if (i > 0 && (!q.d_gamma[i] || !q.d_beta[i])) return E.bad("layer %d: the GroupNorm on its input needs gamma and beta", i);
+        off[i] = blob;
+        blob += (size_t)3 * q.chan[i + 1] * q.chan[i];
+    }
+    const int slots = stats_slots(q.HW, CHAIN_M_TILE, 1);
+    SPDM_TRY(E.doubles("d_stats", q.d_stats, q.stats_cap, (uint64_t)q.B * slots * 2, false));
+    // the layers' weights as one blob, laid out as Loader::conv lays a 3-tap layer out (split copy: the range verdict; its
+    // fragment-order copy: what the kernel reads)
+    std::vector<float> hblob(blob);
+    for (int i = 0; i < n; ++i) memcpy(hblob.data() + off[i], q.h_weight[i], (size_t)3 * q.chan[i + 1] * q.chan[i] * sizeof(float));
+    OwnWeights ow(blob);
+    Recorder& R = ow.R;
+    float* wf[CHAIN_MAX_LAYERS] = {};
+    auto walk = [&]() {
+        for (int i = 0; i < n; ++i) {
+            const WeightCopy v = Recorder::dense((long long)off[i], 3, q.chan[i + 1], q.chan[i]);
+            char name[32];
+            snprintf(name, sizeof(name), "weight%d", i);
+            wf[i] = R.split(v, q.chan[i], name) ? R.frag(v, 3, q.chan[i + 1], q.chan[i]) : nullptr;
+        }
+        return R.err;
+    };
+    SPDM_TRY(ow.lay_out(hblob.data(), walk));
+    ChainArgs a{};
+    a.src = q.d_src; a.src_ld = q.src_ld; a.dst = q.d_dst; a.dst_ld = q.dst_ld; a.stats = q.d_stats; a.slots = slots;
+    a.M = (int)M; a.HW = q.HW; a.n_layers = n;
+    for (int i = 0; i < n; ++i) {
+        if (!wf[i]) return OwnWeights::outside("op_chain", "weights", "the plan keeps such a site on its per-layer launches");
+        a.layer[i] = ChainLayer{wf[i], i ? q.d_gamma[i] : nullptr, i ? q.d_beta[i] : nullptr, q.chan[i], q.chan[i + 1], i ? (q.gelu[i] != 0) : 0};
+    }
+    HIP_TRY(hipMemset(q.d_stats, 0xff, (size_t)q.B * slots * 2 * sizeof(double)));       // unwritten partials read as NaN
+    SPDM_TRY(op_finish("op_chain", 0, launch_conv_chain(a, nullptr)));
+    q.out[0] = conv_chain_blocks(a.M); q.out[1] = slots; q.out[2] = CHAIN_M_TILE; q.out[3] = 1;
     return SPDM_OK;
 }
 

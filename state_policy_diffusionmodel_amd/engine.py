@@ -290,12 +290,12 @@ class SpdmEngine:
     def plan_routes(self, B: int) -> dict:
         """The kernel routes the plan chooses for one U-Net evaluation at batch ``B`` (spdm_debug_plan_routes; test hook, host
         arithmetic only): ``pool`` / ``up`` / ``film``: tuples of 3 / 3 / 6 route codes, ``sa``: six dicts
-        {fused, crop, outc, in, tail} -- the codes are listed in include/spdm.h."""
-        v = (ctypes.c_int32 * 42)()
+        {fused, crop, outc, in, tail}, ``chain``: (down block 3, bottleneck) -- the codes are listed in include/spdm.h."""
+        v = (ctypes.c_int32 * 44)()
         _lib.check(self.lib.spdm_debug_plan_routes(self._h, int(B), v, len(v)), "spdm_debug_plan_routes")
         v = [int(x) for x in v]
         sa = [dict(zip(("fused", "crop", "outc", "in", "tail"), v[12 + 5 * i:17 + 5 * i])) for i in range(6)]
-        return {"pool": tuple(v[0:3]), "up": tuple(v[3:6]), "film": tuple(v[6:12]), "sa": sa}
+        return {"pool": tuple(v[0:3]), "up": tuple(v[3:6]), "film": tuple(v[6:12]), "sa": sa, "chain": tuple(v[42:44])}
 
     def set_scheduler(self, sched) -> None:
         """Install the tables of a host scheduler object (schedulers.py) for the loop."""
