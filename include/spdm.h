@@ -996,6 +996,29 @@ int  spdm_adam_step(int32_t device, const spdm_optim_segment* h_segments, int32_
                     double* d_workspace, void* stream);
 size_t spdm_adam_norm_index(void);
 
+/* The exponential moving average of the weights on the device.  Replaces: the EMA that diffusion-policy code
+ * bases keep beside their optimiser (diffusers' EMAModel.step: s.sub_(one_minus_decay * (s - p)) per parameter), which the
+ * reference's train.py does not have and whose users validate and sample from the average.  Stateless: there is no handle;
+ * the shadow is the caller's arrays and the decay is an argument (the warm-up schedule lives in optim.ema_decay).
+ *
+ * A segment is one flat fp32 device array of numel shadow floats with the parameter array it follows: the same segments
+ * spdm_adam_step steps.  Both pointers must be 16-byte aligned and the two ranges disjoint.
+ *
+ * spdm_ema_step.  One update of h_segments[0 .. n_segments) (a HOST array) in ONE launch enqueued on `stream` (NULL: the null
+ * stream, and the call synchronises); no workspace, nothing is read back.  Per element in fp32
+ *    ema = ema - one_minus_decay * (ema - p)
+ *  as three operations each rounded on its own (a subtraction, a multiplication, a subtraction; no fused multiply-add), which
+ *  is bit for bit what torch's e.sub_((e - p) * one_minus_decay) computes -- and not what torch.lerp_ computes.
+ *  one_minus_decay is float32(1.0 - decay) with the subtraction in double, rounded once by the caller.  one_minus_decay = 0
+ *  leaves d_ema's bits; a NaN or an infinity in d_param reaches its own element only.  d_param is only read.
+ * Deterministic: no atomics, no reduction, one thread per element; two calls on the same inputs give bit-identical results.
+ * SPDM_ERR_INVALID, before the GPU is touched: h_segments null; n_segments outside 1 .. SPDM_OPTIM_MAX_SEGMENTS; a null
+ * pointer; numel == 0; a pointer that is not 16-byte aligned; d_ema == d_param or overlapping ranges within a segment;
+ * one_minus_decay NaN or outside [0, 1]. */
+typedef struct { float* d_ema; const float* d_param; uint64_t numel; } spdm_ema_segment;
+int  spdm_ema_step(int32_t device, const spdm_ema_segment* h_segments, int32_t n_segments, float one_minus_decay,
+                   void* stream);
+
 /* Host-only test hook (no GPU call): the launch geometry chosen for a split-precision 3x3 / 3x1 convolution with the
  * statistics epilogue -- out = {m_tile, n_tile, n_tiles, slots, ksplit, kernel, st_m_tile, st_n_tiles, reserved_slots,
  * combine_rows}; kernel: bit 0 = the small-grid kernel (conv_skinny.hip), bit 1 = the register-resident kernel (conv_reg.hip).

@@ -121,6 +121,11 @@ class SpdmOptimSegment(ctypes.Structure):
                 ("numel", c_uint64)]
 
 
+class SpdmEmaSegment(ctypes.Structure):
+    """spdm_ema_segment (include/spdm.h)."""
+    _fields_ = [("d_ema", c_void_p), ("d_param", c_void_p), ("numel", c_uint64)]
+
+
 class SpdmForwardProcessArgs(ctypes.Structure):
     """spdm_forward_process_args (include/spdm.h)."""
     _fields_ = ([(n, c_int32) for n in ("B", "H", "D", "inp_h", "T", "time_dim")] +
@@ -286,6 +291,7 @@ SYMBOLS = {
     "spdm_adam_step": (c_int32, [c_int32, POINTER(SpdmOptimSegment), c_int32, c_int64, c_float, c_float, c_float, c_float, c_float,
                                  c_void_p, c_void_p]),
     "spdm_adam_norm_index": (c_size_t, []),
+    "spdm_ema_step": (c_int32, [c_int32, POINTER(SpdmEmaSegment), c_int32, c_float, c_void_p]),
     "spdm_op_gelu": (c_int32, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "spdm_op_gemm": (c_int32, [POINTER(SpdmOpGemmArgs)]),
     "spdm_op_chain": (c_int32, [POINTER(SpdmOpChainArgs)]),

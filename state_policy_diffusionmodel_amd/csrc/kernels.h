@@ -447,6 +447,17 @@ struct OptimArgs {
 // one or two launches on s: [partial sums of g^2 ->] Adam on every segment in place; workspace: ADAM_GRID + 1 doubles
 hipError_t launch_adam_step(OptimArgs a, double* workspace, hipStream_t s);
 
+// ---- EMA of the weights (optim.hip; spdm_ema_step) -----------------------------------------------------------
+struct EmaSeg { float* ema; const float* p; unsigned long long n; };     // two flat fp32 arrays of n floats, 16-byte aligned, disjoint
+struct EmaArgs {
+    EmaSeg seg[OPTIM_MAX_SEGMENTS];
+    int nseg;
+    float omd;                         // 1 - decay, rounded once from double by the caller
+    unsigned long long quads, per;     // filled by the launch, as OptimArgs'
+};
+// one launch of ADAM_GRID workgroups on s: ema = ema - omd (ema - p) on every segment, on adam_apply_kernel's partition
+hipError_t launch_ema_step(EmaArgs a, hipStream_t s);
+
 // ---- the forward (noising) process of a training step (train_noise.hip; spdm_train_forward_process) --------
 struct ForwardProcessArgs {
     int B, H, D, inp_h, T;

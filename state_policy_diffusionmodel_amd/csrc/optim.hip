@@ -1,4 +1,5 @@
-// optim.hip -- gradient clipping + Adam on the device (spdm_adam_step).
+// optim.hip -- gradient clipping + Adam on the device (spdm_adam_step), and the exponential moving average of
+// the weights on the same partition (spdm_ema_step, ema_apply_kernel below).
 //
 // Replaces: torch.nn.utils.clip_grad_norm_ (Lightning's gradient_clip_val, train.py) followed by torch.optim.Adam.step()
 // (configure_optimizers, models/diffusion_ddpm.py:114-124; models/encoder/autoencoder.py:73-74) over up to four flat fp32
@@ -24,8 +25,10 @@ constexpr int THREADS = 256;
 typedef unsigned long long u64;
 
 // the part of segment s (quads [base, base + nq) of the concatenation) inside the workgroup's range [lo, hi), segment-local
+// (Seg: OptimSeg or EmaSeg -- only its n is read)
 struct Part { u64 b, e, full; bool any; };
-__device__ inline Part part_of(const OptimSeg& sg, u64 base, u64 lo, u64 hi) {
+template <class Seg>
+__device__ inline Part part_of(const Seg& sg, u64 base, u64 lo, u64 hi) {
     const u64 nq = (sg.n + 3) >> 2;
     Part p;
     p.full = sg.n >> 2;                                  // whole quads; quad `full` (if nq > full) holds the n & 3 tail floats
@@ -36,7 +39,8 @@ __device__ inline Part part_of(const OptimSeg& sg, u64 base, u64 lo, u64 hi) {
     return p;
 }
 // does this thread own the segment's short last quad?  (it is quad `full` of the thread order b + t, b + t + 256, ...)
-__device__ inline bool owns_tail(const Part& p, const OptimSeg& sg) {
+template <class Seg>
+__device__ inline bool owns_tail(const Part& p, const Seg& sg) {
     return (sg.n & 3) != 0 && p.any && p.full >= p.b && p.full < p.e && ((p.full - p.b) & (THREADS - 1)) == threadIdx.x;
 }
 
@@ -151,7 +155,60 @@ __global__ __launch_bounds__(THREADS) void adam_apply_kernel(const OptimArgs a, 
     }
 }
 
+// One EMA update of one element: ema - omd (ema - p), the recipe s.sub_(one_minus_decay * (s - p)) of diffusion-policy code
+// bases, as torch evaluates it: a subtraction, a multiplication and a subtraction, each rounded on its own (no contraction:
+// fma(-omd, ema - p, ema) differs from it on about one element in a hundred at decay 0.4 .. 0.9).  NOT torch.lerp_, which
+// rounds differently.  omd = 0 returns ema's bits; a NaN or an infinity in p reaches this element alone.
+__device__ inline float ema1(const float e, const float p, const float omd) {
+#pragma clang fp contract(off)
+    const float d = e - p;
+    const float s = omd * d;
+    return e - s;
+}
+__device__ inline float4 ema4(const float4 e, const float4 p, const float omd) {
+    return make_float4(ema1(e.x, p.x, omd), ema1(e.y, p.y, omd), ema1(e.z, p.z, omd), ema1(e.w, p.w, omd));
+}
+
+// adam_apply_kernel's partition over (ema, p) pairs: every element is read and written by exactly one thread, which loads its
+// ema before it stores it.  Nothing is reduced, so the result does not depend on the partition at all.
+__global__ __launch_bounds__(THREADS) void ema_apply_kernel(const EmaArgs a) {
+    const u64 lo = (u64)blockIdx.x * a.per, hi = lo + a.per < a.quads ? lo + a.per : a.quads;
+    u64 base = 0;
+#pragma unroll
+    for (int s = 0; s < OPTIM_MAX_SEGMENTS; ++s) {
+        if (s >= a.nseg) break;
+        const EmaSeg& sg = a.seg[s];
+        const Part pt = part_of(sg, base, lo, hi);
+        base += (sg.n + 3) >> 2;
+        if (!pt.any) continue;
+        float4* e4 = reinterpret_cast<float4*>(sg.ema);
+        const float4* p4 = reinterpret_cast<const float4*>(sg.p);
+        const u64 ef = pt.e < pt.full ? pt.e : pt.full;
+        u64 q = pt.b + threadIdx.x;
+        for (; q + 3 * THREADS < ef; q += 4 * THREADS) {      // eight 16-byte loads in flight, then the stores
+            const u64 r1 = q + THREADS, r2 = q + 2 * THREADS, r3 = q + 3 * THREADS;
+            const float4 e0 = e4[q], e1 = e4[r1], e2 = e4[r2], e3 = e4[r3];
+            const float4 p0 = p4[q], p1 = p4[r1], p2 = p4[r2], p3 = p4[r3];
+            e4[q] = ema4(e0, p0, a.omd);
+            e4[r1] = ema4(e1, p1, a.omd);
+            e4[r2] = ema4(e2, p2, a.omd);
+            e4[r3] = ema4(e3, p3, a.omd);
+        }
+        for (; q < ef; q += THREADS) e4[q] = ema4(e4[q], p4[q], a.omd);
+        if (owns_tail(pt, sg))
+            for (u64 i = pt.full * 4; i < sg.n; ++i) sg.ema[i] = ema1(sg.ema[i], sg.p[i], a.omd);
+    }
+}
+
 }  // namespace
+
+hipError_t launch_ema_step(EmaArgs a, hipStream_t s) {
+    a.quads = 0;
+    for (int i = 0; i < a.nseg; ++i) a.quads += (a.seg[i].n + 3) >> 2;
+    a.per = (a.quads + ADAM_GRID - 1) / ADAM_GRID;
+    hipLaunchKernelGGL(ema_apply_kernel, dim3(ADAM_GRID), dim3(THREADS), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_adam_step(OptimArgs a, double* workspace, hipStream_t s) {
     a.quads = 0;

@@ -4218,6 +4218,34 @@ extern "C" int spdm_adam_step(int32_t device, const spdm_optim_segment* h_segmen
     return SPDM_OK;
 }
 
+// EMA of the weights (include/spdm.h, optim.hip).  Stateless, like spdm_adam_step: the shadow is the caller's arrays.
+extern "C" int spdm_ema_step(int32_t device, const spdm_ema_segment* h_segments, int32_t n_segments, float one_minus_decay,
+                             void* stream) {
+    if (!h_segments) return fail(SPDM_ERR_INVALID, "ema_step: null argument");
+    if (n_segments < 1 || n_segments > SPDM_OPTIM_MAX_SEGMENTS)
+        return fail(SPDM_ERR_INVALID, "ema_step: %d segments (1 .. %d)", n_segments, SPDM_OPTIM_MAX_SEGMENTS);
+    if (!(one_minus_decay >= 0.f && one_minus_decay <= 1.f))        // (a NaN fails both comparisons)
+        return fail(SPDM_ERR_INVALID, "ema_step: one_minus_decay %g outside [0, 1]", (double)one_minus_decay);
+    EmaArgs a = {};
+    for (int i = 0; i < n_segments; ++i) {
+        const spdm_ema_segment& g = h_segments[i];
+        if (!g.d_ema || !g.d_param) return fail(SPDM_ERR_INVALID, "ema_step: segment %d: null pointer", i);
+        if (g.numel == 0) return fail(SPDM_ERR_INVALID, "ema_step: segment %d is empty", i);
+        const uintptr_t e = (uintptr_t)g.d_ema, p = (uintptr_t)g.d_param;
+        if ((e | p) % 16) return fail(SPDM_ERR_INVALID, "ema_step: segment %d: a pointer is not 16-byte aligned", i);
+        const uintptr_t gap = e > p ? e - p : p - e;      // the ranges [e, e + 4 numel) and [p, p + 4 numel) must be disjoint
+        if (gap / sizeof(float) < g.numel)
+            return fail(SPDM_ERR_INVALID, "ema_step: segment %d: d_ema and d_param overlap", i);
+        a.seg[i] = {g.d_ema, g.d_param, (unsigned long long)g.numel};
+    }
+    a.nseg = n_segments;
+    a.omd = one_minus_decay;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(launch_ema_step(a, (hipStream_t)stream));
+    if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));
+    return SPDM_OK;
+}
+
 // Host-only introspection (no GPU): the launch geometry gemm_geometry picks for a statistics-epilogue convolution, plus the
 // statistics-slot reservation the plan makes for it (stats_slots_reserved, as Ctx::salloc).  tests/test_geometry.py checks the invariants between the
 // two on a grid of shapes (a mismatch is a silent wrong-statistics bug on the GPU).

@@ -33,6 +33,7 @@ B = 1 by taking ``obs_cond[0]``, ``models/diffusion_ddpm.py:246``).
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Callable, Dict, List, Optional
 
 import numpy as np
@@ -96,14 +97,18 @@ class NoiseEstimator:
     def _sd(self) -> Dict[str, np.ndarray]:
         """The host copy of the weights, brought up to date from ``flat_parameter()`` when an optimiser changed it."""
         if self._flat is not None and self._flat._version != self._flat_version:
-            host = self._flat.detach().cpu().numpy()
-            sd = {}
-            for name, off, shape in self._flat_index:
-                n = int(np.prod(shape)) if shape else 1
-                sd[name] = host[off:off + n].reshape(shape).copy()
-            self._host_sd = sd
+            self._host_sd = self._unpack(self._flat)
             self._flat_version = self._flat._version
         return self._host_sd
+
+    def _unpack(self, flat: torch.Tensor) -> Dict[str, np.ndarray]:
+        """A device tensor in ``flat_parameter()``'s layout as name -> host array (copies)."""
+        host = flat.detach().cpu().numpy()
+        sd = {}
+        for name, off, shape in self._flat_index:
+            n = int(np.prod(shape)) if shape else 1
+            sd[name] = host[off:off + n].reshape(shape).copy()
+        return sd
 
     def state_dict(self):
         return {k: torch.from_numpy(v) for k, v in self._sd.items()}
@@ -150,14 +155,16 @@ class NoiseEstimator:
             self._flat_version = self._flat._version
         return self._flat
 
-    def _push(self) -> None:
-        """Put ``flat_parameter()``'s values into every cached engine (in place where the layout matches)."""
-        flat = self._flat.detach()
-        for eng in self._engines():
+    def _push(self, other: Optional[torch.Tensor] = None, engines=None) -> None:
+        """Put ``flat_parameter()``'s values into every cached engine (in place where the layout matches).  ``other``: a device
+        tensor in the flat parameter's layout whose values go in instead (the EMA shadow, ``Diffusion_DDPM.ema_weights``);
+        the flat parameter and the host copy stay as they are.  ``engines``: these engines only."""
+        flat = self._flat.detach() if other is None else other.detach()
+        for eng in (self._engines() if engines is None else engines):
             if eng._index == self._flat_index:
                 eng.update_weights(flat)
             else:
-                eng.refresh_weights(self._sd)
+                eng.refresh_weights(self._sd if other is None else self._unpack(flat))
 
     def grads(self) -> Dict[str, torch.Tensor]:
         """Gradients of the loss of the last ``training_step(..., backward=True)``: state_dict name -> tensor (torch layout,
@@ -226,23 +233,29 @@ class Diffusion_DDPM:
         self._engine_key = None
         self._train_engine: Optional[SpdmEngine] = None     # training_step(backward=True): cached apart from sampling
         self._train_key = None
+        self._ema = None                                    # configure_ema(): optim.DeviceEMA over the optimiser's parameters
+        self._ema_swapped = False                           # inside ema_weights(): the engines hold the shadow
 
     # ------------------------------------------------------------------------------------------
     _HPARAM_KEYS = ("noise_steps", "obs_horizon", "pred_horizon", "observation_dim", "prediction_dim", "learning_rate",
                     "model", "noise_scheduler_type", "inpaint_horizon", "step_size")
 
     @classmethod
-    def load_from_checkpoint(cls, checkpoint_path, hparams_file=None, map_location=None, **kwargs):
+    def load_from_checkpoint(cls, checkpoint_path, hparams_file=None, map_location=None, use_ema: bool = False, **kwargs):
         """Lightning's ``LightningModule.load_from_checkpoint(ckpt, hparams_file=yaml)`` as generate.py:25,27 and
         run_predictions.py call it: constructor arguments from ``hparams.yaml`` (``save_hyperparameters()`` of
         models/diffusion_ddpm.py:37), U-Net tensors from the checkpoint's ``noise_estimator.*`` entries, the observation
-        encoder's from its ``vision_encoder.*`` entries when present (vision.VisionEncoder)."""
+        encoder's from its ``vision_encoder.*`` entries when present (vision.VisionEncoder).  ``use_ema=True``: the model's
+        weights are the averaged tensors of the checkpoint's ``ema_state_dict`` instead (``save_checkpoint`` of a model with
+        ``configure_ema()``) -- for inference; raises when the file holds none."""
         from .weights import check_state_dict, fetch_hyperparams_from_yaml, load_checkpoint_state_dict
         hp = dict(fetch_hyperparams_from_yaml(hparams_file)) if hparams_file else {}
         ctor = {k: hp[k] for k in cls._HPARAM_KEYS if k in hp}
         if isinstance(hp.get("vision_encoder"), str) or hp.get("vision_encoder") is None:
             pass                                   # a name (e.g. 'resnet18') in the yaml is not a callable: ignored
         ctor.update(kwargs)
+        if use_ema:
+            return cls._load_ema_checkpoint(str(checkpoint_path), ctor)
         sd, other = load_checkpoint_state_dict(str(checkpoint_path))
         model = ctor.get("model", "UNet")            # (no key: the constructor's default, simple_Unet.UNet)
         attention = model != "UNet_FilmnoAttention"
@@ -252,6 +265,29 @@ class Diffusion_DDPM:
             from .vision import encoder_state_dict_from
             from .weights import safe_load_state_dict
             ctor["vision_encoder_state_dict"] = encoder_state_dict_from(safe_load_state_dict(str(checkpoint_path)))
+        return cls(state_dict=sd, **ctor)
+
+    @classmethod
+    def _load_ema_checkpoint(cls, checkpoint_path: str, ctor: dict):
+        """``load_from_checkpoint(use_ema=True)``: the model built from ``ema_state_dict``'s tensors.  The encoder is the
+        averaged one when the checkpoint averaged it, the checkpoint's own otherwise."""
+        from .vision import encoder_state_dict_from
+        from .weights import check_state_dict
+        ck = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
+        ema_sd = ck.get("ema_state_dict") if isinstance(ck, dict) else None
+        if not isinstance(ema_sd, dict) or not ema_sd:
+            raise ValueError(f"{checkpoint_path} holds no 'ema_state_dict': it was written by a run without an EMA of the "
+                             f"weights (train --ema, or configure_ema() before save_checkpoint); load it without use_ema")
+        prefix = "noise_estimator."
+        sd = {k[len(prefix):]: v for k, v in ema_sd.items() if k.startswith(prefix)}
+        model = ctor.get("model", "UNet")
+        cond_dim = int(ctor.get("observation_dim", 2)) * int(ctor.get("obs_horizon", 10))
+        check_state_dict(sd, cond_dim, attention=model != "UNet_FilmnoAttention", model=model,
+                         noise_steps=int(ctor.get("noise_steps", 1000)))
+        if "vision_encoder_state_dict" not in ctor:
+            enc = encoder_state_dict_from(ema_sd) or encoder_state_dict_from(ck.get("state_dict", {}))
+            if enc is not None:
+                ctor["vision_encoder_state_dict"] = enc
         return cls(state_dict=sd, **ctor)
 
     # Lightning look-alikes used by callers (generate.py:36)
@@ -280,6 +316,8 @@ class Diffusion_DDPM:
                                       model="UNet" if self.simple else None)
             self._engine.load_state_dict(self.noise_estimator._sd)
             self._engine_key = key
+            if self._ema_swapped:           # built inside ema_weights(): it takes the shadow like the engines swapped on entry
+                self.noise_estimator._push(self._ema.shadow[0], engines=[self._engine])
         return self._engine
 
     def _check_trainable(self) -> None:
@@ -305,6 +343,8 @@ class Diffusion_DDPM:
                                             model="UNet" if self.simple else None, train_simple=self.simple)
             self._train_engine.load_state_dict(self.noise_estimator._sd)
             self._train_key = key
+            if self._ema_swapped:
+                self.noise_estimator._push(self._ema.shadow[0], engines=[self._train_engine])
         return self._train_engine
 
     def add_constraints(self, x_t: torch.Tensor, x_inpaint: torch.Tensor) -> torch.Tensor:
@@ -316,7 +356,8 @@ class Diffusion_DDPM:
     def sample(self, batch: Dict[str, torch.Tensor], option: Optional[str] = None, *,
                x_T: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                batched: bool = False, seed: Optional[int] = None, sample_offset: int = 0, every: int = 1,
-               sharded: Optional[bool] = None, group=None, shard_exact: bool = False, candidates: int = 1, start_step: int = 0):
+               sharded: Optional[bool] = None, group=None, shard_exact: bool = False, candidates: int = 1, use_ema: bool = False,
+               start_step: int = 0):
         """``option``: None -> x_0 (B,1,H,D); 'sample_history' -> list of the N+1 iterates (the reference's form);
         'sample_history_stream' -> a generator of ``(i, x_i)`` host tensors handed out while the loop runs
         (``every``: stride in steps; SpdmEngine.sample_stream).
@@ -345,7 +386,19 @@ class Diffusion_DDPM:
         and ``inpaint`` are built for the E rows -- the frame encoder runs E obs_h frames -- and each row is then repeated K
         times on the device, so row ``e K + k`` of the (E K,1,H,D) result is candidate k of row e.  ``x_T``, if given, is
         (E K,1,H,D).  The device noise is keyed by the row index, so every candidate has a stream of its own.  Not available
-        with a history option or ``sharded=True``."""
+        with a history option or ``sharded=True``.
+
+        ``use_ema=True`` runs the call inside ``ema_weights()``: the engines hold the averaged weights for
+        its duration.  It raises when no EMA is configured, and with ``option='sample_history_stream'``, whose generator
+        would run after the live weights are back."""
+        if use_ema:
+            if option == "sample_history_stream":
+                raise ValueError("use_ema=True is not available with option='sample_history_stream': the generator runs after "
+                                 "this call has put the live weights back")
+            with self.ema_weights():
+                return self.sample(batch, option, x_T=x_T, noise=noise, batched=batched, seed=seed, sample_offset=sample_offset,
+                                   every=every, sharded=sharded, group=group, shard_exact=shard_exact, candidates=candidates,
+                                   start_step=start_step)
         from .distributed import ShardedSampler, shard_bounds, world_and_rank
         if isinstance(candidates, bool) or not isinstance(candidates, (int, np.integer)) or candidates < 1:
             raise ValueError(f"candidates = {candidates!r} must be an integer >= 1")
@@ -603,7 +656,8 @@ class Diffusion_DDPM:
     def validation_step(self, batch, batch_idx: int = 0, **kw):
         return self.training_step(batch, batch_idx, **kw)
 
-    def validation_loss(self, batches, *, seed: int = 0, noise_step: int = 0xFFFFFFFF, return_terms: bool = False):
+    def validation_loss(self, batches, *, seed: int = 0, noise_step: int = 0xFFFFFFFF, return_terms: bool = False,
+                        use_ema: bool = False):
         """The reference's ``val_loss`` (``validation_step`` over a ``val_dataloader()``, averaged by Lightning over the epoch
         with batch-size weights) as a deterministic function of the weights, formed on the device.
 
@@ -615,7 +669,11 @@ class Diffusion_DDPM:
         squared error to its slot of a float64 buffer.  After the last batch one ``spdm_eval_reduce`` takes the mean and ONE
         read-back returns it as a Python float: every element weighs equally.  ``return_terms=True``: ``(val_loss, terms (N)
         float64, t (N) int32)``, the last two on the device.  Forward-only: it serves all three models, ``'UNet_Film'``
-        without ``train_attention`` included."""
+        without ``train_attention`` included.  ``use_ema=True``: the same pass with the averaged weights in
+        the engines (``ema_weights()``); raises when no EMA is configured."""
+        if use_ema:
+            with self.ema_weights():
+                return self.validation_loss(batches, seed=seed, noise_step=noise_step, return_terms=return_terms)
         from .evaluation import reduce_errors
         from .train_metrics import loss_terms_into
         ids = getattr(batches, "window_ids", None)
@@ -699,7 +757,20 @@ class Diffusion_DDPM:
                 "optimizer_states": [host(optimizer.state_dict())] if optimizer is not None else [],
                 "lr_schedulers": [host(scheduler.state_dict())] if scheduler is not None else [],
                 "spdm_trainer": ts}
+        if self._ema is not None:               # (no EMA: the file is what it was, key for key)
+            ckpt["ema_state_dict"] = self._ema_host_state_dict()
+            ckpt["spdm_ema"] = {"optimization_step": int(self._ema.optimization_step), "schedule": dict(self._ema.schedule)}
         torch.save(ckpt, str(path))
+
+    def _ema_host_state_dict(self) -> Dict[str, torch.Tensor]:
+        """The shadow as host tensors under checkpoint names: ``noise_estimator.<name>``, and ``vision_encoder.<name>`` when
+        the encoder is averaged."""
+        out = {"noise_estimator." + k: torch.from_numpy(v) for k, v in self.noise_estimator._unpack(self._ema.shadow[0]).items()}
+        if len(self._ema.shadow) > 1:
+            host = self._ema.shadow[1].detach().cpu()
+            for name, off, shape in self.vision_encoder._index:
+                out["vision_encoder." + name] = host[off:off + int(torch.Size(shape).numel())].reshape(shape).clone()
+        return out
 
     def restore_checkpoint(self, ckpt: dict) -> None:
         """Take the ``noise_estimator.*`` tensors of a loaded checkpoint dict (``train.fit(ckpt_path=)``): host copy, flat
@@ -711,6 +782,17 @@ class Diffusion_DDPM:
         if not sd:
             raise ValueError("the checkpoint's state_dict holds no noise_estimator.* tensors")
         self.noise_estimator.load_state_dict(sd)
+        if self._ema is not None:               # configure_ema() came first: its shadow and counter are the checkpoint's
+            ema_sd, meta = ckpt.get("ema_state_dict"), ckpt.get("spdm_ema")
+            if not ema_sd or not isinstance(meta, dict):
+                raise ValueError("an EMA is configured but the checkpoint holds no 'ema_state_dict' / 'spdm_ema': it was "
+                                 "written by a run without one")
+            blob, idx = pack_state_dict(state_dict_to_numpy(
+                {k[len("noise_estimator."):]: v for k, v in ema_sd.items() if k.startswith("noise_estimator.")}))
+            if _index_of(idx) != self.noise_estimator._flat_index:
+                raise ValueError("the checkpoint's ema_state_dict does not pack into this model's weight layout")
+            self._ema.load_state_dict({"shadow": [torch.from_numpy(blob)], "optimization_step": meta["optimization_step"],
+                                       "schedule": meta["schedule"]})
 
     # ==================== Optimisation (models/diffusion_ddpm.py:114-124, train.py) ====================
     def configure_optimizers(self, device_optimizer: bool = False):
@@ -741,12 +823,16 @@ class Diffusion_DDPM:
         ``gradient_clip_val``, 0.5 in train.py), ``optimizer.step()``, then put the new weights into every cached engine
         in place (``SpdmEngine.update_weights``) -- no host round trip of the weights."""
         from .optim import DeviceAdam
+        if self._ema_swapped:
+            raise RuntimeError("optimizer_step inside ema_weights(): the engines hold the averaged weights")
         if isinstance(optimizer, DeviceAdam):       # clip (over all its parameters together) + Adam in two HIP launches
             optimizer.step(max_norm=gradient_clip_val or None)
             self.noise_estimator.mark_moved()
             self.noise_estimator._push()
             if self.train_vision_encoder:
                 self.vision_encoder.update_weights(self._trainable_encoder().flat_parameter().detach())
+            if self._ema is not None:       # the weights have moved: one more launch (DESIGN.md 8.22)
+                self._ema.step()
             return
         params = [self.noise_estimator.flat_parameter()]
         if self.train_vision_encoder:       # Lightning clips the norm over ALL parameters together
@@ -757,6 +843,50 @@ class Diffusion_DDPM:
         self.noise_estimator._push()
         if self.train_vision_encoder:
             self.vision_encoder.update_weights(params[1].detach())
+        if self._ema is not None:
+            self._ema.step()
+
+    # ==================== EMA of the weights ====================
+    def configure_ema(self, **schedule):
+        """Keep an exponential moving average of the weights from now on: an ``optim.DeviceEMA`` over exactly the parameters
+        ``configure_optimizers`` hands the optimiser -- ``noise_estimator.flat_parameter()``, and the encoder's flat parameter
+        with ``train_vision_encoder=True`` -- so it averages what the reference's ``Adam(self.parameters())`` steps.
+        ``schedule``: ``optim.ema_decay``'s keywords.  ``optimizer_step`` updates it after the weights have moved;
+        ``ema_weights()``, ``validation_loss(use_ema=True)`` and ``sample(use_ema=True)`` evaluate with it; ``save_checkpoint``
+        writes it.  Stored on the model and returned."""
+        from .optim import DeviceEMA
+        if self._ema_swapped:
+            raise RuntimeError("configure_ema inside ema_weights()")
+        params = [self.noise_estimator.flat_parameter()]
+        if self.train_vision_encoder:
+            params.append(self._trainable_encoder().flat_parameter())
+        self._ema = DeviceEMA(params, **schedule)
+        return self._ema
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """``with model.ema_weights():`` -- every cached engine (and the encoder's handle, when it is averaged) holds the
+        shadow inside the block and the live flat parameters again after it, also when the block raises.  The swap is
+        ``SpdmEngine.update_weights`` in place, through ``NoiseEstimator._push``'s layout check and ``refresh_weights``
+        fallback: no second handle, no host copy of the weights, the engines' addresses -- and a captured step graph -- stay
+        valid.  An engine built inside the block takes the shadow too.  The flat parameters themselves are never written, so
+        ``noise_estimator.state_dict()`` returns the live weights inside the block as outside.  Nesting raises."""
+        if self._ema is None:
+            raise RuntimeError("no EMA is configured: call configure_ema() (train --ema) first")
+        if self._ema_swapped:
+            raise RuntimeError("ema_weights() is not re-entrant: the engines already hold the averaged weights")
+        shadow = self._ema.shadow
+        self._ema_swapped = True
+        try:
+            self.noise_estimator._push(shadow[0])
+            if len(shadow) > 1:
+                self.vision_encoder.update_weights(shadow[1], follow=False)
+            yield self._ema
+        finally:
+            self._ema_swapped = False
+            self.noise_estimator._push()
+            if len(shadow) > 1:
+                self.vision_encoder.update_weights(self._ema.params[1].detach())
 
     def _trainable_encoder(self):
         if self.vision_encoder is None:
@@ -774,17 +904,22 @@ class Diffusion_DDIM(Diffusion_DDPM):
 
 
 def load_model(model_name: str, checkpoint_path=None, hparams_path=None, num_of_ddim_steps: int = 100, *,
-               state_dict=None, solver_steps: Optional[int] = None, **hparams):
+               state_dict=None, solver_steps: Optional[int] = None, use_ema: bool = False, **hparams):
     """generate.py:23-37: build the sampler from a checkpoint + hparams.yaml (same positional signature as the
     reference) -- or from an in-memory ``state_dict`` / random init when no checkpoint is given -- and, for DDIM,
     overwrite scheduler and noise_steps exactly as the reference's loader does.  ``solver_steps = N`` then assigns
     ``DPMSolverMultistepScheduler(num_train_timesteps=model.noise_steps)`` and ``noise_steps = N`` in the same way: the
-    loaded model samples with DPM-Solver++ (2M) in N steps."""
+    loaded model samples with DPM-Solver++ (2M) in N steps.  ``use_ema=True``: the checkpoint's averaged
+    weights (``load_from_checkpoint(use_ema=True)``); it needs a checkpoint file."""
     if model_name not in ("DDPM", "DDIM"):
         raise ValueError("model_name must be 'DDPM' or 'DDIM'")
     cls = Diffusion_DDPM if model_name == "DDPM" else Diffusion_DDIM
     if checkpoint_path is not None and not isinstance(checkpoint_path, (str, bytes)) and not hasattr(checkpoint_path, "__fspath__"):
         state_dict, checkpoint_path = checkpoint_path, None        # load_model(name, state_dict) of earlier callers
+    if use_ema:
+        if checkpoint_path is None:
+            raise ValueError("use_ema=True loads a checkpoint's ema_state_dict: pass a checkpoint file")
+        hparams["use_ema"] = True
     if checkpoint_path is not None:
         model = cls.load_from_checkpoint(checkpoint_path, hparams_file=hparams_path, **hparams)
     else:

@@ -65,6 +65,7 @@ def parse_arguments(argv=None):
     p.add_argument("--data", type=str, required=True, help="arrays.npz (or a zarr store, if zarr is installed)")
     p.add_argument("--ddim_steps", type=int, default=100)
     p.add_argument("--solver_steps", type=int, default=None, metavar="N", help="sample with DPM-Solver++ (2M) in N steps instead of the --model_name schedule (default: off)")
+    p.add_argument("--use_ema", action="store_true", help="load the checkpoint's averaged weights (ema_state_dict, written by train --ema)")
     p.add_argument("--step_size", type=int, default=None, help="rows between a window's samples (default: the hparams' step_size)")
     p.add_argument("--runs", type=int, default=10)
     p.add_argument("--batch_size", type=int, default=4096)
@@ -83,7 +84,7 @@ def main(argv=None):
     from .evaluation import evaluate, robustness
     from .weights import fetch_hyperparams_from_yaml
     model = load_model(args.model_name, args.checkpoint, args.hparams, num_of_ddim_steps=args.ddim_steps, max_batch=args.batch_size,
-                       solver_steps=args.solver_steps)
+                       solver_steps=args.solver_steps, use_ema=args.use_ema)
     step_size = int(args.step_size or dict(fetch_hyperparams_from_yaml(args.hparams)).get("step_size", 1))
     arrays = load_arrays(args.data)
     dataset = DeviceDataset(arrays["position"], arrays["velocity"], arrays["action"], arrays["img"], arrays["episode_ends"],

@@ -42,6 +42,7 @@ def parse_arguments(argv=None):
     p.add_argument("--ddim_steps", type=int, default=100)
     p.add_argument("--solver_steps", type=int, default=None, metavar="N", help="sample with DPM-Solver++ (2M) in N steps instead of the --model_name schedule (default: off)")
     p.add_argument("--batched", action="store_true", help="sample all batch_size trajectories (reference: only the first)")
+    p.add_argument("--use_ema", action="store_true", help="load the checkpoint's averaged weights (ema_state_dict, written by train --ema)")
     p.add_argument("--out", type=str, default=None)
     return p.parse_args(argv)
 
@@ -55,7 +56,7 @@ def main(argv=None):
     if args.hparams:            # generate.py:46-58 of the reference: everything comes from tb_logs/version_*/hparams.yaml
         size = {}
     model = load_model(args.model_name, args.checkpoint or None, args.hparams, num_of_ddim_steps=args.ddim_steps,
-                       max_batch=args.batch_size, solver_steps=args.solver_steps, **size)
+                       max_batch=args.batch_size, solver_steps=args.solver_steps, use_ema=args.use_ema, **size)
     args.obs_horizon, args.observation_dim = model.obs_horizon, model.observation_dim
     B, oh = args.batch_size, args.obs_horizon
     g = torch.Generator().manual_seed(args.seed)

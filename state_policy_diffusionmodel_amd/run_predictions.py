@@ -60,6 +60,7 @@ def parse_arguments(argv=None):
     p.add_argument("--data", type=str, required=True, help="arrays.npz (or a zarr store, if zarr is installed)")
     p.add_argument("--ddim_steps", type=int, default=100)
     p.add_argument("--solver_steps", type=int, default=None, metavar="N", help="sample with DPM-Solver++ (2M) in N steps instead of the --model_name schedule (default: off)")
+    p.add_argument("--use_ema", action="store_true", help="load the checkpoint's averaged weights (ema_state_dict, written by train --ema)")
     p.add_argument("--replan_every", type=int, default=50, help="plan on every n-th row of an episode (run_predictions.py:151)")
     p.add_argument("--seed", type=int, default=0, help="plan i samples with seed + i and its x_T from a generator seeded alike")
     p.add_argument("--warm_start", type=int, default=None, metavar="K",
@@ -86,7 +87,7 @@ def main(argv=None) -> dict:
     from .evaluate import load_arrays, load_stats
     from .policy import ClosedLoopPolicy
     model = load_model(args.model_name, args.checkpoint, args.hparams, num_of_ddim_steps=args.ddim_steps, max_batch=args.candidates,
-                       solver_steps=args.solver_steps)
+                       solver_steps=args.solver_steps, use_ema=args.use_ema)
     stats = load_stats(args.stats)
     arrays = load_arrays(args.data)
     storage = choose_image_storage(arrays["img"])

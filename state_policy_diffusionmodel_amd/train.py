@@ -77,7 +77,7 @@ def _lr(optimizer) -> float:
 
 def fit(model, datamodule, *, max_epochs: int, out_dir, val_check_interval=0.25, gradient_clip_val: Optional[float] = 0.5,
         seed: int = 0, device_optimizer: bool = True, early_stop: Optional[LrEarlyStop] = None, ckpt_path=None,
-        validate_first: bool = True, log_every: int = 0) -> dict:
+        validate_first: bool = True, log_every: int = 0, ema: Optional[dict] = None, ema_monitor: bool = False) -> dict:
     """Train ``model`` on ``datamodule`` for epochs ``[start, max_epochs)`` and write ``out_dir/checkpoints/epoch={e}.ckpt``
     (every epoch, all kept), ``out_dir/STATS.pkl``, ``out_dir/hparams.yaml`` and ``out_dir/metrics.jsonl``.
 
@@ -97,7 +97,14 @@ def fit(model, datamodule, *, max_epochs: int, out_dir, val_check_interval=0.25,
     at the next epoch, appending to ``metrics.jsonl``.  ``log_every`` > 0 prints every that many steps (no read-back: the
     step number only); validation lines are always printed.
 
-    Returns ``{'epoch', 'global_step', 'val_loss', 'lr', 'stopped_early', 'metrics'}``."""
+    ``ema`` (a dict of ``optim.ema_decay``'s schedule keywords, ``{}`` for its defaults): the loop calls
+    ``model.configure_ema(**ema)`` once -- ``optimizer_step`` then keeps the average -- and every validation also computes
+    ``val_loss_ema = validation_loss(..., use_ema=True)``; every ``metrics.jsonl`` line gains ``val_loss_ema`` and ``ema_decay``
+    (the decay of the latest update).  The scheduler, and through its lr the early stop, keep following ``val_loss`` unless
+    ``ema_monitor`` makes them follow ``val_loss_ema``.  A resumed run restores the shadow and its counter
+    (``restore_checkpoint``).  ``None``: none of this; ``configure_ema`` is not looked up.
+
+    Returns ``{'epoch', 'global_step', 'val_loss', 'lr', 'stopped_early', 'metrics'}`` (and ``'val_loss_ema'`` with ``ema``)."""
     out_dir = str(out_dir)
     ckpt_dir = os.path.join(out_dir, "checkpoints")
     os.makedirs(ckpt_dir, exist_ok=True)
@@ -107,6 +114,10 @@ def fit(model, datamodule, *, max_epochs: int, out_dir, val_check_interval=0.25,
     optimizer, scheduler = conf["optimizer"], conf["lr_scheduler"]["scheduler"]
     step_kw = {"time_dropout": 0.1} if is_simple_model(getattr(model, "model_name", "UNet_Film")) else {}
     device = getattr(model, "device", "cpu")
+    if ema_monitor and ema is None:
+        raise ValueError("ema_monitor=True needs ema= (there is no val_loss_ema to follow)")
+    ema_obj = model.configure_ema(**ema) if ema is not None else None
+    val_loss_ema = None
 
     start_epoch, global_step, val_loss = 0, 0, None
     if ckpt_path is not None:
@@ -118,6 +129,7 @@ def fit(model, datamodule, *, max_epochs: int, out_dir, val_check_interval=0.25,
         optimizer.load_state_dict(ckpt["optimizer_states"][0])
         scheduler.load_state_dict(ckpt["lr_schedulers"][0])
         start_epoch, global_step, val_loss = int(st["epoch"]) + 1, int(st["global_step"]), st.get("val_loss")
+        val_loss_ema = st.get("val_loss_ema")
         if int(st.get("seed", seed)) != int(seed):
             raise ValueError(f"{ckpt_path} was trained with seed {st['seed']}, this call has seed {seed}")
         if early_stop is not None and st.get("early_stop"):
@@ -129,15 +141,25 @@ def fit(model, datamodule, *, max_epochs: int, out_dir, val_check_interval=0.25,
     def emit(kind, epoch, train_loss):
         line = {"kind": kind, "epoch": epoch, "global_step": global_step, "val_loss": val_loss, "lr": _lr(optimizer),
                 "train_loss": train_loss}
+        if ema is not None:
+            from .optim import ema_decay
+            line["val_loss_ema"] = val_loss_ema
+            line["ema_decay"] = ema_decay(int(getattr(ema_obj, "optimization_step", global_step)), **ema)
         metrics.append(line)
         log.write(json.dumps(line) + "\n")
         log.flush()
         print(f"[{kind}] epoch {epoch} step {global_step} val_loss {val_loss} lr {line['lr']:g} train_loss {train_loss}", flush=True)
 
+    def validate():
+        nonlocal val_loss, val_loss_ema
+        val_loss = float(model.validation_loss(datamodule.val_dataloader(), seed=seed))
+        if ema is not None:
+            val_loss_ema = float(model.validation_loss(datamodule.val_dataloader(), seed=seed, use_ema=True))
+
     try:
         if ckpt_path is None:
             if validate_first:
-                val_loss = float(model.validation_loss(datamodule.val_dataloader(), seed=seed))
+                validate()
                 emit("val", -1, None)
             datamodule.save_stats(os.path.join(out_dir, "STATS.pkl"))
             model.save_hparams(os.path.join(out_dir, "hparams.yaml"))
@@ -171,16 +193,19 @@ def fit(model, datamodule, *, max_epochs: int, out_dir, val_check_interval=0.25,
                 if log_every and global_step % log_every == 0:
                     print(f"epoch {epoch} batch {i + 1}/{n} step {global_step}", flush=True)
                 if i in points:
-                    val_loss = float(model.validation_loss(datamodule.val_dataloader(), seed=seed))
+                    validate()
                     emit("val", epoch, drain())
                     if early_stop is not None and early_stop.check(_lr(optimizer)):
                         stopped = True
                         break
-            if val_loss is not None:
-                scheduler.step(val_loss)
+            monitored = val_loss_ema if ema_monitor else val_loss
+            if monitored is not None:
+                scheduler.step(monitored)
             emit("epoch", epoch, drain())
             state = {"epoch": epoch, "global_step": global_step, "val_loss": val_loss, "seed": int(seed),
                      "early_stop": early_stop.state_dict() if early_stop is not None else None, "stopped_early": stopped}
+            if ema is not None:
+                state["val_loss_ema"] = val_loss_ema
             model.save_checkpoint(os.path.join(ckpt_dir, f"epoch={epoch}.ckpt"), optimizer=optimizer, scheduler=scheduler,
                                   trainer_state=state)
             if stopped:
@@ -188,8 +213,11 @@ def fit(model, datamodule, *, max_epochs: int, out_dir, val_check_interval=0.25,
                 break
     finally:
         log.close()
-    return {"epoch": epoch, "global_step": global_step, "val_loss": val_loss, "lr": _lr(optimizer), "stopped_early": stopped,
-            "metrics": metrics}
+    result = {"epoch": epoch, "global_step": global_step, "val_loss": val_loss, "lr": _lr(optimizer), "stopped_early": stopped,
+              "metrics": metrics}
+    if ema is not None:
+        result["val_loss_ema"] = val_loss_ema
+    return result
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -217,6 +245,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--no_early_stop", action="store_true")
     p.add_argument("--ckpt_path", type=str, default=None, help="resume from a checkpoint of this loop")
+    p.add_argument("--ema", action="store_true", help="keep an exponential moving average of the weights (DESIGN.md 8.22)")
+    p.add_argument("--ema_max_decay", type=float, default=0.9999, help="the decay the warm-up schedule ends at")
+    p.add_argument("--ema_power", type=float, default=0.75, help="exponent of the warm-up schedule")
+    p.add_argument("--ema_inv_gamma", type=float, default=1.0, help="inverse multiplicative factor of the warm-up schedule")
+    p.add_argument("--ema_update_after_step", type=int, default=0, help="optimiser steps before the average starts to lag")
+    p.add_argument("--ema_monitor", action="store_true", help="the lr scheduler follows val_loss_ema instead of val_loss")
     return p
 
 
@@ -252,8 +286,14 @@ def main(argv=None) -> dict:
     else:
         model = Diffusion_DDPM(weight_seed=args.seed, **kw)
     early = None if args.no_early_stop else LrEarlyStop(1e-4, args.n_epochs // 10)
+    extra = {}
+    if args.ema:
+        extra = {"ema": {"max_value": args.ema_max_decay, "power": args.ema_power, "inv_gamma": args.ema_inv_gamma,
+                         "update_after_step": args.ema_update_after_step}, "ema_monitor": args.ema_monitor}
+    elif args.ema_monitor:
+        parser.error("--ema_monitor needs --ema")
     return fit(model, dm, max_epochs=args.n_epochs, out_dir=args.out_dir, seed=args.seed, early_stop=early,
-               ckpt_path=args.ckpt_path, log_every=50)
+               ckpt_path=args.ckpt_path, log_every=50, **extra)
 
 
 __all__ = ["LrEarlyStop", "validation_points", "fit", "main", "build_parser"]

@@ -123,14 +123,17 @@ class _FrameHandle:
             self._flat = torch.nn.Parameter(torch.from_numpy(self._blob).to(self.device))
         return self._flat
 
-    def update_weights(self, dev_blob: torch.Tensor) -> None:
+    def update_weights(self, dev_blob: torch.Tensor, *, follow: bool = True) -> None:
         """Put new values (a device blob in the packed layout, e.g. ``flat_parameter().detach()``) into the handle in
-        place; a pending training forward is dropped."""
+        place; a pending training forward is dropped.  ``follow=False``: the handle alone takes them -- the flat parameter
+        and ``state_dict()`` keep their values (a temporary swap: ``Diffusion_DDPM.ema_weights``, which puts them back)."""
         b = dev_blob.detach()
         if b.device != self.device or b.dtype != torch.float32 or not b.is_contiguous() or b.numel() != self._n_floats:
             raise ValueError(f"expected a contiguous fp32 blob of {self._n_floats} floats on {self.device}")
         self._run("update_weights", b, b.numel())
         self._pending = None
+        if not follow:
+            return
         if self._flat is None:
             self._blob = b.cpu().numpy()
         elif b.data_ptr() != self._flat.data_ptr():      # values from elsewhere: the parameter follows the handle
