@@ -369,6 +369,31 @@ typedef struct {
 } spdm_dataset_gather_args;
 int  spdm_dataset_gather(int32_t device, const spdm_dataset_gather_args* a, void* stream);
 
+/* The inverse of the gather's frame path in ONE launch (dataset.hip): planar fp32 frames become interleaved
+ * uint8 pixels, written as 96 x 96 tiles of a contact sheet.  Replaces the per-frame recon.permute(1, 2, 0).cpu().numpy()
+ * and imshow's own conversion of the reference's models/encoder/eval_autoencoder.py:91-106.  Stateless.  Enqueued on `stream`,
+ * no atomics, no host synchronisation (NULL stream: the null stream, and the call synchronises).
+ *   n: frames;  d_frames (n,3,96,96) fp32, planar, 16-byte aligned;
+ *   d_out: uint8 of shape (ceil(n_tiles / cols) 96, cols 96, 3), 16-byte aligned;  cols: tiles per sheet row.
+ * Frame i goes to tile j = tile_offset + i, at tile row j / cols and tile column j % cols: pixel (y, x, c) of the frame lands
+ * at out[(j / cols) 96 + y][(j % cols) 96 + x][c].  Tiles outside [tile_offset, tile_offset + n) are not touched.  With
+ * cols = 1 and tile_offset = 0 the output is the image store's own (n,96,96,3) layout.
+ * Quantisation, in fp32: v = x * 255.0f (one fp32 multiply);  q = rintf(v) (ties to even);  the byte is 0 if v is NaN, else
+ * min(max(q, 0), 255).  For a byte k, (float)k / 255.0f -- what spdm_dataset_gather emits -- gives v == k exactly, so gather
+ * followed by this call returns the stored bytes.  The float64 form of the same recipe rounds some values differently: the
+ * fp32 form is the contract.
+ * SPDM_ERR_INVALID, before the GPU is touched: NULL args or a NULL or misaligned d_frames or d_out; n, cols or n_tiles < 1;
+ * tile_offset < 0; tile_offset + n > n_tiles. */
+typedef struct {
+    int32_t n;
+    int32_t cols;
+    int64_t tile_offset;
+    int64_t n_tiles;
+    const float* d_frames;
+    uint8_t* d_out;
+} spdm_frames_to_bytes_args;
+int  spdm_frames_to_bytes(int32_t device, const spdm_frames_to_bytes_args* a, void* stream);
+
 /* The error of sampled trajectories against the windows they were conditioned on, in ONE launch and without the
  * trajectories leaving the device.  Replaces the per-window body of the reference's
  * evaluation/eval_acurracy_diffusion_positions.py:118-140 and evaluation/eval_consistency_diffusion_positions.py:
@@ -789,6 +814,34 @@ typedef struct {
     int32_t* d_slot_t;
 } spdm_loss_terms_args;
 int  spdm_loss_terms(int32_t device, const spdm_loss_terms_args* a, void* stream);
+
+/* The per-frame reconstruction error of one validation batch of the frame autoencoder in ONE launch (DESIGN.md 8.23,
+ * train_metrics.hip).  Replaces: nn.MSELoss(recon, batch) of the reference's validation_step (models/encoder/autoencoder.py:48,
+ * 64-71) as Lightning averages it over an epoch, weighted by batch size: every frame has 27648 elements, so that is the mean
+ * over the frames of each frame's own mean squared error.  Stateless: there is no handle.  Enqueued on `stream`, no atomics,
+ * no host synchronisation (NULL stream: the null stream, and the call synchronises).
+ *   n: frames in the batch;  d_recon, d_target (n,3,96,96) fp32, planar, 16-byte aligned;
+ *   d_terms (n_slots) float64: frame b writes d_terms[slot_offset + b];  slots outside [slot_offset, slot_offset + n) are not
+ *     touched;  reserved: ignored (keeps the pointers 8-byte aligned without implicit padding).
+ * Every operation is a float64 operation rounded on its own (no FMA).  The order is a function of the frame size alone,
+ * 27648 elements = 6912 quads of four consecutive floats (row-major in the frame): quad q belongs to partial q mod 256; a
+ * partial starts at 0.0 and takes its quads in ascending order and within a quad the four elements in ascending order, as
+ * d = (double)target - (double)recon;  p = p + d * d;  the 256 partials p[0..255] are combined by
+ * for off in 128, 64, 32, 16, 8, 4, 2, 1: p[i] = p[i] + p[i + off], i < off;  the term is p[0] / 27648.0.  (One 256-thread
+ * workgroup per frame, thread = partial, 16-byte loads; the tree's first two steps through LDS, the rest by wave shuffles.)
+ * The mean over a pass is spdm_eval_reduce over the (N, 1) terms with runs = 1: its d_mean.
+ * SPDM_ERR_INVALID, before the GPU is touched: NULL args or a NULL d_recon, d_target or d_terms; n < 1; slot_offset < 0;
+ * slot_offset + n > n_slots; a misaligned d_recon or d_target. */
+typedef struct {
+    int32_t n;
+    int32_t reserved;
+    const float* d_recon;
+    const float* d_target;
+    int64_t slot_offset;
+    int64_t n_slots;
+    double* d_terms;
+} spdm_recon_terms_args;
+int  spdm_recon_terms(int32_t device, const spdm_recon_terms_args* a, void* stream);
 
 /* PositionalEncoding's Dropout(p) in training mode (simple_Unet.py:226-257) for the NEXT spdm_train_loss_grad call on a
  * SPDM_FLAG_TRAIN_SIMPLE handle (SPDM_ERR_STATE on any other): d_scale is a (B, time_dim) device array -- the dropout mask

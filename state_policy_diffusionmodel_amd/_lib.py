@@ -222,6 +222,18 @@ class SpdmLossTermsArgs(ctypes.Structure):
                 [(n, c_void_p) for n in ("d_terms", "d_t_in", "d_slot_t")])
 
 
+class SpdmReconTermsArgs(ctypes.Structure):
+    """spdm_recon_terms_args (include/spdm.h)."""
+    _fields_ = [("n", c_int32), ("reserved", c_int32), ("d_recon", c_void_p), ("d_target", c_void_p),
+                ("slot_offset", c_int64), ("n_slots", c_int64), ("d_terms", c_void_p)]
+
+
+class SpdmFramesToBytesArgs(ctypes.Structure):
+    """spdm_frames_to_bytes_args (include/spdm.h)."""
+    _fields_ = [("n", c_int32), ("cols", c_int32), ("tile_offset", c_int64), ("n_tiles", c_int64),
+                ("d_frames", c_void_p), ("d_out", c_void_p)]
+
+
 class SpdmConfig(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("horizon", "state_dim", "cond_dim", "time_dim", "attention", "max_batch",
                                         "device", "num_train_timesteps", "flags")]
@@ -261,6 +273,8 @@ SYMBOLS = {
     "spdm_policy_select": (c_int32, [c_int32, POINTER(SpdmPolicySelectArgs), c_void_p]),
     "spdm_solver_step": (c_int32, [c_int32, POINTER(SpdmSolverStepArgs), c_void_p]),
     "spdm_loss_terms": (c_int32, [c_int32, POINTER(SpdmLossTermsArgs), c_void_p]),
+    "spdm_recon_terms": (c_int32, [c_int32, POINTER(SpdmReconTermsArgs), c_void_p]),
+    "spdm_frames_to_bytes": (c_int32, [c_int32, POINTER(SpdmFramesToBytesArgs), c_void_p]),
     "spdm_train_set_time_scale": (c_int32, [c_void_p, c_void_p, c_int32]),
     "spdm_sample_begin": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                     c_uint64, c_uint64, c_void_p, c_void_p]),

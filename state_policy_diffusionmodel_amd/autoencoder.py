@@ -12,6 +12,7 @@ from __future__ import annotations
 
 from typing import Dict, Optional
 
+import numpy as np
 import torch
 
 from .vision import ENCODER_KEYS, LATENT_DIM, VisionEncoder, _FrameHandle, encoder_state_dict_from
@@ -99,11 +100,22 @@ class autoencoder:
     """The reference's LightningModule surface (models/encoder/autoencoder.py:40-83) over the two HIP handles.
 
     ``state_dict``: an autoencoder checkpoint's (``encoder.N.*`` / ``model.encoder.N.*`` and the decoder's likewise) or
-    None for torch's default initialisation of these layers."""
+    None for torch's default initialisation of these layers -- from the global RNG, or with ``weight_seed`` from a forked
+    generator seeded with it, so that two constructions with one seed are bit-equal.  ``train.fit`` drives it
+    (train_autoencoder.py)."""
 
-    def __init__(self, learning_rate: float = 1e-3, state_dict=None, device: int = 0):
+    model_name = "autoencoder"                  # what ``train.fit`` asks a model for (no time dropout, no EMA)
+
+    def __init__(self, learning_rate: float = 1e-3, state_dict=None, device: int = 0, weight_seed: Optional[int] = None):
         self.lr = learning_rate
-        sd = _default_init() if state_dict is None else state_dict
+        if state_dict is not None:
+            sd = state_dict
+        elif weight_seed is None:
+            sd = _default_init()
+        else:                                   # a forked, seeded generator: the global RNG stream is left as it was
+            with torch.random.fork_rng(devices=[]):
+                torch.manual_seed(int(weight_seed))
+                sd = _default_init()
         enc_sd, dec_sd = encoder_state_dict_from(sd, "encoder."), decoder_state_dict_from(sd)
         if enc_sd is None or dec_sd is None:
             raise ValueError("state_dict holds no autoencoder: expected encoder.N.* (0, 2, 4, 7) and decoder.N.* (0, 2, 4, 6)")
@@ -131,9 +143,13 @@ class autoencoder:
     __call__ = forward
 
     # ==================== Training (:55-71) ====================
-    def training_step(self, batch: torch.Tensor, batch_idx: int = 0, *, backward: bool = False) -> torch.Tensor:
+    def training_step(self, batch: torch.Tensor, batch_idx: int = 0, *, backward: bool = False, device_noise=None, seed=None,
+                      noise_step=None, time_dropout=None) -> torch.Tensor:
         """``MSELoss(decoder(encoder(batch)), batch)`` as a device scalar.  ``backward=True`` also backpropagates: the
-        gradients are then in ``encoder.grads()`` / ``decoder.grads()`` and on both flat parameters' ``.grad``."""
+        gradients are then in ``encoder.grads()`` / ``decoder.grads()`` and on both flat parameters' ``.grad``.
+        ``device_noise``, ``seed`` and ``noise_step`` are ``train.fit``'s keywords for a step's random draws, and
+        ``time_dropout`` the one it adds for every model whose name is not a FiLM one: accepted and unused, because
+        reconstruction draws nothing and has no time embedding.  Any other keyword is a TypeError."""
         x = batch.detach().to(self.device, torch.float32).contiguous()
         if not backward:
             return self.decoder.train_loss(self.encoder(x), x)
@@ -145,6 +161,111 @@ class autoencoder:
 
     def validation_step(self, batch: torch.Tensor, batch_idx: int = 0) -> torch.Tensor:
         return self.training_step(batch, batch_idx)
+
+    # ==================== Validation on the device ====================
+    def _recon_pass(self, batches, keep: int = 0):
+        """One pass over ``batches``: per batch ``decoder(encoder(x))`` and ONE ``spdm_recon_terms`` into the batch's slots of
+        a float64 buffer sized for the pass; then one ``spdm_eval_reduce`` and ONE read-back.  Returns ``(val_loss, terms (N)
+        on the device, the first `keep` frames, their reconstructions)``."""
+        from .evaluation import reduce_errors
+        from .train_metrics import recon_terms_into
+        ids = getattr(batches, "row_ids", None)
+        terms = torch.empty(max(len(ids) if ids is not None else 1024, 1), dtype=torch.float64, device=self.device)
+        count, kept_x, kept_r = 0, [], []
+        for batch in batches:
+            x = batch.detach().to(self.device, torch.float32).contiguous()
+            recon = self.decoder(self.encoder(x))
+            n = x.shape[0]
+            if count + n > terms.numel():       # a source of unknown length: the buffer grows on the device
+                terms = torch.cat([terms, torch.empty(max(terms.numel(), count + n - terms.numel()), dtype=torch.float64, device=self.device)])
+            recon_terms_into(recon, x, terms, count)
+            if count < keep:
+                kept_x.append(x[:keep - count]), kept_r.append(recon[:keep - count])
+            count += n
+        if count == 0:
+            raise ValueError("validation_loss: no batches")
+        terms = terms[:count]
+        val_loss = float(reduce_errors(terms.view(count, 1), 1)[2].item())       # the one read-back
+        return val_loss, terms, (torch.cat(kept_x) if kept_x else None), (torch.cat(kept_r) if kept_r else None)
+
+    def validation_loss(self, batches, *, seed: int = 0, return_terms: bool = False):
+        """The reference's ``val_loss`` (``validation_step`` over a ``val_dataloader()``, averaged by Lightning over the epoch
+        with batch-size weights) formed on the device: every frame has 27648 elements, so it is the mean over the frames of
+        each frame's own mean squared error (``spdm_recon_terms``, then ``spdm_eval_reduce``).  A Python float after ONE
+        read-back; a deterministic function of the weights and the frames, whatever the batch size.  ``seed`` is ``train.fit``'s
+        keyword and unused: nothing is drawn.  ``return_terms=True``: ``(val_loss, terms (N) float64 on the device)``."""
+        val_loss, terms, _, _ = self._recon_pass(batches)
+        return (val_loss, terms) if return_terms else val_loss
+
+    def reconstruction_report(self, batches, *, sheet_frames: int = 8, cols: int = 8) -> dict:
+        """What the reference's eval_autoencoder.py shows of a trained autoencoder, as numbers and one picture:
+        ``{'val_loss', 'psnr_mean', 'psnr_min', 'worst', 'terms', 'sheet'}``.  ``terms`` (N) float64 on the host, the per-frame
+        mean squared errors of ``validation_loss``; PSNR is ``10 log10(1 / mse)`` per frame in float64 on the host (``inf``
+        for an exact reconstruction); ``worst``: the frames in descending order of error (the ``sheet_frames`` worst at most),
+        as store rows when ``batches`` carries ``row_ids``, else as positions in the pass.  ``sheet``: a uint8 device tensor
+        ``(2 ceil(k / cols) 96, cols 96, 3)`` from two ``spdm_frames_to_bytes`` launches, the first ``k = min(sheet_frames, N)``
+        originals in the upper tiles and their reconstructions beneath (eval_autoencoder.py:91-106)."""
+        from .dataset import frames_to_u8
+        if sheet_frames < 1 or cols < 1:
+            raise ValueError(f"sheet_frames = {sheet_frames} and cols = {cols} must be >= 1")
+        val_loss, terms, x, recon = self._recon_pass(batches, keep=int(sheet_frames))
+        k = x.shape[0]
+        half = -(-k // cols) * cols                                  # tiles in the upper half: whole sheet rows
+        sheet = torch.zeros((2 * half // cols * 96, cols * 96, 3), dtype=torch.uint8, device=self.device)
+        frames_to_u8(x.contiguous(), sheet, cols=cols, tile_offset=0)
+        frames_to_u8(recon.contiguous(), sheet, cols=cols, tile_offset=half)
+        mse = terms.cpu().numpy()
+        with np.errstate(divide="ignore"):
+            psnr = 10.0 * np.log10(1.0 / mse)
+        order = np.argsort(-mse, kind="stable")[:int(sheet_frames)]
+        ids = getattr(batches, "row_ids", None)
+        worst = [int(ids[i]) if ids is not None else int(i) for i in order]
+        return {"val_loss": val_loss, "psnr_mean": float(psnr.mean()), "psnr_min": float(psnr.min()), "worst": worst,
+                "terms": mse, "sheet": sheet}
+
+    # ==================== Checkpoints (Lightning's layout; train_autoencoder.py's ModelCheckpoint) ====================
+    def hparams(self) -> dict:
+        """The constructor argument ``save_hyperparameters()`` records (models/encoder/autoencoder.py:44)."""
+        return {"learning_rate": float(self.lr)}
+
+    def save_hparams(self, path) -> None:
+        import yaml
+        with open(path, "w") as fh:
+            fh.write(yaml.safe_dump(self.hparams(), sort_keys=False))
+
+    def save_checkpoint(self, path, *, optimizer=None, scheduler=None, trainer_state: Optional[dict] = None) -> None:
+        """Write ``path`` with ``torch.save`` in the layout of a Lightning checkpoint: ``state_dict`` (``self.state_dict()`` at
+        the CURRENT values of both flat parameters), ``hyper_parameters``, ``epoch``, ``global_step``, ``optimizer_states``,
+        ``lr_schedulers`` and the loop's counters under ``'spdm_trainer'``.  Host tensors only: the file holds nothing
+        ``torch.load(weights_only=True)`` refuses, and ``load_from_checkpoint``, ``Diffusion_DDPM(vision_encoder_state_dict=
+        safe_load_state_dict(path))`` and ``train --encoder_checkpoint path`` take it as it is."""
+        def host(v):
+            if isinstance(v, torch.Tensor):
+                return v.detach().cpu()
+            if isinstance(v, dict):
+                return {k: host(x) for k, x in v.items()}
+            if isinstance(v, (list, tuple)):
+                return [host(x) for x in v]
+            if isinstance(v, np.generic):
+                return v.item()
+            return v
+
+        ts = host(dict(trainer_state or {}))
+        torch.save({"epoch": int(ts.get("epoch", 0)), "global_step": int(ts.get("global_step", 0)),
+                    "pytorch-lightning_version": "2.0.0", "state_dict": self.state_dict(), "hyper_parameters": self.hparams(),
+                    "optimizer_states": [host(optimizer.state_dict())] if optimizer is not None else [],
+                    "lr_schedulers": [host(scheduler.state_dict())] if scheduler is not None else [],
+                    "spdm_trainer": ts}, str(path))
+
+    def restore_checkpoint(self, ckpt: dict) -> None:
+        """Take both halves' tensors of a loaded checkpoint dict (``train.fit(ckpt_path=)``) into the existing handles and
+        flat parameters in place: a configured optimiser keeps pointing at them."""
+        sd = ckpt["state_dict"]
+        enc_sd, dec_sd = encoder_state_dict_from(sd, "encoder."), decoder_state_dict_from(sd)
+        if enc_sd is None or dec_sd is None:
+            raise ValueError("the checkpoint's state_dict holds no autoencoder (encoder.N.* and decoder.N.*)")
+        self.encoder.load_state_dict(enc_sd)
+        self.decoder.load_state_dict(dec_sd)
 
     # ==================== Optimisation (:73-83, train_autoencoder.py) ====================
     def _params(self):

@@ -10,6 +10,9 @@
 //
 // Frame staging: frame_tiles.h, shared with policy.hip.
 //
+// The way back, fp32 planes to uint8 pixels laid out as tiles of a contact sheet, is spdm_frames_to_bytes,
+// described at its kernel below.
+//
 // Safety: no row number comes from the caller.  A window id is clamped into [0, n_windows - 1] and a start read from the
 // table is clamped into [0, T - 1 - (seq_len - 1) step_size] before either is used, so every store row lies in [0, T).
 // No atomics: outputs are indexed by batch slot and the clamp count is one workgroup's fixed-order integer sum.
@@ -104,7 +107,63 @@ __global__ __launch_bounds__(THREADS) void dataset_gather_kernel(const DatasetGa
     }
 }
 
+// spdm_frames_to_bytes: the inverse of the gather's frame path.  Planar CHW fp32 frames become interleaved
+// HWC uint8 pixels, each frame one 96 x 96 tile of a contact sheet.
+//
+// Replaces: the recon.permute(1, 2, 0).cpu().numpy() and imshow's own float -> 8-bit conversion of the reference's
+// models/encoder/eval_autoencoder.py:91-106, frame by frame on the host.
+//
+// ONE launch, a third of a frame (32 pixel rows, 3072 pixels) per workgroup.  Thread q of a pass owns pixels 4q .. 4q+3: one
+// 16-byte load from each of the three planes (lanes contiguous within a plane), twelve bytes out as three dwords written to
+// LDS at dwords 3q .. 3q+2 (ds_write_b32, lane stride 3 dwords: odd, the 32 lanes of a group fall on 32 different banks).
+// The slice is then 9216 contiguous bytes in pixel order = 32 pixel rows of 288 B = 18 16-byte pieces each; piece p is read
+// back with ds_read_b128 at consecutive addresses and stored with one 16-byte store at row p / 18, piece p % 18 of the tile,
+// whose rows lie cols x 288 B apart in the sheet.  Every tile row starts 16-byte aligned because 288 = 18 x 16.
+__device__ __forceinline__ unsigned quantise(float x) {
+    const float v = x * 255.0f;                                        // ONE fp32 multiply
+    const float q = rintf(v);                                          // ties to even
+    return v != v ? 0u : (unsigned)(int)fminf(fmaxf(q, 0.0f), 255.0f);
+}
+
+__global__ __launch_bounds__(THREADS) void frames_to_u8_kernel(const FramesToU8Args a) {
+    constexpr int SLICE_PIX = frame_tiles::SLICE_PIX, SLICE_QUADS = frame_tiles::SLICE_QUADS;
+    constexpr int PIECES = SLICE_PIX * 3 / 16, ROW_PIECES = 96 * 3 / 16;   // 576 pieces, 18 per pixel row
+    __shared__ uint4 lds[PIECES];                                      // 9 KiB
+    const int f = blockIdx.x / SLICES, slice = blockIdx.x - f * SLICES;    // f < n
+    const float* planes = a.frames + (size_t)f * 3 * FRAME_PIX + (size_t)slice * SLICE_PIX;
+    unsigned* words = reinterpret_cast<unsigned*>(lds);
+#pragma unroll
+    for (int k = 0; k < SLICE_QUADS / THREADS; ++k) {
+        const int q = k * THREADS + threadIdx.x;                       // < 768
+        float4 c[3];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) c[ch] = *reinterpret_cast<const float4*>(planes + (size_t)ch * FRAME_PIX + 4 * q);
+        const unsigned r0 = quantise(c[0].x), g0 = quantise(c[1].x), b0 = quantise(c[2].x);
+        const unsigned r1 = quantise(c[0].y), g1 = quantise(c[1].y), b1 = quantise(c[2].y);
+        const unsigned r2 = quantise(c[0].z), g2 = quantise(c[1].z), b2 = quantise(c[2].z);
+        const unsigned r3 = quantise(c[0].w), g3 = quantise(c[1].w), b3 = quantise(c[2].w);
+        words[3 * q + 0] = r0 | (g0 << 8) | (b0 << 16) | (r1 << 24);   // little endian: byte 0 is the first pixel's red
+        words[3 * q + 1] = g1 | (b1 << 8) | (r2 << 16) | (g2 << 24);
+        words[3 * q + 2] = b2 | (r3 << 8) | (g3 << 16) | (b3 << 24);
+    }
+    __syncthreads();
+    const long long tile = a.tile_offset + f;                          // < n_tiles
+    const long long trow = tile / a.cols, tcol = tile - trow * a.cols;
+    const size_t pitch = (size_t)a.cols * 96 * 3;                      // bytes per sheet row
+    unsigned char* dst = a.out + ((size_t)trow * 96 + (size_t)slice * (SLICE_PIX / 96)) * pitch + (size_t)tcol * 96 * 3;
+    for (int p = threadIdx.x; p < PIECES; p += THREADS) {
+        const int row = p / ROW_PIECES, piece = p - row * ROW_PIECES;  // row < 32, piece < 18
+        *reinterpret_cast<uint4*>(dst + (size_t)row * pitch + (size_t)piece * 16) = lds[p];
+    }
+}
+
 }  // namespace
+
+hipError_t launch_frames_to_u8(const FramesToU8Args& a, hipStream_t s) {
+    if (a.n < 1 || a.cols < 1 || a.tile_offset < 0 || (long long)a.n * SLICES > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(frames_to_u8_kernel, dim3((unsigned)(a.n * SLICES)), dim3(THREADS), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_dataset_gather(DatasetGatherArgs a, hipStream_t s) {
     if (a.B < 1 || a.seq_len < 1 || a.step_size < 1 || a.n_windows < 1 || a.n_frames < 0 || a.max_start < 0) return hipErrorInvalidValue;

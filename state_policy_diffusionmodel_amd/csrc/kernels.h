@@ -503,6 +503,16 @@ struct DatasetGatherArgs {
 // one launch of B n_frames x 3 + ceil(B seq_len / 256) workgroups
 hipError_t launch_dataset_gather(DatasetGatherArgs a, hipStream_t s);
 
+// ---- planar fp32 frames to interleaved uint8 tiles of a contact sheet (dataset.hip; spdm_frames_to_bytes) ----
+struct FramesToU8Args {
+    int n, cols;                       // frames; tiles per sheet row
+    long long tile_offset;             // frame i is tile tile_offset + i, inside [0, n_tiles): checked by the host
+    const float* frames;               // (n, 3, 96, 96), 16-byte aligned
+    unsigned char* out;                // (ceil(n_tiles / cols) 96, cols 96, 3), 16-byte aligned
+};
+// one launch of n x 3 workgroups (a third of a frame each)
+hipError_t launch_frames_to_u8(const FramesToU8Args& a, hipStream_t s);
+
 // ---- position / action error of sampled trajectories and its statistics (evaluation.hip; spdm_eval_*) -----
 struct EvalErrorsArgs {
     int B, H, D, seq, obs_h, inp_h, P, runs;
@@ -664,6 +674,19 @@ struct LossTermsArgs {
 };
 // one launch of ceil(B / LOSS_WAVES) workgroups
 hipError_t launch_loss_terms(const LossTermsArgs& a, hipStream_t s);
+
+// ---- per-frame reconstruction error of a validation batch (train_metrics.hip; spdm_recon_terms) -----------
+constexpr int RECON_FRAME = 3 * 96 * 96;           // 27648 elements = 6912 quads of four consecutive floats
+constexpr int RECON_THREADS = 256;                 // one workgroup per frame: 27 quads per thread
+struct ReconTermsArgs {
+    int n;                             // frames
+    long long slot_offset;             // frame b writes slot slot_offset + b, inside [0, n_slots): checked by the host
+    const float* recon;                // (n, 3, 96, 96), 16-byte aligned
+    const float* target;               // (n, 3, 96, 96), 16-byte aligned
+    double* terms;                     // (n_slots)
+};
+// one launch of n workgroups
+hipError_t launch_recon_terms(const ReconTermsArgs& a, hipStream_t s);
 
 hipError_t launch_advance(int* step_dev, int* t_dev, const int* timesteps_dev, int n_steps, hipStream_t s);
 hipError_t launch_set_step(int* step_dev, int* t_dev, const int* timesteps_dev, int n_steps, int i, hipStream_t s);

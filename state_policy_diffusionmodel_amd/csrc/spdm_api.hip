@@ -3374,6 +3374,46 @@ extern "C" int spdm_loss_terms(int32_t device, const spdm_loss_terms_args* a, vo
     return SPDM_OK;
 }
 
+// The per-frame reconstruction error of a validation batch in one launch (include/spdm.h, train_metrics.hip).  Stateless.
+extern "C" int spdm_recon_terms(int32_t device, const spdm_recon_terms_args* a, void* stream) {
+    if (!a) return fail(SPDM_ERR_INVALID, "recon_terms: null argument");
+    if (a->n < 1) return fail(SPDM_ERR_INVALID, "recon_terms: n = %d must be >= 1", a->n);
+    if (!a->d_recon || !a->d_target || !a->d_terms) return fail(SPDM_ERR_INVALID, "recon_terms: null pointer");
+    if (((uintptr_t)a->d_recon | (uintptr_t)a->d_target) & 15)
+        return fail(SPDM_ERR_INVALID, "recon_terms: d_recon and d_target must be 16-byte aligned");
+    if (a->slot_offset < 0) return fail(SPDM_ERR_INVALID, "recon_terms: slot_offset = %lld is negative", (long long)a->slot_offset);
+    if (a->n_slots < a->n || a->slot_offset > a->n_slots - a->n)
+        return fail(SPDM_ERR_INVALID, "recon_terms: slots [%lld, %lld + %d) lie outside [0, n_slots = %lld)", (long long)a->slot_offset,
+                    (long long)a->slot_offset, a->n, (long long)a->n_slots);
+    ReconTermsArgs k = {};
+    k.n = a->n; k.slot_offset = a->slot_offset; k.recon = a->d_recon; k.target = a->d_target; k.terms = a->d_terms;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(launch_recon_terms(k, (hipStream_t)stream));
+    if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));
+    return SPDM_OK;
+}
+
+// Planar fp32 frames to uint8 tiles of a contact sheet in one launch (include/spdm.h, dataset.hip).  Stateless.
+extern "C" int spdm_frames_to_bytes(int32_t device, const spdm_frames_to_bytes_args* a, void* stream) {
+    if (!a) return fail(SPDM_ERR_INVALID, "frames_to_u8: null argument");
+    if (a->n < 1 || a->cols < 1 || a->n_tiles < 1)
+        return fail(SPDM_ERR_INVALID, "frames_to_u8: n, cols, n_tiles = %d, %d, %lld must all be >= 1", a->n, a->cols, (long long)a->n_tiles);
+    if ((long long)a->n * 3 > 0x7fffffffLL) return fail(SPDM_ERR_INVALID, "frames_to_u8: n = %d frames do not fit one launch", a->n);
+    if (!a->d_frames || !a->d_out) return fail(SPDM_ERR_INVALID, "frames_to_u8: null pointer");
+    if (((uintptr_t)a->d_frames | (uintptr_t)a->d_out) & 15)
+        return fail(SPDM_ERR_INVALID, "frames_to_u8: d_frames and d_out must be 16-byte aligned");
+    if (a->tile_offset < 0) return fail(SPDM_ERR_INVALID, "frames_to_u8: tile_offset = %lld is negative", (long long)a->tile_offset);
+    if (a->n_tiles < a->n || a->tile_offset > a->n_tiles - a->n)
+        return fail(SPDM_ERR_INVALID, "frames_to_u8: tiles [%lld, %lld + %d) lie outside [0, n_tiles = %lld)", (long long)a->tile_offset,
+                    (long long)a->tile_offset, a->n, (long long)a->n_tiles);
+    FramesToU8Args k = {};
+    k.n = a->n; k.cols = a->cols; k.tile_offset = a->tile_offset; k.frames = a->d_frames; k.out = a->d_out;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(launch_frames_to_u8(k, (hipStream_t)stream));
+    if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));
+    return SPDM_OK;
+}
+
 extern "C" int spdm_train_set_time_scale(spdm_handle* h, const float* d_scale, int32_t B) {
     if (!h) return fail(SPDM_ERR_INVALID, "null handle");
     if (!h->train_simple) return fail(SPDM_ERR_STATE, "spdm_train_set_time_scale needs a handle created with SPDM_FLAG_TRAIN_SIMPLE");

@@ -102,6 +102,98 @@ def _ptr(t: Optional[torch.Tensor]):
     return t.data_ptr() if t is not None else None
 
 
+def _device_ids(ids, n: int, device: torch.device) -> torch.Tensor:
+    """``ids`` as a flat int32 device tensor.  Host ids (list, numpy, CPU tensor) outside ``[0, n)`` raise IndexError; a
+    device tensor is passed through (the kernel clamps it)."""
+    if isinstance(ids, torch.Tensor) and ids.is_cuda:
+        if ids.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
+            raise TypeError(f"ids must be an integer tensor, got {ids.dtype}")
+        return ids.to(device=device, dtype=torch.int32).reshape(-1).contiguous()        # the kernel clamps these
+    h = np.asarray(ids.numpy() if isinstance(ids, torch.Tensor) else ids)
+    if h.size and not np.issubdtype(h.dtype, np.integer):
+        raise TypeError(f"ids must be integers, got {h.dtype}")
+    h = h.reshape(-1).astype(np.int64)
+    if h.size and (h.min() < 0 or h.max() >= n):
+        raise IndexError(f"id {int(h[(h < 0) | (h >= n)][0])} outside [0, {n})")
+    return torch.from_numpy(h.astype(np.int32)).to(device)
+
+
+class FrameStore:
+    """The image half of ``DeviceDataset``: ``img`` (T,96,96,3) with values ``pixel / 255.0`` (or uint8 pixels) kept in HBM,
+    as uint8 where that is exact (``choose_image_storage``), uploaded ``_CHUNK_ROWS`` frames at a time.  ``frames(row_ids)``
+    is ONE ``spdm_dataset_gather`` launch with one-row windows and no low-dimensional store."""
+
+    def __init__(self, img, device: int = 0, image_storage: str = "auto"):
+        img = np.asarray(img)
+        if img.ndim != 4 or img.shape[1:] != FRAME_SHAPE or len(img) < 1:
+            raise ValueError(f"expected img (T,96,96,3) with T >= 1, got {img.shape}")
+        T = len(img)
+        self.image_storage = choose_image_storage(img, image_storage)
+        self.device = torch.device("cuda", device)
+        self._T = T
+        u8 = self.image_storage == "uint8"
+        self._img = torch.empty((T,) + FRAME_SHAPE, dtype=torch.uint8 if u8 else torch.float32, device=self.device)
+        for i in range(0, T, _CHUNK_ROWS):                                             # piecewise: the host never holds a second copy
+            piece = img[i:i + _CHUNK_ROWS]
+            if u8 and piece.dtype != np.uint8:
+                piece = np.rint(piece * 255).astype(np.uint8)
+            self._img[i:i + len(piece)] = torch.from_numpy(np.ascontiguousarray(piece, dtype=np.uint8 if u8 else np.float32)).to(self.device)
+        self._bad = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def __len__(self) -> int:
+        return self._T
+
+    def frames(self, row_ids) -> torch.Tensor:
+        """``(n, 3, 96, 96)`` float32 frames of arbitrary store rows -- what ``autoencoder.training_step`` takes, enqueued on
+        torch's current stream.  Host ids outside ``[0, len(self))`` raise IndexError; a device tensor is passed through and
+        clamped by the kernel (``last_bad()``)."""
+        ids = _device_ids(row_ids, self._T, self.device)
+        if ids.numel() < 1:
+            raise ValueError("an empty batch")
+        out = torch.empty((ids.numel(), 3, 96, 96), dtype=torch.float32, device=self.device)
+        a = _lib.SpdmDatasetGatherArgs(T=self._T, n_windows=self._T, B=ids.numel(), seq_len=1, step_size=1, n_frames=1,
+                                       img_dtype=0 if self.image_storage == "uint8" else 1, reserved=0, d_img=self._img.data_ptr(),
+                                       d_window_id=ids.data_ptr(), d_image_out=out.data_ptr(), d_bad=self._bad.data_ptr())
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(_lib.load().spdm_dataset_gather(self.device.index, ctypes.byref(a), stream), "spdm_dataset_gather")
+        return out
+
+    def last_bad(self) -> int:
+        """How many ids of the LAST ``frames`` call the kernel had to clamp into range.  Synchronises."""
+        return int(self._bad.item())
+
+
+def frames_to_u8(frames: torch.Tensor, out: Optional[torch.Tensor] = None, *, cols: int = 1, tile_offset: int = 0,
+                 n_tiles: Optional[int] = None) -> torch.Tensor:
+    """ONE ``spdm_frames_to_bytes`` launch on torch's current stream: the n planar fp32 ``frames`` (n,3,96,96)
+    become the uint8 tiles ``tile_offset .. tile_offset + n - 1`` of the contact sheet ``out``, a contiguous uint8 device
+    tensor ``(ceil(n_tiles / cols) * 96, cols * 96, 3)`` with ``cols`` tiles per row (made here, zero-filled, when None;
+    ``n_tiles`` then defaults to ``tile_offset + n``).  The byte is ``clamp(rint(x * 255), 0, 255)`` in fp32, 0 for NaN; other
+    tiles are not touched.  With ``cols=1`` the sheet viewed ``(n_tiles,96,96,3)`` is the image store's layout."""
+    if frames.dim() != 4 or tuple(frames.shape[1:]) != (3, 96, 96) or not frames.is_cuda or frames.dtype != torch.float32 \
+            or not frames.is_contiguous():
+        raise ValueError(f"frames must be a contiguous (n,3,96,96) fp32 device tensor, got {tuple(frames.shape)} {frames.dtype}")
+    n, cols, tile_offset = frames.shape[0], int(cols), int(tile_offset)
+    if cols < 1:
+        raise ValueError(f"cols = {cols} must be >= 1")
+    if out is None:
+        n_tiles = tile_offset + n if n_tiles is None else int(n_tiles)
+        out = torch.zeros((-(-max(n_tiles, 1) // cols) * 96, cols * 96, 3), dtype=torch.uint8, device=frames.device)
+    else:
+        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.dim() != 3 \
+                or out.shape[1:] != (cols * 96, 3) or out.shape[0] % 96:
+            raise ValueError(f"out must be a contiguous uint8 device tensor (rows * 96, cols * 96, 3), got {tuple(out.shape)}")
+        held = out.shape[0] // 96 * cols
+        n_tiles = held if n_tiles is None else int(n_tiles)
+        if n_tiles > held:
+            raise ValueError(f"n_tiles = {n_tiles}, out holds {held} tiles")
+    a = _lib.SpdmFramesToBytesArgs(n=n, cols=cols, tile_offset=tile_offset, n_tiles=n_tiles, d_frames=frames.data_ptr(),
+                                d_out=out.data_ptr())
+    stream = ctypes.c_void_p(torch.cuda.current_stream(frames.device).cuda_stream)
+    _lib.check(_lib.load().spdm_frames_to_bytes(frames.device.index, ctypes.byref(a), stream), "spdm_frames_to_bytes")
+    return out
+
+
 class DeviceDataset:
     """``CarRacingDataset`` (``stats=None``: the statistics are computed) or ``CarRacingDatasetForInference`` (``stats``
     given and used as they are) with every array on the device.
@@ -125,8 +217,8 @@ class DeviceDataset:
         if len(self.indices) == 0:
             raise ValueError("no episode holds a window of sequence_length * step_size rows")
         self.stats = stats if stats else compute_stats(position, velocity, action, self.indices, self.step_size)
-        self.image_storage = choose_image_storage(img, image_storage)
-        self.device = torch.device("cuda", device)
+        self._store = FrameStore(img, device, image_storage)                           # the image half: storage choice, upload
+        self.image_storage, self.device, self._img, self._bad = self._store.image_storage, self._store.device, self._store._img, self._store._bad
         self._T = T
         self._pos_min, self._pos_max = float(self.stats["position"]["min"]), float(self.stats["position"]["max"])
         dev = self.device
@@ -135,33 +227,12 @@ class DeviceDataset:
         self._action = torch.from_numpy(np.ascontiguousarray(normalize_data(action, self.stats["action"]), dtype=np.float32)).to(dev)
         self._h_start = np.ascontiguousarray(self.indices[:, 0], dtype=np.int32)      # the library checks this copy on the host
         self._d_start = torch.from_numpy(self._h_start).to(dev)
-        u8 = self.image_storage == "uint8"
-        self._img = torch.empty((T,) + FRAME_SHAPE, dtype=torch.uint8 if u8 else torch.float32, device=dev)
-        for i in range(0, T, _CHUNK_ROWS):                                             # piecewise: the host never holds a second copy
-            piece = img[i:i + _CHUNK_ROWS]
-            if u8 and piece.dtype != np.uint8:
-                piece = np.rint(piece * 255).astype(np.uint8)
-            self._img[i:i + len(piece)] = torch.from_numpy(np.ascontiguousarray(piece, dtype=np.uint8 if u8 else np.float32)).to(dev)
-        self._bad = torch.zeros(1, dtype=torch.int32, device=dev)
 
     def __len__(self) -> int:
         return len(self.indices)
 
     # ---- the one launch -------------------------------------------------------------------------------------------------------
-    def _ids(self, ids, n: int) -> torch.Tensor:
-        if isinstance(ids, torch.Tensor) and ids.is_cuda:
-            if ids.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
-                raise TypeError(f"ids must be an integer tensor, got {ids.dtype}")
-            return ids.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()        # the kernel clamps these
-        h = np.asarray(ids.numpy() if isinstance(ids, torch.Tensor) else ids)
-        if h.size and not np.issubdtype(h.dtype, np.integer):
-            raise TypeError(f"ids must be integers, got {h.dtype}")
-        h = h.reshape(-1).astype(np.int64)
-        if h.size and (h.min() < 0 or h.max() >= n):
-            raise IndexError(f"id {int(h[(h < 0) | (h >= n)][0])} outside [0, {n})")
-        return torch.from_numpy(h.astype(np.int32)).to(self.device)
-
-    def _gather(self, ids: torch.Tensor, *, table: bool, seq: int, step: int, n_frames: int, low: bool, translation: bool):
+    def _gather(self, ids: torch.Tensor, *, seq: int, step: int, n_frames: int, low: bool, translation: bool):
         B = ids.numel()
         if B < 1:
             raise ValueError("an empty batch")
@@ -176,10 +247,10 @@ class DeviceDataset:
             out["translation"] = torch.empty((B, 2), dtype=torch.float64, device=dev)
             out["start"] = torch.empty(B, dtype=torch.int32, device=dev)
         a = _lib.SpdmDatasetGatherArgs(
-            T=self._T, n_windows=len(self.indices) if table else self._T, B=B, seq_len=seq, step_size=step, n_frames=n_frames,
+            T=self._T, n_windows=len(self.indices), B=B, seq_len=seq, step_size=step, n_frames=n_frames,
             img_dtype=0 if self.image_storage == "uint8" else 1, reserved=0,
             d_img=_ptr(self._img), d_position=_ptr(self._position), d_velocity=_ptr(self._velocity), d_action=_ptr(self._action),
-            d_window_start=_ptr(self._d_start) if table else None, h_window_start=self._h_start.ctypes.data if table else None,
+            d_window_start=_ptr(self._d_start), h_window_start=self._h_start.ctypes.data,
             d_window_id=_ptr(ids), pos_min=self._pos_min, pos_max=self._pos_max,
             d_image_out=_ptr(out.get("image")), d_position_out=_ptr(out.get("position")), d_velocity_out=_ptr(out.get("velocity")),
             d_action_out=_ptr(out.get("action")), d_translation_out=_ptr(out.get("translation")), d_start_out=_ptr(out.get("start")),
@@ -198,7 +269,7 @@ class DeviceDataset:
         if frames not in ("obs", "all", None):
             raise ValueError(f"frames must be 'obs', 'all' or None, got {frames!r}")
         n_frames = {"obs": self.obs_horizon, "all": self.sequence_len, None: 0}[frames]
-        out = self._gather(self._ids(window_ids, len(self)), table=True, seq=self.sequence_len, step=self.step_size,
+        out = self._gather(_device_ids(window_ids, len(self), self.device), seq=self.sequence_len, step=self.step_size,
                            n_frames=n_frames, low=True, translation=with_translation)
         if with_translation:
             out["end"] = out["start"] + self.sequence_len * self.step_size
@@ -206,9 +277,8 @@ class DeviceDataset:
 
     def frames(self, row_ids) -> torch.Tensor:
         """``(n, 3, 96, 96)`` float32 frames of arbitrary store rows -- what ``autoencoder.training_step`` takes.  The same
-        kernel with one-row windows, window i starting at row i."""
-        ids = self._ids(row_ids, self._T)
-        return self._gather(ids, table=False, seq=1, step=1, n_frames=1, low=False, translation=False)["image"].view(-1, 3, 96, 96)
+        kernel with one-row windows, window i starting at row i (``FrameStore.frames``)."""
+        return self._store.frames(row_ids)
 
     def last_bad(self) -> int:
         """How many ids of the LAST ``batch`` / ``frames`` call the kernel had to clamp into range.  Synchronises."""
@@ -268,8 +338,7 @@ class CarRacingDataModule:
         """The train split in a fresh random order per epoch: a ``torch.randperm`` from a generator seeded by
         ``(seed, epoch)``.  This order is this project's own: the reference's comes from the global RNG of its DataLoader
         and is not reproducible from ``seed`` either."""
-        g = torch.Generator().manual_seed((int(self.seed or 0) * 0x9E3779B1 + int(epoch)) & (2 ** 63 - 1))
-        order = torch.randperm(len(self.train_ids), generator=g).numpy()
+        order = _epoch_order(len(self.train_ids), self.seed, epoch)
         return _Batches(self.data_full, self.train_ids[order], self.batch_size)
 
     def val_dataloader(self) -> _Batches:
@@ -280,5 +349,61 @@ class CarRacingDataModule:
             pickle.dump([self.stats], f)
 
 
-__all__ = ["create_sample_indices_sparse", "compute_stats", "normalize_data", "unnormalize_data", "unnormalize_position", "split_indices",
+def _epoch_order(n: int, seed, epoch: int) -> np.ndarray:
+    """A fresh order of ``n`` items for ``(seed, epoch)``: the loaders' one generator recipe."""
+    g = torch.Generator().manual_seed((int(seed or 0) * 0x9E3779B1 + int(epoch)) & (2 ** 63 - 1))
+    return torch.randperm(n, generator=g).numpy()
+
+
+class _FrameBatches:
+    """A sized re-iterable over the ``(B,3,96,96)`` float32 device batches of one row order of a frame store."""
+
+    def __init__(self, store, ids: np.ndarray, batch_size: int):
+        self.store, self.row_ids, self.batch_size = store, np.asarray(ids, dtype=np.int64), int(batch_size)
+        self._d_ids = None
+
+    def __len__(self) -> int:
+        return -(-len(self.row_ids) // self.batch_size)              # the last short batch is kept
+
+    def __iter__(self):
+        if self._d_ids is None:                                      # one upload per order
+            self._d_ids = torch.from_numpy(self.row_ids.astype(np.int32)).to(self.store.device)
+        for i in range(0, len(self.row_ids), self.batch_size):
+            yield self.store.frames(self._d_ids[i:i + self.batch_size])
+
+
+class FramesDataModule:
+    """The reference's ``ImagesDataset`` + ``DataModule`` of models/encoder/train_autoencoder.py:24-61 over a ``FrameStore``:
+    every frame of the store is a sample, an 80 / 20 ``random_split``, loaders that yield ``(B,3,96,96)`` float32 device
+    batches.  There are no statistics: the autoencoder's run writes no STATS.pkl, as in the reference."""
+
+    def __init__(self, batch_size: int, data_dir: Optional[str] = None, seed=None, device: int = 0, image_storage: str = "auto"):
+        self.batch_size, self.data_dir, self.seed, self.device, self.image_storage = int(batch_size), data_dir, seed, device, image_storage
+        self.data_full = None
+
+    def setup(self, name: Optional[str] = None, arrays: Optional[dict] = None, store=None) -> None:
+        """``arrays``: ``{'img': (T,96,96,3)}`` (other keys are ignored, so the arrays of ``CarRacingDataModule`` serve).
+        ``name`` instead opens ``data_dir/name`` with zarr, imported only then and NOT covered by the tests.  ``store``: a
+        ready ``FrameStore`` (or anything with ``frames(ids)``, ``device`` and ``__len__``)."""
+        if (name is None) + (arrays is None) + (store is None) != 2:
+            raise ValueError("pass exactly one of name (a zarr store under data_dir), arrays and store")
+        if name is not None:
+            try:
+                import zarr
+            except ImportError as e:
+                raise ImportError("FramesDataModule.setup(name=...) reads a zarr store and needs the zarr package; "
+                                  "pass arrays=... to use numpy arrays") from e
+            arrays = {"img": zarr.open(os.path.join(self.data_dir or "", name), "r")["data"]["img"][:]}
+        self.data_full = store if store is not None else FrameStore(arrays["img"], self.device, self.image_storage)
+        self.train_ids, self.val_ids = split_indices(len(self.data_full), self.seed)
+
+    def train_dataloader(self, epoch: int = 0) -> _FrameBatches:
+        """The train split in a fresh ``(seed, epoch)`` order, ``CarRacingDataModule.train_dataloader``'s recipe."""
+        return _FrameBatches(self.data_full, self.train_ids[_epoch_order(len(self.train_ids), self.seed, epoch)], self.batch_size)
+
+    def val_dataloader(self) -> _FrameBatches:
+        return _FrameBatches(self.data_full, self.val_ids, self.batch_size)      # shuffle=False: the split's order
+
+
+__all__ = ["FrameStore", "FramesDataModule", "frames_to_u8", "create_sample_indices_sparse", "compute_stats", "normalize_data", "unnormalize_data", "unnormalize_position", "split_indices",
            "choose_image_storage", "DeviceDataset", "CarRacingDataModule"]

@@ -85,7 +85,8 @@ def fit(model, datamodule, *, max_epochs: int, out_dir, val_check_interval=0.25,
     seed=, noise_step=[, time_dropout=0.1 for model='UNet'])`` returning a loss scalar tensor, ``optimizer_step(optimizer,
     gradient_clip_val)``, ``validation_loss(batches, seed=)`` returning a float, ``save_checkpoint``, ``save_hparams``,
     ``restore_checkpoint(ckpt)`` (resume only), and the attributes ``model_name`` and ``device``.  Of ``datamodule``:
-    ``train_dataloader(epoch)`` (sized, iterable), ``val_dataloader()``, ``save_stats(path)``.
+    ``train_dataloader(epoch)`` (sized, iterable), ``val_dataloader()`` and, when it has one, ``save_stats(path)`` (no
+    ``STATS.pkl`` otherwise).
 
     A step is ``training_step`` then ``optimizer_step``; training step ``g`` (counted over the whole run) draws its noise from
     ``(seed, g)``, epoch ``e`` its order from the data module's ``(seed, e)``.  Validation runs after the train batches
@@ -161,7 +162,8 @@ def fit(model, datamodule, *, max_epochs: int, out_dir, val_check_interval=0.25,
             if validate_first:
                 validate()
                 emit("val", -1, None)
-            datamodule.save_stats(os.path.join(out_dir, "STATS.pkl"))
+            if hasattr(datamodule, "save_stats"):       # (the frame autoencoder's data has no statistics, as in the reference)
+                datamodule.save_stats(os.path.join(out_dir, "STATS.pkl"))
             model.save_hparams(os.path.join(out_dir, "hparams.yaml"))
 
         ring = None

@@ -1,6 +1,8 @@
 """The loss of a validation pass on the device: ``loss_terms_into`` is one ``spdm_loss_terms`` launch
 (csrc/train_metrics.hip) that turns a batch's predicted and drawn noise into per-sample mean squared errors at the batch's
 slots of a pass-wide float64 buffer; ``evaluation.reduce_errors`` over that buffer gives the pass's mean.
+``recon_terms_into`` is the same for the frame autoencoder (``spdm_recon_terms``): a batch's frames and their
+reconstructions into per-frame mean squared errors.
 
 There is no CPU fallback."""
 from __future__ import annotations
@@ -35,4 +37,22 @@ def loss_terms_into(eps: torch.Tensor, noise: torch.Tensor, terms: torch.Tensor,
     _lib.check(_lib.load().spdm_loss_terms(eps.device.index, ctypes.byref(a), stream), "spdm_loss_terms")
 
 
-__all__ = ["loss_terms_into"]
+def recon_terms_into(recon: torch.Tensor, target: torch.Tensor, terms: torch.Tensor, slot_offset: int = 0) -> None:
+    """``terms[slot_offset + b] = mean(((double)target[b] - (double)recon[b]) ** 2)`` for the n frames of ``recon`` /
+    ``target`` ((n,3,96,96) contiguous fp32 device tensors), ONE ``spdm_recon_terms`` launch on torch's current stream
+    (DESIGN.md 8.23); ``terms`` is a contiguous float64 device vector.  Slots outside ``[slot_offset, slot_offset + n)``
+    are not touched."""
+    if recon.shape != target.shape or recon.dim() != 4 or tuple(recon.shape[1:]) != (3, 96, 96):
+        raise ValueError(f"recon and target must both be (n,3,96,96), got {tuple(recon.shape)} and {tuple(target.shape)}")
+    for name, v, dt in (("recon", recon, torch.float32), ("target", target, torch.float32), ("terms", terms, torch.float64)):
+        if not v.is_cuda or v.dtype != dt or not v.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} device tensor")
+    if terms.dim() != 1:
+        raise ValueError("terms must be a vector")
+    a = _lib.SpdmReconTermsArgs(n=recon.shape[0], reserved=0, d_recon=recon.data_ptr(), d_target=target.data_ptr(),
+                                slot_offset=int(slot_offset), n_slots=terms.numel(), d_terms=terms.data_ptr())
+    stream = ctypes.c_void_p(torch.cuda.current_stream(recon.device).cuda_stream)
+    _lib.check(_lib.load().spdm_recon_terms(recon.device.index, ctypes.byref(a), stream), "spdm_recon_terms")
+
+
+__all__ = ["loss_terms_into", "recon_terms_into"]

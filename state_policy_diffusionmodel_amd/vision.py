@@ -63,12 +63,8 @@ class _FrameHandle:
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError(f"{type(self).__name__} needs a visible MI355X (HIP device); there is no CPU fallback")
-        sd = {k: state_dict[k] for k in self._keys}
-        for k, shp in self._shapes.items():
-            if tuple(sd[k].shape) != shp:
-                raise ValueError(f"{self._what} tensor {k}: shape {tuple(sd[k].shape)}, expected {shp}")
         self.device = torch.device("cuda", device)
-        blob, idx = pack_state_dict(sd)
+        blob, idx = self._pack(state_dict)
         self._index = [(e.name.decode(), int(e.offset), tuple(e.shape[d] for d in range(e.ndim))) for e in idx]
         self._blob = blob                      # host values at creation; the device copy below follows updates
         self._n_floats = int(blob.size)
@@ -79,6 +75,20 @@ class _FrameHandle:
         _lib.check(getattr(self.lib, f"spdm_{self._what}_create")(device, blob.ctypes.data_as(ctypes.c_void_p), blob.size, idx,
                                                                  len(idx), ctypes.byref(h)), f"spdm_{self._what}_create")
         self._h = h
+
+    @classmethod
+    def _pack(cls, state_dict):
+        """The ``_keys`` tensors of ``state_dict``, shapes checked, as ``pack_state_dict``'s (flat fp32 blob, index)."""
+        sd = {k: state_dict[k] for k in cls._keys}
+        for k, shp in cls._shapes.items():
+            if tuple(sd[k].shape) != shp:
+                raise ValueError(f"{cls._what} tensor {k}: shape {tuple(sd[k].shape)}, expected {shp}")
+        return pack_state_dict(sd)
+
+    def load_state_dict(self, state_dict) -> None:
+        """Put a state_dict's values into the handle IN PLACE (``update_weights``): the flat parameter, if it exists, keeps
+        its address, so an optimiser configured over it keeps pointing at the weights."""
+        self.update_weights(torch.from_numpy(self._pack(state_dict)[0]).to(self.device))
 
     def close(self):
         if getattr(self, "_h", None):
